@@ -6,7 +6,7 @@ examples/inference.ipynb, 4096-walker ensembles, fp64 -- with `--ensembles` inde
 stacked into ONE launch (default 4096 -> 16.8M walkers / launch), theta resident in HBM when the
 timed region starts.  A "step" is one pass of the hot path (one kernel launch) over that batch.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -36,6 +36,9 @@ metric's own wording, x {1, 16, 256, 4096}).
 The line is put together by `assemble_line` / `scan_record_from_phases` from plain numbers, and the cross-rank reductions go
 through `reduce_step_timing` / `reduce_phases` on the control plane: tests/test_bench_line.py drives them with two ranks'
 synthetic measurements over the socket control plane on a box without a GPU.
+
+`--dump-outputs DIR` writes rank 0's result of the last timed step (lnprob per walker, a fixed sample of it: `dump_outputs`)
+as .npy files; the inputs are seeded, so two builds of the project can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -79,7 +82,12 @@ def parse():
     ap.add_argument("--cpu-sample", type=int, default=0, help="evaluations in the CPU-baseline sample (0 = auto)")
     ap.add_argument("--scan-burnin", type=int, default=REF_BURNIN, help="burn-in steps of c4_scan_ref / c5_scan_ref")
     ap.add_argument("--scan-nsteps", type=int, default=REF_NSTEPS, help="stored steps of c4_scan_ref / c5_scan_ref")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0; see dump_outputs)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def notebook_descriptor():
@@ -534,6 +542,27 @@ def extra_emcee(model, ps, walkers):
     return out
 
 
+DUMP_SAMPLE = 1 << 21          # lnprob values kept by --dump-outputs (16 MiB, plus 16 MiB of indices)
+DUMP_SEED = 20260
+
+
+def dump_outputs(outdir, lnprob):
+    """--dump-outputs: the timed path's result (one lnprob per walker of the stacked batch, fp64) as .npy files, so that two builds
+    can be compared output for output.  Up to DUMP_SAMPLE values are written whole; above that a fixed sample (the same walkers
+    on every run, drawn with DUMP_SEED, sorted): `lnprob.npy` holds the values and `lnprob_index.npy` their flat walker indices
+    (as float64, exact below 2**53).  Returns the names written."""
+    lnprob = np.asarray(lnprob, dtype=np.float64).reshape(-1)
+    n = lnprob.size
+    if n <= DUMP_SAMPLE:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=DUMP_SAMPLE, replace=False))
+    os.makedirs(outdir, exist_ok=True)
+    np.save(os.path.join(outdir, "lnprob.npy"), np.ascontiguousarray(lnprob[idx]))
+    np.save(os.path.join(outdir, "lnprob_index.npy"), idx.astype(np.float64))
+    return ["lnprob", "lnprob_index"]
+
+
 def reduce_step_timing(control, elapsed, kernel_ms):
     """The job's step time is the MAX over ranks (contract); so is the kernel's average launch duration."""
     e, k = [float(x) for x in control.allreduce_max([elapsed, kernel_ms])]
@@ -709,6 +738,9 @@ def run(a, json_out):
     fence()                                            # closing bracket: barrier + synchronize (its latency is not a step)
     kernel_ms = ev0.elapsed_ms(ev1) / a.steps          # average launch duration on the kernel's stream
     elapsed, kernel_ms = reduce_step_timing(control, elapsed, kernel_ms)
+    if a.dump_outputs and rank == 0:
+        # every step recomputes the same batch into d_out: what it holds now is the last timed step's result
+        dump_outputs(a.dump_outputs, d_out.download((n,)))
 
     # after the timed region: one chain block (the first ensemble's lnprob) from every rank to rank 0 over RCCL
     gathered_ok, rccl_nranks = None, None

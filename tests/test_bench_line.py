@@ -556,3 +556,25 @@ def test_host_segment_registration_is_local_and_survives_having_no_gpu():
     assert seg.register() == (ok, 0.0)                      # asked once
     del a
     seg.close()
+
+
+def test_dump_outputs_writes_a_fixed_sample_within_the_size_cap(tmp_path, monkeypatch):
+    """--dump-outputs: the whole result when it is small, else the same seeded sample of walkers on every call, fp64, indices
+    beside the values, under 64 MB in all."""
+    import bench
+    small = np.linspace(-3.0, 0.0, 1000)
+    assert bench.dump_outputs(str(tmp_path / "small"), small) == ["lnprob", "lnprob_index"]
+    assert np.array_equal(np.load(tmp_path / "small" / "lnprob.npy"), small)
+    assert np.array_equal(np.load(tmp_path / "small" / "lnprob_index.npy"), np.arange(1000.0))
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 4096)
+    big = np.random.default_rng(1).normal(size=100000)
+    big[::7] = -np.inf
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    v, i = np.load(tmp_path / "a" / "lnprob.npy"), np.load(tmp_path / "a" / "lnprob_index.npy")
+    assert v.dtype == np.float64 and i.dtype == np.float64 and v.shape == i.shape == (4096,)
+    assert np.all(np.diff(i) > 0) and np.array_equal(v, big[i.astype(np.int64)])
+    assert np.array_equal(v, np.load(tmp_path / "b" / "lnprob.npy"))
+    assert np.array_equal(i, np.load(tmp_path / "b" / "lnprob_index.npy"))
+    monkeypatch.undo()
+    assert 2 * 8 * bench.DUMP_SAMPLE <= 64 * 1024 * 1024

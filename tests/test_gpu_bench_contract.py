@@ -38,6 +38,30 @@ def test_bench_line_contract():
 
 
 @pytest.mark.gpu
+def test_dump_outputs_holds_the_timed_path_s_result(tmp_path):
+    """--dump-outputs: two runs of the real command write the same lnprob, and it is the oracle's for bench.py's own inputs."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from oracle import oracle as O
+    for d in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--ensembles", "8", "--no-sampler",
+               "--no-extras", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / d)]
+        res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert res.returncode == 0, res.stderr[-2000:]
+        assert json.loads(res.stdout.strip().splitlines()[-1])["steps"] == 3
+    got = np.load(tmp_path / "a" / "lnprob.npy")
+    assert got.dtype == np.float64 and got.shape == (8 * 4096,)
+    assert np.array_equal(np.load(tmp_path / "a" / "lnprob_index.npy"), np.arange(8 * 4096.0))
+    assert np.array_equal(got, np.load(tmp_path / "b" / "lnprob.npy"), equal_nan=True)
+    ps, bf, _ = bench.notebook_descriptor()
+    ref = O.lnprob_batch(O.make_model(ps, "SM_GAUSS", bestfit_fr=bf, smearing=0.02), bench.synth_theta(ps, got.size, seed=26))
+    fin = np.isfinite(ref)
+    assert np.array_equal(np.isfinite(got), fin) and fin.sum() > 0
+    assert np.max(np.abs(got[fin] - ref[fin]) / np.abs(ref[fin])) < 1e-10
+
+
+@pytest.mark.gpu
 def test_bench_line_sub_records_at_reduced_scan_length():
     """The sub-records of the line through the real command, the sharded scans at a reduced chain length (the full
     reference length is exercised by tests/test_gpu_mcmc.py::test_reference_length_scan_on_one_gpu): every BASELINE
