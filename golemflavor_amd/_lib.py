@@ -124,6 +124,14 @@ SIGNATURES = {
     "gf_sampler_postprocess_device": (C.c_int, [_vp, C.POINTER(_vp), _vp, _vp]),
     "gf_sampler_postprocess_rows_device": (C.c_int, [_vp, C.POINTER(_vp), _vp]),
     "gf_sampler_postprocess_rows": (C.c_int, [_vp, C.POINTER(_vp), _dp]),
+    "gf_nested_create": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, _ip, _dp, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int,
+                                   C.POINTER(_vp)]),
+    "gf_nested_set_run_ids": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+    "gf_nested_set_tolerance": (C.c_int, [_vp, C.c_double]),
+    "gf_nested_destroy": (None, [_vp]),
+    "gf_nested_run": (C.c_int, [_vp, C.c_int64]),
+    "gf_nested_result": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_uint32), _ip]),
+    "gf_nested_get_dead": (C.c_int, [_vp, C.c_int, C.c_int64, _dp, _dp, _dp, C.POINTER(C.c_int64)]),
 }
 
 _lib = None

@@ -9,6 +9,7 @@ ranges, seeds, stds, priors, tags and declaration order -- the order is the colu
   C4     texture_paramset(d)    scripts/mc_texture.py:28-76             (7-dim)
   --     mcx_paramset()         scripts/mc_x.py:28-46                   (5-dim: 4 mixing + astroX)
   C5     fr_paramsets(d, inj)   scripts/fr.py:30-104                    (12-dim)
+  --     sens_paramsets(d, inj) scripts/sens.py:34-108                  (12-dim; evidence scan, golemflavor_amd.sens)
 """
 import numpy as np
 
@@ -54,13 +55,13 @@ def _mass_params():
     ]
 
 
-def _gf_nuisance():
+def _gf_nuisance(astro_norm=6.9):
     tag, lg = ParamTag.NUISANCE, PriorsCateg.LIMITEDGAUSS
     return [
         Param(name='convNorm', value=1., seed=[0.5, 2.], ranges=[0.1, 10.], std=0.4, prior=lg, tag=tag),
         Param(name='promptNorm', value=0., seed=[0., 6.], ranges=[0., 20.], std=2.4, prior=lg, tag=tag),
         Param(name='muonNorm', value=1., seed=[0.1, 2.], ranges=[0., 10.], std=0.1, tag=tag),
-        Param(name='astroNorm', value=6.9, seed=[0., 5.], ranges=[0., 20.], std=1.5, tag=tag),
+        Param(name='astroNorm', value=astro_norm, seed=[0., 5.], ranges=[0., 20.], std=1.5, tag=tag),
         Param(name='astroDeltaGamma', value=2.5, seed=[2.4, 3.], ranges=[-5., 5.], std=0.1, tag=tag),
     ]
 
@@ -132,5 +133,25 @@ def fr_paramsets(dimension, bestfit_angles):
     asimov = ParamSet(nuis + [
         Param(name='astroFlavorAngle1', value=bestfit_angles[0], ranges=[0., 1.], std=0.2, tag=tag),
         Param(name='astroFlavorAngle2', value=bestfit_angles[1], ranges=[-1., 1.], std=0.2, tag=tag),
+    ])
+    return asimov, llh_ps
+
+
+def sens_paramsets(dimension, injected_ratio, data=None):
+    """(asimov_paramset, llh_paramset) of scripts/sens.py:34-108 (define_nuisance + get_paramsets, 12-dim): the columns of
+    fr_paramsets, astroNorm 8.0, and the asimov BESTFIT angles fr_to_angles(injected_ratio) -- fr_to_angles([1, 1, 1]) for
+    REAL data (`data` a DataType or its name; default ASIMOV).  injected_ratio is normalised first (sens.py:130-131)."""
+    from . import fr as fr_utils
+    name = getattr(data, "name", data) or "ASIMOV"
+    if name == "REAL":
+        angles = fr_utils.fr_to_angles([1, 1, 1])
+    else:
+        angles = fr_utils.fr_to_angles(fr_utils.normalize_fr(injected_ratio))
+    nuis = _gf_nuisance(astro_norm=8.0)
+    llh_ps = ParamSet(_mixing_params(True, True) + _mass_params() + nuis + [_scale_param(dimension)])
+    tag = ParamTag.BESTFIT
+    asimov = ParamSet(nuis + [
+        Param(name='astroFlavorAngle1', value=angles[0], ranges=[0., 1.], std=0.2, tag=tag),
+        Param(name='astroFlavorAngle2', value=angles[1], ranges=[-1., 1.], std=0.2, tag=tag),
     ])
     return asimov, llh_ps

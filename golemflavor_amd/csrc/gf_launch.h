@@ -69,5 +69,16 @@ struct GfSettleArgs {
     const GfBsm* const* tbs;    // [nchains] (multi != 0), else null
     const GfBsm* tb;            // multi == 0
     int32_t multi;
+    // the nested sampler's variant (gf_launch_nested_settle; unused by the stretch move): walker t = run * batch + slot,
+    // nchains = runs, nwalkers = 2 * batch, multi = 1; an accepted proposal moves ns_prop_u [t][ns_nscan] into ns_wu
+    const double* ns_lstar;     // [runs] L* of the current iteration
+    const double* ns_prop_u;    // [runs * batch][ns_nscan] the parked proposals in the unit cube
+    double* ns_wu;              // [runs * batch][ns_nscan] walker positions
+    double* ns_wl;              // [runs * batch] their lnprob
+    uint32_t* ns_wacc;          // [runs * batch] accepted steps
+    uint32_t* ns_wev;           // [runs * batch] evaluated steps
+    uint32_t* ns_nonunit;       // [runs] proposals the reference would have raised on
+    int32_t ns_nscan;
 };
 hipError_t gf_launch_stretch_settle(const GfSettleArgs& a, int cus, hipStream_t s);
+hipError_t gf_launch_nested_settle(const GfSettleArgs& a, int cus, hipStream_t s);

@@ -136,7 +136,9 @@ __device__ unsigned long long g_settle_cmax[4];
 #else
 #define GF_ST_MARK(i) do { } while (0)
 #endif
-template <class Team>
+// NESTED (gf_nested.hip): the same settlement for the nested sampler's replacement walks; only the completion differs -- a
+// proposal the reference would have raised on is rejected and counted per run, any other is accepted iff lnq > L* of its run.
+template <class Team, bool NESTED = false>
 __global__ __launch_bounds__(UNI_BLOCK, GF_UNI_WAVES) void k_stretch_settle(const GfSettleArgs s)
 {
     __shared__ __attribute__((aligned(16))) double lds[(UNI_BLOCK / 64) * Team::PER_WAVE * Team::DOUBLES];
@@ -247,6 +249,19 @@ __global__ __launch_bounds__(UNI_BLOCK, GF_UNI_WAVES) void k_stretch_settle(cons
                             s.ctl[2 * t + 1] = 0u;
                         }
                     }
+                    if constexpr (NESTED) {
+                        if (last) {
+                            const double lnq = s.pend_rows[(size_t)t * GF_PEND_STRIDE + GF_MAX_DIM];
+                            s.ns_wev[t] += 1u;
+                            if (bad) {
+                                atomicAdd(&s.ns_nonunit[chain], 1u);
+                            } else if (lnq > s.ns_lstar[chain]) {
+                                for (int d = 0; d < s.ns_nscan; ++d) s.ns_wu[t * s.ns_nscan + d] = s.ns_prop_u[t * s.ns_nscan + d];
+                                s.ns_wl[t] = lnq;
+                                s.ns_wacc[t] += 1u;
+                            }
+                        }
+                    } else
                     if (last) {
                         const double* row = s.pend_rows + (size_t)t * GF_PEND_STRIDE;
                         const int kk = (int)(t - (int64_t)chain * nhalf);
@@ -386,6 +401,18 @@ hipError_t gf_launch_stretch_settle(const GfSettleArgs& a, int cus, hipStream_t 
     static const int forced = [] { const char* e = gf_internal_env("GF_SETTLE_BLOCKS", 0); return e ? std::atoi(e) : 0; }();   // diagnostics / A-B
     if (forced > 0) blocks = forced;
     hipLaunchKernelGGL(k_stretch_settle<Team9>, dim3((unsigned)blocks), dim3(UNI_BLOCK), 0, s, a);
+    return hipGetLastError();
+}
+
+// the nested sampler's settle step (gf_nested.hip): one launch after every walk step, same grid rule
+hipError_t gf_launch_nested_settle(const GfSettleArgs& a, int cus, hipStream_t s)
+{
+    constexpr int64_t per_block = (UNI_BLOCK / 64) * Team9::PER_WAVE;
+    const int64_t nprop = (int64_t)a.nchains * (a.nwalkers / 2);
+    int64_t blocks = (nprop * GF_UNI_MAX_FANOUT + per_block - 1) / per_block;
+    if (blocks > cus) blocks = cus;
+    if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL((k_stretch_settle<Team9, true>), dim3((unsigned)blocks), dim3(UNI_BLOCK), 0, s, a);
     return hipGetLastError();
 }
 

@@ -1,0 +1,297 @@
+"""Nested sampling on the device: the Bayesian evidence golemflavor/mn.py asks MultiNest for, at every new-physics scale of
+scripts/sens.py, computed for all scales in one set of launches (gf_nested.hip, include/golemflavor_hip.h gf_nested_*).
+
+The semantics are the reference's (mn.py:22-45): the prior is uniform on the unit cube of the scanned columns, the
+log-likelihood is the full ln_prob (lnprior + llh) of theta, theta_i = (hi_i - lo_i) u_i + lo_i on the scanned columns, the
+paramset's value elsewhere; so Z = int_[0,1]^n exp(ln_prob(theta(u))) du.  Each iteration removes the `batch` lowest live points
+(the j-th removed sees nlive - j live points: dynamic nested sampling, Higson et al. 2019) and replaces them by constrained
+Metropolis walks started from survivors; the run stops at MultiNest's evidence tolerance ln(Z + L_max X) - ln Z < tol.
+
+    NestedSampler          the device sampler over several posteriors (one run each)
+    mn_evidence            mn.py:71-108, same name and return: (ln Z, max ln L)
+    evidence_scan          sens.py's loop over scales in one device call
+    evidence_from_dead     the accounting restated on the host (the tests' reference for the device accumulators)
+    bayes_factor_limit     plot.py:149-213 get_limit, BAYESIAN branch
+"""
+import copy
+import ctypes as C
+import math
+
+import numpy as np
+
+from . import _lib
+from . import configs as Cf
+from . import fr as fr_utils
+from .descriptor import compile_model
+from .enums import ParamTag
+from .model import Model
+
+__all__ = ["NestedSampler", "mn_evidence", "evidence_scan", "evidence_from_dead", "bayes_factor_limit", "sens_scales",
+           "BAYES_K"]
+
+BAYES_K = 1.0                 # golemflavor/plot.py: Bayes factor threshold 10^K
+DEFAULT_NLIVE = 3000          # mn.py:51-53 --mn-live-points
+DEFAULT_TOL = 0.01            # mn.py:55-57 --mn-tolerance
+DEFAULT_WALKS = 25
+
+
+def _handle(m):
+    model = getattr(m, "model", m)          # an LnProb or a Model
+    return model._h
+
+
+class NestedSampler:
+    """`nruns` independent nested-sampling runs, run r on posterior models[r] (Model or LnProb; they share device, ndim and
+    mode and must stay open while the sampler lives).  `cols`: the scanned columns (indices into theta); `bases`
+    ([nruns][ndim] or [ndim]): the values of every other column.  `run_ids`: the Philox stream of each run (default 0..nruns-1);
+    a scan passes each point's index in its full list so that a point's result does not depend on what else shares the call.
+    `labels`: what an AssertionError names for a failed run (default: the run index)."""
+
+    def __init__(self, models, cols, bases, nlive=DEFAULT_NLIVE, batch=None, walks=DEFAULT_WALKS, seed=0,
+                 on_nonunitary="raise", tol=DEFAULT_TOL, run_ids=None, labels=None):
+        if on_nonunitary not in ("raise", "-inf"):
+            raise ValueError("on_nonunitary must be 'raise' or '-inf'")
+        self._L = _lib.lib()
+        self.models = list(models)
+        self.nruns = len(self.models)
+        self.cols = np.ascontiguousarray(cols, dtype=np.int32)
+        ndim = self._L.gf_model_ndim(_handle(self.models[0]))
+        b = np.asarray(bases, dtype=np.float64)
+        if b.ndim == 1:
+            b = np.tile(b, (self.nruns, 1))
+        self.bases = np.ascontiguousarray(b.reshape(self.nruns, ndim))
+        self.nlive = int(nlive)
+        self.batch = int(batch) if batch is not None else max(1, self.nlive // 8)
+        self.walks = int(walks)
+        self.seed = int(seed)
+        self.on_nonunitary = on_nonunitary
+        self.labels = list(labels) if labels is not None else list(range(self.nruns))
+        hs = (C.c_void_p * self.nruns)(*[_handle(m) for m in self.models])
+        h = C.c_void_p()
+        _lib.check(self._L.gf_nested_create(hs, self.nruns, len(self.cols), self.cols.ctypes.data_as(_lib._ip),
+                                            self.bases.ctypes.data_as(_lib._dp), self.nlive, self.batch, self.walks,
+                                            self.seed & 0xFFFFFFFFFFFFFFFF, 0 if on_nonunitary == "raise" else 1, C.byref(h)),
+                   "gf_nested_create")
+        self._h = h
+        _lib.check(self._L.gf_nested_set_tolerance(self._h, float(tol)), "gf_nested_set_tolerance")
+        if run_ids is not None:
+            ids = np.ascontiguousarray(run_ids, dtype=np.uint64)
+            _lib.check(self._L.gf_nested_set_run_ids(self._h, ids.ctypes.data_as(C.POINTER(C.c_uint64))),
+                       "gf_nested_set_run_ids")
+
+    def run(self, max_iter=100000, check=True):
+        """Iterate every run to its tolerance; returns result(), raising AssertionError for a run that met a proposal the
+        reference would have raised on (on_nonunitary == 'raise', sens.py:283-285) when `check`."""
+        _lib.check(self._L.gf_nested_run(self._h, int(max_iter)), "gf_nested_run")
+        res = self.result()
+        if check and self.on_nonunitary == "raise" and res["failed"].any():
+            r = int(np.argmax(res["failed"]))
+            raise AssertionError("Matrix is not unitary! (nested run {0}: {1})".format(r, self.labels[r]))
+        return res
+
+    def result(self):
+        n = self.nruns
+        out = {k: np.zeros(n) for k in ("lnz", "lnz_err", "info", "max_lnl")}
+        it, ev = np.zeros(n, np.int64), np.zeros(n, np.int64)
+        nu, fl = np.zeros(n, np.uint32), np.zeros(n, np.int32)
+        _lib.check(self._L.gf_nested_result(self._h, *[out[k].ctypes.data_as(_lib._dp) for k in ("lnz", "lnz_err", "info", "max_lnl")],
+                                            it.ctypes.data_as(C.POINTER(C.c_int64)), ev.ctypes.data_as(C.POINTER(C.c_int64)),
+                                            nu.ctypes.data_as(C.POINTER(C.c_uint32)), fl.ctypes.data_as(_lib._ip)),
+                   "gf_nested_result")
+        out.update(niter=it, nevals=ev, nonunitary=nu, failed=fl.astype(bool))
+        return out
+
+    def dead(self, run=0):
+        """Run `run`'s dead points in removal order, then its final live set: dict(lnl, lnw (log-weights), cube, theta,
+        nlive_seq (live points each removed point saw), ndead (removed points; the rest is the final live set))."""
+        n = C.c_int64(0)
+        _lib.check(self._L.gf_nested_get_dead(self._h, int(run), 0, None, None, None, C.byref(n)), "gf_nested_get_dead")
+        n = n.value
+        lnl, lnw = np.empty(n), np.empty(n)
+        cube = np.empty((n, len(self.cols)))
+        m = C.c_int64(0)
+        _lib.check(self._L.gf_nested_get_dead(self._h, int(run), n, lnl.ctypes.data_as(_lib._dp), lnw.ctypes.data_as(_lib._dp),
+                                              cube.ctypes.data_as(_lib._dp), C.byref(m)), "gf_nested_get_dead")
+        ndead = n - self.nlive
+        seq = np.tile(self.nlive - np.arange(self.batch), ndead // self.batch)
+        desc = getattr(self.models[run], "model", self.models[run]).desc
+        lo, hi = np.asarray(desc.lo)[self.cols], np.asarray(desc.hi)[self.cols]
+        theta = np.tile(self.bases[run], (n, 1))
+        theta[:, self.cols] = (hi - lo) * cube + lo          # mn.py:35-36
+        return dict(lnl=lnl, lnw=lnw, cube=cube, theta=theta, nlive_seq=seq, ndead=ndead)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.gf_nested_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _logaddexp(x, y):
+    if x == -math.inf:
+        return y
+    if y == -math.inf:
+        return x
+    m = x if x > y else y
+    return m + math.log1p(math.exp(-abs(x - y)))
+
+
+def evidence_from_dead(lnl, nlive_seq, live_lnl=None):
+    """The device's accounting on the host.  Dead point i (in removal order, lnL lnl[i]) saw nlive_seq[i] live points:
+    ln X_{i+1} = ln X_i - 1/n_i, weight L_i (X_i - X_{i+1}); Z and H (Skilling 2006) accumulate in that order.  `live_lnl`: the
+    final live set, added as X mean(L_live) in ascending lnL.  Returns dict(lnz, lnz_err = sqrt(H / n_last), info, lnx)."""
+    lnl = np.asarray(lnl, dtype=np.float64)
+    seq = np.asarray(nlive_seq)
+    lnz, h, lnx = -math.inf, 0.0, 0.0
+
+    def acc(l, lnw):
+        nonlocal lnz, h
+        if lnw == -math.inf:
+            return
+        new = _logaddexp(lnz, lnw)
+        if lnz == -math.inf:
+            h = math.exp(lnw - new) * l - new
+        else:
+            h = math.exp(lnw - new) * l + math.exp(lnz - new) * (h + lnz) - new
+        lnz = new
+
+    for l, n in zip(lnl.tolist(), seq.tolist()):
+        dx = 1.0 / n
+        acc(l, l + lnx + math.log(-math.expm1(-dx)))
+        lnx -= dx
+    nlast = int(seq[0]) if len(seq) else 1
+    if live_lnl is not None:
+        live = np.sort(np.asarray(live_lnl, dtype=np.float64))
+        nlast = len(live)
+        w0 = lnx - math.log(len(live))
+        for l in live.tolist():
+            acc(l, l + w0)
+    return dict(lnz=lnz, lnz_err=math.sqrt(max(h, 0.0) / nlast), info=h, lnx=lnx)
+
+
+def bayes_factor_limit(scales, lnZ, k=BAYES_K):
+    """golemflavor/plot.py:149-213 get_limit, BAYESIAN branch: the lowest scale on the splined curve (splprep, s=0, 1000
+    points) where the evidence has fallen by more than ln(10^k) below the null point (the smallest scale), minus log10(2)
+    (the standard SME coefficient).  None where the reference returns None: no such scale, a curve that does not exclude the
+    large scales (two or more scanned points above the crossing within 0.1 of the threshold), or fewer than two scanned points
+    above it beyond the threshold.  AssertionError('Discovered LV!') as the reference."""
+    from scipy.interpolate import splev, splprep
+    scales = np.asarray(scales, dtype=np.float64)
+    st = np.asarray(lnZ, dtype=np.float64)
+    thr = np.log(10 ** k)
+    if (st[0] - np.max(st)) > thr:
+        raise AssertionError('Discovered LV!')
+    tck, _ = splprep([scales, st], s=0)
+    sc, sst = splev(np.linspace(0, 1, 1000), tck)
+    null = st[np.argmin(scales)]
+    reduced = -(sst - null)
+    al = sc[reduced > thr]
+    if len(al) == 0:
+        return None
+    re = -(st - null)[scales > al[0]]
+    if np.sum(re < thr - 0.1) >= 2:
+        return None
+    if np.sum(re >= thr + 0.0) < 2:
+        return None
+    return al[0] - np.log10(2.)
+
+
+def sens_scales(dimension, segments):
+    """scripts/sens.py:226-229: the null point -100 then linspace over SCALE_BOUNDARIES[d] in segments - 1 steps."""
+    b = Cf.SCALE_BOUNDARIES[dimension]
+    return np.concatenate([[-100.], np.linspace(b[0], b[1], segments - 1)])
+
+
+def _scale_paramset(llh_paramset, scale):
+    """sens.py:255-263: the scale column fixed at `scale`, its lower boundary lowered for the null point."""
+    ps = copy.deepcopy(llh_paramset)
+    prm = ps.from_tag(ParamTag.SCALE)[0]
+    if scale < prm.ranges[0]:
+        prm.ranges = (scale, prm.ranges[1])
+    prm.value = scale
+    return ps
+
+
+def _bsm_desc(args, asimov_paramset, llh_paramset, smearing):
+    bf = fr_utils.angles_to_fr(asimov_paramset.from_tag(ParamTag.BESTFIT, values=True))
+    return compile_model(llh_paramset, "BSM_GAUSS", bestfit_fr=bf, smearing=smearing, source_ratio=args.source_ratio,
+                         texture=args.texture, dimension=args.dimension, binning=args.binning)
+
+
+def _opt(args, name, default):
+    v = getattr(args, name, None)
+    return default if v is None else v
+
+
+def evidence_scan(args, asimov_paramset, llh_paramset, scales, run_ids=None, nlive=None, tol=None, batch=None, walks=None,
+                  seed=None, on_nonunitary="raise", smearing=None, device=0, max_iter=100000, return_sampler=False):
+    """sens.py:231-303 for every scale at once: the scanned columns are every column but the scale (sens.py:217-218), the scale
+    column is fixed at each scale (with its box lowered for the null point), one device call.  `args` as for bsm_ln_prob
+    (source_ratio, dimension, texture, binning) plus the --mn-* options.  Returns dict(scales, lnz, lnz_err, max_lnl, niter,
+    nevals, nonunitary, seconds)."""
+    import time
+    scales = np.asarray(scales, dtype=np.float64)
+    names = list(llh_paramset.names)
+    scale_col = names.index(llh_paramset.from_tag(ParamTag.SCALE)[0].name)
+    cols = [i for i in range(len(names)) if i != scale_col]
+    smearing = float(smearing if smearing is not None else _opt(args, "smearing", 0.02))
+    models, bases = [], []
+    for sc in scales:
+        ps = _scale_paramset(llh_paramset, float(sc))
+        models.append(Model(_bsm_desc(args, asimov_paramset, ps, smearing), device=device))
+        bases.append(np.array(ps.values, dtype=np.float64))
+    labels = ["scale {0:.6g} (Lambda^-1 = {1:.0E})".format(sc, np.power(10., sc)) for sc in scales]
+    try:
+        s = NestedSampler(models, cols, bases, nlive=int(nlive or _opt(args, "mn_live_points", DEFAULT_NLIVE)),
+                          batch=batch if batch is not None else _opt(args, "mn_batch", None),
+                          walks=int(walks or _opt(args, "mn_walks", DEFAULT_WALKS)),
+                          seed=int(seed if seed is not None else _opt(args, "seed", 0)), on_nonunitary=on_nonunitary,
+                          tol=float(tol or _opt(args, "mn_tolerance", DEFAULT_TOL)), run_ids=run_ids, labels=labels)
+        t0 = time.perf_counter()
+        try:
+            res = s.run(max_iter=max_iter)
+        finally:
+            if not return_sampler:
+                s.close()
+        res["seconds"] = time.perf_counter() - t0
+        res["scales"] = scales
+        if return_sampler:
+            res["sampler"] = s
+            res["models"] = models
+        return res
+    finally:
+        if not return_sampler:
+            for m in models:
+                m.close()
+
+
+def mn_evidence(mn_paramset, llh_paramset, asimov_paramset, args, prefix=None):
+    """golemflavor/mn.py:71-108, same name, arguments and return: (evidence, maxllh) = (ln Z, max ln L) of the nested run over
+    mn_paramset's columns with every other column of llh_paramset at its value.  `prefix` (MultiNest's output basename) is
+    accepted and unused: nothing is written."""
+    for n in mn_paramset.names:
+        llh_paramset[n].value = mn_paramset[n].value
+    names = list(llh_paramset.names)
+    cols = [names.index(n) for n in mn_paramset.names]
+    smearing = float(_opt(args, "smearing", 0.02))
+    with Model(_bsm_desc(args, asimov_paramset, llh_paramset, smearing), device=int(_opt(args, "device", 0))) as m:
+        s = NestedSampler([m], cols, np.array(llh_paramset.values, dtype=np.float64),
+                          nlive=int(_opt(args, "mn_live_points", DEFAULT_NLIVE)), batch=_opt(args, "mn_batch", None),
+                          walks=int(_opt(args, "mn_walks", DEFAULT_WALKS)), seed=int(_opt(args, "seed", 0)),
+                          tol=float(_opt(args, "mn_tolerance", DEFAULT_TOL)), labels=[prefix or "mn"])
+        try:
+            res = s.run()
+        finally:
+            s.close()
+    return float(res["lnz"][0]), float(res["max_lnl"][0])

@@ -1,0 +1,108 @@
+"""`python -m golemflavor_amd.sens`: scripts/sens.py on the device nested sampler (golemflavor_amd.nested).
+
+Same arguments as the reference's driver for what applies here (the likelihood is the package's Gaussian substitute,
+README.md:70-74), same scale list ([-100] + linspace over SCALE_BOUNDARIES[d] in segments - 1 steps, sens.py:226-229) and the
+same two output arrays, {datadir}/{stat_method}/{data}/fr_stat{identifier}.npy and fr_maxllh{identifier}.npy of shape
+(segments, 2) -- (1, 2) with --eval-segment, whose files carry `_scale_{10^scale:.0E}` (sens.py:232-258).  All scales run in
+one device call.  Prints one JSON summary line.
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+from . import configs as Cf
+from . import fr as fr_utils
+from . import nested
+from .enums import DataType, StatCateg, Texture
+from .mcmc import chain_identifier
+
+
+def _enum(E):
+    def parse(s):
+        return E[str(s).rsplit(".", 1)[-1].upper()]
+    return parse
+
+
+def _bool(s):
+    return str(s).lower() in ("true", "1", "yes", "y")
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m golemflavor_amd.sens", description="BSM flavor ratio evidence scan "
+                                 "(scripts/sens.py) on the device nested sampler")
+    ap.add_argument("--seed", type=int, default=25, help="random seed")
+    ap.add_argument("--datadir", type=str, default="./untitled", help="where the arrays are written")
+    ap.add_argument("--segments", type=int, default=10, help="number of new physics scales to evaluate (with the null point)")
+    ap.add_argument("--eval-segment", type=str, default="all", help="which point to evaluate ('all' or an index)")
+    ap.add_argument("--overwrite", type=_bool, default=False, help="overwrite existing arrays")
+    ap.add_argument("--dimension", type=int, default=6, choices=sorted(Cf.SCALE_BOUNDARIES))
+    ap.add_argument("--texture", type=_enum(Texture), default=Texture.OET)
+    ap.add_argument("--source-ratio", type=float, nargs=3, default=[0, 1, 0])
+    ap.add_argument("--injected-ratio", type=float, nargs=3, default=[1, 1, 1])
+    ap.add_argument("--data", type=_enum(DataType), default=DataType.ASIMOV)
+    ap.add_argument("--stat-method", type=_enum(StatCateg), default=StatCateg.BAYESIAN)
+    ap.add_argument("--binning", type=float, nargs=3, default=list(Cf.DEFAULT_BINNING))
+    ap.add_argument("--smearing", type=float, default=0.02, help="width of the Gaussian substitute likelihood")
+    ap.add_argument("--mn-live-points", type=int, default=nested.DEFAULT_NLIVE)
+    ap.add_argument("--mn-tolerance", type=float, default=nested.DEFAULT_TOL)
+    ap.add_argument("--mn-batch", type=int, default=None, help="live points replaced per iteration (default nlive // 8)")
+    ap.add_argument("--mn-walks", type=int, default=nested.DEFAULT_WALKS, help="Metropolis steps per replacement")
+    ap.add_argument("--on-nonunitary", choices=["raise", "-inf"], default="raise")
+    ap.add_argument("--device", type=int, default=0)
+    args = ap.parse_args(argv)
+    if args.texture is Texture.NONE:
+        ap.error("Must assume a BSM texture")                         # sens.py:145-146
+    if args.stat_method is not StatCateg.BAYESIAN:
+        ap.error("only the BAYESIAN statistic is implemented")       # sens.py:140-143
+    args.source_ratio = fr_utils.normalize_fr(args.source_ratio)
+    if args.data is not DataType.REAL:
+        args.injected_ratio = fr_utils.normalize_fr(args.injected_ratio)
+    args.binning = Cf.default_bin_edges((args.binning[0], args.binning[1], int(args.binning[2])))
+    args.eval_segment = None if args.eval_segment.lower() == "all" else int(args.eval_segment)
+    return args
+
+
+def output_paths(args, scales=None):
+    """sens.py:235-240, 247-250: (fr_stat, fr_maxllh) file names without '.npy'."""
+    base = os.path.join(args.datadir, args.stat_method.name.lower(), args.data.name.lower())
+    ident = chain_identifier(args)
+    stat, llh = os.path.join(base, "fr_stat" + ident), os.path.join(base, "fr_maxllh" + ident)
+    if args.eval_segment is not None:
+        sc = (scales if scales is not None else nested.sens_scales(args.dimension, args.segments))[args.eval_segment]
+        tail = "_scale_{0:.0E}".format(np.power(10., sc))
+        stat, llh = stat + tail, llh + tail
+    return stat, llh
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    scales = nested.sens_scales(args.dimension, args.segments)
+    outfile, outfile_llh = output_paths(args, scales)
+    for f in (outfile, outfile_llh):
+        if not args.overwrite and os.path.isfile(f + ".npy") and np.all(np.isfinite(np.load(f + ".npy"))):
+            print("FILE EXISTS {0}".format(f + ".npy"))
+            return 0
+    idx = np.arange(len(scales)) if args.eval_segment is None else np.array([args.eval_segment])
+    asimov, llh_ps = Cf.sens_paramsets(args.dimension, args.injected_ratio, data=args.data)
+    res = nested.evidence_scan(args, asimov, llh_ps, scales[idx], run_ids=idx, on_nonunitary=args.on_nonunitary,
+                               device=args.device)
+    evidence_arr = np.stack([scales[idx], res["lnz"]], axis=1)
+    maxllh_arr = np.stack([scales[idx], res["max_lnl"]], axis=1)
+    for f, arr in ((outfile, evidence_arr), (outfile_llh, maxllh_arr)):
+        os.makedirs(os.path.dirname(f) or ".", exist_ok=True)
+        np.save(f + ".npy", arr)
+    print(json.dumps({
+        "tool": "golemflavor_amd.sens", "dimension": args.dimension, "texture": args.texture.name,
+        "segments": args.segments, "nlive": args.mn_live_points, "scales": scales[idx].tolist(),
+        "lnz": res["lnz"].tolist(), "lnz_err": res["lnz_err"].tolist(), "max_lnl": res["max_lnl"].tolist(),
+        "niter": res["niter"].tolist(), "nevals": int(res["nevals"].sum()), "nonunitary": res["nonunitary"].tolist(),
+        "seconds": round(res["seconds"], 4), "evals_per_s": float(res["nevals"].sum() / max(res["seconds"], 1e-12)),
+        "fr_stat": outfile + ".npy", "fr_maxllh": outfile_llh + ".npy"}))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -279,6 +279,36 @@ int gf_sampler_postprocess_rows_device(gf_sampler* s, gf_model* const* models, d
  * hands to scripts/mc_texture.py's np.save); synchronous */
 int gf_sampler_postprocess_rows(gf_sampler* s, gf_model* const* models, double* rows);
 
+/* ---- device-resident nested sampler ------------------------------------------------------- */
+/* The evidence golemflavor/mn.py:71-108 asks MultiNest for (scripts/sens.py runs it at every new-physics scale), computed on the
+ * device for `nruns` independent runs in one set of launches.  Run r samples models[r] (one model per run: the null point of
+ * sens.py:201,260-263 has its own box; all share device, ndim and mode and must outlive the sampler).  The prior is uniform on
+ * the unit cube of the nscan columns cols[] (mn.py:22-23), theta = lo + (hi - lo) u on those (the model's box, mn.py:35-36), every
+ * other column is bases[r][col] ([nruns][ndim]); the log-likelihood is the full ln_prob.  nlive <= 4096 live points; each
+ * iteration removes the `batch` lowest (1 <= batch < nlive; the j-th removed point sees nlive - j live points) and replaces them
+ * by constrained Metropolis walks of `walks` steps in the cube, proposal u + s C z with C the Cholesky factor of the survivors'
+ * covariance.  Stops at ln(Z + L_max X) - ln Z < tol (default 0.01, mn.py:61) and adds the live set's X mean(L).  Philox4x32-10
+ * keyed by `seed`, counter (run id, iteration, slot, step): a run's result is independent of the other runs.  on_nonunitary: 0 =
+ * "raise" (a proposal the reference would have raised on, fr.py:493-498, ends that run and sets its `failed`), 1 = "-inf" (such
+ * proposals lie outside the support and are counted). */
+typedef struct gf_nested gf_nested;
+int gf_nested_create(gf_model* const* models, int nruns, int nscan, const int32_t* cols, const double* bases, int nlive, int batch,
+                     int walks, uint64_t seed, int on_nonunitary, gf_nested** out);
+/* run ids [nruns] (default: the index in this sampler): a scan passes each point's index in its full list.  Before the first run. */
+int gf_nested_set_run_ids(gf_nested* s, const uint64_t* ids);
+/* evidence tolerance (mn.py:58-61 --mn-tolerance), default 0.01 */
+int gf_nested_set_tolerance(gf_nested* s, double tol);
+void gf_nested_destroy(gf_nested* s);
+/* Synchronous: iterates until every run has met its tolerance.  More than max_iter iterations of one run: GF_ERR_UNSUPPORTED. */
+int gf_nested_run(gf_nested* s, int64_t max_iter);
+/* per run [nruns]: ln Z, its error sqrt(H / nlive), H, max lnL, iterations, likelihood evaluations, proposals the reference
+ * would have raised on, failed (raise mode); NULL = skip */
+int gf_nested_result(gf_nested* s, double* lnz, double* lnz_err, double* info, double* max_lnl, int64_t* niter, int64_t* nevals,
+                     uint32_t* nonunitary, int32_t* failed);
+/* run `run`'s dead points in removal order followed by its final live set: *n = iterations * batch + nlive rows of lnl, lnw
+ * (log-weights) and cube [n][nscan]; NULL = skip; all NULL: only *n.  cap = rows the arrays hold. */
+int gf_nested_get_dead(gf_nested* s, int run, int64_t cap, double* lnl, double* lnw, double* cube, int64_t* n);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI -------------------------------------- */
 /* Independent chains (grid points) shard across ranks with no data-path collective; the only
  * exchanges are the broadcast of the packed descriptors at start and the gather of the chain blocks
