@@ -8,8 +8,12 @@
 //                K - j live points: ln X_{i+1} = ln X_i - 1/(K - j), weight L_i (X_i - X_{i+1}) (dynamic nested sampling,
 //                Higson et al. 2019) -- appends them to the dead points, updates ln Z, H and max lnL, sets L* = the highest
 //                removed lnL, forms the survivors' covariance and its Cholesky factor C (fp64), and draws each replacement's
-//                start among the survivors.  It also applies the termination rule ln(Z + L_max X) - ln Z < tol and then adds
-//                the live set's X mean(L_live).
+//                start among the survivors above L*.  It also applies the termination rule ln(Z + L_max X) - ln Z < tol and
+//                then adds the live set's X mean(L_live).
+//                Where the likelihood is zero (lnL = -inf) the live points tie on a plateau; replacements never land on it, so
+//                its points are removed without replacement across iterations: the i-th -inf point of the run (they all come
+//                first) sees K - i live points (Fowlie, Handley & Su 2021), and their compression variance sum 1/(K - i)^2
+//                is added to the error of ln Z.
 //   k_ns_walk    (x walks) one Metropolis step of every replacement walker of every live run: u' = u + s C z, z ~ N(0, I); a
 //                step outside the cube is rejected unevaluated, otherwise it is accepted iff lnq > L*.  Proposals whose
 //                unitarity verdict the in-kernel tiers cannot settle are parked and settled by the emulated-x87 team
@@ -49,6 +53,8 @@ constexpr uint32_t NS_START_STEP = 0xFFFFFFFFu;     // step word of a replacemen
 
 struct NsRun {
     double lnx, lnz, h, lmax, scale;
+    double pvar;            // compression variance of the plateau removals, sum 1/n^2
+    int64_t nplat;          // plateau (lnL = -inf) points removed so far
     int64_t iter;           // completed removal iterations
     int64_t nevals;         // likelihood evaluations
     int32_t done, failed;   // failed: on_nonunitary == raise and a proposal the reference would have raised on
@@ -163,7 +169,7 @@ __global__ __launch_bounds__(NS_SEL_BLOCK) void k_ns_select(const NsArgs a)
     __shared__ double mean[GF_MAX_DIM];
     __shared__ double cov[GF_MAX_DIM * GF_MAX_DIM];
     __shared__ double part[NS_SEL_BLOCK];
-    __shared__ int skip;
+    __shared__ int skip, first;
     const int r = blockIdx.x, tid = threadIdx.x;
     const int K = a.nlive, B = a.batch, D = a.nscan;
     NsRun* run = a.runs + r;
@@ -217,14 +223,25 @@ __global__ __launch_bounds__(NS_SEL_BLOCK) void k_ns_select(const NsArgs a)
             double* dl = a.dead_l + (it * a.nruns + r) * B;
             double* dw = a.dead_w + (it * a.nruns + r) * B;
             for (int j = 0; j < B; ++j) {
-                const double dx = 1.0 / (double)(K - j);
+                // a plateau point sees the K - i live points left of the i-th removal: fewer than K - j from the second batch
+                // on (no replacement lands on the plateau, so it never gains a point back); K - i >= 1 since a live set
+                // of K plateau points stops the run
+                const bool plat = key[j] == -gf_inf();
+                const double dx = 1.0 / (double)(plat ? K - R.nplat : K - j);
                 const double lnw = key[j] + R.lnx + log(-expm1(-dx));     // ln(X_i - X_{i+1}) = ln X_i + ln(1 - e^{-1/n})
                 ns_accumulate(R, key[j], lnw);
                 dl[j] = key[j];
                 dw[j] = lnw;
                 R.lnx -= dx;
+                if (plat) { R.nplat += 1; R.pvar += dx * dx; }
             }
-            a.lstar[r] = key[B - 1];
+            const double ls = key[B - 1];
+            a.lstar[r] = ls;
+            // the first survivor above L* (binary search of the sorted keys); a walk started on a point tied at L* might
+            // commit it unmoved.  Only if every survivor ties a finite L* are they all start points.
+            int lo = B, hi = K;
+            while (lo < hi) { const int mid = (lo + hi) >> 1; if (key[mid] > ls) hi = mid; else lo = mid + 1; }
+            first = lo < K ? lo : B;
         }
         *run = R;
         skip = R.done;
@@ -294,11 +311,12 @@ __global__ __launch_bounds__(NS_SEL_BLOCK) void k_ns_select(const NsArgs a)
             for (int q = p + 1; q < D; ++q) L[p * D + q] = 0.0;
         }
     }
-    // start points: survivor drawn uniformly (counter (run id, iteration, slot, NS_START_STEP))
+    // start points: a survivor above L* drawn uniformly (counter (run id, iteration, slot, NS_START_STEP))
+    const int m0 = first;
     for (int j = tid; j < B; j += NS_SEL_BLOCK) {
         double v[2];
         ns_uniform2(a, r, (uint32_t)it, (uint32_t)j, NS_START_STEP, v);
-        int m = B + (int)(v[0] * (double)ns);
+        int m = m0 + (int)(v[0] * (double)(K - m0));
         if (m >= K) m = K - 1;
         const int src = idx[m];
         const int64_t w = (int64_t)r * B + j;
@@ -639,7 +657,7 @@ int gf_nested_create(gf_model* const* models, int nruns, int nscan, const int32_
     std::vector<uint64_t> ids(R);
     for (size_t r = 0; r < R; ++r) {
         NsRun& x = hr[r];
-        x.lnx = 0.0; x.lnz = -HUGE_VAL; x.h = 0.0; x.lmax = -HUGE_VAL; x.scale = 1.0;
+        x.lnx = 0.0; x.lnz = -HUGE_VAL; x.h = 0.0; x.lmax = -HUGE_VAL; x.scale = 1.0; x.pvar = 0.0; x.nplat = 0;
         x.iter = 0; x.nevals = (int64_t)K; x.done = 0; x.failed = 0;
         ids[r] = r;
     }
@@ -757,13 +775,30 @@ int gf_nested_result(gf_nested* s, double* lnz, double* lnz_err, double* info, d
     for (int r = 0; r < R; ++r) {
         const NsRun& x = hr[r];
         if (lnz) lnz[r] = x.lnz;
-        if (lnz_err) lnz_err[r] = std::sqrt((x.h > 0.0 ? x.h : 0.0) / (double)s->a.nlive);
+        if (lnz_err) lnz_err[r] = std::sqrt((x.h > 0.0 ? x.h : 0.0) / (double)s->a.nlive + x.pvar);
         if (info) info[r] = x.h;
         if (max_lnl) max_lnl[r] = x.lmax;
         if (niter) niter[r] = x.iter;
         if (nevals) nevals[r] = x.nevals;
         if (nonunitary) nonunitary[r] = nu[r];
         if (failed) failed[r] = x.failed;
+    }
+    return GF_OK;
+}
+
+// Test access, not declared in the header: every run's walk step scale s and ln X, [nruns] each; NULL = skip.  With the live
+// set and the dead rows (gf_nested_get_dead) they are the whole state the next iteration starts from.
+int gf_internal_nested_state(gf_nested* s, double* scale, double* lnx)
+{
+    if (!s) return GF_ERR_INVALID_ARG;
+    GFN_HIP(hipSetDevice(s->device));
+    const int R = s->a.nruns;
+    std::vector<NsRun> hr(R);
+    GFN_HIP(hipMemcpyAsync(hr.data(), s->a.runs, sizeof(NsRun) * R, hipMemcpyDeviceToHost, s->stream));
+    GFN_HIP(hipStreamSynchronize(s->stream));
+    for (int r = 0; r < R; ++r) {
+        if (scale) scale[r] = hr[r].scale;
+        if (lnx) lnx[r] = hr[r].lnx;
     }
     return GF_OK;
 }

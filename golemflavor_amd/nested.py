@@ -5,7 +5,9 @@ The semantics are the reference's (mn.py:22-45): the prior is uniform on the uni
 log-likelihood is the full ln_prob (lnprior + llh) of theta, theta_i = (hi_i - lo_i) u_i + lo_i on the scanned columns, the
 paramset's value elsewhere; so Z = int_[0,1]^n exp(ln_prob(theta(u))) du.  Each iteration removes the `batch` lowest live points
 (the j-th removed sees nlive - j live points: dynamic nested sampling, Higson et al. 2019) and replaces them by constrained
-Metropolis walks started from survivors; the run stops at MultiNest's evidence tolerance ln(Z + L_max X) - ln Z < tol.
+Metropolis walks started from survivors above L*; the run stops at MultiNest's evidence tolerance ln(Z + L_max X) - ln Z < tol.
+Points of zero likelihood (lnL = -inf) are never replaced by such points, so the i-th of them removed in a run sees nlive - i
+live points, whatever the batch (nlive_sequence; Fowlie, Handley & Su 2021).
 
     NestedSampler          the device sampler over several posteriors (one run each)
     mn_evidence            mn.py:71-108, same name and return: (ln Z, max ln L)
@@ -26,8 +28,8 @@ from .descriptor import compile_model
 from .enums import ParamTag
 from .model import Model
 
-__all__ = ["NestedSampler", "mn_evidence", "evidence_scan", "evidence_from_dead", "bayes_factor_limit", "sens_scales",
-           "BAYES_K"]
+__all__ = ["NestedSampler", "mn_evidence", "evidence_scan", "evidence_from_dead", "nlive_sequence", "bayes_factor_limit",
+           "sens_scales", "BAYES_K"]
 
 BAYES_K = 1.0                 # golemflavor/plot.py: Bayes factor threshold 10^K
 DEFAULT_NLIVE = 3000          # mn.py:51-53 --mn-live-points
@@ -113,7 +115,7 @@ class NestedSampler:
         _lib.check(self._L.gf_nested_get_dead(self._h, int(run), n, lnl.ctypes.data_as(_lib._dp), lnw.ctypes.data_as(_lib._dp),
                                               cube.ctypes.data_as(_lib._dp), C.byref(m)), "gf_nested_get_dead")
         ndead = n - self.nlive
-        seq = np.tile(self.nlive - np.arange(self.batch), ndead // self.batch)
+        seq = nlive_sequence(lnl[:ndead], self.nlive, self.batch)
         desc = getattr(self.models[run], "model", self.models[run]).desc
         lo, hi = np.asarray(desc.lo)[self.cols], np.asarray(desc.hi)[self.cols]
         theta = np.tile(self.bases[run], (n, 1))
@@ -147,13 +149,25 @@ def _logaddexp(x, y):
     return m + math.log1p(math.exp(-abs(x - y)))
 
 
+def nlive_sequence(lnl_dead, nlive, batch):
+    """The live points each dead point saw, in removal order (`lnl_dead`: the dead lnL, whole batches).  The j-th point removed
+    in a batch sees nlive - j; a point of zero likelihood is removed without replacement over the whole run, so the i-th
+    lnL = -inf point of the run (they come first) sees nlive - i."""
+    lnl = np.asarray(lnl_dead, dtype=np.float64)
+    seq = nlive - np.arange(len(lnl), dtype=np.int64) % int(batch)
+    plat = lnl == -np.inf
+    seq[plat] = nlive - np.arange(int(plat.sum()), dtype=np.int64)
+    return seq
+
+
 def evidence_from_dead(lnl, nlive_seq, live_lnl=None):
     """The device's accounting on the host.  Dead point i (in removal order, lnL lnl[i]) saw nlive_seq[i] live points:
     ln X_{i+1} = ln X_i - 1/n_i, weight L_i (X_i - X_{i+1}); Z and H (Skilling 2006) accumulate in that order.  `live_lnl`: the
-    final live set, added as X mean(L_live) in ascending lnL.  Returns dict(lnz, lnz_err = sqrt(H / n_last), info, lnx)."""
+    final live set, added as X mean(L_live) in ascending lnL.  Returns dict(lnz, lnz_err = sqrt(H / n_last + plateau_var), info,
+    lnx, plateau_var = sum 1/n_i^2 over the dead points with lnL = -inf: the variance their compression adds to ln X)."""
     lnl = np.asarray(lnl, dtype=np.float64)
     seq = np.asarray(nlive_seq)
-    lnz, h, lnx = -math.inf, 0.0, 0.0
+    lnz, h, lnx, pvar = -math.inf, 0.0, 0.0, 0.0
 
     def acc(l, lnw):
         nonlocal lnz, h
@@ -170,6 +184,8 @@ def evidence_from_dead(lnl, nlive_seq, live_lnl=None):
         dx = 1.0 / n
         acc(l, l + lnx + math.log(-math.expm1(-dx)))
         lnx -= dx
+        if l == -math.inf:
+            pvar += dx * dx
     nlast = int(seq[0]) if len(seq) else 1
     if live_lnl is not None:
         live = np.sort(np.asarray(live_lnl, dtype=np.float64))
@@ -177,7 +193,7 @@ def evidence_from_dead(lnl, nlive_seq, live_lnl=None):
         w0 = lnx - math.log(len(live))
         for l in live.tolist():
             acc(l, l + w0)
-    return dict(lnz=lnz, lnz_err=math.sqrt(max(h, 0.0) / nlast), info=h, lnx=lnx)
+    return dict(lnz=lnz, lnz_err=math.sqrt(max(h, 0.0) / nlast + pvar), info=h, lnx=lnx, plateau_var=pvar)
 
 
 def bayes_factor_limit(scales, lnZ, k=BAYES_K):

@@ -301,8 +301,8 @@ int gf_nested_set_tolerance(gf_nested* s, double tol);
 void gf_nested_destroy(gf_nested* s);
 /* Synchronous: iterates until every run has met its tolerance.  More than max_iter iterations of one run: GF_ERR_UNSUPPORTED. */
 int gf_nested_run(gf_nested* s, int64_t max_iter);
-/* per run [nruns]: ln Z, its error sqrt(H / nlive), H, max lnL, iterations, likelihood evaluations, proposals the reference
- * would have raised on, failed (raise mode); NULL = skip */
+/* per run [nruns]: ln Z, its error sqrt(H / nlive + the compression variance of the zero-likelihood plateau), H, max lnL,
+ * iterations, likelihood evaluations, proposals the reference would have raised on, failed (raise mode); NULL = skip */
 int gf_nested_result(gf_nested* s, double* lnz, double* lnz_err, double* info, double* max_lnl, int64_t* niter, int64_t* nevals,
                      uint32_t* nonunitary, int32_t* failed);
 /* run `run`'s dead points in removal order followed by its final live set: *n = iterations * batch + nlive rows of lnl, lnw

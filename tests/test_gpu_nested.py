@@ -138,6 +138,20 @@ def test_sens_evidence_matches_importance_monte_carlo():
         assert abs(res["lnz"][k] - lnz_mc) < 4 * sig, (sc, res["lnz"][k], lnz_mc, sig)
 
 
+@pytest.mark.parametrize("scale", [-43.5, -42.75, -42.5, -42.25])
+def test_sens_evidence_in_the_falloff_band(scale):
+    """Where part of the cube has L = 0 (about 18, 49, 68 and 92 % of it at these scales) the plateau is removed without
+    replacement; charging it the per-batch compression instead overstates ln Z by about -1.06 f - ln(1 - f)."""
+    res = run_scan(np.array([scale]))
+    _, ps = sens_sets()
+    lnz_mc, se_mc = _importance_lnz(ps, scale, np.random.default_rng(12))
+    assert np.isfinite(lnz_mc) and se_mc < 0.05, (scale, lnz_mc, se_mc)
+    sig = np.sqrt(res["lnz_err"][0] ** 2 + se_mc ** 2)
+    print("scale %g: ln Z nested %.4f +- %.4f, importance MC %.4f +- %.4f" % (scale, res["lnz"][0], res["lnz_err"][0], lnz_mc,
+                                                                              se_mc))
+    assert abs(res["lnz"][0] - lnz_mc) < 4 * sig, (scale, res["lnz"][0], lnz_mc, sig)
+
+
 def test_device_accounting_matches_host_restatement():
     lo, hi = Cf.SCALE_BOUNDARIES[6]
     res = run_scan(np.array([-100., lo]), nlive=600, return_sampler=True)
@@ -181,8 +195,8 @@ def test_runs_are_deterministic_and_independent():
             os.environ["GF_NESTED_LPW"] = old
 
 
-def _nonunitary_scale():
-    args = sens_args()
+def _nonunitary_scale(texture):
+    args = sens_args(texture=texture)
     asimov, ps = sens_sets()
     rng = np.random.default_rng(5)
     lo, hi = Cf.SCALE_BOUNDARIES[6]
@@ -202,13 +216,17 @@ def _nonunitary_scale():
 
 
 def test_nonunitary_options():
-    sc = _nonunitary_scale()
-    if sc is None:
-        pytest.skip("no scale of the d = 6 OET sens posterior has prior draws the reference would raise on")
-    res = run_scan(np.array([sc]), nlive=400, on_nonunitary="-inf")
+    # texture OEU: at the scales where its prior draws start to fail the reference's unitarity assert (about 1 % near -36) most
+    # of the cube is still finite (OET has no such scale: its likelihood underflows everywhere first)
+    sc = _nonunitary_scale(Texture.OEU)
+    assert sc is not None, "no scale of the d = 6 OEU sens posterior has prior draws the reference would raise on"
+    args = sens_args(texture=Texture.OEU)
+    asimov, ps = sens_sets()
+    kw = dict(nlive=400, seed=7)
+    res = nested.evidence_scan(args, asimov, ps, np.array([sc]), on_nonunitary="-inf", **kw)
     assert res["nonunitary"][0] > 0 and np.isfinite(res["lnz"][0])
     with pytest.raises(AssertionError, match="scale %.6g" % sc):
-        run_scan(np.array([sc]), nlive=400, on_nonunitary="raise")
+        nested.evidence_scan(args, asimov, ps, np.array([sc]), on_nonunitary="raise", **kw)
 
 
 def test_sens_cli_end_to_end(tmp_path):

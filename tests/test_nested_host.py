@@ -21,61 +21,106 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 # ---- 1. evidence_from_dead on a problem with exact constrained draws --------------------------------------------------------
-def _exact_nested(rng, n, sigma, nlive, b, tol=0.01):
+def _exact_nested(rng, n, sigma, nlive, b, tol=0.01, f=0.0):
     """Nested sampling of L = N(u; c, sigma^2 I) on [0,1]^n with EXACT constrained draws: {L > L*} is a ball around c (cut by
-    the cube), sampled uniformly by rejection.  Same removal and termination rules as the device."""
+    the cube), sampled uniformly by rejection.  Where u_0 < f the likelihood is zero (lnL = -inf): a plateau of prior mass f,
+    and c_0 sits mid-way in [f, 1].  Same removal, start and termination rules as the device (nested.nlive_sequence: the
+    i-th plateau point of the run sees nlive - i live points).  Returns (evidence_from_dead, nlive_seq, dead lnL,
+    final live lnL)."""
     c = np.full(n, 0.5)
+    c[0] = 0.5 * (1.0 + f)
     lnorm = -0.5 * n * math.log(2 * math.pi * sigma * sigma)
 
     def lnl(u):
-        return lnorm - 0.5 * np.sum((u - c) ** 2, axis=-1) / (sigma * sigma)
+        out = lnorm - 0.5 * np.sum((u - c) ** 2, axis=-1) / (sigma * sigma)
+        return np.where(u[..., 0] < f, -np.inf, out)
 
-    def draw(k, rho):
+    def draw(k, lstar):
         out = []
+        rho = math.inf if lstar == -math.inf else math.sqrt(max(2 * sigma * sigma * (lnorm - lstar), 0.0))
         while len(out) < k:
-            if rho > 0.5:
+            if rho > 0.5 * (1.0 - f):
                 u = rng.uniform(size=(4 * k, n))
-                u = u[np.sum((u - c) ** 2, axis=1) < rho * rho]
+                u[:, 0] = f + (1.0 - f) * u[:, 0]
             else:
                 d = rng.normal(size=(4 * k, n))
                 d /= np.linalg.norm(d, axis=1)[:, None]
                 u = c + d * (rho * rng.uniform(size=(4 * k, 1)) ** (1.0 / n))
-            out.extend(u)
+            inside = np.all((u >= 0) & (u <= 1), axis=1) & (u[:, 0] >= f) & (np.sum((u - c) ** 2, axis=1) < rho * rho)
+            out.extend(u[inside])
         return np.array(out[:k])
 
     live = rng.uniform(size=(nlive, n))
     ll = lnl(live)
     dead, seq = [], []
-    lnz, lnx = -math.inf, 0.0
+    lnz, lnx, nplat = -math.inf, 0.0, 0
     while True:
         lmax = ll.max()
         if lnz > -math.inf and np.logaddexp(lnz, lmax + lnx) - lnz < tol:
             break
         order = np.argsort(ll, kind="stable")[:b]
         for j, i in enumerate(order):
-            dx = 1.0 / (nlive - j)
+            nl = nlive - (nplat if ll[i] == -math.inf else j)
+            nplat += ll[i] == -math.inf
+            dx = 1.0 / nl
             lnz = np.logaddexp(lnz, ll[i] + lnx + math.log(-math.expm1(-dx)))
             lnx -= dx
             dead.append(ll[i])
-            seq.append(nlive - j)
-        lstar = ll[order[-1]]
-        rho = math.sqrt(max(2 * sigma * sigma * (lnorm - lstar), 0.0))
-        new = draw(b, rho)
+            seq.append(nl)
+        new = draw(b, ll[order[-1]])
         live[order] = new
         ll[order] = lnl(new)
-    return nested.evidence_from_dead(dead, seq, live_lnl=ll), np.array(seq)
+    return nested.evidence_from_dead(dead, seq, live_lnl=ll), np.array(seq), np.array(dead), ll
+
+
+def _exact_lnz(n, sigma, f):
+    """ln of the integral of N(u; c, sigma^2 I) over [f, 1] x [0, 1]^(n-1), c as in _exact_nested."""
+    half = 0.5 * (1.0 - f)
+    return math.log(math.erf(half / (sigma * math.sqrt(2)))) + (n - 1) * math.log(math.erf(0.5 / (sigma * math.sqrt(2))))
 
 
 @pytest.mark.parametrize("batch_of", [lambda k: 1, lambda k: k // 8], ids=["b1", "b_nlive_over_8"])
 def test_evidence_from_dead_exact_problem(batch_of):
     n, sigma, nlive = 3, 0.05, 160
     exact = n * math.log(math.erf(0.5 / (sigma * math.sqrt(2))))
+    assert abs(_exact_lnz(n, sigma, 0.0) - exact) < 1e-15
     for seed in range(4):
-        res, seq = _exact_nested(np.random.default_rng(seed), n, sigma, nlive, batch_of(nlive))
+        res, seq, dead, live = _exact_nested(np.random.default_rng(seed), n, sigma, nlive, batch_of(nlive))
         err = math.sqrt(res["info"] / nlive)
-        assert res["info"] > 1.0 and abs(res["lnz_err"] - err) < 1e-15
+        assert res["info"] > 1.0 and abs(res["lnz_err"] - err) < 1e-15 and res["plateau_var"] == 0.0
         assert abs(res["lnz"] - exact) < 4 * err, (seed, res["lnz"], exact, err)
         assert seq.min() == nlive - batch_of(nlive) + 1
+        assert np.array_equal(seq, nested.nlive_sequence(dead, nlive, batch_of(nlive)))
+
+
+@pytest.mark.parametrize("f", [0.0, 0.5, 0.9])
+@pytest.mark.parametrize("batch_of", [lambda k: 1, lambda k: k // 8], ids=["b1", "b_nlive_over_8"])
+def test_evidence_with_a_zero_likelihood_plateau(f, batch_of):
+    """A region of prior mass f where L = 0: ln Z within 4 sigma of the closed form, sigma including the plateau's compression
+    variance.  The old per-batch rule (every removal of an iteration sees nlive - j, plateau or not) is off by about
+    -1.06 f - ln(1 - f) for a batch of nlive / 8: more than 4 sigma at f = 0.9."""
+    n, sigma, nlive = 3, 0.03, 400
+    b = batch_of(nlive)
+    exact = _exact_lnz(n, sigma, f)
+    for seed in range(4):
+        res, seq, dead, live = _exact_nested(np.random.default_rng(100 + seed), n, sigma, nlive, b, f=f)
+        nd = len(dead)
+        plat = dead == -np.inf
+        assert np.array_equal(seq, nested.nlive_sequence(dead, nlive, b))
+        if f == 0.0:
+            assert not plat.any() and res["plateau_var"] == 0.0
+        else:
+            k = int(plat.sum())
+            assert plat[:k].all() and not plat[k:].any()             # the plateau comes first
+            assert abs(k / nlive - f) < 5 * math.sqrt(f * (1 - f) / nlive), (k, f)
+            assert np.array_equal(seq[:k], nlive - np.arange(k))
+            assert res["plateau_var"] == pytest.approx(np.sum(1.0 / seq[:k].astype(float) ** 2), rel=1e-12)
+        sig = math.sqrt(res["info"] / nlive + res["plateau_var"])
+        assert res["lnz_err"] == pytest.approx(sig, rel=1e-12)
+        assert abs(res["lnz"] - exact) < 4 * sig, (f, seed, res["lnz"], exact, sig)
+        if f == 0.9 and b > 1:
+            old = nested.evidence_from_dead(dead, np.tile(nlive - np.arange(b), nd // b), live_lnl=live)
+            assert old["lnz"] - exact > 4 * sig, (seed, old["lnz"], exact, sig)
 
 
 def test_evidence_from_dead_accounting_small_cases():
@@ -86,6 +131,12 @@ def test_evidence_from_dead_accounting_small_cases():
     # -inf points carry no weight but still shrink X
     r = nested.evidence_from_dead([-math.inf, 0.0], [3, 2])
     assert abs(math.exp(r["lnz"]) - math.exp(-1 / 3) * (1 - math.exp(-0.5))) < 1e-14
+    assert r["plateau_var"] == 1 / 9 and r["lnz_err"] == math.sqrt(r["info"] / 3 + 1 / 9)
+    # the plateau is counted without replacement across batches; finite points keep the per-batch rule
+    inf = -math.inf
+    seq = nested.nlive_sequence([inf, inf, inf, inf, inf, 1.0, 2.0, 3.0], 10, 3)
+    assert seq.tolist() == [10, 9, 8, 7, 6, 8, 10, 9]
+    assert nested.nlive_sequence([1.0, 2.0, 3.0, 4.0], 5, 2).tolist() == [5, 4, 5, 4]
 
 
 # ---- 2. sens.py:34-108 paramsets, scale list and output paths ----------------------------------------------------------------
