@@ -358,20 +358,31 @@ __global__ __launch_bounds__(GF_BLOCK) void k_haar(const GfCommon c, uint64_t se
 // Flavor-triangle histogram of a block of compositions: the reduction golemflavor/plot.py:365-370 does
 // with np.histogramdd(frs, bins=(nb, nb, nb), range=((0,1),)*3): nb equal bins per axis on [0, 1], the
 // last bin closed on the right, samples outside the cube (or NaN) dropped.  counts is [nb][nb][nb].
+// The bin is numpy's, edge for edge: np.linspace(0, 1, nb + 1) has edge(k) = k * (1.0 / nb), one rounded
+// product, and searchsorted(side="right") puts v in the bin b with edge(b) <= v < edge(b + 1).  (int)(v * nb)
+// is a first guess that can sit one bin off for v on an edge or within an ulp of one (nb = 5, v = 0.6:
+// 0.6 * 5 == 3.0, but edge(3) == 0.6000000000000001, so numpy's bin is 2); it is moved down when
+// v < edge(b) and up when v >= edge(b + 1).  step is an IEEE division and each edge a single __dmul_rn,
+// so nothing is contracted or approximated.
 __global__ __launch_bounds__(GF_BLOCK) void k_flavor_hist(const double* __restrict__ fr, int64_t n, int nb,
                                                           unsigned long long* __restrict__ counts)
 {
     const int64_t stride = (int64_t)gridDim.x * GF_BLOCK;
     const double scale = (double)nb;
+    const double step = __ddiv_rn(1.0, scale);
     for (int64_t i = (int64_t)blockIdx.x * GF_BLOCK + threadIdx.x; i < n; i += stride) {
         int idx[3];
         bool ok = true;
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
             const double v = fr[3 * i + a];
-            ok = ok && (v >= 0.0) && (v <= 1.0);
-            int b = (int)(v * scale);
-            idx[a] = b >= nb ? nb - 1 : b;
+            const bool in = (v >= 0.0) && (v <= 1.0);
+            ok = ok && in;
+            int b = in ? (int)(v * scale) : 0;                 // no conversion of NaN or inf to int
+            b = b >= nb ? nb - 1 : b;                          // v == 1.0: the last bin
+            if (v < __dmul_rn((double)b, step)) b -= 1;
+            else if (b + 1 < nb && v >= __dmul_rn((double)(b + 1), step)) b += 1;
+            idx[a] = b;
         }
         if (ok) atomicAdd(counts + ((int64_t)idx[0] * nb + idx[1]) * nb + idx[2], 1ull);
     }
