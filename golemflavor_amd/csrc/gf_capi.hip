@@ -1825,6 +1825,45 @@ int gf_internal_uni_residuals(gf_model* m, const double* d_theta, int layout, in
     return GF_OK;
 }
 
+// internal, test hook (tests/test_gpu_x87_device.py): the model's own inputs of the emulated-x87 chain as the kernels read them --
+// smu / npu split into (hi, lo) (18 doubles each, row-major (re, im) pairs), inv2e and epow (nbins doubles each; *nbins <- the count)
+int gf_internal_bsm_tables(gf_model* m, double* smu_hi, double* smu_lo, double* npu_hi, double* npu_lo, double* inv2e, double* epow,
+                           int* nbins)
+{
+    if (!m || !smu_hi || !smu_lo || !npu_hi || !npu_lo || !inv2e || !epow || !nbins || m->c.mode != GF_MODE_BSM_GAUSS) return GF_ERR_INVALID_ARG;
+    const GfBsm& b = m->hb;
+    std::memcpy(smu_hi, b.smu_hi, sizeof(b.smu_hi)); std::memcpy(smu_lo, b.smu_lo, sizeof(b.smu_lo));
+    std::memcpy(npu_hi, b.npu_hi, sizeof(b.npu_hi)); std::memcpy(npu_lo, b.npu_lo, sizeof(b.npu_lo));
+    std::memcpy(inv2e, b.inv2e, sizeof(double) * b.nbins); std::memcpy(epow, b.epow, sizeof(double) * b.nbins);
+    *nbins = b.nbins;
+    return GF_OK;
+}
+
+// internal, test hook (tests/test_gpu_x87_device.py): the primitives of gf_x87.hpp on device arrays (k_x87_eval, gf_unitarity.hip).
+// op 0-3, 8: a, b -> one pair; 4, 6, 7: a -> one pair; 5: a -> two pairs; 9: n doubles ahi -> ohi; 10: 4 n doubles ahi -> 18 n pairs.
+// All arrays are device pointers; synchronous.
+int gf_internal_x87_eval(int device, int op, int64_t n, const double* d_ahi, const double* d_alo, const double* d_bhi, const double* d_blo,
+                         double* d_ohi, double* d_olo)
+{
+    if (op < 0 || op > 10 || n < 0 || !d_ahi || !d_ohi) return GF_ERR_INVALID_ARG;
+    if (op != 9 && op != 10 && !d_alo) return GF_ERR_INVALID_ARG;
+    if (op != 9 && !d_olo) return GF_ERR_INVALID_ARG;
+    if ((op <= 3 || op == 8) && (!d_bhi || !d_blo)) return GF_ERR_INVALID_ARG;
+    if (n == 0) return GF_OK;
+    int cus = 0;
+    const int rc = pool_device(device, &cus);
+    if (rc != GF_OK) return rc;
+    GF_HIP(hipSetDevice(device));
+    hipStream_t st = nullptr;
+    GF_HIP(pool_stream(device, &st));
+    const bool two = op <= 3 || op == 8;
+    hipError_t e = gf_launch_x87_eval(op, n, d_ahi, d_alo, two ? d_bhi : nullptr, two ? d_blo : nullptr, d_ohi, d_olo, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    pool_release(device, st, nullptr);
+    if (e != hipSuccess) return hip_fail(e, "x87 eval");
+    return GF_OK;
+}
+
 // internal (gf_sampler.hip): the same report for launches the sampler put on `stream` and has just synchronised
 int gf_internal_check_overflow(int device, void* stream)
 {

@@ -36,6 +36,8 @@ hipError_t gf_launch_cube_to_theta(const GfCommon& c, int nscan, const int32_t* 
 // test hook (gf_unitarity.hip): emulated-x87 residuals of explicit (walker, bin) pairs; which = 0 serial chain, 1 three-lane groups
 hipError_t gf_launch_uni_debug(const GfCommon* d_common, const GfBsm* d_bsm, const double* theta, int layout, int64_t n, const int64_t* walkers,
                                const int32_t* bins, int64_t npairs, int which, double* out, hipStream_t s);
+hipError_t gf_launch_x87_eval(int op, int64_t n, const double* ahi, const double* alo, const double* bhi, const double* blo, double* ohi,
+                              double* olo, hipStream_t s);
 
 // ---- the device sampler's settlement of undecided proposals (gf_sampler.hip -> gf_unitarity.hip) ---------------------------
 // Step counters of the device sampler (live on the device so that a captured hipGraph can be replayed with constant kernel

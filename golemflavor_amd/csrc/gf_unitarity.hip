@@ -330,6 +330,45 @@ __global__ __launch_bounds__(64) void k_uni_debug_serial(const GfCommon* __restr
     }
 }
 
+// test hook (gf_internal_x87_eval): the primitives of gf_x87.hpp on explicit operands, compiled here with this file's flags and
+// inlining; tests/x87/x87_host.cpp (x87t_apply) is the host build of the same calls: op 0 add, 1 sub, 2 mul, 3 div, 4 sqrt(|a|),
+// 5 sincos (2 pairs out per operand), 6 asin, 7 acos, 8 hypot, 9 cr_pow10 (ahi -> ohi), 10 angles_to_u (ahi[4 i ..] -> 18 pairs)
+__global__ __launch_bounds__(64) void k_x87_eval(int op, int64_t n, const double* __restrict__ ahi, const double* __restrict__ alo,
+                                                 const double* __restrict__ bhi, const double* __restrict__ blo, double* __restrict__ ohi,
+                                                 double* __restrict__ olo)
+{
+    for (int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 64) {
+        if (op == 9) { ohi[i] = cr_pow10(ahi[i]); continue; }
+        if (op == 10) {
+            double ang[4];
+            for (int q = 0; q < 4; ++q) ang[q] = ahi[4 * i + q];
+            cx87 u[3][3];
+            angles_to_u(ang, u);
+            for (int k = 0; k < 9; ++k) {
+                const x87 re = u[k / 3][k % 3].re, im = u[k / 3][k % 3].im;
+                ohi[18 * i + 2 * k] = re.hi; olo[18 * i + 2 * k] = re.lo; ohi[18 * i + 2 * k + 1] = im.hi; olo[18 * i + 2 * k + 1] = im.lo;
+            }
+            continue;
+        }
+        const x87 a = {ahi[i], alo[i]};
+        const x87 b = bhi ? x87{bhi[i], blo[i]} : x_from(0.0);
+        x87 r = x_from(0.0), r2 = x_from(0.0);
+        switch (op) {
+        case 0: r = x_add(a, b); break;
+        case 1: r = x_sub(a, b); break;
+        case 2: r = x_mul(a, b); break;
+        case 3: r = x_div(a, b); break;
+        case 4: r = x_sqrt(x_abs(a)); break;
+        case 5: x_sincos(a, r, r2); break;
+        case 6: r = x_asin(a); break;
+        case 7: r = x_acos(a); break;
+        default: r = x_hypot(a, b); break;
+        }
+        if (op == 5) { ohi[2 * i] = r.hi; olo[2 * i] = r.lo; ohi[2 * i + 1] = r2.hi; olo[2 * i + 1] = r2.lo; }
+        else { ohi[i] = r.hi; olo[i] = r.lo; }
+    }
+}
+
 template <class Team>
 __global__ __launch_bounds__(UNI_BLOCK) void k_uni_debug_group(const GfCommon* __restrict__ cp, const GfBsm* __restrict__ tbp,
                                                                const double* __restrict__ theta, int layout, int64_t n,
@@ -462,5 +501,13 @@ hipError_t gf_launch_uni_resolve(const GfCommon* d_common, const GfBsm* d_bsm, c
         hipLaunchKernelGGL(k_uni_resolve<Team9>, dim3((unsigned)blocks), dim3(UNI_BLOCK), 0, s, d_common, d_bsm, theta, layout, n, lnprob, status, uq, wq, seen);
     else
         hipLaunchKernelGGL(k_uni_resolve<Team3>, dim3((unsigned)blocks), dim3(UNI_BLOCK), 0, s, d_common, d_bsm, theta, layout, n, lnprob, status, uq, wq, seen);
+    return hipGetLastError();
+}
+
+// test hook: k_x87_eval on device arrays (op and array sizes checked by the caller, gf_internal_x87_eval)
+hipError_t gf_launch_x87_eval(int op, int64_t n, const double* ahi, const double* alo, const double* bhi, const double* blo, double* ohi,
+                              double* olo, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_x87_eval, dim3(256), dim3(64), 0, s, op, n, ahi, alo, bhi, blo, ohi, olo);
     return hipGetLastError();
 }

@@ -21,38 +21,26 @@ REL = 1e-10
 ABS_FR = 1e-10
 
 
-_X87 = {}
-
-
-def _emulated_host_verdict(oracle, desc, row, edges, dim, tex):
-    """Non-unitary by the host build of gf_x87.hpp (tests/x87/x87_host.cpp, g++): the reference's chain, bin by bin, with the
-    SM matrix from the emulated functions and the texture's matrix in long double, as the device has them."""
+def _arbitrate(model, row, layout):
+    """Per-bin residuals of one walker by the host build of the device's own chain (tests/x87_harness.py: x87t_walker_residuals on
+    the model's own tables, sc2 by cr_pow10 as the device forms it) and by the device's serial chain (gf_internal_uni_residuals).
+    Returns (host residuals, device residuals)."""
     import ctypes as C
-    import math
-    import os
-    import subprocess
-    import tempfile
-    if "lib" not in _X87:
-        root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-        out = os.path.join(tempfile.mkdtemp(prefix="x87host"), "libx87host.so")
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-mfma", "-fPIC", "-shared", "-ffp-contract=off", "-o", out,
-                               os.path.join(root, "tests", "x87", "x87_host.cpp")])
-        L = C.CDLL(out)
-        L.x87t_bin_residual.restype = C.c_double
-        L.x87t_bin_residual.argtypes = [C.POINTER(C.c_double)] * 2 + [C.c_double] * 4 + [C.c_int, C.c_void_p, C.c_void_p]
-        _X87["lib"] = L
-    L = _X87["lib"]
-    z = 1e-9
-    tex_ang = {1: (0.5, 1.0, z, z), 2: (z, 0.25, z, z), 3: (z, 1.0, 0.5, z)}[int(tex.value)]
-    arr = lambda x: (C.c_double * len(x))(*[float(v) for v in x])
-    npu = np.zeros(18, dtype=np.longdouble)
-    oracle.lib().orc_angles_to_u_ldout(arr(tex_ang), npu.ctypes.data_as(C.c_void_p))
-    sm = [row[desc.idx_sm[q]] if desc.idx_sm[q] >= 0 else desc.sm_fixed[q] for q in range(4)]
-    mass = [row[desc.idx_mass[q]] if desc.idx_mass[q] >= 0 else desc.mass_fixed[q] for q in range(2)]
-    sc2 = math.pow(10., row[desc.idx_scale] if desc.idx_scale >= 0 else desc.scale_fixed)
-    centres = np.sqrt(edges[:-1] * edges[1:])
-    worst = max(L.x87t_bin_residual(arr(sm), arr(tex_ang), mass[0], mass[1], sc2, float(e), dim, None, npu.ctypes.data_as(C.c_void_p)) for e in centres)
-    return not (worst < 1e-7)
+    import x87_harness as H
+    L = H.build()
+    want = H.walker_residuals(L, model.desc, H.model_tables(model), row[None, :])[0]
+    nb = want.size
+    th = np.ascontiguousarray(row[None, :] if layout == GF_LAYOUT_AOS else row[:, None])
+    w, b = np.zeros(nb, dtype=np.int64), np.arange(nb, dtype=np.int32)
+    Lg = _lib.lib()
+    Lg.gf_internal_uni_residuals.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
+                                             C.c_void_p]
+    d_th, d_w, d_b, d_o = model.alloc(th.nbytes).upload(th), model.alloc(w.nbytes).upload(w), model.alloc(b.nbytes).upload(b), model.alloc(8 * nb)
+    _lib.check(Lg.gf_internal_uni_residuals(model._h, d_th.ptr, int(layout), 1, d_w.ptr, d_b.ptr, nb, 0, d_o.ptr), "uni residuals")
+    got = d_o.download((nb,))
+    for d in (d_th, d_w, d_b, d_o):
+        d.free()
+    return want, got
 
 
 def _random_paramset(rng):
@@ -204,9 +192,14 @@ def test_random_bsm_configurations(oracle, seed):
         # Arbitrate with the host build of the device's own chain (gf_x87.hpp: correctly rounded functions, the same on every
         # host; pinned to the x87 unit by tests/test_x87_emulation.py): the device must agree with THAT, and such walkers stay rare.
         assert differ.size <= 2, (seed, dim, tex, nbins, differ)
-        desc = compile_model(ps, "BSM_GAUSS", **kw)
-        for i in differ:
-            assert _emulated_host_verdict(oracle, desc, th[i], edges, dim, tex) == bool(flagged[i]), (seed, dim, tex, nbins, int(i), float(r80[i]))
+        import x87_harness as H
+        with Model(compile_model(ps, "BSM_GAUSS", **kw)) as m:
+            for i in differ:
+                want, got = _arbitrate(m, th[i], GF_LAYOUT_SOA if i % 2 else GF_LAYOUT_AOS)
+                print("seed %d d=%d %s bins=%d walker %d: oracle %.6e, host build %.6e, device %s" % (
+                    seed, dim, tex.name, nbins, int(i), float(r80[i]), float(np.max(want)), "non-unitary" if flagged[i] else "unitary"))
+                assert H.same_bits(got, want).all(), (seed, int(i), got, want)
+                assert bool(H.non_unitary(want[None, :])[0]) == bool(flagged[i]), (seed, dim, tex, nbins, int(i), float(r80[i]))
     assert np.mean(flagged[inbox] == ref_flagged[inbox]) >= 0.998, (seed, dim, tex, nbins)
     good = (ref_st == 0) & (st == 0)
     if good.any():

@@ -621,10 +621,12 @@ def test_bsm_sampler_unitarity_through_the_failing_region(oracle):
     arithmetic in emulated x87.  So with on_nonunitary='-inf' the chain is the chain of a host-driven run in which those
     proposals score -inf.  Checked against the numpy stretch move on the same Philox stream, evaluated by the ORACLE with the
     oracle's verdicts, proposal by proposal (the proposals bit-identical to the device's: its fused multiply-add is restated
-    exactly): every accept decision agrees, except where the oracle's residual lies within half a decade of 1e-7 -- there the
-    reference's own verdict is a property of its libm's last bits, the device's decision is adopted and
-    the comparison goes on.  The number of non-unitary proposals agrees up to those.  `raise` (the reference's behaviour):
-    the run dies."""
+    exactly): every accept decision agrees.  Where the oracle's residual lies within half a decade of 1e-7 the reference's own
+    verdict is a property of its libm's last bits; there the proposal's verdict is the host build of the
+    device's chain (tests/x87_harness.py: x87t_walker_residuals on the model's own tables), independent of the device, and the
+    device must take the same decision.  The number of non-unitary proposals agrees with the oracle's up to the band.  `raise`
+    (the reference's behaviour): the run dies."""
+    import x87_harness as H
     from fractions import Fraction
     inj = fr_utils.fr_to_angles((1, 1, 1))
     asimov, ps = Cf.fr_paramsets(6, inj)
@@ -648,6 +650,9 @@ def test_bsm_sampler_unitarity_through_the_failing_region(oracle):
     lp, st = oracle.lnprob_batch(om, pos, want_status=True)
     lnp = np.where(st == oracle.NON_UNITARY, -np.inf, lp)                # a start the reference would have died on
     nbad, nband, nforced, naccept = int(np.sum(st == oracle.NON_UNITARY)), 0, 0, 0
+    hx = H.build()
+    tables = H.model_tables(f.model)
+    nflip = 0                                                            # band proposals on which the harness overrules the oracle
     key = (seed & 0xffffffff, seed >> 32)
     for it in range(nsteps):
         for half in (0, 1):
@@ -667,7 +672,16 @@ def test_bsm_sampler_unitarity_through_the_failing_region(oracle):
             lq, sq = oracle.lnprob_batch(om, q, want_status=True)
             res = oracle.unitarity_residual_batch(om, q)
             band = (sq != oracle.OUT_OF_PRIOR) & (res > 10 ** -7.25) & (res < 10 ** -6.75)
-            lq = np.where(sq == oracle.NON_UNITARY, -np.inf, lq)
+            bad = sq == oracle.NON_UNITARY
+            if band.any():
+                hbad = H.non_unitary(H.walker_residuals(hx, f.model.desc, tables, q[band]))
+                flip = np.flatnonzero(band)[hbad != bad[band]]
+                nflip += flip.size
+                acquit = flip[~hbad[hbad != bad[band]]]
+                if acquit.size:                                          # the oracle did not finish these: the model's value
+                    lq[acquit] = f.model.lnprob(q[acquit])[0]
+                bad[band] = hbad
+            lq = np.where(bad, -np.inf, lq)
             nbad += int(np.sum(sq == oracle.NON_UNITARY))
             nband += int(band.sum())
             idx = np.arange(half * nhalf, (half + 1) * nhalf)
@@ -676,18 +690,19 @@ def test_bsm_sampler_unitarity_through_the_failing_region(oracle):
             want = np.where(acc[:, None], q, pos[idx])
             dev = got[it][idx]
             differ = np.abs(dev - want).max(axis=1) > 1e-12
-            assert not np.any(differ & ~band), "step %d half %d: decisions differ outside the band (residuals %s)" % (it, half, res[differ & ~band])
+            assert not np.any(differ), "step %d half %d: decisions differ (residuals %s, band %s)" % (it, half, res[differ], band[differ])
             nforced += int(differ.sum())
             pos[idx] = dev                                                # (= want wherever they agree)
             lnp[idx] = np.where(differ, got_lnp[it][idx], np.where(acc, lq, lnp[idx]))
             naccept += int(acc.sum())
     assert nbad > 500 and naccept > 200                                  # the chain does live in the failing region, and moves
-    assert nforced <= nband and abs(nbad_dev - nbad) <= nband, (nbad_dev, nbad, nband, nforced)
+    print("band proposals %d, harness verdict differs from the oracle's on %d" % (nband, nflip))
+    assert nforced == 0 and nflip <= nband and abs(nbad_dev - nbad) <= nband, (nbad_dev, nbad, nband, nforced, nflip)
     assert np.allclose(smp.state[1], lnp, rtol=1e-10)
     # no stored sample is one the reference would have died on, except a start position that never moved (or a band case)
     st = oracle.lnprob_batch(om, got.reshape(-1, ndim), want_status=True)[1].reshape(nsteps, nw)
     moved = np.any(got != p0[None], axis=2)
-    assert np.sum((st == oracle.NON_UNITARY) & moved) <= nforced * nsteps
+    assert np.sum((st == oracle.NON_UNITARY) & moved) <= nflip * nsteps
     smp.close()
     g = llh_utils.bsm_ln_prob(args, asimov, ps, smearing=0.3)              # on_nonunitary="raise", the reference's behaviour
     smp = mcmc_utils.DeviceEnsembleSampler(nw, ndim, g, seed=seed)

@@ -6,16 +6,14 @@ the whole chain, with the oracle, whose residual is the reference's bit for bit 
 The host build is test infrastructure: the product never evaluates this code on the CPU."""
 import ctypes as C
 import math
-import os
 import platform
-import subprocess
 
 import numpy as np
 import pytest
 
+import x87_harness as H
 from common import BIN_EDGES
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.skipif(platform.machine() != "x86_64", reason="needs the x87 unit as the reference")
 LD = np.longdouble
 Z = 1e-9
@@ -24,14 +22,7 @@ TEX = {1: (0.5, 1.0, Z, Z), 2: (Z, 0.25, Z, Z), 3: (Z, 1.0, 0.5, Z)}
 
 @pytest.fixture(scope="module")
 def x87lib(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("x87") / "libx87host.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-mfma", "-fPIC", "-shared", "-ffp-contract=off", "-o", out,
-                           os.path.join(ROOT, "tests", "x87", "x87_host.cpp")])
-    L = C.CDLL(out)
-    L.x87t_bin_residual.restype = C.c_double
-    L.x87t_pow10.argtypes = [C.c_uint64, C.c_int, C.c_double, C.c_double]
-    L.x87t_bin_residual.argtypes = [C.POINTER(C.c_double)] * 2 + [C.c_double] * 4 + [C.c_int, C.c_void_p, C.c_void_p]
-    return L
+    return H.build(str(tmp_path_factory.mktemp("x87")))
 
 
 def _arr(x):
@@ -52,10 +43,7 @@ def test_round4_primitives_equal_round3s(x87lib, tmp_path):
     in 11 floating-point operations instead of 20; gf_x87.hpp).  Both forms on the same 48 M operand pairs -- random, cancelling,
     ties and near-ties 42-64 binades apart, sums under a power of two, short significands: the same digest of all results, and
     not one result that differs from the x87 unit's."""
-    out = str(tmp_path / "libx87host_r3.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-mfma", "-fPIC", "-shared", "-ffp-contract=off", "-DGFX87_ROUND64_R3", "-o", out,
-                           os.path.join(ROOT, "tests", "x87", "x87_host.cpp")])
-    old = C.CDLL(out)
+    old = H.build(str(tmp_path), ("GFX87_ROUND64_R3",))
     for L in (x87lib, old):
         L.x87t_digest.restype = C.c_uint64
         L.x87t_digest.argtypes = [C.c_uint64, C.c_int64, C.POINTER(C.c_int64)]
@@ -70,10 +58,7 @@ def test_round4_primitives_equal_round3s(x87lib, tmp_path):
 def test_round4_chain_residuals_equal_round3s(golden, x87lib, tmp_path):
     """The same A/B through the whole chain (angles_to_u with the emulated functions, both sandwiches, the Cardano chain, |X X^+|):
     the residual of 160 G17 rows x 20 energy bins, bit for bit the same double from both forms of the primitives."""
-    out = str(tmp_path / "libx87host_r3.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-mfma", "-fPIC", "-shared", "-ffp-contract=off", "-DGFX87_ROUND64_R3", "-o", out,
-                           os.path.join(ROOT, "tests", "x87", "x87_host.cpp")])
-    old = C.CDLL(out)
+    old = H.build(str(tmp_path), ("GFX87_ROUND64_R3",))
     old.x87t_bin_residual.restype = C.c_double
     old.x87t_bin_residual.argtypes = x87lib.x87t_bin_residual.argtypes
     rows = golden["g17_rows"]
@@ -99,10 +84,7 @@ def test_exact_shortcuts_of_the_three_lane_chain(golden, x87lib, tmp_path):
     the diagonal of |X X^+| is a sum of squares and its own modulus).  The serial chain with the same shortcuts switched on
     (-DGFX87_SHORT_A/B/C) gives the same residual, bit for bit, on 300 G17 rows x 20 bins; on the device the three-lane chain is
     compared with the serial one (tests/test_gpu_unitarity_r3.py)."""
-    out = str(tmp_path / "libx87host_short.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-mfma", "-fPIC", "-shared", "-ffp-contract=off", "-DGFX87_SHORT_A", "-DGFX87_SHORT_B",
-                           "-DGFX87_SHORT_C", "-o", out, os.path.join(ROOT, "tests", "x87", "x87_host.cpp")])
-    short = C.CDLL(out)
+    short = H.build(str(tmp_path), ("GFX87_SHORT_A", "GFX87_SHORT_B", "GFX87_SHORT_C"))
     short.x87t_bin_residual.restype = C.c_double
     short.x87t_bin_residual.argtypes = x87lib.x87t_bin_residual.argtypes
     rows = golden["g17_rows"]
@@ -230,3 +212,81 @@ def test_chain_residual_vs_oracle(golden, oracle, x87lib):
     assert exact["host"] / tot > 0.95 and exact["emu"] / tot > 0.75, exact
     assert worst["host"] < 0.35 and worst["emu"] < 0.35, worst          # a factor ~2 at most
     assert verdict_diff <= 2
+
+
+def _in_domain(*xs):
+    """Where a double-double evaluation can hold a 64-bit significand: every value zero or of magnitude in [2^-960, 2^1020]
+    (below, the error terms of the error-free transformations turn subnormal; gf_x87.hpp's round64 passes values under 2^-1011
+    through unrounded).  The chain's quantities lie within 2^-300 .. 2^300."""
+    ok = np.ones(len(xs[0]), dtype=bool)
+    for x in xs:
+        a = np.abs(x)
+        ok &= (a == 0) | ((a >= LD(2.0) ** -960) & (a <= LD(2.0) ** 1020))
+    return ok
+
+
+def test_apply_equals_the_x87_unit_on_the_operand_stream(x87lib):
+    """x87t_apply -- the entry point whose arrays the device build (gf_internal_x87_eval) takes too -- on x87t_arith's operand
+    stream (x87t_operands, 2 x 800 000 pairs) equals the x87 unit for + - * / sqrt, as values, on every pair.  The structured
+    extras (+-0, +-inf, NaN, the extreme normal doubles, subnormal lo parts, every pair of them): equal where operands and result
+    lie in the emulated range; where the x87 unit's result is inf or NaN, the emulation's is not finite either (it reports NaN,
+    which the chain turns into "not unitary")."""
+    for seed in (1, 2):
+        ops = H.operands(x87lib, seed, 800000)
+        n_extra = len(ops[0]) - 800000
+        assert n_extra >= 400
+        for op in ("add", "sub", "mul", "div", "sqrt"):
+            args = ops if op != "sqrt" else ops[:2]
+            (o, x) = H.apply(x87lib, op, *args, want_x87=True)
+            with np.errstate(invalid="ignore"):
+                got = o[0].astype(LD) + o[1].astype(LD)
+                want = x[0].astype(LD) + x[1].astype(LD)
+                a = ops[0].astype(LD) + ops[1].astype(LD)
+                b = ops[2].astype(LD) + ops[3].astype(LD)
+            same = (got == want) | (np.isnan(got) & np.isnan(want))
+            stream, extra = slice(0, 800000), slice(800000, None)
+            assert same[stream].all(), (seed, op, int((~same[stream]).sum()))
+            fin = np.isfinite(want[extra])
+            dom = fin & _in_domain(a[extra], b[extra], want[extra])
+            assert same[extra][dom].all(), (seed, op, np.flatnonzero(dom & ~same[extra]))
+            assert not np.isfinite(got[extra][~fin]).any(), (seed, op)
+            assert dom.sum() >= 30, (op, int(dom.sum()))
+
+
+def test_walker_residuals_restate_bin_residual(golden, x87lib, oracle):
+    """x87t_walker_residuals (walker_terms + walker_bin_residual of gf_unitarity_teams.hpp, all bins of a walker in one call, from a
+    model's column indices and tables) equals x87t_bin_residual pair by pair given the same sc2 (cr_pow10 of the scale) and matrices,
+    bit for bit: SM angles sampled (emulated angles_to_u) or fixed (the long-double matrix split into hi / lo), texture matrices."""
+    from types import SimpleNamespace
+    from golemflavor_amd.enums import Texture
+    LO = oracle.lib()
+    x87lib.x87t_pow10_value.restype = C.c_double
+    x87lib.x87t_pow10_value.argtypes = [C.c_double]
+    rows = golden["g17_rows"]
+    centres = np.sqrt(BIN_EDGES[:-1] * BIN_EDGES[1:])
+    rng = np.random.default_rng(9)
+    nb = big = 0
+    for i in rng.permutation(len(rows))[:60]:
+        r = rows[i]
+        dim, tex, th = int(r[0]), int(r[1]), np.array(r[2:], dtype=float)
+        npu = np.zeros(18, dtype=LD)
+        LO.orc_angles_to_u_ldout(_arr(TEX[tex]), npu.ctypes.data_as(C.c_void_p))
+        smu = np.zeros(18, dtype=LD)
+        LO.orc_angles_to_u_ldout(_arr(th[:4]), smu.ctypes.data_as(C.c_void_p))
+        split = lambda u: (u.astype(np.float64), (u - u.astype(np.float64).astype(LD)).astype(np.float64))
+        tables = dict(zip(("smu_hi", "smu_lo"), split(smu)))
+        tables.update(zip(("npu_hi", "npu_lo"), split(npu)))
+        tables["inv2e"] = 1. / (2 * centres)
+        tables["epow"] = np.array([math.pow(e, dim - 3) for e in centres])
+        sc2 = x87lib.x87t_pow10_value(th[6])
+        for sampled in (True, False):
+            desc = SimpleNamespace(idx_sm=[0, 1, 2, 3] if sampled else [-1] * 4, idx_mass=[4, 5], mass_fixed=[0., 0.], idx_mm=[-1] * 4,
+                                   texture=Texture(tex).value, idx_scale=6, scale_fixed=0.)
+            got = H.walker_residuals(x87lib, desc, tables, th[None, :])[0]
+            for k, e in enumerate(centres):
+                want = x87lib.x87t_bin_residual(_arr(th[:4]), _arr(TEX[tex]), th[4], th[5], sc2, e, dim,
+                                                None if sampled else smu.ctypes.data_as(C.c_void_p), npu.ctypes.data_as(C.c_void_p))
+                assert H.same_bits(got[k], want), (i, sampled, k, got[k], want)
+                nb += 1
+                big += int(want > 1e-12)
+    assert nb == 2400 and big > 500

@@ -204,4 +204,134 @@ double x87t_bin_residual(const double sm_ang[4], const double np_ang[4], double 
     return bin_residual(hsm, hnp, 1. / (2 * energy), pow(energy, (double)(dim - 3)));
 }
 
+// ---- the same operations on explicit operands, for the device build of the header (tests/test_gpu_x87_device.py) ----------------
+// The operand stream of x87t_arith (its five kinds, in the same order from the same seed) as (hi, lo) pairs, followed by
+// structured extras: +-0, +-inf, NaN, +-1, the largest and smallest normal doubles, values whose lo part is subnormal, and every
+// pair of them.  Returns the number of pairs; with ahi == NULL only counts.
+static void extras(ld* v, int* nv)
+{
+    int k = 0;
+    v[k++] = 0.0L; v[k++] = -0.0L; v[k++] = (ld)INFINITY; v[k++] = -(ld)INFINITY; v[k++] = (ld)NAN;
+    v[k++] = 1.0L; v[k++] = -1.0L; v[k++] = 1.0L + ldexpl(1.0L, -52); v[k++] = 3.0L; v[k++] = -0.75L - ldexpl(1.0L, -63);
+    v[k++] = (ld)1.7976931348623157e308; v[k++] = (ld)2.2250738585072014e-308;
+    // a 64-bit significand at 2^-1000 .. 2^-1010: the lo part lies below 2^-1022, a subnormal double
+    uint64_t s = 77;
+    for (int e = 1000; e <= 1010; e += 2) {
+        const ld x = ldexpl((ld)(sm64(s) | 0x8000000000000000ull), -e - 63);
+        v[k++] = x; v[k++] = -x * 1.5L;
+    }
+    *nv = k;
+}
+int64_t x87t_operands(uint64_t seed, int64_t n, double* ahi, double* alo, double* bhi, double* blo)
+{
+    ld v[64];
+    int nv = 0;
+    extras(v, &nv);
+    const int64_t total = n + (int64_t)nv * nv;
+    if (!ahi) return total;
+    uint64_t s = seed;
+    auto put = [&](int64_t i, ld a, ld b) {
+        const x87 xa = from_ld(a), xb = from_ld(b);
+        ahi[i] = xa.hi; alo[i] = xa.lo; bhi[i] = xb.hi; blo[i] = xb.lo;
+    };
+    for (int64_t it = 0; it < n; ++it) {                                   // exactly x87t_arith's stream
+        ld a, b;
+        const int kind = (int)(it % 8);
+        if (kind == 0) { a = rnd_ld(s, 40); b = a * (1.0L + ldexpl((ld)(sm64(s) % 4096), -60)); b = -b; }
+        else if (kind == 1) { a = rnd_ld(s, 2); b = (ld)(1 + sm64(s) % 60); }
+        else if (kind == 2) { a = rnd_ld(s, 5); b = rnd_ld(s, 5) * ldexpl(1.0L, -(int)(sm64(s) % 80)); }
+        else if (kind == 3) { a = (ld)(double)rnd_ld(s, 30); b = (ld)(double)rnd_ld(s, 30); }
+        else { a = rnd_ld(s, 60); b = rnd_ld(s, 60); }
+        put(it, a, b);
+    }
+    for (int i = 0; i < nv; ++i)
+        for (int j = 0; j < nv; ++j) put(n + (int64_t)i * nv + j, v[i], v[j]);
+    return total;
+}
+
+// The host build's results of operation `op` on n operands (the device's gf_internal_x87_eval takes the same arrays):
+//   0 add, 1 sub, 2 mul, 3 div (a, b -> 1 pair), 4 sqrt(|a|) (a -> 1 pair), 5 sincos (a -> sin, cos: 2 pairs per operand),
+//   6 asin, 7 acos (a -> 1 pair), 8 hypot (a, b -> 1 pair), 9 cr_pow10 (ahi -> ohi), 10 angles_to_u (ahi[4 i .. 4 i + 3] ->
+//   18 pairs per operand: the matrix row-major, (re, im)).
+// For ops 0-4, xhi / xlo (may be NULL) get the x87 unit's result on the same operands, split as from_ld.
+int x87t_apply(int op, int64_t n, const double* ahi, const double* alo, const double* bhi, const double* blo, double* ohi, double* olo,
+               double* xhi, double* xlo)
+{
+    for (int64_t i = 0; i < n; ++i) {
+        if (op == 9) { ohi[i] = cr_pow10(ahi[i]); continue; }
+        if (op == 10) {
+            cx87 u[3][3];
+            angles_to_u(ahi + 4 * i, u);
+            for (int k = 0; k < 9; ++k) {
+                const x87 re = u[k / 3][k % 3].re, im = u[k / 3][k % 3].im;
+                ohi[18 * i + 2 * k] = re.hi; olo[18 * i + 2 * k] = re.lo; ohi[18 * i + 2 * k + 1] = im.hi; olo[18 * i + 2 * k + 1] = im.lo;
+            }
+            continue;
+        }
+        const x87 a = {ahi[i], alo[i]};
+        const x87 b = bhi ? x87{bhi[i], blo[i]} : x_from(0.0);
+        x87 r = x_from(0.0), r2 = x_from(0.0);
+        ld want = 0.0L;
+        const ld la = to_ld(a), lb = to_ld(b);
+        switch (op) {
+        case 0: r = x_add(a, b); want = la + lb; break;
+        case 1: r = x_sub(a, b); want = la - lb; break;
+        case 2: r = x_mul(a, b); want = la * lb; break;
+        case 3: r = x_div(a, b); want = la / lb; break;
+        case 4: r = x_sqrt(x_abs(a)); want = sqrtl(fabsl(la)); break;
+        case 5: x_sincos(a, r, r2); break;
+        case 6: r = x_asin(a); break;
+        case 7: r = x_acos(a); break;
+        case 8: r = x_hypot(a, b); break;
+        default: return 1;
+        }
+        if (op == 5) { ohi[2 * i] = r.hi; olo[2 * i] = r.lo; ohi[2 * i + 1] = r2.hi; olo[2 * i + 1] = r2.lo; }
+        else { ohi[i] = r.hi; olo[i] = r.lo; }
+        if (op <= 4 && xhi) { const x87 w = from_ld(want); xhi[i] = w.hi; xlo[i] = w.lo; }
+    }
+    return 0;
+}
+
+// walker_terms + walker_bin_residual (gf_unitarity_teams.hpp) restated line by line: every bin's residual of nw walkers (theta
+// rows of ndim doubles, row-major) -> out[w * nbins + k].  The column indices and fixed values are the model's (GfCommon), the
+// tables its own (GfBsm: smu / npu split into hi / lo, inv2e, epow), read back from the device; tex_none: texture NONE.
+int x87t_walker_residuals(int64_t nw, int ndim, const double* theta, const int* idx_sm, const int* idx_mass, const double* mass_fixed,
+                          const int* idx_mm, int tex_none, int idx_scale, double scale_fixed, const double* smu_hi, const double* smu_lo,
+                          const double* npu_hi, const double* npu_lo, int nbins, const double* inv2e, const double* epow, double* out)
+{
+    auto load = [](const double* hi, const double* lo, cx87 u[3][3]) {
+        for (int k = 0; k < 9; ++k) {
+            const x87 re = {hi[2 * k], lo[2 * k]}, im = {hi[2 * k + 1], lo[2 * k + 1]};
+            u[k / 3][k % 3] = c_make(re, im);
+        }
+    };
+    for (int64_t i = 0; i < nw; ++i) {
+        const double* row = theta + i * ndim;
+        cx87 u[3][3], hsm[3][3], hnp[3][3];
+        if (idx_sm[0] >= 0) {
+            double ang[4];
+            for (int q = 0; q < 4; ++q) ang[q] = row[idx_sm[q]];
+            angles_to_u(ang, u);
+        } else {
+            load(smu_hi, smu_lo, u);
+        }
+        const double m21 = idx_mass[0] >= 0 ? row[idx_mass[0]] : mass_fixed[0];
+        const double m3x = idx_mass[1] >= 0 ? row[idx_mass[1]] : mass_fixed[1];
+        sandwich(u, m21, m3x, hsm);
+        if (tex_none && idx_mm[0] >= 0) {
+            double ang[4];
+            for (int q = 0; q < 4; ++q) ang[q] = row[idx_mm[q]];
+            angles_to_u(ang, u);
+        } else {
+            load(npu_hi, npu_lo, u);
+        }
+        const double ll = idx_scale >= 0 ? row[idx_scale] : scale_fixed;
+        const double sc2 = cr_pow10(ll);
+        const double sc1 = sc2 / 100.0;
+        sandwich(u, sc1, sc2, hnp);
+        for (int k = 0; k < nbins; ++k) out[i * nbins + k] = bin_residual(hsm, hnp, inv2e[k], epow[k]);
+    }
+    return 0;
+}
+
 }  // extern "C"
