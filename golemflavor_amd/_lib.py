@@ -132,6 +132,16 @@ SIGNATURES = {
     "gf_nested_run": (C.c_int, [_vp, C.c_int64]),
     "gf_nested_result": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_uint32), _ip]),
     "gf_nested_get_dead": (C.c_int, [_vp, C.c_int, C.c_int64, _dp, _dp, _dp, C.POINTER(C.c_int64)]),
+    "gf_simplex_create": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, _ip, _dp, C.c_int, C.c_int, C.c_uint64, C.c_int,
+                                    C.POINTER(_vp)]),
+    "gf_simplex_set_run_ids": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+    "gf_simplex_set_starts": (C.c_int, [_vp, C.c_int, _dp]),
+    "gf_simplex_set_options": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int]),
+    "gf_simplex_destroy": (None, [_vp]),
+    "gf_simplex_run": (C.c_int, [_vp, C.c_int64]),
+    "gf_simplex_result": (C.c_int, [_vp, _dp, _dp, _ip, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                    C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _ip]),
+    "gf_simplex_get_starts": (C.c_int, [_vp, C.c_int, _dp, _dp, _ip, C.POINTER(C.c_int64)]),
 }
 
 _lib = None

@@ -71,6 +71,8 @@ struct GfSettleArgs {
     const GfBsm* const* tbs;    // [nchains] (multi != 0), else null
     const GfBsm* tb;            // multi == 0
     int32_t multi;
+    union {
+        struct {
     // the nested sampler's variant (gf_launch_nested_settle; unused by the stretch move): walker t = run * batch + slot,
     // nchains = runs, nwalkers = 2 * batch, multi = 1; an accepted proposal moves ns_prop_u [t][ns_nscan] into ns_wu
     const double* ns_lstar;     // [runs] L* of the current iteration
@@ -81,6 +83,16 @@ struct GfSettleArgs {
     uint32_t* ns_wev;           // [runs * batch] evaluated steps
     uint32_t* ns_nonunit;       // [runs] proposals the reference would have raised on
     int32_t ns_nscan;
+        };
+        struct {
+    // the maximiser's variant (gf_launch_simplex_settle), in the same bytes: candidate t = run * (nwalkers / 2) + slot,
+    // nchains = runs, multi = 1; the settled candidate's lnprob and verdict (0 or GF_ST_NON_UNITARY) go to sx_lnq[t] and
+    // sx_status[t]
+    double* sx_lnq;
+    int32_t* sx_status;
+        };
+    };
 };
 hipError_t gf_launch_stretch_settle(const GfSettleArgs& a, int cus, hipStream_t s);
 hipError_t gf_launch_nested_settle(const GfSettleArgs& a, int cus, hipStream_t s);
+hipError_t gf_launch_simplex_settle(const GfSettleArgs& a, int cus, hipStream_t s);

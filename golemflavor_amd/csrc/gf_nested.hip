@@ -444,30 +444,6 @@ __global__ __launch_bounds__(GF_BLOCK) void k_ns_commit(const NsArgs a)
     }
 }
 
-// Lanes per walker of a step of `walkers` BSM walkers (the cost model of gf_sampler.hip's lanes_per_walker, restricted to the
-// instances compiled here); GF_NESTED_LPW forces one.  Any choice gives the same bits.
-int ns_lanes_per_walker(int mode, int64_t walkers, int nbins_max, int cus)
-{
-    if (mode != MODE_BSM_GAUSS || nbins_max < 2) return 1;
-    const char* force = gf_internal_env("GF_NESTED_LPW", 0);
-    if (force) { const int f = std::atoi(force); if (f == 1 || f == 4 || f == 16) return f; }
-    const int64_t simds = (int64_t)(cus > 0 ? cus : 256) * 4;
-    int best = 1;
-    double best_cost = 0.0;
-    for (int lpw : {1, 4, 16}) {
-        const size_t lds = (size_t)(GF_BLOCK / lpw) * GF_FGRP_DOUBLES(nbins_max, lpw) * sizeof(double);
-        if (lpw > 1 && lds > 32 * 1024) continue;
-        const int64_t waves = (walkers * lpw + GF_WAVE - 1) / GF_WAVE;
-        const int64_t per_simd = (waves + simds - 1) / simds;
-        const int64_t wv = per_simd < 3 ? per_simd : 3;
-        const int64_t rounds = (waves + simds * 3 - 1) / (simds * 3);
-        const double interval = 4.0 * (double)wv > 7.0 ? 4.0 * (double)wv : 7.0;
-        const double cost = (double)rounds * (2000.0 + 400.0 * (double)((nbins_max + lpw - 1) / lpw)) * interval;
-        if (lpw == 1 || cost < best_cost) { best = lpw; best_cost = cost; }
-    }
-    return best;
-}
-
 template <int MODE, int LPW>
 hipError_t launch_walk(const NsArgs& a, hipStream_t st)
 {
@@ -732,7 +708,7 @@ int gf_nested_run(gf_nested* s, int64_t max_iter)
     GFN_HIP(hipSetDevice(s->device));
     NsArgs& a = s->a;
     if (!s->initialised) { const int rc = ns_init(s); if (rc != GF_OK) return rc; }
-    const int lpw = ns_lanes_per_walker(s->mode, (int64_t)a.nruns * a.batch, a.nbins_max, s->cus);
+    const int lpw = gf_propose_lanes_per_walker(s->mode, (int64_t)a.nruns * a.batch, a.nbins_max, s->cus, "GF_NESTED_LPW");
     constexpr int check = 4;
     std::vector<NsRun> hr(a.nruns);
     for (;;) {

@@ -1,6 +1,9 @@
-// Device pieces shared by the ensemble sampler (gf_sampler.hip) and the nested sampler (gf_nested.hip): the Philox4x32-10
-// block behind both samplers' random streams and the evaluation of one proposal with its unitarity verdict.
+// Device pieces shared by the ensemble sampler (gf_sampler.hip), the nested sampler (gf_nested.hip) and the maximiser
+// (gf_simplex.hip): the Philox4x32-10 block behind the random streams, the evaluation of one proposal with its unitarity verdict,
+// and the lanes-per-walker rule of the nested sampler's and the maximiser's evaluation kernels.
 #pragma once
+#include <cstdlib>
+
 #include "gf_device.hpp"
 #include "gf_bsm_device.hpp"
 
@@ -54,6 +57,31 @@ __device__ __forceinline__ double proposal_lnprob(const GfCommon& c, const GfBsm
         eval_walker<NDIM, MODE, 0, false>(c, ctab, row, ndim, val, fr, st);
     }
     return val;
+}
+
+// Lanes per walker of a step of `walkers` BSM walkers (the cost model of gf_sampler.hip's lanes_per_walker, restricted to the
+// instances the nested sampler and the maximiser compile); the environment variable `force_env` forces one.  Any choice gives
+// the same bits.
+inline int gf_propose_lanes_per_walker(int mode, int64_t walkers, int nbins_max, int cus, const char* force_env)
+{
+    if (mode != MODE_BSM_GAUSS || nbins_max < 2) return 1;
+    const char* force = gf_internal_env(force_env, 0);
+    if (force) { const int f = std::atoi(force); if (f == 1 || f == 4 || f == 16) return f; }
+    const int64_t simds = (int64_t)(cus > 0 ? cus : 256) * 4;
+    int best = 1;
+    double best_cost = 0.0;
+    for (int lpw : {1, 4, 16}) {
+        const size_t lds = (size_t)(GF_BLOCK / lpw) * GF_FGRP_DOUBLES(nbins_max, lpw) * sizeof(double);
+        if (lpw > 1 && lds > 32 * 1024) continue;
+        const int64_t waves = (walkers * lpw + GF_WAVE - 1) / GF_WAVE;
+        const int64_t per_simd = (waves + simds - 1) / simds;
+        const int64_t wv = per_simd < 3 ? per_simd : 3;
+        const int64_t rounds = (waves + simds * 3 - 1) / (simds * 3);
+        const double interval = 4.0 * (double)wv > 7.0 ? 4.0 * (double)wv : 7.0;
+        const double cost = (double)rounds * (2000.0 + 400.0 * (double)((nbins_max + lpw - 1) / lpw)) * interval;
+        if (lpw == 1 || cost < best_cost) { best = lpw; best_cost = cost; }
+    }
+    return best;
 }
 
 }  // namespace

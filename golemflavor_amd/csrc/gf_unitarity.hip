@@ -138,7 +138,9 @@ __device__ unsigned long long g_settle_cmax[4];
 #endif
 // NESTED (gf_nested.hip): the same settlement for the nested sampler's replacement walks; only the completion differs -- a
 // proposal the reference would have raised on is rejected and counted per run, any other is accepted iff lnq > L* of its run.
-template <class Team, bool NESTED = false>
+// SIMPLEX (gf_simplex.hip): the maximiser's candidate points; the completion only records the verdict and the lnprob -- the
+// commit kernel decides what they mean for the simplex.
+template <class Team, bool NESTED = false, bool SIMPLEX = false>
 __global__ __launch_bounds__(UNI_BLOCK, GF_UNI_WAVES) void k_stretch_settle(const GfSettleArgs s)
 {
     __shared__ __attribute__((aligned(16))) double lds[(UNI_BLOCK / 64) * Team::PER_WAVE * Team::DOUBLES];
@@ -249,6 +251,12 @@ __global__ __launch_bounds__(UNI_BLOCK, GF_UNI_WAVES) void k_stretch_settle(cons
                             s.ctl[2 * t + 1] = 0u;
                         }
                     }
+                    if constexpr (SIMPLEX) {
+                        if (last) {
+                            s.sx_lnq[t] = s.pend_rows[(size_t)t * GF_PEND_STRIDE + GF_MAX_DIM];
+                            s.sx_status[t] = bad ? UT_NON_UNITARY : 0;
+                        }
+                    } else
                     if constexpr (NESTED) {
                         if (last) {
                             const double lnq = s.pend_rows[(size_t)t * GF_PEND_STRIDE + GF_MAX_DIM];
@@ -452,6 +460,18 @@ hipError_t gf_launch_nested_settle(const GfSettleArgs& a, int cus, hipStream_t s
     if (blocks > cus) blocks = cus;
     if (blocks < 1) blocks = 1;
     hipLaunchKernelGGL((k_stretch_settle<Team9, true>), dim3((unsigned)blocks), dim3(UNI_BLOCK), 0, s, a);
+    return hipGetLastError();
+}
+
+// the maximiser's settle step (gf_simplex.hip): one launch after every evaluation round, same grid rule
+hipError_t gf_launch_simplex_settle(const GfSettleArgs& a, int cus, hipStream_t s)
+{
+    constexpr int64_t per_block = (UNI_BLOCK / 64) * Team9::PER_WAVE;
+    const int64_t nprop = (int64_t)a.nchains * (a.nwalkers / 2);
+    int64_t blocks = (nprop * GF_UNI_MAX_FANOUT + per_block - 1) / per_block;
+    if (blocks > cus) blocks = cus;
+    if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL((k_stretch_settle<Team9, false, true>), dim3((unsigned)blocks), dim3(UNI_BLOCK), 0, s, a);
     return hipGetLastError();
 }
 

@@ -1,10 +1,12 @@
-"""`python -m golemflavor_amd.sens`: scripts/sens.py on the device nested sampler (golemflavor_amd.nested).
+"""`python -m golemflavor_amd.sens`: scripts/sens.py on the device nested sampler (golemflavor_amd.nested) or, with
+--stat-method frequentist, on the device profile-likelihood maximiser (golemflavor_amd.profile_llh).
 
 Same arguments as the reference's driver for what applies here (the likelihood is the package's Gaussian substitute,
 README.md:70-74), same scale list ([-100] + linspace over SCALE_BOUNDARIES[d] in segments - 1 steps, sens.py:226-229) and the
 same two output arrays, {datadir}/{stat_method}/{data}/fr_stat{identifier}.npy and fr_maxllh{identifier}.npy of shape
 (segments, 2) -- (1, 2) with --eval-segment, whose files carry `_scale_{10^scale:.0E}` (sens.py:232-258).  All scales run in
-one device call.  Prints one JSON summary line.
+one device call.  Prints one JSON summary line.  The frequentist arrays hold [scale, profile max lnL] in both files: the
+statistic golemflavor/plot.py:605-608 (plot_statistic) receives.
 """
 import argparse
 import json
@@ -16,6 +18,7 @@ import numpy as np
 from . import configs as Cf
 from . import fr as fr_utils
 from . import nested
+from . import profile_llh
 from .enums import DataType, StatCateg, Texture
 from .mcmc import chain_identifier
 
@@ -50,13 +53,21 @@ def parse_args(argv=None):
     ap.add_argument("--mn-tolerance", type=float, default=nested.DEFAULT_TOL)
     ap.add_argument("--mn-batch", type=int, default=None, help="live points replaced per iteration (default nlive // 8)")
     ap.add_argument("--mn-walks", type=int, default=nested.DEFAULT_WALKS, help="Metropolis steps per replacement")
+    ap.add_argument("--pl-starts", type=int, default=profile_llh.DEFAULT_STARTS,
+                    help="frequentist: Nelder-Mead starts per scale (the best seed points)")
+    ap.add_argument("--pl-seed-points", type=int, default=profile_llh.DEFAULT_SEED_POINTS,
+                    help="frequentist: uniform points per scale the starts are picked from")
+    ap.add_argument("--pl-xatol", type=float, default=profile_llh.DEFAULT_XATOL, help="frequentist: scipy's xatol")
+    ap.add_argument("--pl-fatol", type=float, default=profile_llh.DEFAULT_FATOL, help="frequentist: scipy's fatol")
+    ap.add_argument("--pl-maxiter", type=int, default=None, help="frequentist: iterations per start (default 200 n)")
+    ap.add_argument("--pl-restarts", type=int, default=profile_llh.DEFAULT_RESTARTS,
+                    help="frequentist: restarts of a converged start from its best vertex")
+    ap.add_argument("--pl-adaptive", type=_bool, default=True, help="frequentist: scipy's adaptive coefficients")
     ap.add_argument("--on-nonunitary", choices=["raise", "-inf"], default="raise")
     ap.add_argument("--device", type=int, default=0)
     args = ap.parse_args(argv)
     if args.texture is Texture.NONE:
         ap.error("Must assume a BSM texture")                         # sens.py:145-146
-    if args.stat_method is not StatCateg.BAYESIAN:
-        ap.error("only the BAYESIAN statistic is implemented")       # sens.py:140-143
     args.source_ratio = fr_utils.normalize_fr(args.source_ratio)
     if args.data is not DataType.REAL:
         args.injected_ratio = fr_utils.normalize_fr(args.injected_ratio)
@@ -87,6 +98,8 @@ def main(argv=None):
             return 0
     idx = np.arange(len(scales)) if args.eval_segment is None else np.array([args.eval_segment])
     asimov, llh_ps = Cf.sens_paramsets(args.dimension, args.injected_ratio, data=args.data)
+    if args.stat_method is StatCateg.FREQUENTIST:
+        return _frequentist(args, scales, idx, asimov, llh_ps, outfile, outfile_llh)
     res = nested.evidence_scan(args, asimov, llh_ps, scales[idx], run_ids=idx, on_nonunitary=args.on_nonunitary,
                                device=args.device)
     evidence_arr = np.stack([scales[idx], res["lnz"]], axis=1)
@@ -101,6 +114,28 @@ def main(argv=None):
         "niter": res["niter"].tolist(), "nevals": int(res["nevals"].sum()), "nonunitary": res["nonunitary"].tolist(),
         "seconds": round(res["seconds"], 4), "evals_per_s": float(res["nevals"].sum() / max(res["seconds"], 1e-12)),
         "fr_stat": outfile + ".npy", "fr_maxllh": outfile_llh + ".npy"}))
+    return 0
+
+
+def _frequentist(args, scales, idx, asimov, llh_ps, outfile, outfile_llh):
+    res = profile_llh.profile_scan(args, asimov, llh_ps, scales[idx], run_ids=idx, on_nonunitary=args.on_nonunitary,
+                                   device=args.device)
+    arr = np.stack([scales[idx], res["max_lnl"]], axis=1)
+    for f in (outfile, outfile_llh):
+        os.makedirs(os.path.dirname(f) or ".", exist_ok=True)
+        np.save(f + ".npy", arr)
+    ml = res["max_lnl"]
+    null = np.flatnonzero(scales[idx] == scales[0])
+    ts = (-2 * (ml - ml[null[0]])).tolist() if len(null) and np.isfinite(ml[null[0]]) else None
+    limit = profile_llh.profile_likelihood_limit(scales[idx], ml) if args.eval_segment is None else None
+    print(json.dumps({
+        "tool": "golemflavor_amd.sens", "stat_method": "FREQUENTIST", "dimension": args.dimension,
+        "texture": args.texture.name, "segments": args.segments, "scales": scales[idx].tolist(), "max_lnl": ml.tolist(),
+        "ts": ts, "limit": None if limit is None else float(limit), "starts": res["nstarts"].tolist(),
+        "starts_agreeing": res["starts_agreeing"].tolist(), "niter": res["niter"].tolist(), "nfev": res["nfev"].tolist(),
+        "nevals": int(res["nevals"].sum()), "nonunitary": res["nonunitary"].tolist(), "seconds": round(res["seconds"], 4),
+        "evals_per_s": float(res["nevals"].sum() / max(res["seconds"], 1e-12)),
+        "fr_stat": outfile + ".npy", "fr_maxllh": outfile_llh + ".npy"}, allow_nan=True))
     return 0
 
 

@@ -309,6 +309,37 @@ int gf_nested_result(gf_nested* s, double* lnz, double* lnz_err, double* info, d
  * (log-weights) and cube [n][nscan]; NULL = skip; all NULL: only *n.  cap = rows the arrays hold. */
 int gf_nested_get_dead(gf_nested* s, int run, int64_t cap, double* lnl, double* lnw, double* cube, int64_t* n);
 
+/* ---- device multi-start Nelder-Mead maximiser (the profile likelihood) ------------------------------------------------------ */
+/* The maximum of ln_prob over the unit cube of the nscan columns cols[] for `nruns` independent runs in one set of launches:
+ * scripts/sens.py's frequentist statistic (golemflavor/plot.py:605-608).  Models, cols and bases as for gf_nested_create; f(u) =
+ * -ln_prob(theta(u)) (-inf, NaN or a non-unitary verdict: +inf) is minimised from every start by scipy's bounded Nelder-Mead
+ * (scipy.optimize._optimize._minimize_neldermead, bounds [0, 1]^n) step for step.  Starts: the nstarts best finite points of
+ * nseed uniform cube points per run (Philox4x32-10 keyed by `seed`, counter (run id, ...)), then the caller's starts
+ * (gf_simplex_set_starts); a run without a finite seed point and without caller's starts has max lnL = -inf and 0 starts.
+ * on_nonunitary as for gf_nested_create, counted only for points scipy's sequential algorithm evaluates. */
+typedef struct gf_simplex gf_simplex;
+int gf_simplex_create(gf_model* const* models, int nruns, int nscan, const int32_t* cols, const double* bases, int nstarts,
+                      int nseed, uint64_t seed, int on_nonunitary, gf_simplex** out);
+/* run ids [nruns] (default: the index in this maximiser).  Before the first run. */
+int gf_simplex_set_run_ids(gf_simplex* s, const uint64_t* ids);
+/* nuser caller's starts per run, cube [nruns][nuser][nscan] (clipped to the cube as scipy clips x0).  Before the first run. */
+int gf_simplex_set_starts(gf_simplex* s, int nuser, const double* cube);
+/* scipy's xatol, fatol, maxiter (default 1e-4, 1e-4, 200 nscan) and adaptive coefficients (0/1, default 0); restarts: how many
+ * times a converged start begins again from its best vertex with a fresh simplex (stopping when the gain is <= fatol).  Before
+ * the first run. */
+int gf_simplex_set_options(gf_simplex* s, double xatol, double fatol, int maxiter, int adaptive, int restarts);
+void gf_simplex_destroy(gf_simplex* s);
+/* Synchronous: at most max_rounds evaluation rounds in this call (one per Nelder-Mead iteration, one more per shrink); returns
+ * when every start of every run is done or the rounds are used up.  A later call continues. */
+int gf_simplex_run(gf_simplex* s, int64_t max_rounds);
+/* per run [nruns]: max lnL, its cube point [nruns][nscan], starts used, iterations and scipy's nfev summed over the starts,
+ * device evaluations (seed points included), non-unitary points counted, candidates whose unitarity verdict the emulated-x87
+ * settlement took (evaluated or speculative), failed (raise mode); NULL = skip */
+int gf_simplex_result(gf_simplex* s, double* max_lnl, double* argmax_cube, int32_t* nstarts, int64_t* niter, int64_t* nfev,
+                      int64_t* nevals, uint32_t* nonunitary, uint32_t* parked, int32_t* failed);
+/* run `run`'s starts [nstarts + nuser]: final f (+inf for an unused start), final cube point [..][nscan], nit, nfev; NULL = skip */
+int gf_simplex_get_starts(gf_simplex* s, int run, double* fun, double* cube, int32_t* nit, int64_t* nfev);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI -------------------------------------- */
 /* Independent chains (grid points) shard across ranks with no data-path collective; the only
  * exchanges are the broadcast of the packed descriptors at start and the gather of the chain blocks
