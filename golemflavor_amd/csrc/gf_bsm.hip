@@ -101,15 +101,7 @@ __global__ __launch_bounds__(GF_BLOCK, GF_BSM_WAVES(UNI_MODE, NDIM)) void k_bsm(
     __shared__ __attribute__((aligned(16))) double tiles[PREFETCH ? 2 : 1][GF_WAVES_PER_BLOCK][GF_WAVE * (NDIM ? NDIM : GF_MAX_DIM)];
     __shared__ __attribute__((aligned(16))) double ctab[GF_MAX_DIM * 4 + 20];
     double* ttab = ctab + GF_MAX_DIM * 4;       // texture projector entries, see flux_average
-    if (threadIdx.x < GF_MAX_DIM * 4) ctab[threadIdx.x] = ptab[threadIdx.x];
-    if (threadIdx.x >= 64 && threadIdx.x < 64 + 18) {
-        // {t1, t2} pairs: re[0], re[4], re[8], re[1], im[1], re[2], im[2], re[5], im[5]
-        const int k = threadIdx.x - 64, e = k >> 1;
-        const int idx = e == 0 ? 0 : e == 1 ? 4 : e == 2 ? 8 : e <= 4 ? 1 : e <= 6 ? 2 : 5;
-        const bool im = e == 4 || e == 6 || e == 8;
-        const double* srcp = (k & 1) ? (im ? tb->t2_im : tb->t2_re) : (im ? tb->t1_im : tb->t1_re);
-        ttab[k] = srcp[idx];
-    }
+    load_eval_tables(ctab, ptab, tb, true);
     __syncthreads();
     const int lane = threadIdx.x & (GF_WAVE - 1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / GF_WAVE);   // uniform, and the compiler may know: tile indices and

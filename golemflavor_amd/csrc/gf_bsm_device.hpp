@@ -530,6 +530,21 @@ __device__ __forceinline__ bool lnprior_tab(const double* ctab, const double* ro
     return inbox;
 }
 
+// The LDS prologue of an evaluation kernel; no barrier here, the caller syncs.  ctab [GF_MAX_DIM * 4 + 20]: the prior table
+// (ptab) and, with `bsm`, behind it at ttab = ctab + GF_MAX_DIM * 4 the 18 texture projector entries flux_average reads,
+// {t1, t2} pairs: re[0], re[4], re[8], re[1], im[1], re[2], im[2], re[5], im[5]
+__device__ __forceinline__ void load_eval_tables(double* ctab, const double* ptab, const GfBsm* tb, bool bsm)
+{
+    if (threadIdx.x < GF_MAX_DIM * 4) ctab[threadIdx.x] = ptab[threadIdx.x];
+    if (bsm && threadIdx.x >= 64 && threadIdx.x < 64 + 18) {
+        const int k = threadIdx.x - 64, e = k >> 1;
+        const int idx = e == 0 ? 0 : e == 1 ? 4 : e == 2 ? 8 : e <= 4 ? 1 : e <= 6 ? 2 : 5;
+        const bool im = e == 4 || e == 6 || e == 8;
+        const double* srcp = (k & 1) ? (im ? tb->t2_im : tb->t2_re) : (im ? tb->t1_im : tb->t1_re);
+        ctab[GF_MAX_DIM * 4 + k] = srcp[idx];
+    }
+}
+
 
 }  // namespace gfdev
 

@@ -1,0 +1,235 @@
+// The run set the nested sampler (gf_nested.hip) and the maximiser (gf_simplex.hip) share.  Run r is one posterior (one
+// gf_model) over the unit cube of its scanned columns: theta_i = (hi_i - lo_i) u_i + lo_i there (mn.py:35-39, the product and
+// the sum each rounded), the run's base value on every other column.  Random numbers: Philox4x32-10, key = seed, counter =
+// (run id, iteration word, point, step): a run's result does not depend on the other runs of the launch or on the launch shape.
+#pragma once
+#include <cstring>
+#include <cstddef>
+#include <new>
+#include <type_traits>
+#include <vector>
+
+#include "gf_host.h"
+#include "gf_propose.hpp"
+
+// the kernels' view: NsArgs and SxArgs start with it
+struct GfCubeRuns {
+    const GfCommon* commons;        // [R]
+    const GfBsm* const* tbs;        // [R]
+    const double* const* ptabs;     // [R]
+    const uint64_t* run_ids;        // [R] Philox counter word 0
+    const double* bases;            // [R][GF_MAX_DIM] values of the columns that are not scanned
+    GfArbQueue* pq;                 // BSM: parked proposals, capacity = the proposals of one step
+    double* pend_rows;              // BSM: [capacity][GF_PEND_STRIDE]
+    uint64_t seed;
+    int32_t slot[GF_MAX_DIM];       // column -> scanned slot, -1 = fixed
+    int32_t nruns, nbins_max, ndim, nscan;     // last: a kernel loads nscan with the counters that follow it (k_sx_pick)
+};
+
+// the host's: the models, their stream, and the buffers behind GfCubeRuns and the settle kernel's arguments
+struct GfCubeRunsHost {
+    gf_model** models = nullptr;        // [nruns]; models[0]'s stream carries every launch
+    hipStream_t stream = nullptr;
+    int device = 0, cus = 256, mode = 0;
+    int initialised = 0;
+    GfCommon* d_commons = nullptr;
+    const GfBsm** d_tbs = nullptr;
+    const double** d_ptabs = nullptr;
+    uint64_t* d_run_ids = nullptr;
+    double* d_bases = nullptr;
+    GfStepState* d_state = nullptr;     // the settle kernel's step state: zeros (no stored chain)
+    unsigned int* d_ctl = nullptr;
+};
+
+namespace {
+using namespace gfdev;
+
+// two uniform doubles in [0, 1), 53 bits each, of counter (run id, it, point, step)
+__device__ __forceinline__ void cube_uniform2(const GfCubeRuns& a, int r, uint32_t it, uint32_t point, uint32_t step, double out[2])
+{
+    uint32_t q[4];
+    const uint64_t key = a.seed, id = a.run_ids[r];
+    philox_block((uint32_t)id, it, point, step, (uint32_t)key, (uint32_t)(key >> 32) ^ (uint32_t)(id >> 32), q);
+    out[0] = ((double)(q[0] >> 5) * 67108864.0 + (double)(q[1] >> 6)) * (1.0 / 9007199254740992.0);
+    out[1] = ((double)(q[2] >> 5) * 67108864.0 + (double)(q[3] >> 6)) * (1.0 / 9007199254740992.0);
+}
+
+// theta of cube point u for run r (as k_cube_to_theta)
+__device__ __forceinline__ void cube_to_theta(const GfCubeRuns& a, const GfCommon& c, int r, const double* u, double* row)
+{
+    for (int d = 0; d < a.ndim; ++d) {
+        const int sl = a.slot[d];
+        row[d] = sl >= 0 ? __dadd_rn(__dmul_rn(c.hi[d] - c.lo[d], u[sl]), c.lo[d]) : a.bases[r * GF_MAX_DIM + d];
+    }
+}
+
+// n cube points per run (blockIdx.y), drawn uniformly (counter (run id, it, point, pair of coordinates)) into u [R][n][nscan]
+// and mapped to theta [R][n][ndim]
+__global__ __launch_bounds__(GF_BLOCK) void k_cube_draw(const GfCubeRuns a, uint32_t it, int n, double* u, double* theta)
+{
+    const int r = blockIdx.y;
+    const int i = blockIdx.x * GF_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    double v[GF_MAX_DIM];
+    for (int p = 0; 2 * p < a.nscan; ++p) {
+        double w[2];
+        cube_uniform2(a, r, it, (uint32_t)i, (uint32_t)p, w);
+        v[2 * p] = w[0];
+        if (2 * p + 1 < a.nscan) v[2 * p + 1] = w[1];
+    }
+    double* dst = u + ((int64_t)r * n + i) * a.nscan;
+    for (int d = 0; d < a.nscan; ++d) dst[d] = v[d];
+    cube_to_theta(a, a.commons[r], r, v, theta + ((int64_t)r * n + i) * a.ndim);
+}
+
+// An evaluation kernel's instances: PRIOR_ONLY and SM_GAUSS at one lane per point, BSM at 1, 4 or 16.  `launch` is called with
+// std::integral_constant<int, MODE> and <int, LPW>.
+template <class Launch>
+hipError_t launch_mode_lpw(int mode, int lpw, Launch launch)
+{
+    using M = std::integral_constant<int, MODE_BSM_GAUSS>;
+    switch (mode) {
+    case MODE_PRIOR_ONLY: return launch(std::integral_constant<int, MODE_PRIOR_ONLY>(), std::integral_constant<int, 1>());
+    case MODE_SM_GAUSS: return launch(std::integral_constant<int, MODE_SM_GAUSS>(), std::integral_constant<int, 1>());
+    default:
+        switch (lpw) {
+        case 4: return launch(M(), std::integral_constant<int, 4>());
+        case 16: return launch(M(), std::integral_constant<int, 16>());
+        default: return launch(M(), std::integral_constant<int, 1>());
+        }
+    }
+}
+
+// Its launch: `points` per run (blockIdx.y = run), LPW lanes each, with the lane groups' LDS
+template <class Kernel, class Args>
+hipError_t launch_points(Kernel kernel, const Args& a, int lpw, int64_t points, hipStream_t st)
+{
+    const size_t lds = lpw > 1 ? (size_t)(GF_BLOCK / lpw) * GF_FGRP_DOUBLES(a.nbins_max, lpw) * sizeof(double) : 0;
+    const dim3 grid((unsigned)((points * lpw + GF_BLOCK - 1) / GF_BLOCK), a.nruns);
+    hipLaunchKernelGGL(kernel, grid, dim3(GF_BLOCK), lds, st, a);
+    return hipGetLastError();
+}
+
+// the shared buffers and the model list; the stream is synchronised first
+void cube_runs_free(GfCubeRunsHost& h, GfCubeRuns& a)
+{
+    (void)hipSetDevice(h.device);
+    if (h.stream) (void)hipStreamSynchronize(h.stream);
+    void* ptrs[] = {h.d_commons, (void*)h.d_tbs, (void*)h.d_ptabs, h.d_run_ids, h.d_bases, h.d_state, h.d_ctl, a.pq, a.pend_rows};
+    for (void* p : ptrs) if (p) (void)hipFree(p);
+    h.d_commons = nullptr; h.d_tbs = nullptr; h.d_ptabs = nullptr; h.d_run_ids = nullptr; h.d_bases = nullptr;
+    h.d_state = nullptr; h.d_ctl = nullptr; a.pq = nullptr; a.pend_rows = nullptr;
+    delete[] h.models;
+    h.models = nullptr;
+}
+
+// Validates the models against models[0] (device, ndim, mode; `who` names the call in the error), builds the slot map of
+// `cols`, and uploads every run's constants: fills `a` but pq and pend_rows.  On failure nothing stays allocated.
+int cube_runs_create(GfCubeRunsHost& h, GfCubeRuns& a, gf_model* const* models, int nruns, int nscan, const int32_t* cols,
+                     const double* bases, uint64_t seed, const char* who)
+{
+    const GfCommon* c0; const GfBsm* tb0; const double* pt0; void* stream0; int device0;
+    if (!models[0] || gf_model_internal(models[0], &c0, &tb0, &pt0, &stream0, &device0) != GF_OK) return GF_ERR_INVALID_ARG;
+    const int ndim = c0->ndim;
+    std::vector<int32_t> slot(GF_MAX_DIM, -1);
+    for (int k = 0; k < nscan; ++k) {
+        if (cols[k] < 0 || cols[k] >= ndim || slot[cols[k]] >= 0) return GF_ERR_INVALID_ARG;
+        slot[cols[k]] = k;
+    }
+    std::vector<GfCommon> hc(nruns);
+    std::vector<const GfBsm*> htb(nruns);
+    std::vector<const double*> hpt(nruns);
+    std::vector<double> hb((size_t)nruns * GF_MAX_DIM, 0.0);
+    int cus = 256, nbins_max = 0;
+    for (int r = 0; r < nruns; ++r) {
+        const GfCommon* c; int device, nb;
+        if (!models[r] || gf_model_constants(models[r], &c, &htb[r], &hpt[r], &device, &cus, &nb) != GF_OK || device != device0 ||
+            c->ndim != ndim || c->mode != c0->mode)
+            return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: every model must share device, ndim and mode with model 0", who);
+        hc[r] = *c;
+        if (nb > nbins_max) nbins_max = nb;
+        for (int d = 0; d < ndim; ++d) hb[(size_t)r * GF_MAX_DIM + d] = bases[(size_t)r * ndim + d];
+    }
+    h.models = new (std::nothrow) gf_model*[nruns];
+    if (!h.models) return GF_ERR_ALLOC;
+    for (int r = 0; r < nruns; ++r) h.models[r] = models[r];
+    h.stream = (hipStream_t)stream0; h.device = device0; h.cus = cus; h.mode = c0->mode;
+    a.seed = seed;
+    a.nruns = nruns; a.nscan = nscan; a.ndim = ndim; a.nbins_max = nbins_max;
+    for (int d = 0; d < GF_MAX_DIM; ++d) a.slot[d] = slot[d];
+    const size_t R = nruns;
+    std::vector<uint64_t> ids(R);
+    for (size_t r = 0; r < R; ++r) ids[r] = r;
+    GfStepState hs;
+    std::memset(&hs, 0, sizeof(hs));
+    hs.thin = 1;
+    hipError_t e = hipSetDevice(device0);
+    auto al = [&](void** p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes); };
+    auto up = [&](void* dst, const void* src, size_t bytes) { if (e == hipSuccess) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h.stream); };
+    al((void**)&h.d_commons, sizeof(GfCommon) * R);
+    al((void**)&h.d_tbs, sizeof(void*) * R);
+    al((void**)&h.d_ptabs, sizeof(void*) * R);
+    al((void**)&h.d_run_ids, sizeof(uint64_t) * R);
+    al((void**)&h.d_bases, sizeof(double) * R * GF_MAX_DIM);
+    al((void**)&h.d_state, sizeof(GfStepState));
+    up(h.d_commons, hc.data(), sizeof(GfCommon) * R);
+    up((void*)h.d_tbs, htb.data(), sizeof(void*) * R);
+    up((void*)h.d_ptabs, hpt.data(), sizeof(void*) * R);
+    up(h.d_run_ids, ids.data(), sizeof(uint64_t) * R);
+    up(h.d_bases, hb.data(), sizeof(double) * R * GF_MAX_DIM);
+    up(h.d_state, &hs, sizeof(hs));
+    if (e == hipSuccess) e = hipStreamSynchronize(h.stream);              // the host vectors go out of scope
+    if (e != hipSuccess) { const int rc = gf_hip_fail(e, who); cube_runs_free(h, a); return rc; }
+    a.commons = h.d_commons; a.tbs = h.d_tbs; a.ptabs = h.d_ptabs; a.run_ids = h.d_run_ids; a.bases = h.d_bases;
+    return GF_OK;
+}
+
+// BSM: the arbitration queue for `w` proposals a step, their pend rows and the settle kernel's counters, all empty
+hipError_t cube_runs_alloc_queue(GfCubeRunsHost& h, GfCubeRuns& a, size_t w)
+{
+    if (h.mode != MODE_BSM_GAUSS) return hipSuccess;
+    GfArbQueue qh;
+    std::memset(&qh, 0, sizeof(qh));
+    qh.cap = (unsigned int)w;
+    hipError_t e = hipMalloc((void**)&a.pq, sizeof(GfArbQueue) + sizeof(GfArbItem) * w);
+    if (e == hipSuccess) e = hipMalloc((void**)&a.pend_rows, sizeof(double) * w * GF_PEND_STRIDE);
+    if (e == hipSuccess) e = hipMalloc((void**)&h.d_ctl, sizeof(unsigned int) * 2 * w);
+    if (e == hipSuccess) e = hipMemcpyAsync(a.pq, &qh, offsetof(GfArbQueue, items), hipMemcpyHostToDevice, h.stream);
+    if (e == hipSuccess) e = hipMemsetAsync(h.d_ctl, 0, sizeof(unsigned int) * 2 * w, h.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h.stream);             // qh goes out of scope
+    return e;
+}
+
+// the settle kernel's arguments common to both variants: run r is its chain r, `nwalkers` / 2 proposals each
+void cube_runs_settle_args(const GfCubeRunsHost& h, const GfCubeRuns& a, int nwalkers, GfSettleArgs& sa)
+{
+    sa.state = h.d_state; sa.pq = a.pq; sa.pend_rows = a.pend_rows; sa.ctl = h.d_ctl;
+    sa.nchains = a.nruns; sa.nwalkers = nwalkers; sa.ndim = a.ndim; sa.commons = h.d_commons; sa.tbs = h.d_tbs; sa.multi = 1;
+}
+
+// the Philox streams of the runs; `late` is the error before the first run
+int cube_runs_set_ids(GfCubeRunsHost& h, const GfCubeRuns& a, const uint64_t* ids, const char* late)
+{
+    if (h.initialised) return gf_fail_msg(GF_ERR_INVALID_ARG, "%s", late);
+    GF_HIP(hipSetDevice(h.device));
+    GF_HIP(hipMemcpyAsync(h.d_run_ids, ids, sizeof(uint64_t) * (size_t)a.nruns, hipMemcpyHostToDevice, h.stream));
+    GF_HIP(hipStreamSynchronize(h.stream));
+    return GF_OK;
+}
+
+// n uniform cube points per run (k_cube_draw, iteration word `it`), then every run's lnprob by its model's bulk path with its
+// own unitarity arbitration: lnl [R][n], status [R][n]
+int cube_runs_draw(const GfCubeRunsHost& h, const GfCubeRuns& a, uint32_t it, int n, double* u, double* theta, double* lnl,
+                   int32_t* status)
+{
+    const dim3 grid((unsigned)((n + GF_BLOCK - 1) / GF_BLOCK), a.nruns);
+    hipLaunchKernelGGL(k_cube_draw, grid, dim3(GF_BLOCK), 0, h.stream, a, it, n, u, theta);
+    GF_HIP(hipGetLastError());
+    for (int r = 0; r < a.nruns; ++r) {
+        const int rc = gf_model_lnprob_on(h.models[r], h.stream, theta + (size_t)r * n * a.ndim, GF_LAYOUT_AOS, n,
+                                          lnl + (size_t)r * n, nullptr, status + (size_t)r * n);
+        if (rc != GF_OK) return rc;
+    }
+    return GF_OK;
+}
+}  // namespace

@@ -27,24 +27,12 @@
 #include <stdint.h>
 
 #include <cmath>
-#include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <cstddef>
-#include <new>
 #include <vector>
 
-#include "../../include/golemflavor_hip.h"
-#include "gf_consts.h"
-
-extern "C" const char* gf_internal_env(const char* name, int affects_results);   // gf_capi.hip: getenv with a record
-#include "gf_device.hpp"
-#include "gf_bsm_device.hpp"
-#include "gf_launch.h"
-#include "gf_propose.hpp"
+#include "gf_cube_runs.hpp"
 
 namespace {
-using namespace gfdev;
 
 constexpr int NS_MAX_LIVE = 4096;       // live points per run: k_ns_select sorts them in LDS
 constexpr int NS_SEL_BLOCK = 1024;
@@ -60,12 +48,9 @@ struct NsRun {
     int32_t done, failed;   // failed: on_nonunitary == raise and a proposal the reference would have raised on
 };
 
-struct NsArgs {
-    const GfCommon* commons;        // [R]
-    const GfBsm* const* tbs;        // [R]
-    const double* const* ptabs;     // [R]
-    const uint64_t* run_ids;        // [R] Philox counter word 0
-    const double* bases;            // [R][GF_MAX_DIM] values of the columns that are not scanned
+struct NsArgs : GfCubeRuns {       // pq: capacity R * B
+    int32_t nlive, batch, walks, raise, step;     // first: next to GfCubeRuns::nscan in the kernel arguments
+    double tol;
     NsRun* runs;                    // [R]
     double* lstar;                  // [R]
     uint32_t* nonunit;              // [R]
@@ -78,56 +63,12 @@ struct NsArgs {
     uint32_t* wacc;                 // [R][B]
     uint32_t* wev;                  // [R][B]
     double* prop_u;                 // [R][B][D] parked proposals
-    GfArbQueue* pq;                 // capacity R * B
-    double* pend_rows;              // [R * B][GF_PEND_STRIDE]
     double* dead_l;                 // [cap][R][B] (iteration-major: growing the buffer is one copy)
     double* dead_w;                 // [cap][R][B] log-weights
     double* dead_u;                 // [cap][R][B][D]
-    double* theta;                  // [R][K][ndim] initial points (k_ns_init)
+    double* theta;                  // [R][K][ndim] initial points (k_cube_draw)
     int32_t* status;                // [R][K]
-    uint64_t seed;
-    double tol;
-    int32_t nruns, nlive, batch, nscan, ndim, walks, raise, step;
-    int32_t slot[GF_MAX_DIM];       // column -> scanned slot, -1 = fixed
-    int32_t nbins_max;
 };
-
-__device__ __forceinline__ void ns_uniform2(const NsArgs& a, int r, uint32_t it, uint32_t slot, uint32_t step, double out[2])
-{
-    uint32_t q[4];
-    const uint64_t key = a.seed, id = a.run_ids[r];
-    philox_block((uint32_t)id, it, slot, step, (uint32_t)key, (uint32_t)(key >> 32) ^ (uint32_t)(id >> 32), q);
-    out[0] = ((double)(q[0] >> 5) * 67108864.0 + (double)(q[1] >> 6)) * (1.0 / 9007199254740992.0);
-    out[1] = ((double)(q[2] >> 5) * 67108864.0 + (double)(q[3] >> 6)) * (1.0 / 9007199254740992.0);
-}
-
-// theta of cube point u for run r: mn.py:35-39, the product and the sum each rounded (as k_cube_to_theta)
-__device__ __forceinline__ void ns_cube_to_theta(const NsArgs& a, const GfCommon& c, int r, const double* u, double* row)
-{
-    for (int d = 0; d < a.ndim; ++d) {
-        const int sl = a.slot[d];
-        row[d] = sl >= 0 ? __dadd_rn(__dmul_rn(c.hi[d] - c.lo[d], u[sl]), c.lo[d]) : a.bases[r * GF_MAX_DIM + d];
-    }
-}
-
-// K cube points per run, drawn uniformly (counter (run id, NS_INIT_ITER, point, pair of coordinates)) and mapped to theta;
-// the bulk lnprob path evaluates them next, with its own unitarity arbitration
-__global__ __launch_bounds__(GF_BLOCK) void k_ns_init(const NsArgs a)
-{
-    const int r = blockIdx.y;
-    const int i = blockIdx.x * GF_BLOCK + threadIdx.x;
-    if (i >= a.nlive) return;
-    double u[GF_MAX_DIM];
-    for (int p = 0; 2 * p < a.nscan; ++p) {
-        double v[2];
-        ns_uniform2(a, r, NS_INIT_ITER, (uint32_t)i, (uint32_t)p, v);
-        u[2 * p] = v[0];
-        if (2 * p + 1 < a.nscan) u[2 * p + 1] = v[1];
-    }
-    double* lu = a.live_u + ((int64_t)r * a.nlive + i) * a.nscan;
-    for (int d = 0; d < a.nscan; ++d) lu[d] = u[d];
-    ns_cube_to_theta(a, a.commons[r], r, u, a.theta + ((int64_t)r * a.nlive + i) * a.ndim);
-}
 
 // after the bulk evaluation: a point the reference would have raised on is outside the support (-inf) and counted; NaN too
 __global__ __launch_bounds__(GF_BLOCK) void k_ns_init_fix(const NsArgs a)
@@ -315,7 +256,7 @@ __global__ __launch_bounds__(NS_SEL_BLOCK) void k_ns_select(const NsArgs a)
     const int m0 = first;
     for (int j = tid; j < B; j += NS_SEL_BLOCK) {
         double v[2];
-        ns_uniform2(a, r, (uint32_t)it, (uint32_t)j, NS_START_STEP, v);
+        cube_uniform2(a, r, (uint32_t)it, (uint32_t)j, NS_START_STEP, v);
         int m = m0 + (int)(v[0] * (double)(K - m0));
         if (m >= K) m = K - 1;
         const int src = idx[m];
@@ -342,14 +283,7 @@ __global__ __launch_bounds__(GF_BLOCK) void k_ns_walk(const NsArgs a)
     const GfBsm* tb = a.tbs[r];
     const double* ptab = a.ptabs[r];
     double* ttab = ctab + GF_MAX_DIM * 4;
-    if (threadIdx.x < GF_MAX_DIM * 4) ctab[threadIdx.x] = ptab[threadIdx.x];
-    if (MODE == MODE_BSM_GAUSS && threadIdx.x >= 64 && threadIdx.x < 64 + 18) {
-        const int k = threadIdx.x - 64, e = k >> 1;
-        const int id = e == 0 ? 0 : e == 1 ? 4 : e == 2 ? 8 : e <= 4 ? 1 : e <= 6 ? 2 : 5;
-        const bool im = e == 4 || e == 6 || e == 8;
-        const double* srcp = (k & 1) ? (im ? tb->t2_im : tb->t2_re) : (im ? tb->t1_im : tb->t1_re);
-        ttab[k] = srcp[id];
-    }
+    load_eval_tables(ctab, ptab, tb, MODE == MODE_BSM_GAUSS);
     __syncthreads();
     const int t = blockIdx.x * GF_BLOCK + threadIdx.x;
     const int k = t / LPW, sub = t % LPW;
@@ -362,7 +296,7 @@ __global__ __launch_bounds__(GF_BLOCK) void k_ns_walk(const NsArgs a)
     double u[GF_MAX_DIM], z[GF_MAX_DIM];
     for (int p = 0; 2 * p < D; ++p) {
         double v[2];
-        ns_uniform2(a, r, it, (uint32_t)k, ((uint32_t)p << 24) | (uint32_t)a.step, v);
+        cube_uniform2(a, r, it, (uint32_t)k, ((uint32_t)p << 24) | (uint32_t)a.step, v);
         // Box-Muller on (1 - v0, v1): the radius stays finite
         const double rad = sqrt(-2.0 * log(1.0 - v[0]));
         double sn, cs;
@@ -381,26 +315,15 @@ __global__ __launch_bounds__(GF_BLOCK) void k_ns_walk(const NsArgs a)
     if (!inside) return;                                     // rejected without evaluating
     const int lane = threadIdx.x & (GF_WAVE - 1);
     double* row = tiles[threadIdx.x / GF_WAVE] + lane * GF_MAX_DIM;
-    ns_cube_to_theta(a, c, r, u, row);
+    cube_to_theta(a, c, r, u, row);
     int st;
     unsigned long long pending;
     const double lnq = proposal_lnprob<0, MODE, LPW>(c, tb, ctab, ttab, row, a.ndim, st, sub, fgrp, pending);
     if (LPW > 1 && sub != 0) return;                         // the group's results are identical: one writer
     if (MODE == MODE_BSM_GAUSS && pending != 0ull) {
         // undecided unitarity: park; k_stretch_settle<Team9, true> settles and completes this step
-        double* dst = a.pend_rows + (size_t)w * GF_PEND_STRIDE;
-        for (int d = 0; d < a.ndim; ++d) dst[d] = row[d];
-        dst[GF_MAX_DIM] = lnq;
         for (int d = 0; d < D; ++d) a.prop_u[w * D + d] = u[d];
-        const unsigned int at = atomicAdd(&a.pq->count, 1u);
-        if (at < a.pq->cap) {
-            GfArbItem item;
-            item.walker = (unsigned long long)w;
-            item.mask = pending;
-            a.pq->items[at] = item;
-        } else {
-            a.pq->overflow = 1u;                             // capacity = every walker of a step: cannot happen
-        }
+        park_proposal(a.pq, a.pend_rows, w, row, a.ndim, lnq, pending);
         return;
     }
     a.wev[w] += 1u;
@@ -444,78 +367,24 @@ __global__ __launch_bounds__(GF_BLOCK) void k_ns_commit(const NsArgs a)
     }
 }
 
-template <int MODE, int LPW>
-hipError_t launch_walk(const NsArgs& a, hipStream_t st)
-{
-    const size_t lds = LPW > 1 ? (size_t)(GF_BLOCK / LPW) * GF_FGRP_DOUBLES(a.nbins_max, LPW) * sizeof(double) : 0;
-    const dim3 grid((unsigned)(((int64_t)a.batch * LPW + GF_BLOCK - 1) / GF_BLOCK), a.nruns);
-    hipLaunchKernelGGL((k_ns_walk<MODE, LPW>), grid, dim3(GF_BLOCK), lds, st, a);
-    return hipGetLastError();
-}
-
 hipError_t launch_walk_any(int mode, int lpw, const NsArgs& a, hipStream_t st)
 {
-    switch (mode) {
-    case MODE_PRIOR_ONLY: return launch_walk<MODE_PRIOR_ONLY, 1>(a, st);
-    case MODE_SM_GAUSS: return launch_walk<MODE_SM_GAUSS, 1>(a, st);
-    default:
-        switch (lpw) {
-        case 4: return launch_walk<MODE_BSM_GAUSS, 4>(a, st);
-        case 16: return launch_walk<MODE_BSM_GAUSS, 16>(a, st);
-        default: return launch_walk<MODE_BSM_GAUSS, 1>(a, st);
-        }
-    }
+    return launch_mode_lpw(mode, lpw, [&](auto m, auto l) {
+        return launch_points(k_ns_walk<decltype(m)::value, decltype(l)::value>, a, l, a.batch, st);
+    });
 }
 
 }  // namespace
 
-// accessors implemented in gf_capi.hip (gf_model is private to it)
-extern "C" {
-int gf_model_internal(gf_model* m, const GfCommon** c, const GfBsm** d_bsm, const double** d_ptab, void** stream, int* device);
-int gf_model_constants(gf_model* m, const GfCommon** c, const GfBsm** d_bsm, const double** d_ptab, int* device, int* cus,
-                       int* nbins);
-void gf_internal_set_error(const char* msg);
-int gf_model_lnprob_on(gf_model* m, void* stream, const double* d_theta, int layout, int64_t n, double* d_lnprob,
-                       double* d_fr, int32_t* d_status);
-}
-
 struct gf_nested {
-    gf_model** models = nullptr;        // [nruns]; models[0]'s stream carries every launch
-    hipStream_t stream = nullptr;
-    int device = 0, cus = 256, mode = 0;
-    int initialised = 0;
+    GfCubeRunsHost rs;
     int64_t dead_cap = 0;               // iterations the dead buffers hold
     int64_t launched = 0;               // iterations enqueued so far (an upper bound of every run's iteration count)
     NsArgs a = {};
     GfSettleArgs sa = {};
-    GfStepState* d_state = nullptr;     // the settle kernel's step state: zeros (no stored chain)
-    unsigned int* d_ctl = nullptr;
-    GfCommon* d_commons = nullptr;
-    const GfBsm** d_tbs = nullptr;
-    const double** d_ptabs = nullptr;
-    uint64_t* d_run_ids = nullptr;
-    double* d_bases = nullptr;
 };
 
 namespace {
-thread_local char g_nerr[256] = "";
-int nfail(hipError_t e, const char* what)
-{
-    std::snprintf(g_nerr, sizeof(g_nerr), "%s: %s", what, hipGetErrorString(e));
-    gf_internal_set_error(g_nerr);
-    return GF_ERR_HIP;
-}
-int nmsg(int rc, const char* msg)
-{
-    std::snprintf(g_nerr, sizeof(g_nerr), "%s", msg);
-    gf_internal_set_error(g_nerr);
-    return rc;
-}
-#define GFN_HIP(call)                                   \
-    do {                                                \
-        hipError_t e_ = (call);                         \
-        if (e_ != hipSuccess) return nfail(e_, #call);  \
-    } while (0)
 
 // grow the dead buffers (iteration-major) to hold `need` iterations
 int ns_grow_dead(gf_nested* s, int64_t need)
@@ -525,14 +394,14 @@ int ns_grow_dead(gf_nested* s, int64_t need)
     while (cap < need) cap *= 2;
     const size_t per = (size_t)s->a.nruns * s->a.batch;
     double *l = nullptr, *w = nullptr, *u = nullptr;
-    GFN_HIP(hipMalloc((void**)&l, sizeof(double) * per * cap));
-    GFN_HIP(hipMalloc((void**)&w, sizeof(double) * per * cap));
-    GFN_HIP(hipMalloc((void**)&u, sizeof(double) * per * s->a.nscan * cap));
+    GF_HIP(hipMalloc((void**)&l, sizeof(double) * per * cap));
+    GF_HIP(hipMalloc((void**)&w, sizeof(double) * per * cap));
+    GF_HIP(hipMalloc((void**)&u, sizeof(double) * per * s->a.nscan * cap));
     if (s->dead_cap > 0) {
-        GFN_HIP(hipMemcpyAsync(l, s->a.dead_l, sizeof(double) * per * s->dead_cap, hipMemcpyDeviceToDevice, s->stream));
-        GFN_HIP(hipMemcpyAsync(w, s->a.dead_w, sizeof(double) * per * s->dead_cap, hipMemcpyDeviceToDevice, s->stream));
-        GFN_HIP(hipMemcpyAsync(u, s->a.dead_u, sizeof(double) * per * s->a.nscan * s->dead_cap, hipMemcpyDeviceToDevice, s->stream));
-        GFN_HIP(hipStreamSynchronize(s->stream));
+        GF_HIP(hipMemcpyAsync(l, s->a.dead_l, sizeof(double) * per * s->dead_cap, hipMemcpyDeviceToDevice, s->rs.stream));
+        GF_HIP(hipMemcpyAsync(w, s->a.dead_w, sizeof(double) * per * s->dead_cap, hipMemcpyDeviceToDevice, s->rs.stream));
+        GF_HIP(hipMemcpyAsync(u, s->a.dead_u, sizeof(double) * per * s->a.nscan * s->dead_cap, hipMemcpyDeviceToDevice, s->rs.stream));
+        GF_HIP(hipStreamSynchronize(s->rs.stream));
         (void)hipFree(s->a.dead_l); (void)hipFree(s->a.dead_w); (void)hipFree(s->a.dead_u);
     }
     s->a.dead_l = l; s->a.dead_w = w; s->a.dead_u = u;
@@ -540,20 +409,16 @@ int ns_grow_dead(gf_nested* s, int64_t need)
     return GF_OK;
 }
 
+// K cube points per run (iteration word NS_INIT_ITER), evaluated by the bulk lnprob path
 int ns_init(gf_nested* s)
 {
     NsArgs& a = s->a;
+    const int rc = cube_runs_draw(s->rs, a, NS_INIT_ITER, a.nlive, a.live_u, a.theta, a.live_l, a.status);
+    if (rc != GF_OK) return rc;
     const dim3 grid((unsigned)((a.nlive + GF_BLOCK - 1) / GF_BLOCK), a.nruns);
-    hipLaunchKernelGGL(k_ns_init, grid, dim3(GF_BLOCK), 0, s->stream, a);
-    GFN_HIP(hipGetLastError());
-    for (int r = 0; r < a.nruns; ++r) {
-        const int rc = gf_model_lnprob_on(s->models[r], s->stream, a.theta + (size_t)r * a.nlive * a.ndim, GF_LAYOUT_AOS, a.nlive,
-                                          a.live_l + (size_t)r * a.nlive, nullptr, a.status + (size_t)r * a.nlive);
-        if (rc != GF_OK) return rc;
-    }
-    hipLaunchKernelGGL(k_ns_init_fix, grid, dim3(GF_BLOCK), 0, s->stream, a);
-    GFN_HIP(hipGetLastError());
-    s->initialised = 1;
+    hipLaunchKernelGGL(k_ns_init_fix, grid, dim3(GF_BLOCK), 0, s->rs.stream, a);
+    GF_HIP(hipGetLastError());
+    s->rs.initialised = 1;
     return GF_OK;
 }
 }  // namespace
@@ -567,48 +432,17 @@ int gf_nested_create(gf_model* const* models, int nruns, int nscan, const int32_
         nlive > NS_MAX_LIVE || batch < 1 || batch >= nlive || walks < 1 || (on_nonunitary != 0 && on_nonunitary != 1))
         return GF_ERR_INVALID_ARG;
     *out = nullptr;
-    const GfCommon* c0; const GfBsm* tb0; const double* pt0; void* stream0; int device0;
-    if (!models[0] || gf_model_internal(models[0], &c0, &tb0, &pt0, &stream0, &device0) != GF_OK) return GF_ERR_INVALID_ARG;
-    const int ndim = c0->ndim;
-    std::vector<int32_t> slot(GF_MAX_DIM, -1);
-    for (int k = 0; k < nscan; ++k) {
-        if (cols[k] < 0 || cols[k] >= ndim || slot[cols[k]] >= 0) return GF_ERR_INVALID_ARG;
-        slot[cols[k]] = k;
-    }
-    std::vector<GfCommon> hc(nruns);
-    std::vector<const GfBsm*> htb(nruns);
-    std::vector<const double*> hpt(nruns);
-    std::vector<double> hb((size_t)nruns * GF_MAX_DIM, 0.0);
-    int cus = 256, nbins_max = 0;
-    for (int r = 0; r < nruns; ++r) {
-        const GfCommon* c; int device, nb;
-        if (!models[r] || gf_model_constants(models[r], &c, &htb[r], &hpt[r], &device, &cus, &nb) != GF_OK || device != device0 ||
-            c->ndim != ndim || c->mode != c0->mode)
-            return nmsg(GF_ERR_INVALID_ARG, "gf_nested_create: every model must share device, ndim and mode with model 0");
-        hc[r] = *c;
-        if (nb > nbins_max) nbins_max = nb;
-        for (int d = 0; d < ndim; ++d) hb[(size_t)r * GF_MAX_DIM + d] = bases[(size_t)r * ndim + d];
-    }
     gf_nested* s = new (std::nothrow) gf_nested();
     if (!s) return GF_ERR_ALLOC;
-    s->models = new (std::nothrow) gf_model*[nruns];
-    if (!s->models) { delete s; return GF_ERR_ALLOC; }
-    for (int r = 0; r < nruns; ++r) s->models[r] = models[r];
-    s->stream = (hipStream_t)stream0; s->device = device0; s->cus = cus; s->mode = c0->mode;
     NsArgs& a = s->a;
-    a.seed = seed; a.tol = 0.01;
-    a.nruns = nruns; a.nlive = nlive; a.batch = batch; a.nscan = nscan; a.ndim = ndim; a.walks = walks; a.raise = on_nonunitary == 0;
-    a.nbins_max = nbins_max;
-    for (int d = 0; d < GF_MAX_DIM; ++d) a.slot[d] = slot[d];
+    const int rc = cube_runs_create(s->rs, a, models, nruns, nscan, cols, bases, seed, "gf_nested_create");
+    if (rc != GF_OK) { delete s; return rc; }
+    a.tol = 0.01;
+    a.nlive = nlive; a.batch = batch; a.walks = walks; a.raise = on_nonunitary == 0;
     const size_t R = nruns, K = nlive, B = batch, D = nscan, W = R * B;
-    hipError_t e = hipSetDevice(device0);
-    hipStream_t st = s->stream;
+    hipError_t e = hipSuccess;
+    hipStream_t st = s->rs.stream;
     auto al = [&](void** p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes); };
-    al((void**)&s->d_commons, sizeof(GfCommon) * R);
-    al((void**)&s->d_tbs, sizeof(void*) * R);
-    al((void**)&s->d_ptabs, sizeof(void*) * R);
-    al((void**)&s->d_run_ids, sizeof(uint64_t) * R);
-    al((void**)&s->d_bases, sizeof(double) * R * GF_MAX_DIM);
     al((void**)&a.runs, sizeof(NsRun) * R);
     al((void**)&a.lstar, sizeof(double) * R);
     al((void**)&a.nonunit, sizeof(uint32_t) * R);
@@ -621,48 +455,23 @@ int gf_nested_create(gf_model* const* models, int nruns, int nscan, const int32_
     al((void**)&a.wacc, sizeof(uint32_t) * W);
     al((void**)&a.wev, sizeof(uint32_t) * W);
     al((void**)&a.prop_u, sizeof(double) * W * D);
-    al((void**)&a.theta, sizeof(double) * R * K * ndim);
+    al((void**)&a.theta, sizeof(double) * R * K * a.ndim);
     al((void**)&a.status, sizeof(int32_t) * R * K);
-    al((void**)&s->d_state, sizeof(GfStepState));
-    if (s->mode == MODE_BSM_GAUSS) {
-        al((void**)&a.pq, sizeof(GfArbQueue) + sizeof(GfArbItem) * W);
-        al((void**)&a.pend_rows, sizeof(double) * W * GF_PEND_STRIDE);
-        al((void**)&s->d_ctl, sizeof(unsigned int) * 2 * W);
-    }
     std::vector<NsRun> hr(R);
-    std::vector<uint64_t> ids(R);
     for (size_t r = 0; r < R; ++r) {
         NsRun& x = hr[r];
         x.lnx = 0.0; x.lnz = -HUGE_VAL; x.h = 0.0; x.lmax = -HUGE_VAL; x.scale = 1.0; x.pvar = 0.0; x.nplat = 0;
         x.iter = 0; x.nevals = (int64_t)K; x.done = 0; x.failed = 0;
-        ids[r] = r;
     }
-    GfArbQueue qh;
-    std::memset(&qh, 0, sizeof(qh));
-    qh.cap = (unsigned int)W;
-    auto up = [&](void* dst, const void* src, size_t bytes) { if (e == hipSuccess) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st); };
-    up(s->d_commons, hc.data(), sizeof(GfCommon) * R);
-    up((void*)s->d_tbs, htb.data(), sizeof(void*) * R);
-    up((void*)s->d_ptabs, hpt.data(), sizeof(void*) * R);
-    up(s->d_run_ids, ids.data(), sizeof(uint64_t) * R);
-    up(s->d_bases, hb.data(), sizeof(double) * R * GF_MAX_DIM);
-    up(a.runs, hr.data(), sizeof(NsRun) * R);
+    if (e == hipSuccess) e = hipMemcpyAsync(a.runs, hr.data(), sizeof(NsRun) * R, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemsetAsync(a.nonunit, 0, sizeof(uint32_t) * R, st);
     if (e == hipSuccess) e = hipMemsetAsync(a.lstar, 0, sizeof(double) * R, st);
-    GfStepState hs;
-    std::memset(&hs, 0, sizeof(hs));
-    hs.thin = 1;
-    up(s->d_state, &hs, sizeof(hs));
-    if (s->mode == MODE_BSM_GAUSS) {
-        up(a.pq, &qh, offsetof(GfArbQueue, items));
-        if (e == hipSuccess) e = hipMemsetAsync(s->d_ctl, 0, sizeof(unsigned int) * 2 * W, st);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(st);                  // the host vectors go out of scope
-    if (e != hipSuccess) { const int rc = nfail(e, "gf_nested_create"); gf_nested_destroy(s); return rc; }
-    a.commons = s->d_commons; a.tbs = s->d_tbs; a.ptabs = s->d_ptabs; a.run_ids = s->d_run_ids; a.bases = s->d_bases;
+    if (e == hipSuccess) e = hipStreamSynchronize(st);                  // hr goes out of scope
+    if (e == hipSuccess) e = cube_runs_alloc_queue(s->rs, a, W);
+    if (e != hipSuccess) { const int rc2 = gf_hip_fail(e, "gf_nested_create"); gf_nested_destroy(s); return rc2; }
     GfSettleArgs& sa = s->sa;
-    sa.state = s->d_state; sa.pq = a.pq; sa.pend_rows = a.pend_rows; sa.ctl = s->d_ctl; sa.flags = a.nonunit;
-    sa.nchains = nruns; sa.nwalkers = 2 * batch; sa.ndim = ndim; sa.commons = s->d_commons; sa.tbs = s->d_tbs; sa.multi = 1;
+    cube_runs_settle_args(s->rs, a, 2 * batch, sa);
+    sa.flags = a.nonunit;
     sa.ns_lstar = a.lstar; sa.ns_prop_u = a.prop_u; sa.ns_wu = a.wu; sa.ns_wl = a.wl; sa.ns_wacc = a.wacc; sa.ns_wev = a.wev;
     sa.ns_nonunit = a.nonunit; sa.ns_nscan = nscan;
     *out = s;
@@ -672,11 +481,7 @@ int gf_nested_create(gf_model* const* models, int nruns, int nscan, const int32_
 int gf_nested_set_run_ids(gf_nested* s, const uint64_t* ids)
 {
     if (!s || !ids) return GF_ERR_INVALID_ARG;
-    if (s->initialised) return nmsg(GF_ERR_INVALID_ARG, "gf_nested_set_run_ids: before the first gf_nested_run");
-    GFN_HIP(hipSetDevice(s->device));
-    GFN_HIP(hipMemcpyAsync(s->d_run_ids, ids, sizeof(uint64_t) * (size_t)s->a.nruns, hipMemcpyHostToDevice, s->stream));
-    GFN_HIP(hipStreamSynchronize(s->stream));
-    return GF_OK;
+    return cube_runs_set_ids(s->rs, s->a, ids, "gf_nested_set_run_ids: before the first gf_nested_run");
 }
 
 int gf_nested_set_tolerance(gf_nested* s, double tol)
@@ -689,14 +494,11 @@ int gf_nested_set_tolerance(gf_nested* s, double tol)
 void gf_nested_destroy(gf_nested* s)
 {
     if (!s) return;
-    (void)hipSetDevice(s->device);
-    if (s->stream) (void)hipStreamSynchronize(s->stream);
     NsArgs& a = s->a;
-    void* ptrs[] = {s->d_commons, (void*)s->d_tbs, (void*)s->d_ptabs, s->d_run_ids, s->d_bases, a.runs, a.lstar, a.nonunit,
-                    a.live_u, a.live_l, a.chol, a.freed, a.wu, a.wl, a.wacc, a.wev, a.prop_u, a.theta, a.status, s->d_state,
-                    a.pq, a.pend_rows, s->d_ctl, a.dead_l, a.dead_w, a.dead_u};
+    cube_runs_free(s->rs, a);
+    void* ptrs[] = {a.runs, a.lstar, a.nonunit, a.live_u, a.live_l, a.chol, a.freed, a.wu, a.wl, a.wacc, a.wev, a.prop_u, a.theta,
+                    a.status, a.dead_l, a.dead_w, a.dead_u};
     for (void* p : ptrs) if (p) (void)hipFree(p);
-    delete[] s->models;
     delete s;
 }
 
@@ -705,32 +507,32 @@ void gf_nested_destroy(gf_nested* s)
 int gf_nested_run(gf_nested* s, int64_t max_iter)
 {
     if (!s || max_iter < 1) return GF_ERR_INVALID_ARG;
-    GFN_HIP(hipSetDevice(s->device));
+    GF_HIP(hipSetDevice(s->rs.device));
     NsArgs& a = s->a;
-    if (!s->initialised) { const int rc = ns_init(s); if (rc != GF_OK) return rc; }
-    const int lpw = gf_propose_lanes_per_walker(s->mode, (int64_t)a.nruns * a.batch, a.nbins_max, s->cus, "GF_NESTED_LPW");
+    if (!s->rs.initialised) { const int rc = ns_init(s); if (rc != GF_OK) return rc; }
+    const int lpw = gf_propose_lanes_per_walker(s->rs.mode, (int64_t)a.nruns * a.batch, a.nbins_max, s->rs.cus, "GF_NESTED_LPW");
     constexpr int check = 4;
     std::vector<NsRun> hr(a.nruns);
     for (;;) {
-        GFN_HIP(hipMemcpyAsync(hr.data(), a.runs, sizeof(NsRun) * a.nruns, hipMemcpyDeviceToHost, s->stream));
-        GFN_HIP(hipStreamSynchronize(s->stream));
+        GF_HIP(hipMemcpyAsync(hr.data(), a.runs, sizeof(NsRun) * a.nruns, hipMemcpyDeviceToHost, s->rs.stream));
+        GF_HIP(hipStreamSynchronize(s->rs.stream));
         bool all = true;
         int64_t most = 0;
         for (const NsRun& x : hr) { all = all && x.done; if (!x.done && x.iter > most) most = x.iter; }
         if (all) break;
-        if (most >= max_iter) return nmsg(GF_ERR_UNSUPPORTED, "gf_nested_run: max_iter reached before every run met its tolerance");
+        if (most >= max_iter) return gf_fail_msg(GF_ERR_UNSUPPORTED, "gf_nested_run: max_iter reached before every run met its tolerance");
         for (int i = 0; i < check; ++i) {
             const int rc = ns_grow_dead(s, s->launched + 1);
             if (rc != GF_OK) return rc;
-            hipLaunchKernelGGL(k_ns_select, dim3(a.nruns), dim3(NS_SEL_BLOCK), 0, s->stream, a);
-            GFN_HIP(hipGetLastError());
+            hipLaunchKernelGGL(k_ns_select, dim3(a.nruns), dim3(NS_SEL_BLOCK), 0, s->rs.stream, a);
+            GF_HIP(hipGetLastError());
             for (int step = 0; step < a.walks; ++step) {
                 a.step = step;
-                GFN_HIP(launch_walk_any(s->mode, lpw, a, s->stream));
-                if (s->mode == MODE_BSM_GAUSS) GFN_HIP(gf_launch_nested_settle(s->sa, s->cus, s->stream));
+                GF_HIP(launch_walk_any(s->rs.mode, lpw, a, s->rs.stream));
+                if (s->rs.mode == MODE_BSM_GAUSS) GF_HIP(gf_launch_nested_settle(s->sa, s->rs.cus, s->rs.stream));
             }
-            hipLaunchKernelGGL(k_ns_commit, dim3(a.nruns), dim3(GF_BLOCK), 0, s->stream, a);
-            GFN_HIP(hipGetLastError());
+            hipLaunchKernelGGL(k_ns_commit, dim3(a.nruns), dim3(GF_BLOCK), 0, s->rs.stream, a);
+            GF_HIP(hipGetLastError());
             s->launched += 1;
         }
     }
@@ -741,13 +543,13 @@ int gf_nested_result(gf_nested* s, double* lnz, double* lnz_err, double* info, d
                      uint32_t* nonunitary, int32_t* failed)
 {
     if (!s) return GF_ERR_INVALID_ARG;
-    GFN_HIP(hipSetDevice(s->device));
+    GF_HIP(hipSetDevice(s->rs.device));
     const int R = s->a.nruns;
     std::vector<NsRun> hr(R);
     std::vector<uint32_t> nu(R);
-    GFN_HIP(hipMemcpyAsync(hr.data(), s->a.runs, sizeof(NsRun) * R, hipMemcpyDeviceToHost, s->stream));
-    GFN_HIP(hipMemcpyAsync(nu.data(), s->a.nonunit, sizeof(uint32_t) * R, hipMemcpyDeviceToHost, s->stream));
-    GFN_HIP(hipStreamSynchronize(s->stream));
+    GF_HIP(hipMemcpyAsync(hr.data(), s->a.runs, sizeof(NsRun) * R, hipMemcpyDeviceToHost, s->rs.stream));
+    GF_HIP(hipMemcpyAsync(nu.data(), s->a.nonunit, sizeof(uint32_t) * R, hipMemcpyDeviceToHost, s->rs.stream));
+    GF_HIP(hipStreamSynchronize(s->rs.stream));
     for (int r = 0; r < R; ++r) {
         const NsRun& x = hr[r];
         if (lnz) lnz[r] = x.lnz;
@@ -767,11 +569,11 @@ int gf_nested_result(gf_nested* s, double* lnz, double* lnz_err, double* info, d
 int gf_internal_nested_state(gf_nested* s, double* scale, double* lnx)
 {
     if (!s) return GF_ERR_INVALID_ARG;
-    GFN_HIP(hipSetDevice(s->device));
+    GF_HIP(hipSetDevice(s->rs.device));
     const int R = s->a.nruns;
     std::vector<NsRun> hr(R);
-    GFN_HIP(hipMemcpyAsync(hr.data(), s->a.runs, sizeof(NsRun) * R, hipMemcpyDeviceToHost, s->stream));
-    GFN_HIP(hipStreamSynchronize(s->stream));
+    GF_HIP(hipMemcpyAsync(hr.data(), s->a.runs, sizeof(NsRun) * R, hipMemcpyDeviceToHost, s->rs.stream));
+    GF_HIP(hipStreamSynchronize(s->rs.stream));
     for (int r = 0; r < R; ++r) {
         if (scale) scale[r] = hr[r].scale;
         if (lnx) lnx[r] = hr[r].lnx;
@@ -785,32 +587,32 @@ int gf_internal_nested_state(gf_nested* s, double* scale, double* lnx)
 int gf_nested_get_dead(gf_nested* s, int run, int64_t cap, double* lnl, double* lnw, double* cube, int64_t* n)
 {
     if (!s || !n || run < 0 || run >= s->a.nruns) return GF_ERR_INVALID_ARG;
-    GFN_HIP(hipSetDevice(s->device));
+    GF_HIP(hipSetDevice(s->rs.device));
     const NsArgs& a = s->a;
     NsRun x;
-    GFN_HIP(hipMemcpyAsync(&x, a.runs + run, sizeof(NsRun), hipMemcpyDeviceToHost, s->stream));
-    GFN_HIP(hipStreamSynchronize(s->stream));
+    GF_HIP(hipMemcpyAsync(&x, a.runs + run, sizeof(NsRun), hipMemcpyDeviceToHost, s->rs.stream));
+    GF_HIP(hipStreamSynchronize(s->rs.stream));
     const int64_t nd = x.iter * a.batch, total = nd + a.nlive;
     *n = total;
     if (!lnl && !lnw && !cube) return GF_OK;
-    if (cap < total) return nmsg(GF_ERR_INVALID_ARG, "gf_nested_get_dead: cap is smaller than the number of rows");
+    if (cap < total) return gf_fail_msg(GF_ERR_INVALID_ARG, "gf_nested_get_dead: cap is smaller than the number of rows");
     const size_t B = a.batch, D = a.nscan, R = a.nruns;
     for (int64_t it = 0; it < x.iter; ++it) {
         const size_t off = ((size_t)it * R + run) * B;
-        if (lnl) GFN_HIP(hipMemcpyAsync(lnl + it * B, a.dead_l + off, sizeof(double) * B, hipMemcpyDeviceToHost, s->stream));
-        if (lnw) GFN_HIP(hipMemcpyAsync(lnw + it * B, a.dead_w + off, sizeof(double) * B, hipMemcpyDeviceToHost, s->stream));
-        if (cube) GFN_HIP(hipMemcpyAsync(cube + it * B * D, a.dead_u + off * D, sizeof(double) * B * D, hipMemcpyDeviceToHost, s->stream));
+        if (lnl) GF_HIP(hipMemcpyAsync(lnl + it * B, a.dead_l + off, sizeof(double) * B, hipMemcpyDeviceToHost, s->rs.stream));
+        if (lnw) GF_HIP(hipMemcpyAsync(lnw + it * B, a.dead_w + off, sizeof(double) * B, hipMemcpyDeviceToHost, s->rs.stream));
+        if (cube) GF_HIP(hipMemcpyAsync(cube + it * B * D, a.dead_u + off * D, sizeof(double) * B * D, hipMemcpyDeviceToHost, s->rs.stream));
     }
     double* ll = lnl ? lnl + nd : (double*)std::malloc(sizeof(double) * a.nlive);
     if (!ll) return GF_ERR_ALLOC;
-    GFN_HIP(hipMemcpyAsync(ll, a.live_l + (size_t)run * a.nlive, sizeof(double) * a.nlive, hipMemcpyDeviceToHost, s->stream));
-    if (cube) GFN_HIP(hipMemcpyAsync(cube + nd * D, a.live_u + (size_t)run * a.nlive * D, sizeof(double) * a.nlive * D,
-                                     hipMemcpyDeviceToHost, s->stream));
-    const hipError_t e = hipStreamSynchronize(s->stream);
+    GF_HIP(hipMemcpyAsync(ll, a.live_l + (size_t)run * a.nlive, sizeof(double) * a.nlive, hipMemcpyDeviceToHost, s->rs.stream));
+    if (cube) GF_HIP(hipMemcpyAsync(cube + nd * D, a.live_u + (size_t)run * a.nlive * D, sizeof(double) * a.nlive * D,
+                                     hipMemcpyDeviceToHost, s->rs.stream));
+    const hipError_t e = hipStreamSynchronize(s->rs.stream);
     if (e == hipSuccess && lnw)
         for (int k = 0; k < a.nlive; ++k) lnw[nd + k] = x.lnx - std::log((double)a.nlive) + ll[k];
     if (!lnl) std::free(ll);
-    if (e != hipSuccess) return nfail(e, "gf_nested_get_dead");
+    if (e != hipSuccess) return gf_hip_fail(e, "gf_nested_get_dead");
     return GF_OK;
 }
 

@@ -1,11 +1,13 @@
 // Device pieces shared by the ensemble sampler (gf_sampler.hip), the nested sampler (gf_nested.hip) and the maximiser
 // (gf_simplex.hip): the Philox4x32-10 block behind the random streams, the evaluation of one proposal with its unitarity verdict,
-// and the lanes-per-walker rule of the nested sampler's and the maximiser's evaluation kernels.
+// the parking of an undecided one (the nested sampler and the maximiser; stretch_body keeps its own copy, which also writes the
+// acceptance threshold), and the lanes-per-walker rule of the nested sampler's and the maximiser's evaluation kernels.
 #pragma once
 #include <cstdlib>
 
 #include "gf_device.hpp"
 #include "gf_bsm_device.hpp"
+#include "gf_launch.h"
 
 namespace {
 using namespace gfdev;
@@ -57,6 +59,25 @@ __device__ __forceinline__ double proposal_lnprob(const GfCommon& c, const GfBsm
         eval_walker<NDIM, MODE, 0, false>(c, ctab, row, ndim, val, fr, st);
     }
     return val;
+}
+
+// Parks a proposal whose unitarity verdict the in-kernel tiers cannot settle: theta and its lnprob go to row t of `pend_rows`,
+// {t, undecided bins} onto `pq`, for the settle kernel next in stream order
+__device__ __forceinline__ void park_proposal(GfArbQueue* pq, double* pend_rows, int64_t t, const double* row, int ndim, double lnq,
+                                              unsigned long long pending)
+{
+    double* dst = pend_rows + (size_t)t * GF_PEND_STRIDE;
+    for (int d = 0; d < ndim; ++d) dst[d] = row[d];
+    dst[GF_MAX_DIM] = lnq;
+    const unsigned int at = atomicAdd(&pq->count, 1u);
+    if (at < pq->cap) {
+        GfArbItem it;
+        it.walker = (unsigned long long)t;
+        it.mask = pending;
+        pq->items[at] = it;
+    } else {
+        pq->overflow = 1u;                                   // capacity = every proposal of a step: cannot happen
+    }
 }
 
 // Lanes per walker of a step of `walkers` BSM walkers (the cost model of gf_sampler.hip's lanes_per_walker, restricted to the

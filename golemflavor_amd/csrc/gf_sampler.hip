@@ -24,10 +24,7 @@
 #include <cstddef>
 #include <new>
 
-#include "../../include/golemflavor_hip.h"
-#include "gf_consts.h"
-
-extern "C" const char* gf_internal_env(const char* name, int affects_results);   // gf_capi.hip: getenv with a record
+#include "gf_host.h"
 #include "gf_device.hpp"
 #include "gf_bsm_device.hpp"
 #include "gf_launch.h"
@@ -98,14 +95,7 @@ __device__ __forceinline__ void stretch_body(const GfCommon& c, const GfBsm* __r
     __shared__ __attribute__((aligned(16))) double tiles[GF_WAVES_PER_BLOCK][GF_WAVE * ND];
     __shared__ __attribute__((aligned(16))) double ctab[GF_MAX_DIM * 4 + 20];
     double* ttab = ctab + GF_MAX_DIM * 4;
-    if (threadIdx.x < GF_MAX_DIM * 4) ctab[threadIdx.x] = ptab[threadIdx.x];
-    if (MODE == MODE_BSM_GAUSS && threadIdx.x >= 64 && threadIdx.x < 64 + 18) {
-        const int k = threadIdx.x - 64, e = k >> 1;
-        const int idx = e == 0 ? 0 : e == 1 ? 4 : e == 2 ? 8 : e <= 4 ? 1 : e <= 6 ? 2 : 5;
-        const bool im = e == 4 || e == 6 || e == 8;
-        const double* srcp = (k & 1) ? (im ? tb->t2_im : tb->t2_re) : (im ? tb->t1_im : tb->t1_re);
-        ttab[k] = srcp[idx];
-    }
+    load_eval_tables(ctab, ptab, tb, MODE == MODE_BSM_GAUSS);
     __syncthreads();
 
     const int ndim = NDIM ? NDIM : c.ndim;
@@ -739,14 +729,7 @@ __global__ __launch_bounds__(CH_BLOCK) void k_stretch_chain(const ChainArgs s)
     const GfBsm* __restrict__ tb = s.nmodels > 1 ? s.tbs[chain] : s.tb;
     const double* __restrict__ ptab = s.ptabs[s.nmodels > 1 ? chain : 0];
     double* ttab = ctab + GF_MAX_DIM * 4;
-    if (threadIdx.x < GF_MAX_DIM * 4) ctab[threadIdx.x] = ptab[threadIdx.x];
-    if (threadIdx.x >= 64 && threadIdx.x < 64 + 18) {                                // as stretch_body: the texture's two projectors
-        const int k = threadIdx.x - 64, e = k >> 1;
-        const int idx = e == 0 ? 0 : e == 1 ? 4 : e == 2 ? 8 : e <= 4 ? 1 : e <= 6 ? 2 : 5;
-        const bool im = e == 4 || e == 6 || e == 8;
-        const double* srcp = (k & 1) ? (im ? tb->t2_im : tb->t2_re) : (im ? tb->t1_im : tb->t1_re);
-        ttab[k] = srcp[idx];
-    }
+    load_eval_tables(ctab, ptab, tb, true);
     for (int i = threadIdx.x; i < 2 * CH_BLOCK; i += CH_BLOCK) pk_ctl[i] = 0u;
     if (threadIdx.x == 0) lz_n = 0u;
     __syncthreads();
@@ -972,14 +955,7 @@ __global__ __launch_bounds__(CH_BLOCK) void k_stretch_flow(const ChainArgs s)
     const GfBsm* __restrict__ tb = s.nmodels > 1 ? s.tbs[chain] : s.tb;
     const double* __restrict__ ptab = s.ptabs[s.nmodels > 1 ? chain : 0];
     double* ttab = ctab + GF_MAX_DIM * 4;
-    if (threadIdx.x < GF_MAX_DIM * 4) ctab[threadIdx.x] = ptab[threadIdx.x];
-    if (threadIdx.x >= 64 && threadIdx.x < 64 + 18) {
-        const int k = threadIdx.x - 64, e = k >> 1;
-        const int idx = e == 0 ? 0 : e == 1 ? 4 : e == 2 ? 8 : e <= 4 ? 1 : e <= 6 ? 2 : 5;
-        const bool im = e == 4 || e == 6 || e == 8;
-        const double* srcp = (k & 1) ? (im ? tb->t2_im : tb->t2_re) : (im ? tb->t1_im : tb->t1_re);
-        ttab[k] = srcp[idx];
-    }
+    load_eval_tables(ctab, ptab, tb, true);
     const int ndim = NDIM ? NDIM : c.ndim;
     const int nw = s.nwalkers, nhalf = nw / 2;
     const unsigned int U_END = (unsigned int)s.nsteps;
@@ -1316,15 +1292,8 @@ struct HostSink {
 double g_last_run_to_host_times[8] = {};
 double g_last_run_prologue[4] = {};             // the last gf_sampler_run: [0] growing the chain buffers, [1] capturing + instantiating the graph (seconds)
 
-// accessors implemented in gf_capi.hip (gf_model is private to it)
+// more of gf_capi.hip's internals (the model accessors are in gf_host.h)
 extern "C" {
-int gf_model_internal(gf_model* m, const GfCommon** c, const GfBsm** d_bsm, const double** d_ptab, void** stream,
-                      int* device);
-int gf_model_constants(gf_model* m, const GfCommon** c, const GfBsm** d_bsm, const double** d_ptab, int* device, int* cus,
-                       int* nbins);
-void gf_internal_set_error(const char* msg);
-int gf_model_lnprob_on(gf_model* m, void* stream, const double* d_theta, int layout, int64_t n, double* d_lnprob,
-                       double* d_fr, int32_t* d_status);
 void gf_internal_full_arbitration_grids(int device, void* stream, int on);
 int gf_internal_borrow_stream(int device, void** stream);
 int gf_internal_borrow_copy_stream(int device, void** stream);
@@ -1342,21 +1311,6 @@ int gf_internal_d2h_pipe_open(int device, void* stream, gf_d2h_pipe** out);
 int gf_internal_d2h_pipe_rows(gf_d2h_pipe* p, void* dst_host, size_t dpitch, const void* src_dev, size_t spitch, size_t width, size_t height);
 int gf_internal_d2h_pipe_close(gf_d2h_pipe* p);
 }
-
-namespace {
-thread_local char g_serr[256] = "";     // composed here, published through gf_last_hip_error()
-int sfail(hipError_t e, const char* what)
-{
-    std::snprintf(g_serr, sizeof(g_serr), "%s: %s", what, hipGetErrorString(e));
-    gf_internal_set_error(g_serr);
-    return GF_ERR_HIP;
-}
-#define GFS_HIP(call)                              \
-    do {                                           \
-        hipError_t e_ = (call);                    \
-        if (e_ != hipSuccess) return sfail(e_, #call); \
-    } while (0)
-}  // namespace
 
 extern "C" {
 
@@ -1408,7 +1362,7 @@ int gf_sampler_create(gf_model* m, int nchains, int nwalkers, uint64_t seed, dou
     if (e == hipSuccess) e = hipMemcpyAsync(s->d_commons, c, sizeof(GfCommon), hipMemcpyHostToDevice, st0);
     if (e == hipSuccess) e = hipMemcpyAsync((void*)s->d_ptabs, &ptab, sizeof(void*), hipMemcpyHostToDevice, st0);
     if (e == hipSuccess) e = hipStreamSynchronize(st0);
-    if (e != hipSuccess) { int rc = sfail(e, "gf_sampler_create"); gf_sampler_destroy(s); return rc; }
+    if (e != hipSuccess) { int rc = gf_hip_fail(e, "gf_sampler_create"); gf_sampler_destroy(s); return rc; }
     *out = s;
     return GF_OK;
 }
@@ -1470,10 +1424,8 @@ int gf_sampler_create_multi(gf_model* const* models, int nchains, int nwalkers, 
         const GfCommon* c; int device, cus, nbins;
         if (gf_model_constants(models[ch], &c, &htb[ch], &hpt[ch], &device, &cus, &nbins) != GF_OK || device != device0 ||
             c->ndim != c0->ndim || c->mode != c0->mode) {
-            std::snprintf(g_serr, sizeof(g_serr), "gf_sampler_create_multi: model %d differs from model 0 in device, ndim or mode", ch);
-            gf_internal_set_error(g_serr);
             cleanup(); delete[] keep;
-            return GF_ERR_INVALID_ARG;
+            return gf_fail_msg(GF_ERR_INVALID_ARG, "gf_sampler_create_multi: model %d differs from model 0 in device, ndim or mode", ch);
         }
         hc[ch] = *c;
         keep[ch] = models[ch];
@@ -1495,7 +1447,7 @@ int gf_sampler_create_multi(gf_model* const* models, int nchains, int nwalkers, 
     if (e == hipSuccess) e = hipMemcpyAsync((void*)s->d_ptabs, hpt, sizeof(void*) * nchains, hipMemcpyHostToDevice, st0);
     if (e == hipSuccess) e = hipStreamSynchronize(st0);               // the host arrays are freed next
     cleanup();
-    if (e != hipSuccess) { rc = sfail(e, "gf_sampler_create_multi"); gf_sampler_destroy(s); return rc; }
+    if (e != hipSuccess) { rc = gf_hip_fail(e, "gf_sampler_create_multi"); gf_sampler_destroy(s); return rc; }
     *out = s;
     return GF_OK;
 }
@@ -1506,12 +1458,12 @@ int gf_sampler_set_stream_ids(gf_sampler* s, const uint64_t* ids)
     if (!s || !ids) return GF_ERR_INVALID_ARG;
     const GfCommon* c; const GfBsm* tb; const double* ptab; void* stream; int device;
     if (gf_model_internal(s->model, &c, &tb, &ptab, &stream, &device) != GF_OK) return GF_ERR_INVALID_ARG;
-    GFS_HIP(hipSetDevice(device));
+    GF_HIP(hipSetDevice(device));
     hipStream_t st = (hipStream_t)stream;
-    GFS_HIP(hipStreamSynchronize(st));
-    if (!s->d_stream_ids) GFS_HIP(hipMalloc((void**)&s->d_stream_ids, sizeof(uint64_t) * (size_t)s->nchains));
-    GFS_HIP(hipMemcpyAsync(s->d_stream_ids, ids, sizeof(uint64_t) * (size_t)s->nchains, hipMemcpyHostToDevice, st));
-    GFS_HIP(hipStreamSynchronize(st));
+    GF_HIP(hipStreamSynchronize(st));
+    if (!s->d_stream_ids) GF_HIP(hipMalloc((void**)&s->d_stream_ids, sizeof(uint64_t) * (size_t)s->nchains));
+    GF_HIP(hipMemcpyAsync(s->d_stream_ids, ids, sizeof(uint64_t) * (size_t)s->nchains, hipMemcpyHostToDevice, st));
+    GF_HIP(hipStreamSynchronize(st));
     if (s->graph) { (void)hipGraphExecDestroy(s->graph); s->graph = nullptr; }     // its kernel arguments froze the old pointer
     return GF_OK;
 }
@@ -1522,12 +1474,12 @@ int gf_sampler_set_state(gf_sampler* s, const double* pos)
     if (!s || !pos) return GF_ERR_INVALID_ARG;
     const GfCommon* c; const GfBsm* tb; const double* ptab; void* stream; int device;
     gf_model_internal(s->model, &c, &tb, &ptab, &stream, &device);
-    GFS_HIP(hipSetDevice(device));
+    GF_HIP(hipSetDevice(device));
     const size_t nw = (size_t)s->nchains * s->nwalkers;
-    GFS_HIP(hipMemcpyAsync(s->d_pos, pos, sizeof(double) * nw * s->ndim, hipMemcpyHostToDevice, (hipStream_t)stream));
+    GF_HIP(hipMemcpyAsync(s->d_pos, pos, sizeof(double) * nw * s->ndim, hipMemcpyHostToDevice, (hipStream_t)stream));
     // BSM posteriors: with the unitarity status, so that a start position the reference would have raised on is treated as such
     int32_t* d_st = nullptr;
-    if (c->mode == MODE_BSM_GAUSS) GFS_HIP(hipMalloc((void**)&d_st, sizeof(int32_t) * nw));
+    if (c->mode == MODE_BSM_GAUSS) GF_HIP(hipMalloc((void**)&d_st, sizeof(int32_t) * nw));
     int rc = GF_OK;
     if (!s->models) {
         rc = gf_model_lnprob_on(s->model, stream, s->d_pos, GF_LAYOUT_AOS, (int64_t)nw, s->d_lnp, nullptr, d_st);
@@ -1546,7 +1498,7 @@ int gf_sampler_set_state(gf_sampler* s, const double* pos)
     if (d_st) (void)hipFree(d_st);
     if (rc != GF_OK) return rc;
     if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) return sfail(e, "gf_sampler_set_state");
+    if (e != hipSuccess) return gf_hip_fail(e, "gf_sampler_set_state");
     return gf_internal_check_overflow(device, stream);
 }
 
@@ -1555,12 +1507,12 @@ int gf_sampler_reset(gf_sampler* s)
     if (!s) return GF_ERR_INVALID_ARG;
     const GfCommon* c; const GfBsm* tb; const double* ptab; void* stream; int device;
     gf_model_internal(s->model, &c, &tb, &ptab, &stream, &device);
-    GFS_HIP(hipSetDevice(device));
-    GFS_HIP(hipStreamSynchronize((hipStream_t)stream));
-    GFS_HIP(hipMemsetAsync(s->d_naccept, 0, sizeof(uint32_t) * (size_t)s->nchains * s->nwalkers, (hipStream_t)stream));
-    GFS_HIP(hipMemsetAsync(s->d_flags, 0, sizeof(uint32_t) * 4, (hipStream_t)stream));
-    if (s->d_chain_stats) GFS_HIP(hipMemsetAsync(s->d_chain_stats, 0, sizeof(unsigned long long) * 8 * (size_t)s->nchains, (hipStream_t)stream));
-    GFS_HIP(hipStreamSynchronize((hipStream_t)stream));
+    GF_HIP(hipSetDevice(device));
+    GF_HIP(hipStreamSynchronize((hipStream_t)stream));
+    GF_HIP(hipMemsetAsync(s->d_naccept, 0, sizeof(uint32_t) * (size_t)s->nchains * s->nwalkers, (hipStream_t)stream));
+    GF_HIP(hipMemsetAsync(s->d_flags, 0, sizeof(uint32_t) * 4, (hipStream_t)stream));
+    if (s->d_chain_stats) GF_HIP(hipMemsetAsync(s->d_chain_stats, 0, sizeof(unsigned long long) * 8 * (size_t)s->nchains, (hipStream_t)stream));
+    GF_HIP(hipStreamSynchronize((hipStream_t)stream));
     s->nstored = 0;
     s->steps_since_reset = 0;
     return GF_OK;
@@ -1657,7 +1609,7 @@ int gf_sampler_run(gf_sampler* s, int64_t nsteps, int thin, int store)
     if (!s || nsteps < 0 || thin < 1) return GF_ERR_INVALID_ARG;
     const GfCommon* c; const GfBsm* tb; const double* ptab; void* stream; int device;
     gf_model_internal(s->model, &c, &tb, &ptab, &stream, &device);
-    GFS_HIP(hipSetDevice(device));
+    GF_HIP(hipSetDevice(device));
     hipStream_t st = (hipStream_t)stream;
     const size_t nw = (size_t)s->nchains * s->nwalkers;
     if (store) {
@@ -1667,13 +1619,13 @@ int gf_sampler_run(gf_sampler* s, int64_t nsteps, int thin, int store)
             int64_t cap = s->nstore_cap ? s->nstore_cap : 64;
             while (cap < need) cap *= 2;
             double *nc = nullptr, *nl = nullptr;
-            GFS_HIP(hipStreamSynchronize(st));
+            GF_HIP(hipStreamSynchronize(st));
             const auto t_grow = std::chrono::steady_clock::now();
             struct Grow { std::chrono::steady_clock::time_point t0; ~Grow() { g_last_run_prologue[0] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); } } grow_{t_grow};
-            GFS_HIP(hipMalloc((void**)&nc, sizeof(double) * nw * s->ndim * cap));
+            GF_HIP(hipMalloc((void**)&nc, sizeof(double) * nw * s->ndim * cap));
             {
                 hipError_t e_ = hipMalloc((void**)&nl, sizeof(double) * nw * cap);
-                if (e_ != hipSuccess) { (void)hipFree(nc); return sfail(e_, "hipMalloc(lnprob chain)"); }
+                if (e_ != hipSuccess) { (void)hipFree(nc); return gf_hip_fail(e_, "hipMalloc(lnprob chain)"); }
             }
             if (s->nstored > 0) {
                 // every chain's stored prefix in one strided copy: row = chain, pitch = old / new chain stride
@@ -1684,7 +1636,7 @@ int gf_sampler_run(gf_sampler* s, int64_t nsteps, int thin, int store)
                     e_ = hipMemcpy2DAsync(nl, lrow * cap, s->d_lnp_chain, lrow * s->nstore_cap, lrow * s->nstored, s->nchains,
                                           hipMemcpyDeviceToDevice, st);
                 if (e_ == hipSuccess) e_ = hipStreamSynchronize(st);                  // the old buffers are freed next
-                if (e_ != hipSuccess) { (void)hipFree(nc); (void)hipFree(nl); return sfail(e_, "chain repack"); }
+                if (e_ != hipSuccess) { (void)hipFree(nc); (void)hipFree(nl); return gf_hip_fail(e_, "chain repack"); }
             }
             if (s->d_chain) (void)hipFree(s->d_chain);
             if (s->d_lnp_chain) (void)hipFree(s->d_lnp_chain);
@@ -1697,9 +1649,9 @@ int gf_sampler_run(gf_sampler* s, int64_t nsteps, int thin, int store)
     StepState& hs = s->h_state;                   // member: outlives the asynchronous upload
     hs.iteration_base = s->iteration; hs.run_step_base = 0; hs.store_base = s->nstored;
     hs.store = store ? 1 : 0; hs.thin = thin;
-    GFS_HIP(hipStreamSynchronize(st));          // earlier runs must be done with the counters
+    GF_HIP(hipStreamSynchronize(st));          // earlier runs must be done with the counters
     s->flight_enq = s->flight_done = 0;         // (so nothing of an earlier run is in flight either)
-    GFS_HIP(hipMemcpyAsync(s->d_state, &hs, sizeof(hs), hipMemcpyHostToDevice, st));
+    GF_HIP(hipMemcpyAsync(s->d_state, &hs, sizeof(hs), hipMemcpyHostToDevice, st));
     StretchArgs a;
     a.state = s->d_state;
     a.pos = s->d_pos; a.lnp = s->d_lnp; a.naccept = s->d_naccept; a.flags = s->d_flags;
@@ -1764,7 +1716,7 @@ int gf_sampler_run(gf_sampler* s, int64_t nsteps, int thin, int store)
                 pa.store_base = s->nstored + (done_p + thin - 1) / thin;
                 pa.nsteps = count;
                 hipError_t e = launch_persist(c->mode, s->ndim, s->nchains, threads, lds, pa, st);
-                if (e != hipSuccess) return sfail(e, "persistent stretch launch");
+                if (e != hipSuccess) return gf_hip_fail(e, "persistent stretch launch");
                 done_p += count;
             }
             s->iteration += (uint64_t)nsteps;
@@ -1790,25 +1742,25 @@ int gf_sampler_run(gf_sampler* s, int64_t nsteps, int thin, int store)
     bool flow = false;                                                   // per chain as a dataflow (k_stretch_flow) or half-step by half-step (k_stretch_chain)
     auto chain_block = [&](int64_t count) -> int {                       // `count` steps from `done` on, one launch
         hipError_t e = flight_admit(s);
-        if (e != hipSuccess) return sfail(e, "block in flight");
+        if (e != hipSuccess) return gf_hip_fail(e, "block in flight");
         ca.iteration_base = s->iteration + (uint64_t)done;
         ca.run_step_base = done;
         ca.nsteps = (int32_t)count;
         e = launch_chain(s->ndim, s->nchains, ca, st, flow);
-        if (e != hipSuccess) return sfail(e, "chain launch");
+        if (e != hipSuccess) return gf_hip_fail(e, "chain launch");
         done += count;
         e = flight_mark(s, st, store ? s->nstored + (done + thin - 1) / thin : s->nstored);
-        if (e != hipSuccess) return sfail(e, "hipEventRecord");
+        if (e != hipSuccess) return gf_hip_fail(e, "hipEventRecord");
         return GF_OK;
     };
     auto grid_block = [&](int count) -> int {                            // the same with the grid kernels, launched one by one
         hipError_t e = flight_admit(s);
-        if (e != hipSuccess) return sfail(e, "block in flight");
+        if (e != hipSuccess) return gf_hip_fail(e, "block in flight");
         e = steps(count);
-        if (e != hipSuccess) return sfail(e, "stretch launch");
+        if (e != hipSuccess) return gf_hip_fail(e, "stretch launch");
         done += count;
         e = flight_mark(s, st, store ? hs.store_base + (done + thin - 1) / thin : hs.store_base);
-        if (e != hipSuccess) return sfail(e, "hipEventRecord");
+        if (e != hipSuccess) return gf_hip_fail(e, "hipEventRecord");
         return GF_OK;
     };
     if (small_bsm) {
@@ -1825,10 +1777,10 @@ int gf_sampler_run(gf_sampler* s, int64_t nsteps, int thin, int store)
                 int64_t cap = ((int64_t)64 << 20) / ((int64_t)s->nchains * (int64_t)(sizeof(double) * GF_PEND_STRIDE + 8));
                 if (cap > 1024) cap = 1024;
                 if (cap < 2 * pass) cap = 2 * pass;
-                GFS_HIP(hipMalloc((void**)&s->d_lazy_rows, sizeof(double) * GF_PEND_STRIDE * (size_t)cap * s->nchains));
+                GF_HIP(hipMalloc((void**)&s->d_lazy_rows, sizeof(double) * GF_PEND_STRIDE * (size_t)cap * s->nchains));
                 {
                     hipError_t e_ = hipMalloc((void**)&s->d_lazy_mask, sizeof(unsigned long long) * (size_t)cap * s->nchains);
-                    if (e_ != hipSuccess) { (void)hipFree(s->d_lazy_rows); s->d_lazy_rows = nullptr; return sfail(e_, "hipMalloc(lazy list)"); }
+                    if (e_ != hipSuccess) { (void)hipFree(s->d_lazy_rows); s->d_lazy_rows = nullptr; return gf_hip_fail(e_, "hipMalloc(lazy list)"); }
                 }
                 s->lazy_cap = (int)cap;
                 if (hipMalloc((void**)&s->d_chain_stats, sizeof(unsigned long long) * 8 * (size_t)s->nchains) == hipSuccess)
@@ -1850,7 +1802,7 @@ int gf_sampler_run(gf_sampler* s, int64_t nsteps, int thin, int store)
                 if (e_ == hipSuccess) e_ = hipMalloc((void**)&s->d_lv, sizeof(double) * FLOW_VERS * nwk);
                 if (e_ == hipSuccess) e_ = hipMalloc((void**)&s->d_frows, sizeof(double) * GF_PEND_STRIDE * nwk);
                 if (e_ == hipSuccess) e_ = hipMalloc((void**)&s->d_fterms, sizeof(double) * Team9::LANES * 8 * nwk);
-                if (e_ != hipSuccess) return sfail(e_, "hipMalloc(dataflow sampler)");
+                if (e_ != hipSuccess) return gf_hip_fail(e_, "hipMalloc(dataflow sampler)");
             }
             ca.pv = s->d_pv; ca.lv = s->d_lv; ca.frows = s->d_frows; ca.fterms = s->d_fterms;
 #endif
@@ -1860,7 +1812,7 @@ int gf_sampler_run(gf_sampler* s, int64_t nsteps, int thin, int store)
             double us[2] = {0.0, 0.0};
             for (int which = 0; which < 2; ++which)
                 for (int rep = 0; rep < 2; ++rep) {
-                    GFS_HIP(hipStreamSynchronize(st));
+                    GF_HIP(hipStreamSynchronize(st));
                     const auto t0 = std::chrono::steady_clock::now();
                     int rc = GF_OK;
                     if (which == 0) {
@@ -1870,7 +1822,7 @@ int gf_sampler_run(gf_sampler* s, int64_t nsteps, int thin, int store)
                         rc = grid_block((int)CHAIN_STEPS);
                     }
                     if (rc != GF_OK) return rc;
-                    GFS_HIP(hipStreamSynchronize(st));
+                    GF_HIP(hipStreamSynchronize(st));
                     if (rep == 1) us[which] = 1e6 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
                 }
             s->probe_us[0] = us[0]; s->probe_us[1] = us[1];
@@ -1917,28 +1869,28 @@ int gf_sampler_run(gf_sampler* s, int64_t nsteps, int thin, int store)
         }
         while (s->graph && nsteps - done >= GRAPH_STEPS) {
             hipError_t e = flight_admit(s);
-            if (e != hipSuccess) return sfail(e, "block in flight");
+            if (e != hipSuccess) return gf_hip_fail(e, "block in flight");
             const auto t_g = std::chrono::steady_clock::now();
             e = hipGraphLaunch(s->graph, st);
             if (s->sink) {
                 const double d = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_g).count();
                 s->sink->t[5] += d; if (d > s->sink->t[6]) s->sink->t[6] = d;
             }
-            if (e != hipSuccess) return sfail(e, "hipGraphLaunch");
+            if (e != hipSuccess) return gf_hip_fail(e, "hipGraphLaunch");
             done += GRAPH_STEPS;
             e = flight_mark(s, st, store ? hs.store_base + (done + thin - 1) / thin : hs.store_base);
-            if (e != hipSuccess) return sfail(e, "hipEventRecord");
+            if (e != hipSuccess) return gf_hip_fail(e, "hipEventRecord");
         }
     }
     while (done < nsteps) {
         const int count = (int)((nsteps - done < 64) ? (nsteps - done) : 64);
         hipError_t e = flight_admit(s);
-        if (e != hipSuccess) return sfail(e, "block in flight");
+        if (e != hipSuccess) return gf_hip_fail(e, "block in flight");
         e = steps(count);
-        if (e != hipSuccess) return sfail(e, "stretch launch");
+        if (e != hipSuccess) return gf_hip_fail(e, "stretch launch");
         done += count;
         e = flight_mark(s, st, store ? hs.store_base + (done + thin - 1) / thin : hs.store_base);
-        if (e != hipSuccess) return sfail(e, "hipEventRecord");
+        if (e != hipSuccess) return gf_hip_fail(e, "hipEventRecord");
     }
     s->iteration += (uint64_t)nsteps;
     s->steps_since_reset += nsteps;
@@ -1964,7 +1916,7 @@ int gf_sampler_run_to_host(gf_sampler* s, int64_t nsteps, int thin, double* chai
     if (!s || !chain || nsteps < 0 || thin < 1) return GF_ERR_INVALID_ARG;
     const GfCommon* c; const GfBsm* tb; const double* ptab; void* stream; int device;
     if (gf_model_internal(s->model, &c, &tb, &ptab, &stream, &device) != GF_OK) return GF_ERR_INVALID_ARG;
-    GFS_HIP(hipSetDevice(device));
+    GF_HIP(hipSetDevice(device));
     void* copy_stream = nullptr;
     int rc = gf_internal_borrow_copy_stream(device, &copy_stream);
     if (rc != GF_OK) return rc;
@@ -2001,7 +1953,7 @@ int gf_sampler_run_to_host(gf_sampler* s, int64_t nsteps, int thin, double* chai
     if (rc != GF_OK) return rc;
     if (sink.rc != GF_OK) return sink.rc;
     if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) return sfail(e, "gf_sampler_run_to_host");
+    if (e != hipSuccess) return gf_hip_fail(e, "gf_sampler_run_to_host");
     return GF_OK;
 }
 
@@ -2013,8 +1965,8 @@ int gf_internal_sampler_chain_stats(gf_sampler* s, unsigned long long* out)
     if (!s->d_chain_stats) return GF_ERR_UNSUPPORTED;
     const GfCommon* c; const GfBsm* tb; const double* ptab; void* stream; int device;
     if (gf_model_internal(s->model, &c, &tb, &ptab, &stream, &device) != GF_OK) return GF_ERR_INVALID_ARG;
-    GFS_HIP(hipMemcpyAsync(out, s->d_chain_stats, sizeof(unsigned long long) * 8 * (size_t)s->nchains, hipMemcpyDeviceToHost, (hipStream_t)stream));
-    GFS_HIP(hipStreamSynchronize((hipStream_t)stream));
+    GF_HIP(hipMemcpyAsync(out, s->d_chain_stats, sizeof(unsigned long long) * 8 * (size_t)s->nchains, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    GF_HIP(hipStreamSynchronize((hipStream_t)stream));
     return GF_OK;
 }
 
@@ -2054,9 +2006,9 @@ int gf_sampler_get_state(gf_sampler* s, double* pos, double* lnprob)
     const GfCommon* c; const GfBsm* tb; const double* ptab; void* stream; int device;
     if (gf_model_internal(s->model, &c, &tb, &ptab, &stream, &device) != GF_OK) return GF_ERR_INVALID_ARG;
     hipStream_t st = (hipStream_t)stream;
-    if (pos) GFS_HIP(hipMemcpyAsync(pos, s->d_pos, sizeof(double) * nw * s->ndim, hipMemcpyDeviceToHost, st));
-    if (lnprob) GFS_HIP(hipMemcpyAsync(lnprob, s->d_lnp, sizeof(double) * nw, hipMemcpyDeviceToHost, st));
-    GFS_HIP(hipStreamSynchronize(st));
+    if (pos) GF_HIP(hipMemcpyAsync(pos, s->d_pos, sizeof(double) * nw * s->ndim, hipMemcpyDeviceToHost, st));
+    if (lnprob) GF_HIP(hipMemcpyAsync(lnprob, s->d_lnp, sizeof(double) * nw, hipMemcpyDeviceToHost, st));
+    GF_HIP(hipStreamSynchronize(st));
     return GF_OK;
 }
 
@@ -2085,9 +2037,9 @@ int gf_sampler_get_chain(gf_sampler* s, double* chain, double* lnprob_chain, uin
         }
     }
     if (naccepted)
-        GFS_HIP(hipMemcpyAsync(naccepted, s->d_naccept, sizeof(uint32_t) * (size_t)s->nchains * per, hipMemcpyDeviceToHost, st));
-    if (nonunitary) GFS_HIP(hipMemcpyAsync(nonunitary, s->d_flags, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    GFS_HIP(hipStreamSynchronize(st));
+        GF_HIP(hipMemcpyAsync(naccepted, s->d_naccept, sizeof(uint32_t) * (size_t)s->nchains * per, hipMemcpyDeviceToHost, st));
+    if (nonunitary) GF_HIP(hipMemcpyAsync(nonunitary, s->d_flags, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    GF_HIP(hipStreamSynchronize(st));
     return GF_OK;
 }
 
@@ -2099,18 +2051,18 @@ int gf_sampler_get_chain_device(gf_sampler* s, double* d_chain, double* d_lnprob
     if (!s) return GF_ERR_INVALID_ARG;
     const GfCommon* c; const GfBsm* tb; const double* ptab; void* stream; int device;
     if (gf_model_internal(s->model, &c, &tb, &ptab, &stream, &device) != GF_OK) return GF_ERR_INVALID_ARG;
-    GFS_HIP(hipSetDevice(device));
+    GF_HIP(hipSetDevice(device));
     hipStream_t st = (hipStream_t)stream;
     if (s->nstored > 0) {
         const size_t row = sizeof(double) * (size_t)s->nwalkers * s->ndim, lrow = sizeof(double) * (size_t)s->nwalkers;
         if (d_chain)
-            GFS_HIP(hipMemcpy2DAsync(d_chain, row * s->nstored, s->d_chain, row * s->nstore_cap, row * s->nstored, s->nchains,
+            GF_HIP(hipMemcpy2DAsync(d_chain, row * s->nstored, s->d_chain, row * s->nstore_cap, row * s->nstored, s->nchains,
                                      hipMemcpyDeviceToDevice, st));
         if (d_lnprob_chain)
-            GFS_HIP(hipMemcpy2DAsync(d_lnprob_chain, lrow * s->nstored, s->d_lnp_chain, lrow * s->nstore_cap, lrow * s->nstored,
+            GF_HIP(hipMemcpy2DAsync(d_lnprob_chain, lrow * s->nstored, s->d_lnp_chain, lrow * s->nstore_cap, lrow * s->nstored,
                                      s->nchains, hipMemcpyDeviceToDevice, st));
     }
-    GFS_HIP(hipStreamSynchronize(st));
+    GF_HIP(hipStreamSynchronize(st));
     return GF_OK;
 }
 
@@ -2121,12 +2073,12 @@ int gf_sampler_walker_mean(gf_sampler* s, double* mean)
     if (!s || !mean) return GF_ERR_INVALID_ARG;
     const GfCommon* c; const GfBsm* tb; const double* ptab; void* stream; int device;
     if (gf_model_internal(s->model, &c, &tb, &ptab, &stream, &device) != GF_OK) return GF_ERR_INVALID_ARG;
-    GFS_HIP(hipSetDevice(device));
+    GF_HIP(hipSetDevice(device));
     hipStream_t st = (hipStream_t)stream;
-    if (s->nstored == 0) { GFS_HIP(hipStreamSynchronize(st)); return GF_OK; }
+    if (s->nstored == 0) { GF_HIP(hipStreamSynchronize(st)); return GF_OK; }
     const size_t bytes = sizeof(double) * (size_t)s->nchains * s->nstored * s->ndim;
     double* d_mean = nullptr;
-    GFS_HIP(hipMalloc((void**)&d_mean, bytes));
+    GF_HIP(hipMalloc((void**)&d_mean, bytes));
     hipError_t e = hipSuccess;
     for (int ch0 = 0; ch0 < s->nchains && e == hipSuccess; ch0 += 65535) {          // gridDim.y <= 65535
         const int nch = s->nchains - ch0 < 65535 ? s->nchains - ch0 : 65535;
@@ -2139,7 +2091,7 @@ int gf_sampler_walker_mean(gf_sampler* s, double* mean)
     hipError_t e2 = hipStreamSynchronize(st);
     (void)hipFree(d_mean);
     if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) return sfail(e, "gf_sampler_walker_mean");
+    if (e != hipSuccess) return gf_hip_fail(e, "gf_sampler_walker_mean");
     return GF_OK;
 }
 
@@ -2171,7 +2123,7 @@ int gf_sampler_postprocess_device(gf_sampler* s, gf_model* const* models, double
         if (gf_model_constants(mc, &c, &tb, &ptab, &device, &cus, &nbins) != GF_OK || c->ndim != s->ndim || device != device0)
             return GF_ERR_INVALID_ARG;
     }
-    GFS_HIP(hipSetDevice(device0));
+    GF_HIP(hipSetDevice(device0));
     hipStream_t st = (hipStream_t)stream;
     const int64_t per_chain = s->nstored * s->nwalkers;
     int rc = GF_OK;
@@ -2187,7 +2139,7 @@ int gf_sampler_postprocess_device(gf_sampler* s, gf_model* const* models, double
                                    d_status ? d_status + (size_t)ch * per_chain : nullptr);
     }
     gf_internal_full_arbitration_grids(device0, stream, 0);
-    GFS_HIP(hipStreamSynchronize(st));
+    GF_HIP(hipStreamSynchronize(st));
     if (rc == GF_OK && d_status) rc = gf_internal_check_overflow(device0, stream);
     return rc;
 }
@@ -2200,16 +2152,16 @@ int gf_sampler_postprocess_rows_device(gf_sampler* s, gf_model* const* models, d
     if (!s || !d_rows) return GF_ERR_INVALID_ARG;
     const GfCommon* c0; const GfBsm* tb; const double* ptab; void* stream; int device0;
     if (gf_model_internal(s->model, &c0, &tb, &ptab, &stream, &device0) != GF_OK) return GF_ERR_INVALID_ARG;
-    GFS_HIP(hipSetDevice(device0));
+    GF_HIP(hipSetDevice(device0));
     hipStream_t st = (hipStream_t)stream;
     const int64_t per_chain = s->nstored * s->nwalkers;
-    if (per_chain == 0) { GFS_HIP(hipStreamSynchronize(st)); return GF_OK; }
+    if (per_chain == 0) { GF_HIP(hipStreamSynchronize(st)); return GF_OK; }
     double* d_fr = nullptr;
     int32_t* d_st = nullptr;
-    GFS_HIP(hipMalloc((void**)&d_fr, sizeof(double) * 3 * per_chain * s->nchains));
+    GF_HIP(hipMalloc((void**)&d_fr, sizeof(double) * 3 * per_chain * s->nchains));
     {
         hipError_t e_ = hipMalloc((void**)&d_st, sizeof(int32_t) * per_chain * s->nchains);
-        if (e_ != hipSuccess) { (void)hipFree(d_fr); return sfail(e_, "hipMalloc(status)"); }
+        if (e_ != hipSuccess) { (void)hipFree(d_fr); return gf_hip_fail(e_, "hipMalloc(status)"); }
     }
     int rc = gf_sampler_postprocess_device(s, models, d_fr, d_st);
     hipError_t e = hipSuccess;
@@ -2223,7 +2175,7 @@ int gf_sampler_postprocess_rows_device(gf_sampler* s, gf_model* const* models, d
     (void)hipFree(d_st);
     if (rc != GF_OK) return rc;
     if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) return sfail(e, "gf_sampler_postprocess_rows_device");
+    if (e != hipSuccess) return gf_hip_fail(e, "gf_sampler_postprocess_rows_device");
     return GF_OK;
 }
 
@@ -2242,10 +2194,10 @@ int gf_sampler_postprocess_rows(gf_sampler* s, gf_model* const* models, double* 
         if (gf_model_constants(mc, &c, &tb, &ptab, &device, &cus, &nbins) != GF_OK || c->ndim != s->ndim || device != device0)
             return GF_ERR_INVALID_ARG;
     }
-    GFS_HIP(hipSetDevice(device0));
+    GF_HIP(hipSetDevice(device0));
     hipStream_t st = (hipStream_t)stream;
     const int64_t per_chain = s->nstored * s->nwalkers;
-    if (per_chain == 0) { GFS_HIP(hipStreamSynchronize(st)); return GF_OK; }
+    if (per_chain == 0) { GF_HIP(hipStreamSynchronize(st)); return GF_OK; }
     const size_t width = 3 + (size_t)s->ndim, chain_bytes = sizeof(double) * width * (size_t)per_chain;
     constexpr int MAX_GROUPS = 16;
     const int per_group = (s->nchains + MAX_GROUPS - 1) / MAX_GROUPS;
@@ -2298,7 +2250,7 @@ int gf_sampler_postprocess_rows(gf_sampler* s, gf_model* const* models, double* 
     if (d_rows) (void)hipFree(d_rows);
     if (rc != GF_OK) return rc;
     if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) return sfail(e, "gf_sampler_postprocess_rows");
+    if (e != hipSuccess) return gf_hip_fail(e, "gf_sampler_postprocess_rows");
     return gf_internal_check_overflow(device0, stream);
 }
 
@@ -2315,9 +2267,9 @@ int gf_sampler_postprocess_with(gf_sampler* s, gf_model* const* models, double* 
         if (gf_model_constants(mc, &c, &tb, &ptab, &device, &cus, &nbins) != GF_OK || c->ndim != s->ndim || device != device0)
             return GF_ERR_INVALID_ARG;
     }
-    GFS_HIP(hipSetDevice(device0));
+    GF_HIP(hipSetDevice(device0));
     hipStream_t st = (hipStream_t)stream;
-    GFS_HIP(hipStreamSynchronize(st));
+    GF_HIP(hipStreamSynchronize(st));
     if (s->nstored == 0) return GF_OK;
     const int64_t per_chain = s->nstored * s->nwalkers;
     const size_t nbin3 = counts ? (size_t)nbins * nbins * nbins : 0;
@@ -2352,7 +2304,7 @@ int gf_sampler_postprocess_with(gf_sampler* s, gf_model* const* models, double* 
     if (d_st) (void)hipFree(d_st);
     if (d_c) (void)hipFree(d_c);
     if (rc != GF_OK) return rc;
-    if (e != hipSuccess) return sfail(e, "gf_sampler_postprocess");
+    if (e != hipSuccess) return gf_hip_fail(e, "gf_sampler_postprocess");
     return status ? gf_internal_check_overflow(device0, stream) : GF_OK;
 }
 

@@ -28,24 +28,11 @@
 #include <stdint.h>
 
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <cstddef>
-#include <new>
 #include <vector>
 
-#include "../../include/golemflavor_hip.h"
-#include "gf_consts.h"
-
-extern "C" const char* gf_internal_env(const char* name, int affects_results);   // gf_capi.hip: getenv with a record
-#include "gf_device.hpp"
-#include "gf_bsm_device.hpp"
-#include "gf_launch.h"
-#include "gf_propose.hpp"
+#include "gf_cube_runs.hpp"
 
 namespace {
-using namespace gfdev;
 
 constexpr uint32_t SX_SEED_ITER = 0xFFFFFFFEu;     // iteration word of the seeding draws (the nested sampler's is 0xFFFFFFFF)
 constexpr int SX_PICK_BLOCK = 256;
@@ -73,12 +60,10 @@ struct SxRun {
     uint32_t pad;
 };
 
-struct SxArgs {
-    const GfCommon* commons;        // [R]
-    const GfBsm* const* tbs;        // [R]
-    const double* const* ptabs;     // [R]
-    const uint64_t* run_ids;        // [R]
-    const double* bases;            // [R][GF_MAX_DIM]
+struct SxArgs : GfCubeRuns {       // pq: capacity R * S * Q
+    int32_t nstarts, nuser, nseed, maxiter, restarts, raise;     // first: next to GfCubeRuns::nscan (k_sx_pick loads them together)
+    int32_t S, P;                   // starts per run (nstarts + nuser), vertices per simplex (nscan + 1)
+    int32_t Q;                      // points per start and round: max(P, 4) -- the initial simplex, the four candidates, a shrink
     SxRun* runs;                    // [R]
     SxStart* starts;                // [R][S]
     double* sim;                    // [R][S][P][N]
@@ -92,35 +77,9 @@ struct SxArgs {
     double* seed_l;                 // [R][M]
     int32_t* seed_st;               // [R][M]
     double* theta;                  // [R][M][ndim]
-    GfArbQueue* pq;                 // capacity R * S * Q
-    double* pend_rows;              // [R * S * Q][GF_PEND_STRIDE]
-    uint64_t seed;
     double coef[9];                 // 1 + rho, rho, 1 + rho chi, rho chi, 1 + psi rho, psi rho, 1 - psi, psi, sigma
     double xatol, fatol;
-    int32_t nruns, nstarts, nuser, nseed, nscan, ndim, maxiter, restarts, raise;
-    int32_t S, P;                   // starts per run (nstarts + nuser), vertices per simplex (nscan + 1)
-    int32_t Q;                      // points per start and round: max(P, 4) -- the initial simplex, the four candidates, a shrink
-    int32_t nbins_max;
-    int32_t slot[GF_MAX_DIM];       // column -> scanned slot, -1 = fixed
 };
-
-__device__ __forceinline__ void sx_uniform2(const SxArgs& a, int r, uint32_t it, uint32_t slot, uint32_t step, double out[2])
-{
-    uint32_t q[4];
-    const uint64_t key = a.seed, id = a.run_ids[r];
-    philox_block((uint32_t)id, it, slot, step, (uint32_t)key, (uint32_t)(key >> 32) ^ (uint32_t)(id >> 32), q);
-    out[0] = ((double)(q[0] >> 5) * 67108864.0 + (double)(q[1] >> 6)) * (1.0 / 9007199254740992.0);
-    out[1] = ((double)(q[2] >> 5) * 67108864.0 + (double)(q[3] >> 6)) * (1.0 / 9007199254740992.0);
-}
-
-// theta of cube point u for run r: the nested sampler's ns_cube_to_theta (mn.py:35-39), the product and the sum each rounded
-__device__ __forceinline__ void sx_cube_to_theta(const SxArgs& a, const GfCommon& c, int r, const double* u, double* row)
-{
-    for (int d = 0; d < a.ndim; ++d) {
-        const int sl = a.slot[d];
-        row[d] = sl >= 0 ? __dadd_rn(__dmul_rn(c.hi[d] - c.lo[d], u[sl]), c.lo[d]) : a.bases[r * GF_MAX_DIM + d];
-    }
-}
 
 // np.clip(x, 0, 1): maximum(x, 0) then minimum(., 1), NaN kept; -0.0 becomes +0.0 as in numpy
 __device__ __forceinline__ double sx_clip(double x)
@@ -132,24 +91,6 @@ __device__ __forceinline__ double sx_clip(double x)
 
 // f of a round's point: -lnprob, +inf for -inf, NaN or a non-unitary verdict
 __device__ __forceinline__ double sx_f(double lnq, int32_t st) { return (st != ST_NON_UNITARY && lnq > -gf_inf()) ? -lnq : gf_inf(); }
-
-// nscan uniform cube points per seed point, mapped to theta for the bulk lnprob path
-__global__ __launch_bounds__(GF_BLOCK) void k_sx_seed(const SxArgs a)
-{
-    const int r = blockIdx.y;
-    const int i = blockIdx.x * GF_BLOCK + threadIdx.x;
-    if (i >= a.nseed) return;
-    double u[GF_MAX_DIM];
-    for (int p = 0; 2 * p < a.nscan; ++p) {
-        double v[2];
-        sx_uniform2(a, r, SX_SEED_ITER, (uint32_t)i, (uint32_t)p, v);
-        u[2 * p] = v[0];
-        if (2 * p + 1 < a.nscan) u[2 * p + 1] = v[1];
-    }
-    double* su = a.seed_u + ((int64_t)r * a.nseed + i) * a.nscan;
-    for (int d = 0; d < a.nscan; ++d) su[d] = u[d];
-    sx_cube_to_theta(a, a.commons[r], r, u, a.theta + ((int64_t)r * a.nseed + i) * a.ndim);
-}
 
 // a fresh initial simplex around x0 (_minimize_neldermead with bounds [0, 1]^n): every vertex goes to the next round
 __device__ void sx_begin(const SxArgs& a, int64_t s, const double* x0)
@@ -265,14 +206,7 @@ __global__ __launch_bounds__(GF_BLOCK) void k_sx_eval(const SxArgs a)
     const GfBsm* tb = a.tbs[r];
     const double* ptab = a.ptabs[r];
     double* ttab = ctab + GF_MAX_DIM * 4;
-    if (threadIdx.x < GF_MAX_DIM * 4) ctab[threadIdx.x] = ptab[threadIdx.x];
-    if (MODE == MODE_BSM_GAUSS && threadIdx.x >= 64 && threadIdx.x < 64 + 18) {
-        const int k = threadIdx.x - 64, e = k >> 1;
-        const int id = e == 0 ? 0 : e == 1 ? 4 : e == 2 ? 8 : e <= 4 ? 1 : e <= 6 ? 2 : 5;
-        const bool im = e == 4 || e == 6 || e == 8;
-        const double* srcp = (k & 1) ? (im ? tb->t2_im : tb->t2_re) : (im ? tb->t1_im : tb->t1_re);
-        ttab[k] = srcp[id];
-    }
+    load_eval_tables(ctab, ptab, tb, MODE == MODE_BSM_GAUSS);
     __syncthreads();
     const int t = blockIdx.x * GF_BLOCK + threadIdx.x;
     const int k = t / LPW, sub = t % LPW;
@@ -284,27 +218,16 @@ __global__ __launch_bounds__(GF_BLOCK) void k_sx_eval(const SxArgs a)
     const int64_t w = s * a.Q + p;
     const int lane = threadIdx.x & (GF_WAVE - 1);
     double* row = tiles[threadIdx.x / GF_WAVE] + lane * GF_MAX_DIM;
-    sx_cube_to_theta(a, c, r, a.pts + w * a.nscan, row);
+    cube_to_theta(a, c, r, a.pts + w * a.nscan, row);
     int status;
     unsigned long long pending;
     const double lnq = proposal_lnprob<0, MODE, LPW>(c, tb, ctab, ttab, row, a.ndim, status, sub, fgrp, pending);
     if (LPW > 1 && sub != 0) return;                         // the group's results are identical: one writer
     if (MODE == MODE_BSM_GAUSS && pending != 0ull) {
         // undecided unitarity: park; k_stretch_settle<Team9, false, true> writes lnq and the verdict
-        double* dst = a.pend_rows + (size_t)w * GF_PEND_STRIDE;
-        for (int d = 0; d < a.ndim; ++d) dst[d] = row[d];
-        dst[GF_MAX_DIM] = lnq;
         a.pst[w] = SX_PARKED;
         atomicAdd(&a.runs[r].parked, 1u);
-        const unsigned int at = atomicAdd(&a.pq->count, 1u);
-        if (at < a.pq->cap) {
-            GfArbItem item;
-            item.walker = (unsigned long long)w;
-            item.mask = pending;
-            a.pq->items[at] = item;
-        } else {
-            a.pq->overflow = 1u;                             // capacity = every point of a round: cannot happen
-        }
+        park_proposal(a.pq, a.pend_rows, w, row, a.ndim, lnq, pending);
         return;
     }
     a.lnq[w] = lnq;
@@ -472,77 +395,24 @@ __global__ __launch_bounds__(SX_STEP_BLOCK) void k_sx_step(const SxArgs a)
     if (!sx_next(a, s)) sx_finish(a, r, s);
 }
 
-template <int MODE, int LPW>
-hipError_t launch_eval(const SxArgs& a, hipStream_t st)
-{
-    const size_t lds = LPW > 1 ? (size_t)(GF_BLOCK / LPW) * GF_FGRP_DOUBLES(a.nbins_max, LPW) * sizeof(double) : 0;
-    const dim3 grid((unsigned)(((int64_t)a.S * a.Q * LPW + GF_BLOCK - 1) / GF_BLOCK), a.nruns);
-    hipLaunchKernelGGL((k_sx_eval<MODE, LPW>), grid, dim3(GF_BLOCK), lds, st, a);
-    return hipGetLastError();
-}
-
 hipError_t launch_eval_any(int mode, int lpw, const SxArgs& a, hipStream_t st)
 {
-    switch (mode) {
-    case MODE_PRIOR_ONLY: return launch_eval<MODE_PRIOR_ONLY, 1>(a, st);
-    case MODE_SM_GAUSS: return launch_eval<MODE_SM_GAUSS, 1>(a, st);
-    default:
-        switch (lpw) {
-        case 4: return launch_eval<MODE_BSM_GAUSS, 4>(a, st);
-        case 16: return launch_eval<MODE_BSM_GAUSS, 16>(a, st);
-        default: return launch_eval<MODE_BSM_GAUSS, 1>(a, st);
-        }
-    }
+    return launch_mode_lpw(mode, lpw, [&](auto m, auto l) {
+        return launch_points(k_sx_eval<decltype(m)::value, decltype(l)::value>, a, l, (int64_t)a.S * a.Q, st);
+    });
 }
 
 }  // namespace
 
-extern "C" {
-int gf_model_internal(gf_model* m, const GfCommon** c, const GfBsm** d_bsm, const double** d_ptab, void** stream, int* device);
-int gf_model_constants(gf_model* m, const GfCommon** c, const GfBsm** d_bsm, const double** d_ptab, int* device, int* cus,
-                       int* nbins);
-void gf_internal_set_error(const char* msg);
-int gf_model_lnprob_on(gf_model* m, void* stream, const double* d_theta, int layout, int64_t n, double* d_lnprob,
-                       double* d_fr, int32_t* d_status);
-}
-
 struct gf_simplex {
-    gf_model** models = nullptr;        // [nruns]; models[0]'s stream carries every launch
-    hipStream_t stream = nullptr;
-    int device = 0, cus = 256, mode = 0;
-    int initialised = 0;
+    GfCubeRunsHost rs;
     int64_t rounds = 0;                 // evaluation rounds launched
     SxArgs a = {};
     GfSettleArgs sa = {};
-    GfStepState* d_state = nullptr;     // the settle kernel's step state: zeros (no stored chain)
-    unsigned int* d_ctl = nullptr;
-    GfCommon* d_commons = nullptr;
-    const GfBsm** d_tbs = nullptr;
-    const double** d_ptabs = nullptr;
-    uint64_t* d_run_ids = nullptr;
-    double* d_bases = nullptr;
     double* d_ustart = nullptr;
 };
 
 namespace {
-thread_local char g_serr[256] = "";
-int sfail(hipError_t e, const char* what)
-{
-    std::snprintf(g_serr, sizeof(g_serr), "%s: %s", what, hipGetErrorString(e));
-    gf_internal_set_error(g_serr);
-    return GF_ERR_HIP;
-}
-int smsg(int rc, const char* msg)
-{
-    std::snprintf(g_serr, sizeof(g_serr), "%s", msg);
-    gf_internal_set_error(g_serr);
-    return rc;
-}
-#define GFS_HIP(call)                                   \
-    do {                                                \
-        hipError_t e_ = (call);                         \
-        if (e_ != hipSuccess) return sfail(e_, #call);  \
-    } while (0)
 
 // scipy's coefficients (_minimize_neldermead: dim = float(len(x0))) and the scalars of its candidate expressions
 void sx_coefficients(int n, int adaptive, double coef[9])
@@ -565,18 +435,12 @@ int sx_init(gf_simplex* s)
 {
     SxArgs& a = s->a;
     if (a.nseed > 0) {
-        const dim3 grid((unsigned)((a.nseed + GF_BLOCK - 1) / GF_BLOCK), a.nruns);
-        hipLaunchKernelGGL(k_sx_seed, grid, dim3(GF_BLOCK), 0, s->stream, a);
-        GFS_HIP(hipGetLastError());
-        for (int r = 0; r < a.nruns; ++r) {
-            const int rc = gf_model_lnprob_on(s->models[r], s->stream, a.theta + (size_t)r * a.nseed * a.ndim, GF_LAYOUT_AOS,
-                                              a.nseed, a.seed_l + (size_t)r * a.nseed, nullptr, a.seed_st + (size_t)r * a.nseed);
-            if (rc != GF_OK) return rc;
-        }
+        const int rc = cube_runs_draw(s->rs, a, SX_SEED_ITER, a.nseed, a.seed_u, a.theta, a.seed_l, a.seed_st);
+        if (rc != GF_OK) return rc;
     }
-    hipLaunchKernelGGL(k_sx_pick, dim3(a.nruns), dim3(SX_PICK_BLOCK), 0, s->stream, a);
-    GFS_HIP(hipGetLastError());
-    s->initialised = 1;
+    hipLaunchKernelGGL(k_sx_pick, dim3(a.nruns), dim3(SX_PICK_BLOCK), 0, s->rs.stream, a);
+    GF_HIP(hipGetLastError());
+    s->rs.initialised = 1;
     return GF_OK;
 }
 }  // namespace
@@ -590,73 +454,26 @@ int gf_simplex_create(gf_model* const* models, int nruns, int nscan, const int32
         nseed < 0 || nstarts > nseed || nstarts > 4096 || nseed > (1 << 22) || (on_nonunitary != 0 && on_nonunitary != 1))
         return GF_ERR_INVALID_ARG;
     *out = nullptr;
-    const GfCommon* c0; const GfBsm* tb0; const double* pt0; void* stream0; int device0;
-    if (!models[0] || gf_model_internal(models[0], &c0, &tb0, &pt0, &stream0, &device0) != GF_OK) return GF_ERR_INVALID_ARG;
-    const int ndim = c0->ndim;
-    std::vector<int32_t> slot(GF_MAX_DIM, -1);
-    for (int k = 0; k < nscan; ++k) {
-        if (cols[k] < 0 || cols[k] >= ndim || slot[cols[k]] >= 0) return GF_ERR_INVALID_ARG;
-        slot[cols[k]] = k;
-    }
-    std::vector<GfCommon> hc(nruns);
-    std::vector<const GfBsm*> htb(nruns);
-    std::vector<const double*> hpt(nruns);
-    std::vector<double> hb((size_t)nruns * GF_MAX_DIM, 0.0);
-    int cus = 256, nbins_max = 0;
-    for (int r = 0; r < nruns; ++r) {
-        const GfCommon* c; int device, nb;
-        if (!models[r] || gf_model_constants(models[r], &c, &htb[r], &hpt[r], &device, &cus, &nb) != GF_OK || device != device0 ||
-            c->ndim != ndim || c->mode != c0->mode)
-            return smsg(GF_ERR_INVALID_ARG, "gf_simplex_create: every model must share device, ndim and mode with model 0");
-        hc[r] = *c;
-        if (nb > nbins_max) nbins_max = nb;
-        for (int d = 0; d < ndim; ++d) hb[(size_t)r * GF_MAX_DIM + d] = bases[(size_t)r * ndim + d];
-    }
     gf_simplex* s = new (std::nothrow) gf_simplex();
     if (!s) return GF_ERR_ALLOC;
-    s->models = new (std::nothrow) gf_model*[nruns];
-    if (!s->models) { delete s; return GF_ERR_ALLOC; }
-    for (int r = 0; r < nruns; ++r) s->models[r] = models[r];
-    s->stream = (hipStream_t)stream0; s->device = device0; s->cus = cus; s->mode = c0->mode;
     SxArgs& a = s->a;
-    a.seed = seed;
-    a.nruns = nruns; a.nstarts = nstarts; a.nuser = 0; a.nseed = nseed; a.nscan = nscan; a.ndim = ndim;
-    a.raise = on_nonunitary == 0; a.nbins_max = nbins_max;
+    const int rc = cube_runs_create(s->rs, a, models, nruns, nscan, cols, bases, seed, "gf_simplex_create");
+    if (rc != GF_OK) { delete s; return rc; }
+    a.nstarts = nstarts; a.nuser = 0; a.nseed = nseed; a.raise = on_nonunitary == 0;
     a.xatol = 1e-4; a.fatol = 1e-4; a.maxiter = 200 * nscan; a.restarts = 0;
     sx_coefficients(nscan, 0, a.coef);
     a.S = nstarts; a.P = nscan + 1; a.Q = nscan + 1 > 4 ? nscan + 1 : 4;
-    for (int d = 0; d < GF_MAX_DIM; ++d) a.slot[d] = slot[d];
     const size_t R = nruns, M = nseed;
-    hipError_t e = hipSetDevice(device0);
-    hipStream_t st = s->stream;
+    hipError_t e = hipSuccess;
     auto al = [&](void** p, size_t bytes) { if (e == hipSuccess && bytes > 0) e = hipMalloc(p, bytes); };
-    al((void**)&s->d_commons, sizeof(GfCommon) * R);
-    al((void**)&s->d_tbs, sizeof(void*) * R);
-    al((void**)&s->d_ptabs, sizeof(void*) * R);
-    al((void**)&s->d_run_ids, sizeof(uint64_t) * R);
-    al((void**)&s->d_bases, sizeof(double) * R * GF_MAX_DIM);
     al((void**)&a.runs, sizeof(SxRun) * R);
     al((void**)&a.seed_u, sizeof(double) * R * M * nscan);
     al((void**)&a.seed_l, sizeof(double) * R * M);
     al((void**)&a.seed_st, sizeof(int32_t) * R * M);
-    al((void**)&a.theta, sizeof(double) * R * M * ndim);
-    al((void**)&s->d_state, sizeof(GfStepState));
-    std::vector<uint64_t> ids(R);
-    for (size_t r = 0; r < R; ++r) ids[r] = r;
-    auto up = [&](void* dst, const void* src, size_t bytes) { if (e == hipSuccess) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st); };
-    up(s->d_commons, hc.data(), sizeof(GfCommon) * R);
-    up((void*)s->d_tbs, htb.data(), sizeof(void*) * R);
-    up((void*)s->d_ptabs, hpt.data(), sizeof(void*) * R);
-    up(s->d_run_ids, ids.data(), sizeof(uint64_t) * R);
-    up(s->d_bases, hb.data(), sizeof(double) * R * GF_MAX_DIM);
-    if (e == hipSuccess) e = hipMemsetAsync(a.runs, 0, sizeof(SxRun) * R, st);
-    GfStepState hs;
-    std::memset(&hs, 0, sizeof(hs));
-    hs.thin = 1;
-    up(s->d_state, &hs, sizeof(hs));
-    if (e == hipSuccess) e = hipStreamSynchronize(st);                  // the host vectors go out of scope
-    if (e != hipSuccess) { const int rc = sfail(e, "gf_simplex_create"); gf_simplex_destroy(s); return rc; }
-    a.commons = s->d_commons; a.tbs = s->d_tbs; a.ptabs = s->d_ptabs; a.run_ids = s->d_run_ids; a.bases = s->d_bases;
+    al((void**)&a.theta, sizeof(double) * R * M * a.ndim);
+    if (e == hipSuccess) e = hipMemsetAsync(a.runs, 0, sizeof(SxRun) * R, s->rs.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->rs.stream);
+    if (e != hipSuccess) { const int rc2 = gf_hip_fail(e, "gf_simplex_create"); gf_simplex_destroy(s); return rc2; }
     *out = s;
     return GF_OK;
 }
@@ -664,26 +481,22 @@ int gf_simplex_create(gf_model* const* models, int nruns, int nscan, const int32
 int gf_simplex_set_run_ids(gf_simplex* s, const uint64_t* ids)
 {
     if (!s || !ids) return GF_ERR_INVALID_ARG;
-    if (s->initialised) return smsg(GF_ERR_INVALID_ARG, "gf_simplex_set_run_ids: before the first gf_simplex_run");
-    GFS_HIP(hipSetDevice(s->device));
-    GFS_HIP(hipMemcpyAsync(s->d_run_ids, ids, sizeof(uint64_t) * (size_t)s->a.nruns, hipMemcpyHostToDevice, s->stream));
-    GFS_HIP(hipStreamSynchronize(s->stream));
-    return GF_OK;
+    return cube_runs_set_ids(s->rs, s->a, ids, "gf_simplex_set_run_ids: before the first gf_simplex_run");
 }
 
 int gf_simplex_set_starts(gf_simplex* s, int nuser, const double* cube)
 {
     if (!s || nuser < 0 || nuser > 4096 || (nuser > 0 && !cube)) return GF_ERR_INVALID_ARG;
-    if (s->initialised) return smsg(GF_ERR_INVALID_ARG, "gf_simplex_set_starts: before the first gf_simplex_run");
+    if (s->rs.initialised) return gf_fail_msg(GF_ERR_INVALID_ARG, "gf_simplex_set_starts: before the first gf_simplex_run");
     const size_t n = (size_t)s->a.nruns * nuser * s->a.nscan;
     for (size_t i = 0; i < n; ++i)
-        if (!(cube[i] == cube[i])) return smsg(GF_ERR_INVALID_ARG, "gf_simplex_set_starts: NaN in a start");
-    GFS_HIP(hipSetDevice(s->device));
+        if (!(cube[i] == cube[i])) return gf_fail_msg(GF_ERR_INVALID_ARG, "gf_simplex_set_starts: NaN in a start");
+    GF_HIP(hipSetDevice(s->rs.device));
     if (s->d_ustart) { (void)hipFree(s->d_ustart); s->d_ustart = nullptr; }
     if (n > 0) {
-        GFS_HIP(hipMalloc((void**)&s->d_ustart, sizeof(double) * n));
-        GFS_HIP(hipMemcpyAsync(s->d_ustart, cube, sizeof(double) * n, hipMemcpyHostToDevice, s->stream));
-        GFS_HIP(hipStreamSynchronize(s->stream));
+        GF_HIP(hipMalloc((void**)&s->d_ustart, sizeof(double) * n));
+        GF_HIP(hipMemcpyAsync(s->d_ustart, cube, sizeof(double) * n, hipMemcpyHostToDevice, s->rs.stream));
+        GF_HIP(hipStreamSynchronize(s->rs.stream));
     }
     s->a.ustart = s->d_ustart;
     s->a.nuser = nuser;
@@ -694,7 +507,7 @@ int gf_simplex_set_options(gf_simplex* s, double xatol, double fatol, int maxite
 {
     if (!s || !(xatol >= 0.0) || !(fatol >= 0.0) || maxiter < 1 || (adaptive != 0 && adaptive != 1) || restarts < 0)
         return GF_ERR_INVALID_ARG;
-    if (s->initialised) return smsg(GF_ERR_INVALID_ARG, "gf_simplex_set_options: before the first gf_simplex_run");
+    if (s->rs.initialised) return gf_fail_msg(GF_ERR_INVALID_ARG, "gf_simplex_set_options: before the first gf_simplex_run");
     SxArgs& a = s->a;
     a.xatol = xatol; a.fatol = fatol; a.maxiter = maxiter; a.restarts = restarts;
     sx_coefficients(a.nscan, adaptive, a.coef);
@@ -704,14 +517,10 @@ int gf_simplex_set_options(gf_simplex* s, double xatol, double fatol, int maxite
 void gf_simplex_destroy(gf_simplex* s)
 {
     if (!s) return;
-    (void)hipSetDevice(s->device);
-    if (s->stream) (void)hipStreamSynchronize(s->stream);
     SxArgs& a = s->a;
-    void* ptrs[] = {s->d_commons, (void*)s->d_tbs, (void*)s->d_ptabs, s->d_run_ids, s->d_bases, s->d_ustart, s->d_state,
-                    s->d_ctl, a.runs, a.starts, a.sim, a.fsim, a.tmp, a.pts, a.lnq, a.pst, a.seed_u, a.seed_l, a.seed_st,
-                    a.theta, a.pq, a.pend_rows};
+    cube_runs_free(s->rs, a);
+    void* ptrs[] = {s->d_ustart, a.runs, a.starts, a.sim, a.fsim, a.tmp, a.pts, a.lnq, a.pst, a.seed_u, a.seed_l, a.seed_st, a.theta};
     for (void* p : ptrs) if (p) (void)hipFree(p);
-    delete[] s->models;
     delete s;
 }
 
@@ -719,9 +528,9 @@ void gf_simplex_destroy(gf_simplex* s)
 int gf_simplex_run(gf_simplex* s, int64_t max_rounds)
 {
     if (!s || max_rounds < 1) return GF_ERR_INVALID_ARG;
-    GFS_HIP(hipSetDevice(s->device));
+    GF_HIP(hipSetDevice(s->rs.device));
     SxArgs& a = s->a;
-    if (!s->initialised) {
+    if (!s->rs.initialised) {
         // the per-start buffers are sized once the caller's starts are known
         a.S = a.nstarts + a.nuser;
         // simplex rows: P per start; rows of a round (points, values, statuses, parked candidates): Q = max(P, 4) per start
@@ -735,48 +544,35 @@ int gf_simplex_run(gf_simplex* s, int64_t max_rounds)
         al((void**)&a.pts, sizeof(double) * W * N);
         al((void**)&a.lnq, sizeof(double) * W);
         al((void**)&a.pst, sizeof(int32_t) * W);
-        if (s->mode == MODE_BSM_GAUSS) {
-            al((void**)&a.pq, sizeof(GfArbQueue) + sizeof(GfArbItem) * W);
-            al((void**)&a.pend_rows, sizeof(double) * W * GF_PEND_STRIDE);
-            al((void**)&s->d_ctl, sizeof(unsigned int) * 2 * W);
-        }
-        if (e == hipSuccess) e = hipMemsetAsync(a.starts, 0, sizeof(SxStart) * R * S, s->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(a.pst, 0, sizeof(int32_t) * W, s->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(a.lnq, 0, sizeof(double) * W, s->stream);
-        if (s->mode == MODE_BSM_GAUSS) {
-            GfArbQueue qh;
-            std::memset(&qh, 0, sizeof(qh));
-            qh.cap = (unsigned int)W;
-            if (e == hipSuccess) e = hipMemcpyAsync(a.pq, &qh, offsetof(GfArbQueue, items), hipMemcpyHostToDevice, s->stream);
-            if (e == hipSuccess) e = hipMemsetAsync(s->d_ctl, 0, sizeof(unsigned int) * 2 * W, s->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(s->stream);       // qh goes out of scope
-        }
-        if (e != hipSuccess) return sfail(e, "gf_simplex_run: buffers");
+        if (e == hipSuccess) e = hipMemsetAsync(a.starts, 0, sizeof(SxStart) * R * S, s->rs.stream);
+        if (e == hipSuccess) e = hipMemsetAsync(a.pst, 0, sizeof(int32_t) * W, s->rs.stream);
+        if (e == hipSuccess) e = hipMemsetAsync(a.lnq, 0, sizeof(double) * W, s->rs.stream);
+        if (e == hipSuccess) e = cube_runs_alloc_queue(s->rs, a, W);
+        if (e != hipSuccess) return gf_hip_fail(e, "gf_simplex_run: buffers");
         GfSettleArgs& sa = s->sa;
-        sa.state = s->d_state; sa.pq = a.pq; sa.pend_rows = a.pend_rows; sa.ctl = s->d_ctl; sa.flags = nullptr;
-        sa.nchains = a.nruns; sa.nwalkers = (int32_t)(2 * S * a.Q); sa.ndim = a.ndim; sa.commons = s->d_commons; sa.tbs = s->d_tbs;
-        sa.multi = 1; sa.sx_lnq = a.lnq; sa.sx_status = a.pst;
+        cube_runs_settle_args(s->rs, a, (int32_t)(2 * S * a.Q), sa);
+        sa.flags = nullptr; sa.sx_lnq = a.lnq; sa.sx_status = a.pst;
         const int rc = sx_init(s);
         if (rc != GF_OK) return rc;
     }
     if (a.S == 0) return GF_OK;
-    const int lpw = gf_propose_lanes_per_walker(s->mode, (int64_t)a.nruns * a.S * a.Q, a.nbins_max, s->cus, "GF_SIMPLEX_LPW");
+    const int lpw = gf_propose_lanes_per_walker(s->rs.mode, (int64_t)a.nruns * a.S * a.Q, a.nbins_max, s->rs.cus, "GF_SIMPLEX_LPW");
     constexpr int check = 4;
     std::vector<SxRun> hr(a.nruns);
     const dim3 sgrid((unsigned)((a.S + SX_STEP_BLOCK - 1) / SX_STEP_BLOCK), a.nruns);
     int64_t done_here = 0;
     for (;;) {
-        GFS_HIP(hipMemcpyAsync(hr.data(), a.runs, sizeof(SxRun) * a.nruns, hipMemcpyDeviceToHost, s->stream));
-        GFS_HIP(hipStreamSynchronize(s->stream));
+        GF_HIP(hipMemcpyAsync(hr.data(), a.runs, sizeof(SxRun) * a.nruns, hipMemcpyDeviceToHost, s->rs.stream));
+        GF_HIP(hipStreamSynchronize(s->rs.stream));
         bool all = true;
         for (const SxRun& x : hr) all = all && (x.active == 0 || x.failed);
         if (all) break;
         if (done_here >= max_rounds) return GF_OK;                      // stepping: the caller asked for this many rounds
         for (int i = 0; i < check && done_here < max_rounds; ++i, ++done_here) {
-            GFS_HIP(launch_eval_any(s->mode, lpw, a, s->stream));
-            if (s->mode == MODE_BSM_GAUSS) GFS_HIP(gf_launch_simplex_settle(s->sa, s->cus, s->stream));
-            hipLaunchKernelGGL(k_sx_step, sgrid, dim3(SX_STEP_BLOCK), 0, s->stream, a);
-            GFS_HIP(hipGetLastError());
+            GF_HIP(launch_eval_any(s->rs.mode, lpw, a, s->rs.stream));
+            if (s->rs.mode == MODE_BSM_GAUSS) GF_HIP(gf_launch_simplex_settle(s->sa, s->rs.cus, s->rs.stream));
+            hipLaunchKernelGGL(k_sx_step, sgrid, dim3(SX_STEP_BLOCK), 0, s->rs.stream, a);
+            GF_HIP(hipGetLastError());
             s->rounds += 1;
         }
     }
@@ -787,21 +583,21 @@ int gf_simplex_result(gf_simplex* s, double* max_lnl, double* argmax_cube, int32
                       int64_t* nevals, uint32_t* nonunitary, uint32_t* parked, int32_t* failed)
 {
     if (!s) return GF_ERR_INVALID_ARG;
-    GFS_HIP(hipSetDevice(s->device));
+    GF_HIP(hipSetDevice(s->rs.device));
     const SxArgs& a = s->a;
     const int R = a.nruns, S = a.S, P = a.P, N = a.nscan;
     std::vector<SxRun> hr(R);
-    GFS_HIP(hipMemcpyAsync(hr.data(), a.runs, sizeof(SxRun) * R, hipMemcpyDeviceToHost, s->stream));
+    GF_HIP(hipMemcpyAsync(hr.data(), a.runs, sizeof(SxRun) * R, hipMemcpyDeviceToHost, s->rs.stream));
     std::vector<SxStart> hs((size_t)R * S);
     std::vector<double> f((size_t)R * S * P), x((size_t)R * S * P * N);
-    if (s->initialised && S > 0) {
-        GFS_HIP(hipMemcpyAsync(hs.data(), a.starts, sizeof(SxStart) * hs.size(), hipMemcpyDeviceToHost, s->stream));
-        GFS_HIP(hipMemcpyAsync(f.data(), a.fsim, sizeof(double) * f.size(), hipMemcpyDeviceToHost, s->stream));
-        GFS_HIP(hipMemcpyAsync(x.data(), a.sim, sizeof(double) * x.size(), hipMemcpyDeviceToHost, s->stream));
+    if (s->rs.initialised && S > 0) {
+        GF_HIP(hipMemcpyAsync(hs.data(), a.starts, sizeof(SxStart) * hs.size(), hipMemcpyDeviceToHost, s->rs.stream));
+        GF_HIP(hipMemcpyAsync(f.data(), a.fsim, sizeof(double) * f.size(), hipMemcpyDeviceToHost, s->rs.stream));
+        GF_HIP(hipMemcpyAsync(x.data(), a.sim, sizeof(double) * x.size(), hipMemcpyDeviceToHost, s->rs.stream));
     }
-    GFS_HIP(hipStreamSynchronize(s->stream));
+    GF_HIP(hipStreamSynchronize(s->rs.stream));
     for (int r = 0; r < R; ++r) {
-        const int used = s->initialised ? hr[r].nstarts : 0;
+        const int used = s->rs.initialised ? hr[r].nstarts : 0;
         double best = HUGE_VAL;
         int bj = -1;
         int64_t it = 0, fe = 0, ev = 0;
@@ -828,16 +624,16 @@ int gf_simplex_result(gf_simplex* s, double* max_lnl, double* argmax_cube, int32
 int gf_simplex_get_starts(gf_simplex* s, int run, double* fun, double* cube, int32_t* nit, int64_t* nfev)
 {
     if (!s || run < 0 || run >= s->a.nruns) return GF_ERR_INVALID_ARG;
-    GFS_HIP(hipSetDevice(s->device));
+    GF_HIP(hipSetDevice(s->rs.device));
     const SxArgs& a = s->a;
     const int S = a.S, P = a.P, N = a.nscan;
-    if (!s->initialised || S == 0) return GF_OK;
+    if (!s->rs.initialised || S == 0) return GF_OK;
     std::vector<SxStart> hs(S);
     std::vector<double> f((size_t)S * P), x((size_t)S * P * N);
-    GFS_HIP(hipMemcpyAsync(hs.data(), a.starts + (size_t)run * S, sizeof(SxStart) * S, hipMemcpyDeviceToHost, s->stream));
-    GFS_HIP(hipMemcpyAsync(f.data(), a.fsim + (size_t)run * S * P, sizeof(double) * f.size(), hipMemcpyDeviceToHost, s->stream));
-    GFS_HIP(hipMemcpyAsync(x.data(), a.sim + (size_t)run * S * P * N, sizeof(double) * x.size(), hipMemcpyDeviceToHost, s->stream));
-    GFS_HIP(hipStreamSynchronize(s->stream));
+    GF_HIP(hipMemcpyAsync(hs.data(), a.starts + (size_t)run * S, sizeof(SxStart) * S, hipMemcpyDeviceToHost, s->rs.stream));
+    GF_HIP(hipMemcpyAsync(f.data(), a.fsim + (size_t)run * S * P, sizeof(double) * f.size(), hipMemcpyDeviceToHost, s->rs.stream));
+    GF_HIP(hipMemcpyAsync(x.data(), a.sim + (size_t)run * S * P * N, sizeof(double) * x.size(), hipMemcpyDeviceToHost, s->rs.stream));
+    GF_HIP(hipStreamSynchronize(s->rs.stream));
     for (int j = 0; j < S; ++j) {
         if (fun) fun[j] = hs[j].calls > 0 ? f[(size_t)j * P] : HUGE_VAL;
         if (cube) for (int d = 0; d < N; ++d) cube[(size_t)j * N + d] = x[(size_t)j * P * N + d];

@@ -432,46 +432,41 @@ extern "C" int gf_internal_settle_timing(unsigned long long* out, int reset)
 }
 #endif
 
-// the sampler's settle step; the count is on the device, the groups fetch dynamically: a modest fixed grid (it sits in a captured
-// graph and runs after every half-step, almost always on an empty queue -- where its cost is the launch)
+// The settle steps' grid; the count is on the device, the groups fetch dynamically: a modest fixed grid (it sits in a captured
+// graph and runs after every half-step, almost always on an empty queue -- where its cost is the launch).  Enough groups to
+// spread a short queue's walkers over (fan-out); on an empty queue every block returns after one load.  One block per CU:
+// measured on the C5 scan's sampling phase (256 chains x 512 walkers, a few hundred parked proposals per half-step) 128 / 256 /
+// 512 / 1024 / 2048 blocks give 0.105 / 0.120 / 0.116 / 0.130 / 0.141 s -- the step waits for ONE walker's chain of dependent
+// instructions (~70 us for the set-up and one bin, tools/arb_latency_probe.py), not for throughput
+static unsigned settle_blocks(const GfSettleArgs& a, int cus)
+{
+    constexpr int64_t per_block = (UNI_BLOCK / 64) * Team9::PER_WAVE;
+    const int64_t nprop = (int64_t)a.nchains * (a.nwalkers / 2);
+    int64_t blocks = (nprop * GF_UNI_MAX_FANOUT + per_block - 1) / per_block;
+    if (blocks > cus) blocks = cus;
+    if (blocks < 1) blocks = 1;
+    return (unsigned)blocks;
+}
+
+// the sampler's settle step
 hipError_t gf_launch_stretch_settle(const GfSettleArgs& a, int cus, hipStream_t s)
 {
-    constexpr int64_t per_block = (UNI_BLOCK / 64) * Team9::PER_WAVE;
-    const int64_t nprop = (int64_t)a.nchains * (a.nwalkers / 2);
-    // enough groups to spread a short queue's walkers over (fan-out); on an empty queue every block returns after one load.  One
-    // block per CU: measured on the C5 scan's sampling phase (256 chains x 512 walkers, a few hundred parked proposals per
-    // half-step) 128 / 256 / 512 / 1024 / 2048 blocks give 0.105 / 0.120 / 0.116 / 0.130 / 0.141 s -- the step waits for ONE walker's
-    // chain of dependent instructions (~70 us for the set-up and one bin, tools/arb_latency_probe.py), not for throughput
-    int64_t blocks = (nprop * GF_UNI_MAX_FANOUT + per_block - 1) / per_block;
-    if (blocks > cus) blocks = cus;
-    if (blocks < 1) blocks = 1;
     static const int forced = [] { const char* e = gf_internal_env("GF_SETTLE_BLOCKS", 0); return e ? std::atoi(e) : 0; }();   // diagnostics / A-B
-    if (forced > 0) blocks = forced;
-    hipLaunchKernelGGL(k_stretch_settle<Team9>, dim3((unsigned)blocks), dim3(UNI_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(k_stretch_settle<Team9>, dim3(forced > 0 ? (unsigned)forced : settle_blocks(a, cus)), dim3(UNI_BLOCK), 0, s, a);
     return hipGetLastError();
 }
 
-// the nested sampler's settle step (gf_nested.hip): one launch after every walk step, same grid rule
+// the nested sampler's settle step (gf_nested.hip): one launch after every walk step
 hipError_t gf_launch_nested_settle(const GfSettleArgs& a, int cus, hipStream_t s)
 {
-    constexpr int64_t per_block = (UNI_BLOCK / 64) * Team9::PER_WAVE;
-    const int64_t nprop = (int64_t)a.nchains * (a.nwalkers / 2);
-    int64_t blocks = (nprop * GF_UNI_MAX_FANOUT + per_block - 1) / per_block;
-    if (blocks > cus) blocks = cus;
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL((k_stretch_settle<Team9, true>), dim3((unsigned)blocks), dim3(UNI_BLOCK), 0, s, a);
+    hipLaunchKernelGGL((k_stretch_settle<Team9, true>), dim3(settle_blocks(a, cus)), dim3(UNI_BLOCK), 0, s, a);
     return hipGetLastError();
 }
 
-// the maximiser's settle step (gf_simplex.hip): one launch after every evaluation round, same grid rule
+// the maximiser's settle step (gf_simplex.hip): one launch after every evaluation round
 hipError_t gf_launch_simplex_settle(const GfSettleArgs& a, int cus, hipStream_t s)
 {
-    constexpr int64_t per_block = (UNI_BLOCK / 64) * Team9::PER_WAVE;
-    const int64_t nprop = (int64_t)a.nchains * (a.nwalkers / 2);
-    int64_t blocks = (nprop * GF_UNI_MAX_FANOUT + per_block - 1) / per_block;
-    if (blocks > cus) blocks = cus;
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL((k_stretch_settle<Team9, false, true>), dim3((unsigned)blocks), dim3(UNI_BLOCK), 0, s, a);
+    hipLaunchKernelGGL((k_stretch_settle<Team9, false, true>), dim3(settle_blocks(a, cus)), dim3(UNI_BLOCK), 0, s, a);
     return hipGetLastError();
 }
 

@@ -42,54 +42,90 @@ def _handle(m):
     return model._h
 
 
-class NestedSampler:
-    """`nruns` independent nested-sampling runs, run r on posterior models[r] (Model or LnProb; they share device, ndim and
-    mode and must stay open while the sampler lives).  `cols`: the scanned columns (indices into theta); `bases`
-    ([nruns][ndim] or [ndim]): the values of every other column.  `run_ids`: the Philox stream of each run (default 0..nruns-1);
-    a scan passes each point's index in its full list so that a point's result does not depend on what else shares the call.
-    `labels`: what an AssertionError names for a failed run (default: the run index)."""
+class _CubeRuns:
+    """What NestedSampler and SimplexMaximizer share: `nruns` runs, run r on posterior models[r] (Model or LnProb; they share
+    device, ndim and mode and must stay open while the object lives) over the unit cube of the columns `cols` (indices into
+    theta), every other column at `bases` ([nruns][ndim] or [ndim]); the device object of the C ABI's gf_<_abi>_* calls.
+    `run_ids`: the Philox stream of each run (default 0..nruns-1); a scan passes each point's index in its full list so that a
+    point's result does not depend on what else shares the call.  `labels`: what an AssertionError names for a failed run
+    (default: the run index)."""
+    _abi = None                 # "nested" or "simplex"
+    _what = None                # a run's name in the AssertionError
 
-    def __init__(self, models, cols, bases, nlive=DEFAULT_NLIVE, batch=None, walks=DEFAULT_WALKS, seed=0,
-                 on_nonunitary="raise", tol=DEFAULT_TOL, run_ids=None, labels=None):
+    def _open(self, models, cols, bases, on_nonunitary, labels):
+        """Checks and keeps the common arguments; returns the models' handles for gf_<_abi>_create."""
         if on_nonunitary not in ("raise", "-inf"):
             raise ValueError("on_nonunitary must be 'raise' or '-inf'")
         self._L = _lib.lib()
         self.models = list(models)
         self.nruns = len(self.models)
         self.cols = np.ascontiguousarray(cols, dtype=np.int32)
+        self.nscan = len(self.cols)
         ndim = self._L.gf_model_ndim(_handle(self.models[0]))
         b = np.asarray(bases, dtype=np.float64)
         if b.ndim == 1:
             b = np.tile(b, (self.nruns, 1))
         self.bases = np.ascontiguousarray(b.reshape(self.nruns, ndim))
+        self.on_nonunitary = on_nonunitary
+        self.labels = list(labels) if labels is not None else list(range(self.nruns))
+        return (C.c_void_p * self.nruns)(*[_handle(m) for m in self.models])
+
+    def _set_run_ids(self, run_ids):
+        if run_ids is not None:
+            ids = np.ascontiguousarray(run_ids, dtype=np.uint64)
+            name = "gf_{0}_set_run_ids".format(self._abi)
+            _lib.check(getattr(self._L, name)(self._h, ids.ctypes.data_as(C.POINTER(C.c_uint64))), name)
+
+    def _checked(self, res, check):
+        """res, or AssertionError for the first run that failed on a non-unitary point (on_nonunitary == 'raise') when `check`."""
+        if check and self.on_nonunitary == "raise" and res["failed"].any():
+            r = int(np.argmax(res["failed"]))
+            raise AssertionError("Matrix is not unitary! ({0} {1}: {2})".format(self._what, r, self.labels[r]))
+        return res
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(self._L, "gf_{0}_destroy".format(self._abi))(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class NestedSampler(_CubeRuns):
+    """`nruns` independent nested-sampling runs (_CubeRuns: models, cols, bases, run_ids, labels)."""
+    _abi, _what = "nested", "nested run"
+
+    def __init__(self, models, cols, bases, nlive=DEFAULT_NLIVE, batch=None, walks=DEFAULT_WALKS, seed=0,
+                 on_nonunitary="raise", tol=DEFAULT_TOL, run_ids=None, labels=None):
+        hs = self._open(models, cols, bases, on_nonunitary, labels)
         self.nlive = int(nlive)
         self.batch = int(batch) if batch is not None else max(1, self.nlive // 8)
         self.walks = int(walks)
         self.seed = int(seed)
-        self.on_nonunitary = on_nonunitary
-        self.labels = list(labels) if labels is not None else list(range(self.nruns))
-        hs = (C.c_void_p * self.nruns)(*[_handle(m) for m in self.models])
         h = C.c_void_p()
-        _lib.check(self._L.gf_nested_create(hs, self.nruns, len(self.cols), self.cols.ctypes.data_as(_lib._ip),
+        _lib.check(self._L.gf_nested_create(hs, self.nruns, self.nscan, self.cols.ctypes.data_as(_lib._ip),
                                             self.bases.ctypes.data_as(_lib._dp), self.nlive, self.batch, self.walks,
                                             self.seed & 0xFFFFFFFFFFFFFFFF, 0 if on_nonunitary == "raise" else 1, C.byref(h)),
                    "gf_nested_create")
         self._h = h
         _lib.check(self._L.gf_nested_set_tolerance(self._h, float(tol)), "gf_nested_set_tolerance")
-        if run_ids is not None:
-            ids = np.ascontiguousarray(run_ids, dtype=np.uint64)
-            _lib.check(self._L.gf_nested_set_run_ids(self._h, ids.ctypes.data_as(C.POINTER(C.c_uint64))),
-                       "gf_nested_set_run_ids")
+        self._set_run_ids(run_ids)
 
     def run(self, max_iter=100000, check=True):
         """Iterate every run to its tolerance; returns result(), raising AssertionError for a run that met a proposal the
         reference would have raised on (on_nonunitary == 'raise', sens.py:283-285) when `check`."""
         _lib.check(self._L.gf_nested_run(self._h, int(max_iter)), "gf_nested_run")
-        res = self.result()
-        if check and self.on_nonunitary == "raise" and res["failed"].any():
-            r = int(np.argmax(res["failed"]))
-            raise AssertionError("Matrix is not unitary! (nested run {0}: {1})".format(r, self.labels[r]))
-        return res
+        return self._checked(self.result(), check)
 
     def result(self):
         n = self.nruns
@@ -121,23 +157,6 @@ class NestedSampler:
         theta = np.tile(self.bases[run], (n, 1))
         theta[:, self.cols] = (hi - lo) * cube + lo          # mn.py:35-36
         return dict(lnl=lnl, lnw=lnw, cube=cube, theta=theta, nlive_seq=seq, ndead=ndead)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.gf_nested_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _logaddexp(x, y):
@@ -250,6 +269,28 @@ def _opt(args, name, default):
     return default if v is None else v
 
 
+def _scan_models(args, asimov_paramset, llh_paramset, scales, smearing, device):
+    """The per-scale set-up of sens.py's scans: the scanned columns are every column but the scale (sens.py:217-218), the scale
+    column is fixed at each scale with its box lowered for the null point, one Model per scale.  Returns (cols, models, bases,
+    labels); a model that cannot be built closes the ones before it."""
+    names = list(llh_paramset.names)
+    scale_col = names.index(llh_paramset.from_tag(ParamTag.SCALE)[0].name)
+    cols = [i for i in range(len(names)) if i != scale_col]
+    smearing = float(smearing if smearing is not None else _opt(args, "smearing", 0.02))
+    models, bases = [], []
+    try:
+        for sc in scales:
+            ps = _scale_paramset(llh_paramset, float(sc))
+            models.append(Model(_bsm_desc(args, asimov_paramset, ps, smearing), device=device))
+            bases.append(np.array(ps.values, dtype=np.float64))
+    except BaseException:
+        for m in models:
+            m.close()
+        raise
+    labels = ["scale {0:.6g} (Lambda^-1 = {1:.0E})".format(sc, np.power(10., sc)) for sc in scales]
+    return cols, models, bases, labels
+
+
 def evidence_scan(args, asimov_paramset, llh_paramset, scales, run_ids=None, nlive=None, tol=None, batch=None, walks=None,
                   seed=None, on_nonunitary="raise", smearing=None, device=0, max_iter=100000, return_sampler=False):
     """sens.py:231-303 for every scale at once: the scanned columns are every column but the scale (sens.py:217-218), the scale
@@ -258,16 +299,7 @@ def evidence_scan(args, asimov_paramset, llh_paramset, scales, run_ids=None, nli
     nevals, nonunitary, seconds)."""
     import time
     scales = np.asarray(scales, dtype=np.float64)
-    names = list(llh_paramset.names)
-    scale_col = names.index(llh_paramset.from_tag(ParamTag.SCALE)[0].name)
-    cols = [i for i in range(len(names)) if i != scale_col]
-    smearing = float(smearing if smearing is not None else _opt(args, "smearing", 0.02))
-    models, bases = [], []
-    for sc in scales:
-        ps = _scale_paramset(llh_paramset, float(sc))
-        models.append(Model(_bsm_desc(args, asimov_paramset, ps, smearing), device=device))
-        bases.append(np.array(ps.values, dtype=np.float64))
-    labels = ["scale {0:.6g} (Lambda^-1 = {1:.0E})".format(sc, np.power(10., sc)) for sc in scales]
+    cols, models, bases, labels = _scan_models(args, asimov_paramset, llh_paramset, scales, smearing, device)
     try:
         s = NestedSampler(models, cols, bases, nlive=int(nlive or _opt(args, "mn_live_points", DEFAULT_NLIVE)),
                           batch=batch if batch is not None else _opt(args, "mn_batch", None),

@@ -18,9 +18,7 @@ import time
 import numpy as np
 
 from . import _lib
-from .model import Model
-from .nested import _bsm_desc, _handle, _opt, _scale_paramset
-from .enums import ParamTag
+from .nested import _CubeRuns, _opt, _scan_models
 
 __all__ = ["SimplexMaximizer", "nelder_mead_speculative", "nm_coefficients", "profile_scan", "profile_likelihood_limit",
            "DEFAULT_STARTS", "DEFAULT_SEED_POINTS", "DEFAULT_XATOL", "DEFAULT_FATOL", "DEFAULT_RESTARTS", "AGREE_TOL"]
@@ -189,35 +187,19 @@ def nelder_mead_speculative(f_batch, x0, xatol=DEFAULT_XATOL, fatol=DEFAULT_FATO
     return out
 
 
-class SimplexMaximizer:
-    """`nruns` independent maximisations of ln_prob, run r on posterior models[r] (Model or LnProb; they share device, ndim and
-    mode and must stay open while the maximiser lives), over the unit cube of the columns `cols`, every other column at
-    `bases` ([nruns][ndim] or [ndim]).  Starts: the `nstarts` best finite points of `nseed` uniform cube points per run, then
-    `starts` ([nruns][k][nscan] or [k][nscan] cube points; optional).  `run_ids`: the Philox stream of each run (default
-    0..nruns-1); `labels`: what an AssertionError names for a failed run.  Options as scipy's Nelder-Mead (xatol, fatol,
-    maxiter = 200 n by default, adaptive) plus `restarts`."""
+class SimplexMaximizer(_CubeRuns):
+    """`nruns` independent maximisations of ln_prob (nested._CubeRuns: models, cols, bases, run_ids, labels).  Starts: the
+    `nstarts` best finite points of `nseed` uniform cube points per run, then `starts` ([nruns][k][nscan] or [k][nscan] cube
+    points; optional).  Options as scipy's Nelder-Mead (xatol, fatol, maxiter = 200 n by default, adaptive) plus `restarts`."""
+    _abi, _what = "simplex", "profile run"
 
     def __init__(self, models, cols, bases, nstarts=DEFAULT_STARTS, nseed=DEFAULT_SEED_POINTS, seed=0, starts=None,
                  on_nonunitary="raise", xatol=DEFAULT_XATOL, fatol=DEFAULT_FATOL, maxiter=None, adaptive=False,
                  restarts=DEFAULT_RESTARTS, run_ids=None, labels=None):
-        if on_nonunitary not in ("raise", "-inf"):
-            raise ValueError("on_nonunitary must be 'raise' or '-inf'")
-        self._L = _lib.lib()
-        self.models = list(models)
-        self.nruns = len(self.models)
-        self.cols = np.ascontiguousarray(cols, dtype=np.int32)
-        self.nscan = len(self.cols)
-        ndim = self._L.gf_model_ndim(_handle(self.models[0]))
-        b = np.asarray(bases, dtype=np.float64)
-        if b.ndim == 1:
-            b = np.tile(b, (self.nruns, 1))
-        self.bases = np.ascontiguousarray(b.reshape(self.nruns, ndim))
+        hs = self._open(models, cols, bases, on_nonunitary, labels)
         self.nstarts, self.nseed, self.seed = int(nstarts), int(nseed), int(seed)
         self.maxiter = int(maxiter) if maxiter is not None else 200 * self.nscan
         self.restarts = int(restarts)
-        self.on_nonunitary = on_nonunitary
-        self.labels = list(labels) if labels is not None else list(range(self.nruns))
-        hs = (C.c_void_p * self.nruns)(*[_handle(m) for m in self.models])
         h = C.c_void_p()
         _lib.check(self._L.gf_simplex_create(hs, self.nruns, self.nscan, self.cols.ctypes.data_as(_lib._ip),
                                              self.bases.ctypes.data_as(_lib._dp), self.nstarts, self.nseed,
@@ -234,10 +216,7 @@ class SimplexMaximizer:
             st = np.ascontiguousarray(st.reshape(self.nruns, -1, self.nscan))
             self.nuser = st.shape[1]
             _lib.check(self._L.gf_simplex_set_starts(self._h, self.nuser, st.ctypes.data_as(_lib._dp)), "gf_simplex_set_starts")
-        if run_ids is not None:
-            ids = np.ascontiguousarray(run_ids, dtype=np.uint64)
-            _lib.check(self._L.gf_simplex_set_run_ids(self._h, ids.ctypes.data_as(C.POINTER(C.c_uint64))),
-                       "gf_simplex_set_run_ids")
+        self._set_run_ids(run_ids)
 
     def max_rounds(self):
         """Evaluation rounds after which every start has finished: per minimize call one round for the initial simplex and at
@@ -248,11 +227,7 @@ class SimplexMaximizer:
         """Every start to its end; returns result(), raising AssertionError for a run that evaluated a point the reference
         would have raised on (on_nonunitary == 'raise') when `check`."""
         _lib.check(self._L.gf_simplex_run(self._h, self.max_rounds()), "gf_simplex_run")
-        res = self.result()
-        if check and self.on_nonunitary == "raise" and res["failed"].any():
-            r = int(np.argmax(res["failed"]))
-            raise AssertionError("Matrix is not unitary! (profile run {0}: {1})".format(r, self.labels[r]))
-        return res
+        return self._checked(self.result(), check)
 
     def result(self):
         n = self.nruns
@@ -289,23 +264,6 @@ class SimplexMaximizer:
         lo, hi = np.asarray(desc.lo)[self.cols], np.asarray(desc.hi)[self.cols]
         return (hi - lo) * np.asarray(cube, dtype=np.float64) + lo
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.gf_simplex_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def profile_scan(args, asimov_paramset, llh_paramset, scales, run_ids=None, nstarts=None, nseed=None, xatol=None, fatol=None,
                  maxiter=None, restarts=None, adaptive=None, seed=None, on_nonunitary="raise", smearing=None, device=0,
@@ -315,16 +273,7 @@ def profile_scan(args, asimov_paramset, llh_paramset, scales, run_ids=None, nsta
     `args` as for evidence_scan plus the --pl-* options.  Returns dict(scales, max_lnl, argmax_theta, nstarts, nfev, nevals,
     niter, nonunitary, seconds, starts_agreeing: the starts whose final lnL is within AGREE_TOL of the run's best)."""
     scales = np.asarray(scales, dtype=np.float64)
-    names = list(llh_paramset.names)
-    scale_col = names.index(llh_paramset.from_tag(ParamTag.SCALE)[0].name)
-    cols = [i for i in range(len(names)) if i != scale_col]
-    smearing = float(smearing if smearing is not None else _opt(args, "smearing", 0.02))
-    models, bases = [], []
-    for sc in scales:
-        ps = _scale_paramset(llh_paramset, float(sc))
-        models.append(Model(_bsm_desc(args, asimov_paramset, ps, smearing), device=device))
-        bases.append(np.array(ps.values, dtype=np.float64))
-    labels = ["scale {0:.6g} (Lambda^-1 = {1:.0E})".format(sc, np.power(10., sc)) for sc in scales]
+    cols, models, bases, labels = _scan_models(args, asimov_paramset, llh_paramset, scales, smearing, device)
 
     def pick(v, name, default):
         return v if v is not None else _opt(args, name, default)
