@@ -188,16 +188,7 @@ int cube_runs_create(GfCubeRunsHost& h, GfCubeRuns& a, gf_model* const* models, 
 hipError_t cube_runs_alloc_queue(GfCubeRunsHost& h, GfCubeRuns& a, size_t w)
 {
     if (h.mode != MODE_BSM_GAUSS) return hipSuccess;
-    GfArbQueue qh;
-    std::memset(&qh, 0, sizeof(qh));
-    qh.cap = (unsigned int)w;
-    hipError_t e = hipMalloc((void**)&a.pq, sizeof(GfArbQueue) + sizeof(GfArbItem) * w);
-    if (e == hipSuccess) e = hipMalloc((void**)&a.pend_rows, sizeof(double) * w * GF_PEND_STRIDE);
-    if (e == hipSuccess) e = hipMalloc((void**)&h.d_ctl, sizeof(unsigned int) * 2 * w);
-    if (e == hipSuccess) e = hipMemcpyAsync(a.pq, &qh, offsetof(GfArbQueue, items), hipMemcpyHostToDevice, h.stream);
-    if (e == hipSuccess) e = hipMemsetAsync(h.d_ctl, 0, sizeof(unsigned int) * 2 * w, h.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h.stream);             // qh goes out of scope
-    return e;
+    return gf_alloc_arb_queue(w, h.stream, &a.pq, &a.pend_rows, &h.d_ctl);
 }
 
 // the settle kernel's arguments common to both variants: run r is its chain r, `nwalkers` / 2 proposals each

@@ -18,7 +18,6 @@
 
 #include "gf_consts.h"
 
-extern "C" const char* gf_internal_env(const char* name, int affects_results);   // gf_capi.hip: getenv with a record
 #include "gf_launch.h"
 
 #include "gf_device.hpp"
@@ -207,11 +206,6 @@ __global__ __launch_bounds__(GF_BLOCK, (sm_waves_per_eu<NDIM, MODE, SAMPLED, tru
         if (status) status[i] = st;
     }
 }
-
-#if defined(GF_ASM_PIPE) || defined(GF_EXPERIMENTAL_RING)
-#include "../../tools/experiments/gf_sm_experiments.hpp"   // measured alternatives, not built by default
-#endif
-
 
 // Generic kernel: any layout, runtime row length, ragged tiles; walkers [first, n) of the batch.
 template <int NDIM, int MODE>
@@ -449,50 +443,17 @@ hipError_t launch_lnprob_sm_nm(const GfCommon& c, const double* ptab, const doub
         // a small ragged batch (emcee's half-ensembles) is one launch of the generic kernel, not fast + tail
         if (n <= 2048 && n % GF_WAVE != 0) nfull = 0;
         if (layout == 0 && nfull > 0) {
-#ifdef GF_EXPERIMENTAL_RING
-            static const bool use_ring = gf_internal_env("GF_SM_RING", 0) != nullptr;
-#else
-            constexpr bool use_ring = false;
-#endif
-            if (use_ring && (NDIM % 2) == 0 && c.idx_sm[0] == 0 && c.idx_sm[1] == 1 && c.idx_sm[2] == 2 && c.idx_sm[3] == 3 &&
-                c.idx_src[0] == 4 && c.idx_src[1] == 5 && !fr) {
-#ifdef GF_EXPERIMENTAL_RING
-                if constexpr (NDIM >= 6 && (NDIM % 2) == 0) {
-                    static int* d_err = nullptr;
-                    if (!d_err) { (void)hipMalloc((void**)&d_err, sizeof(int)); (void)hipMemset(d_err, 0, sizeof(int)); }
-                    const int64_t cap = (int64_t)cus * 2;
-                    const int rgrid = (int)(nfull < cap ? nfull : cap);
-                    hipLaunchKernelGGL((k_lnprob_sm_ring<NDIM, MODE, 2, false>), dim3(rgrid), dim3(512), 0, s, c, ptab, theta, nfull,
-                                       lnprob, fr, status, d_err);
-                    first = nfull * GF_WAVE;
-                }
-#endif
-            } else {
             const int grid = grid_for(nfull * GF_WAVE, GF_BLOCK, cus);
             const bool sampled = c.idx_sm[0] >= 0 && c.idx_sm[1] >= 0 && c.idx_sm[2] >= 0 && c.idx_sm[3] >= 0 &&
                                  c.idx_src[0] >= 0 && c.idx_src[1] >= 0;
-#define GF_GO(S, F) hipLaunchKernelGGL((k_lnprob_sm_fast<NDIM, MODE, S, F>), dim3(grid), dim3(GF_BLOCK), 0, s, c, ptab, theta, nfull, lnprob, fr, status)
-            bool piped = false;
-#ifdef GF_ASM_PIPE
-            if constexpr (NDIM == 6 || NDIM == 4) {
-                const bool canon6 = sampled && NDIM >= 6 && c.idx_sm[0] == 0 && c.idx_sm[1] == 1 && c.idx_sm[2] == 2 &&
-                                    c.idx_sm[3] == 3 && c.idx_src[0] == 4 && c.idx_src[1] == 5;
-                if (!fr && (canon6 || MODE == MODE_PRIOR_ONLY)) {
-                    if (canon6) hipLaunchKernelGGL((k_lnprob_sm_pipe<NDIM, MODE, 2>), dim3(grid), dim3(GF_BLOCK), 0, s, c, ptab, theta, nfull, lnprob, status);
-                    else hipLaunchKernelGGL((k_lnprob_sm_pipe<NDIM, MODE, 0>), dim3(grid), dim3(GF_BLOCK), 0, s, c, ptab, theta, nfull, lnprob, status);
-                    piped = true;
-                }
-            }
-#endif
             const bool canon = sampled && NDIM >= 6 && c.idx_sm[0] == 0 && c.idx_sm[1] == 1 && c.idx_sm[2] == 2 &&
                                c.idx_sm[3] == 3 && c.idx_src[0] == 4 && c.idx_src[1] == 5;
-            if (piped)        { }
-            else if (canon)   { if (fr) GF_GO(2, true); else GF_GO(2, false); }
+#define GF_GO(S, F) hipLaunchKernelGGL((k_lnprob_sm_fast<NDIM, MODE, S, F>), dim3(grid), dim3(GF_BLOCK), 0, s, c, ptab, theta, nfull, lnprob, fr, status)
+            if (canon)        { if (fr) GF_GO(2, true); else GF_GO(2, false); }
             else if (sampled) { if (fr) GF_GO(1, true); else GF_GO(1, false); }
             else              { if (fr) GF_GO(0, true); else GF_GO(0, false); }
 #undef GF_GO
             first = nfull * GF_WAVE;
-            }
         }
     }
     if constexpr (NDIM != 0) {

@@ -22,15 +22,16 @@
 #include <cstdlib>
 #include <cstring>
 #include <cstddef>
+#include <memory>
 #include <new>
 
-#include "gf_host.h"
+#include "gf_devcache.h"                // large device allocations are cached, not handed back to the driver (hipMalloc / hipFree are macros from here on)
+#include "gf_host.h"                    // (after gf_devcache.h: gf_alloc_arb_queue allocates through the cache)
 #include "gf_device.hpp"
 #include "gf_bsm_device.hpp"
 #include "gf_launch.h"
 #include "gf_unitarity_teams.hpp"      // Team9: the reference's unitarity chain on nine lanes (k_stretch_chain settles its own parked proposals)
 #include "gf_propose.hpp"               // philox_block, proposal_lnprob: shared with the nested sampler (gf_nested.hip)
-#include "gf_devcache.h"                // large device allocations are cached, not handed back to the driver (hipMalloc / hipFree are macros from here on)
 
 namespace {
 using namespace gfdev;
@@ -495,11 +496,6 @@ struct ChainArgs {
     double* lazy_rows;              // [nchains][lazy_cap][GF_PEND_STRIDE]: undecided proposals that are rejected either way ...
     unsigned long long* lazy_mask;  // [nchains][lazy_cap]: ... with their undecided bins (k_stretch_chain settles them in bulk)
     int32_t lazy_cap;
-    // k_stretch_flow: versioned walker states and the in-flight proposals' rows / Hamiltonian terms
-    double* pv;                     // [nchains][FLOW_VERS][nwalkers][ndim]: a walker's position after its v-th update, in slot v mod FLOW_VERS
-    double* lv;                     // [nchains][FLOW_VERS][nwalkers]
-    double* frows;                  // [nchains][nwalkers][GF_PEND_STRIDE]: the parked proposal of a walker (it has at most one in flight)
-    double* fterms;                 // [nchains][nwalkers][9][8]: its two Hamiltonian terms once a team has built them
     unsigned long long* stats;      // [nchains][8] (may be null): per chain, ns on the 100 MHz wall clock spent in [0] proposals, [1] settling
                                     // parked proposals, [2] bulk settlement; [3] proposals waited for, [4] passes that waited, [5] settled in bulk,
                                     // [6] passes, [7] bulk settlements
@@ -820,343 +816,8 @@ __global__ __launch_bounds__(CH_BLOCK) void k_stretch_chain(const ChainArgs s)
     flush_lazy();
 }
 
-#ifdef GF_EXPERIMENTAL_FLOW
-// (measured and not kept, round 4 -- compiled only with -DGF_EXPERIMENTAL_FLOW, selected with GF_SAMPLER_CHAIN=3: bitwise the grid
-// sampler's chain on the full C5 scan, 480 rounds for 400 half-steps on the heaviest chain -- the dataflow does what it should -- but
-// a round costs a full proposal phase AND a full settle slice one after the other (55 + 65 us measured, thread 0 building the unit
-// list serially among it), 190 us per half-step against 152 for k_stretch_chain and 117 for the grid kernels; a work-conserving
-// version (any wave proposing or settling as needed) is bounded at ~64 us per half-step for such a chain by the emulated-x87 work
-// itself: profiles/r04/chain_dataflow_not_kept.txt)
-// ---- the same chain as a DATAFLOW inside the workgroup ---------------------------------------------------------------------------
-// k_stretch_chain still moves a chain half-step by half-step: when a half-step parks proposals, ALL its walkers wait until the parked
-// ones are settled -- and the census says that the chains which bound a scan park ~10 proposals in every half-step and spend half
-// their time in that wait (profiles/r04/chain_census.txt).  But a stretch move needs only TWO inputs: the walker's own position and
-// its partner's.  So here every walker carries the count of updates it has completed; a walker's next update runs as soon as its own
-// previous update and its partner's required one are FINAL, whatever the rest of the ensemble is doing; a parked proposal is settled
-// in slices (one team-unit of ~16-23 us per round: the walker's terms, then its undecided bins, highest energy first, stopping at the
-// first failure) while everybody who does not depend on it moves on, and the walkers that fell behind catch up at one update per
-// round.  A walker's last FLOW_VERS positions are kept (slot = update count mod FLOW_VERS) and nobody runs more than FLOW_AHEAD
-// updates ahead of the slowest, so a partner's required version is always still there.  Every update is the computation
-// k_stretch / k_stretch_chain make -- same Philox counter (walker slot, half-step), same inputs, same accept rule, same stored
-// sample -- only the ORDER in which independent updates are executed differs: the chain is the same bit for bit.
-//
-// One round:  P  thread w (= walker w) proposes if its inputs are final: decided -> final at once; undecided and rejected either way ->
-//                final, verdict counted later (bulk); undecided and the verdict decides -> parked (row kept, walker busy)
-//             S  one slice of settling: up to 56 units -- TERMS of a newly parked proposal, or one (walker, bin) PAIR of one whose
-//                terms are ready, handed out rank-major -- one per nine-lane team; proposals whose bins are all done (or one failed)
-//                are completed: accept step, new version, walker free again
-// Barriers only, no wave ever waits for another outside them.
-constexpr int FLOW_VERS = 4;
-constexpr int FLOW_AHEAD = 2;
-constexpr unsigned int FLOW_TERMS = 255u;                 // unit kind: build the Hamiltonian terms (else: the rank of the bin to evaluate)
-// e_info: bits 0-6 undecided bins (<= 64), 7-13 ranks handed out, 14-20 pairs done, 21 one failed, 22 terms being built, 23 terms ready, 24 dead
-#define FLOW_NBITS(i) ((i) & 127u)
-#define FLOW_STARTED(i) (((i) >> 7) & 127u)
-#define FLOW_DONE(i) (((i) >> 14) & 127u)
-#define FLOW_ONE_STARTED (1u << 7)
-#define FLOW_ONE_DONE (1u << 14)
-#define FLOW_FAIL (1u << 21)
-#define FLOW_TBUSY (1u << 22)
-#define FLOW_TREADY (1u << 23)
-#define FLOW_DEAD (1u << 24)
-
-// one walker's update u of k_stretch_flow: returns true when the walker is final again (decided here), false when its proposal was parked
-template <int NDIM>
-__device__ __attribute__((noinline)) bool flow_propose(const ChainArgs& s, const GfCommon& c, const GfBsm* __restrict__ tb, LdsD ctab_l, LdsD ttab_l,
-                                                       LdsD row_l, const int chain, const int w, const unsigned int u, const int wj,
-                                                       const unsigned int need, const double z, const double u3, double* lz_rows,
-                                                       unsigned long long* lz_mask, LdsU new_n, LdsI new_w, LdsL new_mask, LdsU lz_n)
+hipError_t launch_chain(int ndim, int nchains, const ChainArgs& a, hipStream_t st)
 {
-    constexpr int ND = NDIM ? NDIM : GF_MAX_DIM;
-    const double* ctab = (const double*)ctab_l;
-    const double* ttab = (const double*)ttab_l;
-    double* row = (double*)row_l;
-    const int ndim = NDIM ? NDIM : c.ndim;
-    const int nw = s.nwalkers;
-    const int64_t run_step = s.run_step_base + (int64_t)u;
-    const bool store_now = s.store != 0 && s.chain != nullptr && (run_step % s.thin) == 0;
-    const int64_t store_index = s.store_base + (run_step + s.thin - 1) / s.thin;
-    const size_t vbase = (size_t)chain * FLOW_VERS;
-    const double* sk = s.pv + ((vbase + (u & (FLOW_VERS - 1))) * nw + w) * ndim;
-    const double* cj = s.pv + ((vbase + (need & (FLOW_VERS - 1))) * nw + wj) * ndim;
-    double* nx = s.pv + ((vbase + ((u + 1u) & (FLOW_VERS - 1))) * nw + w) * ndim;
-#pragma unroll
-    for (int d = 0; d < ND; ++d) {
-        if (!NDIM && d >= ndim) break;
-        const double cv = cj[d];
-        row[d] = fma(-z, cv - sk[d], cv);
-    }
-    int st;
-    unsigned long long pending;
-    const double lnq = proposal_lnprob<NDIM, MODE_BSM_GAUSS, 1>(c, tb, ctab, ttab, row, ndim, st, 0, nullptr, pending);
-    const double lnk = s.lv[(vbase + (u & (FLOW_VERS - 1))) * nw + w];
-    double zp = 1.0;
-    for (int d = 1; d < ndim; ++d) zp *= z;
-    const double lhs = log(zp / u3);
-    bool accept = lhs > lnk - lnq;                        // false for NaN and for lnq = -inf
-    if (pending != 0ull && accept) {
-        double* dst = s.frows + ((size_t)chain * nw + w) * GF_PEND_STRIDE;
-        for (int d = 0; d < ndim; ++d) dst[d] = row[d];
-        dst[GF_MAX_DIM] = lnq;
-        const unsigned int at = atomicAdd((unsigned int*)new_n, 1u);
-        new_w[at] = w;
-        new_mask[at] = pending;
-        return false;
-    }
-    if (pending != 0ull) {                                // undecided, rejected either way: only the count wants the verdict
-        const unsigned int at = atomicAdd((unsigned int*)lz_n, 1u);
-        double* dst = lz_rows + (size_t)at * GF_PEND_STRIDE;
-        for (int d = 0; d < ndim; ++d) dst[d] = row[d];
-        lz_mask[at] = pending;
-    }
-    if (st == ST_NON_UNITARY) { accept = false; atomicAdd(s.flags, 1u); }
-#pragma unroll
-    for (int d = 0; d < ND; ++d) {
-        if (!NDIM && d >= ndim) break;
-        nx[d] = accept ? row[d] : sk[d];
-    }
-    s.lv[(vbase + ((u + 1u) & (FLOW_VERS - 1))) * nw + w] = accept ? lnq : lnk;
-    if (accept) s.naccept[(int64_t)chain * nw + w] += 1u;
-    if (store_now) {
-        double* dst = s.chain + (((int64_t)chain * s.nstore_cap + store_index) * nw + w) * ndim;
-#pragma unroll
-        for (int d = 0; d < ND; ++d) {
-            if (!NDIM && d >= ndim) break;
-            dst[d] = accept ? row[d] : sk[d];
-        }
-        if (s.lnp_chain) s.lnp_chain[((int64_t)chain * s.nstore_cap + store_index) * nw + w] = accept ? lnq : lnk;
-    }
-    return true;
-}
-
-template <int NDIM>
-__global__ __launch_bounds__(CH_BLOCK) void k_stretch_flow(const ChainArgs s)
-{
-    constexpr int ND = NDIM ? NDIM : GF_MAX_DIM;
-    constexpr int TEAMS = CH_WAVES * Team9::PER_WAVE;
-    constexpr int TEAM_DOUBLES = TEAMS * Team9::DOUBLES;
-    constexpr int TILE_DOUBLES = CH_WAVES * GF_WAVE * ND;
-    __shared__ __attribute__((aligned(16))) double uni[TEAM_DOUBLES > TILE_DOUBLES ? TEAM_DOUBLES : TILE_DOUBLES];
-    __shared__ __attribute__((aligned(16))) double ctab[GF_MAX_DIM * 4 + 20];
-    __shared__ __attribute__((aligned(16))) double wt[WT_DOUBLES];      // chain_settle (the bulk settlement of the count-only proposals)
-    __shared__ unsigned int du[CH_BLOCK];                 // updates completed, per walker
-    __shared__ unsigned int busy[CH_BLOCK];               // the walker has a parked proposal in flight
-    __shared__ int e_w[CH_BLOCK];                         // parked proposals in flight: walker ...
-    __shared__ unsigned long long e_mask[CH_BLOCK];       // ... undecided bins ...
-    __shared__ unsigned int e_info[CH_BLOCK];             // ... progress (FLOW_* above)
-    __shared__ int new_w[CH_BLOCK];
-    __shared__ unsigned long long new_mask[CH_BLOCK];
-    __shared__ unsigned int unit_e[TEAMS], unit_r[TEAMS];
-    __shared__ unsigned int pk_ctl[2 * CH_BLOCK];         // chain_settle's counters (zero between uses)
-    __shared__ unsigned int e_n, new_n, unit_n, lz_n, min_u, pk_head, pk_aux;
-
-    const int chain = blockIdx.x;
-    const GfCommon& c = s.commons[s.nmodels > 1 ? chain : 0];
-    const GfBsm* __restrict__ tb = s.nmodels > 1 ? s.tbs[chain] : s.tb;
-    const double* __restrict__ ptab = s.ptabs[s.nmodels > 1 ? chain : 0];
-    double* ttab = ctab + GF_MAX_DIM * 4;
-    load_eval_tables(ctab, ptab, tb, true);
-    const int ndim = NDIM ? NDIM : c.ndim;
-    const int nw = s.nwalkers, nhalf = nw / 2;
-    const unsigned int U_END = (unsigned int)s.nsteps;
-    const int tid = threadIdx.x, lane = tid & (GF_WAVE - 1), wave = tid / GF_WAVE;
-    const size_t vbase = (size_t)chain * FLOW_VERS;
-    // version 0 = the state the launch starts from
-    for (int i = tid; i < nw * ndim; i += CH_BLOCK) s.pv[vbase * nw * ndim + i] = s.pos[(size_t)chain * nw * ndim + i];
-    for (int i = tid; i < nw; i += CH_BLOCK) s.lv[vbase * nw + i] = s.lnp[(size_t)chain * nw + i];
-    du[tid] = tid < nw ? 0u : U_END;
-    busy[tid] = 0u;
-    pk_ctl[tid] = 0u; pk_ctl[CH_BLOCK + tid] = 0u;
-    if (tid == 0) { e_n = 0u; lz_n = 0u; }
-    __syncthreads();
-
-    const uint64_t sid = s.stream_ids ? s.stream_ids[chain] : (uint64_t)chain;
-    const uint32_t k0s = (uint32_t)s.seed, k1s = (uint32_t)(s.seed >> 32);
-    double* row = uni + (size_t)wave * GF_WAVE * ND + (size_t)lane * ndim;
-    double* const lz_rows = s.lazy_rows + (size_t)chain * s.lazy_cap * GF_PEND_STRIDE;
-    unsigned long long* const lz_mask = s.lazy_mask + (size_t)chain * s.lazy_cap;
-    unsigned long long* const stat = s.stats ? s.stats + (size_t)chain * 8 : nullptr;
-    const int grp = lane / Team9::LANES;
-    const bool team_active = grp < Team9::PER_WAVE;
-    const int tl = lane - grp * Team9::LANES;
-    const int team = wave * Team9::PER_WAVE + grp;
-    auto flush_lazy = [&]() {                              // workgroup-uniform call; barriers inside
-        const unsigned int n = lz_n;
-        if (n != 0u) {
-            const unsigned long long t0 = wall_clock64();
-            chain_settle(uni, wt, n, &pk_head, &pk_aux, pk_ctl, c, tb,
-                         [&](unsigned int i) { return lz_rows + (size_t)i * GF_PEND_STRIDE; },
-                         [&](unsigned int i) { return lz_mask[i]; },
-                         [&](unsigned int, bool bad) { if (bad) atomicAdd(s.flags, 1u); });
-            __syncthreads();
-            if (tid == 0) {
-                lz_n = 0u;
-                if (stat) { stat[2] += 10ull * (wall_clock64() - t0); stat[5] += n; stat[7] += 1ull; }
-            }
-            __syncthreads();
-        }
-    };
-
-    const unsigned int round_limit = 64u * U_END + 4096u;  // a chain needs 2 U_END rounds when nothing is parked: far below this
-    for (unsigned int round = 0;; ++round) {
-        if (tid == 0) { min_u = U_END; new_n = 0u; }
-        __syncthreads();
-        if (tid < nw) atomicMin(&min_u, du[tid]);
-        __syncthreads();
-        const unsigned int mu = min_u;
-        if (mu >= U_END && e_n == 0u) break;               // every walker has made its updates and nothing is in flight
-        if (round > round_limit) { if (tid == 0) atomicAdd(s.flags + 1, 1u); break; }    // (never: reported by the host)
-        if (lz_n + (unsigned int)nw > (unsigned int)s.lazy_cap) flush_lazy();
-        const unsigned long long t_p = wall_clock64();
-        // ---- P: every walker whose inputs are final makes its next update
-        bool fin = false;
-        unsigned int u = 0u;
-        if (tid < nw && busy[tid] == 0u) {
-            u = du[tid];
-            if (u < U_END && u <= mu + (unsigned int)FLOW_AHEAD) {
-                const int half = tid >= nhalf ? 1 : 0;
-                const int k = tid - half * nhalf;
-                const uint64_t g = sid * (uint64_t)nhalf + (uint64_t)k;
-                const uint64_t ctr = 2 * (s.iteration_base + (uint64_t)u) + (uint64_t)half;
-                uint32_t r[4];
-                philox_block((uint32_t)g, (uint32_t)(g >> 32), (uint32_t)ctr, (uint32_t)(ctr >> 32), k0s, k1s, r);
-                const int j = (int)(((uint64_t)r[2] * (uint64_t)nhalf) >> 32);
-                const int wj = (1 - half) * nhalf + j;
-                const unsigned int need = u + (unsigned int)half;     // updates the partner must have completed: its position BEFORE this half-step
-                if (du[wj] >= need) {
-                    const double u1 = ((double)(r[0] >> 5) * 67108864.0 + (double)(r[1] >> 6)) * (1.0 / 9007199254740992.0);
-                    const double u3 = ((double)r[3] + 0.5) * (1.0 / 4294967296.0);
-                    const double zr = fma(s.a - 1.0, u1, 1.0);
-                    const double z = zr * zr / s.a;
-                    fin = flow_propose<NDIM>(s, c, tb, (LdsD)ctab, (LdsD)ttab, (LdsD)row, chain, tid, u, wj, need, z, u3, lz_rows, lz_mask,
-                                             (LdsU)&new_n, (LdsI)new_w, (LdsL)new_mask, (LdsU)&lz_n);
-                    if (!fin) busy[tid] = 1u;
-                }
-            }
-        }
-        __syncthreads();                                    // every read of du[] of this round is done
-        if (fin) du[tid] = u + 1u;
-        // the newly parked proposals join the list
-        const unsigned int nn = new_n, base = e_n;
-        if ((unsigned int)tid < nn) {
-            e_w[base + tid] = new_w[tid];
-            e_mask[base + tid] = new_mask[tid];
-            e_info[base + tid] = (unsigned int)__popcll(new_mask[tid]);
-        }
-        __syncthreads();
-        if (tid == 0) {
-            e_n = base + nn;
-            if (stat) { stat[0] += 10ull * (wall_clock64() - t_p); stat[6] += 1ull; stat[3] += nn; }
-        }
-        __syncthreads();
-        const unsigned int ne = e_n;
-        if (ne == 0u) continue;
-        // ---- S: one slice.  Thread 0 hands out the units: the terms of every proposal that has none yet, then pairs rank-major
-        const unsigned long long t_s = wall_clock64();
-        if (tid == 0) {
-            unsigned int n = 0;
-            for (unsigned int e = 0; e < ne && n < (unsigned int)TEAMS; ++e)
-                if ((e_info[e] & (FLOW_TBUSY | FLOW_TREADY)) == 0u) { unit_e[n] = e; unit_r[n] = FLOW_TERMS; ++n; e_info[e] |= FLOW_TBUSY; }
-            bool more = true;
-            while (more && n < (unsigned int)TEAMS) {
-                more = false;
-                for (unsigned int e = 0; e < ne && n < (unsigned int)TEAMS; ++e) {
-                    const unsigned int inf = e_info[e];
-                    if ((inf & FLOW_TREADY) && !(inf & FLOW_FAIL) && FLOW_STARTED(inf) < FLOW_NBITS(inf)) {
-                        unit_e[n] = e; unit_r[n] = FLOW_STARTED(inf); ++n;
-                        e_info[e] = inf + FLOW_ONE_STARTED;
-                        more = true;
-                    }
-                }
-            }
-            unit_n = n;
-        }
-        __syncthreads();
-        if (team_active && (unsigned int)team < unit_n) {
-            Team9 tm;
-            tm.init(uni + (size_t)team * Team9::DOUBLES, tl);
-            const unsigned int e = unit_e[team], r = unit_r[team];
-            const int w = e_w[e];
-            double* ft = s.fterms + (((size_t)chain * nw + w) * Team9::LANES + tl) * 8;
-            if (r == FLOW_TERMS) {
-                tm.terms(c, *tb, s.frows + ((size_t)chain * nw + w) * GF_PEND_STRIDE, 0, 1, 0, GF_PEND_STRIDE);
-                ft[0] = tm.hs.re.hi; ft[1] = tm.hs.re.lo; ft[2] = tm.hs.im.hi; ft[3] = tm.hs.im.lo;
-                ft[4] = tm.hn.re.hi; ft[5] = tm.hn.re.lo; ft[6] = tm.hn.im.hi; ft[7] = tm.hn.im.lo;
-                if (tm.leader()) atomicOr(&e_info[e], FLOW_TREADY);
-            } else {
-                tm.hs.re.hi = ft[0]; tm.hs.re.lo = ft[1]; tm.hs.im.hi = ft[2]; tm.hs.im.lo = ft[3];
-                tm.hn.re.hi = ft[4]; tm.hn.re.lo = ft[5]; tm.hn.im.hi = ft[6]; tm.hn.im.lo = ft[7];
-                const int kk = nth_bit_from_top(e_mask[e], r);
-                const double res = tm.bin(tb->inv2e[kk], tb->epow[kk]);
-                if (tm.leader()) {
-                    if (!(res < 1e-7)) atomicOr(&e_info[e], FLOW_FAIL);          // fr.py:493-494 (NaN raises too)
-                    atomicAdd(&e_info[e], FLOW_ONE_DONE);
-                }
-            }
-        }
-        __syncthreads();
-        // complete what is settled: every bin done, or one failed (its started pairs have all ended with this slice)
-        if ((unsigned int)tid < ne) {
-            const unsigned int inf = e_info[tid];
-            const bool failed = (inf & FLOW_FAIL) != 0u;
-            if ((inf & FLOW_TREADY) && (failed || FLOW_DONE(inf) == FLOW_NBITS(inf)) && FLOW_DONE(inf) == FLOW_STARTED(inf)) {
-                const int w = e_w[tid];
-                const unsigned int uw = du[w];
-                const double* prow = s.frows + ((size_t)chain * nw + w) * GF_PEND_STRIDE;
-                const double* old = s.pv + ((vbase + (uw & (FLOW_VERS - 1))) * nw + w) * ndim;
-                double* nx = s.pv + ((vbase + ((uw + 1u) & (FLOW_VERS - 1))) * nw + w) * ndim;
-                const double lnq = prow[GF_MAX_DIM];
-                const double lnk = s.lv[(vbase + (uw & (FLOW_VERS - 1))) * nw + w];
-                const bool accept = !failed;                 // the accept test itself passed when the proposal was parked
-                if (failed) atomicAdd(s.flags, 1u);
-                for (int d = 0; d < ndim; ++d) nx[d] = accept ? prow[d] : old[d];
-                s.lv[(vbase + ((uw + 1u) & (FLOW_VERS - 1))) * nw + w] = accept ? lnq : lnk;
-                if (accept) s.naccept[(int64_t)chain * nw + w] += 1u;
-                const int64_t run_step = s.run_step_base + (int64_t)uw;
-                if (s.store != 0 && s.chain != nullptr && (run_step % s.thin) == 0) {
-                    const int64_t store_index = s.store_base + (run_step + s.thin - 1) / s.thin;
-                    double* dst = s.chain + (((int64_t)chain * s.nstore_cap + store_index) * nw + w) * ndim;
-                    for (int d = 0; d < ndim; ++d) dst[d] = accept ? prow[d] : old[d];
-                    if (s.lnp_chain) s.lnp_chain[((int64_t)chain * s.nstore_cap + store_index) * nw + w] = accept ? lnq : lnk;
-                }
-                du[w] = uw + 1u;
-                busy[w] = 0u;
-                e_info[tid] = inf | FLOW_DEAD;
-            }
-        }
-        __syncthreads();
-        if (tid == 0) {                                     // close the gaps
-            unsigned int m = 0;
-            for (unsigned int e = 0; e < ne; ++e)
-                if (!(e_info[e] & FLOW_DEAD)) { if (m != e) { e_w[m] = e_w[e]; e_mask[m] = e_mask[e]; e_info[m] = e_info[e]; } ++m; }
-            e_n = m;
-            if (stat) { stat[1] += 10ull * (wall_clock64() - t_s); stat[4] += 1ull; }
-        }
-        __syncthreads();
-    }
-    __syncthreads();
-    flush_lazy();
-    // the state the launch ends with
-    for (int i = tid; i < nw * ndim; i += CH_BLOCK) s.pos[(size_t)chain * nw * ndim + i] = s.pv[(vbase + (U_END & (FLOW_VERS - 1))) * nw * ndim + i];
-    for (int i = tid; i < nw; i += CH_BLOCK) s.lnp[(size_t)chain * nw + i] = s.lv[(vbase + (U_END & (FLOW_VERS - 1))) * nw + i];
-}
-
-#endif  // GF_EXPERIMENTAL_FLOW
-
-hipError_t launch_chain(int ndim, int nchains, const ChainArgs& a, hipStream_t st, bool flow)
-{
-#ifdef GF_EXPERIMENTAL_FLOW
-    if (flow) {
-        switch (ndim) {
-        case 7: hipLaunchKernelGGL(k_stretch_flow<7>, dim3(nchains), dim3(CH_BLOCK), 0, st, a); break;
-        case 12: hipLaunchKernelGGL(k_stretch_flow<12>, dim3(nchains), dim3(CH_BLOCK), 0, st, a); break;
-        default: hipLaunchKernelGGL(k_stretch_flow<0>, dim3(nchains), dim3(CH_BLOCK), 0, st, a); break;
-        }
-        return hipGetLastError();
-    }
-#else
-    (void)flow;
-#endif
     switch (ndim) {
     case 7: hipLaunchKernelGGL(k_stretch_chain<7>, dim3(nchains), dim3(CH_BLOCK), 0, st, a); break;
     case 12: hipLaunchKernelGGL(k_stretch_chain<12>, dim3(nchains), dim3(CH_BLOCK), 0, st, a); break;
@@ -1225,7 +886,13 @@ hipError_t launch_stretch(const GfCommon& c, const GfBsm* tb, const double* ptab
 struct gf_sampler {
     gf_model* model = nullptr;          // chain 0's model: its stream carries the sampler's launches
     gf_model** models = nullptr;        // [nchains] when every chain has its own posterior, else null
-    GfCommon* d_commons = nullptr;      // device copies for k_stretch_multi
+    // chain 0's model as gf_sampler_create found it (the model outlives the sampler, and its stream never changes)
+    const GfCommon* c = nullptr;        // its constants (host)
+    const GfBsm* tb = nullptr;          // its BSM table (device)
+    const double* ptab = nullptr;       // its prior table (device)
+    hipStream_t stream = nullptr;
+    int device = 0;
+    GfCommon* d_commons = nullptr;      // device copies of every model's constants, [nchains] or [1] (the kernels that take them by pointer)
     const GfBsm** d_tbs = nullptr;
     const double** d_ptabs = nullptr;
     int nchains = 0, nwalkers = 0, ndim = 0;
@@ -1243,10 +910,6 @@ struct gf_sampler {
     unsigned long long* d_lazy_mask = nullptr;   // [nchains][lazy_cap]
     int lazy_cap = 0;
     unsigned long long* d_chain_stats = nullptr;   // [nchains][8]: k_stretch_chain's per-chain census (ChainArgs::stats), zeroed by gf_sampler_reset
-    double* d_pv = nullptr;                        // k_stretch_flow: [nchains][FLOW_VERS][nwalkers][ndim] versioned positions ...
-    double* d_lv = nullptr;                        // ... [nchains][FLOW_VERS][nwalkers] lnprob
-    double* d_frows = nullptr;                     // ... [nchains][nwalkers][GF_PEND_STRIDE] parked proposals
-    double* d_fterms = nullptr;                    // ... [nchains][nwalkers][72] their Hamiltonian terms
     // launch shape of a BSM sampler on small ensembles: 0 = not decided yet, 1 = one workgroup per chain (k_stretch_chain), 2 = the
     // per-half-step grid kernels + k_stretch_settle.  Decided at the start of every run of 128 steps or more, by timing a block of 16
     // steps of each on the sampler's own chains (gf_sampler_run); GF_SAMPLER_CHAIN=0 / 1 forces one
@@ -1312,213 +975,89 @@ int gf_internal_d2h_pipe_rows(gf_d2h_pipe* p, void* dst_host, size_t dpitch, con
 int gf_internal_d2h_pipe_close(gf_d2h_pipe* p);
 }
 
-extern "C" {
-
-
-int gf_sampler_create(gf_model* m, int nchains, int nwalkers, uint64_t seed, double a, gf_sampler** out)
+namespace {
+// gf_sampler_create (multi false: every chain samples models[0]) and gf_sampler_create_multi (multi true: chain ch samples
+// models[ch]): the constant tables are allocated once, with one entry per model
+int sampler_create(gf_model* const* models, bool multi, int nchains, int nwalkers, uint64_t seed, double a, gf_sampler** out)
 {
-    if (!m || !out || nchains < 1 || nwalkers < 2 || (nwalkers & 1) || !(a > 1.0)) return GF_ERR_INVALID_ARG;
+    if (!out || nchains < 1 || nwalkers < 2 || (nwalkers & 1) || !(a > 1.0)) return GF_ERR_INVALID_ARG;
     *out = nullptr;
     const GfCommon* c; const GfBsm* tb; const double* ptab; void* stream; int device;
-    if (gf_model_internal(m, &c, &tb, &ptab, &stream, &device) != GF_OK) return GF_ERR_INVALID_ARG;
+    if (gf_model_internal(models[0], &c, &tb, &ptab, &stream, &device) != GF_OK) return GF_ERR_INVALID_ARG;
     if (nwalkers < 2 * c->ndim) return GF_ERR_INVALID_ARG;        // emcee's own requirement
+    const int nmodels = multi ? nchains : 1;
+    std::unique_ptr<GfCommon[]> hc(new (std::nothrow) GfCommon[nmodels]);
+    std::unique_ptr<const GfBsm*[]> htb(new (std::nothrow) const GfBsm*[nmodels]);
+    std::unique_ptr<const double*[]> hpt(new (std::nothrow) const double*[nmodels]);
+    std::unique_ptr<gf_model*[]> keep(multi ? new (std::nothrow) gf_model*[nmodels] : nullptr);
+    if (!hc || !htb || !hpt || (multi && !keep)) return GF_ERR_ALLOC;
+    int cus0 = 256, nbins_max = 0;
+    for (int ch = 0; ch < nmodels; ++ch) {
+        const GfCommon* cm; int dev, cus, nbins;
+        if (gf_model_constants(models[ch], &cm, &htb[ch], &hpt[ch], &dev, &cus, &nbins) != GF_OK || dev != device ||
+            cm->ndim != c->ndim || cm->mode != c->mode)
+            return gf_fail_msg(GF_ERR_INVALID_ARG, "gf_sampler_create_multi: model %d differs from model 0 in device, ndim or mode", ch);
+        hc[ch] = *cm;
+        if (multi) keep[ch] = models[ch];
+        if (ch == 0) cus0 = cus;
+        if (nbins > nbins_max) nbins_max = nbins;
+    }
     gf_sampler* s = new (std::nothrow) gf_sampler();
     if (!s) return GF_ERR_ALLOC;
-    s->model = m; s->nchains = nchains; s->nwalkers = nwalkers; s->ndim = c->ndim; s->seed = seed; s->a = a;
-    {
-        const GfCommon* cc; const GfBsm* tbb; const double* pt; int dev;
-        gf_model_constants(m, &cc, &tbb, &pt, &dev, &s->cus, &s->nbins_max);
-    }
-    const size_t nw = (size_t)nchains * nwalkers;
+    s->model = models[0]; s->models = keep.release();
+    s->c = c; s->tb = tb; s->ptab = ptab; s->stream = (hipStream_t)stream; s->device = device;
+    s->nchains = nchains; s->nwalkers = nwalkers; s->ndim = c->ndim; s->seed = seed; s->a = a; s->cus = cus0; s->nbins_max = nbins_max;
+    const size_t nw = (size_t)nchains * nwalkers, nm = (size_t)nmodels;
+    // every transfer of this file goes through the sampler's stream: a synchronous (null-stream) hipMemcpy / hipMemset
+    // issued while ANOTHER host thread is capturing its sampler's graph fails and poisons that capture on this runtime
+    hipStream_t st0 = s->stream;
     hipError_t e = hipSetDevice(device);
     if (e == hipSuccess) e = hipMalloc((void**)&s->d_pos, sizeof(double) * nw * s->ndim);
     if (e == hipSuccess) e = hipMalloc((void**)&s->d_lnp, sizeof(double) * nw);
     if (e == hipSuccess) e = hipMalloc((void**)&s->d_naccept, sizeof(uint32_t) * nw);
     if (e == hipSuccess) e = hipMalloc((void**)&s->d_flags, sizeof(uint32_t) * 4);
-    if (e == hipSuccess && c->mode == MODE_BSM_GAUSS) {
-        const size_t nprop = (size_t)nchains * (nwalkers / 2);
-        e = hipMalloc((void**)&s->d_pq, sizeof(GfArbQueue) + sizeof(GfArbItem) * nprop);
-        if (e == hipSuccess) e = hipMalloc((void**)&s->d_pend_rows, sizeof(double) * nprop * GF_PEND_STRIDE);
-        if (e == hipSuccess) e = hipMalloc((void**)&s->d_pend_ctl, sizeof(unsigned int) * 2 * nprop);
-        if (e == hipSuccess) e = hipMemsetAsync(s->d_pend_ctl, 0, sizeof(unsigned int) * 2 * nprop, (hipStream_t)stream);
-        if (e == hipSuccess) {
-            GfArbQueue ah;
-            std::memset(&ah, 0, sizeof(ah));
-            ah.cap = (unsigned int)nprop;
-            e = hipMemcpyAsync(s->d_pq, &ah, offsetof(GfArbQueue, items), hipMemcpyHostToDevice, (hipStream_t)stream);
-            if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);      // `ah` is a local
-        }
-    }
+    if (e == hipSuccess && c->mode == MODE_BSM_GAUSS)
+        e = gf_alloc_arb_queue((size_t)nchains * (nwalkers / 2), st0, &s->d_pq, &s->d_pend_rows, &s->d_pend_ctl);
     if (e == hipSuccess) e = hipMalloc((void**)&s->d_state, sizeof(StepState));
-    // every transfer of this file goes through the sampler's stream: a synchronous (null-stream) hipMemcpy / hipMemset
-    // issued while ANOTHER host thread is capturing its sampler's graph fails and poisons that capture on this runtime
-    hipStream_t st0 = (hipStream_t)stream;
     if (e == hipSuccess) e = hipMemsetAsync(s->d_state, 0, sizeof(StepState), st0);
     if (e == hipSuccess) e = hipMemsetAsync(s->d_naccept, 0, sizeof(uint32_t) * nw, st0);
     if (e == hipSuccess) e = hipMemsetAsync(s->d_flags, 0, sizeof(uint32_t) * 4, st0);
-    // device copies of the constants for the kernels that take them by pointer (k_stretch_persist)
-    if (e == hipSuccess) e = hipMalloc((void**)&s->d_commons, sizeof(GfCommon));
-    if (e == hipSuccess) e = hipMalloc((void**)&s->d_ptabs, sizeof(void*));
-    if (e == hipSuccess) e = hipMemcpyAsync(s->d_commons, c, sizeof(GfCommon), hipMemcpyHostToDevice, st0);
-    if (e == hipSuccess) e = hipMemcpyAsync((void*)s->d_ptabs, &ptab, sizeof(void*), hipMemcpyHostToDevice, st0);
-    if (e == hipSuccess) e = hipStreamSynchronize(st0);
-    if (e != hipSuccess) { int rc = gf_hip_fail(e, "gf_sampler_create"); gf_sampler_destroy(s); return rc; }
+    if (e == hipSuccess) e = hipMalloc((void**)&s->d_commons, sizeof(GfCommon) * nm);
+    if (e == hipSuccess) e = hipMalloc((void**)&s->d_tbs, sizeof(void*) * nm);
+    if (e == hipSuccess) e = hipMalloc((void**)&s->d_ptabs, sizeof(void*) * nm);
+    if (e == hipSuccess) e = hipMemcpyAsync(s->d_commons, hc.get(), sizeof(GfCommon) * nm, hipMemcpyHostToDevice, st0);
+    if (e == hipSuccess) e = hipMemcpyAsync((void*)s->d_tbs, htb.get(), sizeof(void*) * nm, hipMemcpyHostToDevice, st0);
+    if (e == hipSuccess) e = hipMemcpyAsync((void*)s->d_ptabs, hpt.get(), sizeof(void*) * nm, hipMemcpyHostToDevice, st0);
+    if (e == hipSuccess) e = hipStreamSynchronize(st0);               // the host tables are freed on return
+    if (e != hipSuccess) {
+        const int rc = gf_hip_fail(e, multi ? "gf_sampler_create_multi" : "gf_sampler_create");
+        gf_sampler_destroy(s);
+        return rc;
+    }
     *out = s;
     return GF_OK;
 }
 
-void gf_sampler_destroy(gf_sampler* s)
+// the model chain ch is post-processed with: models[ch] if the caller gives models, else the posterior the chain samples
+gf_model* chain_model(const gf_sampler* s, gf_model* const* models, int ch)
 {
-    if (!s) return;
-    const GfCommon* c; const GfBsm* tb; const double* ptab; void* stream; int device;
-    if (gf_model_internal(s->model, &c, &tb, &ptab, &stream, &device) == GF_OK) {
-        (void)hipSetDevice(device);
-        (void)hipStreamSynchronize((hipStream_t)stream);
-    }
-    if (s->d_pos) (void)hipFree(s->d_pos);
-    if (s->d_lnp) (void)hipFree(s->d_lnp);
-    if (s->d_naccept) (void)hipFree(s->d_naccept);
-    if (s->d_flags) (void)hipFree(s->d_flags);
-    if (s->d_pq) (void)hipFree(s->d_pq);
-    if (s->d_pend_rows) (void)hipFree(s->d_pend_rows);
-    if (s->d_pend_ctl) (void)hipFree(s->d_pend_ctl);
-    if (s->d_lazy_rows) (void)hipFree(s->d_lazy_rows);
-    if (s->d_lazy_mask) (void)hipFree(s->d_lazy_mask);
-    if (s->d_chain_stats) (void)hipFree(s->d_chain_stats);
-    if (s->d_pv) (void)hipFree(s->d_pv);
-    if (s->d_lv) (void)hipFree(s->d_lv);
-    if (s->d_frows) (void)hipFree(s->d_frows);
-    if (s->d_fterms) (void)hipFree(s->d_fterms);
-    if (s->d_state) (void)hipFree(s->d_state);
-    if (s->graph) (void)hipGraphExecDestroy(s->graph);
-    for (int i = 0; i < gf_sampler::FLIGHT; ++i) if (s->flight_ev[i]) (void)hipEventDestroy(s->flight_ev[i]);
-    if (s->d_chain) (void)hipFree(s->d_chain);
-    if (s->d_lnp_chain) (void)hipFree(s->d_lnp_chain);
-    if (s->d_commons) (void)hipFree(s->d_commons);
-    if (s->d_stream_ids) (void)hipFree(s->d_stream_ids);
-    if (s->d_tbs) (void)hipFree((void*)s->d_tbs);
-    if (s->d_ptabs) (void)hipFree((void*)s->d_ptabs);
-    delete[] s->models;
-    delete s;
+    return models ? models[ch] : s->models ? s->models[ch] : s->model;
 }
 
-// One ensemble per model: chain ch samples the posterior of models[ch].  All models must live on the same
-// device and share ndim and mode (one kernel instance); everything else -- priors, fixed values, best fit,
-// smearing, texture, dimension, binning -- may differ.  The models must outlive the sampler.
-int gf_sampler_create_multi(gf_model* const* models, int nchains, int nwalkers, uint64_t seed, double a, gf_sampler** out)
+// the post-processing entry points: every chain's model must have the sampler's ndim and device.  *cus (may be NULL): the CUs
+// the last chain's model sizes its grids for
+int check_chain_models(const gf_sampler* s, gf_model* const* models, int* cus = nullptr)
 {
-    if (!models || !out || nchains < 1 || nchains > 65535) return GF_ERR_INVALID_ARG;   // blockIdx.y = chain
-    *out = nullptr;
-    for (int ch = 0; ch < nchains; ++ch)
-        if (!models[ch]) return GF_ERR_INVALID_ARG;
-    const GfCommon* c0; const GfBsm* tb0; const double* ptab0; void* stream0; int device0;
-    if (gf_model_internal(models[0], &c0, &tb0, &ptab0, &stream0, &device0) != GF_OK) return GF_ERR_INVALID_ARG;
-    int nbins_max = 0;
-    GfCommon* hc = new (std::nothrow) GfCommon[nchains];
-    const GfBsm** htb = new (std::nothrow) const GfBsm*[nchains];
-    const double** hpt = new (std::nothrow) const double*[nchains];
-    gf_model** keep = new (std::nothrow) gf_model*[nchains];
-    auto cleanup = [&]() { delete[] hc; delete[] htb; delete[] hpt; };
-    if (!hc || !htb || !hpt || !keep) { cleanup(); delete[] keep; return GF_ERR_ALLOC; }
-    for (int ch = 0; ch < nchains; ++ch) {
-        const GfCommon* c; int device, cus, nbins;
-        if (gf_model_constants(models[ch], &c, &htb[ch], &hpt[ch], &device, &cus, &nbins) != GF_OK || device != device0 ||
-            c->ndim != c0->ndim || c->mode != c0->mode) {
-            cleanup(); delete[] keep;
-            return gf_fail_msg(GF_ERR_INVALID_ARG, "gf_sampler_create_multi: model %d differs from model 0 in device, ndim or mode", ch);
-        }
-        hc[ch] = *c;
-        keep[ch] = models[ch];
-        if (nbins > nbins_max) nbins_max = nbins;
+    for (int ch = 0; ch < s->nchains; ++ch) {
+        const GfCommon* c; const GfBsm* tb; const double* ptab; int device, mcus, nbins;
+        if (gf_model_constants(chain_model(s, models, ch), &c, &tb, &ptab, &device, &mcus, &nbins) != GF_OK || c->ndim != s->ndim ||
+            device != s->device)
+            return GF_ERR_INVALID_ARG;
+        if (cus) *cus = mcus;
     }
-    gf_sampler* s = nullptr;
-    int rc = gf_sampler_create(models[0], nchains, nwalkers, seed, a, &s);
-    if (rc != GF_OK) { cleanup(); delete[] keep; return rc; }
-    s->models = keep;
-    s->nbins_max = nbins_max;
-    (void)hipFree(s->d_commons); s->d_commons = nullptr;            // the one-entry tables of gf_sampler_create
-    (void)hipFree((void*)s->d_ptabs); s->d_ptabs = nullptr;
-    hipError_t e = hipMalloc((void**)&s->d_commons, sizeof(GfCommon) * nchains);
-    if (e == hipSuccess) e = hipMalloc((void**)&s->d_tbs, sizeof(void*) * nchains);
-    if (e == hipSuccess) e = hipMalloc((void**)&s->d_ptabs, sizeof(void*) * nchains);
-    hipStream_t st0 = (hipStream_t)stream0;
-    if (e == hipSuccess) e = hipMemcpyAsync(s->d_commons, hc, sizeof(GfCommon) * nchains, hipMemcpyHostToDevice, st0);
-    if (e == hipSuccess) e = hipMemcpyAsync((void*)s->d_tbs, htb, sizeof(void*) * nchains, hipMemcpyHostToDevice, st0);
-    if (e == hipSuccess) e = hipMemcpyAsync((void*)s->d_ptabs, hpt, sizeof(void*) * nchains, hipMemcpyHostToDevice, st0);
-    if (e == hipSuccess) e = hipStreamSynchronize(st0);               // the host arrays are freed next
-    cleanup();
-    if (e != hipSuccess) { rc = gf_hip_fail(e, "gf_sampler_create_multi"); gf_sampler_destroy(s); return rc; }
-    *out = s;
     return GF_OK;
 }
 
-// Random stream of every chain (default: the chain's index in this sampler).  ids [nchains]; call before the first run.
-int gf_sampler_set_stream_ids(gf_sampler* s, const uint64_t* ids)
-{
-    if (!s || !ids) return GF_ERR_INVALID_ARG;
-    const GfCommon* c; const GfBsm* tb; const double* ptab; void* stream; int device;
-    if (gf_model_internal(s->model, &c, &tb, &ptab, &stream, &device) != GF_OK) return GF_ERR_INVALID_ARG;
-    GF_HIP(hipSetDevice(device));
-    hipStream_t st = (hipStream_t)stream;
-    GF_HIP(hipStreamSynchronize(st));
-    if (!s->d_stream_ids) GF_HIP(hipMalloc((void**)&s->d_stream_ids, sizeof(uint64_t) * (size_t)s->nchains));
-    GF_HIP(hipMemcpyAsync(s->d_stream_ids, ids, sizeof(uint64_t) * (size_t)s->nchains, hipMemcpyHostToDevice, st));
-    GF_HIP(hipStreamSynchronize(st));
-    if (s->graph) { (void)hipGraphExecDestroy(s->graph); s->graph = nullptr; }     // its kernel arguments froze the old pointer
-    return GF_OK;
-}
-
-// p0: [nchains][nwalkers][ndim] host; evaluates lnprob of the start positions on the device.
-int gf_sampler_set_state(gf_sampler* s, const double* pos)
-{
-    if (!s || !pos) return GF_ERR_INVALID_ARG;
-    const GfCommon* c; const GfBsm* tb; const double* ptab; void* stream; int device;
-    gf_model_internal(s->model, &c, &tb, &ptab, &stream, &device);
-    GF_HIP(hipSetDevice(device));
-    const size_t nw = (size_t)s->nchains * s->nwalkers;
-    GF_HIP(hipMemcpyAsync(s->d_pos, pos, sizeof(double) * nw * s->ndim, hipMemcpyHostToDevice, (hipStream_t)stream));
-    // BSM posteriors: with the unitarity status, so that a start position the reference would have raised on is treated as such
-    int32_t* d_st = nullptr;
-    if (c->mode == MODE_BSM_GAUSS) GF_HIP(hipMalloc((void**)&d_st, sizeof(int32_t) * nw));
-    int rc = GF_OK;
-    if (!s->models) {
-        rc = gf_model_lnprob_on(s->model, stream, s->d_pos, GF_LAYOUT_AOS, (int64_t)nw, s->d_lnp, nullptr, d_st);
-    } else {
-        for (int ch = 0; ch < s->nchains && rc == GF_OK; ++ch)         // every chain's own posterior, on the sampler's stream
-            rc = gf_model_lnprob_on(s->models[ch], stream, s->d_pos + (size_t)ch * s->nwalkers * s->ndim, GF_LAYOUT_AOS,
-                                    s->nwalkers, s->d_lnp + (size_t)ch * s->nwalkers, nullptr, d_st ? d_st + (size_t)ch * s->nwalkers : nullptr);
-    }
-    hipError_t e = hipSuccess;
-    if (rc == GF_OK && d_st) {
-        hipLaunchKernelGGL(k_fix_start, dim3((unsigned)((nw + 255) / 256 < 1024 ? (nw + 255) / 256 : 1024)), dim3(256), 0, (hipStream_t)stream,
-                           d_st, (int64_t)nw, s->d_lnp, s->d_flags);
-        e = hipGetLastError();
-    }
-    const hipError_t e2 = hipStreamSynchronize((hipStream_t)stream);
-    if (d_st) (void)hipFree(d_st);
-    if (rc != GF_OK) return rc;
-    if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) return gf_hip_fail(e, "gf_sampler_set_state");
-    return gf_internal_check_overflow(device, stream);
-}
-
-int gf_sampler_reset(gf_sampler* s)
-{
-    if (!s) return GF_ERR_INVALID_ARG;
-    const GfCommon* c; const GfBsm* tb; const double* ptab; void* stream; int device;
-    gf_model_internal(s->model, &c, &tb, &ptab, &stream, &device);
-    GF_HIP(hipSetDevice(device));
-    GF_HIP(hipStreamSynchronize((hipStream_t)stream));
-    GF_HIP(hipMemsetAsync(s->d_naccept, 0, sizeof(uint32_t) * (size_t)s->nchains * s->nwalkers, (hipStream_t)stream));
-    GF_HIP(hipMemsetAsync(s->d_flags, 0, sizeof(uint32_t) * 4, (hipStream_t)stream));
-    if (s->d_chain_stats) GF_HIP(hipMemsetAsync(s->d_chain_stats, 0, sizeof(unsigned long long) * 8 * (size_t)s->nchains, (hipStream_t)stream));
-    GF_HIP(hipStreamSynchronize((hipStream_t)stream));
-    s->nstored = 0;
-    s->steps_since_reset = 0;
-    return GF_OK;
-}
-
-namespace {
 // the stored steps [sink->copied, upto) of every chain -> host: their chunks are ISSUED into the sink's pipe (pinned ring, copy stream); the
 // host threads empty them into the destination while the caller goes on
 int sink_copy(gf_sampler* s, int64_t upto)
@@ -1600,59 +1139,67 @@ hipError_t flight_mark(gf_sampler* s, hipStream_t st, int64_t nstored)
     ++s->flight_enq;
     return hipSuccess;
 }
-}  // namespace
 
-// Advance every ensemble by nsteps stretch-move steps (2 launches each), asynchronously on the model's
-// stream.  store != 0 appends every `thin`-th step to the device chain (capacity grows as needed).
-int gf_sampler_run(gf_sampler* s, int64_t nsteps, int thin, int store)
+// ---- gf_sampler_run: a prologue, one of three launch shapes, an epilogue -------------------------------------------------------
+// One run: what it was asked for and the steps enqueued so far.  A shape enqueues the steps [done, nsteps); the per-chain shape
+// may leave the rest of the run to the grid shape after its probe.
+struct Run {
+    gf_sampler* s;
+    int64_t nsteps;
+    int thin, store;
+    int64_t done;
+};
+
+// One block of `count` steps from r.done on, enqueued by launch(): admitted into the ring of blocks in flight, then marked with
+// the stored steps of every chain that are final once it has run.  `what` names a failed launch.
+template <class Launch>
+int run_block(Run& r, int64_t count, const char* what, Launch launch)
 {
-    if (!s || nsteps < 0 || thin < 1) return GF_ERR_INVALID_ARG;
-    const GfCommon* c; const GfBsm* tb; const double* ptab; void* stream; int device;
-    gf_model_internal(s->model, &c, &tb, &ptab, &stream, &device);
-    GF_HIP(hipSetDevice(device));
-    hipStream_t st = (hipStream_t)stream;
-    const size_t nw = (size_t)s->nchains * s->nwalkers;
-    if (store) {
-        const int64_t need = s->nstored + (nsteps + thin - 1) / thin;
-        if (need > s->nstore_cap) {
-            // grow: chains are [chain][slot][walker][dim]; a new capacity changes the chain stride, so repack
-            int64_t cap = s->nstore_cap ? s->nstore_cap : 64;
-            while (cap < need) cap *= 2;
-            double *nc = nullptr, *nl = nullptr;
-            GF_HIP(hipStreamSynchronize(st));
-            const auto t_grow = std::chrono::steady_clock::now();
-            struct Grow { std::chrono::steady_clock::time_point t0; ~Grow() { g_last_run_prologue[0] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); } } grow_{t_grow};
-            GF_HIP(hipMalloc((void**)&nc, sizeof(double) * nw * s->ndim * cap));
-            {
-                hipError_t e_ = hipMalloc((void**)&nl, sizeof(double) * nw * cap);
-                if (e_ != hipSuccess) { (void)hipFree(nc); return gf_hip_fail(e_, "hipMalloc(lnprob chain)"); }
-            }
-            if (s->nstored > 0) {
-                // every chain's stored prefix in one strided copy: row = chain, pitch = old / new chain stride
-                const size_t row = sizeof(double) * s->nwalkers * s->ndim, lrow = sizeof(double) * s->nwalkers;
-                hipError_t e_ = hipMemcpy2DAsync(nc, row * cap, s->d_chain, row * s->nstore_cap, row * s->nstored, s->nchains,
-                                                 hipMemcpyDeviceToDevice, st);
-                if (e_ == hipSuccess)
-                    e_ = hipMemcpy2DAsync(nl, lrow * cap, s->d_lnp_chain, lrow * s->nstore_cap, lrow * s->nstored, s->nchains,
-                                          hipMemcpyDeviceToDevice, st);
-                if (e_ == hipSuccess) e_ = hipStreamSynchronize(st);                  // the old buffers are freed next
-                if (e_ != hipSuccess) { (void)hipFree(nc); (void)hipFree(nl); return gf_hip_fail(e_, "chain repack"); }
-            }
-            if (s->d_chain) (void)hipFree(s->d_chain);
-            if (s->d_lnp_chain) (void)hipFree(s->d_lnp_chain);
-            s->d_chain = nc; s->d_lnp_chain = nl; s->nstore_cap = cap;
-            // the captured graph froze the old buffers and their capacity stride in its kernel arguments
-            if (s->graph) { (void)hipGraphExecDestroy(s->graph); s->graph = nullptr; }
-        }
-    }
-    // device-side step counters for this run
-    StepState& hs = s->h_state;                   // member: outlives the asynchronous upload
-    hs.iteration_base = s->iteration; hs.run_step_base = 0; hs.store_base = s->nstored;
-    hs.store = store ? 1 : 0; hs.thin = thin;
-    GF_HIP(hipStreamSynchronize(st));          // earlier runs must be done with the counters
-    s->flight_enq = s->flight_done = 0;         // (so nothing of an earlier run is in flight either)
-    GF_HIP(hipMemcpyAsync(s->d_state, &hs, sizeof(hs), hipMemcpyHostToDevice, st));
+    gf_sampler* s = r.s;
+    hipError_t e = flight_admit(s);
+    if (e != hipSuccess) return gf_hip_fail(e, "block in flight");
+    e = launch();
+    if (e != hipSuccess) return gf_hip_fail(e, what);
+    r.done += count;
+    e = flight_mark(s, s->stream, r.store ? s->nstored + (r.done + r.thin - 1) / r.thin : s->nstored);
+    if (e != hipSuccess) return gf_hip_fail(e, "hipEventRecord");
+    return GF_OK;
+}
+
+// The per-half-step grid kernels of a run: k_stretch (k_stretch_multi: one model per chain) over all chains, and for BSM
+// posteriors k_stretch_settle behind every half-step.
+struct GridSteps {
+    gf_sampler* s;
     StretchArgs a;
+    GfSettleArgs sa;
+    // `count` steps relative to the device-side base counters, then k_tick
+    hipError_t enqueue(int count)
+    {
+        for (int i = 0; i < count; ++i) {
+            a.step_offset = i;
+            for (int half = 0; half < 2; ++half) {
+                a.half = half;
+                hipError_t e = launch_stretch(*s->c, s->tb, s->ptab, a, s->stream);
+                if (e != hipSuccess) return e;
+                if (s->c->mode == MODE_BSM_GAUSS) {
+                    // the proposals whose unitarity the half-step could not settle: exact verdict, then their accept step
+                    sa.half = half; sa.step_offset = i;
+                    e = gf_launch_stretch_settle(sa, s->cus, s->stream);
+                    if (e != hipSuccess) return e;
+                }
+            }
+        }
+        hipLaunchKernelGGL(k_tick, dim3(1), dim3(1), 0, s->stream, s->d_state, count);
+        return hipGetLastError();
+    }
+};
+
+GridSteps grid_steps(gf_sampler* s, int store, int lpw)
+{
+    GridSteps g;
+    g.s = s;
+    StretchArgs& a = g.a;
+    a = {};
     a.state = s->d_state;
     a.pos = s->d_pos; a.lnp = s->d_lnp; a.naccept = s->d_naccept; a.flags = s->d_flags;
     a.pq = s->d_pq; a.pend_rows = s->d_pend_rows;
@@ -1662,239 +1209,395 @@ int gf_sampler_run(gf_sampler* s, int64_t nsteps, int thin, int store)
     a.commons = s->models ? s->d_commons : nullptr; a.tbs = s->d_tbs; a.ptabs = s->d_ptabs;
     a.nbins_max = s->nbins_max;
     a.stream_ids = s->d_stream_ids;
-    a.lpw = lanes_per_walker(c->mode, (int64_t)s->nchains * (s->nwalkers / 2), s->nbins_max, s->cus);
-    GfSettleArgs sa = {};
+    a.lpw = lpw;
+    GfSettleArgs& sa = g.sa;
+    sa = {};
     sa.state = s->d_state; sa.pq = s->d_pq; sa.pend_rows = s->d_pend_rows; sa.ctl = s->d_pend_ctl; sa.pos = s->d_pos; sa.lnp = s->d_lnp; sa.naccept = s->d_naccept;
     sa.flags = s->d_flags; sa.chain = a.chain; sa.lnp_chain = a.lnp_chain; sa.nstore_cap = s->nstore_cap; sa.nchains = s->nchains;
-    sa.nwalkers = s->nwalkers; sa.half = 0; sa.step_offset = 0; sa.ndim = s->ndim; sa.commons = s->d_commons; sa.tbs = s->d_tbs; sa.tb = tb;
+    sa.nwalkers = s->nwalkers; sa.half = 0; sa.step_offset = 0; sa.ndim = s->ndim; sa.commons = s->d_commons; sa.tbs = s->d_tbs; sa.tb = s->tb;
     sa.multi = s->models ? 1 : 0;
-    auto steps = [&](int count) -> hipError_t {       // `count` steps relative to the current base, then tick
-        for (int i = 0; i < count; ++i) {
-            a.step_offset = i;
-            for (int half = 0; half < 2; ++half) {
-                a.half = half;
-                hipError_t e = launch_stretch(*c, tb, ptab, a, st);
-                if (e != hipSuccess) return e;
-                if (c->mode == MODE_BSM_GAUSS) {
-                    // the proposals whose unitarity the half-step could not settle: exact verdict, then their accept step
-                    sa.half = half; sa.step_offset = i;
-                    e = gf_launch_stretch_settle(sa, s->cus, st);
-                    if (e != hipSuccess) return e;
-                }
-            }
-        }
-        hipLaunchKernelGGL(k_tick, dim3(1), dim3(1), 0, st, s->d_state, count);
-        return hipGetLastError();
-    };
-    // small ensembles of a PRIOR_ONLY / SM_GAUSS posterior: one workgroup per ensemble, the whole run in one launch
+    return g;
+}
+
+// room for `need` stored steps of every chain: chains are [chain][slot][walker][dim], so a new capacity changes the chain stride
+// and the stored prefix is repacked
+int grow_chain(gf_sampler* s, int64_t need)
+{
+    const size_t nw = (size_t)s->nchains * s->nwalkers;
+    hipStream_t st = s->stream;
+    int64_t cap = s->nstore_cap ? s->nstore_cap : 64;
+    while (cap < need) cap *= 2;
+    double *nc = nullptr, *nl = nullptr;
+    GF_HIP(hipStreamSynchronize(st));
+    const auto t_grow = std::chrono::steady_clock::now();
+    struct Grow { std::chrono::steady_clock::time_point t0; ~Grow() { g_last_run_prologue[0] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); } } grow_{t_grow};
+    GF_HIP(hipMalloc((void**)&nc, sizeof(double) * nw * s->ndim * cap));
     {
-        int threads = 0;
-        size_t lds = 0;
-        int workers = 0;
-        persist_geometry(s->nwalkers, s->ndim, &threads, &lds, &workers, s->nchains, s->cus);
-        const char* env = gf_internal_env("GF_SAMPLER_PERSIST", 0);          // "0": always the per-half-step grid kernels
-        if (c->mode != MODE_BSM_GAUSS && lds > 0 && !(env && env[0] == '0')) {
-            PersistArgs pa;
-            pa.commons = s->d_commons; pa.ptabs = s->d_ptabs; pa.nmodels = s->models ? s->nchains : 1;
-            pa.nwalkers = s->nwalkers; pa.pos = s->d_pos; pa.lnp = s->d_lnp; pa.naccept = s->d_naccept;
-            pa.chain = store ? s->d_chain : nullptr; pa.lnp_chain = store ? s->d_lnp_chain : nullptr;
-            pa.nstore_cap = s->nstore_cap; pa.seed = s->seed; pa.thin = thin; pa.store = store ? 1 : 0; pa.a = s->a;
-            pa.stream_ids = s->d_stream_ids;
-            pa.workers = workers;
-            constexpr int64_t CHUNK = 1 << 16;                          // steps per launch: bounds a kernel's run time
-            int64_t done_p = 0;
-            while (done_p < nsteps) {
-                // every launch but the last covers a whole multiple of `thin` steps, so that the kernel's
-                // (step % thin) == 0 test, which counts from the launch's first step, stays aligned with the run
-                int64_t count = nsteps - done_p < CHUNK ? nsteps - done_p : CHUNK;
-                if (count < nsteps - done_p) {
-                    const int64_t whole = (count / thin) * thin;
-                    count = whole > 0 ? whole : thin;
-                    if (count > nsteps - done_p) count = nsteps - done_p;      // thin longer than what is left
-                }
-                pa.iteration_base = s->iteration + (uint64_t)done_p;
-                pa.store_base = s->nstored + (done_p + thin - 1) / thin;
-                pa.nsteps = count;
-                hipError_t e = launch_persist(c->mode, s->ndim, s->nchains, threads, lds, pa, st);
-                if (e != hipSuccess) return gf_hip_fail(e, "persistent stretch launch");
-                done_p += count;
-            }
-            s->iteration += (uint64_t)nsteps;
-            s->steps_since_reset += nsteps;
-            if (store) s->nstored += (nsteps + thin - 1) / thin;
-            return GF_OK;
-        }
+        hipError_t e_ = hipMalloc((void**)&nl, sizeof(double) * nw * cap);
+        if (e_ != hipSuccess) { (void)hipFree(nc); return gf_hip_fail(e_, "hipMalloc(lnprob chain)"); }
     }
-    // BSM posteriors on ensembles of up to 1024 walkers have two launch shapes with the same chain, bit for bit:
-    //   per chain   one workgroup owns a chain for a block of 16 steps and settles its own parked proposals (k_stretch_chain): a chain that
-    //               parks nothing never waits for one that does -- 21 us per half-step where nothing is parked (C5: 256 x 512 walkers);
-    //   grid        one launch per half-step for all chains + k_stretch_settle on the whole GPU (round 3): every chain waits for the
-    //               slowest parked proposal, but a chain that parks TEN proposals per half-step (the top-scale grid points of C5) gets
-    //               3 584 teams for them instead of its workgroup's 56 -- 115 us per half-step against 150.
-    // Which is faster depends on where the chains live NOW (a burn-in that starts below the failing region and drifts into it parks
-    // nothing at first), so every run of 128 steps or more times one block of each shape on its own chains at its start (the second
-    // block of two, the first warms the kernel up; the blocks are the run's own steps, nothing is computed twice) and takes the faster
-    // for the rest of the run; shorter runs take the last decision (none yet: per chain).  GF_SAMPLER_CHAIN=1 / 0 forces a shape.
-    int64_t done = 0;
-    const bool small_bsm = c->mode == MODE_BSM_GAUSS && s->nwalkers / 2 <= 512;
-    constexpr int64_t CHAIN_STEPS = 16;                                  // steps per launch: the granule of the overlapped read-back
+    if (s->nstored > 0) {
+        // every chain's stored prefix in one strided copy: row = chain, pitch = old / new chain stride
+        const size_t row = sizeof(double) * s->nwalkers * s->ndim, lrow = sizeof(double) * s->nwalkers;
+        hipError_t e_ = hipMemcpy2DAsync(nc, row * cap, s->d_chain, row * s->nstore_cap, row * s->nstored, s->nchains,
+                                         hipMemcpyDeviceToDevice, st);
+        if (e_ == hipSuccess)
+            e_ = hipMemcpy2DAsync(nl, lrow * cap, s->d_lnp_chain, lrow * s->nstore_cap, lrow * s->nstored, s->nchains,
+                                  hipMemcpyDeviceToDevice, st);
+        if (e_ == hipSuccess) e_ = hipStreamSynchronize(st);                  // the old buffers are freed next
+        if (e_ != hipSuccess) { (void)hipFree(nc); (void)hipFree(nl); return gf_hip_fail(e_, "chain repack"); }
+    }
+    if (s->d_chain) (void)hipFree(s->d_chain);
+    if (s->d_lnp_chain) (void)hipFree(s->d_lnp_chain);
+    s->d_chain = nc; s->d_lnp_chain = nl; s->nstore_cap = cap;
+    // the captured graph froze the old buffers and their capacity stride in its kernel arguments
+    if (s->graph) { (void)hipGraphExecDestroy(s->graph); s->graph = nullptr; }
+    return GF_OK;
+}
+
+// Small ensembles of a PRIOR_ONLY / SM_GAUSS posterior: one workgroup per ensemble (k_stretch_persist), the whole run in one
+// launch per CHUNK steps.
+int run_persistent(Run& r, int threads, size_t lds, int workers)
+{
+    gf_sampler* s = r.s;
+    PersistArgs pa = {};
+    pa.commons = s->d_commons; pa.ptabs = s->d_ptabs; pa.nmodels = s->models ? s->nchains : 1;
+    pa.nwalkers = s->nwalkers; pa.pos = s->d_pos; pa.lnp = s->d_lnp; pa.naccept = s->d_naccept;
+    pa.chain = r.store ? s->d_chain : nullptr; pa.lnp_chain = r.store ? s->d_lnp_chain : nullptr;
+    pa.nstore_cap = s->nstore_cap; pa.seed = s->seed; pa.thin = r.thin; pa.store = r.store; pa.a = s->a;
+    pa.stream_ids = s->d_stream_ids;
+    pa.workers = workers;
+    constexpr int64_t CHUNK = 1 << 16;                          // steps per launch: bounds a kernel's run time
+    while (r.done < r.nsteps) {
+        // every launch but the last covers a whole multiple of `thin` steps, so that the kernel's
+        // (step % thin) == 0 test, which counts from the launch's first step, stays aligned with the run
+        const int64_t left = r.nsteps - r.done;
+        int64_t count = left < CHUNK ? left : CHUNK;
+        if (count < left) {
+            const int64_t whole = (count / r.thin) * r.thin;
+            count = whole > 0 ? whole : r.thin;
+            if (count > left) count = left;                     // thin longer than what is left
+        }
+        pa.iteration_base = s->iteration + (uint64_t)r.done;
+        pa.store_base = s->nstored + (r.done + r.thin - 1) / r.thin;
+        pa.nsteps = count;
+        hipError_t e = launch_persist(s->c->mode, s->ndim, s->nchains, threads, lds, pa, s->stream);
+        if (e != hipSuccess) return gf_hip_fail(e, "persistent stretch launch");
+        r.done += count;
+    }
+    return GF_OK;
+}
+
+// `count` steps of the grid kernels, one block in flight
+int grid_block(Run& r, GridSteps& g, int count)
+{
+    return run_block(r, count, "stretch launch", [&] { return g.enqueue(count); });
+}
+
+// k_stretch_chain's lists of the proposals whose verdict only the count waits for -- at least two passes' worth per chain, ~64 MB
+// in all -- and its per-chain census (left out if it cannot be allocated), at the sampler's first per-chain run
+int alloc_lazy_lists(gf_sampler* s)
+{
+    if (s->d_lazy_rows) return GF_OK;
+    const int pass = s->nwalkers < CH_BLOCK ? s->nwalkers : CH_BLOCK;
+    int64_t cap = ((int64_t)64 << 20) / ((int64_t)s->nchains * (int64_t)(sizeof(double) * GF_PEND_STRIDE + 8));
+    if (cap > 1024) cap = 1024;
+    if (cap < 2 * pass) cap = 2 * pass;
+    GF_HIP(hipMalloc((void**)&s->d_lazy_rows, sizeof(double) * GF_PEND_STRIDE * (size_t)cap * s->nchains));
+    {
+        hipError_t e_ = hipMalloc((void**)&s->d_lazy_mask, sizeof(unsigned long long) * (size_t)cap * s->nchains);
+        if (e_ != hipSuccess) { (void)hipFree(s->d_lazy_rows); s->d_lazy_rows = nullptr; return gf_hip_fail(e_, "hipMalloc(lazy list)"); }
+    }
+    s->lazy_cap = (int)cap;
+    if (hipMalloc((void**)&s->d_chain_stats, sizeof(unsigned long long) * 8 * (size_t)s->nchains) == hipSuccess)
+        (void)hipMemsetAsync(s->d_chain_stats, 0, sizeof(unsigned long long) * 8 * (size_t)s->nchains, s->stream);
+    else { s->d_chain_stats = nullptr; (void)hipGetLastError(); }
+    return GF_OK;
+}
+
+// BSM posteriors on ensembles of up to 1024 walkers have two launch shapes with the same chain, bit for bit:
+//   per chain   one workgroup owns a chain for a block of 16 steps and settles its own parked proposals (k_stretch_chain): a chain that
+//               parks nothing never waits for one that does -- 21 us per half-step where nothing is parked (C5: 256 x 512 walkers);
+//   grid        one launch per half-step for all chains + k_stretch_settle on the whole GPU (round 3): every chain waits for the
+//               slowest parked proposal, but a chain that parks TEN proposals per half-step (the top-scale grid points of C5) gets
+//               3 584 teams for them instead of its workgroup's 56 -- 115 us per half-step against 150.
+// Which is faster depends on where the chains live NOW (a burn-in that starts below the failing region and drifts into it parks
+// nothing at first), so every run of 128 steps or more times one block of each shape on its own chains at its start (the second
+// block of two, the first warms the kernel up; the blocks are the run's own steps, nothing is computed twice) and takes the faster
+// for the rest of the run; shorter runs take the last decision (none yet: per chain).  GF_SAMPLER_CHAIN=1 / 0 forces a shape.
+// *grid on return: the rest of the run is the grid shape's.
+constexpr int64_t CHAIN_STEPS = 16;                                      // steps per launch: the granule of the overlapped read-back
+int run_per_chain(Run& r, GridSteps& g, bool* grid)
+{
+    gf_sampler* s = r.s;
+    hipStream_t st = s->stream;
+    const char* env = gf_internal_env("GF_SAMPLER_CHAIN", 0);       // "0": grid kernels; "1": per chain (k_stretch_chain)
+    const bool forced = env && (env[0] == '0' || env[0] == '1');
+    const bool probe = !forced && r.nsteps >= 8 * CHAIN_STEPS;
+    *grid = forced ? env[0] == '0' : !probe && s->shape == 2;
+    if (*grid) return GF_OK;
+    int rc = alloc_lazy_lists(s);
+    if (rc != GF_OK) return rc;
     ChainArgs ca = {};
-    bool flow = false;                                                   // per chain as a dataflow (k_stretch_flow) or half-step by half-step (k_stretch_chain)
-    auto chain_block = [&](int64_t count) -> int {                       // `count` steps from `done` on, one launch
-        hipError_t e = flight_admit(s);
-        if (e != hipSuccess) return gf_hip_fail(e, "block in flight");
-        ca.iteration_base = s->iteration + (uint64_t)done;
-        ca.run_step_base = done;
-        ca.nsteps = (int32_t)count;
-        e = launch_chain(s->ndim, s->nchains, ca, st, flow);
-        if (e != hipSuccess) return gf_hip_fail(e, "chain launch");
-        done += count;
-        e = flight_mark(s, st, store ? s->nstored + (done + thin - 1) / thin : s->nstored);
-        if (e != hipSuccess) return gf_hip_fail(e, "hipEventRecord");
-        return GF_OK;
+    ca.lazy_rows = s->d_lazy_rows; ca.lazy_mask = s->d_lazy_mask; ca.lazy_cap = s->lazy_cap;
+    ca.stats = s->d_chain_stats;
+    ca.commons = s->d_commons; ca.tbs = s->models ? s->d_tbs : nullptr; ca.tb = s->tb; ca.ptabs = s->d_ptabs;
+    ca.nmodels = s->models ? s->nchains : 1; ca.nwalkers = s->nwalkers;
+    ca.pos = s->d_pos; ca.lnp = s->d_lnp; ca.naccept = s->d_naccept; ca.flags = s->d_flags; ca.pend_rows = s->d_pend_rows;
+    ca.chain = r.store ? s->d_chain : nullptr; ca.lnp_chain = r.store ? s->d_lnp_chain : nullptr;
+    ca.nstore_cap = s->nstore_cap; ca.store_base = s->nstored; ca.seed = s->seed; ca.thin = r.thin; ca.store = r.store;
+    ca.a = s->a; ca.stream_ids = s->d_stream_ids;
+    auto chain_block = [&](int64_t count) {                              // `count` steps from r.done on, one launch
+        return run_block(r, count, "chain launch", [&] {
+            ca.iteration_base = s->iteration + (uint64_t)r.done;
+            ca.run_step_base = r.done;
+            ca.nsteps = (int32_t)count;
+            return launch_chain(s->ndim, s->nchains, ca, st);
+        });
     };
-    auto grid_block = [&](int count) -> int {                            // the same with the grid kernels, launched one by one
-        hipError_t e = flight_admit(s);
-        if (e != hipSuccess) return gf_hip_fail(e, "block in flight");
-        e = steps(count);
-        if (e != hipSuccess) return gf_hip_fail(e, "stretch launch");
-        done += count;
-        e = flight_mark(s, st, store ? hs.store_base + (done + thin - 1) / thin : hs.store_base);
-        if (e != hipSuccess) return gf_hip_fail(e, "hipEventRecord");
-        return GF_OK;
-    };
-    if (small_bsm) {
-        const char* env = gf_internal_env("GF_SAMPLER_CHAIN", 0);       // "0": grid kernels; "1": per chain (k_stretch_chain)
-        const bool forced = env && (env[0] == '0' || env[0] == '1' || env[0] == '3');
-        int shape = forced ? (env[0] == '0' ? 2 : 1) : (nsteps >= 8 * CHAIN_STEPS ? 0 : s->shape);
-#ifdef GF_EXPERIMENTAL_FLOW
-        flow = s->nwalkers <= CH_BLOCK && env && env[0] == '3';               // the dataflow kernel has one thread per walker
-#endif
-        if (shape != 2) {
-            if (!s->d_lazy_rows) {
-                // room for the proposals whose verdict only the count waits for: at least two passes' worth per chain, ~64 MB in all
-                const int pass = s->nwalkers < CH_BLOCK ? s->nwalkers : CH_BLOCK;          // (k_stretch_flow: up to nwalkers per round)
-                int64_t cap = ((int64_t)64 << 20) / ((int64_t)s->nchains * (int64_t)(sizeof(double) * GF_PEND_STRIDE + 8));
-                if (cap > 1024) cap = 1024;
-                if (cap < 2 * pass) cap = 2 * pass;
-                GF_HIP(hipMalloc((void**)&s->d_lazy_rows, sizeof(double) * GF_PEND_STRIDE * (size_t)cap * s->nchains));
-                {
-                    hipError_t e_ = hipMalloc((void**)&s->d_lazy_mask, sizeof(unsigned long long) * (size_t)cap * s->nchains);
-                    if (e_ != hipSuccess) { (void)hipFree(s->d_lazy_rows); s->d_lazy_rows = nullptr; return gf_hip_fail(e_, "hipMalloc(lazy list)"); }
+    if (probe) {
+        // two blocks per chain, two blocks on the grid, the second of each timed; k_tick after a per-chain block brings the grid
+        // kernels' device-side counters along
+        double us[2] = {0.0, 0.0};
+        for (int which = 0; which < 2; ++which)
+            for (int rep = 0; rep < 2; ++rep) {
+                GF_HIP(hipStreamSynchronize(st));
+                const auto t0 = std::chrono::steady_clock::now();
+                if (which == 0) {
+                    rc = chain_block(CHAIN_STEPS);
+                    if (rc == GF_OK) { hipLaunchKernelGGL(k_tick, dim3(1), dim3(1), 0, st, s->d_state, (int)CHAIN_STEPS); if (hipGetLastError() != hipSuccess) rc = GF_ERR_HIP; }
+                } else {
+                    rc = grid_block(r, g, (int)CHAIN_STEPS);
                 }
-                s->lazy_cap = (int)cap;
-                if (hipMalloc((void**)&s->d_chain_stats, sizeof(unsigned long long) * 8 * (size_t)s->nchains) == hipSuccess)
-                    (void)hipMemsetAsync(s->d_chain_stats, 0, sizeof(unsigned long long) * 8 * (size_t)s->nchains, st);
-                else { s->d_chain_stats = nullptr; (void)hipGetLastError(); }
-            }
-            ca.lazy_rows = s->d_lazy_rows; ca.lazy_mask = s->d_lazy_mask; ca.lazy_cap = s->lazy_cap;
-            ca.stats = s->d_chain_stats;
-            ca.commons = s->d_commons; ca.tbs = s->models ? s->d_tbs : nullptr; ca.tb = tb; ca.ptabs = s->d_ptabs;
-            ca.nmodels = s->models ? s->nchains : 1; ca.nwalkers = s->nwalkers;
-            ca.pos = s->d_pos; ca.lnp = s->d_lnp; ca.naccept = s->d_naccept; ca.flags = s->d_flags; ca.pend_rows = s->d_pend_rows;
-            ca.chain = store ? s->d_chain : nullptr; ca.lnp_chain = store ? s->d_lnp_chain : nullptr;
-            ca.nstore_cap = s->nstore_cap; ca.store_base = s->nstored; ca.seed = s->seed; ca.thin = thin; ca.store = store ? 1 : 0;
-            ca.a = s->a; ca.stream_ids = s->d_stream_ids;
-#ifdef GF_EXPERIMENTAL_FLOW
-            if (flow && !s->d_pv) {
-                const size_t nwk = (size_t)s->nchains * s->nwalkers;
-                hipError_t e_ = hipMalloc((void**)&s->d_pv, sizeof(double) * FLOW_VERS * nwk * s->ndim);
-                if (e_ == hipSuccess) e_ = hipMalloc((void**)&s->d_lv, sizeof(double) * FLOW_VERS * nwk);
-                if (e_ == hipSuccess) e_ = hipMalloc((void**)&s->d_frows, sizeof(double) * GF_PEND_STRIDE * nwk);
-                if (e_ == hipSuccess) e_ = hipMalloc((void**)&s->d_fterms, sizeof(double) * Team9::LANES * 8 * nwk);
-                if (e_ != hipSuccess) return gf_hip_fail(e_, "hipMalloc(dataflow sampler)");
-            }
-            ca.pv = s->d_pv; ca.lv = s->d_lv; ca.frows = s->d_frows; ca.fterms = s->d_fterms;
-#endif
-        }
-        if (shape == 0 && !forced && nsteps >= 8 * CHAIN_STEPS) {
-            // the probe: two blocks per chain, two blocks on the grid, the second of each timed
-            double us[2] = {0.0, 0.0};
-            for (int which = 0; which < 2; ++which)
-                for (int rep = 0; rep < 2; ++rep) {
-                    GF_HIP(hipStreamSynchronize(st));
-                    const auto t0 = std::chrono::steady_clock::now();
-                    int rc = GF_OK;
-                    if (which == 0) {
-                        rc = chain_block(CHAIN_STEPS);
-                        if (rc == GF_OK) { hipLaunchKernelGGL(k_tick, dim3(1), dim3(1), 0, st, s->d_state, (int)CHAIN_STEPS); if (hipGetLastError() != hipSuccess) rc = GF_ERR_HIP; }
-                    } else {
-                        rc = grid_block((int)CHAIN_STEPS);
-                    }
-                    if (rc != GF_OK) return rc;
-                    GF_HIP(hipStreamSynchronize(st));
-                    if (rep == 1) us[which] = 1e6 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-                }
-            s->probe_us[0] = us[0]; s->probe_us[1] = us[1];
-            shape = s->shape = us[0] <= us[1] ? 1 : 2;
-        }
-        if (shape != 2) {                                                  // per chain (also: not decided, and the run too short to probe)
-            while (done < nsteps) {
-                const int rc = chain_block(nsteps - done < CHAIN_STEPS ? nsteps - done : CHAIN_STEPS);
                 if (rc != GF_OK) return rc;
+                GF_HIP(hipStreamSynchronize(st));
+                if (rep == 1) us[which] = 1e6 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
             }
-            s->iteration += (uint64_t)nsteps;
-            s->steps_since_reset += nsteps;
-            if (store) s->nstored += (nsteps + thin - 1) / thin;
-            return GF_OK;
-        }
+        s->probe_us[0] = us[0]; s->probe_us[1] = us[1];
+        s->shape = us[0] <= us[1] ? 1 : 2;
+        *grid = s->shape == 2;
+        if (*grid) return GF_OK;
     }
-    constexpr int GRAPH_STEPS = 16;
+    while (r.done < r.nsteps) {
+        rc = chain_block(r.nsteps - r.done < CHAIN_STEPS ? r.nsteps - r.done : CHAIN_STEPS);
+        if (rc != GF_OK) return rc;
+    }
+    return GF_OK;
+}
+
+// s->graph: GRAPH_STEPS steps of `g` captured (2 nodes per step + one tick), recaptured when the chain buffers, their capacity or
+// the store flag it froze in its kernel arguments have changed; null where capture fails (the run launches eagerly then)
+constexpr int GRAPH_STEPS = 16;
+void capture_graph(gf_sampler* s, GridSteps& g, int store)
+{
+    if (s->graph && s->graph_chain == g.a.chain && s->graph_lnp_chain == g.a.lnp_chain && s->graph_cap == g.a.nstore_cap &&
+        s->graph_has_chain == store)
+        return;
+    if (s->graph) { (void)hipGraphExecDestroy(s->graph); s->graph = nullptr; }
+    hipGraph_t gr = nullptr;
+    const auto t_cap = std::chrono::steady_clock::now();
+    struct Cap { std::chrono::steady_clock::time_point t0; ~Cap() { g_last_run_prologue[1] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); } } cap_{t_cap};
+    hipError_t e = hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal);
+    if (e == hipSuccess) {
+        e = g.enqueue(GRAPH_STEPS);
+        hipError_t e2 = hipStreamEndCapture(s->stream, &gr);
+        if (e == hipSuccess) e = e2;
+    }
+    if (e == hipSuccess) e = hipGraphInstantiate(&s->graph, gr, nullptr, nullptr, 0);
+    if (gr) (void)hipGraphDestroy(gr);
+    if (e != hipSuccess) {                      // graphs unavailable: eager launches
+        (void)hipGetLastError();
+        s->graph = nullptr;
+    } else {
+        s->graph_chain = g.a.chain;
+        s->graph_lnp_chain = g.a.lnp_chain;
+        s->graph_cap = g.a.nstore_cap;
+        s->graph_has_chain = store;
+    }
+}
+
+// Every other run, and what the per-chain shape leaves: graph replays of GRAPH_STEPS steps (the launch-bound inner loop), then
+// eager blocks of up to 64 steps.
+int run_grid(Run& r, GridSteps& g)
+{
+    gf_sampler* s = r.s;
     const bool no_graph = gf_internal_env("GF_SAMPLER_NO_GRAPH", 0) != nullptr;          // diagnostics, read per run
-    if (!no_graph && nsteps >= 2 * GRAPH_STEPS) {
-        // launch-bound inner loop -> hipGraph: capture GRAPH_STEPS steps once, replay
-        if (!s->graph || s->graph_chain != a.chain || s->graph_lnp_chain != a.lnp_chain || s->graph_cap != a.nstore_cap ||
-            s->graph_has_chain != (store ? 1 : 0)) {
-            if (s->graph) { (void)hipGraphExecDestroy(s->graph); s->graph = nullptr; }
-            hipGraph_t g = nullptr;
-            const auto t_cap = std::chrono::steady_clock::now();
-            struct Cap { std::chrono::steady_clock::time_point t0; ~Cap() { g_last_run_prologue[1] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); } } cap_{t_cap};
-            hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
-            if (e == hipSuccess) {
-                e = steps(GRAPH_STEPS);
-                hipError_t e2 = hipStreamEndCapture(st, &g);
-                if (e == hipSuccess) e = e2;
-            }
-            if (e == hipSuccess) e = hipGraphInstantiate(&s->graph, g, nullptr, nullptr, 0);
-            if (g) (void)hipGraphDestroy(g);
-            if (e != hipSuccess) {                      // graphs unavailable: fall through to eager launches
-                (void)hipGetLastError();
-                s->graph = nullptr;
-            } else {
-                s->graph_chain = a.chain;
-                s->graph_lnp_chain = a.lnp_chain;
-                s->graph_cap = a.nstore_cap;
-                s->graph_has_chain = store ? 1 : 0;
-            }
-        }
-        while (s->graph && nsteps - done >= GRAPH_STEPS) {
-            hipError_t e = flight_admit(s);
-            if (e != hipSuccess) return gf_hip_fail(e, "block in flight");
-            const auto t_g = std::chrono::steady_clock::now();
-            e = hipGraphLaunch(s->graph, st);
-            if (s->sink) {
-                const double d = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_g).count();
-                s->sink->t[5] += d; if (d > s->sink->t[6]) s->sink->t[6] = d;
-            }
-            if (e != hipSuccess) return gf_hip_fail(e, "hipGraphLaunch");
-            done += GRAPH_STEPS;
-            e = flight_mark(s, st, store ? hs.store_base + (done + thin - 1) / thin : hs.store_base);
-            if (e != hipSuccess) return gf_hip_fail(e, "hipEventRecord");
+    if (!no_graph && r.nsteps >= 2 * GRAPH_STEPS) {
+        capture_graph(s, g, r.store);
+        while (s->graph && r.nsteps - r.done >= GRAPH_STEPS) {
+            const int rc = run_block(r, GRAPH_STEPS, "hipGraphLaunch", [&] {
+                const auto t_g = std::chrono::steady_clock::now();
+                const hipError_t e = hipGraphLaunch(s->graph, s->stream);
+                if (s->sink) {
+                    const double d = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_g).count();
+                    s->sink->t[5] += d; if (d > s->sink->t[6]) s->sink->t[6] = d;
+                }
+                return e;
+            });
+            if (rc != GF_OK) return rc;
         }
     }
-    while (done < nsteps) {
-        const int count = (int)((nsteps - done < 64) ? (nsteps - done) : 64);
-        hipError_t e = flight_admit(s);
-        if (e != hipSuccess) return gf_hip_fail(e, "block in flight");
-        e = steps(count);
-        if (e != hipSuccess) return gf_hip_fail(e, "stretch launch");
-        done += count;
-        e = flight_mark(s, st, store ? hs.store_base + (done + thin - 1) / thin : hs.store_base);
-        if (e != hipSuccess) return gf_hip_fail(e, "hipEventRecord");
+    while (r.done < r.nsteps) {
+        const int rc = grid_block(r, g, (int)(r.nsteps - r.done < 64 ? r.nsteps - r.done : 64));
+        if (rc != GF_OK) return rc;
     }
+    return GF_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int gf_sampler_create(gf_model* m, int nchains, int nwalkers, uint64_t seed, double a, gf_sampler** out)
+{
+    if (!m) return GF_ERR_INVALID_ARG;
+    return sampler_create(&m, false, nchains, nwalkers, seed, a, out);
+}
+
+// One ensemble per model: chain ch samples the posterior of models[ch].  All models must live on the same
+// device and share ndim and mode (one kernel instance); everything else -- priors, fixed values, best fit,
+// smearing, texture, dimension, binning -- may differ.  The models must outlive the sampler.
+int gf_sampler_create_multi(gf_model* const* models, int nchains, int nwalkers, uint64_t seed, double a, gf_sampler** out)
+{
+    if (!models || !out || nchains < 1 || nchains > 65535) return GF_ERR_INVALID_ARG;   // blockIdx.y = chain
+    *out = nullptr;
+    for (int ch = 0; ch < nchains; ++ch)
+        if (!models[ch]) return GF_ERR_INVALID_ARG;
+    return sampler_create(models, true, nchains, nwalkers, seed, a, out);
+}
+
+void gf_sampler_destroy(gf_sampler* s)
+{
+    if (!s) return;
+    if (s->stream) {
+        (void)hipSetDevice(s->device);
+        (void)hipStreamSynchronize(s->stream);
+    }
+    if (s->d_pos) (void)hipFree(s->d_pos);
+    if (s->d_lnp) (void)hipFree(s->d_lnp);
+    if (s->d_naccept) (void)hipFree(s->d_naccept);
+    if (s->d_flags) (void)hipFree(s->d_flags);
+    if (s->d_pq) (void)hipFree(s->d_pq);
+    if (s->d_pend_rows) (void)hipFree(s->d_pend_rows);
+    if (s->d_pend_ctl) (void)hipFree(s->d_pend_ctl);
+    if (s->d_lazy_rows) (void)hipFree(s->d_lazy_rows);
+    if (s->d_lazy_mask) (void)hipFree(s->d_lazy_mask);
+    if (s->d_chain_stats) (void)hipFree(s->d_chain_stats);
+    if (s->d_state) (void)hipFree(s->d_state);
+    if (s->graph) (void)hipGraphExecDestroy(s->graph);
+    for (int i = 0; i < gf_sampler::FLIGHT; ++i) if (s->flight_ev[i]) (void)hipEventDestroy(s->flight_ev[i]);
+    if (s->d_chain) (void)hipFree(s->d_chain);
+    if (s->d_lnp_chain) (void)hipFree(s->d_lnp_chain);
+    if (s->d_commons) (void)hipFree(s->d_commons);
+    if (s->d_stream_ids) (void)hipFree(s->d_stream_ids);
+    if (s->d_tbs) (void)hipFree((void*)s->d_tbs);
+    if (s->d_ptabs) (void)hipFree((void*)s->d_ptabs);
+    delete[] s->models;
+    delete s;
+}
+
+// Random stream of every chain (default: the chain's index in this sampler).  ids [nchains]; call before the first run.
+int gf_sampler_set_stream_ids(gf_sampler* s, const uint64_t* ids)
+{
+    if (!s || !ids) return GF_ERR_INVALID_ARG;
+    GF_HIP(hipSetDevice(s->device));
+    hipStream_t st = s->stream;
+    GF_HIP(hipStreamSynchronize(st));
+    if (!s->d_stream_ids) GF_HIP(hipMalloc((void**)&s->d_stream_ids, sizeof(uint64_t) * (size_t)s->nchains));
+    GF_HIP(hipMemcpyAsync(s->d_stream_ids, ids, sizeof(uint64_t) * (size_t)s->nchains, hipMemcpyHostToDevice, st));
+    GF_HIP(hipStreamSynchronize(st));
+    if (s->graph) { (void)hipGraphExecDestroy(s->graph); s->graph = nullptr; }     // its kernel arguments froze the old pointer
+    return GF_OK;
+}
+
+// p0: [nchains][nwalkers][ndim] host; evaluates lnprob of the start positions on the device.
+int gf_sampler_set_state(gf_sampler* s, const double* pos)
+{
+    if (!s || !pos) return GF_ERR_INVALID_ARG;
+    GF_HIP(hipSetDevice(s->device));
+    hipStream_t st = s->stream;
+    const size_t nw = (size_t)s->nchains * s->nwalkers;
+    GF_HIP(hipMemcpyAsync(s->d_pos, pos, sizeof(double) * nw * s->ndim, hipMemcpyHostToDevice, st));
+    // BSM posteriors: with the unitarity status, so that a start position the reference would have raised on is treated as such
+    int32_t* d_st = nullptr;
+    if (s->c->mode == MODE_BSM_GAUSS) GF_HIP(hipMalloc((void**)&d_st, sizeof(int32_t) * nw));
+    int rc = GF_OK;
+    if (!s->models) {
+        rc = gf_model_lnprob_on(s->model, st, s->d_pos, GF_LAYOUT_AOS, (int64_t)nw, s->d_lnp, nullptr, d_st);
+    } else {
+        for (int ch = 0; ch < s->nchains && rc == GF_OK; ++ch)         // every chain's own posterior, on the sampler's stream
+            rc = gf_model_lnprob_on(s->models[ch], st, s->d_pos + (size_t)ch * s->nwalkers * s->ndim, GF_LAYOUT_AOS,
+                                    s->nwalkers, s->d_lnp + (size_t)ch * s->nwalkers, nullptr, d_st ? d_st + (size_t)ch * s->nwalkers : nullptr);
+    }
+    hipError_t e = hipSuccess;
+    if (rc == GF_OK && d_st) {
+        hipLaunchKernelGGL(k_fix_start, dim3((unsigned)((nw + 255) / 256 < 1024 ? (nw + 255) / 256 : 1024)), dim3(256), 0, st,
+                           d_st, (int64_t)nw, s->d_lnp, s->d_flags);
+        e = hipGetLastError();
+    }
+    const hipError_t e2 = hipStreamSynchronize(st);
+    if (d_st) (void)hipFree(d_st);
+    if (rc != GF_OK) return rc;
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) return gf_hip_fail(e, "gf_sampler_set_state");
+    return gf_internal_check_overflow(s->device, st);
+}
+
+int gf_sampler_reset(gf_sampler* s)
+{
+    if (!s) return GF_ERR_INVALID_ARG;
+    GF_HIP(hipSetDevice(s->device));
+    hipStream_t st = s->stream;
+    GF_HIP(hipStreamSynchronize(st));
+    GF_HIP(hipMemsetAsync(s->d_naccept, 0, sizeof(uint32_t) * (size_t)s->nchains * s->nwalkers, st));
+    GF_HIP(hipMemsetAsync(s->d_flags, 0, sizeof(uint32_t) * 4, st));
+    if (s->d_chain_stats) GF_HIP(hipMemsetAsync(s->d_chain_stats, 0, sizeof(unsigned long long) * 8 * (size_t)s->nchains, st));
+    GF_HIP(hipStreamSynchronize(st));
+    s->nstored = 0;
+    s->steps_since_reset = 0;
+    return GF_OK;
+}
+
+// Advance every ensemble by nsteps stretch-move steps (2 launches each), asynchronously on the model's
+// stream.  store != 0 appends every `thin`-th step to the device chain (capacity grows as needed).
+int gf_sampler_run(gf_sampler* s, int64_t nsteps, int thin, int store)
+{
+    if (!s || nsteps < 0 || thin < 1) return GF_ERR_INVALID_ARG;
+    GF_HIP(hipSetDevice(s->device));
+    hipStream_t st = s->stream;
+    const int64_t nstore = store ? (nsteps + thin - 1) / thin : 0;     // steps this run stores
+    if (s->nstored + nstore > s->nstore_cap) {
+        const int rc = grow_chain(s, s->nstored + nstore);
+        if (rc != GF_OK) return rc;
+    }
+    // device-side step counters for this run
+    StepState& hs = s->h_state;                   // member: outlives the asynchronous upload
+    hs.iteration_base = s->iteration; hs.run_step_base = 0; hs.store_base = s->nstored;
+    hs.store = store ? 1 : 0; hs.thin = thin;
+    GF_HIP(hipStreamSynchronize(st));          // earlier runs must be done with the counters
+    s->flight_enq = s->flight_done = 0;         // (so nothing of an earlier run is in flight either)
+    GF_HIP(hipMemcpyAsync(s->d_state, &hs, sizeof(hs), hipMemcpyHostToDevice, st));
+
+    // the launch shape; the overrides are read in this order, once per run
+    Run r = {s, nsteps, thin, store ? 1 : 0, 0};
+    GridSteps g = grid_steps(s, r.store, lanes_per_walker(s->c->mode, (int64_t)s->nchains * (s->nwalkers / 2), s->nbins_max, s->cus));
+    int threads = 0, workers = 0;
+    size_t lds = 0;
+    persist_geometry(s->nwalkers, s->ndim, &threads, &lds, &workers, s->nchains, s->cus);
+    const char* env = gf_internal_env("GF_SAMPLER_PERSIST", 0);          // "0": always the per-half-step grid kernels
+    const bool bsm = s->c->mode == MODE_BSM_GAUSS;
+    int rc = GF_OK;
+    if (!bsm && lds > 0 && !(env && env[0] == '0')) {
+        rc = run_persistent(r, threads, lds, workers);
+    } else {
+        bool grid = true;
+        if (bsm && s->nwalkers / 2 <= 512) rc = run_per_chain(r, g, &grid);
+        if (rc == GF_OK && grid) rc = run_grid(r, g);
+    }
+    if (rc != GF_OK) return rc;
+
     s->iteration += (uint64_t)nsteps;
     s->steps_since_reset += nsteps;
-    if (store) s->nstored += (nsteps + thin - 1) / thin;
+    s->nstored += nstore;
     return GF_OK;
 }
 
@@ -1914,9 +1617,8 @@ int gf_sampler_sync(gf_sampler* s)
 int gf_sampler_run_to_host(gf_sampler* s, int64_t nsteps, int thin, double* chain, double* lnprob_chain, double* readback_tail_s)
 {
     if (!s || !chain || nsteps < 0 || thin < 1) return GF_ERR_INVALID_ARG;
-    const GfCommon* c; const GfBsm* tb; const double* ptab; void* stream; int device;
-    if (gf_model_internal(s->model, &c, &tb, &ptab, &stream, &device) != GF_OK) return GF_ERR_INVALID_ARG;
-    GF_HIP(hipSetDevice(device));
+    GF_HIP(hipSetDevice(s->device));
+    const int device = s->device;
     void* copy_stream = nullptr;
     int rc = gf_internal_borrow_copy_stream(device, &copy_stream);
     if (rc != GF_OK) return rc;
@@ -1937,7 +1639,7 @@ int gf_sampler_run_to_host(gf_sampler* s, int64_t nsteps, int thin, double* chai
     hipError_t e = hipSuccess;
     while (rc == GF_OK && e == hipSuccess && s->flight_done < s->flight_enq) e = flight_consume(s, true);   // the blocks still in flight
     s->sink = nullptr;
-    const hipError_t e2 = hipStreamSynchronize((hipStream_t)stream);
+    const hipError_t e2 = hipStreamSynchronize(s->stream);
     auto t_done = marks && s->flight_enq > 0 ? sink.last_event : std::chrono::steady_clock::now();        // when the run itself was complete on the GPU
     if (rc == GF_OK && e == hipSuccess && e2 == hipSuccess && sink.rc == GF_OK) {
         s->sink = &sink;                                            // whatever no block's event covered (one-launch runs; no marks)
@@ -1963,10 +1665,9 @@ int gf_internal_sampler_chain_stats(gf_sampler* s, unsigned long long* out)
 {
     if (!s || !out) return GF_ERR_INVALID_ARG;
     if (!s->d_chain_stats) return GF_ERR_UNSUPPORTED;
-    const GfCommon* c; const GfBsm* tb; const double* ptab; void* stream; int device;
-    if (gf_model_internal(s->model, &c, &tb, &ptab, &stream, &device) != GF_OK) return GF_ERR_INVALID_ARG;
-    GF_HIP(hipMemcpyAsync(out, s->d_chain_stats, sizeof(unsigned long long) * 8 * (size_t)s->nchains, hipMemcpyDeviceToHost, (hipStream_t)stream));
-    GF_HIP(hipStreamSynchronize((hipStream_t)stream));
+    GF_HIP(hipSetDevice(s->device));
+    GF_HIP(hipMemcpyAsync(out, s->d_chain_stats, sizeof(unsigned long long) * 8 * (size_t)s->nchains, hipMemcpyDeviceToHost, s->stream));
+    GF_HIP(hipStreamSynchronize(s->stream));
     return GF_OK;
 }
 
@@ -2002,10 +1703,9 @@ int gf_sampler_get_state(gf_sampler* s, double* pos, double* lnprob)
     if (!s) return GF_ERR_INVALID_ARG;
     int rc = gf_model_sync(s->model);
     if (rc != GF_OK) return rc;
+    GF_HIP(hipSetDevice(s->device));
     const size_t nw = (size_t)s->nchains * s->nwalkers;
-    const GfCommon* c; const GfBsm* tb; const double* ptab; void* stream; int device;
-    if (gf_model_internal(s->model, &c, &tb, &ptab, &stream, &device) != GF_OK) return GF_ERR_INVALID_ARG;
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = s->stream;
     if (pos) GF_HIP(hipMemcpyAsync(pos, s->d_pos, sizeof(double) * nw * s->ndim, hipMemcpyDeviceToHost, st));
     if (lnprob) GF_HIP(hipMemcpyAsync(lnprob, s->d_lnp, sizeof(double) * nw, hipMemcpyDeviceToHost, st));
     GF_HIP(hipStreamSynchronize(st));
@@ -2017,21 +1717,20 @@ int gf_sampler_get_state(gf_sampler* s, double* pos, double* lnprob)
 int gf_sampler_get_chain(gf_sampler* s, double* chain, double* lnprob_chain, uint32_t* naccepted, uint32_t* nonunitary)
 {
     if (!s) return GF_ERR_INVALID_ARG;
-    const GfCommon* c; const GfBsm* tb; const double* ptab; void* stream; int device;
-    if (gf_model_internal(s->model, &c, &tb, &ptab, &stream, &device) != GF_OK) return GF_ERR_INVALID_ARG;
-    hipStream_t st = (hipStream_t)stream;                 // in order behind the sampler's launches
+    GF_HIP(hipSetDevice(s->device));
+    hipStream_t st = s->stream;                           // in order behind the sampler's launches
     const size_t per = (size_t)s->nwalkers;
     if (s->nstored > 0) {
         // one strided copy per array: row = chain (stored prefix), device pitch = capacity stride
         const size_t row = sizeof(double) * per * s->ndim, lrow = sizeof(double) * per;
         // (gf_internal_d2h_2d: a plain strided copy below 16 MB, the pinned ring + host copy pool from there on)
         if (chain) {
-            const int rc = gf_internal_d2h_2d(device, stream, chain, row * s->nstored, s->d_chain, row * s->nstore_cap, row * s->nstored,
+            const int rc = gf_internal_d2h_2d(s->device, st, chain, row * s->nstored, s->d_chain, row * s->nstore_cap, row * s->nstored,
                                               (size_t)s->nchains);
             if (rc != GF_OK) return rc;
         }
         if (lnprob_chain) {
-            const int rc = gf_internal_d2h_2d(device, stream, lnprob_chain, lrow * s->nstored, s->d_lnp_chain, lrow * s->nstore_cap,
+            const int rc = gf_internal_d2h_2d(s->device, st, lnprob_chain, lrow * s->nstored, s->d_lnp_chain, lrow * s->nstore_cap,
                                               lrow * s->nstored, (size_t)s->nchains);
             if (rc != GF_OK) return rc;
         }
@@ -2049,10 +1748,8 @@ int gf_sampler_get_chain(gf_sampler* s, double* chain, double* lnprob_chain, uin
 int gf_sampler_get_chain_device(gf_sampler* s, double* d_chain, double* d_lnprob_chain)
 {
     if (!s) return GF_ERR_INVALID_ARG;
-    const GfCommon* c; const GfBsm* tb; const double* ptab; void* stream; int device;
-    if (gf_model_internal(s->model, &c, &tb, &ptab, &stream, &device) != GF_OK) return GF_ERR_INVALID_ARG;
-    GF_HIP(hipSetDevice(device));
-    hipStream_t st = (hipStream_t)stream;
+    GF_HIP(hipSetDevice(s->device));
+    hipStream_t st = s->stream;
     if (s->nstored > 0) {
         const size_t row = sizeof(double) * (size_t)s->nwalkers * s->ndim, lrow = sizeof(double) * (size_t)s->nwalkers;
         if (d_chain)
@@ -2071,10 +1768,8 @@ int gf_sampler_get_chain_device(gf_sampler* s, double* d_chain, double* d_lnprob
 int gf_sampler_walker_mean(gf_sampler* s, double* mean)
 {
     if (!s || !mean) return GF_ERR_INVALID_ARG;
-    const GfCommon* c; const GfBsm* tb; const double* ptab; void* stream; int device;
-    if (gf_model_internal(s->model, &c, &tb, &ptab, &stream, &device) != GF_OK) return GF_ERR_INVALID_ARG;
-    GF_HIP(hipSetDevice(device));
-    hipStream_t st = (hipStream_t)stream;
+    GF_HIP(hipSetDevice(s->device));
+    hipStream_t st = s->stream;
     if (s->nstored == 0) { GF_HIP(hipStreamSynchronize(st)); return GF_OK; }
     const size_t bytes = sizeof(double) * (size_t)s->nchains * s->nstored * s->ndim;
     double* d_mean = nullptr;
@@ -2115,32 +1810,24 @@ int gf_sampler_postprocess(gf_sampler* s, double* fr, int32_t* status, int nbins
 int gf_sampler_postprocess_device(gf_sampler* s, gf_model* const* models, double* d_fr, int32_t* d_status)
 {
     if (!s || !d_fr) return GF_ERR_INVALID_ARG;
-    const GfCommon* c0; const GfBsm* tb; const double* ptab; void* stream; int device0;
-    if (gf_model_internal(s->model, &c0, &tb, &ptab, &stream, &device0) != GF_OK) return GF_ERR_INVALID_ARG;
-    for (int ch = 0; ch < s->nchains; ++ch) {
-        gf_model* mc = models ? models[ch] : s->models ? s->models[ch] : s->model;
-        const GfCommon* c; int device, cus, nbins;
-        if (gf_model_constants(mc, &c, &tb, &ptab, &device, &cus, &nbins) != GF_OK || c->ndim != s->ndim || device != device0)
-            return GF_ERR_INVALID_ARG;
-    }
-    GF_HIP(hipSetDevice(device0));
-    hipStream_t st = (hipStream_t)stream;
+    if (check_chain_models(s, models) != GF_OK) return GF_ERR_INVALID_ARG;
+    GF_HIP(hipSetDevice(s->device));
+    hipStream_t st = s->stream;
     const int64_t per_chain = s->nstored * s->nwalkers;
     int rc = GF_OK;
     // the chains are enqueued faster than they run, so the arbitration grid of each would follow what some EARLIER chain found,
     // and the chains of a scan differ (its high-scale grid points sit in the failing region, the others have empty queues):
     // full grids throughout, ~30 us per chain (measured: the hint left 57 of 64 chains of the C4 scan on a sixth of the
     // GPU, 114 ms of arbitration instead of ~20)
-    gf_internal_full_arbitration_grids(device0, stream, 1);
+    gf_internal_full_arbitration_grids(s->device, st, 1);
     for (int ch = 0; ch < s->nchains && rc == GF_OK && per_chain > 0; ++ch) {
-        gf_model* mc = models ? models[ch] : s->models ? s->models[ch] : s->model;
         const double* d_theta = s->d_chain + (size_t)ch * s->nstore_cap * s->nwalkers * s->ndim;
-        rc = gf_model_propagate_on(mc, stream, d_theta, GF_LAYOUT_AOS, per_chain, d_fr + (size_t)ch * per_chain * 3,
+        rc = gf_model_propagate_on(chain_model(s, models, ch), st, d_theta, GF_LAYOUT_AOS, per_chain, d_fr + (size_t)ch * per_chain * 3,
                                    d_status ? d_status + (size_t)ch * per_chain : nullptr);
     }
-    gf_internal_full_arbitration_grids(device0, stream, 0);
+    gf_internal_full_arbitration_grids(s->device, st, 0);
     GF_HIP(hipStreamSynchronize(st));
-    if (rc == GF_OK && d_status) rc = gf_internal_check_overflow(device0, stream);
+    if (rc == GF_OK && d_status) rc = gf_internal_check_overflow(s->device, st);
     return rc;
 }
 
@@ -2150,10 +1837,8 @@ int gf_sampler_postprocess_device(gf_sampler* s, gf_model* const* models, double
 int gf_sampler_postprocess_rows_device(gf_sampler* s, gf_model* const* models, double* d_rows)
 {
     if (!s || !d_rows) return GF_ERR_INVALID_ARG;
-    const GfCommon* c0; const GfBsm* tb; const double* ptab; void* stream; int device0;
-    if (gf_model_internal(s->model, &c0, &tb, &ptab, &stream, &device0) != GF_OK) return GF_ERR_INVALID_ARG;
-    GF_HIP(hipSetDevice(device0));
-    hipStream_t st = (hipStream_t)stream;
+    GF_HIP(hipSetDevice(s->device));
+    hipStream_t st = s->stream;
     const int64_t per_chain = s->nstored * s->nwalkers;
     if (per_chain == 0) { GF_HIP(hipStreamSynchronize(st)); return GF_OK; }
     double* d_fr = nullptr;
@@ -2186,16 +1871,10 @@ int gf_sampler_postprocess_rows_device(gf_sampler* s, gf_model* const* models, d
 int gf_sampler_postprocess_rows(gf_sampler* s, gf_model* const* models, double* rows)
 {
     if (!s || !rows) return GF_ERR_INVALID_ARG;
-    const GfCommon* c0; const GfBsm* tb; const double* ptab; void* stream; int device0;
-    if (gf_model_internal(s->model, &c0, &tb, &ptab, &stream, &device0) != GF_OK) return GF_ERR_INVALID_ARG;
-    for (int ch = 0; ch < s->nchains; ++ch) {
-        gf_model* mc = models ? models[ch] : s->models ? s->models[ch] : s->model;
-        const GfCommon* c; int device, cus, nbins;
-        if (gf_model_constants(mc, &c, &tb, &ptab, &device, &cus, &nbins) != GF_OK || c->ndim != s->ndim || device != device0)
-            return GF_ERR_INVALID_ARG;
-    }
-    GF_HIP(hipSetDevice(device0));
-    hipStream_t st = (hipStream_t)stream;
+    if (check_chain_models(s, models) != GF_OK) return GF_ERR_INVALID_ARG;
+    GF_HIP(hipSetDevice(s->device));
+    const int device0 = s->device;
+    hipStream_t st = s->stream;
     const int64_t per_chain = s->nstored * s->nwalkers;
     if (per_chain == 0) { GF_HIP(hipStreamSynchronize(st)); return GF_OK; }
     const size_t width = 3 + (size_t)s->ndim, chain_bytes = sizeof(double) * width * (size_t)per_chain;
@@ -2213,11 +1892,10 @@ int gf_sampler_postprocess_rows(gf_sampler* s, gf_model* const* models, double* 
     for (int g = 0; g < ngroups && e == hipSuccess; ++g) e = hipEventCreateWithFlags(&ev[g], hipEventDisableTiming);
     if (e == hipSuccess) rc = gf_internal_borrow_copy_stream(device0, &copy_stream);
     if (e == hipSuccess && rc == GF_OK) {
-        gf_internal_full_arbitration_grids(device0, stream, 1);      // see gf_sampler_postprocess_device
+        gf_internal_full_arbitration_grids(device0, st, 1);      // see gf_sampler_postprocess_device
         for (int ch = 0; ch < s->nchains && rc == GF_OK && e == hipSuccess; ++ch) {
-            gf_model* mc = models ? models[ch] : s->models ? s->models[ch] : s->model;
             const double* d_theta = s->d_chain + (size_t)ch * s->nstore_cap * s->nwalkers * s->ndim;
-            rc = gf_model_propagate_on(mc, stream, d_theta, GF_LAYOUT_AOS, per_chain, d_fr + (size_t)ch * per_chain * 3,
+            rc = gf_model_propagate_on(chain_model(s, models, ch), st, d_theta, GF_LAYOUT_AOS, per_chain, d_fr + (size_t)ch * per_chain * 3,
                                        d_st + (size_t)ch * per_chain);
             if (rc == GF_OK)
                 e = gf_launch_join_rows(d_fr + (size_t)ch * per_chain * 3, d_st + (size_t)ch * per_chain, d_theta, s->ndim, per_chain,
@@ -2225,7 +1903,7 @@ int gf_sampler_postprocess_rows(gf_sampler* s, gf_model* const* models, double* 
             if (rc == GF_OK && e == hipSuccess && ((ch + 1) % per_group == 0 || ch + 1 == s->nchains))
                 e = hipEventRecord(ev[ch / per_group], st);
         }
-        gf_internal_full_arbitration_grids(device0, stream, 0);
+        gf_internal_full_arbitration_grids(device0, st, 0);
         // the rows cross PCIe on the copy stream through the library's pinned ring (gf_internal_d2h_gated: the DMA fills a slot
         // while host threads empty the previous ones into `rows`, mapping its pages as they go) -- ONE pipeline over the whole
         // block, each 16 MB chunk issued as soon as the group of chains it ends in has been post-processed on the sampler's stream
@@ -2251,24 +1929,17 @@ int gf_sampler_postprocess_rows(gf_sampler* s, gf_model* const* models, double* 
     if (rc != GF_OK) return rc;
     if (e == hipSuccess) e = e2;
     if (e != hipSuccess) return gf_hip_fail(e, "gf_sampler_postprocess_rows");
-    return gf_internal_check_overflow(device0, stream);
+    return gf_internal_check_overflow(device0, st);
 }
 
 int gf_sampler_postprocess_with(gf_sampler* s, gf_model* const* models, double* fr, int32_t* status, int nbins,
                                 uint64_t* counts)
 {
     if (!s || (counts && (nbins < 1 || nbins > 1024))) return GF_ERR_INVALID_ARG;
-    const GfCommon* c0; const GfBsm* tb; const double* ptab; void* stream; int device0;
-    if (gf_model_internal(s->model, &c0, &tb, &ptab, &stream, &device0) != GF_OK) return GF_ERR_INVALID_ARG;
     int cus = 256;
-    for (int ch = 0; ch < s->nchains; ++ch) {
-        gf_model* mc = models ? models[ch] : s->models ? s->models[ch] : s->model;
-        const GfCommon* c; int device, nbins;
-        if (gf_model_constants(mc, &c, &tb, &ptab, &device, &cus, &nbins) != GF_OK || c->ndim != s->ndim || device != device0)
-            return GF_ERR_INVALID_ARG;
-    }
-    GF_HIP(hipSetDevice(device0));
-    hipStream_t st = (hipStream_t)stream;
+    if (check_chain_models(s, models, &cus) != GF_OK) return GF_ERR_INVALID_ARG;
+    GF_HIP(hipSetDevice(s->device));
+    hipStream_t st = s->stream;
     GF_HIP(hipStreamSynchronize(st));
     if (s->nstored == 0) return GF_OK;
     const int64_t per_chain = s->nstored * s->nwalkers;
@@ -2283,9 +1954,8 @@ int gf_sampler_postprocess_with(gf_sampler* s, gf_model* const* models, double* 
     // everything in order on the sampler's stream (the one the chain was written on): propagate, histogram,
     // copies back; the scratch buffers are reused chain after chain, one sync at the end
     for (int ch = 0; ch < s->nchains && e == hipSuccess && rc == GF_OK; ++ch) {
-        gf_model* mc = models ? models[ch] : s->models ? s->models[ch] : s->model;
         const double* d_theta = s->d_chain + (size_t)ch * s->nstore_cap * s->nwalkers * s->ndim;
-        rc = gf_model_propagate_on(mc, stream, d_theta, GF_LAYOUT_AOS, per_chain, d_fr, d_st);
+        rc = gf_model_propagate_on(chain_model(s, models, ch), st, d_theta, GF_LAYOUT_AOS, per_chain, d_fr, d_st);
         if (rc != GF_OK) break;
         if (counts) {
             e = hipMemsetAsync(d_c, 0, sizeof(uint64_t) * nbin3, st);
@@ -2305,7 +1975,7 @@ int gf_sampler_postprocess_with(gf_sampler* s, gf_model* const* models, double* 
     if (d_c) (void)hipFree(d_c);
     if (rc != GF_OK) return rc;
     if (e != hipSuccess) return gf_hip_fail(e, "gf_sampler_postprocess");
-    return status ? gf_internal_check_overflow(device0, stream) : GF_OK;
+    return status ? gf_internal_check_overflow(s->device, st) : GF_OK;
 }
 
 }  // extern "C"
