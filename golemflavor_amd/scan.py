@@ -14,6 +14,12 @@ RANK / WORLD_SIZE / LOCAL_RANK / MASTER_ADDR / MASTER_PORT works, torch.distribu
 
     python -m golemflavor_amd.scan --config C4 [--nwalkers 2048 --burnin 100 --nsteps 200]
     python -m torch.distributed.run --nproc-per-node 8 ... -m golemflavor_amd.scan --config C5
+
+Row order.  A grid point's result holds one row per stored sample, in the order the device stores them: row
+step * nwalkers + walker, so `rows.reshape(nsteps, nwalkers, -1)` recovers the chain (step, walker, column).  Every delivery
+path -- the gathers, --datadir, --no-stack -- writes this order.  emcee's `flatchain`, which the reference's jobs save
+(golemflavor/mcmc.py:44), is walker-major: the same set of samples in another order.  The reference's consumers load a chain
+as a set of samples (scripts/fr.py:209, golemflavor/plot.py:482), so either order serves them.
 """
 import argparse
 import json
@@ -344,7 +350,7 @@ def run_points(points, indices, make, burnin, nsteps, stacked=True, seed=25, gat
     out = {}
     for g, sm in samplers.items():
         sm.wait()
-        flat = sm.flatchain
+        flat = sm.flat_steps()                                    # the stacked paths' row order (module docstring)
         sm.close()
         out[g] = jobs[g].collect(flat)
     return out

@@ -262,7 +262,7 @@ def test_random_stacked_posteriors_follow_the_reference_stretch_move(oracle, see
     smearing and source, random walkers / steps) against the numpy restatement of the stretch move that evaluates
     every chain with the ORACLE on the same Philox stream."""
     from golemflavor_amd import mcmc as mcmc_utils
-    from test_gpu_sampler import _reference_stretch
+    from stretch_ref import reference_stretch as _reference_stretch
     rng = np.random.default_rng(11000 + seed)
     ps, mode = _random_paramset(rng)
     nd = len(ps)

@@ -9,50 +9,9 @@ from golemflavor_amd import fr as fr_utils
 from golemflavor_amd import llh as llh_utils
 from golemflavor_amd import mcmc as mcmc_utils
 from golemflavor_amd.enums import Texture
+from stretch_ref import reference_stretch as _reference_stretch
 
 pytestmark = pytest.mark.gpu
-
-
-def _reference_stretch(oracle, om, p0, nsteps, seed, a=2.0, lnprob=None):
-    """The published stretch move, written out in numpy with the sampler's random stream: one
-    Philox4x32-10 block per (walker slot, half-step), u1 53 bits, partner and u3 32 bits."""
-    nchains, nwalkers, ndim = p0.shape
-    nhalf = nwalkers // 2
-    pos = p0.copy()
-    oms = list(om) if isinstance(om, (list, tuple)) else [om] * nchains      # one posterior per chain, or one for all
-    lnprob = lnprob or oracle.lnprob_batch
-    lnp = np.stack([lnprob(oms[c], pos[c]) for c in range(nchains)])
-    chain = np.empty((nchains, nsteps, nwalkers, ndim))
-    nacc = np.zeros((nchains, nwalkers), dtype=int)
-    key = (seed & 0xffffffff, seed >> 32)
-    for it in range(nsteps):
-        for half in (0, 1):
-            t = 2 * it + half
-            cbase = (1 - half) * nhalf
-            newpos, newlnp = pos.copy(), lnp.copy()
-            for c in range(nchains):
-                q = np.empty((nhalf, ndim)); zz = np.empty(nhalf); u3 = np.empty(nhalf)
-                for k in range(nhalf):
-                    g = c * nhalf + k
-                    r = oracle.philox4x32_10((g & 0xffffffff, g >> 32, t & 0xffffffff, t >> 32), key)
-                    u1 = ((r[0] >> 5) * 67108864.0 + (r[1] >> 6)) / 9007199254740992.0
-                    j = (r[2] * nhalf) >> 32
-                    u3[k] = (r[3] + 0.5) / 4294967296.0
-                    zr = (a - 1.0) * u1 + 1.0
-                    zz[k] = zr * zr / a
-                    cj, sk = pos[c, cbase + j], pos[c, half * nhalf + k]
-                    q[k] = cj - zz[k] * (cj - sk)
-                lq = lnprob(oms[c], q)
-                lk = lnp[c, half * nhalf:(half + 1) * nhalf]
-                with np.errstate(all="ignore"):
-                    acc = np.log(zz ** (ndim - 1) / u3) > lk - lq
-                idx = np.arange(half * nhalf, (half + 1) * nhalf)[acc]
-                newpos[c, idx] = q[acc]
-                newlnp[c, idx] = lq[acc]
-                nacc[c, idx] += 1
-            pos, lnp = newpos, newlnp
-        chain[:, it] = pos
-    return chain, lnp, nacc
 
 
 def test_device_sampler_equals_reference_stretch_move(golden, oracle):
@@ -627,7 +586,7 @@ def test_bsm_sampler_unitarity_through_the_failing_region(oracle):
     device must take the same decision.  The number of non-unitary proposals agrees with the oracle's up to the band.  `raise`
     (the reference's behaviour): the run dies."""
     import x87_harness as H
-    from fractions import Fraction
+    from stretch_ref import Arbiter, accept_lhs, propose
     inj = fr_utils.fr_to_angles((1, 1, 1))
     asimov, ps = Cf.fr_paramsets(6, inj)
     src = (1 / 3, 2 / 3, 0.)
@@ -651,42 +610,21 @@ def test_bsm_sampler_unitarity_through_the_failing_region(oracle):
     lnp = np.where(st == oracle.NON_UNITARY, -np.inf, lp)                # a start the reference would have died on
     nbad, nband, nforced, naccept = int(np.sum(st == oracle.NON_UNITARY)), 0, 0, 0
     hx = H.build()
-    tables = H.model_tables(f.model)
-    nflip = 0                                                            # band proposals on which the harness overrules the oracle
+    arb = Arbiter(oracle, om, f.model, harness=hx)                       # band proposals: the harness decides (arb.nflip: overrules)
     key = (seed & 0xffffffff, seed >> 32)
     for it in range(nsteps):
         for half in (0, 1):
             t = 2 * it + half
-            cbase = (1 - half) * nhalf
-            q = np.empty((nhalf, ndim)); zz = np.empty(nhalf); u3 = np.empty(nhalf)
-            for k in range(nhalf):
-                r = oracle.philox4x32_10((k, 0, t & 0xffffffff, t >> 32), key)
-                u1 = ((r[0] >> 5) * 67108864.0 + (r[1] >> 6)) / 9007199254740992.0
-                j = (r[2] * nhalf) >> 32
-                u3[k] = (r[3] + 0.5) / 4294967296.0
-                zr = (a - 1.0) * u1 + 1.0
-                zz[k] = zr * zr / a
-                cj, sk = pos[cbase + j], pos[half * nhalf + k]
-                # q = fma(-z, c_j - s_k, c_j), rounded once, as the kernel forms it
-                q[k] = [float(Fraction(-zz[k]) * Fraction(float(cj[d] - sk[d])) + Fraction(float(cj[d]))) for d in range(ndim)]
+            q, zz, u3 = propose(oracle, key, pos, half, t, a=a)                # q = fma(-z, c_j - s_k, c_j), as the kernel forms it
             lq, sq = oracle.lnprob_batch(om, q, want_status=True)
-            res = oracle.unitarity_residual_batch(om, q)
-            band = (sq != oracle.OUT_OF_PRIOR) & (res > 10 ** -7.25) & (res < 10 ** -6.75)
-            bad = sq == oracle.NON_UNITARY
-            if band.any():
-                hbad = H.non_unitary(H.walker_residuals(hx, f.model.desc, tables, q[band]))
-                flip = np.flatnonzero(band)[hbad != bad[band]]
-                nflip += flip.size
-                acquit = flip[~hbad[hbad != bad[band]]]
-                if acquit.size:                                          # the oracle did not finish these: the model's value
-                    lq[acquit] = f.model.lnprob(q[acquit])[0]
-                bad[band] = hbad
+            bad, band, acquit = arb.verdict(q, sq)
+            if acquit.size:                                              # the oracle did not finish these: the model's value
+                lq[acquit] = f.model.lnprob(q[acquit])[0]
             lq = np.where(bad, -np.inf, lq)
             nbad += int(np.sum(sq == oracle.NON_UNITARY))
             nband += int(band.sum())
             idx = np.arange(half * nhalf, (half + 1) * nhalf)
-            with np.errstate(all="ignore"):
-                acc = np.log(zz ** (ndim - 1) / u3) > lnp[idx] - lq
+            acc = accept_lhs(zz, u3, ndim) > lnp[idx] - lq
             want = np.where(acc[:, None], q, pos[idx])
             dev = got[it][idx]
             differ = np.abs(dev - want).max(axis=1) > 1e-12
@@ -696,6 +634,7 @@ def test_bsm_sampler_unitarity_through_the_failing_region(oracle):
             lnp[idx] = np.where(differ, got_lnp[it][idx], np.where(acc, lq, lnp[idx]))
             naccept += int(acc.sum())
     assert nbad > 500 and naccept > 200                                  # the chain does live in the failing region, and moves
+    nflip = arb.nflip
     print("band proposals %d, harness verdict differs from the oracle's on %d" % (nband, nflip))
     assert nforced == 0 and nflip <= nband and abs(nbad_dev - nbad) <= nband, (nbad_dev, nbad, nband, nforced, nflip)
     assert np.allclose(smp.state[1], lnp, rtol=1e-10)
