@@ -30,6 +30,7 @@
 #include "gf_device.hpp"
 #include "gf_bsm_device.hpp"
 #include "gf_launch.h"
+#include "gf_region.h"
 #include "gf_unitarity_teams.hpp"      // Team9: the reference's unitarity chain on nine lanes (k_stretch_chain settles its own parked proposals)
 #include "gf_propose.hpp"               // philox_block, proposal_lnprob: shared with the nested sampler (gf_nested.hip)
 
@@ -1976,6 +1977,52 @@ int gf_sampler_postprocess_with(gf_sampler* s, gf_model* const* models, double* 
     if (rc != GF_OK) return rc;
     if (e != hipSuccess) return gf_hip_fail(e, "gf_sampler_postprocess");
     return status ? gf_internal_check_overflow(s->device, st) : GF_OK;
+}
+
+// Stored chain -> compositions -> histogram (the steps of gf_sampler_postprocess_with, one chain after the other through the same
+// scratch buffers) -> credible regions of all chains at once (gf_region.hip).  The counts never leave the device.
+int gf_sampler_regions(gf_sampler* s, gf_model* const* models, int nbins, int radius, const double* weights, const double* coverage,
+                       int ncov, int64_t cap, int64_t* thres, int32_t* saturated, double* level_in, double* level_out, double* mass,
+                       int32_t* cells, double* density)
+{
+    if (!s) return GF_ERR_INVALID_ARG;
+    int rc = gf_region_check_args(s->nchains, nbins, radius, weights, coverage, ncov, cap);
+    if (rc != GF_OK) return rc;
+    int cus = 256;
+    if (check_chain_models(s, models, &cus) != GF_OK) return GF_ERR_INVALID_ARG;
+    GF_HIP(hipSetDevice(s->device));
+    hipStream_t st = s->stream;
+    const int64_t per_chain = s->nstored * s->nwalkers;
+    const size_t nbin3 = (size_t)nbins * nbins * nbins;
+    double* d_fr = nullptr;
+    int32_t* d_st = nullptr;
+    uint64_t* d_c = nullptr;
+    hipError_t e = hipMalloc((void**)&d_c, sizeof(uint64_t) * nbin3 * s->nchains);
+    if (e == hipSuccess) e = hipMemsetAsync(d_c, 0, sizeof(uint64_t) * nbin3 * s->nchains, st);
+    if (e == hipSuccess && per_chain > 0) e = hipMalloc((void**)&d_fr, sizeof(double) * 3 * per_chain);
+    if (e == hipSuccess && per_chain > 0) e = hipMalloc((void**)&d_st, sizeof(int32_t) * per_chain);
+    if (e == hipSuccess && per_chain > 0) {
+        gf_internal_full_arbitration_grids(s->device, st, 1);      // see gf_sampler_postprocess_device
+        for (int ch = 0; ch < s->nchains && e == hipSuccess && rc == GF_OK; ++ch) {
+            const double* d_theta = s->d_chain + (size_t)ch * s->nstore_cap * s->nwalkers * s->ndim;
+            rc = gf_model_propagate_on(chain_model(s, models, ch), st, d_theta, GF_LAYOUT_AOS, per_chain, d_fr, d_st);
+            if (rc != GF_OK) break;
+            e = gf_launch_mask_fr(d_fr, d_st, per_chain, st);
+            if (e == hipSuccess) e = gf_launch_flavor_hist(d_fr, per_chain, nbins, (unsigned long long*)(d_c + (size_t)ch * nbin3), cus, st);
+        }
+        gf_internal_full_arbitration_grids(s->device, st, 0);
+    }
+    if (e == hipSuccess && rc == GF_OK)
+        rc = gf_region_run(st, d_c, s->nchains, nbins, radius, weights, coverage, ncov, cap, thres, saturated, level_in, level_out, mass, cells,
+                           density, nullptr);
+    else
+        (void)hipStreamSynchronize(st);
+    if (d_fr) (void)hipFree(d_fr);
+    if (d_st) (void)hipFree(d_st);
+    if (d_c) (void)hipFree(d_c);
+    if (rc != GF_OK) return rc;
+    if (e != hipSuccess) return gf_hip_fail(e, "gf_sampler_regions");
+    return per_chain > 0 ? gf_internal_check_overflow(s->device, st) : GF_OK;
 }
 
 }  // extern "C"

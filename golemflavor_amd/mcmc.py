@@ -496,6 +496,29 @@ class DeviceEnsembleSampler:
             out["hist"] = hist[0] if self.nchains == 1 else hist
         return out
 
+    def regions(self, nbins, coverage, hist_smooth=0.05, oversample=1., models=None, truncate=4.0, cap=None):
+        """The credible regions of the stored samples' compositions, `plot.flavor_contour`'s reduction
+        (golemflavor/plot.py:365-392: int(nbins * oversample) + 1 bins per axis, H / sum, gaussian_filter(sigma=hist_smooth),
+        cells in descending order until the running sum reaches coverage / 100) for every chain at once: the chains'
+        histograms stay on the device, only the regions come back.  coverage: a number or up to 8; returns a
+        `contour.RegionResult` (a list of them for several coverages), with a leading list level over the chains when
+        nchains > 1.  models as in `postprocess`; a sample the reference would have raised on is left out."""
+        from . import contour
+        C = self._C
+        handles = None
+        if models is not None:
+            ms = [getattr(m, "model", m) for m in models]
+            if len(ms) != self.nchains:
+                raise ValueError("%d post-processing models for %d chains" % (len(ms), self.nchains))
+            handles = (C.c_void_p * self.nchains)(*[m._h.value if hasattr(m._h, "value") else m._h for m in ms])
+        nb = int(nbins * oversample) + 1
+        scalar, _ = contour._coverages(coverage)
+
+        def call(*args):
+            return self._L.gf_sampler_regions(self._h, handles, nb, *args)
+        res = contour.run_region_call(call, "gf_sampler_regions", self.nchains, nb, coverage, hist_smooth, truncate, cap)
+        return contour.shape_results(res, scalar, self.nchains == 1)
+
     @property
     def nstored(self):
         return int(self._L.gf_sampler_nstored(self._h))

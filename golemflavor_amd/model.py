@@ -233,6 +233,12 @@ class Model:
                                           counts.ctypes.data_as(C.POINTER(C.c_uint64))), "gf_flavor_histogram")
         return counts
 
+    def flavor_region(self, frs, nbins, coverage, hist_smooth=0.05, oversample=1., **kw):
+        """The credible region(s) `plot.flavor_contour(frs, nbins, coverage, hist_smooth=..., oversample=...)` finds before it
+        draws (golemflavor/plot.py:365-392), on the GPU: see `contour.flavor_region`."""
+        from . import contour
+        return contour.flavor_region(frs, nbins, coverage, hist_smooth, oversample, model=self, **kw)
+
     # -- device-resident path ----------------------------------------------------------
     def alloc(self, nbytes):
         return DeviceBuffer(self, nbytes)

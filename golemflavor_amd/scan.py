@@ -257,7 +257,47 @@ GATHER_STATS = {}     # the last DeviceGather.run: bytes and seconds by phase
 LAST_NONUNITARY = {}  # the last stacked run_points call: proposals the reference would have raised on, and how they were settled
 
 
-def run_points(points, indices, make, burnin, nsteps, stacked=True, seed=25, gather=None):
+REGION_STATS = {}     # the last run_points call with regions: what --regions computed on this rank (reported by main)
+
+
+class RegionWriter:
+    """--regions: the credible regions of every grid point's compositions (golemflavor/plot.py:365-392, `DeviceEnsembleSampler.regions`),
+    computed while the point's sampler still holds its chain and saved as contour_region_<point file name>.npz beside the chain
+    file.  The regions of one point are nested -- each is a prefix of the same ordering of the cells -- so a file holds the cells
+    and densities of the largest region once: `cells` (n, 3), `density` (n,), and per coverage `coverage`, `thres` (region q is
+    cells[:thres[q]]), `level_in`, `level_out`, `mass`, `saturated`; `nbins` is the number of bins per axis."""
+
+    def __init__(self, datadir, name_of, coverage, nbins=25, oversample=5., smooth=0.05):
+        self.datadir, self.name_of = datadir, name_of
+        self.coverage = [float(c) for c in coverage]
+        self.nbins, self.oversample, self.smooth = int(nbins), float(oversample), float(smooth)
+        self.seconds, self.thres = 0.0, []
+
+    def take(self, sampler, models, order):
+        """sampler: the chains of grid points `order`; models: their post-processing models (None: the sampled posteriors)."""
+        t0 = time.perf_counter()
+        res = sampler.regions(self.nbins, self.coverage, hist_smooth=self.smooth, oversample=self.oversample, models=models)
+        for g, row in zip(order, [res] if len(order) == 1 else res):
+            big = max(row, key=lambda r: len(r.flat_cells))
+            os.makedirs(self.datadir, exist_ok=True)
+            np.savez(os.path.join(self.datadir, "contour_region_%s.npz" % self.name_of(g)), cells=big.cells, density=big.density,
+                     coverage=np.array([r.coverage for r in row]), thres=np.array([r.thres for r in row], dtype=np.int64),
+                     level_in=np.array([r.level_in for r in row]), level_out=np.array([r.level_out for r in row]),
+                     mass=np.array([r.mass for r in row]), saturated=np.array([r.saturated for r in row]), nbins=np.int64(big.nbins))
+            self.thres.append([r.thres for r in row])
+        self.seconds += time.perf_counter() - t0
+        REGION_STATS.clear()
+        REGION_STATS.update({"coverage": self.coverage, "bins_per_axis": int(self.nbins * self.oversample) + 1, "hist_smooth": self.smooth,
+                             "points": len(self.thres), "seconds": round(self.seconds, 4),
+                             "thres_min": np.min(self.thres, axis=0).tolist(), "thres_max": np.max(self.thres, axis=0).tolist()})
+
+
+def _post_models(jobs, order):
+    first = jobs[order[0]]
+    return [jobs[g].post_model for g in order] if getattr(first, "post_model", None) is not None else None
+
+
+def run_points(points, indices, make, burnin, nsteps, stacked=True, seed=25, gather=None, regions=None):
     """All of this rank's grid points advance together.  stacked (default): one sampler, one ensemble per
     grid point's posterior, every half-step of every chain in one launch; chain g draws from random stream g (its
     GLOBAL grid index), so that a grid point's chain does not depend on the number of ranks.  Otherwise one sampler per
@@ -265,7 +305,8 @@ def run_points(points, indices, make, burnin, nsteps, stacked=True, seed=25, gat
 
     gather: None -> {grid index: collected array} of this rank's points (host);
             a `DeviceGather` -> every grid point's array, in grid order, on rank 0 (None elsewhere): the chain blocks
-            go from the sampler's device buffer through RCCL and cross PCIe once."""
+            go from the sampler's device buffer through RCCL and cross PCIe once.
+    regions: a `RegionWriter` -> every point's credible regions are computed and saved while its sampler holds the chain."""
     t0 = time.perf_counter()
     jobs = {g: make(points[g], g) for g in indices}
     if not jobs:
@@ -315,6 +356,8 @@ def run_points(points, indices, make, burnin, nsteps, stacked=True, seed=25, gat
             times = sampler.run_to_host_times()
             if times is not None:
                 LAST_NONUNITARY["host_thread_times"] = times
+        if regions is not None:
+            regions.take(sampler, _post_models(jobs, order), order)
         t0 = time.perf_counter()
         if gather is not None:
             out = gather.run(sampler, jobs, order, len(points), streamed=streamed)
@@ -350,6 +393,8 @@ def run_points(points, indices, make, burnin, nsteps, stacked=True, seed=25, gat
     out = {}
     for g, sm in samplers.items():
         sm.wait()
+        if regions is not None:
+            regions.take(sm, _post_models(jobs, [g]), [g])
         flat = sm.flat_steps()                                    # the stacked paths' row order (module docstring)
         sm.close()
         out[g] = jobs[g].collect(flat)
@@ -654,7 +699,20 @@ def main(argv=None):
     ap.add_argument("--datadir", default=None,
                     help="write one .npy per grid point, named as the reference's jobs name theirs "
                          "(scripts/mc_texture.py:184, misc.py:44-51), each rank its own points")
+    ap.add_argument("--regions", type=float, nargs="+", default=None, metavar="COVERAGE",
+                    help="also save every grid point's credible regions of the flavor triangle at these coverages (percent), "
+                         "contour_region_<point>.npz beside the chain file; needs --datadir and --config C4")
+    ap.add_argument("--region-nbins", type=int, default=25, help="nbins of plot.flavor_contour")
+    ap.add_argument("--region-oversample", type=float, default=5., help="oversample of plot.flavor_contour")
+    ap.add_argument("--region-smooth", type=float, default=0.05, help="hist_smooth of plot.flavor_contour")
     a = ap.parse_args(argv)
+    if a.regions is not None:
+        if not a.datadir:
+            ap.error("--regions needs --datadir (the regions are saved beside the chain files)")
+        if a.config != "C4":
+            ap.error("--regions needs --config C4 (the C5 rows carry no composition)")
+        if not 1 <= len(a.regions) <= 8 or not all(0. < c <= 100. for c in a.regions):
+            ap.error("--regions takes 1 to 8 coverages in (0, 100]")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -697,22 +755,26 @@ def main(argv=None):
         rccl, rccl_err, stuck = gdist.open_device_gather(rank, world, device, control, timeout=float(os.environ.get("GF_RCCL_TIMEOUT", "60")))
     device_gather = want_gather and can_deliver and not shared and (rccl is not None or world == 1)
     gather_name, chains, local = "local", None, None
+    regions = None
+    if a.regions is not None:
+        regions = RegionWriter(a.datadir, lambda g: point_filename(a.config, pts[g], a), a.regions, nbins=a.region_nbins,
+                               oversample=a.region_oversample, smooth=a.region_smooth)
     if a.datadir and not want_gather:
-        local = run_points(pts, mine, make, a.burnin, a.nsteps, stacked=stacked)
+        local = run_points(pts, mine, make, a.burnin, a.nsteps, stacked=stacked, regions=regions)
         gather_name = "none: every rank saved its own files (--datadir)"
     elif shared:
         g = SharedHostGather(control, rank, world, arena=arena)
-        chains = run_points(pts, mine, make, a.burnin, a.nsteps, stacked=True, gather=g)
+        chains = run_points(pts, mine, make, a.burnin, a.nsteps, stacked=True, gather=g, regions=regions)
         gather_name = g.stats.get("delivery", g.kind)
         g.release()
     elif device_gather:
         stage = Model(compile_model(Cf.unitary_paramset(), "PRIOR_ONLY", source_ratio=(1, 2, 0)), device=device)
         chains = run_points(pts, mine, make, a.burnin, a.nsteps, stacked=True,
-                            gather=DeviceGather(rccl, rank, world, stage, control=control))
+                            gather=DeviceGather(rccl, rank, world, stage, control=control), regions=regions)
         stage.close()
         gather_name = ("%s device gather to rank 0" % rccl.kind) if rccl is not None else "device -> host"
     else:
-        local = run_points(pts, mine, make, a.burnin, a.nsteps, stacked=stacked)
+        local = run_points(pts, mine, make, a.burnin, a.nsteps, stacked=stacked, regions=regions)
         t1 = time.perf_counter()
         chains = gdist.gather_chains_to_root(local, len(pts), control)
         PHASES["gather"] = time.perf_counter() - t1
@@ -751,7 +813,7 @@ def main(argv=None):
                           "chains_shape": chains_shape, "seconds": dt,
                           "phases": {k: round(v, 4) for k, v in PHASES.items()},
                           "evals_per_s": len(pts) * evals_per_point / dt,
-                          "finite_fraction": finite}), flush=True)
+                          "finite_fraction": finite, **({"regions": REGION_STATS} if regions is not None else {})}), flush=True)
     control.barrier()
     control.close()
     if rccl_err is not None:

@@ -189,6 +189,33 @@ int gf_haar_draw_device(gf_model* m, uint64_t seed, int64_t first_draw, int64_t 
 int gf_flavor_histogram_device(gf_model* m, const double* d_fr, int64_t n, int nbins, uint64_t* d_counts);
 int gf_flavor_histogram(gf_model* m, const double* fr, int64_t n, int nbins, uint64_t* counts);
 int gf_model_sync(gf_model* m);
+/* Credible regions of the flavor triangle (golemflavor/plot.py:371-392: H / np.sum(H), scipy.ndimage.gaussian_filter, then argsort /
+ * cumsum / searchsorted / mask), for `nchains` histograms d_counts [nchains][nbins]^3 (device; what gf_flavor_histogram_device fills) in
+ * one set of launches.  H = count / total per cell (total < 2^53, else GF_ERR_UNSUPPORTED); smoothing = three passes of scipy's
+ * correlate1d, mode 'reflect', with the 2 * radius + 1 weights the caller computed (golemflavor_amd.contour.gaussian_weights: scipy's
+ * own expression, truncate 4.0); radius 0 (every sigma < 0.125, the reference's default 0.05 included) skips them, radius >
+ * GF_REGION_MAX_RADIUS is GF_ERR_UNSUPPORTED.  The cells with H_s > 0 are ordered by descending H_s (equal values: descending flat index
+ * (i * nbins + j) * nbins + k) and summed sequentially in fp64 in that order (np.cumsum).  Per chain and coverage[q] (percent, in
+ * (0, 100], 1 <= ncov <= GF_REGION_MAX_COVERAGES, any order), host arrays [nchains][ncov], each may be NULL:
+ *   thres      leading cells whose inclusive running sum is < coverage / 100. (np.searchsorted): the region; the cell that crosses
+ *              the coverage is outside, as in the reference
+ *   saturated  1: the sum never reaches coverage / 100. (coverage 100, or rounding): the reference's mask is the whole cube; thres is
+ *              then the number of cells with H_s > 0
+ *   level_in, level_out   H_s of the last cell inside / the first cell outside (NaN where there is none)
+ *   mass       the running sum at the last cell inside (0 for an empty region)
+ * and the region itself, host arrays [nchains][ncov][cap] (NULL = skip): flat indices `cells` and their H_s `density` in sorted order,
+ * the first min(thres, cap) of them -- thres is always the true count, nothing is written past them.  An empty histogram (total == 0)
+ * has no region: thres 0, saturated 0, mass 0, both levels NaN.  d_smoothed (device, [nchains][nbins]^3, may be NULL) receives H_s.
+ * Synchronous. */
+#define GF_REGION_MAX_RADIUS 32
+#define GF_REGION_MAX_COVERAGES 8
+int gf_flavor_region_device(gf_model* m, const uint64_t* d_counts, int nchains, int nbins, int radius, const double* weights,
+                            const double* coverage, int ncov, int64_t cap, int64_t* thres, int32_t* saturated, double* level_in,
+                            double* level_out, double* mass, int32_t* cells, double* density, double* d_smoothed);
+/* the same for ONE chain of host compositions fr [n][3]: histogram (as gf_flavor_histogram), then its region */
+int gf_flavor_region(gf_model* m, const double* fr, int64_t n, int nbins, int radius, const double* weights, const double* coverage,
+                     int ncov, int64_t cap, int64_t* thres, int32_t* saturated, double* level_in, double* level_out, double* mass,
+                     int32_t* cells, double* density, double* d_smoothed);
 /* Touch the pages of a freshly allocated host buffer from several threads (the content is preserved, and a copy may be filling
  * the buffer at the same time: madvise(MADV_POPULATE_WRITE), or a locked OR of zero per page where the kernel lacks it), so that a following
  * large device-to-host copy (gf_sampler_get_chain: sampler.chain of golemflavor/mcmc.py:43) runs at PCIe speed instead of
@@ -269,6 +296,13 @@ int gf_sampler_postprocess(gf_sampler* s, double* fr, int32_t* status, int nbins
 int gf_sampler_postprocess_with(gf_sampler* s, gf_model* const* models, double* fr, int32_t* status, int nbins,
                                 uint64_t* counts);
 
+/* The credible regions of every chain's stored samples (gf_flavor_region_device's outputs, [nchains] leading): chain ch is propagated
+ * with models[ch] (NULL: the sampling models) and binned as gf_sampler_postprocess_with does, except that a sample the reference would
+ * have raised on (status != 0; NaN in the rows a scan saves) is left out of the histogram; the counts of all chains stay on the device
+ * and only the results cross PCIe. */
+int gf_sampler_regions(gf_sampler* s, gf_model* const* models, int nbins, int radius, const double* weights, const double* coverage,
+                       int ncov, int64_t cap, int64_t* thres, int32_t* saturated, double* level_in, double* level_out, double* mass,
+                       int32_t* cells, double* density);
 /* same with DEVICE destinations d_fr [nchains][nstored][nwalkers][3], d_status (NULL = skip); synchronous */
 int gf_sampler_postprocess_device(gf_sampler* s, gf_model* const* models, double* d_fr, int32_t* d_status);
 /* the rows a scan saves, assembled on the device: d_rows [nchains][nstored][nwalkers][3 + ndim] = composition (NaN where the
