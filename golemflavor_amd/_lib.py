@@ -17,6 +17,7 @@ GF_COMM_ID_BYTES = 128
 GF_IPC_HANDLE_BYTES = 64
 GF_REGION_MAX_RADIUS = 32
 GF_REGION_MAX_COVERAGES = 8
+GF_MARGINAL_MAX_RANKS = 16
 
 GF_OK, GF_ERR_INVALID_ARG, GF_ERR_NO_DEVICE, GF_ERR_HIP, GF_ERR_ALLOC, GF_ERR_COMM, GF_ERR_UNSUPPORTED, GF_ERR_QUEUE_OVERFLOW = range(8)
 GF_ST_OK, GF_ST_OUT_OF_PRIOR, GF_ST_NON_UNITARY, GF_ST_NAN = range(4)
@@ -56,6 +57,22 @@ class GfModelDesc(C.Structure):
 
 
 _vp, _dp, _ip = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32)
+_lp, _up = C.POINTER(C.c_int64), C.POINTER(C.c_uint64)
+
+
+class GfMarginalSpec(C.Structure):
+    """struct gf_marginal_spec, field for field."""
+    _fields_ = [("nbins1", C.c_int32), ("nbins2", C.c_int32), ("edges1", _dp), ("edges2", _dp), ("radius", C.c_int32), ("ncov", C.c_int32),
+                ("weights", _dp), ("coverage", _dp), ("nranks", C.c_int32), ("nq", C.c_int32), ("ranks", _lp), ("q", _dp),
+                ("cap1", C.c_int64), ("cap2", C.c_int64)]
+
+
+class GfMarginalOut(C.Structure):
+    """struct gf_marginal_out, field for field; NULL = skip."""
+    _fields_ = [("counts1", _up), ("counts2", _up), ("nvalid", _lp), ("mean", _dp), ("cov", _dp), ("ncol", _lp), ("orank", _lp), ("ostat", _dp),
+                ("thres1", _lp), ("saturated1", _ip), ("level_in1", _dp), ("level_out1", _dp), ("mass1", _dp), ("cells1", _ip), ("density1", _dp),
+                ("thres2", _lp), ("saturated2", _ip), ("level_in2", _dp), ("level_out2", _dp), ("mass2", _dp), ("cells2", _ip), ("density2", _dp)]
+
 
 # name -> (restype, argtypes): every symbol include/golemflavor_hip.h declares
 SIGNATURES = {
@@ -146,6 +163,9 @@ SIGNATURES = {
     "gf_flavor_region_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int64, C.POINTER(C.c_int64), _ip, _dp, _dp, _dp, _ip, _dp, _vp]),
     "gf_flavor_region": (C.c_int, [_vp, _dp, C.c_int64, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int64, C.POINTER(C.c_int64), _ip, _dp, _dp, _dp, _ip, _dp, _vp]),
     "gf_sampler_regions": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int64, C.POINTER(C.c_int64), _ip, _dp, _dp, _dp, _ip, _dp]),
+    "gf_marginals_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, C.c_int, C.POINTER(GfMarginalSpec), C.POINTER(GfMarginalOut)]),
+    "gf_marginals": (C.c_int, [_vp, _dp, C.c_int64, C.c_int, C.POINTER(GfMarginalSpec), C.POINTER(GfMarginalOut)]),
+    "gf_sampler_marginals": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(GfMarginalSpec), C.POINTER(GfMarginalOut)]),
     "gf_simplex_get_starts": (C.c_int, [_vp, C.c_int, _dp, _dp, _ip, C.POINTER(C.c_int64)]),
 }
 

@@ -273,6 +273,19 @@ __global__ __launch_bounds__(RG_BLOCK) void k_region_scan(const double* __restri
         }
 }
 
+// One list per marginal (gf_marginal.hip): the first min(take[ch], cap) sorted pairs of segment ch -> cells / density [ch][cap]
+__global__ __launch_bounds__(RG_BLOCK) void k_region_gather(const double* __restrict__ vals, const int32_t* __restrict__ idx, int64_t N,
+                                                            const long long* __restrict__ take, int64_t cap, int32_t* __restrict__ cells,
+                                                            double* __restrict__ density)
+{
+    const int ch = blockIdx.y;
+    const int64_t n = take[ch] < cap ? take[ch] : cap;
+    for (int64_t i = (int64_t)blockIdx.x * RG_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * RG_BLOCK) {
+        if (cells) cells[(size_t)ch * cap + i] = idx[(size_t)ch * N + i];
+        if (density) density[(size_t)ch * cap + i] = vals[(size_t)ch * N + i];
+    }
+}
+
 // the compositions of samples whose status is not OK become NaN (the rows a scan saves hold NaN there): k_flavor_hist drops them
 __global__ __launch_bounds__(RG_BLOCK) void k_region_mask_fr(double* __restrict__ fr, const int32_t* __restrict__ status, int64_t n)
 {
@@ -309,16 +322,23 @@ int gf_region_check_args(int nchains, int nbins, int radius, const double* weigh
     return GF_OK;
 }
 
-// Everything after the histogram, on stream `st` of the current device; synchronous.  Host outputs [nchains][ncov] (and
-// [nchains][ncov][cap]) may each be NULL; d_smoothed [nchains][nb]^3 (device) may be NULL.
-int gf_region_run(hipStream_t st, const uint64_t* d_counts, int nchains, int nb, int radius, const double* weights, const double* coverage,
-                  int ncov, int64_t cap, int64_t* thres, int32_t* saturated, double* level_in, double* level_out, double* mass,
-                  int32_t* cells, double* density, double* d_smoothed)
+// Everything after the histogram, on stream `st` of the current device; synchronous.  d_counts [nchains][n0][n1][n2] (axis 2
+// contiguous); an axis of length 1 is not filtered (a reflected halo of one cell would sum w * x, which is not x in fp64), so a
+// batch of 1-D histograms is (1, 1, n) and a batch of 2-D ones (1, n, n).  Host outputs [nchains][ncov] (and [nchains][ncov][cap])
+// may each be NULL; d_smoothed [nchains][n0][n1][n2] (device) may be NULL.  one_list: the regions of a chain are prefixes of one
+// sorted list, so cells / density are [nchains][cap] and hold the first min(cap, largest thres) pairs, fetched in
+// one copy instead of one per (chain, coverage).
+int gf_region_run_shape(hipStream_t st, const uint64_t* d_counts, int nchains, int n0, int n1, int n2, int radius, const double* weights,
+                        const double* coverage, int ncov, int64_t cap, int64_t* thres, int32_t* saturated, double* level_in, double* level_out,
+                        double* mass, int32_t* cells, double* density, double* d_smoothed, int one_list)
 {
-    int rc = gf_region_check_args(nchains, nb, radius, weights, coverage, ncov, cap);
+    int rc = gf_region_check_args(nchains, n0, radius, weights, coverage, ncov, cap);
+    if (rc == GF_OK) rc = gf_region_check_args(nchains, n1, radius, weights, coverage, ncov, cap);
+    if (rc == GF_OK) rc = gf_region_check_args(nchains, n2, radius, weights, coverage, ncov, cap);
     if (rc != GF_OK) return rc;
     if (!d_counts || ((uintptr_t)d_counts % 8) || ((uintptr_t)d_smoothed % 8)) return GF_ERR_INVALID_ARG;
-    const int64_t nb3 = (int64_t)nb * nb * nb;
+    const int64_t nb3 = (int64_t)n0 * n1 * n2;
+    const int naxes = radius > 0 ? (n0 > 1) + (n1 > 1) + (n2 > 1) : 0;          // filter passes executed
     const int64_t ncells = nb3 * nchains;
     const int nres = nchains * ncov;
 
@@ -343,7 +363,7 @@ int gf_region_run(hipStream_t st, const uint64_t* d_counts, int nchains, int nb,
     hipError_t e = hipMalloc((void**)&d_small, small_bytes);
     if (e == hipSuccess) e = hipMemsetAsync(d_small, 0, small_bytes, st);
     if (e == hipSuccess && !d_smoothed) e = hipMalloc((void**)&d_y, sizeof(double) * (size_t)ncells);
-    if (e == hipSuccess && radius > 0) e = hipMalloc((void**)&d_x, sizeof(double) * (size_t)ncells);
+    if (e == hipSuccess && naxes > 0) e = hipMalloc((void**)&d_x, sizeof(double) * (size_t)ncells);
     unsigned long long* d_sums = reinterpret_cast<unsigned long long*>(d_small);
     unsigned long long* d_nnz = d_sums + 2 * (size_t)nchains;
     unsigned long long* d_cursor = d_nnz + nchains;
@@ -357,16 +377,27 @@ int gf_region_run(hipStream_t st, const uint64_t* d_counts, int nchains, int nb,
     int64_t N = 0, maxnnz = 0;
     if (e == hipSuccess) {
         hipLaunchKernelGGL(k_region_total, per_chain, dim3(RG_BLOCK), 0, st, (const unsigned long long*)d_counts, nb3, d_sums);
-        hipLaunchKernelGGL(k_region_normalise, per_chain, dim3(RG_BLOCK), 0, st, (const unsigned long long*)d_counts, nb3, d_sums,
-                           radius > 0 ? d_x : H);
-        if (radius > 0) {
-            // x -> H (axis 0), H -> x (axis 1), x -> H (axis 2)
-            hipLaunchKernelGGL(k_region_smooth_axis, dim3(rg_grid(ncells)), dim3(RG_BLOCK), 0, st, d_x, H, nb, (int64_t)nb * nb, ncells, radius, W);
-            hipLaunchKernelGGL(k_region_smooth_axis, dim3(rg_grid(ncells)), dim3(RG_BLOCK), 0, st, H, d_x, nb, (int64_t)nb, ncells, radius, W);
-            const int rows = RG_ROW_LDS / (nb + 2 * radius);     // >= 1: nb + 2 r <= 1024 + 64
-            const int64_t nrows = (int64_t)nchains * nb * nb, blocks = (nrows + rows - 1) / rows;
-            hipLaunchKernelGGL(k_region_smooth_rows, dim3((unsigned)(blocks > RG_MAX_GRID ? RG_MAX_GRID : blocks)), dim3(RG_BLOCK), 0, st, d_x,
-                               H, nb, nrows, rows, radius, W);
+        // the passes alternate between x and H and the last one writes H: three passes are x -> H (axis 0), H -> x (axis 1),
+        // x -> H (axis 2)
+        double* src = (naxes & 1) ? d_x : H;
+        hipLaunchKernelGGL(k_region_normalise, per_chain, dim3(RG_BLOCK), 0, st, (const unsigned long long*)d_counts, nb3, d_sums, src);
+        if (naxes > 0 && n0 > 1) {
+            double* dst = src == H ? d_x : H;
+            hipLaunchKernelGGL(k_region_smooth_axis, dim3(rg_grid(ncells)), dim3(RG_BLOCK), 0, st, src, dst, n0, (int64_t)n1 * n2, ncells, radius, W);
+            src = dst;
+        }
+        if (naxes > 0 && n1 > 1) {
+            double* dst = src == H ? d_x : H;
+            hipLaunchKernelGGL(k_region_smooth_axis, dim3(rg_grid(ncells)), dim3(RG_BLOCK), 0, st, src, dst, n1, (int64_t)n2, ncells, radius, W);
+            src = dst;
+        }
+        if (naxes > 0 && n2 > 1) {
+            double* dst = src == H ? d_x : H;
+            const int rows = RG_ROW_LDS / (n2 + 2 * radius);     // >= 1: n2 + 2 r <= 1024 + 64
+            const int64_t nrows = (int64_t)nchains * n0 * n1, blocks = (nrows + rows - 1) / rows;
+            hipLaunchKernelGGL(k_region_smooth_rows, dim3((unsigned)(blocks > RG_MAX_GRID ? RG_MAX_GRID : blocks)), dim3(RG_BLOCK), 0, st, src,
+                               dst, n2, nrows, rows, radius, W);
+            src = dst;
         }
         hipLaunchKernelGGL(k_region_count, per_chain, dim3(RG_BLOCK), 0, st, H, nb3, d_nnz);
         e = hipGetLastError();
@@ -410,6 +441,7 @@ int gf_region_run(hipStream_t st, const uint64_t* d_counts, int nchains, int nb,
         const double* h_lin = reinterpret_cast<const double*>(h_thres + nres);
         const double *h_lout = h_lin + nres, *h_mass = h_lout + nres;
         const int32_t* h_sat = reinterpret_cast<const int32_t*>(h_mass + nres);
+        std::vector<long long> h_take(one_list ? nchains : 0, 0);
         for (int ch = 0; ch < nchains && e == hipSuccess; ++ch)
             for (int q = 0; q < ncov && e == hipSuccess; ++q) {
                 const int src = ch * ncov + q, dst = ch * ncov + order[q];
@@ -419,12 +451,41 @@ int gf_region_run(hipStream_t st, const uint64_t* d_counts, int nchains, int nb,
                 if (level_out) level_out[dst] = h_lout[src];
                 if (mass) mass[dst] = h_mass[src];
                 // the region is a prefix of the chain's sorted cells: the first min(thres, cap) of them, nothing past them
+                if (one_list) {
+                    h_take[ch] = std::max<long long>(h_take[ch], h_thres[src]);
+                    continue;
+                }
                 const size_t take = (size_t)std::min<int64_t>(h_thres[src], cap);
                 if (take && cells)
                     e = hipMemcpyAsync(cells + (size_t)dst * cap, d_idx + (size_t)ch * N, sizeof(int32_t) * take, hipMemcpyDeviceToHost, st);
                 if (take && density && e == hipSuccess)
                     e = hipMemcpyAsync(density + (size_t)dst * cap, d_vals + (size_t)ch * N, sizeof(double) * take, hipMemcpyDeviceToHost, st);
             }
+        if (one_list && cap > 0 && (cells || density) && e == hipSuccess) {
+            // cells / density are host arrays [nchains][cap]: gather on the device, then one copy each
+            long long* d_take = nullptr;
+            int32_t* d_cells = nullptr;
+            double* d_dens = nullptr;
+            const size_t nout = (size_t)nchains * (size_t)cap;
+            e = hipMalloc((void**)&d_take, sizeof(long long) * nchains);
+            if (e == hipSuccess && cells) e = hipMalloc((void**)&d_cells, sizeof(int32_t) * nout);
+            if (e == hipSuccess && density) e = hipMalloc((void**)&d_dens, sizeof(double) * nout);
+            if (e == hipSuccess && d_cells) e = hipMemsetAsync(d_cells, 0xff, sizeof(int32_t) * nout, st);           // -1 past the list
+            if (e == hipSuccess && d_dens) e = hipMemsetAsync(d_dens, 0, sizeof(double) * nout, st);
+            if (e == hipSuccess) e = hipMemcpyAsync(d_take, h_take.data(), sizeof(long long) * nchains, hipMemcpyHostToDevice, st);
+            if (e == hipSuccess) {
+                hipLaunchKernelGGL(k_region_gather, dim3(rg_grid(cap) > 64 ? 64 : rg_grid(cap), nchains), dim3(RG_BLOCK), 0, st, d_vals, d_idx, N,
+                                   d_take, cap, d_cells, d_dens);
+                e = hipGetLastError();
+            }
+            if (e == hipSuccess && cells) e = hipMemcpyAsync(cells, d_cells, sizeof(int32_t) * nout, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess && density) e = hipMemcpyAsync(density, d_dens, sizeof(double) * nout, hipMemcpyDeviceToHost, st);
+            const hipError_t e3 = hipStreamSynchronize(st);
+            if (e == hipSuccess) e = e3;
+            if (d_take) (void)hipFree(d_take);
+            if (d_cells) (void)hipFree(d_cells);
+            if (d_dens) (void)hipFree(d_dens);
+        }
         const hipError_t e2 = hipStreamSynchronize(st);
         if (e == hipSuccess) e = e2;
     } else {
@@ -438,6 +499,14 @@ int gf_region_run(hipStream_t st, const uint64_t* d_counts, int nchains, int nb,
     if (rc != GF_OK) return rc;
     if (e != hipSuccess) return gf_hip_fail(e, "flavor region");
     return GF_OK;
+}
+
+int gf_region_run(hipStream_t st, const uint64_t* d_counts, int nchains, int nb, int radius, const double* weights, const double* coverage,
+                  int ncov, int64_t cap, int64_t* thres, int32_t* saturated, double* level_in, double* level_out, double* mass,
+                  int32_t* cells, double* density, double* d_smoothed)
+{
+    return gf_region_run_shape(st, d_counts, nchains, nb, nb, nb, radius, weights, coverage, ncov, cap, thres, saturated, level_in, level_out,
+                               mass, cells, density, d_smoothed, 0);
 }
 
 extern "C" {

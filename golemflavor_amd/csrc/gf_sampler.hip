@@ -31,6 +31,7 @@
 #include "gf_bsm_device.hpp"
 #include "gf_launch.h"
 #include "gf_region.h"
+#include "gf_marginal.h"
 #include "gf_unitarity_teams.hpp"      // Team9: the reference's unitarity chain on nine lanes (k_stretch_chain settles its own parked proposals)
 #include "gf_propose.hpp"               // philox_block, proposal_lnprob: shared with the nested sampler (gf_nested.hip)
 
@@ -2023,6 +2024,30 @@ int gf_sampler_regions(gf_sampler* s, gf_model* const* models, int nbins, int ra
     if (rc != GF_OK) return rc;
     if (e != hipSuccess) return gf_hip_fail(e, "gf_sampler_regions");
     return per_chain > 0 ? gf_internal_check_overflow(s->device, st) : GF_OK;
+}
+
+// The marginals of every stored chain (gf_marginal.hip).  with_fr: the rows a scan saves are assembled first
+// (gf_sampler_postprocess_rows_device) and reduced in place of the chain; either way the rows never leave the device.
+int gf_sampler_marginals(gf_sampler* s, gf_model* const* models, int with_fr, const gf_marginal_spec* spec, const gf_marginal_out* out)
+{
+    if (!s || !out) return GF_ERR_INVALID_ARG;
+    const int width = (with_fr ? 3 : 0) + s->ndim;
+    const int64_t per_chain = s->nstored * s->nwalkers;
+    int rc = gf_marginal_check_args(s->nchains, per_chain, width, spec);
+    if (rc != GF_OK) return rc;
+    if (check_chain_models(s, models) != GF_OK) return GF_ERR_INVALID_ARG;
+    GF_HIP(hipSetDevice(s->device));
+    hipStream_t st = s->stream;
+    if (!with_fr || per_chain == 0) {
+        GF_HIP(hipStreamSynchronize(st));
+        return gf_marginal_run(st, s->d_chain, with_fr ? 0 : s->nstore_cap * s->nwalkers * s->ndim, s->nchains, per_chain, width, spec, out);
+    }
+    double* d_rows = nullptr;
+    GF_HIP(hipMalloc((void**)&d_rows, sizeof(double) * (size_t)per_chain * width * s->nchains));
+    rc = gf_sampler_postprocess_rows_device(s, models, d_rows);
+    if (rc == GF_OK) rc = gf_marginal_run(st, d_rows, per_chain * width, s->nchains, per_chain, width, spec, out);
+    (void)hipFree(d_rows);
+    return rc;
 }
 
 }  // extern "C"

@@ -519,6 +519,35 @@ class DeviceEnsembleSampler:
         res = contour.run_region_call(call, "gf_sampler_regions", self.nchains, nb, coverage, hist_smooth, truncate, cap)
         return contour.shape_results(res, scalar, self.nchains == 1)
 
+    def marginals(self, ranges=None, with_fr=False, models=None, names=None, **kw):
+        """The posterior marginals of the stored samples (`marginals.chain_marginals`'s reduction and keyword arguments:
+        bins_1d, bins_2d, coverage, percentiles, ranks, hist_smooth, truncate, cap_2d) for every chain at once, the chain
+        staying on the device.  with_fr: the rows a scan saves -- composition (NaN where the reference would have raised), then
+        the sample -- propagated with `models` as in `postprocess`.  ranges: (width, 2); default: the box of the sampled model's
+        descriptor, and (0, 1) for the composition columns.  Returns a `marginals.MarginalResult`, a list of them over the
+        chains when nchains > 1."""
+        from . import marginals as mg
+        C = self._C
+        handles = None
+        if models is not None:
+            ms = [getattr(m, "model", m) for m in models]
+            if len(ms) != self.nchains:
+                raise ValueError("%d post-processing models for %d chains" % (len(ms), self.nchains))
+            handles = (C.c_void_p * self.nchains)(*[m._h.value if hasattr(m._h, "value") else m._h for m in ms])
+        width = (3 if with_fr else 0) + self.dim
+        if ranges is None:
+            d = self.model.desc
+            ranges = ([(0., 1.)] * 3 if with_fr else []) + [(d.lo[c], d.hi[c]) for c in range(self.dim)]
+        if names is None:
+            names = (["fr_e", "fr_mu", "fr_tau"] if with_fr else []) + ["theta%d" % c for c in range(self.dim)]
+        cap_2d = kw.pop("cap_2d", None)
+        prep = mg.prepare(width, ranges, names, **kw)
+
+        def call(spec, out):
+            return self._L.gf_sampler_marginals(self._h, handles, int(bool(with_fr)), spec, out)
+        res = mg.run_marginal_call(call, "gf_sampler_marginals", self.nchains, prep, cap_2d)
+        return res[0] if self.nchains == 1 else res
+
     @property
     def nstored(self):
         return int(self._L.gf_sampler_nstored(self._h))

@@ -292,6 +292,44 @@ class RegionWriter:
                              "thres_min": np.min(self.thres, axis=0).tolist(), "thres_max": np.max(self.thres, axis=0).tolist()})
 
 
+MARGINAL_STATS = {}   # the last run_points call with marginals: what --marginals computed on this rank (reported by main)
+
+
+class MarginalWriter:
+    """--marginals: the posterior marginals of every grid point's saved rows (`DeviceEnsembleSampler.marginals`: 1-D and 2-D
+    histograms over the sampled model's box, (0, 1) for the composition columns, their credible regions, percentiles, mean and
+    covariance), computed while the point's sampler still holds its chain and saved as marginals_<point file name>.npz beside the
+    chain file; the arrays are `marginals.MarginalResult.as_arrays()`."""
+
+    def __init__(self, datadir, name_of, bins_1d=100, bins_2d=50, coverage=(90., 99.), percentiles=(5., 50., 95.)):
+        self.datadir, self.name_of = datadir, name_of
+        self.kw = dict(bins_1d=int(bins_1d), bins_2d=int(bins_2d), coverage=[float(c) for c in coverage],
+                       percentiles=[float(q) for q in percentiles])
+        self.seconds, self.points = 0.0, 0
+
+    def take(self, sampler, models, order):
+        t0 = time.perf_counter()
+        res = sampler.marginals(with_fr=models is not None, models=models, **self.kw)
+        os.makedirs(self.datadir, exist_ok=True)
+        for g, r in zip(order, [res] if len(order) == 1 else res):
+            r.save(os.path.join(self.datadir, "marginals_%s.npz" % self.name_of(g)))
+            self.points += 1
+        self.seconds += time.perf_counter() - t0
+        MARGINAL_STATS.clear()
+        MARGINAL_STATS.update({"bins": [self.kw["bins_1d"], self.kw["bins_2d"]], "points": self.points, "seconds": round(self.seconds, 4)})
+
+
+class _Takers:
+    """several writers behind the one `regions` argument of run_points"""
+
+    def __init__(self, takers):
+        self.takers = takers
+
+    def take(self, sampler, models, order):
+        for t in self.takers:
+            t.take(sampler, models, order)
+
+
 def _post_models(jobs, order):
     first = jobs[order[0]]
     return [jobs[g].post_model for g in order] if getattr(first, "post_model", None) is not None else None
@@ -705,7 +743,21 @@ def main(argv=None):
     ap.add_argument("--region-nbins", type=int, default=25, help="nbins of plot.flavor_contour")
     ap.add_argument("--region-oversample", type=float, default=5., help="oversample of plot.flavor_contour")
     ap.add_argument("--region-smooth", type=float, default=0.05, help="hist_smooth of plot.flavor_contour")
+    ap.add_argument("--marginals", action="store_true",
+                    help="also save every grid point's posterior marginals (histograms, credible regions, percentiles, moments), "
+                         "marginals_<point>.npz beside the chain file; needs --datadir")
+    ap.add_argument("--marginal-bins-1d", type=int, default=100)
+    ap.add_argument("--marginal-bins-2d", type=int, default=50)
+    ap.add_argument("--marginal-coverage", type=float, nargs="+", default=[90., 99.], metavar="COVERAGE")
+    ap.add_argument("--marginal-percentiles", type=float, nargs="+", default=[5., 50., 95.], metavar="Q")
     a = ap.parse_args(argv)
+    if a.marginals:
+        if not a.datadir:
+            ap.error("--marginals needs --datadir (the marginals are saved beside the chain files)")
+        if not 1 <= len(a.marginal_coverage) <= 8 or not all(0. < c <= 100. for c in a.marginal_coverage):
+            ap.error("--marginal-coverage takes 1 to 8 coverages in (0, 100]")
+        if not 1 <= len(a.marginal_percentiles) <= 8 or not all(0. <= q <= 100. for q in a.marginal_percentiles):
+            ap.error("--marginal-percentiles takes 1 to 8 percentiles in [0, 100]")
     if a.regions is not None:
         if not a.datadir:
             ap.error("--regions needs --datadir (the regions are saved beside the chain files)")
@@ -759,6 +811,13 @@ def main(argv=None):
     if a.regions is not None:
         regions = RegionWriter(a.datadir, lambda g: point_filename(a.config, pts[g], a), a.regions, nbins=a.region_nbins,
                                oversample=a.region_oversample, smooth=a.region_smooth)
+    marginal_writer = None
+    if a.marginals:
+        marginal_writer = MarginalWriter(a.datadir, lambda g: point_filename(a.config, pts[g], a), a.marginal_bins_1d, a.marginal_bins_2d,
+                                         a.marginal_coverage, a.marginal_percentiles)
+    region_stats_wanted = regions is not None
+    if marginal_writer is not None:
+        regions = _Takers([t for t in (regions, marginal_writer) if t is not None])
     if a.datadir and not want_gather:
         local = run_points(pts, mine, make, a.burnin, a.nsteps, stacked=stacked, regions=regions)
         gather_name = "none: every rank saved its own files (--datadir)"
@@ -813,7 +872,8 @@ def main(argv=None):
                           "chains_shape": chains_shape, "seconds": dt,
                           "phases": {k: round(v, 4) for k, v in PHASES.items()},
                           "evals_per_s": len(pts) * evals_per_point / dt,
-                          "finite_fraction": finite, **({"regions": REGION_STATS} if regions is not None else {})}), flush=True)
+                          "finite_fraction": finite, **({"regions": REGION_STATS} if region_stats_wanted else {}),
+                          **({"marginals": MARGINAL_STATS} if marginal_writer is not None else {})}), flush=True)
     control.barrier()
     control.close()
     if rccl_err is not None:

@@ -374,6 +374,70 @@ int gf_simplex_result(gf_simplex* s, double* max_lnl, double* argmax_cube, int32
 /* run `run`'s starts [nstarts + nuser]: final f (+inf for an unused start), final cube point [..][nscan], nit, nfev; NULL = skip */
 int gf_simplex_get_starts(gf_simplex* s, int run, double* fun, double* cube, int32_t* nit, int64_t* nfev);
 
+/* ---- posterior marginals of a chain (the numbers behind golemflavor/plot.py:450-469 plot_Tchain) ---------------------------- */
+/* Every chain's rows [nrows][width] reduced on the device to its 1-D and 2-D histograms, moments, order statistics and the
+ * credible regions of each marginal.  getdist (the reference's plotter) is not a dependency, so the definition is this
+ * package's own, stated in numpy's terms:
+ *   counts1 [nchains][width][nbins1]            np.histogram(x_c, bins=nbins1, range=(lo_c, hi_c)): bin b holds edge[b] <= v <
+ *                                               edge[b + 1], the last bin closed on the right, decided by comparison with the
+ *                                               caller's edges1 [width][nbins1 + 1] (np.linspace(lo, hi, nbins1 + 1));
+ *   counts2 [nchains][npairs][nbins2][nbins2]   np.histogram2d(x_i, x_j) over edges2 [width][nbins2 + 1] for the pairs i < j in
+ *                                               lexicographic order, npairs = width (width - 1) / 2; a value outside its
+ *                                               range or NaN drops the sample from that column's histogram and from every
+ *                                               pair with that column;
+ *   nvalid [nchains], mean [nchains][width], cov [nchains][width][width]
+ *                                               over the rows without a NaN in any column; cov is two-pass, centred on the
+ *                                               device mean, ddof = 1; both sums follow one fixed tree (4096-row leaves), so
+ *                                               they do not depend on the launch;
+ *   ncol [nchains][width]                       the column's non-NaN values;
+ *   orank, ostat [nchains][width][nranks + 2 nq]
+ *                                               exact order statistics (radix select on the order-preserving key of the
+ *                                               double, no interpolation in a histogram) of the column's non-NaN values:
+ *                                               first the caller's ranks (k >= 0 from the bottom, k < 0 from the top: -1 is the
+ *                                               largest), then for every q (percent) the two neighbours floor(v) and
+ *                                               min(floor(v) + 1, n - 1) of numpy's `linear` virtual index v = (n - 1) * (q /
+ *                                               100); orank holds the rank used (-1 and NaN where there is none);
+ *   regions                                     gf_flavor_region_device's reduction (H / sum, gaussian_filter of `radius` /
+ *                                               `weights` along every axis longer than 1, descending sort with ties by
+ *                                               descending flat index, sequential running sum) of every 1-D marginal
+ *                                               ([nchains][width][ncov]) and 2-D marginal ([nchains][npairs][ncov]).  The
+ *                                               regions of one marginal are prefixes of ONE sorted list, returned once:
+ *                                               cells1 / density1 [nchains][width][cap1], cells2 / density2
+ *                                               [nchains][npairs][cap2] hold its first min(cap, largest thres) entries
+ *                                               (flat index b, or b_i * nbins2 + b_j).
+ * Any output pointer may be NULL.  At most GF_MARGINAL_MAX_RANKS rank slots; nbins and width so large that one pair's
+ * histogram (4 nbins2^2 bytes) plus the 1-D ones (4 width nbins1) exceed 64 KiB of LDS: GF_ERR_UNSUPPORTED. */
+#define GF_MARGINAL_MAX_RANKS 16
+typedef struct gf_marginal_spec {
+    int32_t nbins1, nbins2;
+    const double* edges1;       /* host [width][nbins1 + 1], strictly increasing */
+    const double* edges2;       /* host [width][nbins2 + 1] */
+    int32_t radius, ncov;       /* smoothing: as gf_flavor_region_device */
+    const double* weights;      /* host [2 radius + 1], NULL when radius == 0 */
+    const double* coverage;     /* host [ncov], percent */
+    int32_t nranks, nq;
+    const int64_t* ranks;       /* host [nranks] */
+    const double* q;            /* host [nq], percent in [0, 100] */
+    int64_t cap1, cap2;
+} gf_marginal_spec;
+typedef struct gf_marginal_out {
+    uint64_t *counts1, *counts2;
+    int64_t* nvalid;
+    double *mean, *cov;
+    int64_t *ncol, *orank;
+    double* ostat;
+    int64_t* thres1; int32_t* saturated1; double *level_in1, *level_out1, *mass1; int32_t* cells1; double* density1;
+    int64_t* thres2; int32_t* saturated2; double *level_in2, *level_out2, *mass2; int32_t* cells2; double* density2;
+} gf_marginal_out;
+/* rows on the device, chain after chain: d_rows [nchains][nrows][width] */
+int gf_marginals_device(gf_model* m, const double* d_rows, int nchains, int64_t nrows, int width, const gf_marginal_spec* spec,
+                        const gf_marginal_out* out);
+/* host rows [nrows][width] of one chain: upload, then the same path */
+int gf_marginals(gf_model* m, const double* rows, int64_t nrows, int width, const gf_marginal_spec* spec, const gf_marginal_out* out);
+/* the stored chains of a sampler, width = ndim; with_fr != 0: the rows a scan saves (gf_sampler_postprocess_rows_device: chain ch
+ * propagated with models[ch], NULL = the sampling models), width = 3 + ndim.  The rows stay on the device. */
+int gf_sampler_marginals(gf_sampler* s, gf_model* const* models, int with_fr, const gf_marginal_spec* spec, const gf_marginal_out* out);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI -------------------------------------- */
 /* Independent chains (grid points) shard across ranks with no data-path collective; the only
  * exchanges are the broadcast of the packed descriptors at start and the gather of the chain blocks

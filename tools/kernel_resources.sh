@@ -1,12 +1,13 @@
 #!/bin/bash
 # Static resources of every kernel of libgolemhip.so as compiled (the code object's own metadata: registers, scratch, LDS):
 #   tools/kernel_resources.sh > profiles/rNN/kernel_resources.txt
+#   tools/kernel_resources.sh gf_marginal gf_region > profiles/marginals/kernel_resources.txt     (only these files)
 # No GPU needed.  scratch = .private_segment_fixed_size (bytes per lane), lds = .group_segment_fixed_size (static bytes per block).
 set -e
 cd "$(dirname "$0")/../golemflavor_amd/csrc"
 T=$(mktemp -d)
 printf "%-110s %6s %6s %8s %8s %7s\n" kernel vgpr sgpr scratch lds spills
-for f in gf_kernels gf_bsm gf_unitarity gf_sampler gf_capi gf_nested gf_simplex; do
+for f in ${@:-gf_kernels gf_bsm gf_unitarity gf_sampler gf_capi gf_nested gf_simplex gf_region gf_marginal}; do
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -c $f.hip -o $T/$f.o -save-temps=obj 2>/dev/null
   S=$T/$f-hip-amdgcn-amd-amdhsa-gfx950.s
   [ -f $S ] || continue
