@@ -18,6 +18,8 @@ GF_IPC_HANDLE_BYTES = 64
 GF_REGION_MAX_RADIUS = 32
 GF_REGION_MAX_COVERAGES = 8
 GF_MARGINAL_MAX_RANKS = 16
+GF_ELEMENT_MAX_WIDTH = GF_MAX_DIM + 3
+GF_ELEMENT_COPY, GF_ELEMENT_U9, GF_ELEMENT_FR3 = range(3)
 
 GF_OK, GF_ERR_INVALID_ARG, GF_ERR_NO_DEVICE, GF_ERR_HIP, GF_ERR_ALLOC, GF_ERR_COMM, GF_ERR_UNSUPPORTED, GF_ERR_QUEUE_OVERFLOW = range(8)
 GF_ST_OK, GF_ST_OUT_OF_PRIOR, GF_ST_NON_UNITARY, GF_ST_NAN = range(4)
@@ -72,6 +74,16 @@ class GfMarginalOut(C.Structure):
     _fields_ = [("counts1", _up), ("counts2", _up), ("nvalid", _lp), ("mean", _dp), ("cov", _dp), ("ncol", _lp), ("orank", _lp), ("ostat", _dp),
                 ("thres1", _lp), ("saturated1", _ip), ("level_in1", _dp), ("level_out1", _dp), ("mass1", _dp), ("cells1", _ip), ("density1", _dp),
                 ("thres2", _lp), ("saturated2", _ip), ("level_in2", _dp), ("level_out2", _dp), ("mass2", _dp), ("cells2", _ip), ("density2", _dp)]
+
+
+class GfElementGroup(C.Structure):
+    """struct gf_element_group, field for field."""
+    _fields_ = [("kind", C.c_int32), ("col", C.c_int32 * 4)]
+
+
+class GfElementPlan(C.Structure):
+    """struct gf_element_plan, field for field."""
+    _fields_ = [("ngroups", C.c_int32), ("round32", C.c_int32), ("group", GfElementGroup * GF_ELEMENT_MAX_WIDTH)]
 
 
 # name -> (restype, argtypes): every symbol include/golemflavor_hip.h declares
@@ -166,6 +178,10 @@ SIGNATURES = {
     "gf_marginals_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, C.c_int, C.POINTER(GfMarginalSpec), C.POINTER(GfMarginalOut)]),
     "gf_marginals": (C.c_int, [_vp, _dp, C.c_int64, C.c_int, C.POINTER(GfMarginalSpec), C.POINTER(GfMarginalOut)]),
     "gf_sampler_marginals": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(GfMarginalSpec), C.POINTER(GfMarginalOut)]),
+    "gf_element_plan_width": (C.c_int, [C.POINTER(GfElementPlan), C.c_int]),
+    "gf_element_rows_device": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.POINTER(GfElementPlan), _vp]),
+    "gf_element_rows": (C.c_int, [_vp, _dp, C.c_int64, C.c_int, C.POINTER(GfElementPlan), _dp]),
+    "gf_sampler_element_marginals": (C.c_int, [_vp, C.POINTER(GfElementPlan), C.POINTER(GfMarginalSpec), C.POINTER(GfMarginalOut)]),
     "gf_simplex_get_starts": (C.c_int, [_vp, C.c_int, _dp, _dp, _ip, C.POINTER(C.c_int64)]),
 }
 

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "gf_consts.h"
+#include "gf_elements.hpp"
 
 #define GF_WAVE 64
 #define GF_BLOCK 256
@@ -33,18 +34,7 @@ __device__ __forceinline__ double gf_nan() { return __longlong_as_double(0x7ff80
 
 // sqrt for x in [0, ~1e300): v_rsq_f64 seed + two Newton-Raphson (Goldschmidt) refinements, no denormal
 // scaling.  x == 0 -> 0; x < 0 or NaN -> NaN.
-__device__ __forceinline__ double fast_sqrt(double x)
-{
-    const double y = __builtin_amdgcn_rsq(x);
-    double g = x * y;
-    double h = 0.5 * y;
-    const double r = fma(-h, g, 0.5);
-    g = fma(g, r, g);
-    h = fma(h, r, h);
-    const double d = fma(-g, g, x);
-    g = fma(d, h, g);
-    return x == 0.0 ? 0.0 : g;
-}
+__device__ __forceinline__ double fast_sqrt(double x) { return gfel::el_sqrt(x); }      // gf_elements.hpp: shared with its host build
 
 // 1/x for finite normal x: v_rcp_f64 seed + two Newton-Raphson steps.
 __device__ __forceinline__ double fast_rcp(double x)
@@ -66,30 +56,7 @@ __device__ __forceinline__ void fast_sincos(double x, double* sn, double* cs)
     // beyond the reduction's range (never a physical phase): NaN -> GF_ST_NAN.  gf_model_create refuses models
     // whose phase columns could get here (GF_PHASE_MAX), so that the library's Payne-Hanek path -- ~100 VGPRs and
     // a scratch frame for every kernel that can reach it -- stays out of the hot kernels' register budget.
-    if (!(fabs(x) < 1.6e6)) { *sn = gf_nan(); *cs = gf_nan(); return; }
-    const double fn = rint(x * 6.36619772367581382433e-01);          // x * 2/pi
-    double r = fma(-fn, 1.57079632673412561417e+00, x);              // pio2_1 (33 bits)
-    r = fma(-fn, 6.07710050630396597660e-11, r);                     // pio2_2 (33 bits)
-    r = fma(-fn, 2.02226624879595063154e-21, r);                     // pio2_2t: the rest of pi/2
-    const int q = (int)fn;
-    const double z = r * r;
-    double ps = fma(z, 1.58969099521155010221e-10, -2.50507602534068634195e-08);
-    ps = fma(z, ps, 2.75573137070700676789e-06);
-    ps = fma(z, ps, -1.98412698298579493134e-04);
-    ps = fma(z, ps, 8.33333333332248946124e-03);
-    ps = fma(z, ps, -1.66666666666666324348e-01);
-    const double s = fma(r * z, ps, r);
-    double pc = fma(z, -1.13596475577881948265e-11, 2.08757232129817482790e-09);
-    pc = fma(z, pc, -2.75573143513906633035e-07);
-    pc = fma(z, pc, 2.48015872894767294178e-05);
-    pc = fma(z, pc, -1.38888888888741095749e-03);
-    pc = fma(z, pc, 4.16666666666666019037e-02);
-    const double c = fma(z * z, pc, fma(-0.5, z, 1.0));
-    // quadrant: (sin, cos)(x) = (s, c), (c, -s), (-s, -c), (-c, s) for q mod 4 = 0, 1, 2, 3
-    const double ss = (q & 1) ? c : s;
-    const double cc = (q & 1) ? s : c;
-    *sn = (q & 2) ? -ss : ss;
-    *cs = ((q + 1) & 2) ? -cc : cc;
+    gfel::sincos_cw(x, sn, cs);                                      // gf_elements.hpp: shared with its host build
 }
 
 __device__ __forceinline__ double fast_cos(double x)
@@ -348,15 +315,7 @@ __device__ __forceinline__ void pmns_abs2(double s12_2, double c13_4, double s23
 
 // golemflavor/fr.py:82-113 angles_to_fr: (sin^4 phi, cos 2psi) -> composition.  sin^2(acos(c)/2) =
 // (1-c)/2 exactly, so no trigonometry is needed.
-__device__ __forceinline__ void angles_to_fr(double sphi4, double c2psi, double f[3])
-{
-    const double sphi2 = fast_sqrt(sphi4);
-    const double spsi2 = 0.5 * (1.0 - c2psi);
-    const double cpsi2 = 1.0 - spsi2;
-    f[0] = fabs(sphi2 * cpsi2);
-    f[1] = fabs(sphi2 * spsi2);
-    f[2] = fabs(1.0 - sphi2);
-}
+using gfel::angles_to_fr;                                   // gf_elements.hpp: shared with the element-space transform
 
 // golemflavor/fr.py:502-536 u_to_fr: out_b = sum_a sum_i |U_ai|^2 |U_bi|^2 src_a / sum(src) = (P P^T s)_b with P = |U|^2 and
 // s = src / sum(src).  The rows and columns of P sum to one, so its e and mu rows carry everything:

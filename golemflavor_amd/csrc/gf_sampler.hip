@@ -32,6 +32,7 @@
 #include "gf_launch.h"
 #include "gf_region.h"
 #include "gf_marginal.h"
+#include "gf_elements.h"
 #include "gf_unitarity_teams.hpp"      // Team9: the reference's unitarity chain on nine lanes (k_stretch_chain settles its own parked proposals)
 #include "gf_propose.hpp"               // philox_block, proposal_lnprob: shared with the nested sampler (gf_nested.hip)
 
@@ -2047,6 +2048,29 @@ int gf_sampler_marginals(gf_sampler* s, gf_model* const* models, int with_fr, co
     rc = gf_sampler_postprocess_rows_device(s, models, d_rows);
     if (rc == GF_OK) rc = gf_marginal_run(st, d_rows, per_chain * width, s->nchains, per_chain, width, spec, out);
     (void)hipFree(d_rows);
+    return rc;
+}
+
+// The marginals of every stored chain in element space (gf_elements.hip): the chains are transformed into a buffer of the
+// library's cache, which is reduced in place of the chain; the stored chain is only read and the rows never leave the device.
+int gf_sampler_element_marginals(gf_sampler* s, const gf_element_plan* plan, const gf_marginal_spec* spec, const gf_marginal_out* out)
+{
+    if (!s || !out) return GF_ERR_INVALID_ARG;
+    const int width = gf_element_plan_width(plan, s->ndim);
+    if (width < 0) return GF_ERR_INVALID_ARG;
+    const int64_t per_chain = s->nstored * s->nwalkers;
+    int rc = gf_marginal_check_args(s->nchains, per_chain, width, spec);
+    if (rc != GF_OK) return rc;
+    GF_HIP(hipSetDevice(s->device));
+    hipStream_t st = s->stream;
+    double* d_rows = nullptr;
+    const size_t n = (size_t)per_chain * width * s->nchains;
+    GF_HIP(hipMalloc((void**)&d_rows, sizeof(double) * (n ? n : 1)));
+    const hipError_t e = gf_element_run(st, s->d_chain, s->nstore_cap * s->nwalkers * s->ndim, s->nchains, per_chain, s->ndim, plan, d_rows,
+                                        per_chain * width, s->cus);
+    if (e == hipSuccess) rc = gf_marginal_run(st, d_rows, per_chain * width, s->nchains, per_chain, width, spec, out);
+    (void)hipFree(d_rows);
+    if (e != hipSuccess) return gf_hip_fail(e, "gf_sampler_element_marginals");
     return rc;
 }
 

@@ -519,13 +519,22 @@ class DeviceEnsembleSampler:
         res = contour.run_region_call(call, "gf_sampler_regions", self.nchains, nb, coverage, hist_smooth, truncate, cap)
         return contour.shape_results(res, scalar, self.nchains == 1)
 
-    def marginals(self, ranges=None, with_fr=False, models=None, names=None, **kw):
+    def marginals(self, ranges=None, with_fr=False, models=None, names=None, space="theta", llh_paramset=None, round32=True, **kw):
         """The posterior marginals of the stored samples (`marginals.chain_marginals`'s reduction and keyword arguments:
         bins_1d, bins_2d, coverage, percentiles, ranks, hist_smooth, truncate, cap_2d) for every chain at once, the chain
         staying on the device.  with_fr: the rows a scan saves -- composition (NaN where the reference would have raised), then
         the sample -- propagated with `models` as in `postprocess`.  ranges: (width, 2); default: the box of the sampled model's
         descriptor, and (0, 1) for the composition columns.  Returns a `marginals.MarginalResult`, a list of them over the
-        chains when nchains > 1."""
+        chains when nchains > 1.
+
+        space="elements": the marginals of the chain in element space instead (`elements.element_plan(llh_paramset, round32)`:
+        moduli |U_ij| and source composition in place of the angle projections, plot.chainer_plot's --plot-elements table);
+        the stored chain is transformed on the device into a buffer of the library's and is itself left as it is.  names and
+        ranges default to the plan's; with_fr does not combine with it."""
+        if space not in ("theta", "elements"):
+            raise ValueError("space must be 'theta' or 'elements'")
+        if space == "elements":
+            return self._element_marginals(ranges, with_fr, models, names, llh_paramset, round32, kw)
         from . import marginals as mg
         C = self._C
         handles = None
@@ -546,6 +555,26 @@ class DeviceEnsembleSampler:
         def call(spec, out):
             return self._L.gf_sampler_marginals(self._h, handles, int(bool(with_fr)), spec, out)
         res = mg.run_marginal_call(call, "gf_sampler_marginals", self.nchains, prep, cap_2d)
+        return res[0] if self.nchains == 1 else res
+
+    def _element_marginals(self, ranges, with_fr, models, names, llh_paramset, round32, kw):
+        from . import elements as el
+        from . import marginals as mg
+        if with_fr:
+            raise ValueError("space='elements' does not combine with with_fr: the element-space row carries the source composition")
+        if models is not None:
+            raise ValueError("space='elements' propagates nothing: it takes no post-processing models")
+        if llh_paramset is None:
+            raise ValueError("space='elements' needs llh_paramset, the set the chain was sampled over")
+        if len(llh_paramset) != self.dim:
+            raise ValueError("llh_paramset has %d parameters, the chain %d columns" % (len(llh_paramset), self.dim))
+        plan, pnames, pranges = el.element_plan(llh_paramset, round32)
+        cap_2d = kw.pop("cap_2d", None)
+        prep = mg.prepare(len(pnames), pranges if ranges is None else ranges, pnames if names is None else names, **kw)
+
+        def call(spec, out):
+            return self._L.gf_sampler_element_marginals(self._h, self._C.byref(plan), spec, out)
+        res = mg.run_marginal_call(call, "gf_sampler_element_marginals", self.nchains, prep, cap_2d)
         return res[0] if self.nchains == 1 else res
 
     @property
@@ -631,7 +660,14 @@ class DeviceEnsembleSampler:
             pass
 
 
-def mcmc(p0, ln_prob, ndim, nwalkers, burnin, nsteps, threads=1, device_resident=None, seed=None):
+def element_marginals_file(outfile):
+    """<outfile>_elements.npz beside the chain file <outfile>.npy (the reference exports its plot to <outfile>_elements.<format>)"""
+    stem = outfile[:-4] if outfile.endswith('.npy') else outfile
+    return stem + '_elements.npz'
+
+
+def mcmc(p0, ln_prob, ndim, nwalkers, burnin, nsteps, threads=1, device_resident=None, seed=None, plot_elements=False,
+         llh_paramset=None, outfile=None):
     """Run the MCMC: burn-in, reset, production; returns samples reshaped to (-1, ndim).
 
     Same signature, prints and return as golemflavor/mcmc.py:27-53.  When `ln_prob` is a
@@ -640,7 +676,13 @@ def mcmc(p0, ln_prob, ndim, nwalkers, burnin, nsteps, threads=1, device_resident
     forces the host-driven sampler (one launch + PCIe round trip per half-ensemble), which is also
     what any plain Python callable gets.  `seed` keys the device sampler's Philox stream (default:
     drawn from numpy's global RNG, so `np.random.seed(args.seed)` makes runs reproducible as in the
-    reference's scripts)."""
+    reference's scripts).
+
+    plot_elements (args.plot_elements) with llh_paramset and outfile: where the device-resident sampler ran, the marginals of the
+    chain in element space (`DeviceEnsembleSampler.marginals(space="elements")`, the numbers behind the triangle plot.chainer_plot
+    draws for --plot-elements) are saved as <outfile>_elements.npz, `MarginalResult.as_arrays()`, while the chain is on the device."""
+    if plot_elements and (llh_paramset is None or outfile is None):
+        raise ValueError("plot_elements needs llh_paramset and outfile")
     if device_resident is None:
         device_resident = hasattr(getattr(ln_prob, "model", None), "_h")
     if seed is None:
@@ -673,6 +715,13 @@ def mcmc(p0, ln_prob, ndim, nwalkers, burnin, nsteps, threads=1, device_resident
     except Exception:
         print('WARNING : NEED TO RUN MORE SAMPLES')
 
+    if plot_elements and device_resident:
+        of = element_marginals_file(outfile)
+        if os.path.dirname(of):
+            os.makedirs(os.path.dirname(of), exist_ok=True)
+        print('Saving element-space marginals to location {0}'.format(of))
+        sampler.marginals(space="elements", llh_paramset=llh_paramset).save(of)
+
     return samples
 
 
@@ -698,7 +747,9 @@ def _seed_type(text):
 def mcmc_argparse(parser):
     """The sampler's command-line group, as the reference's scripts compose it (golemflavor/mcmc.py:56-85: same flags,
     types and defaults): --run-mcmc, --burnin 100, --nwalkers 60, --nsteps 2000, --mcmc-seed-type uniform|gaussian,
-    --plot-angles, --plot-elements (the plotting flags are accepted and carried; plotting is out of scope here)."""
+    --plot-angles, --plot-elements.  Drawing is out of scope here: --plot-angles is accepted and carried; --plot-elements is what
+    `mcmc(..., plot_elements=args.plot_elements, llh_paramset=..., outfile=...)` takes to save the element-space marginals of the
+    chain as <outfile>_elements.npz."""
     from .enums import MCMCSeedType
     g = parser
     g.add_argument('--run-mcmc', type=_flag, default=True, help='Run the MCMC')

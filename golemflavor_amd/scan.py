@@ -292,6 +292,13 @@ class RegionWriter:
                              "thres_min": np.min(self.thres, axis=0).tolist(), "thres_max": np.max(self.thres, axis=0).tolist()})
 
 
+def _point_paramset(a, pts):
+    """grid index -> the paramset the point's chain is sampled over (--elements)"""
+    if a.config == "C4":
+        return lambda g: _TexturePoint.descriptors(pts[g], a.dimension, Texture[a.texture])[0]
+    return lambda g: _SensPoint.descriptor(pts[g])[0]
+
+
 MARGINAL_STATS = {}   # the last run_points call with marginals: what --marginals computed on this rank (reported by main)
 
 
@@ -299,10 +306,12 @@ class MarginalWriter:
     """--marginals: the posterior marginals of every grid point's saved rows (`DeviceEnsembleSampler.marginals`: 1-D and 2-D
     histograms over the sampled model's box, (0, 1) for the composition columns, their credible regions, percentiles, mean and
     covariance), computed while the point's sampler still holds its chain and saved as marginals_<point file name>.npz beside the
-    chain file; the arrays are `marginals.MarginalResult.as_arrays()`."""
+    chain file; the arrays are `marginals.MarginalResult.as_arrays()`.  elements (--elements): a function grid index -> the
+    paramset the point's chain is sampled over; the marginals of the chain in element space (`elements.element_plan` of the
+    point's own paramset, ranges included) are then saved as marginals_elements_<point file name>.npz as well."""
 
-    def __init__(self, datadir, name_of, bins_1d=100, bins_2d=50, coverage=(90., 99.), percentiles=(5., 50., 95.)):
-        self.datadir, self.name_of = datadir, name_of
+    def __init__(self, datadir, name_of, bins_1d=100, bins_2d=50, coverage=(90., 99.), percentiles=(5., 50., 95.), elements=None):
+        self.datadir, self.name_of, self.elements = datadir, name_of, elements
         self.kw = dict(bins_1d=int(bins_1d), bins_2d=int(bins_2d), coverage=[float(c) for c in coverage],
                        percentiles=[float(q) for q in percentiles])
         self.seconds, self.points = 0.0, 0
@@ -314,6 +323,18 @@ class MarginalWriter:
         for g, r in zip(order, [res] if len(order) == 1 else res):
             r.save(os.path.join(self.datadir, "marginals_%s.npz" % self.name_of(g)))
             self.points += 1
+        if self.elements is not None:
+            # one call per distinct set of ranges among the sampler's chains (a stacked C5 scan holds dimension-3 and dimension-6
+            # points, whose logLam ranges differ); every call reduces all chains, a point's file comes from its own set's call
+            sets = {}
+            for k, g in enumerate(order):
+                ps = self.elements(g)
+                sets.setdefault(tuple(map(tuple, ps.ranges)), (ps, []))[1].append((k, g))
+            for ps, members in sets.values():
+                res = sampler.marginals(space="elements", llh_paramset=ps, **self.kw)
+                res = [res] if len(order) == 1 else res
+                for k, g in members:
+                    res[k].save(os.path.join(self.datadir, "marginals_elements_%s.npz" % self.name_of(g)))
         self.seconds += time.perf_counter() - t0
         MARGINAL_STATS.clear()
         MARGINAL_STATS.update({"bins": [self.kw["bins_1d"], self.kw["bins_2d"]], "points": self.points, "seconds": round(self.seconds, 4)})
@@ -746,11 +767,16 @@ def main(argv=None):
     ap.add_argument("--marginals", action="store_true",
                     help="also save every grid point's posterior marginals (histograms, credible regions, percentiles, moments), "
                          "marginals_<point>.npz beside the chain file; needs --datadir")
+    ap.add_argument("--elements", action="store_true",
+                    help="with --marginals: also save every grid point's marginals in element space (moduli |U_ij| in place of the "
+                         "mixing columns, plot.chainer_plot's --plot-elements table), marginals_elements_<point>.npz")
     ap.add_argument("--marginal-bins-1d", type=int, default=100)
     ap.add_argument("--marginal-bins-2d", type=int, default=50)
     ap.add_argument("--marginal-coverage", type=float, nargs="+", default=[90., 99.], metavar="COVERAGE")
     ap.add_argument("--marginal-percentiles", type=float, nargs="+", default=[5., 50., 95.], metavar="Q")
     a = ap.parse_args(argv)
+    if a.elements and not a.marginals:
+        ap.error("--elements needs --marginals (it adds the element-space marginals to them)")
     if a.marginals:
         if not a.datadir:
             ap.error("--marginals needs --datadir (the marginals are saved beside the chain files)")
@@ -814,7 +840,7 @@ def main(argv=None):
     marginal_writer = None
     if a.marginals:
         marginal_writer = MarginalWriter(a.datadir, lambda g: point_filename(a.config, pts[g], a), a.marginal_bins_1d, a.marginal_bins_2d,
-                                         a.marginal_coverage, a.marginal_percentiles)
+                                         a.marginal_coverage, a.marginal_percentiles, elements=_point_paramset(a, pts) if a.elements else None)
     region_stats_wanted = regions is not None
     if marginal_writer is not None:
         regions = _Takers([t for t in (regions, marginal_writer) if t is not None])

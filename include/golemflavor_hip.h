@@ -438,6 +438,42 @@ int gf_marginals(gf_model* m, const double* rows, int64_t nrows, int width, cons
  * propagated with models[ch], NULL = the sampling models), width = 3 + ndim.  The rows stay on the device. */
 int gf_sampler_marginals(gf_sampler* s, gf_model* const* models, int with_fr, const gf_marginal_spec* spec, const gf_marginal_out* out);
 
+/* ---- rows in element space (golemflavor/plot.py:528-567, chainer_plot's --plot-elements table) ------------------------------- */
+/* A row of sampled columns turned into the row the reference plots for --plot-elements: the four mixing columns (s12^2, c13^4,
+ * s23^2, delta) become the nine moduli |U_ij| in row-major order e1 ... tau3 (fr.py:165-167 flat_angles_to_u: abs(angles_to_u(x))
+ * cast to float32), the two source columns (sin^4 phi, cos 2psi) become the composition (phi_e, phi_mu, phi_tau) (fr.py:82-113
+ * angles_to_fr, no cast), every other column is copied.  The plan lists the output row's groups in output order; which columns
+ * form a group is the caller's choice (golemflavor_amd.elements.element_plan states this package's rule).
+ *   GF_ELEMENT_COPY  col[0]      -> 1 value
+ *   GF_ELEMENT_U9    col[0..3]   -> 9 values; each entry's real and imaginary parts are formed, then the modulus; a NaN, one of
+ *                                   the first three outside [0, 1] or |delta| >= 1.6e6 gives NaN in all nine; round32 != 0 writes
+ *                                   the reference's table, float32 values: (double)(float)v of the fp64 modulus v (absolute error
+ *                                   of a few 1e-16), and for rows with a modulus below 2^-20, where that error exceeds a float32
+ *                                   step, the float32 rounding of the modulus by the reference's own 80-bit route; 0 keeps the
+ *                                   fp64 value v in every row
+ *   GF_ELEMENT_FR3   col[0..1]   -> 3 values; a NaN in either column gives NaN in all three
+ * 1 <= ngroups <= GF_ELEMENT_MAX_WIDTH, every column in [0, width_in), 1 <= width_in <= GF_MAX_DIM and an output row of at most
+ * GF_ELEMENT_MAX_WIDTH values (what gf_marginals* reduces); anything else: GF_ERR_INVALID_ARG. */
+#define GF_ELEMENT_MAX_WIDTH (GF_MAX_DIM + 3)
+enum { GF_ELEMENT_COPY = 0, GF_ELEMENT_U9 = 1, GF_ELEMENT_FR3 = 2 };
+typedef struct gf_element_group {
+    int32_t kind;
+    int32_t col[4];
+} gf_element_group;
+typedef struct gf_element_plan {
+    int32_t ngroups, round32;
+    gf_element_group group[GF_ELEMENT_MAX_WIDTH];
+} gf_element_plan;
+/* the plan's output width for rows of width_in columns; < 0: the plan is invalid */
+int gf_element_plan_width(const gf_element_plan* plan, int width_in);
+/* device rows d_in [nrows][width_in] -> d_out [nrows][width_out], both 8-byte aligned and not overlapping; synchronous */
+int gf_element_rows_device(gf_model* m, const double* d_in, int64_t nrows, int width_in, const gf_element_plan* plan, double* d_out);
+/* host rows: upload, the same path, download */
+int gf_element_rows(gf_model* m, const double* rows, int64_t nrows, int width_in, const gf_element_plan* plan, double* out);
+/* the stored chains of a sampler [nchains][nstored * nwalkers][ndim], transformed into a device buffer the library owns and reduced
+ * by gf_marginals_device's path with width = the plan's output width; only the results come back, the stored chain is not touched */
+int gf_sampler_element_marginals(gf_sampler* s, const gf_element_plan* plan, const gf_marginal_spec* spec, const gf_marginal_out* out);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI -------------------------------------- */
 /* Independent chains (grid points) shard across ranks with no data-path collective; the only
  * exchanges are the broadcast of the packed descriptors at start and the gather of the chain blocks
