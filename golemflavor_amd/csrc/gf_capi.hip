@@ -22,12 +22,11 @@
 
 #include "../../include/golemflavor_hip.h"
 #include "gf_consts.h"
+#include "gf_internal.h"                // every internal function defined here is compiled against the declaration its callers see
 #include "gf_launch.h"
 #include "gf_devcache.h"                // large device allocations are cached, not handed back to the driver (hipMalloc / hipFree are macros from here on)
 
 static_assert(GF_MAX_DIM == 16 && GF_MAX_BINS == 64, "header / device constant mismatch");
-
-extern "C" const char* gf_internal_env(const char* name, int affects_results);
 
 namespace {
 

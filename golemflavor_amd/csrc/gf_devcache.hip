@@ -1,13 +1,12 @@
 // gf_devcache.hip -- see gf_devcache.h
 #define GF_DEVCACHE_IMPL
 #include "gf_devcache.h"
+#include "gf_internal.h"
 
 #include <cstdlib>
 #include <mutex>
 #include <unordered_map>
 #include <vector>
-
-extern "C" const char* gf_internal_env(const char* name, int affects_results);
 
 namespace {
 constexpr size_t GF_DEVCACHE_MIN = (size_t)64 << 20;        // smaller buffers are freed as before (their wipe takes microseconds)

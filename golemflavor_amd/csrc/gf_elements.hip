@@ -13,10 +13,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gf_devcache.h"
+#include "gf_host.h"                    // (after gf_devcache.h: GfScratch allocates through the cache)
 #include "gf_elements.h"
 #include "gf_elements_exact.hpp"
-#include "gf_host.h"
-#include "gf_devcache.h"
 
 namespace {
 
@@ -120,8 +120,9 @@ hipError_t gf_element_run(hipStream_t st, const double* d_in, int64_t in_stride,
     if (blocks > cap) blocks = cap;
     const dim3 grid((unsigned)blocks, 1u, (unsigned)nchains), block((unsigned)(waves * EL_WAVE));
     const size_t lds = lds_wave * waves;
+    GfScratch buf;
     unsigned long long* d_mask = nullptr;
-    hipError_t e = hipMalloc((void**)&d_mask, sizeof(unsigned long long) * (size_t)ntiles * nchains);
+    hipError_t e = buf.get(&d_mask, sizeof(unsigned long long) * (size_t)ntiles * nchains);
     if (e != hipSuccess) return e;
     // a tile's span starts a multiple of 512 width bytes behind its chain's first row
     const bool vec = el_aligned16(d_in) && el_aligned16(d_out) && (nchains == 1 || (in_stride % 2 == 0 && out_stride % 2 == 0));
@@ -138,7 +139,6 @@ hipError_t gf_element_run(hipStream_t st, const double* d_in, int64_t in_stride,
         e = hipGetLastError();
     }
     const hipError_t e2 = hipStreamSynchronize(st);
-    (void)hipFree(d_mask);
     return e == hipSuccess ? e2 : e;
 }
 
@@ -170,16 +170,15 @@ int gf_element_rows(gf_model* m, const double* rows, int64_t nrows, int width_in
     if (rc != GF_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     const size_t nin = sizeof(double) * (size_t)nrows * width_in, nout = sizeof(double) * (size_t)nrows * wout;
+    GfScratch buf;
     double *d_in = nullptr, *d_out = nullptr;
-    hipError_t e = hipMalloc((void**)&d_in, nin);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_out, nout);
+    hipError_t e = buf.get(&d_in, nin);
+    if (e == hipSuccess) e = buf.get(&d_out, nout);
     if (e == hipSuccess) e = hipMemcpyAsync(d_in, rows, nin, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e == hipSuccess) rc = gf_element_rows_device(m, d_in, nrows, width_in, plan, d_out);
     if (e == hipSuccess && rc == GF_OK) e = hipMemcpyAsync(out, d_out, nout, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && rc == GF_OK) e = hipStreamSynchronize(st);
-    if (d_in) (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
     if (e != hipSuccess) return gf_hip_fail(e, "gf_element_rows");
     return rc;
 }

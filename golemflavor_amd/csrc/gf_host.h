@@ -1,6 +1,7 @@
-// Host pieces shared by the C ABI of the device samplers (gf_sampler.hip, gf_nested.hip, gf_simplex.hip): the accessors
-// gf_capi.hip implements (gf_model is private to it), the error helpers that publish a message through gf_last_hip_error(), and
-// the allocation of the arbitration queue their settle kernels share.
+// Host pieces shared by the C ABI of the device samplers and of chain post-processing (gf_sampler.hip, gf_postprocess.hip, gf_nested.hip,
+// gf_simplex.hip, gf_region.hip, gf_marginal.hip, gf_elements.hip): the library's internal functions (gf_internal.h), the error
+// helpers that publish a message through gf_last_hip_error(), the holder of a call's scratch buffers, and the allocation of the
+// arbitration queue the settle kernels share.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -9,20 +10,12 @@
 #include <cstddef>
 #include <cstdio>
 #include <cstring>
+#include <vector>
 
 #include "../../include/golemflavor_hip.h"
 #include "gf_consts.h"
+#include "gf_internal.h"
 #include "gf_launch.h"
-
-extern "C" {
-const char* gf_internal_env(const char* name, int affects_results);   // getenv with a record
-int gf_model_internal(gf_model* m, const GfCommon** c, const GfBsm** d_bsm, const double** d_ptab, void** stream, int* device);
-int gf_model_constants(gf_model* m, const GfCommon** c, const GfBsm** d_bsm, const double** d_ptab, int* device, int* cus,
-                       int* nbins);
-void gf_internal_set_error(const char* msg);
-int gf_model_lnprob_on(gf_model* m, void* stream, const double* d_theta, int layout, int64_t n, double* d_lnprob,
-                       double* d_fr, int32_t* d_status);
-}
 
 namespace {
 // "what: <HIP's message>" as the last error; returns GF_ERR_HIP
@@ -45,6 +38,23 @@ __attribute__((format(printf, 2, 3))) inline int gf_fail_msg(int rc, const char*
     gf_internal_set_error(msg);
     return rc;
 }
+
+// The device scratch buffers of one call, released together when the holder goes out of scope, in the order they were taken (the
+// order decides which cached block a later request of the same size reuses).  Not for buffers an object owns across calls.
+// hipMalloc / hipFree are the including file's (gf_devcache.h's where that comes first).
+struct GfScratch {
+    std::vector<void*> p;
+    template <typename T>
+    hipError_t get(T** out, size_t bytes)
+    {
+        void* q = nullptr;
+        const hipError_t e = hipMalloc(&q, bytes ? bytes : 8);
+        if (e == hipSuccess) p.push_back(q);
+        *out = static_cast<T*>(q);
+        return e;
+    }
+    ~GfScratch() { for (void* q : p) (void)hipFree(q); }
+};
 
 // BSM: the arbitration queue for `w` parked proposals, empty, with their rows [w][GF_PEND_STRIDE] and the settle kernel's
 // per-proposal counters [w][2], zero; synchronous on return.  hipMalloc is the including file's (gf_devcache.h's where that

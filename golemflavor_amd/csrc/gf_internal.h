@@ -1,0 +1,50 @@
+// gf_internal.h -- the library's internal functions: everything one translation unit defines and another calls that is not in
+// include/golemflavor_hip.h.  Declarations only; the defining file includes this header too, so that every definition is compiled
+// against the declaration its callers see.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/golemflavor_hip.h"
+#include "gf_consts.h"
+
+extern "C" {
+// gf_capi.hip
+const char* gf_internal_env(const char* name, int affects_results);   // getenv with a record
+void gf_internal_set_error(const char* msg);                          // the text gf_last_hip_error() returns
+// gf_model is private to gf_capi.hip: its constants, and (gf_model_internal: sets the device, gives the model a stream) its stream
+int gf_model_internal(gf_model* m, const GfCommon** c, const GfBsm** d_bsm, const double** d_ptab, void** stream, int* device);
+int gf_model_constants(gf_model* m, const GfCommon** c, const GfBsm** d_bsm, const double** d_ptab, int* device, int* cus, int* nbins);
+// the model's kernels on a stream of the caller's
+int gf_model_lnprob_on(gf_model* m, void* stream, const double* d_theta, int layout, int64_t n, double* d_lnprob, double* d_fr, int32_t* d_status);
+int gf_model_propagate_on(gf_model* m, void* stream, const double* d_theta, int layout, int64_t n, double* d_fr, int32_t* d_status);
+// streams of the device's pool (copy stream: for a large read-back that overlaps another stream's kernels); returned idle
+int gf_internal_borrow_stream(int device, void** stream);
+void gf_internal_return_stream(int device, void* stream);
+int gf_internal_borrow_copy_stream(int device, void** stream);
+void gf_internal_return_copy_stream(int device, void* stream);
+// while `on`, every arbitration launch on `stream` takes the full grid whatever the previous one found
+void gf_internal_full_arbitration_grids(int device, void* stream, int on);
+// GF_ERR_QUEUE_OVERFLOW if an arbitration queue dropped a pair in the launches on `stream`, which has just been synchronised
+int gf_internal_check_overflow(int device, void* stream);
+// device -> host through the pinned ring and the host copy threads.  gated: a chunk is issued once gate(ctx, upto) has returned 0
+// for the source bytes [0, upto) it ends in; 2d: `height` rows of `width` bytes; pipe: one pipeline kept open over many 2d copies
+int gf_internal_d2h(int device, void* stream, void* dst_host, const void* src_dev, size_t bytes);
+int gf_internal_d2h_gated(int device, void* stream, void* dst_host, const void* src_dev, size_t bytes, int (*gate)(void* ctx, size_t upto), void* gate_ctx);
+int gf_internal_d2h_2d(int device, void* stream, void* dst_host, size_t dpitch, const void* src_dev, size_t spitch, size_t width, size_t height);
+struct gf_d2h_pipe;
+int gf_internal_d2h_pipe_open(int device, void* stream, gf_d2h_pipe** out);
+int gf_internal_d2h_pipe_rows(gf_d2h_pipe* p, void* dst_host, size_t dpitch, const void* src_dev, size_t spitch, size_t width, size_t height);
+int gf_internal_d2h_pipe_close(gf_d2h_pipe* p);
+
+// gf_sampler.hip
+struct GfChainView {              // the stored chain of a sampler, as post-processing (gf_postprocess.hip) sees it
+    int device; hipStream_t stream; int cus;
+    int nchains, nwalkers, ndim;
+    int64_t nstored, nstore_cap;
+    const double* d_chain;        // [nchains][nstore_cap][nwalkers][ndim]
+    gf_model* model; gf_model* const* models;   // chain 0's, and one per chain or NULL
+};
+int gf_internal_sampler_chain_view(const gf_sampler* s, GfChainView* v);
+}

@@ -22,10 +22,10 @@
 #include <type_traits>
 #include <vector>
 
-#include "gf_host.h"
+#include "gf_devcache.h"
+#include "gf_host.h"                    // (after gf_devcache.h: GfScratch allocates through the cache)
 #include "gf_marginal.h"
 #include "gf_region.h"
-#include "gf_devcache.h"
 
 namespace {
 
@@ -366,20 +366,6 @@ hipError_t mg_by_width(int W, F&& f)
     return f(std::integral_constant<int, MG_MAXW>());
 }
 
-struct MgBuf {                                                      // device allocations of one call, freed together
-    std::vector<void*> p;
-    template <typename T>
-    hipError_t get(T** out, size_t bytes)
-    {
-        void* q = nullptr;
-        const hipError_t e = hipMalloc(&q, bytes ? bytes : 8);
-        if (e == hipSuccess) p.push_back(q);
-        *out = static_cast<T*>(q);
-        return e;
-    }
-    ~MgBuf() { for (void* q : p) (void)hipFree(q); }
-};
-
 }  // namespace
 
 int gf_marginal_check_args(int nchains, int64_t nrows, int W, const gf_marginal_spec* sp)
@@ -422,7 +408,7 @@ int gf_marginal_run(hipStream_t st, const double* d_rows, int64_t chain_stride, 
     const int nb1 = sp->nbins1, nb2 = sp->nbins2, npairs = W * (W - 1) / 2, R = sp->nranks + 2 * sp->nq;
     const size_t n_c1 = (size_t)nchains * W * nb1, n_c2 = (size_t)nchains * npairs * nb2 * nb2;
     const int64_t nchunks = std::max<int64_t>(1, (nrows + MG_CHUNK - 1) / MG_CHUNK);
-    MgBuf buf;
+    GfScratch buf;
     double *d_e1 = nullptr, *d_e2 = nullptr, *d_part = nullptr, *d_sum = nullptr, *d_mean = nullptr, *d_part2 = nullptr, *d_sum2 = nullptr, *d_cov = nullptr;
     unsigned long long *d_c1 = nullptr, *d_c2 = nullptr, *d_nvalid = nullptr, *d_ncol = nullptr;
     hipError_t e = buf.get(&d_e1, sizeof(double) * W * (nb1 + 2));
@@ -610,15 +596,14 @@ int gf_marginals(gf_model* m, const double* rows, int64_t nrows, int width, cons
     rc = gf_model_internal(m, &c, &tb, &ptab, &stream, &device);
     if (rc != GF_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
+    GfScratch buf;
     double* d_rows = nullptr;
     const size_t bytes = sizeof(double) * (size_t)nrows * width;
-    hipError_t e = hipMalloc((void**)&d_rows, bytes ? bytes : 8);
+    hipError_t e = buf.get(&d_rows, bytes);
     if (e == hipSuccess && bytes) e = hipMemcpyAsync(d_rows, rows, bytes, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e == hipSuccess) rc = gf_marginal_run(st, d_rows, nrows * width, 1, nrows, width, spec, out);
-    if (d_rows) (void)hipFree(d_rows);
     if (e != hipSuccess) return gf_hip_fail(e, "gf_marginals");
-    return rc;
+    return gf_marginal_run(st, d_rows, nrows * width, 1, nrows, width, spec, out);
 }
 
 }  // extern "C"

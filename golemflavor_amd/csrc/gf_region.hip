@@ -20,9 +20,9 @@
 #include <limits>
 #include <vector>
 
-#include "gf_host.h"
-#include "gf_region.h"
 #include "gf_devcache.h"
+#include "gf_host.h"                    // (after gf_devcache.h: GfScratch allocates through the cache)
+#include "gf_region.h"
 
 namespace {
 
@@ -356,14 +356,15 @@ int gf_region_run_shape(hipStream_t st, const uint64_t* d_counts, int nchains, i
 
     // one small block: sums [nchains][2] | nnz [nchains] | cursor [nchains] | thres [nres] | level_in | level_out | mass [nres] | saturated [nres]
     const size_t n_u64 = (size_t)4 * nchains, small_bytes = 8 * (n_u64 + (size_t)4 * nres) + 4 * (size_t)nres;
+    GfScratch buf;
     unsigned char* d_small = nullptr;
     double *d_x = nullptr, *d_y = nullptr, *d_vals = nullptr;
     int32_t* d_idx = nullptr;
     std::vector<unsigned char> h_small(small_bytes);
-    hipError_t e = hipMalloc((void**)&d_small, small_bytes);
+    hipError_t e = buf.get(&d_small, small_bytes);
     if (e == hipSuccess) e = hipMemsetAsync(d_small, 0, small_bytes, st);
-    if (e == hipSuccess && !d_smoothed) e = hipMalloc((void**)&d_y, sizeof(double) * (size_t)ncells);
-    if (e == hipSuccess && naxes > 0) e = hipMalloc((void**)&d_x, sizeof(double) * (size_t)ncells);
+    if (e == hipSuccess && !d_smoothed) e = buf.get(&d_y, sizeof(double) * (size_t)ncells);
+    if (e == hipSuccess && naxes > 0) e = buf.get(&d_x, sizeof(double) * (size_t)ncells);
     unsigned long long* d_sums = reinterpret_cast<unsigned long long*>(d_small);
     unsigned long long* d_nnz = d_sums + 2 * (size_t)nchains;
     unsigned long long* d_cursor = d_nnz + nchains;
@@ -416,8 +417,8 @@ int gf_region_run_shape(hipStream_t st, const uint64_t* d_counts, int nchains, i
     if (e == hipSuccess && rc == GF_OK) {
         N = RG_TILE;
         while (N < maxnnz) N <<= 1;
-        e = hipMalloc((void**)&d_vals, sizeof(double) * (size_t)N * nchains);
-        if (e == hipSuccess) e = hipMalloc((void**)&d_idx, sizeof(int32_t) * (size_t)N * nchains);
+        e = buf.get(&d_vals, sizeof(double) * (size_t)N * nchains);
+        if (e == hipSuccess) e = buf.get(&d_idx, sizeof(int32_t) * (size_t)N * nchains);
     }
     if (e == hipSuccess && rc == GF_OK) {
         const int64_t all = N * nchains;
@@ -463,13 +464,14 @@ int gf_region_run_shape(hipStream_t st, const uint64_t* d_counts, int nchains, i
             }
         if (one_list && cap > 0 && (cells || density) && e == hipSuccess) {
             // cells / density are host arrays [nchains][cap]: gather on the device, then one copy each
+            GfScratch gathered;
             long long* d_take = nullptr;
             int32_t* d_cells = nullptr;
             double* d_dens = nullptr;
             const size_t nout = (size_t)nchains * (size_t)cap;
-            e = hipMalloc((void**)&d_take, sizeof(long long) * nchains);
-            if (e == hipSuccess && cells) e = hipMalloc((void**)&d_cells, sizeof(int32_t) * nout);
-            if (e == hipSuccess && density) e = hipMalloc((void**)&d_dens, sizeof(double) * nout);
+            e = gathered.get(&d_take, sizeof(long long) * nchains);
+            if (e == hipSuccess && cells) e = gathered.get(&d_cells, sizeof(int32_t) * nout);
+            if (e == hipSuccess && density) e = gathered.get(&d_dens, sizeof(double) * nout);
             if (e == hipSuccess && d_cells) e = hipMemsetAsync(d_cells, 0xff, sizeof(int32_t) * nout, st);           // -1 past the list
             if (e == hipSuccess && d_dens) e = hipMemsetAsync(d_dens, 0, sizeof(double) * nout, st);
             if (e == hipSuccess) e = hipMemcpyAsync(d_take, h_take.data(), sizeof(long long) * nchains, hipMemcpyHostToDevice, st);
@@ -482,20 +484,12 @@ int gf_region_run_shape(hipStream_t st, const uint64_t* d_counts, int nchains, i
             if (e == hipSuccess && density) e = hipMemcpyAsync(density, d_dens, sizeof(double) * nout, hipMemcpyDeviceToHost, st);
             const hipError_t e3 = hipStreamSynchronize(st);
             if (e == hipSuccess) e = e3;
-            if (d_take) (void)hipFree(d_take);
-            if (d_cells) (void)hipFree(d_cells);
-            if (d_dens) (void)hipFree(d_dens);
         }
         const hipError_t e2 = hipStreamSynchronize(st);
         if (e == hipSuccess) e = e2;
     } else {
         (void)hipStreamSynchronize(st);
     }
-    if (d_small) (void)hipFree(d_small);
-    if (d_x) (void)hipFree(d_x);
-    if (d_y) (void)hipFree(d_y);
-    if (d_vals) (void)hipFree(d_vals);
-    if (d_idx) (void)hipFree(d_idx);
     if (rc != GF_OK) return rc;
     if (e != hipSuccess) return gf_hip_fail(e, "flavor region");
     return GF_OK;
@@ -535,11 +529,12 @@ int gf_flavor_region(gf_model* m, const double* fr, int64_t n, int nbins, int ra
     if (rc != GF_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     const size_t nb3 = (size_t)nbins * nbins * nbins;
+    GfScratch buf;
     double* d_fr = nullptr;
     uint64_t* d_c = nullptr;
-    hipError_t e = hipMalloc((void**)&d_c, sizeof(uint64_t) * nb3);
+    hipError_t e = buf.get(&d_c, sizeof(uint64_t) * nb3);
     if (e == hipSuccess) e = hipMemsetAsync(d_c, 0, sizeof(uint64_t) * nb3, st);
-    if (e == hipSuccess && n > 0) e = hipMalloc((void**)&d_fr, sizeof(double) * 3 * (size_t)n);
+    if (e == hipSuccess && n > 0) e = buf.get(&d_fr, sizeof(double) * 3 * (size_t)n);
     if (e == hipSuccess && n > 0) e = hipMemcpyAsync(d_fr, fr, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, st);
     if (e == hipSuccess && n > 0) e = gf_launch_flavor_hist(d_fr, n, nbins, (unsigned long long*)d_c, 256, st);
     if (e == hipSuccess)
@@ -547,8 +542,6 @@ int gf_flavor_region(gf_model* m, const double* fr, int64_t n, int nbins, int ra
                            d_smoothed);
     else
         (void)hipStreamSynchronize(st);
-    if (d_fr) (void)hipFree(d_fr);
-    if (d_c) (void)hipFree(d_c);
     if (e != hipSuccess) return gf_hip_fail(e, "gf_flavor_region");
     return rc;
 }

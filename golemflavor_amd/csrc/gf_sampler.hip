@@ -30,9 +30,6 @@
 #include "gf_device.hpp"
 #include "gf_bsm_device.hpp"
 #include "gf_launch.h"
-#include "gf_region.h"
-#include "gf_marginal.h"
-#include "gf_elements.h"
 #include "gf_unitarity_teams.hpp"      // Team9: the reference's unitarity chain on nine lanes (k_stretch_chain settles its own parked proposals)
 #include "gf_propose.hpp"               // philox_block, proposal_lnprob: shared with the nested sampler (gf_nested.hip)
 
@@ -958,26 +955,6 @@ struct HostSink {
 double g_last_run_to_host_times[8] = {};
 double g_last_run_prologue[4] = {};             // the last gf_sampler_run: [0] growing the chain buffers, [1] capturing + instantiating the graph (seconds)
 
-// more of gf_capi.hip's internals (the model accessors are in gf_host.h)
-extern "C" {
-void gf_internal_full_arbitration_grids(int device, void* stream, int on);
-int gf_internal_borrow_stream(int device, void** stream);
-int gf_internal_borrow_copy_stream(int device, void** stream);
-void gf_internal_return_copy_stream(int device, void* stream);
-void gf_internal_return_stream(int device, void* stream);
-int gf_model_propagate_on(gf_model* m, void* stream, const double* d_theta, int layout, int64_t n, double* d_fr,
-                          int32_t* d_status);
-int gf_internal_check_overflow(int device, void* stream);
-int gf_internal_d2h_gated(int device, void* stream, void* dst_host, const void* src_dev, size_t bytes,
-                          int (*gate)(void* ctx, size_t upto), void* gate_ctx);
-int gf_internal_d2h_2d(int device, void* stream, void* dst_host, size_t dpitch, const void* src_dev, size_t spitch, size_t width,
-                       size_t height);
-struct gf_d2h_pipe;
-int gf_internal_d2h_pipe_open(int device, void* stream, gf_d2h_pipe** out);
-int gf_internal_d2h_pipe_rows(gf_d2h_pipe* p, void* dst_host, size_t dpitch, const void* src_dev, size_t spitch, size_t width, size_t height);
-int gf_internal_d2h_pipe_close(gf_d2h_pipe* p);
-}
-
 namespace {
 // gf_sampler_create (multi false: every chain samples models[0]) and gf_sampler_create_multi (multi true: chain ch samples
 // models[ch]): the constant tables are allocated once, with one entry per model
@@ -1038,26 +1015,6 @@ int sampler_create(gf_model* const* models, bool multi, int nchains, int nwalker
         return rc;
     }
     *out = s;
-    return GF_OK;
-}
-
-// the model chain ch is post-processed with: models[ch] if the caller gives models, else the posterior the chain samples
-gf_model* chain_model(const gf_sampler* s, gf_model* const* models, int ch)
-{
-    return models ? models[ch] : s->models ? s->models[ch] : s->model;
-}
-
-// the post-processing entry points: every chain's model must have the sampler's ndim and device.  *cus (may be NULL): the CUs
-// the last chain's model sizes its grids for
-int check_chain_models(const gf_sampler* s, gf_model* const* models, int* cus = nullptr)
-{
-    for (int ch = 0; ch < s->nchains; ++ch) {
-        const GfCommon* c; const GfBsm* tb; const double* ptab; int device, mcus, nbins;
-        if (gf_model_constants(chain_model(s, models, ch), &c, &tb, &ptab, &device, &mcus, &nbins) != GF_OK || c->ndim != s->ndim ||
-            device != s->device)
-            return GF_ERR_INVALID_ARG;
-        if (cus) *cus = mcus;
-    }
     return GF_OK;
 }
 
@@ -1700,6 +1657,14 @@ int gf_internal_sampler_shape(const gf_sampler* s, double out[3])
 int64_t gf_sampler_nstored(const gf_sampler* s) { return s ? s->nstored : -1; }
 int64_t gf_sampler_iterations(const gf_sampler* s) { return s ? s->steps_since_reset : -1; }
 
+// internal (gf_postprocess.hip): what chain post-processing needs of a sampler; gf_sampler itself stays private to this file
+int gf_internal_sampler_chain_view(const gf_sampler* s, GfChainView* v)
+{
+    if (!s || !v) return GF_ERR_INVALID_ARG;
+    *v = GfChainView{s->device, s->stream, s->cus, s->nchains, s->nwalkers, s->ndim, s->nstored, s->nstore_cap, s->d_chain, s->model, s->models};
+    return GF_OK;
+}
+
 // pos [nchains][nwalkers][ndim], lnprob [nchains][nwalkers] (either may be NULL)
 int gf_sampler_get_state(gf_sampler* s, double* pos, double* lnprob)
 {
@@ -1791,287 +1756,6 @@ int gf_sampler_walker_mean(gf_sampler* s, double* mean)
     if (e == hipSuccess) e = e2;
     if (e != hipSuccess) return gf_hip_fail(e, "gf_sampler_walker_mean");
     return GF_OK;
-}
-
-// Chain post-processing on the device (scripts/mc_unitary.py:189-193, mc_texture.py:216-221, and the
-// histogram of golemflavor/plot.py:365-370): measured composition of every stored sample, optionally
-// reduced to the [nbins]^3 flavor histogram so that only the counts cross PCIe.
-//   fr      [nchains][nstored][nwalkers][3]  or NULL
-//   status  [nchains][nstored][nwalkers]     or NULL
-//   counts  [nchains][nbins][nbins][nbins]   or NULL (nbins ignored then)
-int gf_sampler_postprocess(gf_sampler* s, double* fr, int32_t* status, int nbins, uint64_t* counts)
-{
-    return gf_sampler_postprocess_with(s, nullptr, fr, status, nbins, counts);
-}
-
-// Same, but chain ch is propagated with models[ch] instead of the posterior it was sampled from
-// (scripts/mc_texture.py: the chain samples the priors, mc_texture.py:148-170, and every sample is then pushed
-// through flux_averaged_BSMu at the grid point's scale and source, mc_texture.py:216-221).  models == NULL:
-// the sampling models.  Each model must have the sampler's ndim and device.
-// Same with DEVICE destinations: d_fr [nchains][nstored][nwalkers][3], d_status [nchains][nstored][nwalkers] (NULL = skip);
-// synchronous on return.
-int gf_sampler_postprocess_device(gf_sampler* s, gf_model* const* models, double* d_fr, int32_t* d_status)
-{
-    if (!s || !d_fr) return GF_ERR_INVALID_ARG;
-    if (check_chain_models(s, models) != GF_OK) return GF_ERR_INVALID_ARG;
-    GF_HIP(hipSetDevice(s->device));
-    hipStream_t st = s->stream;
-    const int64_t per_chain = s->nstored * s->nwalkers;
-    int rc = GF_OK;
-    // the chains are enqueued faster than they run, so the arbitration grid of each would follow what some EARLIER chain found,
-    // and the chains of a scan differ (its high-scale grid points sit in the failing region, the others have empty queues):
-    // full grids throughout, ~30 us per chain (measured: the hint left 57 of 64 chains of the C4 scan on a sixth of the
-    // GPU, 114 ms of arbitration instead of ~20)
-    gf_internal_full_arbitration_grids(s->device, st, 1);
-    for (int ch = 0; ch < s->nchains && rc == GF_OK && per_chain > 0; ++ch) {
-        const double* d_theta = s->d_chain + (size_t)ch * s->nstore_cap * s->nwalkers * s->ndim;
-        rc = gf_model_propagate_on(chain_model(s, models, ch), st, d_theta, GF_LAYOUT_AOS, per_chain, d_fr + (size_t)ch * per_chain * 3,
-                                   d_status ? d_status + (size_t)ch * per_chain : nullptr);
-    }
-    gf_internal_full_arbitration_grids(s->device, st, 0);
-    GF_HIP(hipStreamSynchronize(st));
-    if (rc == GF_OK && d_status) rc = gf_internal_check_overflow(s->device, st);
-    return rc;
-}
-
-// The scan's output rows on the device: d_rows [nchains][nstored][nwalkers][3 + ndim] = composition (NaN where the
-// reference would have raised) then the sample, each chain propagated with models[ch] (NULL: the sampling models).
-// Synchronous on return.  scripts/mc_texture.py:216-223.
-int gf_sampler_postprocess_rows_device(gf_sampler* s, gf_model* const* models, double* d_rows)
-{
-    if (!s || !d_rows) return GF_ERR_INVALID_ARG;
-    GF_HIP(hipSetDevice(s->device));
-    hipStream_t st = s->stream;
-    const int64_t per_chain = s->nstored * s->nwalkers;
-    if (per_chain == 0) { GF_HIP(hipStreamSynchronize(st)); return GF_OK; }
-    double* d_fr = nullptr;
-    int32_t* d_st = nullptr;
-    GF_HIP(hipMalloc((void**)&d_fr, sizeof(double) * 3 * per_chain * s->nchains));
-    {
-        hipError_t e_ = hipMalloc((void**)&d_st, sizeof(int32_t) * per_chain * s->nchains);
-        if (e_ != hipSuccess) { (void)hipFree(d_fr); return gf_hip_fail(e_, "hipMalloc(status)"); }
-    }
-    int rc = gf_sampler_postprocess_device(s, models, d_fr, d_st);
-    hipError_t e = hipSuccess;
-    for (int ch = 0; ch < s->nchains && rc == GF_OK && e == hipSuccess; ++ch) {
-        const double* d_theta = s->d_chain + (size_t)ch * s->nstore_cap * s->nwalkers * s->ndim;
-        e = gf_launch_join_rows(d_fr + (size_t)ch * per_chain * 3, d_st + (size_t)ch * per_chain, d_theta, s->ndim, per_chain,
-                                d_rows + (size_t)ch * per_chain * (3 + s->ndim), s->cus, st);
-    }
-    hipError_t e2 = hipStreamSynchronize(st);
-    (void)hipFree(d_fr);
-    (void)hipFree(d_st);
-    if (rc != GF_OK) return rc;
-    if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) return gf_hip_fail(e, "gf_sampler_postprocess_rows_device");
-    return GF_OK;
-}
-
-// The scan's rows straight to the host.  The chains are post-processed in turn on the sampler's stream (everything is enqueued
-// at once); an event marks the end of every group of chains, and one pinned-ring copy on a SECOND stream follows the events
-// chunk by chunk -- so the read-back of finished groups overlaps the evaluation (and the x87 arbitration, which dominates a
-// texture scan's post-processing) of the later ones.
-int gf_sampler_postprocess_rows(gf_sampler* s, gf_model* const* models, double* rows)
-{
-    if (!s || !rows) return GF_ERR_INVALID_ARG;
-    if (check_chain_models(s, models) != GF_OK) return GF_ERR_INVALID_ARG;
-    GF_HIP(hipSetDevice(s->device));
-    const int device0 = s->device;
-    hipStream_t st = s->stream;
-    const int64_t per_chain = s->nstored * s->nwalkers;
-    if (per_chain == 0) { GF_HIP(hipStreamSynchronize(st)); return GF_OK; }
-    const size_t width = 3 + (size_t)s->ndim, chain_bytes = sizeof(double) * width * (size_t)per_chain;
-    constexpr int MAX_GROUPS = 16;
-    const int per_group = (s->nchains + MAX_GROUPS - 1) / MAX_GROUPS;
-    const int ngroups = (s->nchains + per_group - 1) / per_group;
-    double *d_fr = nullptr, *d_rows = nullptr;
-    int32_t* d_st = nullptr;
-    void* copy_stream = nullptr;
-    hipEvent_t ev[MAX_GROUPS] = {};
-    int rc = GF_OK;
-    hipError_t e = hipMalloc((void**)&d_fr, sizeof(double) * 3 * per_chain * s->nchains);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_st, sizeof(int32_t) * per_chain * s->nchains);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_rows, chain_bytes * s->nchains);
-    for (int g = 0; g < ngroups && e == hipSuccess; ++g) e = hipEventCreateWithFlags(&ev[g], hipEventDisableTiming);
-    if (e == hipSuccess) rc = gf_internal_borrow_copy_stream(device0, &copy_stream);
-    if (e == hipSuccess && rc == GF_OK) {
-        gf_internal_full_arbitration_grids(device0, st, 1);      // see gf_sampler_postprocess_device
-        for (int ch = 0; ch < s->nchains && rc == GF_OK && e == hipSuccess; ++ch) {
-            const double* d_theta = s->d_chain + (size_t)ch * s->nstore_cap * s->nwalkers * s->ndim;
-            rc = gf_model_propagate_on(chain_model(s, models, ch), st, d_theta, GF_LAYOUT_AOS, per_chain, d_fr + (size_t)ch * per_chain * 3,
-                                       d_st + (size_t)ch * per_chain);
-            if (rc == GF_OK)
-                e = gf_launch_join_rows(d_fr + (size_t)ch * per_chain * 3, d_st + (size_t)ch * per_chain, d_theta, s->ndim, per_chain,
-                                        d_rows + (size_t)ch * per_chain * width, s->cus, st);
-            if (rc == GF_OK && e == hipSuccess && ((ch + 1) % per_group == 0 || ch + 1 == s->nchains))
-                e = hipEventRecord(ev[ch / per_group], st);
-        }
-        gf_internal_full_arbitration_grids(device0, st, 0);
-        // the rows cross PCIe on the copy stream through the library's pinned ring (gf_internal_d2h_gated: the DMA fills a slot
-        // while host threads empty the previous ones into `rows`, mapping its pages as they go) -- ONE pipeline over the whole
-        // block, each 16 MB chunk issued as soon as the group of chains it ends in has been post-processed on the sampler's stream
-        if (rc == GF_OK && e == hipSuccess) {
-            struct Gate { hipEvent_t* ev; size_t group_bytes; int ngroups, passed; } gt = {ev, chain_bytes * (size_t)per_group, ngroups, 0};
-            auto gate = [](void* ctx, size_t upto) -> int {
-                Gate* g = static_cast<Gate*>(ctx);
-                int need = (int)((upto + g->group_bytes - 1) / g->group_bytes);
-                if (need > g->ngroups) need = g->ngroups;
-                for (; g->passed < need; ++g->passed)
-                    if (hipEventSynchronize(g->ev[g->passed]) != hipSuccess) return 1;
-                return 0;
-            };
-            rc = gf_internal_d2h_gated(device0, copy_stream, rows, d_rows, chain_bytes * (size_t)s->nchains, gate, &gt);
-        }
-    }
-    const hipError_t e2 = hipStreamSynchronize(st);
-    if (copy_stream) { (void)hipStreamSynchronize((hipStream_t)copy_stream); gf_internal_return_copy_stream(device0, copy_stream); }
-    for (int g = 0; g < ngroups; ++g) if (ev[g]) (void)hipEventDestroy(ev[g]);
-    if (d_fr) (void)hipFree(d_fr);
-    if (d_st) (void)hipFree(d_st);
-    if (d_rows) (void)hipFree(d_rows);
-    if (rc != GF_OK) return rc;
-    if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) return gf_hip_fail(e, "gf_sampler_postprocess_rows");
-    return gf_internal_check_overflow(device0, st);
-}
-
-int gf_sampler_postprocess_with(gf_sampler* s, gf_model* const* models, double* fr, int32_t* status, int nbins,
-                                uint64_t* counts)
-{
-    if (!s || (counts && (nbins < 1 || nbins > 1024))) return GF_ERR_INVALID_ARG;
-    int cus = 256;
-    if (check_chain_models(s, models, &cus) != GF_OK) return GF_ERR_INVALID_ARG;
-    GF_HIP(hipSetDevice(s->device));
-    hipStream_t st = s->stream;
-    GF_HIP(hipStreamSynchronize(st));
-    if (s->nstored == 0) return GF_OK;
-    const int64_t per_chain = s->nstored * s->nwalkers;
-    const size_t nbin3 = counts ? (size_t)nbins * nbins * nbins : 0;
-    double* d_fr = nullptr;
-    int32_t* d_st = nullptr;
-    uint64_t* d_c = nullptr;
-    hipError_t e = hipMalloc((void**)&d_fr, sizeof(double) * 3 * per_chain);
-    if (e == hipSuccess && status) e = hipMalloc((void**)&d_st, sizeof(int32_t) * per_chain);
-    if (e == hipSuccess && counts) e = hipMalloc((void**)&d_c, sizeof(uint64_t) * nbin3);
-    int rc = GF_OK;
-    // everything in order on the sampler's stream (the one the chain was written on): propagate, histogram,
-    // copies back; the scratch buffers are reused chain after chain, one sync at the end
-    for (int ch = 0; ch < s->nchains && e == hipSuccess && rc == GF_OK; ++ch) {
-        const double* d_theta = s->d_chain + (size_t)ch * s->nstore_cap * s->nwalkers * s->ndim;
-        rc = gf_model_propagate_on(chain_model(s, models, ch), st, d_theta, GF_LAYOUT_AOS, per_chain, d_fr, d_st);
-        if (rc != GF_OK) break;
-        if (counts) {
-            e = hipMemsetAsync(d_c, 0, sizeof(uint64_t) * nbin3, st);
-            if (e == hipSuccess) e = gf_launch_flavor_hist(d_fr, per_chain, nbins, (unsigned long long*)d_c, cus, st);
-        }
-        if (e == hipSuccess && fr)
-            e = hipMemcpyAsync(fr + (size_t)ch * per_chain * 3, d_fr, sizeof(double) * 3 * per_chain, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess && status)
-            e = hipMemcpyAsync(status + (size_t)ch * per_chain, d_st, sizeof(int32_t) * per_chain, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess && counts)
-            e = hipMemcpyAsync(counts + (size_t)ch * nbin3, d_c, sizeof(uint64_t) * nbin3, hipMemcpyDeviceToHost, st);
-    }
-    hipError_t e2 = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = e2;
-    if (d_fr) (void)hipFree(d_fr);
-    if (d_st) (void)hipFree(d_st);
-    if (d_c) (void)hipFree(d_c);
-    if (rc != GF_OK) return rc;
-    if (e != hipSuccess) return gf_hip_fail(e, "gf_sampler_postprocess");
-    return status ? gf_internal_check_overflow(s->device, st) : GF_OK;
-}
-
-// Stored chain -> compositions -> histogram (the steps of gf_sampler_postprocess_with, one chain after the other through the same
-// scratch buffers) -> credible regions of all chains at once (gf_region.hip).  The counts never leave the device.
-int gf_sampler_regions(gf_sampler* s, gf_model* const* models, int nbins, int radius, const double* weights, const double* coverage,
-                       int ncov, int64_t cap, int64_t* thres, int32_t* saturated, double* level_in, double* level_out, double* mass,
-                       int32_t* cells, double* density)
-{
-    if (!s) return GF_ERR_INVALID_ARG;
-    int rc = gf_region_check_args(s->nchains, nbins, radius, weights, coverage, ncov, cap);
-    if (rc != GF_OK) return rc;
-    int cus = 256;
-    if (check_chain_models(s, models, &cus) != GF_OK) return GF_ERR_INVALID_ARG;
-    GF_HIP(hipSetDevice(s->device));
-    hipStream_t st = s->stream;
-    const int64_t per_chain = s->nstored * s->nwalkers;
-    const size_t nbin3 = (size_t)nbins * nbins * nbins;
-    double* d_fr = nullptr;
-    int32_t* d_st = nullptr;
-    uint64_t* d_c = nullptr;
-    hipError_t e = hipMalloc((void**)&d_c, sizeof(uint64_t) * nbin3 * s->nchains);
-    if (e == hipSuccess) e = hipMemsetAsync(d_c, 0, sizeof(uint64_t) * nbin3 * s->nchains, st);
-    if (e == hipSuccess && per_chain > 0) e = hipMalloc((void**)&d_fr, sizeof(double) * 3 * per_chain);
-    if (e == hipSuccess && per_chain > 0) e = hipMalloc((void**)&d_st, sizeof(int32_t) * per_chain);
-    if (e == hipSuccess && per_chain > 0) {
-        gf_internal_full_arbitration_grids(s->device, st, 1);      // see gf_sampler_postprocess_device
-        for (int ch = 0; ch < s->nchains && e == hipSuccess && rc == GF_OK; ++ch) {
-            const double* d_theta = s->d_chain + (size_t)ch * s->nstore_cap * s->nwalkers * s->ndim;
-            rc = gf_model_propagate_on(chain_model(s, models, ch), st, d_theta, GF_LAYOUT_AOS, per_chain, d_fr, d_st);
-            if (rc != GF_OK) break;
-            e = gf_launch_mask_fr(d_fr, d_st, per_chain, st);
-            if (e == hipSuccess) e = gf_launch_flavor_hist(d_fr, per_chain, nbins, (unsigned long long*)(d_c + (size_t)ch * nbin3), cus, st);
-        }
-        gf_internal_full_arbitration_grids(s->device, st, 0);
-    }
-    if (e == hipSuccess && rc == GF_OK)
-        rc = gf_region_run(st, d_c, s->nchains, nbins, radius, weights, coverage, ncov, cap, thres, saturated, level_in, level_out, mass, cells,
-                           density, nullptr);
-    else
-        (void)hipStreamSynchronize(st);
-    if (d_fr) (void)hipFree(d_fr);
-    if (d_st) (void)hipFree(d_st);
-    if (d_c) (void)hipFree(d_c);
-    if (rc != GF_OK) return rc;
-    if (e != hipSuccess) return gf_hip_fail(e, "gf_sampler_regions");
-    return per_chain > 0 ? gf_internal_check_overflow(s->device, st) : GF_OK;
-}
-
-// The marginals of every stored chain (gf_marginal.hip).  with_fr: the rows a scan saves are assembled first
-// (gf_sampler_postprocess_rows_device) and reduced in place of the chain; either way the rows never leave the device.
-int gf_sampler_marginals(gf_sampler* s, gf_model* const* models, int with_fr, const gf_marginal_spec* spec, const gf_marginal_out* out)
-{
-    if (!s || !out) return GF_ERR_INVALID_ARG;
-    const int width = (with_fr ? 3 : 0) + s->ndim;
-    const int64_t per_chain = s->nstored * s->nwalkers;
-    int rc = gf_marginal_check_args(s->nchains, per_chain, width, spec);
-    if (rc != GF_OK) return rc;
-    if (check_chain_models(s, models) != GF_OK) return GF_ERR_INVALID_ARG;
-    GF_HIP(hipSetDevice(s->device));
-    hipStream_t st = s->stream;
-    if (!with_fr || per_chain == 0) {
-        GF_HIP(hipStreamSynchronize(st));
-        return gf_marginal_run(st, s->d_chain, with_fr ? 0 : s->nstore_cap * s->nwalkers * s->ndim, s->nchains, per_chain, width, spec, out);
-    }
-    double* d_rows = nullptr;
-    GF_HIP(hipMalloc((void**)&d_rows, sizeof(double) * (size_t)per_chain * width * s->nchains));
-    rc = gf_sampler_postprocess_rows_device(s, models, d_rows);
-    if (rc == GF_OK) rc = gf_marginal_run(st, d_rows, per_chain * width, s->nchains, per_chain, width, spec, out);
-    (void)hipFree(d_rows);
-    return rc;
-}
-
-// The marginals of every stored chain in element space (gf_elements.hip): the chains are transformed into a buffer of the
-// library's cache, which is reduced in place of the chain; the stored chain is only read and the rows never leave the device.
-int gf_sampler_element_marginals(gf_sampler* s, const gf_element_plan* plan, const gf_marginal_spec* spec, const gf_marginal_out* out)
-{
-    if (!s || !out) return GF_ERR_INVALID_ARG;
-    const int width = gf_element_plan_width(plan, s->ndim);
-    if (width < 0) return GF_ERR_INVALID_ARG;
-    const int64_t per_chain = s->nstored * s->nwalkers;
-    int rc = gf_marginal_check_args(s->nchains, per_chain, width, spec);
-    if (rc != GF_OK) return rc;
-    GF_HIP(hipSetDevice(s->device));
-    hipStream_t st = s->stream;
-    double* d_rows = nullptr;
-    const size_t n = (size_t)per_chain * width * s->nchains;
-    GF_HIP(hipMalloc((void**)&d_rows, sizeof(double) * (n ? n : 1)));
-    const hipError_t e = gf_element_run(st, s->d_chain, s->nstore_cap * s->nwalkers * s->ndim, s->nchains, per_chain, s->ndim, plan, d_rows,
-                                        per_chain * width, s->cus);
-    if (e == hipSuccess) rc = gf_marginal_run(st, d_rows, per_chain * width, s->nchains, per_chain, width, spec, out);
-    (void)hipFree(d_rows);
-    if (e != hipSuccess) return gf_hip_fail(e, "gf_sampler_element_marginals");
-    return rc;
 }
 
 }  // extern "C"

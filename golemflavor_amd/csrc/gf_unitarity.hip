@@ -26,8 +26,7 @@
 #include <cstdlib>
 
 #include "gf_consts.h"
-
-extern "C" const char* gf_internal_env(const char* name, int affects_results);   // gf_capi.hip: getenv with a record
+#include "gf_internal.h"
 #include "gf_launch.h"
 #include "gf_unitarity_teams.hpp"
 
