@@ -1,7 +1,7 @@
-// Host pieces shared by the C ABI of the device samplers and of chain post-processing (gf_sampler.hip, gf_postprocess.hip, gf_nested.hip,
-// gf_simplex.hip, gf_region.hip, gf_marginal.hip, gf_elements.hip): the library's internal functions (gf_internal.h), the error
-// helpers that publish a message through gf_last_hip_error(), the holder of a call's scratch buffers, and the allocation of the
-// arbitration queue the settle kernels share.
+// Host pieces shared by the C ABI of the device samplers, of chain post-processing and of read-back (gf_sampler.hip, gf_postprocess.hip,
+// gf_readback.hip, gf_nested.hip, gf_simplex.hip, gf_region.hip, gf_marginal.hip, gf_elements.hip): the library's internal functions
+// (gf_internal.h), the error helpers that publish a message through gf_last_hip_error(), the holder of a call's scratch buffers, and
+// the allocation of the arbitration queue the settle kernels share.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

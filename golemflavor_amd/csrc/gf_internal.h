@@ -9,6 +9,8 @@
 #include "../../include/golemflavor_hip.h"
 #include "gf_consts.h"
 
+constexpr int POOL_MAX_DEVICES = 64;     // devices the per-device pools (gf_capi.hip) and read-back rings (gf_readback.hip) have room for
+
 extern "C" {
 // gf_capi.hip
 const char* gf_internal_env(const char* name, int affects_results);   // getenv with a record
@@ -28,6 +30,8 @@ void gf_internal_return_copy_stream(int device, void* stream);
 void gf_internal_full_arbitration_grids(int device, void* stream, int on);
 // GF_ERR_QUEUE_OVERFLOW if an arbitration queue dropped a pair in the launches on `stream`, which has just been synchronised
 int gf_internal_check_overflow(int device, void* stream);
+
+// gf_readback.hip
 // device -> host through the pinned ring and the host copy threads.  gated: a chunk is issued once gate(ctx, upto) has returned 0
 // for the source bytes [0, upto) it ends in; 2d: `height` rows of `width` bytes; pipe: one pipeline kept open over many 2d copies
 int gf_internal_d2h(int device, void* stream, void* dst_host, const void* src_dev, size_t bytes);
@@ -37,6 +41,10 @@ struct gf_d2h_pipe;
 int gf_internal_d2h_pipe_open(int device, void* stream, gf_d2h_pipe** out);
 int gf_internal_d2h_pipe_rows(gf_d2h_pipe* p, void* dst_host, size_t dpitch, const void* src_dev, size_t spitch, size_t width, size_t height);
 int gf_internal_d2h_pipe_close(gf_d2h_pipe* p);
+// the host copy pool: `nrows` packed rows of `width` bytes to rows `dpitch` apart, shared out over the pool's threads
+void gf_internal_copy_rows(char* dst, size_t dpitch, const char* src, size_t width, size_t nrows);
+// release the pinned slots of `device`'s ring unless a read-back holds it (gf_device_trim)
+void gf_internal_d2h_ring_trim(int device);
 
 // gf_sampler.hip
 struct GfChainView {              // the stored chain of a sampler, as post-processing (gf_postprocess.hip) sees it

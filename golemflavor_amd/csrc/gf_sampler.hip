@@ -942,7 +942,7 @@ struct gf_sampler {
 struct HostSink {
     double* chain; double* lnp; int64_t total;     // host arrays of `total` stored steps per chain
     void* copy_stream; int device;
-    struct gf_d2h_pipe* pipe = nullptr;            // ONE read-back pipeline for the whole run (gf_capi.hip)
+    struct gf_d2h_pipe* pipe = nullptr;            // ONE read-back pipeline for the whole run (gf_readback.hip)
     int64_t copied = 0;                            // stored steps whose copy has been issued
     int rc = GF_OK;
     std::chrono::steady_clock::time_point last_event;   // when the newest consumed block was seen complete

@@ -147,7 +147,7 @@ def test_device_trim_releases_idle_workspaces():
 
 
 def test_large_reads_come_back_through_the_pinned_ring_intact():
-    """Device-to-host copies of 16 MB and more go through four pinned 32 MB slots and host threads (gf_internal_d2h); smaller
+    """Device-to-host copies of 16 MiB and more go through eight pinned 16 MiB slots and host threads (gf_internal_d2h); smaller
     ones are a plain hipMemcpy.  Sizes either side of the threshold, not multiples of a slot or of a page, come back bit for
     bit, also into a destination that is not page-aligned."""
     rng = np.random.default_rng(11)
