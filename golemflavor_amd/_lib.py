@@ -20,6 +20,7 @@ GF_REGION_MAX_COVERAGES = 8
 GF_MARGINAL_MAX_RANKS = 16
 GF_ELEMENT_MAX_WIDTH = GF_MAX_DIM + 3
 GF_ELEMENT_COPY, GF_ELEMENT_U9, GF_ELEMENT_FR3 = range(3)
+GF_DIAG_MAX_STEPS = 16384
 
 GF_OK, GF_ERR_INVALID_ARG, GF_ERR_NO_DEVICE, GF_ERR_HIP, GF_ERR_ALLOC, GF_ERR_COMM, GF_ERR_UNSUPPORTED, GF_ERR_QUEUE_OVERFLOW = range(8)
 GF_ST_OK, GF_ST_OUT_OF_PRIOR, GF_ST_NON_UNITARY, GF_ST_NAN = range(4)
@@ -84,6 +85,17 @@ class GfElementGroup(C.Structure):
 class GfElementPlan(C.Structure):
     """struct gf_element_plan, field for field."""
     _fields_ = [("ngroups", C.c_int32), ("round32", C.c_int32), ("group", GfElementGroup * GF_ELEMENT_MAX_WIDTH)]
+
+
+class GfDiagSpec(C.Structure):
+    """struct gf_diag_spec, field for field."""
+    _fields_ = [("c", C.c_double), ("maxlag", C.c_int64)]
+
+
+class GfDiagOut(C.Structure):
+    """struct gf_diag_out, field for field; NULL = skip."""
+    _fields_ = [("tau", _dp), ("tau_mean", _dp), ("rhat", _dp), ("window", _lp), ("window_mean", _lp), ("nexcluded", _ip), ("rho", _dp),
+                ("rho_mean", _dp)]
 
 
 # name -> (restype, argtypes): every symbol include/golemflavor_hip.h declares
@@ -182,6 +194,9 @@ SIGNATURES = {
     "gf_element_rows_device": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.POINTER(GfElementPlan), _vp]),
     "gf_element_rows": (C.c_int, [_vp, _dp, C.c_int64, C.c_int, C.POINTER(GfElementPlan), _dp]),
     "gf_sampler_element_marginals": (C.c_int, [_vp, C.POINTER(GfElementPlan), C.POINTER(GfMarginalSpec), C.POINTER(GfMarginalOut)]),
+    "gf_chain_diagnostics_device": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_int, C.POINTER(GfDiagSpec), C.POINTER(GfDiagOut)]),
+    "gf_chain_diagnostics": (C.c_int, [_vp, _dp, C.c_int64, C.c_int, C.c_int, C.POINTER(GfDiagSpec), C.POINTER(GfDiagOut)]),
+    "gf_sampler_diagnostics": (C.c_int, [_vp, C.POINTER(GfDiagSpec), C.POINTER(GfDiagOut)]),
     "gf_simplex_get_starts": (C.c_int, [_vp, C.c_int, _dp, _dp, _ip, C.POINTER(C.c_int64)]),
 }
 

@@ -55,4 +55,7 @@ struct GfChainView {              // the stored chain of a sampler, as post-proc
     gf_model* model; gf_model* const* models;   // chain 0's, and one per chain or NULL
 };
 int gf_internal_sampler_chain_view(const gf_sampler* s, GfChainView* v);
+// k_walker_mean on `stream`: chain [nchains][cap][nwalkers][ndim] -> mean [nchains][nstored][ndim], the ensemble mean of every step
+hipError_t gf_launch_walker_mean(const double* d_chain, int64_t cap, int64_t nstored, int nchains, int nwalkers, int ndim, double* d_mean,
+                                 hipStream_t stream);
 }

@@ -1,5 +1,5 @@
 // gf_postprocess.hip -- a sampler's STORED chain turned into what the scripts save: compositions, flavor histograms, the scan's rows,
-// credible regions and marginals.  Host code only; the sampler is seen through a GfChainView (gf_internal.h), and every entry point
+// credible regions, marginals and convergence diagnostics.  Host code only; the sampler is seen through a GfChainView (gf_internal.h), and every entry point
 // works in order on the sampler's stream, the one the chain was written on.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -9,6 +9,7 @@
 #include "gf_region.h"
 #include "gf_marginal.h"
 #include "gf_elements.h"
+#include "gf_diag.h"
 
 namespace {
 
@@ -278,6 +279,17 @@ int gf_sampler_element_marginals(gf_sampler* s, const gf_element_plan* plan, con
                                         per_chain * width, v.cus);
     if (e != hipSuccess) return gf_hip_fail(e, "gf_sampler_element_marginals");
     return gf_marginal_run(st, d_rows, per_chain * width, v.nchains, per_chain, width, spec, out);
+}
+
+// The convergence diagnostics of every stored chain (gf_diag.hip); the stored chain is only read and only the results come back.
+int gf_sampler_diagnostics(gf_sampler* s, const gf_diag_spec* spec, const gf_diag_out* out)
+{
+    GfChainView v; if (gf_internal_sampler_chain_view(s, &v) != GF_OK) return GF_ERR_INVALID_ARG;
+    const int rc = gf_diag_check_args(v.nchains, v.nstored, v.nwalkers, v.ndim, spec, out);
+    if (rc != GF_OK) return rc;
+    GF_HIP(hipSetDevice(v.device));
+    GF_HIP(hipStreamSynchronize(v.stream));
+    return gf_diag_run(v.stream, v.d_chain, v.nstore_cap * v.nwalkers * v.ndim, v.nchains, v.nstored, v.nwalkers, v.ndim, spec, out);
 }
 
 }  // extern "C"

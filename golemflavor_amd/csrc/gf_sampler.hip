@@ -1731,6 +1731,19 @@ int gf_sampler_get_chain_device(gf_sampler* s, double* d_chain, double* d_lnprob
     return GF_OK;
 }
 
+hipError_t gf_launch_walker_mean(const double* d_chain, int64_t cap, int64_t nstored, int nchains, int nwalkers, int ndim, double* d_mean,
+                                 hipStream_t st)
+{
+    hipError_t e = hipSuccess;
+    for (int ch0 = 0; ch0 < nchains && e == hipSuccess; ch0 += 65535) {          // gridDim.y <= 65535
+        const int nch = nchains - ch0 < 65535 ? nchains - ch0 : 65535;
+        hipLaunchKernelGGL(k_walker_mean, dim3((unsigned)nstored, (unsigned)nch), dim3(GF_BLOCK), 0, st,
+                           d_chain + (size_t)ch0 * cap * nwalkers * ndim, cap, nstored, nwalkers, ndim, d_mean + (size_t)ch0 * nstored * ndim);
+        e = hipGetLastError();
+    }
+    return e;
+}
+
 // mean [nchains][nstored][ndim]: the ensemble-averaged series whose integrated autocorrelation time the
 // reference prints (golemflavor/mcmc.py:45-51 sampler.acor); reduced on the device, only the means cross PCIe.
 int gf_sampler_walker_mean(gf_sampler* s, double* mean)
@@ -1742,14 +1755,7 @@ int gf_sampler_walker_mean(gf_sampler* s, double* mean)
     const size_t bytes = sizeof(double) * (size_t)s->nchains * s->nstored * s->ndim;
     double* d_mean = nullptr;
     GF_HIP(hipMalloc((void**)&d_mean, bytes));
-    hipError_t e = hipSuccess;
-    for (int ch0 = 0; ch0 < s->nchains && e == hipSuccess; ch0 += 65535) {          // gridDim.y <= 65535
-        const int nch = s->nchains - ch0 < 65535 ? s->nchains - ch0 : 65535;
-        hipLaunchKernelGGL(k_walker_mean, dim3((unsigned)s->nstored, (unsigned)nch), dim3(GF_BLOCK), 0, st,
-                           s->d_chain + (size_t)ch0 * s->nstore_cap * s->nwalkers * s->ndim, s->nstore_cap, s->nstored, s->nwalkers,
-                           s->ndim, d_mean + (size_t)ch0 * s->nstored * s->ndim);
-        e = hipGetLastError();
-    }
+    hipError_t e = gf_launch_walker_mean(s->d_chain, s->nstore_cap, s->nstored, s->nchains, s->nwalkers, s->ndim, d_mean, st);
     if (e == hipSuccess) e = hipMemcpyAsync(mean, d_mean, bytes, hipMemcpyDeviceToHost, st);
     hipError_t e2 = hipStreamSynchronize(st);
     (void)hipFree(d_mean);

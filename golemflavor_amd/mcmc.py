@@ -23,6 +23,8 @@ import sys
 
 import numpy as np
 
+from .diagnostics import sokal_window
+
 
 try:
     from tqdm import tqdm
@@ -52,9 +54,7 @@ def integrated_time(x, c=5, tol=50):
     for d in range(ndim):
         rho = _autocorr_1d(x[:, d])
         taus = 2.0 * np.cumsum(rho) - 1.0
-        m = np.arange(len(taus)) < c * taus
-        window = int(np.argmin(m)) if not m.all() else len(taus) - 1
-        tau[d] = taus[window]
+        tau[d] = taus[sokal_window(taus, c)]
     if np.any(tol * tau > n) or not np.all(np.isfinite(tau)):
         raise AutocorrError("chain of %d steps is shorter than %d x tau (%s)" % (n, tol, tau))
     return tau
@@ -647,6 +647,25 @@ class DeviceEnsembleSampler:
         if self.nchains == 1:
             return integrated_time(m, c=c, tol=tol)
         return np.array([integrated_time(x, c=c, tol=tol) for x in m])
+
+    def diagnostics(self, c=5, maxlag=None, want_rho=False):
+        """Convergence diagnostics of the stored samples (`diagnostics.chain_diagnostics`'s reduction and definitions) for every
+        chain at once, the chain staying on the device: tau and window of the walker-averaged autocorrelation function and of
+        the ensemble-mean series (the one `acor` estimates), split R-hat, the excluded walker series, and each walker's
+        acceptance fraction from the sampler's counters.  Returns a `diagnostics.ChainDiagnostics`, a list of them over the
+        chains when nchains > 1.  Nothing stored: ValueError; more than 16384 stored steps: ValueError -- thin the chain."""
+        from . import diagnostics as dg
+        ns = self.nstored
+        if ns == 0:
+            raise ValueError("no stored samples: run_mcmc(..., storechain=True) first")
+
+        def call(spec, out):
+            return self._L.gf_sampler_diagnostics(self._h, spec, out)
+        res = dg.run_diag_call(call, "gf_sampler_diagnostics", self.nchains, ns, self.k, self.dim, c, maxlag, want_rho)
+        acc = np.atleast_2d(self.acceptance_fraction)
+        for ch, r in enumerate(res):
+            r.acceptance_fraction = acc[ch]
+        return res[0] if self.nchains == 1 else res
 
     def close(self):
         if getattr(self, "_h", None) is not None:

@@ -340,6 +340,37 @@ class MarginalWriter:
         MARGINAL_STATS.update({"bins": [self.kw["bins_1d"], self.kw["bins_2d"]], "points": self.points, "seconds": round(self.seconds, 4)})
 
 
+DIAGNOSTIC_STATS = {}   # the last run_points call with --diagnostics: what it computed on this rank (reported by main)
+
+
+class DiagnosticsWriter:
+    """--diagnostics: the convergence diagnostics of every grid point's chain (`DeviceEnsembleSampler.diagnostics`: tau and window
+    of the walker-averaged autocorrelation function and of the ensemble-mean series, split R-hat, excluded walker series),
+    computed while the point's sampler still holds its chain and saved as diagnostics_<point file name>.npz beside the chain
+    file: `diagnostics.ChainDiagnostics.as_arrays()` plus the mean and the minimum acceptance fraction and the number of walkers
+    that never moved."""
+
+    def __init__(self, datadir, name_of, tol=50):
+        self.datadir, self.name_of, self.tol = datadir, name_of, tol
+        self.seconds, self.points, self.not_converged = 0.0, 0, 0
+
+    def take(self, sampler, models, order):
+        t0 = time.perf_counter()
+        res = sampler.diagnostics()
+        os.makedirs(self.datadir, exist_ok=True)
+        for g, r in zip(order, [res] if len(order) == 1 else res):
+            arrays = r.as_arrays()
+            acc = arrays["acceptance_fraction"]
+            arrays.update(acceptance_mean=np.float64(acc.mean()), acceptance_min=np.float64(acc.min()), never_moved=np.int64((acc == 0).sum()))
+            with open(os.path.join(self.datadir, "diagnostics_%s.npz" % self.name_of(g)), "wb") as f:
+                np.savez(f, **arrays)
+            self.points += 1
+            self.not_converged += not r.converged(self.tol)
+        self.seconds += time.perf_counter() - t0
+        DIAGNOSTIC_STATS.clear()
+        DIAGNOSTIC_STATS.update({"points": self.points, "seconds": round(self.seconds, 4), "tol": self.tol, "not_converged": self.not_converged})
+
+
 class _Takers:
     """several writers behind the one `regions` argument of run_points"""
 
@@ -770,6 +801,9 @@ def main(argv=None):
     ap.add_argument("--elements", action="store_true",
                     help="with --marginals: also save every grid point's marginals in element space (moduli |U_ij| in place of the "
                          "mixing columns, plot.chainer_plot's --plot-elements table), marginals_elements_<point>.npz")
+    ap.add_argument("--diagnostics", action="store_true",
+                    help="also save every grid point's convergence diagnostics (autocorrelation times, split R-hat, acceptance), "
+                         "diagnostics_<point>.npz beside the chain file; needs --datadir")
     ap.add_argument("--marginal-bins-1d", type=int, default=100)
     ap.add_argument("--marginal-bins-2d", type=int, default=50)
     ap.add_argument("--marginal-coverage", type=float, nargs="+", default=[90., 99.], metavar="COVERAGE")
@@ -777,6 +811,8 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.elements and not a.marginals:
         ap.error("--elements needs --marginals (it adds the element-space marginals to them)")
+    if a.diagnostics and not a.datadir:
+        ap.error("--diagnostics needs --datadir (the diagnostics are saved beside the chain files)")
     if a.marginals:
         if not a.datadir:
             ap.error("--marginals needs --datadir (the marginals are saved beside the chain files)")
@@ -842,8 +878,9 @@ def main(argv=None):
         marginal_writer = MarginalWriter(a.datadir, lambda g: point_filename(a.config, pts[g], a), a.marginal_bins_1d, a.marginal_bins_2d,
                                          a.marginal_coverage, a.marginal_percentiles, elements=_point_paramset(a, pts) if a.elements else None)
     region_stats_wanted = regions is not None
-    if marginal_writer is not None:
-        regions = _Takers([t for t in (regions, marginal_writer) if t is not None])
+    diagnostics_writer = DiagnosticsWriter(a.datadir, lambda g: point_filename(a.config, pts[g], a)) if a.diagnostics else None
+    if marginal_writer is not None or diagnostics_writer is not None:
+        regions = _Takers([t for t in (regions, marginal_writer, diagnostics_writer) if t is not None])
     if a.datadir and not want_gather:
         local = run_points(pts, mine, make, a.burnin, a.nsteps, stacked=stacked, regions=regions)
         gather_name = "none: every rank saved its own files (--datadir)"
@@ -899,7 +936,8 @@ def main(argv=None):
                           "phases": {k: round(v, 4) for k, v in PHASES.items()},
                           "evals_per_s": len(pts) * evals_per_point / dt,
                           "finite_fraction": finite, **({"regions": REGION_STATS} if region_stats_wanted else {}),
-                          **({"marginals": MARGINAL_STATS} if marginal_writer is not None else {})}), flush=True)
+                          **({"marginals": MARGINAL_STATS} if marginal_writer is not None else {}),
+                          **({"diagnostics": DIAGNOSTIC_STATS} if diagnostics_writer is not None else {})}), flush=True)
     control.barrier()
     control.close()
     if rccl_err is not None:

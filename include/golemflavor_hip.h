@@ -474,6 +474,35 @@ int gf_element_rows(gf_model* m, const double* rows, int64_t nrows, int width_in
  * by gf_marginals_device's path with width = the plan's output width; only the results come back, the stored chain is not touched */
 int gf_sampler_element_marginals(gf_sampler* s, const gf_element_plan* plan, const gf_marginal_spec* spec, const gf_marginal_out* out);
 
+/* ---- convergence diagnostics of stored chains (golemflavor/mcmc.py:45-51: the acceptance fraction and sampler.acor a job prints) -- */
+/* Per chain and column of a stored chain [nsteps][nwalkers][ndim], with n = nsteps and L = maxlag (< 0: n - 1):
+ *   A_w(t)     = sum_{i <= n-1-t} (x_i - m_w)(x_{i+t} - m_w) of walker w's series, t = 0 .. L
+ *   rho(t)     = mean over the included walkers of A_w(t) / A_w(0); a walker series is excluded, and counted in nexcluded, if it holds
+ *                a non-finite value or A_w(0) is zero (a walker that never moved) or not finite; none included: rho and tau are NaN
+ *   tau        = taus(window), taus(M) = 2 sum_{t <= M} rho(t) - 1, window = the smallest M with M >= c taus(M), else L
+ *   tau_mean, window_mean, rho_mean: the same of the ensemble-mean series (gf_sampler_walker_mean's, bit for bit)
+ *   rhat       = split R-hat over the included walkers' first and second halves (n div 2 steps each; odd n: the middle step is in
+ *                neither): sqrt(((h-1)/h W + B/h) / W); NaN for n < 4.  Walkers of one ensemble are not independent sequences: a
+ *                diagnostic, not a guarantee.
+ * Every sum has a fixed order (csrc/gf_diag.hpp) and no atomic is used: the results are the same bits whatever the grid and however
+ * many chains are stacked.  The chain is only read.  nsteps < 2, nwalkers < 1, ndim outside [1, GF_MAX_DIM], c <= 0 or
+ * maxlag >= nsteps: GF_ERR_INVALID_ARG; nsteps > 16384 (a series is held in LDS): GF_ERR_UNSUPPORTED -- thin the chain. */
+typedef struct gf_diag_spec { double c; int64_t maxlag; } gf_diag_spec;      /* maxlag < 0: nsteps - 1 */
+typedef struct gf_diag_out {                                                  /* every pointer may be NULL */
+    double *tau, *tau_mean, *rhat;            /* [nchains][ndim] */
+    int64_t *window, *window_mean;            /* [nchains][ndim] */
+    int32_t *nexcluded;                       /* [nchains][ndim] */
+    double *rho, *rho_mean;                   /* [nchains][ndim][maxlag + 1] */
+} gf_diag_out;
+/* device chains: chain ch starts at d_chain + ch * chain_stride (doubles); host destinations; synchronous */
+int gf_chain_diagnostics_device(gf_model* m, const double* d_chain, int64_t chain_stride, int nchains, int64_t nsteps, int nwalkers, int ndim,
+                                const gf_diag_spec* spec, const gf_diag_out* out);
+/* one host chain [nsteps][nwalkers][ndim]: upload, the same path */
+int gf_chain_diagnostics(gf_model* m, const double* chain, int64_t nsteps, int nwalkers, int ndim, const gf_diag_spec* spec,
+                         const gf_diag_out* out);
+/* the stored chains of a sampler, all in one chain loop; nothing stored: GF_ERR_INVALID_ARG */
+int gf_sampler_diagnostics(gf_sampler* s, const gf_diag_spec* spec, const gf_diag_out* out);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI -------------------------------------- */
 /* Independent chains (grid points) shard across ranks with no data-path collective; the only
  * exchanges are the broadcast of the packed descriptors at start and the gather of the chain blocks
