@@ -198,6 +198,12 @@ SIGNATURES = {
     "gf_chain_diagnostics": (C.c_int, [_vp, _dp, C.c_int64, C.c_int, C.c_int, C.POINTER(GfDiagSpec), C.POINTER(GfDiagOut)]),
     "gf_sampler_diagnostics": (C.c_int, [_vp, C.POINTER(GfDiagSpec), C.POINTER(GfDiagOut)]),
     "gf_simplex_get_starts": (C.c_int, [_vp, C.c_int, _dp, _dp, _ip, C.POINTER(C.c_int64)]),
+    "gf_nested_posterior": (C.c_int, [_vp, _lp, _dp, _dp, _dp, _dp]),
+    "gf_nested_posterior_rows_device": (C.c_int, [_vp, C.c_int64, C.c_int, _vp]),
+    "gf_nested_posterior_rows": (C.c_int, [_vp, C.c_int64, C.c_int, _dp, _lp]),
+    "gf_nested_marginals": (C.c_int, [_vp, C.c_int64, C.c_int, C.POINTER(GfMarginalSpec), C.POINTER(GfMarginalOut)]),
+    "gf_nested_element_marginals": (C.c_int, [_vp, C.c_int64, C.POINTER(GfElementPlan), C.POINTER(GfMarginalSpec), C.POINTER(GfMarginalOut)]),
+    "gf_nested_regions": (C.c_int, [_vp, C.c_int64, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int64, C.POINTER(C.c_int64), _ip, _dp, _dp, _dp, _ip, _dp]),
 }
 
 _lib = None

@@ -58,4 +58,22 @@ int gf_internal_sampler_chain_view(const gf_sampler* s, GfChainView* v);
 // k_walker_mean on `stream`: chain [nchains][cap][nwalkers][ndim] -> mean [nchains][nstored][ndim], the ensemble mean of every step
 hipError_t gf_launch_walker_mean(const double* d_chain, int64_t cap, int64_t nstored, int nchains, int nwalkers, int ndim, double* d_mean,
                                  hipStream_t stream);
+
+// gf_nested.hip
+struct GfNestedView {             // the points of a nested sampler's runs, as their posterior (gf_nested_post.hip) sees them
+    int device; hipStream_t stream; int cus;
+    int nruns, nlive, batch, nscan, ndim;
+    uint64_t seed;                // Philox key
+    int32_t slot[GF_MAX_DIM];     // column -> scanned slot, -1 = fixed
+    const GfCommon* d_commons;    // [nruns]: the box of every run
+    const double* d_bases;        // [nruns][GF_MAX_DIM]
+    const uint64_t* d_run_ids;    // [nruns]
+    const double *d_dead_l, *d_dead_w, *d_dead_u;   // [iteration][nruns][batch] (dead_u: [nscan] each), NULL before the first iteration
+    const double *d_live_l, *d_live_u;               // [nruns][nlive] ([nscan] each)
+    gf_model* const* models;      // one per run
+};
+struct GfNestedRunState { int64_t iter; double lnx, lnz; int32_t done, failed; };
+// the view, and (state != NULL: [nruns], read back once on the sampler's stream, which is synchronised) where every run stands; a
+// sampler that has not drawn its live points yet reports every run with done = 0
+int gf_internal_nested_view(gf_nested* s, GfNestedView* v, GfNestedRunState* state);
 }

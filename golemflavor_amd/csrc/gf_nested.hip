@@ -581,6 +581,32 @@ int gf_internal_nested_state(gf_nested* s, double* scale, double* lnx)
     return GF_OK;
 }
 
+// What gf_nested_post.hip reads: the device buffers of the runs' points (gf_internal.h)
+int gf_internal_nested_view(gf_nested* s, GfNestedView* v, GfNestedRunState* state)
+{
+    if (!s || !v) return GF_ERR_INVALID_ARG;
+    const NsArgs& a = s->a;
+    v->device = s->rs.device; v->stream = s->rs.stream; v->cus = s->rs.cus;
+    v->nruns = a.nruns; v->nlive = a.nlive; v->batch = a.batch; v->nscan = a.nscan; v->ndim = a.ndim;
+    v->seed = a.seed;
+    for (int d = 0; d < GF_MAX_DIM; ++d) v->slot[d] = a.slot[d];
+    v->d_commons = a.commons; v->d_bases = a.bases; v->d_run_ids = a.run_ids;
+    v->d_dead_l = a.dead_l; v->d_dead_w = a.dead_w; v->d_dead_u = a.dead_u;
+    v->d_live_l = a.live_l; v->d_live_u = a.live_u;
+    v->models = s->rs.models;
+    if (!state) return GF_OK;
+    GF_HIP(hipSetDevice(s->rs.device));
+    std::vector<NsRun> hr(a.nruns);
+    GF_HIP(hipMemcpyAsync(hr.data(), a.runs, sizeof(NsRun) * a.nruns, hipMemcpyDeviceToHost, s->rs.stream));
+    GF_HIP(hipStreamSynchronize(s->rs.stream));
+    for (int r = 0; r < a.nruns; ++r) {
+        const NsRun& x = hr[r];
+        state[r].iter = x.iter; state[r].lnx = x.lnx; state[r].lnz = x.lnz;
+        state[r].done = s->rs.initialised ? x.done : 0; state[r].failed = x.failed;
+    }
+    return GF_OK;
+}
+
 // Run `run`'s dead points in removal order, then its final live set: n = iterations * batch + nlive rows.  lnl [n], lnw [n]
 // (log-weights; the live set's are ln X_final - ln nlive + lnL), cube [n][nscan]; NULL = skip.  With every pointer NULL only *n
 // is set.  cap: rows the caller's arrays hold.

@@ -10,6 +10,7 @@ Points of zero likelihood (lnL = -inf) are never replaced by such points, so the
 live points, whatever the batch (nlive_sequence; Fowlie, Handley & Su 2021).
 
     NestedSampler          the device sampler over several posteriors (one run each)
+                           and their posterior: posterior(), posterior_rows(), marginals(), regions() (gf_nested_post.hip)
     mn_evidence            mn.py:71-108, same name and return: (ln Z, max ln L)
     evidence_scan          sens.py's loop over scales in one device call
     evidence_from_dead     the accounting restated on the host (the tests' reference for the device accumulators)
@@ -158,6 +159,79 @@ class NestedSampler(_CubeRuns):
         theta[:, self.cols] = (hi - lo) * cube + lo          # mn.py:35-36
         return dict(lnl=lnl, lnw=lnw, cube=cube, theta=theta, nlive_seq=seq, ndead=ndead)
 
+    # ---- the posterior of every run, computed on the device from the points dead() would read back -------------
+    def _desc(self, run=0):
+        return getattr(self.models[run], "model", self.models[run]).desc
+
+    @property
+    def ndim(self):
+        return self.bases.shape[1]
+
+    def posterior(self):
+        """Per run: dict(npoints, ess (Kish), lnz_check (= max lnw + log sum exp, a diagnostic), mean (nruns, ndim), cov (nruns,
+        ndim, ndim)) of the weighted points, theta full-width.  A run without a posterior (not run, failed, ln Z = -inf) has
+        npoints 0, ess 0 and NaN elsewhere."""
+        n, d = self.nruns, self.ndim
+        out = dict(npoints=np.zeros(n, np.int64), ess=np.zeros(n), lnz_check=np.zeros(n), mean=np.zeros((n, d)), cov=np.zeros((n, d, d)))
+        _lib.check(self._L.gf_nested_posterior(self._h, out["npoints"].ctypes.data_as(_lib._lp), *[out[k].ctypes.data_as(_lib._dp)
+                                               for k in ("ess", "lnz_check", "mean", "cov")]), "gf_nested_posterior")
+        return out
+
+    def posterior_rows(self, nrows, with_fr=False, return_index=False):
+        """`nrows` equal-weight rows per run by systematic resampling, (nruns, nrows, ndim) -- with_fr: (nruns, nrows, 3 + ndim),
+        the composition of the run's model in front, NaN where the reference would have raised.  return_index: also (nruns, nrows)
+        int64, the point of dead() each row came from.  A run without a posterior gives NaN rows and index -1."""
+        width = (3 if with_fr else 0) + self.ndim
+        rows = np.empty((self.nruns, int(nrows), width) if nrows >= 1 else (self.nruns, 0, width))
+        index = np.empty(rows.shape[:2], np.int64)
+        _lib.check(self._L.gf_nested_posterior_rows(self._h, int(nrows), int(bool(with_fr)), rows.ctypes.data_as(_lib._dp),
+                                                    index.ctypes.data_as(_lib._lp)), "gf_nested_posterior_rows")
+        return (rows, index) if return_index else rows
+
+    def marginals(self, nrows, ranges=None, space="angles", llh_paramset=None, with_fr=False, names=None, round32=True, **prepare_kwargs):
+        """One `marginals.MarginalResult` per run of its `nrows` equal-weight rows, which stay on the device (`marginals.prepare`'s
+        keyword arguments: bins_1d, bins_2d, coverage, percentiles, ranks, hist_smooth, truncate; cap_2d).  space="angles": the
+        theta columns (with_fr: the composition in front), ranges default to the box of the run-0 model and (0, 1);
+        space="elements": `elements.element_plan(llh_paramset, round32)`'s row, names and ranges the plan's."""
+        from . import marginals as mg
+        if space not in ("angles", "elements"):
+            raise ValueError("space must be 'angles' or 'elements'")
+        cap_2d = prepare_kwargs.pop("cap_2d", None)
+        if space == "elements":
+            from . import elements as el
+            if with_fr:
+                raise ValueError("space='elements' does not combine with with_fr: the element-space row carries the source composition")
+            if llh_paramset is None or len(llh_paramset) != self.ndim:
+                raise ValueError("space='elements' needs llh_paramset, the set of the runs' %d columns" % self.ndim)
+            plan, pnames, pranges = el.element_plan(llh_paramset, round32)
+            prep = mg.prepare(len(pnames), pranges if ranges is None else ranges, pnames if names is None else names, **prepare_kwargs)
+
+            def call(spec, out):
+                return self._L.gf_nested_element_marginals(self._h, int(nrows), C.byref(plan), spec, out)
+            return mg.run_marginal_call(call, "gf_nested_element_marginals", self.nruns, prep, cap_2d)
+        d = self._desc()
+        if ranges is None:
+            ranges = ([(0., 1.)] * 3 if with_fr else []) + [(d.lo[c], d.hi[c]) for c in range(self.ndim)]
+        if names is None:
+            names = (["fr_e", "fr_mu", "fr_tau"] if with_fr else []) + ["theta%d" % c for c in range(self.ndim)]
+        prep = mg.prepare((3 if with_fr else 0) + self.ndim, ranges, names, **prepare_kwargs)
+
+        def call(spec, out):
+            return self._L.gf_nested_marginals(self._h, int(nrows), int(bool(with_fr)), spec, out)
+        return mg.run_marginal_call(call, "gf_nested_marginals", self.nruns, prep, cap_2d)
+
+    def regions(self, nrows, nbins, coverage, hist_smooth=0.05, oversample=1., truncate=4.0, cap=None):
+        """The flavor-triangle credible regions (`DeviceEnsembleSampler.regions`'s reduction) of every run's `nrows` equal-weight
+        rows propagated with the run's model: [run] of `contour.RegionResult` (of lists of them for several coverages)."""
+        from . import contour
+        nb = int(nbins * oversample) + 1
+        scalar, _ = contour._coverages(coverage)
+
+        def call(*args):
+            return self._L.gf_nested_regions(self._h, int(nrows), nb, *args)
+        res = contour.run_region_call(call, "gf_nested_regions", self.nruns, nb, coverage, hist_smooth, truncate, cap)
+        return contour.shape_results(res, scalar, False)
+
 
 def _logaddexp(x, y):
     if x == -math.inf:
@@ -292,11 +366,13 @@ def _scan_models(args, asimov_paramset, llh_paramset, scales, smearing, device):
 
 
 def evidence_scan(args, asimov_paramset, llh_paramset, scales, run_ids=None, nlive=None, tol=None, batch=None, walks=None,
-                  seed=None, on_nonunitary="raise", smearing=None, device=0, max_iter=100000, return_sampler=False):
+                  seed=None, on_nonunitary="raise", smearing=None, device=0, max_iter=100000, return_sampler=False, posterior=None):
     """sens.py:231-303 for every scale at once: the scanned columns are every column but the scale (sens.py:217-218), the scale
     column is fixed at each scale (with its box lowered for the null point), one device call.  `args` as for bsm_ln_prob
     (source_ratio, dimension, texture, binning) plus the --mn-* options.  Returns dict(scales, lnz, lnz_err, max_lnl, niter,
-    nevals, nonunitary, seconds)."""
+    nevals, nonunitary, seconds).  posterior=dict(nrows=..., elements=False, and `NestedSampler.marginals`'s keyword arguments):
+    the result also carries "posterior" (`NestedSampler.posterior()`), "marginals" ([scale] MarginalResult over llh_paramset's
+    columns) and, with elements, "marginals_elements", computed before the sampler is closed."""
     import time
     scales = np.asarray(scales, dtype=np.float64)
     cols, models, bases, labels = _scan_models(args, asimov_paramset, llh_paramset, scales, smearing, device)
@@ -309,10 +385,20 @@ def evidence_scan(args, asimov_paramset, llh_paramset, scales, run_ids=None, nli
         t0 = time.perf_counter()
         try:
             res = s.run(max_iter=max_iter)
+            res["seconds"] = time.perf_counter() - t0
+            if posterior is not None:
+                kw = dict(posterior)
+                nrows, elements = int(kw.pop("nrows")), bool(kw.pop("elements", False))
+                kw.setdefault("names", list(llh_paramset.names))
+                kw.setdefault("ranges", [tuple(float(v) for v in p.ranges) for p in llh_paramset])
+                post = dict(posterior=s.posterior(), marginals=s.marginals(nrows, **kw))
+                if elements:
+                    ekw = {k: v for k, v in kw.items() if k not in ("names", "ranges")}
+                    post["marginals_elements"] = s.marginals(nrows, space="elements", llh_paramset=llh_paramset, **ekw)
+                res.update(post)
         finally:
             if not return_sampler:
                 s.close()
-        res["seconds"] = time.perf_counter() - t0
         res["scales"] = scales
         if return_sampler:
             res["sampler"] = s

@@ -5,7 +5,8 @@ Same arguments as the reference's driver for what applies here (the likelihood i
 README.md:70-74), same scale list ([-100] + linspace over SCALE_BOUNDARIES[d] in segments - 1 steps, sens.py:226-229) and the
 same two output arrays, {datadir}/{stat_method}/{data}/fr_stat{identifier}.npy and fr_maxllh{identifier}.npy of shape
 (segments, 2) -- (1, 2) with --eval-segment, whose files carry `_scale_{10^scale:.0E}` (sens.py:232-258).  All scales run in
-one device call.  Prints one JSON summary line.  The frequentist arrays hold [scale, profile max lnL] in both files: the
+one device call.  Prints one JSON summary line.  --posterior also writes every scale's posterior summary and marginals,
+posterior_<identifier>_scale_<10^scale:.0E>.npz beside the arrays (INTEGRATION.md has the layout).  The frequentist arrays hold [scale, profile max lnL] in both files: the
 statistic golemflavor/plot.py:605-608 (plot_statistic) receives.
 """
 import argparse
@@ -23,6 +24,9 @@ from .enums import DataType, StatCateg, Texture
 from .mcmc import chain_identifier
 
 
+DEFAULT_POSTERIOR_ROWS = 16384
+
+
 def _enum(E):
     def parse(s):
         return E[str(s).rsplit(".", 1)[-1].upper()]
@@ -37,7 +41,7 @@ def parse_args(argv=None):
     ap = argparse.ArgumentParser(prog="python -m golemflavor_amd.sens", description="BSM flavor ratio evidence scan "
                                  "(scripts/sens.py) on the device nested sampler")
     ap.add_argument("--seed", type=int, default=25, help="random seed")
-    ap.add_argument("--datadir", type=str, default="./untitled", help="where the arrays are written")
+    ap.add_argument("--datadir", type=str, default=None, help="where the arrays are written (default ./untitled)")
     ap.add_argument("--segments", type=int, default=10, help="number of new physics scales to evaluate (with the null point)")
     ap.add_argument("--eval-segment", type=str, default="all", help="which point to evaluate ('all' or an index)")
     ap.add_argument("--overwrite", type=_bool, default=False, help="overwrite existing arrays")
@@ -65,7 +69,26 @@ def parse_args(argv=None):
     ap.add_argument("--pl-adaptive", type=_bool, default=True, help="frequentist: scipy's adaptive coefficients")
     ap.add_argument("--on-nonunitary", choices=["raise", "-inf"], default="raise")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--posterior", action="store_true",
+                    help="also save every scale's posterior (effective sample size, mean, covariance and the marginals of its "
+                         "equal-weight rows), posterior_<identifier>_scale_<...>.npz beside fr_stat; needs --datadir")
+    ap.add_argument("--posterior-rows", type=int, default=DEFAULT_POSTERIOR_ROWS,
+                    help="with --posterior: equal-weight rows resampled per scale (default %d, this package's choice)"
+                         % DEFAULT_POSTERIOR_ROWS)
+    ap.add_argument("--posterior-elements", action="store_true",
+                    help="with --posterior: also save the marginals in element space, posterior_elements_<...>.npz")
     args = ap.parse_args(argv)
+    if args.posterior_elements and not args.posterior:
+        ap.error("--posterior-elements needs --posterior (it adds the element-space marginals to it)")
+    if args.posterior:
+        if not args.datadir:
+            ap.error("--posterior needs --datadir (the posteriors are saved beside the fr_stat arrays)")
+        if args.stat_method is StatCateg.FREQUENTIST:
+            ap.error("--posterior needs the nested sampler: it does not combine with --stat-method frequentist")
+        if args.posterior_rows < 1:
+            ap.error("--posterior-rows must be at least 1")
+    if args.datadir is None:
+        args.datadir = "./untitled"
     if args.texture is Texture.NONE:
         ap.error("Must assume a BSM texture")                         # sens.py:145-146
     args.source_ratio = fr_utils.normalize_fr(args.source_ratio)
@@ -88,6 +111,31 @@ def output_paths(args, scales=None):
     return stat, llh
 
 
+def posterior_path(args, scale, elements=False):
+    """posterior[_elements]<identifier>_scale_<10^scale:.0E>.npz beside fr_stat<identifier>.npy."""
+    base = os.path.join(args.datadir, args.stat_method.name.lower(), args.data.name.lower())
+    return os.path.join(base, "posterior{0}{1}_scale_{2:.0E}.npz".format("_elements" if elements else "", chain_identifier(args),
+                                                                       np.power(10., scale)))
+
+
+def save_posteriors(args, scales, res):
+    """One .npz per scale: `MarginalResult.as_arrays()` plus ess, npoints, mean, cov (and lnz_check, scale)."""
+    files = []
+    for k, sc in enumerate(scales):
+        for key, elements in (("marginals", False), ("marginals_elements", True)):
+            if key not in res:
+                continue
+            arrays = res[key][k].as_arrays()
+            arrays.update({f: res["posterior"][f][k] for f in ("ess", "npoints", "lnz_check")})
+            arrays.update(mean=res["posterior"]["mean"][k], cov=res["posterior"]["cov"][k], scale=np.float64(sc))
+            f = posterior_path(args, sc, elements)
+            os.makedirs(os.path.dirname(f) or ".", exist_ok=True)
+            with open(f, "wb") as fh:
+                np.savez(fh, **arrays)
+            files.append(f)
+    return files
+
+
 def main(argv=None):
     args = parse_args(argv)
     scales = nested.sens_scales(args.dimension, args.segments)
@@ -100,14 +148,17 @@ def main(argv=None):
     asimov, llh_ps = Cf.sens_paramsets(args.dimension, args.injected_ratio, data=args.data)
     if args.stat_method is StatCateg.FREQUENTIST:
         return _frequentist(args, scales, idx, asimov, llh_ps, outfile, outfile_llh)
+    post = dict(nrows=args.posterior_rows, elements=args.posterior_elements) if args.posterior else None
     res = nested.evidence_scan(args, asimov, llh_ps, scales[idx], run_ids=idx, on_nonunitary=args.on_nonunitary,
-                               device=args.device)
+                               device=args.device, posterior=post)
     evidence_arr = np.stack([scales[idx], res["lnz"]], axis=1)
     maxllh_arr = np.stack([scales[idx], res["max_lnl"]], axis=1)
     for f, arr in ((outfile, evidence_arr), (outfile_llh, maxllh_arr)):
         os.makedirs(os.path.dirname(f) or ".", exist_ok=True)
         np.save(f + ".npy", arr)
+    posterior_files = save_posteriors(args, scales[idx], res) if args.posterior else None
     print(json.dumps({
+        **({"posterior": posterior_files} if posterior_files is not None else {}),
         "tool": "golemflavor_amd.sens", "dimension": args.dimension, "texture": args.texture.name,
         "segments": args.segments, "nlive": args.mn_live_points, "scales": scales[idx].tolist(),
         "lnz": res["lnz"].tolist(), "lnz_err": res["lnz_err"].tolist(), "max_lnl": res["max_lnl"].tolist(),

@@ -539,6 +539,33 @@ int gf_device_release(int device, void* dptr);
 const char* gf_comm_last_error(void);                 /* thread-local text of the last failing gf_comm_* call */
 int gf_comm_library_info(char* buf, size_t buflen);   /* "<ncclGetVersion code> <path of the loaded librccl>" */
 
+/* ---- the posterior of every run of a nested sampler (csrc/gf_nested_post.hpp holds the arithmetic) --------------- */
+/* A run's points are gf_nested_get_dead's rows in its order (n = iterations * batch + nlive).  With m = max lnw: e_i = exp(lnw_i - m)
+ * (lnw = -inf: 0 exactly), S = sum e, S2 = sum e^2, p_i = e_i / S, ess = S^2 / S2 (Kish), lnz_check = m + log(S); mean =
+ * np.average(theta, axis=0, weights=p) and cov = np.cov(theta.T, aweights=p) over the full-width theta (a column that is not scanned
+ * has its value as mean and zero covariances, exactly); every sum along one fixed tree.  Equal-weight rows by systematic resampling:
+ * C = the inclusive prefix of p in a fixed blocked order, u in [0, 1) from Philox4x32-10 with the sampler's key and counter (run id,
+ * 0xFFFFFFFE, 0, 0), t_k = (k + u) / nrows, row k = the point min(first i with C_i > t_k, n - 1).  A run without a posterior (not run
+ * to its end, failed in raise mode, ln Z = -inf) has npoints 0, ess 0, NaN moments, NaN rows and index -1; the call is GF_OK for
+ * the others.  nrows < 1 or a NULL sampler: GF_ERR_INVALID_ARG; device scratch that is not granted: GF_ERR_ALLOC with a message.
+ * The models of gf_nested_create must still be open.  All synchronous, on the sampler's stream; the sampler's state is only read. */
+/* per run: npoints, ess, lnz_check [nruns], mean [nruns][ndim], cov [nruns][ndim][ndim]; NULL = skip */
+int gf_nested_posterior(gf_nested* s, int64_t* npoints, double* ess, double* lnz_check, double* mean, double* cov);
+/* d_rows [nruns][nrows][(with_fr ? 3 : 0) + ndim] on the device: with_fr puts the composition of models[r] in front (NaN where the
+ * reference would have raised), the layout of gf_sampler_postprocess_rows_device */
+int gf_nested_posterior_rows_device(gf_nested* s, int64_t nrows, int with_fr, double* d_rows);
+/* the same rows in host memory, and index [nruns][nrows] (NULL = skip): the point every row came from */
+int gf_nested_posterior_rows(gf_nested* s, int64_t nrows, int with_fr, double* rows, int64_t* index);
+/* the marginals (gf_marginals_device, nchains = nruns) of those rows, which stay on the device */
+int gf_nested_marginals(gf_nested* s, int64_t nrows, int with_fr, const gf_marginal_spec* spec, const gf_marginal_out* out);
+/* the marginals of the theta rows in element space (gf_element_rows_device, then gf_marginals_device) */
+int gf_nested_element_marginals(gf_nested* s, int64_t nrows, const gf_element_plan* plan, const gf_marginal_spec* spec,
+                                const gf_marginal_out* out);
+/* the flavor-triangle credible regions (gf_sampler_regions' outputs, [nruns] leading) of every run's rows propagated with its model */
+int gf_nested_regions(gf_nested* s, int64_t nrows, int nbins, int radius, const double* weights, const double* coverage, int ncov,
+                      int64_t cap, int64_t* thres, int32_t* saturated, double* level_in, double* level_out, double* mass, int32_t* cells,
+                      double* density);
+
 #ifdef __cplusplus
 }
 #endif
