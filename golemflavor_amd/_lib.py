@@ -21,6 +21,8 @@ GF_MARGINAL_MAX_RANKS = 16
 GF_ELEMENT_MAX_WIDTH = GF_MAX_DIM + 3
 GF_ELEMENT_COPY, GF_ELEMENT_U9, GF_ELEMENT_FR3 = range(3)
 GF_DIAG_MAX_STEPS = 16384
+GF_INTERVAL_MAX_BINS = 1 << 20
+GF_INTERVAL_MAX_PERCENTILES = 8
 
 GF_OK, GF_ERR_INVALID_ARG, GF_ERR_NO_DEVICE, GF_ERR_HIP, GF_ERR_ALLOC, GF_ERR_COMM, GF_ERR_UNSUPPORTED, GF_ERR_QUEUE_OVERFLOW = range(8)
 GF_ST_OK, GF_ST_OUT_OF_PRIOR, GF_ST_NON_UNITARY, GF_ST_NAN = range(4)
@@ -96,6 +98,16 @@ class GfDiagOut(C.Structure):
     """struct gf_diag_out, field for field; NULL = skip."""
     _fields_ = [("tau", _dp), ("tau_mean", _dp), ("rhat", _dp), ("window", _lp), ("window_mean", _lp), ("nexcluded", _ip), ("rho", _dp),
                 ("rho_mean", _dp)]
+
+
+class GfIntervalSpec(C.Structure):
+    """struct gf_interval_spec, field for field."""
+    _fields_ = [("npct", C.c_int32), ("percentile", _dp)]
+
+
+class GfIntervalOut(C.Structure):
+    """struct gf_interval_out, field for field; NULL = skip."""
+    _fields_ = [("low", _dp), ("up", _dp), ("status", _ip), ("center", _dp), ("nbins", _lp), ("nunique", _lp)]
 
 
 # name -> (restype, argtypes): every symbol include/golemflavor_hip.h declares
@@ -203,6 +215,12 @@ SIGNATURES = {
     "gf_nested_posterior_rows": (C.c_int, [_vp, C.c_int64, C.c_int, _dp, _lp]),
     "gf_nested_marginals": (C.c_int, [_vp, C.c_int64, C.c_int, C.POINTER(GfMarginalSpec), C.POINTER(GfMarginalOut)]),
     "gf_nested_element_marginals": (C.c_int, [_vp, C.c_int64, C.POINTER(GfElementPlan), C.POINTER(GfMarginalSpec), C.POINTER(GfMarginalOut)]),
+    "gf_sort_columns_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, C.c_int, _vp]),
+    "gf_column_intervals_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, C.c_int, C.POINTER(GfIntervalSpec), C.POINTER(GfIntervalOut)]),
+    "gf_column_intervals": (C.c_int, [_vp, _dp, C.c_int64, C.c_int, C.POINTER(GfIntervalSpec), C.POINTER(GfIntervalOut)]),
+    "gf_sampler_intervals": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(GfIntervalSpec), C.POINTER(GfIntervalOut)]),
+    "gf_sampler_element_intervals": (C.c_int, [_vp, C.POINTER(GfElementPlan), C.POINTER(GfIntervalSpec), C.POINTER(GfIntervalOut)]),
+    "gf_nested_intervals": (C.c_int, [_vp, C.c_int64, C.c_int, C.POINTER(GfIntervalSpec), C.POINTER(GfIntervalOut)]),
     "gf_nested_regions": (C.c_int, [_vp, C.c_int64, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int64, C.POINTER(C.c_int64), _ip, _dp, _dp, _dp, _ip, _dp]),
 }
 

@@ -22,6 +22,7 @@
 #include "gf_devcache.h"
 #include "gf_host.h"                    // (after gf_devcache.h: GfScratch allocates through the cache)
 #include "gf_elements.h"
+#include "gf_interval.h"
 #include "gf_marginal.h"
 #include "gf_nested_post.hpp"
 #include "gf_region.h"
@@ -526,6 +527,23 @@ int gf_nested_marginals(gf_nested* s, int64_t nrows, int with_fr, const gf_margi
     if (buf.get(&d_rows, bytes) != hipSuccess) return np_alloc_fail("gf_nested_marginals", bytes);
     rc = np_rows(s, nrows, with_fr, d_rows, nullptr, "gf_nested_marginals");
     return rc != GF_OK ? rc : gf_marginal_run(v.stream, d_rows, nrows * width, v.nruns, nrows, width, spec, out);
+}
+
+// the column intervals (gf_interval.hip, nchains = nruns) of gf_nested_posterior_rows_device's rows, which stay on the device
+int gf_nested_intervals(gf_nested* s, int64_t nrows, int with_fr, const gf_interval_spec* spec, const gf_interval_out* out)
+{
+    GfNestedView v;
+    if (gf_internal_nested_view(s, &v, nullptr) != GF_OK || nrows < 1 || !spec || !out) return GF_ERR_INVALID_ARG;
+    const int width = (with_fr ? 3 : 0) + v.ndim;
+    int rc = gf_interval_check_args(v.nruns, nrows, width, spec);
+    if (rc != GF_OK) return rc;
+    GF_HIP(hipSetDevice(v.device));
+    GfScratch buf;
+    double* d_rows = nullptr;
+    const size_t bytes = sizeof(double) * (size_t)v.nruns * nrows * width;
+    if (buf.get(&d_rows, bytes) != hipSuccess) return np_alloc_fail("gf_nested_intervals", bytes);
+    rc = np_rows(s, nrows, with_fr, d_rows, nullptr, "gf_nested_intervals");
+    return rc != GF_OK ? rc : gf_interval_run(v.stream, d_rows, nrows * width, v.nruns, nrows, width, spec, out, nullptr);
 }
 
 int gf_nested_element_marginals(gf_nested* s, int64_t nrows, const gf_element_plan* plan, const gf_marginal_spec* spec, const gf_marginal_out* out)

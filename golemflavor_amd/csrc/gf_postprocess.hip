@@ -10,6 +10,7 @@
 #include "gf_marginal.h"
 #include "gf_elements.h"
 #include "gf_diag.h"
+#include "gf_interval.h"
 
 namespace {
 
@@ -290,6 +291,48 @@ int gf_sampler_diagnostics(gf_sampler* s, const gf_diag_spec* spec, const gf_dia
     GF_HIP(hipSetDevice(v.device));
     GF_HIP(hipStreamSynchronize(v.stream));
     return gf_diag_run(v.stream, v.d_chain, v.nstore_cap * v.nwalkers * v.ndim, v.nchains, v.nstored, v.nwalkers, v.ndim, spec, out);
+}
+
+// The column intervals of every stored chain (gf_interval.hip) over gf_sampler_marginals' rows, which never leave the device.
+int gf_sampler_intervals(gf_sampler* s, gf_model* const* models, int with_fr, const gf_interval_spec* spec, const gf_interval_out* out)
+{
+    GfChainView v; if (gf_internal_sampler_chain_view(s, &v) != GF_OK || !spec || !out) return GF_ERR_INVALID_ARG;
+    const int width = (with_fr ? 3 : 0) + v.ndim;
+    const int64_t per_chain = v.nstored * v.nwalkers;
+    int rc = gf_interval_check_args(v.nchains, per_chain, width, spec);
+    if (rc != GF_OK) return rc;
+    if (check_chain_models(v, models) != GF_OK) return GF_ERR_INVALID_ARG;
+    GF_HIP(hipSetDevice(v.device));
+    hipStream_t st = v.stream;
+    if (!with_fr) {
+        GF_HIP(hipStreamSynchronize(st));
+        return gf_interval_run(st, v.d_chain, v.nstore_cap * v.nwalkers * v.ndim, v.nchains, per_chain, width, spec, out, nullptr);
+    }
+    GfScratch buf;
+    double* d_rows = nullptr;
+    GF_HIP(buf.get(&d_rows, sizeof(double) * (size_t)per_chain * width * v.nchains));
+    rc = gf_sampler_postprocess_rows_device(s, models, d_rows);
+    return rc != GF_OK ? rc : gf_interval_run(st, d_rows, per_chain * width, v.nchains, per_chain, width, spec, out, nullptr);
+}
+
+// The column intervals of every stored chain in element space: gf_sampler_element_marginals' rows.
+int gf_sampler_element_intervals(gf_sampler* s, const gf_element_plan* plan, const gf_interval_spec* spec, const gf_interval_out* out)
+{
+    GfChainView v; if (gf_internal_sampler_chain_view(s, &v) != GF_OK || !spec || !out) return GF_ERR_INVALID_ARG;
+    const int width = gf_element_plan_width(plan, v.ndim);
+    if (width < 0) return GF_ERR_INVALID_ARG;
+    const int64_t per_chain = v.nstored * v.nwalkers;
+    const int rc = gf_interval_check_args(v.nchains, per_chain, width, spec);
+    if (rc != GF_OK) return rc;
+    GF_HIP(hipSetDevice(v.device));
+    hipStream_t st = v.stream;
+    GfScratch buf;
+    double* d_rows = nullptr;
+    GF_HIP(buf.get(&d_rows, sizeof(double) * (size_t)per_chain * width * v.nchains));
+    const hipError_t e = gf_element_run(st, v.d_chain, v.nstore_cap * v.nwalkers * v.ndim, v.nchains, per_chain, v.ndim, plan, d_rows,
+                                        per_chain * width, v.cus);
+    if (e != hipSuccess) return gf_hip_fail(e, "gf_sampler_element_intervals");
+    return gf_interval_run(st, d_rows, per_chain * width, v.nchains, per_chain, width, spec, out, nullptr);
 }
 
 }  // extern "C"

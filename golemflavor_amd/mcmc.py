@@ -667,6 +667,42 @@ class DeviceEnsembleSampler:
             r.acceptance_fraction = acc[ch]
         return res[0] if self.nchains == 1 else res
 
+    def intervals(self, percentiles=(68., 90.), with_fr=False, models=None, space="theta", llh_paramset=None, round32=True):
+        """The reference's shortest interval around the mode (`misc.interval`) of every column of the stored samples, and each
+        column's number of distinct values, for every chain at once, the chain staying on the device: `intervals.chain_intervals`'s
+        dict (low, up, status (width, npct), center, nbins, nunique (width,), percentiles), with a leading chain axis when
+        nchains > 1.  with_fr, models: the rows a scan saves, as in `marginals`; space="elements": the chain in element space
+        (`elements.element_plan(llh_paramset, round32)`), which takes neither.  Nothing stored: ValueError."""
+        from . import intervals as iv
+        if space not in ("theta", "elements"):
+            raise ValueError("space must be 'theta' or 'elements'")
+        if self.nstored == 0:
+            raise ValueError("no stored samples: run_mcmc(..., storechain=True) first")
+        C = self._C
+        if space == "elements":
+            from . import elements as el
+            if with_fr or models is not None:
+                raise ValueError("space='elements' takes neither with_fr nor post-processing models")
+            if llh_paramset is None or len(llh_paramset) != self.dim:
+                raise ValueError("space='elements' needs llh_paramset, the set of the chain's %d columns" % self.dim)
+            plan, pnames, _ = el.element_plan(llh_paramset, round32)
+
+            def call(spec, out):
+                return self._L.gf_sampler_element_intervals(self._h, C.byref(plan), spec, out)
+            res = iv.run_interval_call(call, "gf_sampler_element_intervals", self.nchains, len(pnames), percentiles)
+            return iv._squeeze(res, self.nchains == 1)
+        handles = None
+        if models is not None:
+            ms = [getattr(m, "model", m) for m in models]
+            if len(ms) != self.nchains:
+                raise ValueError("%d post-processing models for %d chains" % (len(ms), self.nchains))
+            handles = (C.c_void_p * self.nchains)(*[m._h.value if hasattr(m._h, "value") else m._h for m in ms])
+
+        def call(spec, out):
+            return self._L.gf_sampler_intervals(self._h, handles, int(bool(with_fr)), spec, out)
+        res = iv.run_interval_call(call, "gf_sampler_intervals", self.nchains, (3 if with_fr else 0) + self.dim, percentiles)
+        return iv._squeeze(res, self.nchains == 1)
+
     def close(self):
         if getattr(self, "_h", None) is not None:
             self._L.gf_sampler_destroy(self._h)

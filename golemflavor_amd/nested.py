@@ -220,6 +220,16 @@ class NestedSampler(_CubeRuns):
             return self._L.gf_nested_marginals(self._h, int(nrows), int(bool(with_fr)), spec, out)
         return mg.run_marginal_call(call, "gf_nested_marginals", self.nruns, prep, cap_2d)
 
+    def intervals(self, nrows, percentiles=(68., 90.), with_fr=False):
+        """The reference's shortest interval around the mode (`misc.interval`) of every column of every run's `nrows` equal-weight
+        rows, which stay on the device: `intervals.chain_intervals`'s dict with a leading run axis.  A run without a posterior has
+        NaN rows: status 1."""
+        from . import intervals as iv
+
+        def call(spec, out):
+            return self._L.gf_nested_intervals(self._h, int(nrows), int(bool(with_fr)), spec, out)
+        return iv.run_interval_call(call, "gf_nested_intervals", self.nruns, (3 if with_fr else 0) + self.ndim, percentiles)
+
     def regions(self, nrows, nbins, coverage, hist_smooth=0.05, oversample=1., truncate=4.0, cap=None):
         """The flavor-triangle credible regions (`DeviceEnsembleSampler.regions`'s reduction) of every run's `nrows` equal-weight
         rows propagated with the run's model: [run] of `contour.RegionResult` (of lists of them for several coverages)."""

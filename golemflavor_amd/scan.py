@@ -371,6 +371,37 @@ class DiagnosticsWriter:
         DIAGNOSTIC_STATS.update({"points": self.points, "seconds": round(self.seconds, 4), "tol": self.tol, "not_converged": self.not_converged})
 
 
+INTERVAL_STATS = {}   # the last run_points call with --intervals: what it computed on this rank (reported by main)
+
+
+class IntervalWriter:
+    """--intervals: the reference's shortest interval around the mode (`misc.interval`, the number `plot.chainer_plot` prints per
+    panel and as the scale's 90 % interval) of every column of every grid point's saved rows, and each column's number of distinct
+    values (`DeviceEnsembleSampler.intervals`), computed while the point's sampler still holds its chain and saved as
+    intervals_<point file name>.npz beside the chain file: low, up, status (width, npct), center, nbins, nunique (width,),
+    percentiles, names."""
+
+    def __init__(self, datadir, name_of, percentiles=(68., 90.)):
+        self.datadir, self.name_of, self.percentiles = datadir, name_of, [float(p) for p in percentiles]
+        self.seconds, self.points, self.not_ok = 0.0, 0, 0
+
+    def take(self, sampler, models, order):
+        from . import intervals as iv
+        t0 = time.perf_counter()
+        with_fr = models is not None
+        res = sampler.intervals(percentiles=self.percentiles, with_fr=with_fr, models=models)
+        names = (["fr_e", "fr_mu", "fr_tau"] if with_fr else []) + ["theta%d" % c for c in range(sampler.dim)]
+        os.makedirs(self.datadir, exist_ok=True)
+        for k, g in enumerate(order):
+            r = res if len(order) == 1 else {f: (v if f == "percentiles" else v[k]) for f, v in res.items()}
+            iv.save(os.path.join(self.datadir, "intervals_%s.npz" % self.name_of(g)), r, names)
+            self.points += 1
+            self.not_ok += int(np.count_nonzero(r["status"]))
+        self.seconds += time.perf_counter() - t0
+        INTERVAL_STATS.clear()
+        INTERVAL_STATS.update({"percentiles": self.percentiles, "points": self.points, "seconds": round(self.seconds, 4), "status_not_ok": self.not_ok})
+
+
 class _Takers:
     """several writers behind the one `regions` argument of run_points"""
 
@@ -804,6 +835,9 @@ def main(argv=None):
     ap.add_argument("--diagnostics", action="store_true",
                     help="also save every grid point's convergence diagnostics (autocorrelation times, split R-hat, acceptance), "
                          "diagnostics_<point>.npz beside the chain file; needs --datadir")
+    ap.add_argument("--intervals", type=float, nargs="*", default=None, metavar="P",
+                    help="also save every grid point's shortest intervals around the mode (misc.interval; default 68 90) and distinct "
+                         "values per column, intervals_<point>.npz beside the chain file; needs --datadir")
     ap.add_argument("--marginal-bins-1d", type=int, default=100)
     ap.add_argument("--marginal-bins-2d", type=int, default=50)
     ap.add_argument("--marginal-coverage", type=float, nargs="+", default=[90., 99.], metavar="COVERAGE")
@@ -813,6 +847,12 @@ def main(argv=None):
         ap.error("--elements needs --marginals (it adds the element-space marginals to them)")
     if a.diagnostics and not a.datadir:
         ap.error("--diagnostics needs --datadir (the diagnostics are saved beside the chain files)")
+    if a.intervals is not None:
+        if not a.datadir:
+            ap.error("--intervals needs --datadir (the intervals are saved beside the chain files)")
+        a.intervals = a.intervals or [68., 90.]
+        if not 1 <= len(a.intervals) <= 8 or not all(0. < p <= 100. for p in a.intervals):
+            ap.error("--intervals takes up to 8 percentiles in (0, 100]")
     if a.marginals:
         if not a.datadir:
             ap.error("--marginals needs --datadir (the marginals are saved beside the chain files)")
@@ -879,8 +919,9 @@ def main(argv=None):
                                          a.marginal_coverage, a.marginal_percentiles, elements=_point_paramset(a, pts) if a.elements else None)
     region_stats_wanted = regions is not None
     diagnostics_writer = DiagnosticsWriter(a.datadir, lambda g: point_filename(a.config, pts[g], a)) if a.diagnostics else None
-    if marginal_writer is not None or diagnostics_writer is not None:
-        regions = _Takers([t for t in (regions, marginal_writer, diagnostics_writer) if t is not None])
+    interval_writer = IntervalWriter(a.datadir, lambda g: point_filename(a.config, pts[g], a), a.intervals) if a.intervals is not None else None
+    if marginal_writer is not None or diagnostics_writer is not None or interval_writer is not None:
+        regions = _Takers([t for t in (regions, marginal_writer, diagnostics_writer, interval_writer) if t is not None])
     if a.datadir and not want_gather:
         local = run_points(pts, mine, make, a.burnin, a.nsteps, stacked=stacked, regions=regions)
         gather_name = "none: every rank saved its own files (--datadir)"
@@ -937,7 +978,8 @@ def main(argv=None):
                           "evals_per_s": len(pts) * evals_per_point / dt,
                           "finite_fraction": finite, **({"regions": REGION_STATS} if region_stats_wanted else {}),
                           **({"marginals": MARGINAL_STATS} if marginal_writer is not None else {}),
-                          **({"diagnostics": DIAGNOSTIC_STATS} if diagnostics_writer is not None else {})}), flush=True)
+                          **({"diagnostics": DIAGNOSTIC_STATS} if diagnostics_writer is not None else {}),
+                          **({"intervals": INTERVAL_STATS} if interval_writer is not None else {})}), flush=True)
     control.barrier()
     control.close()
     if rccl_err is not None:

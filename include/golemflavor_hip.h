@@ -566,6 +566,45 @@ int gf_nested_regions(gf_nested* s, int64_t nrows, int nbins, int radius, const 
                       int64_t cap, int64_t* thres, int32_t* saturated, double* level_in, double* level_out, double* mass, int32_t* cells,
                       double* density);
 
+/* ---- the shortest interval around the mode of every column (golemflavor/misc.py:174-213) ------------------------- */
+/* Per chain and column of rows [nrows][width], with s the sorted column and n = nrows (csrc/gf_interval.hpp states every operation):
+ *   nbins    = floor((s[n-1] - s[0]) / (2 * n**(-1/3) * (p75 - p25))), p25 / p75 np.percentile's default (calc_nbins)
+ *   center   = the centre of the FIRST bin of maximal count of np.histogram(s, np.linspace(s[0], s[n-1] + 2, nbins + 1)) (most_likely)
+ *   low, up  = s[curr_low], s[curr_up] of misc.interval's walk from the first index nearest to center, for every percentile
+ *   nunique  = the number of distinct values (np.unique(column).shape, mcmc.py:47)
+ *   status   per (column, percentile): 0 ok; 1 the column holds a NaN or an infinity (this library's rule: low, up, center NaN,
+ *            nbins and nunique -1); 2 nbins is NaN, infinite or below 1, where the reference raises before the walk (a constant
+ *            column, a zero interquartile range, one row; nbins -1 for NaN); 3 the walk would index s[n], where the reference raises
+ *            IndexError (percentile 100, tiny n); 4 nbins above GF_INTERVAL_MAX_BINS, unsupported.  For 2 to 4 low and up are NaN
+ *            and center is given where it exists (3).
+ * The columns are sorted by a segmented radix sort on the device; the rows are only read.  Two key buffers per batch of chains come
+ * from the library's device cache, and the chains are processed batch after batch so that they stay under 2 GiB (one chain at
+ * least); no result depends on the batching.  width outside [1, GF_ELEMENT_MAX_WIDTH], nrows < 1, npct outside
+ * [1, GF_INTERVAL_MAX_PERCENTILES] or a percentile outside (0, 100]: GF_ERR_INVALID_ARG; nrows >= 2^31: GF_ERR_UNSUPPORTED. */
+#define GF_INTERVAL_MAX_BINS (1 << 20)
+#define GF_INTERVAL_MAX_PERCENTILES 8
+typedef struct gf_interval_spec { int32_t npct; const double* percentile; /* host [npct], percent in (0, 100] */ } gf_interval_spec;
+typedef struct gf_interval_out {                                              /* every pointer may be NULL */
+    double *low, *up;                         /* [nchains][width][npct] */
+    int32_t* status;                          /* [nchains][width][npct] */
+    double* center;                           /* [nchains][width] */
+    int64_t *nbins, *nunique;                 /* [nchains][width] */
+} gf_interval_out;
+/* device rows d_rows [nchains][nrows][width] -> d_sorted [nchains][width][nrows], every column ascending (-0.0 before +0.0, NaN
+ * last); both 8-byte aligned and not overlapping; synchronous */
+int gf_sort_columns_device(gf_model* m, const double* d_rows, int nchains, int64_t nrows, int width, double* d_sorted);
+/* rows on the device, chain after chain: d_rows [nchains][nrows][width]; host destinations; synchronous */
+int gf_column_intervals_device(gf_model* m, const double* d_rows, int nchains, int64_t nrows, int width, const gf_interval_spec* spec,
+                               const gf_interval_out* out);
+/* host rows [nrows][width] of one chain: upload, then the same path */
+int gf_column_intervals(gf_model* m, const double* rows, int64_t nrows, int width, const gf_interval_spec* spec, const gf_interval_out* out);
+/* the stored chains of a sampler: gf_sampler_marginals' rows (width = ndim, or 3 + ndim with_fr); nothing stored: GF_ERR_INVALID_ARG */
+int gf_sampler_intervals(gf_sampler* s, gf_model* const* models, int with_fr, const gf_interval_spec* spec, const gf_interval_out* out);
+/* the stored chains in element space: gf_sampler_element_marginals' rows */
+int gf_sampler_element_intervals(gf_sampler* s, const gf_element_plan* plan, const gf_interval_spec* spec, const gf_interval_out* out);
+/* the equal-weight rows of gf_nested_posterior_rows_device, nchains = nruns; a run without a posterior has NaN rows: status 1 */
+int gf_nested_intervals(gf_nested* s, int64_t nrows, int with_fr, const gf_interval_spec* spec, const gf_interval_out* out);
+
 #ifdef __cplusplus
 }
 #endif
