@@ -110,6 +110,16 @@ class GfIntervalOut(C.Structure):
     _fields_ = [("low", _dp), ("up", _dp), ("status", _ip), ("center", _dp), ("nbins", _lp), ("nunique", _lp)]
 
 
+class GfSpectrumSpec(C.Structure):
+    """struct gf_spectrum_spec, field for field."""
+    _fields_ = [("nbins1", C.c_int32), ("nq", C.c_int32), ("q", _dp)]
+
+
+class GfSpectrumOut(C.Structure):
+    """struct gf_spectrum_out, field for field; NULL = skip."""
+    _fields_ = [("nvalid", _lp), ("mean", _dp), ("cov", _dp), ("ostat", _dp), ("orank", _lp), ("counts", _up)]
+
+
 # name -> (restype, argtypes): every symbol include/golemflavor_hip.h declares
 SIGNATURES = {
     "gf_abi_version": (C.c_int, []),
@@ -221,6 +231,11 @@ SIGNATURES = {
     "gf_sampler_intervals": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(GfIntervalSpec), C.POINTER(GfIntervalOut)]),
     "gf_sampler_element_intervals": (C.c_int, [_vp, C.POINTER(GfElementPlan), C.POINTER(GfIntervalSpec), C.POINTER(GfIntervalOut)]),
     "gf_nested_intervals": (C.c_int, [_vp, C.c_int64, C.c_int, C.POINTER(GfIntervalSpec), C.POINTER(GfIntervalOut)]),
+    "gf_model_nbins": (C.c_int, [_vp]),
+    "gf_propagate_bins_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, _vp, C.c_int, _vp]),
+    "gf_propagate_bins": (C.c_int, [_vp, _dp, C.c_int64, _dp, _ip]),
+    "gf_sampler_spectrum": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(GfSpectrumSpec), C.POINTER(GfSpectrumOut)]),
+    "gf_nested_spectrum": (C.c_int, [_vp, C.c_int64, C.POINTER(GfSpectrumSpec), C.POINTER(GfSpectrumOut)]),
     "gf_nested_regions": (C.c_int, [_vp, C.c_int64, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int64, C.POINTER(C.c_int64), _ip, _dp, _dp, _dp, _ip, _dp]),
 }
 

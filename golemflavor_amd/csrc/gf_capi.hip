@@ -18,6 +18,7 @@
 #include "gf_consts.h"
 #include "gf_internal.h"                // every internal function defined here is compiled against the declaration its callers see
 #include "gf_launch.h"
+#include "gf_spectrum.h"
 #include "gf_devcache.h"                // large device allocations are cached, not handed back to the driver (hipMalloc / hipFree are macros from here on)
 
 static_assert(GF_MAX_DIM == 16 && GF_MAX_BINS == 64, "header / device constant mismatch");
@@ -802,6 +803,7 @@ void gf_model_destroy(gf_model* m)
 }
 
 int gf_model_ndim(const gf_model* m) { return m ? m->c.ndim : -1; }
+int gf_model_nbins(const gf_model* m) { return !m ? -1 : m->c.mode == GF_MODE_BSM_GAUSS ? m->hb.nbins : 0; }
 
 // internal (not in the public header): gf_sampler.hip reaches the model's constants and stream through these
 int gf_model_internal(gf_model* m, const GfCommon** c, const GfBsm** d_bsm, const double** d_ptab, void** stream, int* device)
@@ -885,6 +887,17 @@ int gf_model_propagate_on(gf_model* m, void* stream, const double* d_theta, int 
     if (!m || n < 0) return GF_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(m->call_mu);
     return launch_propagate(m, (hipStream_t)stream, d_theta, layout, n, d_fr, d_status);
+}
+
+// the composition at every energy bin (gf_spectrum.hip) on a stream of the caller's; values only, so no workspace and no lock
+int gf_model_bins_on(gf_model* m, void* stream, const double* d_theta, int layout, int64_t n, double* d_fr_bins, int bin_major,
+                     const int32_t* d_status)
+{
+    if (!m || n < 0) return GF_ERR_INVALID_ARG;
+    if (m->c.mode != GF_MODE_BSM_GAUSS || m->hb.nbins < 1) return GF_ERR_UNSUPPORTED;
+    const hipError_t e = gf_launch_bsm_bins(m->c, m->d_common, m->d_bsm, m->hb.nbins, m->d_ptab, d_theta, layout, n, d_fr_bins, bin_major,
+                                            d_status, m->cus, (hipStream_t)stream);
+    return e != hipSuccess ? hip_fail(e, "bins launch") : GF_OK;
 }
 
 // ---- host-buffer entry points ------------------------------------------------------------

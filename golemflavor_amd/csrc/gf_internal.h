@@ -21,6 +21,9 @@ int gf_model_constants(gf_model* m, const GfCommon** c, const GfBsm** d_bsm, con
 // the model's kernels on a stream of the caller's
 int gf_model_lnprob_on(gf_model* m, void* stream, const double* d_theta, int layout, int64_t n, double* d_lnprob, double* d_fr, int32_t* d_status);
 int gf_model_propagate_on(gf_model* m, void* stream, const double* d_theta, int layout, int64_t n, double* d_fr, int32_t* d_status);
+// k_bsm_bins (gf_spectrum.hip): d_fr_bins [n][nbins][3], or [nbins][n][3] with bin_major; BSM models only (else GF_ERR_UNSUPPORTED)
+int gf_model_bins_on(gf_model* m, void* stream, const double* d_theta, int layout, int64_t n, double* d_fr_bins, int bin_major,
+                     const int32_t* d_status);
 // streams of the device's pool (copy stream: for a large read-back that overlaps another stream's kernels); returned idle
 int gf_internal_borrow_stream(int device, void** stream);
 void gf_internal_return_stream(int device, void* stream);

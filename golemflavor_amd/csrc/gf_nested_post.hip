@@ -26,6 +26,7 @@
 #include "gf_marginal.h"
 #include "gf_nested_post.hpp"
 #include "gf_region.h"
+#include "gf_spectrum.h"
 
 namespace {
 using namespace gfnp;
@@ -544,6 +545,55 @@ int gf_nested_intervals(gf_nested* s, int64_t nrows, int with_fr, const gf_inter
     if (buf.get(&d_rows, bytes) != hipSuccess) return np_alloc_fail("gf_nested_intervals", bytes);
     rc = np_rows(s, nrows, with_fr, d_rows, nullptr, "gf_nested_intervals");
     return rc != GF_OK ? rc : gf_interval_run(v.stream, d_rows, nrows * width, v.nruns, nrows, width, spec, out, nullptr);
+}
+
+// the energy-resolved composition (gf_spectrum.hip) of every run's equal-weight rows, run after run through one bin-major slab; a run
+// without a posterior is not evaluated: nvalid 0, NaN moments and order statistics, rank -1, empty histograms
+int gf_nested_spectrum(gf_nested* s, int64_t nrows, const gf_spectrum_spec* spec, const gf_spectrum_out* out)
+{
+    GfNestedView v0;
+    if (gf_internal_nested_view(s, &v0, nullptr) != GF_OK || nrows < 1) return GF_ERR_INVALID_ARG;
+    int nbins_e = -1;
+    for (int r = 0; r < v0.nruns; ++r) {
+        const int nb = gf_model_nbins(v0.models[r]);
+        if (nb < 1) return GF_ERR_UNSUPPORTED;
+        if (nbins_e >= 0 && nb != nbins_e) return gf_fail_msg(GF_ERR_INVALID_ARG, "spectrum: run %d has %d energy bins, run 0 has %d", r, nb, nbins_e);
+        nbins_e = nb;
+    }
+    int rc = gf_spectrum_check_args(nbins_e, nrows, spec, out);
+    if (rc != GF_OK) return rc;
+    NpWork w;
+    rc = np_prepare(s, w, false, true, "gf_nested_spectrum");
+    if (rc != GF_OK) return rc;
+    const GfNestedView& v = w.a.v;
+    hipStream_t st = v.stream;
+    const size_t RN = (size_t)v.nruns * nrows;
+    int64_t* d_index = nullptr; double *d_theta = nullptr, *d_slab = nullptr; int32_t* d_st = nullptr;
+    size_t bad = 0;
+    if (!np_get(w, &d_index, sizeof(int64_t) * RN, &bad) || !np_get(w, &d_theta, sizeof(double) * RN * v.ndim, &bad) ||
+        !np_get(w, &d_slab, sizeof(double) * 3 * (size_t)nrows * nbins_e, &bad) || !np_get(w, &d_st, sizeof(int32_t) * (size_t)nrows, &bad))
+        return np_alloc_fail("gf_nested_spectrum", bad);
+    const int nb1 = spec->nbins1, R2 = 2 * spec->nq;
+    int rs = GF_OK;
+    rc = np_propagated(s, w, nrows, d_index, d_theta, d_slab, d_st, false, "gf_nested_spectrum",
+                       [&](int r, const double* th, const double*, const int32_t*) {
+                           rs = gf_model_bins_on(v.models[r], st, th, GF_LAYOUT_AOS, nrows, d_slab, 1, d_st);
+                           if (rs == GF_OK) rs = gf_spectrum_reduce(st, d_slab, nbins_e, nrows, spec, out, r);
+                           return rs == GF_OK ? hipSuccess : hipErrorUnknown;
+                       },
+                       [&](int r) {
+                           const size_t at = (size_t)r * nbins_e;
+                           for (size_t i = 0; i < (size_t)nbins_e; ++i) {
+                               if (out->nvalid) out->nvalid[at + i] = 0;
+                               for (int j = 0; j < 3 && out->mean; ++j) out->mean[(at + i) * 3 + j] = gfnp::nan();
+                               for (int j = 0; j < 9 && out->cov; ++j) out->cov[(at + i) * 9 + j] = gfnp::nan();
+                               for (int j = 0; j < 3 * R2 && out->ostat; ++j) out->ostat[(at + i) * 3 * R2 + j] = gfnp::nan();
+                               for (int j = 0; j < 3 * R2 && out->orank; ++j) out->orank[(at + i) * 3 * R2 + j] = -1;
+                               for (int j = 0; j < 3 * nb1 && out->counts; ++j) out->counts[(at + i) * 3 * nb1 + j] = 0;
+                           }
+                           return hipSuccess;
+                       });
+    return rs != GF_OK ? rs : rc;
 }
 
 int gf_nested_element_marginals(gf_nested* s, int64_t nrows, const gf_element_plan* plan, const gf_marginal_spec* spec, const gf_marginal_out* out)

@@ -11,6 +11,7 @@
 #include "gf_elements.h"
 #include "gf_diag.h"
 #include "gf_interval.h"
+#include "gf_spectrum.h"
 
 namespace {
 
@@ -333,6 +334,43 @@ int gf_sampler_element_intervals(gf_sampler* s, const gf_element_plan* plan, con
                                         per_chain * width, v.cus);
     if (e != hipSuccess) return gf_hip_fail(e, "gf_sampler_element_intervals");
     return gf_interval_run(st, d_rows, per_chain * width, v.nchains, per_chain, width, spec, out, nullptr);
+}
+
+// The energy-resolved composition of every stored chain (gf_spectrum.hip).  Chain after chain through one bin-major slab: the
+// propagation leaves the verdict in d_st (its compositions go to the head of the slab and are overwritten), k_bsm_bins fills the slab,
+// gf_marginal_run reduces it with the energy bins as its chains (synchronous, so the slab is free for the next chain).
+int gf_sampler_spectrum(gf_sampler* s, gf_model* const* models, const gf_spectrum_spec* spec, const gf_spectrum_out* out)
+{
+    GfChainView v; if (gf_internal_sampler_chain_view(s, &v) != GF_OK) return GF_ERR_INVALID_ARG;
+    const int64_t per_chain = v.nstored * v.nwalkers;
+    if (check_chain_models(v, models) != GF_OK) return GF_ERR_INVALID_ARG;
+    int nbins_e = -1;
+    for (int ch = 0; ch < v.nchains; ++ch) {
+        const int nb = gf_model_nbins(chain_model(v, models, ch));
+        if (nb < 1) return GF_ERR_UNSUPPORTED;
+        if (nbins_e >= 0 && nb != nbins_e) return gf_fail_msg(GF_ERR_INVALID_ARG, "spectrum: chain %d has %d energy bins, chain 0 has %d", ch, nb, nbins_e);
+        nbins_e = nb;
+    }
+    int rc = gf_spectrum_check_args(nbins_e, per_chain, spec, out);
+    if (rc != GF_OK) return rc;
+    GF_HIP(hipSetDevice(v.device));
+    hipStream_t st = v.stream;
+    GfScratch buf;
+    double* d_slab = nullptr; int32_t* d_st = nullptr;
+    hipError_t e = buf.get(&d_slab, sizeof(double) * 3 * (size_t)per_chain * nbins_e);
+    if (e == hipSuccess) e = buf.get(&d_st, sizeof(int32_t) * (size_t)per_chain);
+    if (e != hipSuccess) return gf_hip_fail(e, "gf_sampler_spectrum: scratch");
+    int rs = GF_OK;
+    rc = for_each_chain(v, models, d_slab, d_st, false, true, &e, [&](int ch, const double* d_theta, double*, int32_t*) {
+        rs = gf_model_bins_on(chain_model(v, models, ch), st, d_theta, GF_LAYOUT_AOS, per_chain, d_slab, 1, d_st);
+        if (rs == GF_OK) rs = gf_spectrum_reduce(st, d_slab, nbins_e, per_chain, spec, out, ch);
+        return rs == GF_OK ? hipSuccess : hipErrorUnknown;
+    });
+    e = first_error(e, hipStreamSynchronize(st));
+    if (rc != GF_OK) return rc;
+    if (rs != GF_OK) return rs;
+    if (e != hipSuccess) return gf_hip_fail(e, "gf_sampler_spectrum");
+    return gf_internal_check_overflow(v.device, st);
 }
 
 }  // extern "C"

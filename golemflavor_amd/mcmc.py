@@ -703,6 +703,34 @@ class DeviceEnsembleSampler:
         res = iv.run_interval_call(call, "gf_sampler_intervals", self.nchains, (3 if with_fr else 0) + self.dim, percentiles)
         return iv._squeeze(res, self.nchains == 1)
 
+    def spectrum(self, percentiles=(5, 16, 50, 84, 95), bins=50, models=None):
+        """The composition at every energy bin of the stored samples, reduced on the device (`spectrum.SpectrumResult`: nvalid,
+        mean, cov, percentiles and np.histogram(f, bins, range=(0, 1)) per energy bin and flavour), one per chain -- a list when
+        nchains > 1.  Chain ch is evaluated with models[ch] (None: the sampling models), as in `marginals`; every model must be a
+        BSM model with the same binning.  A sample the reference would have raised on has no composition at any energy.  Nothing
+        stored, or a model without energy bins: ValueError."""
+        from . import spectrum as sp
+        if self.nstored == 0:
+            raise ValueError("no stored samples: run_mcmc(..., storechain=True) first")
+        C = self._C
+        handles = None
+        if models is not None:
+            ms = [getattr(m, "model", m) for m in models]
+            if len(ms) != self.nchains:
+                raise ValueError("%d post-processing models for %d chains" % (len(ms), self.nchains))
+            handles = (C.c_void_p * self.nchains)(*[m._h.value if hasattr(m._h, "value") else m._h for m in ms])
+        else:
+            ms = list(self.models) if self.models is not None else [self.model]
+        edges = [sp.model_edges(m) for m in ms]
+        if any(not np.array_equal(e, edges[0]) for e in edges[1:]):
+            raise ValueError("the chains' models differ in their energy binning")
+        prep = sp.prepare(edges[0], percentiles, bins)
+
+        def call(spec, out):
+            return self._L.gf_sampler_spectrum(self._h, handles, spec, out)
+        res = sp.run_spectrum_call(call, "gf_sampler_spectrum", self.nchains, prep)
+        return res[0] if self.nchains == 1 else res
+
     def close(self):
         if getattr(self, "_h", None) is not None:
             self._L.gf_sampler_destroy(self._h)

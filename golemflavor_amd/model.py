@@ -217,6 +217,27 @@ class Model:
             st.ctypes.data_as(_lib._ip) if want_status else None), "gf_propagate_batch")
         return (fr, st) if want_status else fr
 
+    @property
+    def nbins(self):
+        """Energy bins of a BSM model, 0 for the other modes."""
+        return int(self._L.gf_model_nbins(self._h))
+
+    def propagate_bins(self, theta, want_status=True):
+        """theta (n, ndim) -> the composition at every energy bin (n, nbins, 3) [, status (n,)]: the terms flux_averaged_BSMu
+        (fr.py:441-457) averages, at the bin centres `spectrum.bin_tables(spectrum.model_edges(self))[0]`.  The status is
+        `propagate`'s; with it a row the reference would have raised on is NaN in every bin.  A model without energy bins
+        (SM, prior-only): ValueError, nothing is launched."""
+        nb = self.nbins
+        if nb < 1:
+            raise ValueError("propagate_bins needs a BSM model (mode BSM_GAUSS, with energy bins)")
+        th = _as_theta(theta, self.ndim)
+        n = th.shape[0]
+        fr = np.empty((n, nb, 3), dtype=np.float64)
+        st = np.empty(n, dtype=np.int32) if want_status else None
+        check(self._L.gf_propagate_bins(self._h, th.ctypes.data_as(_lib._dp), n, fr.ctypes.data_as(_lib._dp),
+                                        st.ctypes.data_as(_lib._ip) if want_status else None), "gf_propagate_bins")
+        return (fr, st) if want_status else fr
+
     def haar_draw(self, seed, n, first_draw=0, want_angles=False):
         fr = np.empty((n, 3), dtype=np.float64)
         ang = np.empty((n, 4), dtype=np.float64) if want_angles else None
@@ -250,6 +271,14 @@ class Model:
     def propagate_device(self, d_theta, n, d_fr, d_status=None, layout=GF_LAYOUT_AOS):
         check(self._L.gf_propagate_batch_device(self._h, d_theta, int(layout), int(n), d_fr, d_status),
               "gf_propagate_batch_device")
+
+    def propagate_bins_device(self, d_theta, n, d_fr_bins, d_status=None, bin_major=False, layout=GF_LAYOUT_AOS):
+        """`propagate_bins` on device buffers, asynchronous: d_fr_bins [n][nbins][3], or [nbins][n][3] with bin_major; d_status [n]
+        as `propagate_device` wrote it for the same rows (None: nothing is masked)."""
+        if self.nbins < 1:
+            raise ValueError("propagate_bins_device needs a BSM model (mode BSM_GAUSS, with energy bins)")
+        check(self._L.gf_propagate_bins_device(self._h, d_theta, int(layout), int(n), d_fr_bins, int(bool(bin_major)), d_status),
+              "gf_propagate_bins_device")
 
     def haar_draw_device(self, seed, first_draw, n, d_angles, d_fr):
         check(self._L.gf_haar_draw_device(self._h, int(seed), int(first_draw), int(n), d_angles, d_fr),

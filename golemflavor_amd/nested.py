@@ -230,6 +230,22 @@ class NestedSampler(_CubeRuns):
             return self._L.gf_nested_intervals(self._h, int(nrows), int(bool(with_fr)), spec, out)
         return iv.run_interval_call(call, "gf_nested_intervals", self.nruns, (3 if with_fr else 0) + self.ndim, percentiles)
 
+    def spectrum(self, nrows, percentiles=(5, 16, 50, 84, 95), bins=50):
+        """The composition at every energy bin of every run's `nrows` equal-weight rows, reduced on the device: one
+        `spectrum.SpectrumResult` per run.  A run without a posterior has nvalid 0 and NaN moments.  Models without energy bins:
+        ValueError."""
+        from . import spectrum as sp
+        edges = [sp.model_edges(m) for m in self.models]
+        if any(not np.array_equal(e, edges[0]) for e in edges[1:]):
+            raise ValueError("the runs' models differ in their energy binning")
+        if int(nrows) < 1:
+            raise ValueError("nrows must be at least 1")
+        prep = sp.prepare(edges[0], percentiles, bins)
+
+        def call(spec, out):
+            return self._L.gf_nested_spectrum(self._h, int(nrows), spec, out)
+        return sp.run_spectrum_call(call, "gf_nested_spectrum", self.nruns, prep)
+
     def regions(self, nrows, nbins, coverage, hist_smooth=0.05, oversample=1., truncate=4.0, cap=None):
         """The flavor-triangle credible regions (`DeviceEnsembleSampler.regions`'s reduction) of every run's `nrows` equal-weight
         rows propagated with the run's model: [run] of `contour.RegionResult` (of lists of them for several coverages)."""
@@ -382,7 +398,8 @@ def evidence_scan(args, asimov_paramset, llh_paramset, scales, run_ids=None, nli
     (source_ratio, dimension, texture, binning) plus the --mn-* options.  Returns dict(scales, lnz, lnz_err, max_lnl, niter,
     nevals, nonunitary, seconds).  posterior=dict(nrows=..., elements=False, and `NestedSampler.marginals`'s keyword arguments):
     the result also carries "posterior" (`NestedSampler.posterior()`), "marginals" ([scale] MarginalResult over llh_paramset's
-    columns) and, with elements, "marginals_elements", computed before the sampler is closed."""
+    columns) and, with elements, "marginals_elements"; spectrum=[percentiles] adds "spectrum" ([scale] `spectrum.SpectrumResult`); all
+    computed before the sampler is closed."""
     import time
     scales = np.asarray(scales, dtype=np.float64)
     cols, models, bases, labels = _scan_models(args, asimov_paramset, llh_paramset, scales, smearing, device)
@@ -399,12 +416,15 @@ def evidence_scan(args, asimov_paramset, llh_paramset, scales, run_ids=None, nli
             if posterior is not None:
                 kw = dict(posterior)
                 nrows, elements = int(kw.pop("nrows")), bool(kw.pop("elements", False))
+                spectrum = kw.pop("spectrum", None)
                 kw.setdefault("names", list(llh_paramset.names))
                 kw.setdefault("ranges", [tuple(float(v) for v in p.ranges) for p in llh_paramset])
                 post = dict(posterior=s.posterior(), marginals=s.marginals(nrows, **kw))
                 if elements:
                     ekw = {k: v for k, v in kw.items() if k not in ("names", "ranges")}
                     post["marginals_elements"] = s.marginals(nrows, space="elements", llh_paramset=llh_paramset, **ekw)
+                if spectrum is not None:
+                    post["spectrum"] = s.spectrum(nrows, percentiles=spectrum)
                 res.update(post)
         finally:
             if not return_sampler:

@@ -340,6 +340,33 @@ class MarginalWriter:
         MARGINAL_STATS.update({"bins": [self.kw["bins_1d"], self.kw["bins_2d"]], "points": self.points, "seconds": round(self.seconds, 4)})
 
 
+SPECTRUM_STATS = {}   # the last run_points call with --spectrum: what it computed on this rank (reported by main)
+
+
+class SpectrumWriter:
+    """--spectrum: the composition at every energy bin of every grid point's chain (`DeviceEnsembleSampler.spectrum`: nvalid, mean,
+    covariance, percentiles and histograms per energy bin and flavour), computed while the point's sampler still holds its chain
+    and saved as spectrum_<point file name>.npz beside the chain file: `spectrum.SpectrumResult.as_arrays()`."""
+
+    def __init__(self, datadir, name_of, percentiles=(5., 16., 50., 84., 95.), bins=50):
+        self.datadir, self.name_of, self.percentiles, self.bins = datadir, name_of, [float(q) for q in percentiles], int(bins)
+        self.seconds, self.points, self.no_composition = 0.0, 0, 0
+
+    def take(self, sampler, models, order):
+        t0 = time.perf_counter()
+        res = sampler.spectrum(percentiles=self.percentiles, bins=self.bins, models=models)
+        per_chain = sampler.nstored * sampler.k
+        os.makedirs(self.datadir, exist_ok=True)
+        for g, r in zip(order, [res] if len(order) == 1 else res):
+            r.save(os.path.join(self.datadir, "spectrum_%s.npz" % self.name_of(g)))
+            self.points += 1
+            self.no_composition += per_chain - int(r.nvalid[0])
+        self.seconds += time.perf_counter() - t0
+        SPECTRUM_STATS.clear()
+        SPECTRUM_STATS.update({"percentiles": self.percentiles, "bins": self.bins, "points": self.points, "seconds": round(self.seconds, 4),
+                               "samples_without_composition": self.no_composition})
+
+
 DIAGNOSTIC_STATS = {}   # the last run_points call with --diagnostics: what it computed on this rank (reported by main)
 
 
@@ -838,6 +865,10 @@ def main(argv=None):
     ap.add_argument("--intervals", type=float, nargs="*", default=None, metavar="P",
                     help="also save every grid point's shortest intervals around the mode (misc.interval; default 68 90) and distinct "
                          "values per column, intervals_<point>.npz beside the chain file; needs --datadir")
+    ap.add_argument("--spectrum", type=float, nargs="*", default=None, metavar="Q",
+                    help="also save every grid point's composition per energy bin (mean, covariance, percentiles Q -- default 5 16 50 "
+                         "84 95 -- and histograms), spectrum_<point>.npz beside the chain file; needs --datadir and a BSM configuration")
+    ap.add_argument("--spectrum-bins", type=int, default=50, help="histogram bins per flavour over [0, 1] of --spectrum")
     ap.add_argument("--marginal-bins-1d", type=int, default=100)
     ap.add_argument("--marginal-bins-2d", type=int, default=50)
     ap.add_argument("--marginal-coverage", type=float, nargs="+", default=[90., 99.], metavar="COVERAGE")
@@ -853,6 +884,14 @@ def main(argv=None):
         a.intervals = a.intervals or [68., 90.]
         if not 1 <= len(a.intervals) <= 8 or not all(0. < p <= 100. for p in a.intervals):
             ap.error("--intervals takes up to 8 percentiles in (0, 100]")
+    if a.spectrum is not None:
+        if not a.datadir:
+            ap.error("--spectrum needs --datadir (the spectra are saved beside the chain files)")
+        a.spectrum = a.spectrum or [5., 16., 50., 84., 95.]
+        if not 1 <= len(a.spectrum) <= 8 or not all(0. <= q <= 100. for q in a.spectrum):
+            ap.error("--spectrum takes up to 8 percentiles in [0, 100]")
+        if not 1 <= a.spectrum_bins <= 1024:
+            ap.error("--spectrum-bins must lie in [1, 1024]")
     if a.marginals:
         if not a.datadir:
             ap.error("--marginals needs --datadir (the marginals are saved beside the chain files)")
@@ -920,8 +959,11 @@ def main(argv=None):
     region_stats_wanted = regions is not None
     diagnostics_writer = DiagnosticsWriter(a.datadir, lambda g: point_filename(a.config, pts[g], a)) if a.diagnostics else None
     interval_writer = IntervalWriter(a.datadir, lambda g: point_filename(a.config, pts[g], a), a.intervals) if a.intervals is not None else None
-    if marginal_writer is not None or diagnostics_writer is not None or interval_writer is not None:
-        regions = _Takers([t for t in (regions, marginal_writer, diagnostics_writer, interval_writer) if t is not None])
+    spectrum_writer = None
+    if a.spectrum is not None:
+        spectrum_writer = SpectrumWriter(a.datadir, lambda g: point_filename(a.config, pts[g], a), a.spectrum, a.spectrum_bins)
+    if marginal_writer is not None or diagnostics_writer is not None or interval_writer is not None or spectrum_writer is not None:
+        regions = _Takers([t for t in (regions, marginal_writer, diagnostics_writer, interval_writer, spectrum_writer) if t is not None])
     if a.datadir and not want_gather:
         local = run_points(pts, mine, make, a.burnin, a.nsteps, stacked=stacked, regions=regions)
         gather_name = "none: every rank saved its own files (--datadir)"
@@ -979,7 +1021,8 @@ def main(argv=None):
                           "finite_fraction": finite, **({"regions": REGION_STATS} if region_stats_wanted else {}),
                           **({"marginals": MARGINAL_STATS} if marginal_writer is not None else {}),
                           **({"diagnostics": DIAGNOSTIC_STATS} if diagnostics_writer is not None else {}),
-                          **({"intervals": INTERVAL_STATS} if interval_writer is not None else {})}), flush=True)
+                          **({"intervals": INTERVAL_STATS} if interval_writer is not None else {}),
+                          **({"spectrum": SPECTRUM_STATS} if spectrum_writer is not None else {})}), flush=True)
     control.barrier()
     control.close()
     if rccl_err is not None:

@@ -77,9 +77,18 @@ def parse_args(argv=None):
                          % DEFAULT_POSTERIOR_ROWS)
     ap.add_argument("--posterior-elements", action="store_true",
                     help="with --posterior: also save the marginals in element space, posterior_elements_<...>.npz")
+    ap.add_argument("--posterior-spectrum", type=float, nargs="*", default=None, metavar="Q",
+                    help="with --posterior: also save every scale's composition per energy bin (mean, covariance, percentiles Q -- "
+                         "default 5 16 50 84 95 -- and histograms of the equal-weight rows), posterior_spectrum_<...>.npz")
     args = ap.parse_args(argv)
     if args.posterior_elements and not args.posterior:
         ap.error("--posterior-elements needs --posterior (it adds the element-space marginals to it)")
+    if args.posterior_spectrum is not None:
+        if not args.posterior:
+            ap.error("--posterior-spectrum needs --posterior (it adds the composition per energy bin to it)")
+        args.posterior_spectrum = args.posterior_spectrum or [5., 16., 50., 84., 95.]
+        if not 1 <= len(args.posterior_spectrum) <= 8 or not all(0. <= q <= 100. for q in args.posterior_spectrum):
+            ap.error("--posterior-spectrum takes up to 8 percentiles in [0, 100]")
     if args.posterior:
         if not args.datadir:
             ap.error("--posterior needs --datadir (the posteriors are saved beside the fr_stat arrays)")
@@ -118,6 +127,26 @@ def posterior_path(args, scale, elements=False):
                                                                        np.power(10., scale)))
 
 
+def spectrum_path(args, scale):
+    """posterior_spectrum<identifier>_scale_<10^scale:.0E>.npz beside the posterior files."""
+    base = os.path.join(args.datadir, args.stat_method.name.lower(), args.data.name.lower())
+    return os.path.join(base, "posterior_spectrum{0}_scale_{1:.0E}.npz".format(chain_identifier(args), np.power(10., scale)))
+
+
+def save_spectra(args, scales, res):
+    """One .npz per scale: `SpectrumResult.as_arrays()` plus the scale."""
+    files = []
+    for k, sc in enumerate(scales):
+        arrays = res["spectrum"][k].as_arrays()
+        arrays.update(scale=np.float64(sc))
+        f = spectrum_path(args, sc)
+        os.makedirs(os.path.dirname(f) or ".", exist_ok=True)
+        with open(f, "wb") as fh:
+            np.savez(fh, **arrays)
+        files.append(f)
+    return files
+
+
 def save_posteriors(args, scales, res):
     """One .npz per scale: `MarginalResult.as_arrays()` plus ess, npoints, mean, cov (and lnz_check, scale)."""
     files = []
@@ -149,6 +178,8 @@ def main(argv=None):
     if args.stat_method is StatCateg.FREQUENTIST:
         return _frequentist(args, scales, idx, asimov, llh_ps, outfile, outfile_llh)
     post = dict(nrows=args.posterior_rows, elements=args.posterior_elements) if args.posterior else None
+    if post is not None and args.posterior_spectrum is not None:
+        post["spectrum"] = args.posterior_spectrum
     res = nested.evidence_scan(args, asimov, llh_ps, scales[idx], run_ids=idx, on_nonunitary=args.on_nonunitary,
                                device=args.device, posterior=post)
     evidence_arr = np.stack([scales[idx], res["lnz"]], axis=1)
@@ -157,6 +188,8 @@ def main(argv=None):
         os.makedirs(os.path.dirname(f) or ".", exist_ok=True)
         np.save(f + ".npy", arr)
     posterior_files = save_posteriors(args, scales[idx], res) if args.posterior else None
+    if posterior_files is not None and "spectrum" in res:
+        posterior_files += save_spectra(args, scales[idx], res)
     print(json.dumps({
         **({"posterior": posterior_files} if posterior_files is not None else {}),
         "tool": "golemflavor_amd.sens", "dimension": args.dimension, "texture": args.texture.name,

@@ -142,6 +142,7 @@ int gf_device_name(int device, char* buf, size_t buflen);   /* gcnArchName, e.g.
 int gf_model_create(const gf_model_desc* desc, int device, gf_model** out);
 void gf_model_destroy(gf_model* m);
 int gf_model_ndim(const gf_model* m);
+int gf_model_nbins(const gf_model* m);   /* energy bins of a GF_MODE_BSM_GAUSS model, 0 for the other modes */
 
 /* ---- the hot path, host buffers --------------------------------------------------------- */
 /* lnprob[i] = ln_prob(theta[i]) for i < n.  Replaces the per-walker Python callback
@@ -604,6 +605,42 @@ int gf_sampler_intervals(gf_sampler* s, gf_model* const* models, int with_fr, co
 int gf_sampler_element_intervals(gf_sampler* s, const gf_element_plan* plan, const gf_interval_spec* spec, const gf_interval_out* out);
 /* the equal-weight rows of gf_nested_posterior_rows_device, nchains = nruns; a run without a posterior has NaN rows: status 1 */
 int gf_nested_intervals(gf_nested* s, int64_t nrows, int with_fr, const gf_interval_spec* spec, const gf_interval_out* out);
+
+/* ---- the composition at every energy bin (golemflavor/fr.py:441-457 before its mean) ---------------------------------- */
+/* flux_averaged_BSMu evaluates u_to_fr(source, params_to_BSMu(..., energy = E_k)) at the centre E_k = sqrt(b_k b_{k+1}) of every bin
+ * (fr.py:413) and returns the width-weighted mean; these entry points return the nbins = gf_model_nbins(m) terms themselves, the same
+ * arithmetic bit for bit: (f_e, f_mu) as the average forms them and f_tau = (1 - f_e) - f_mu.  Values only: a row the reference
+ * would have raised on (fr.py:398-399 raises inside flux_averaged_BSMu at the FIRST failing bin, so such a sample has no composition
+ * at any energy) is one whose status by the existing propagate path is not GF_ST_OK, and it gets NaN in EVERY bin.  A model that
+ * is not GF_MODE_BSM_GAUSS: GF_ERR_UNSUPPORTED. */
+/* d_fr_bins [n][nbins][3], or bin-major [nbins][n][3] (bin_major != 0); d_status [n] as gf_propagate_batch_device wrote it for the
+ * same rows, or NULL: nothing is masked.  Asynchronous on the model's stream. */
+int gf_propagate_bins_device(gf_model* m, const double* d_theta, int layout, int64_t n, double* d_fr_bins, int bin_major,
+                             const int32_t* d_status);
+/* host rows: upload, the existing propagate for the status (status != NULL), the kernel, download.  fr_bins [n][nbins][3], status [n] */
+int gf_propagate_bins(gf_model* m, const double* theta, int64_t n, double* fr_bins, int32_t* status);
+/* The posterior of the composition as a function of energy.  Per chain and energy bin k the rows (f_e, f_mu, f_tau)_k of the chain's
+ * samples are reduced as gf_marginals_device reduces the rows of a chain (same kernels, the energy bins taking the place of the
+ * chains): histograms np.histogram(f, bins = nbins1, range = (0, 1)) per flavour, nvalid / mean / cov (ddof 1) over the samples with
+ * a composition, and for every q (percent) the two order statistics np.percentile's `linear` rule reads.  Host arrays, each may be
+ * NULL, nbinsE = the model's energy bins (the same for every chain):
+ *   nvalid [nchains][nbinsE], mean [nchains][nbinsE][3], cov [nchains][nbinsE][3][3],
+ *   ostat, orank [nchains][nbinsE][3][2 nq], counts [nchains][nbinsE][3][nbins1]
+ * nbins1 in [1, 1024], nq <= GF_MARGINAL_MAX_RANKS / 2. */
+typedef struct gf_spectrum_spec { int32_t nbins1, nq; const double* q; /* host [nq], percent in [0, 100] */ } gf_spectrum_spec;
+typedef struct gf_spectrum_out {
+    int64_t* nvalid;
+    double *mean, *cov;
+    double* ostat; int64_t* orank;
+    uint64_t* counts;
+} gf_spectrum_out;
+/* every stored chain of a sampler, chain ch evaluated with models[ch] (NULL: the sampling models), chain after chain on the sampler's
+ * stream through ONE bin-major slab [nbinsE][nstored nwalkers][3] of scratch (plus the status array and the reduction's buffers);
+ * nothing stored: GF_ERR_INVALID_ARG; synchronous */
+int gf_sampler_spectrum(gf_sampler* s, gf_model* const* models, const gf_spectrum_spec* spec, const gf_spectrum_out* out);
+/* the nrows equal-weight posterior rows of every run (gf_nested_posterior_rows_device), nchains = nruns; a run without a posterior
+ * has nvalid 0 and NaN moments */
+int gf_nested_spectrum(gf_nested* s, int64_t nrows, const gf_spectrum_spec* spec, const gf_spectrum_out* out);
 
 #ifdef __cplusplus
 }
