@@ -2,7 +2,7 @@
 nested_post_host.cpp, g++ with contraction off), seeded log-weight profiles, a numpy restatement of the prefix order the header fixes, a
 np.longdouble evaluation of the definitions, and the error bounds that follow from the orders.
 
-Used by tests/test_nested_posterior_host.py (CPU) and tests/test_gpu_nested_posterior.py."""
+Used by tests/test_nested_posterior_host.py (CPU), tests/test_gpu_nested_posterior.py and tests/test_gpu_nested_posterior_shapes.py."""
 import ctypes as C
 import os
 import subprocess
@@ -134,6 +134,23 @@ def profile(kind, n, seed):
     theta = rng.uniform(-2.0, 3.0, size=(n, 3))
     theta[:, 1] = 0.625
     return lnw, theta, np.array([0, 1, 0], np.int32)
+
+
+WIDE_NDIM, WIDE_FIXED = 12, {3: -41.5, 11: 0.625}          # sens.py's width; the fixed columns at odd positions, the last one among them
+
+
+def profile_wide(kind, n, seed):
+    """profile()'s log-weights with theta [n][12]: ten scanned columns of different centre and width (two of them correlated), the
+    columns of WIDE_FIXED fixed at its values."""
+    lnw = profile(kind, n, seed)[0]
+    rng = np.random.default_rng(seed + 1000)
+    theta = rng.uniform(-1.0, 1.0, size=(n, WIDE_NDIM)) * (0.25 + np.arange(WIDE_NDIM)) + np.linspace(-40.0, 3.0, WIDE_NDIM)
+    theta[:, 5] = 0.5 * theta[:, 4] + 0.1 * theta[:, 5]
+    fixed = np.zeros(WIDE_NDIM, np.int32)
+    for c, v in WIDE_FIXED.items():
+        theta[:, c] = v
+        fixed[c] = 1
+    return lnw, theta, fixed
 
 
 # ---- the prefix order of gf_nested_post.hpp in numpy (np.cumsum is strictly sequential) -------------------------------------------------

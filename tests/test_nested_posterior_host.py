@@ -84,6 +84,30 @@ def test_weights_ess_mean_cov_within_derived_bounds(runs, kind):
             assert not np.isfinite(h["cov"][0, 0])
 
 
+@pytest.mark.parametrize("n", (4097, 9001, 65537))
+@pytest.mark.parametrize("kind", ("generic", "plateau", "span600"))
+def test_twelve_columns_two_fixed_within_derived_bounds(kind, n):
+    """sens.py's width beyond one leaf (2, 3 and 17 leaves), H.profile_wide: the scanned columns within H.bounds of numpy's
+    definitions in long double; the fixed columns' means their values and their covariances zero, exactly; cov symmetric bit for bit.
+    This is the width and the length at which the GPU tests take the host build as their reference."""
+    lnw, theta, fixed = H.profile_wide(kind, n, 1)
+    h, ex = H.host_posterior(lnw, theta, fixed), H.exact_posterior(lnw, theta)
+    b = H.bounds(n, ex)
+    sc, fx = np.flatnonzero(fixed == 0), np.flatnonzero(fixed)
+    assert fx.tolist() == sorted(H.WIDE_FIXED) and all(c % 2 for c in fx) and len(sc) == 10
+    dm, dc = np.abs(h["mean"] - ex["mean"])[sc], np.abs(h["cov"] - ex["cov"])[np.ix_(sc, sc)]
+    print("%s n %d: largest error / bound: mean %.2e cov %.2e ess %.2e" % (kind, n, (dm / b["mean"][sc]).max(), (dc / b["cov"][np.ix_(sc, sc)]).max(),
+                                                                         abs(h["ess"] - ex["ess"]) / b["ess"]))
+    assert abs(h["ess"] - ex["ess"]) <= b["ess"]
+    assert np.all(dm <= b["mean"][sc]), (dm, b["mean"][sc])
+    assert np.all(dc <= b["cov"][np.ix_(sc, sc)]), (dc.max(), b["cov"].max())
+    assert np.all(np.diag(h["cov"])[sc] > 0)
+    for c in fx:
+        assert h["mean"][c] == H.WIDE_FIXED[c]
+        assert np.all(h["cov"][c] == 0.0) and np.all(h["cov"][:, c] == 0.0) and not np.signbit(h["cov"][c]).any() and not np.signbit(h["cov"][:, c]).any()
+    assert H.same_bits(h["cov"], h["cov"].T)
+
+
 @pytest.mark.parametrize("kind", H.PROFILES)
 def test_prefix_and_index_equal_numpy(runs, kind):
     """C bit for bit against the header's blocked order restated with np.cumsum, and within its bound of np.cumsum in long double;
