@@ -23,6 +23,7 @@ GF_ELEMENT_COPY, GF_ELEMENT_U9, GF_ELEMENT_FR3 = range(3)
 GF_DIAG_MAX_STEPS = 16384
 GF_INTERVAL_MAX_BINS = 1 << 20
 GF_INTERVAL_MAX_PERCENTILES = 8
+GF_REWEIGHT_MAX_TARGETS = 64
 
 GF_OK, GF_ERR_INVALID_ARG, GF_ERR_NO_DEVICE, GF_ERR_HIP, GF_ERR_ALLOC, GF_ERR_COMM, GF_ERR_UNSUPPORTED, GF_ERR_QUEUE_OVERFLOW = range(8)
 GF_ST_OK, GF_ST_OUT_OF_PRIOR, GF_ST_NON_UNITARY, GF_ST_NAN = range(4)
@@ -118,6 +119,17 @@ class GfSpectrumSpec(C.Structure):
 class GfSpectrumOut(C.Structure):
     """struct gf_spectrum_out, field for field; NULL = skip."""
     _fields_ = [("nvalid", _lp), ("mean", _dp), ("cov", _dp), ("ostat", _dp), ("orank", _lp), ("counts", _up)]
+
+
+class GfReweightSpec(C.Structure):
+    """struct gf_reweight_spec, field for field."""
+    _fields_ = [("ntargets", C.c_int32), ("use_sampler_seed", C.c_int32), ("seed", C.c_uint64), ("models", C.POINTER(_vp)),
+                ("bestfit_fr", _dp), ("smearing", _dp), ("offset", _dp)]
+
+
+class GfReweightOut(C.Structure):
+    """struct gf_reweight_out, field for field; NULL = skip."""
+    _fields_ = [("ess", _dp), ("lnz_ratio", _dp), ("mean", _dp), ("cov", _dp), ("bad_base", _lp), ("nonunitary", _lp), ("outside", _lp), ("n", _lp)]
 
 
 # name -> (restype, argtypes): every symbol include/golemflavor_hip.h declares
@@ -237,6 +249,14 @@ SIGNATURES = {
     "gf_sampler_spectrum": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(GfSpectrumSpec), C.POINTER(GfSpectrumOut)]),
     "gf_nested_spectrum": (C.c_int, [_vp, C.c_int64, C.POINTER(GfSpectrumSpec), C.POINTER(GfSpectrumOut)]),
     "gf_nested_regions": (C.c_int, [_vp, C.c_int64, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int64, C.POINTER(C.c_int64), _ip, _dp, _dp, _dp, _ip, _dp]),
+    "gf_sampler_reweight": (C.c_int, [_vp, C.POINTER(GfReweightSpec), C.POINTER(GfReweightOut)]),
+    "gf_sampler_reweight_lnw": (C.c_int, [_vp, C.POINTER(GfReweightSpec), C.c_int, _dp]),
+    "gf_sampler_reweight_rows_device": (C.c_int, [_vp, C.POINTER(GfReweightSpec), C.c_int64, C.c_int, _vp]),
+    "gf_sampler_reweight_rows": (C.c_int, [_vp, C.POINTER(GfReweightSpec), C.c_int64, C.c_int, _dp, _lp]),
+    "gf_sampler_reweight_marginals": (C.c_int, [_vp, C.POINTER(GfReweightSpec), C.c_int64, C.c_int, C.POINTER(GfMarginalSpec), C.POINTER(GfMarginalOut)]),
+    "gf_sampler_reweight_intervals": (C.c_int, [_vp, C.POINTER(GfReweightSpec), C.c_int64, C.c_int, C.POINTER(GfIntervalSpec), C.POINTER(GfIntervalOut)]),
+    "gf_sampler_reweight_regions": (C.c_int, [_vp, C.POINTER(GfReweightSpec), C.c_int64, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int64, _lp, _ip, _dp, _dp,
+                                              _dp, _ip, _dp]),
 }
 
 _lib = None

@@ -570,6 +570,17 @@ int gf_device_name(int device, char* buf, size_t buflen)
     return GF_OK;
 }
 
+// multi_gaussian, llh.py:53-54 + scipy _multivariate.py:514-539 for cov = smearing^2 I (gf_reweight.hip builds a measurement target's
+// constants with it, so that they are the bits a model of that measurement holds)
+void gf_internal_gauss_consts(double smearing, double* inv_smear, double* c0, double* mh, double* k)
+{
+    const double s = std::pow(smearing, 2);
+    *inv_smear = std::sqrt(1.0 / s);
+    *c0 = 3.0 * std::log(2.0 * M_PI) + ((std::log(s) + std::log(s)) + std::log(s));
+    *mh = -0.5 * (*inv_smear * *inv_smear);
+    *k = -0.5 * *c0;
+}
+
 int gf_model_create(const gf_model_desc* d, int device, gf_model** out)
 {
     if (!d || !out) return GF_ERR_INVALID_ARG;
@@ -650,11 +661,7 @@ int gf_model_create(const gf_model_desc* d, int device, gf_model** out)
     // multi_gaussian, llh.py:53-54 + scipy _multivariate.py:514-539: cov = smearing^2 I
     if (d->mode != GF_MODE_PRIOR_ONLY) {
         if (!(d->smearing > 0.0) || !finite_all(d->bestfit_fr, 3)) { delete m; return GF_ERR_INVALID_ARG; }
-        const double s = std::pow(d->smearing, 2);
-        c.inv_smear = std::sqrt(1.0 / s);
-        c.gauss_c0 = 3.0 * std::log(2.0 * M_PI) + ((std::log(s) + std::log(s)) + std::log(s));
-        c.gauss_mh = -0.5 * (c.inv_smear * c.inv_smear);
-        c.gauss_k = -0.5 * c.gauss_c0;
+        gf_internal_gauss_consts(d->smearing, &c.inv_smear, &c.gauss_c0, &c.gauss_mh, &c.gauss_k);
     }
     c.offset = d->offset;
     c.flat_llh = d->flat_llh;

@@ -18,6 +18,8 @@ void gf_internal_set_error(const char* msg);                          // the tex
 // gf_model is private to gf_capi.hip: its constants, and (gf_model_internal: sets the device, gives the model a stream) its stream
 int gf_model_internal(gf_model* m, const GfCommon** c, const GfBsm** d_bsm, const double** d_ptab, void** stream, int* device);
 int gf_model_constants(gf_model* m, const GfCommon** c, const GfBsm** d_bsm, const double** d_ptab, int* device, int* cus, int* nbins);
+// the constants of multi_gaussian for cov = smearing^2 I, as gf_model_create derives them: logpdf = fma(mh, |fr - bf|^2, k)
+void gf_internal_gauss_consts(double smearing, double* inv_smear, double* c0, double* mh, double* k);
 // the model's kernels on a stream of the caller's
 int gf_model_lnprob_on(gf_model* m, void* stream, const double* d_theta, int layout, int64_t n, double* d_lnprob, double* d_fr, int32_t* d_status);
 int gf_model_propagate_on(gf_model* m, void* stream, const double* d_theta, int layout, int64_t n, double* d_fr, int32_t* d_status);
@@ -56,6 +58,9 @@ struct GfChainView {              // the stored chain of a sampler, as post-proc
     int64_t nstored, nstore_cap;
     const double* d_chain;        // [nchains][nstore_cap][nwalkers][ndim]
     gf_model* model; gf_model* const* models;   // chain 0's, and one per chain or NULL
+    const double* d_lnp_chain;    // [nchains][nstore_cap][nwalkers]: the stored ln_prob of every sample
+    uint64_t seed;                // Philox key
+    const uint64_t* d_stream_ids; // [nchains] the chains' random stream ids, NULL: chain ch has id ch
 };
 int gf_internal_sampler_chain_view(const gf_sampler* s, GfChainView* v);
 // k_walker_mean on `stream`: chain [nchains][cap][nwalkers][ndim] -> mean [nchains][nstored][ndim], the ensemble mean of every step

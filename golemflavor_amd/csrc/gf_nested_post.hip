@@ -10,6 +10,8 @@
 //                      three launches, no workgroup waits for another
 //   k_np_resample      one lane per output row: the binary search of t_k in the run's C
 //   k_np_rows          the rows, consecutive lanes on consecutive columns
+// Only k_np_gather reads the sampler's view; the others take a GfWeightArgs (gf_weights.h) and are launched through gf_weights_launch,
+// gf_weights_resample and gf_weights_rows, here and from gf_reweight.hip (a stored chain's targets as runs that share one theta).
 // The equal-weight rows [nruns][nrows][width] then go through the reductions the MCMC chains go through (gf_marginal.hip,
 // gf_elements.hip, gf_region.hip) with nchains = nruns.
 #include <hip/hip_runtime.h>
@@ -27,6 +29,7 @@
 #include "gf_nested_post.hpp"
 #include "gf_region.h"
 #include "gf_spectrum.h"
+#include "gf_weights.h"
 
 namespace {
 using namespace gfnp;
@@ -34,28 +37,19 @@ using namespace gfnp;
 constexpr int NP_BLOCK = LANES;
 constexpr int NP_WAVE = 64;
 enum { STAGE_MAX = 0, STAGE_EXP = 1, STAGE_MOM = 2, STAGE_COV = 3 };
-enum { ST_M = 0, ST_S = 1, ST_S2 = 2, ST_ESS = 3, ST_SP = 4, ST_SP2 = 5, ST_FACT = 6, NP_STAT = 8 };
+enum { ST_M = GF_WST_M, ST_S = GF_WST_S, ST_S2 = GF_WST_S2, ST_ESS = GF_WST_ESS, ST_SP = GF_WST_SP, ST_SP2 = GF_WST_SP2, ST_FACT = GF_WST_FACT,
+       NP_STAT = GF_WEIGHT_STAT };
+static_assert(LEAF == GF_WEIGHT_LEAF && MAX_DIM == GF_MAX_DIM && NP_WAVE == GF_WEIGHT_TOT_PER_LEAF, "gf_weights.h states the header's sizes");
 constexpr int np_stage_k(int stage) { return stage == STAGE_MAX ? 1 : stage == STAGE_EXP ? 2 : stage == STAGE_MOM ? 2 + MAX_DIM : MAX_DIM * MAX_DIM; }
 
-struct NpRun {
-    int64_t off, n, nd;     // first point in the compact arrays; points (0: no posterior); dead points among them
-    double lnw0;            // ln X_final - ln nlive
-};
+// what the kernels see (gf_weights.h): only k_np_gather reads the sampler's view
+using NpRun = GfWeightRun;
+using NpArgs = GfWeightArgs;
+static_assert(np_stage_k(STAGE_COV) == GF_WEIGHT_PART_COV && np_stage_k(STAGE_MOM) == GF_WEIGHT_PART, "gf_weights.h states the stages' sizes");
 
-struct NpArgs {
-    GfNestedView v;
-    const NpRun* runs;      // [R]
-    double *lnw, *theta, *w, *C;        // compact: [T], [T][ndim], [T] (e, then p), [T]
-    double* part;           // [R][maxleaves][K of the stage]
-    double* stat;           // [R][NP_STAT]
-    double *mean, *cov;     // [R][MAX_DIM], [R][MAX_DIM][MAX_DIM]
-    double* tot;            // [R][maxleaves * 64]: block totals, then their prefix
-    int64_t maxleaves;
-};
-
-__global__ __launch_bounds__(NP_BLOCK) void k_np_gather(const NpArgs a)
+__global__ __launch_bounds__(NP_BLOCK) void k_np_gather(const NpArgs a, const GfNestedView v, double* __restrict__ lnw, double* __restrict__ theta)
 {
-    const int r = blockIdx.y, ndim = a.v.ndim, D = a.v.nscan, B = a.v.batch, K = a.v.nlive;
+    const int r = blockIdx.y, ndim = v.ndim, D = v.nscan, B = v.batch, K = v.nlive;
     const NpRun R = a.runs[r];
     const int64_t e = (int64_t)blockIdx.x * NP_BLOCK + threadIdx.x;
     if (e >= R.n * ndim) return;
@@ -63,18 +57,18 @@ __global__ __launch_bounds__(NP_BLOCK) void k_np_gather(const NpArgs a)
     const int c = (int)(e - i * ndim);
     int64_t src;                                  // the point's place in the dead or in the live arrays
     const bool dead = i < R.nd;
-    if (dead) { const int64_t it = i / B; src = (it * a.v.nruns + r) * B + (i - it * B); }
+    if (dead) { const int64_t it = i / B; src = (it * v.nruns + r) * B + (i - it * B); }
     else src = (int64_t)r * K + (i - R.nd);
-    const int sl = a.v.slot[c];
+    const int sl = v.slot[c];
     double x;
     if (sl >= 0) {
-        const double u = (dead ? a.v.d_dead_u : a.v.d_live_u)[src * D + sl];
-        x = cube_theta(a.v.d_commons[r].lo[c], a.v.d_commons[r].hi[c], u);
+        const double u = (dead ? v.d_dead_u : v.d_live_u)[src * D + sl];
+        x = cube_theta(v.d_commons[r].lo[c], v.d_commons[r].hi[c], u);
     } else {
-        x = a.v.d_bases[r * MAX_DIM + c];
+        x = v.d_bases[r * MAX_DIM + c];
     }
-    a.theta[(R.off + i) * ndim + c] = x;
-    if (c == 0) a.lnw[R.off + i] = dead ? a.v.d_dead_w[src] : live_lnw(R.lnw0, a.v.d_live_l[src]);
+    theta[(R.toff + i) * ndim + c] = x;
+    if (c == 0) lnw[R.off + i] = dead ? v.d_dead_w[src] : live_lnw(R.lnw0, v.d_live_l[src]);
 }
 
 // the fold of the workgroup's 256 lane values (gf_nested_post.hpp fold_lanes); valid in every lane.  `sm`: 4 doubles of LDS
@@ -98,7 +92,7 @@ __global__ __launch_bounds__(NP_BLOCK) void k_np_leaf(const NpArgs a)
 {
     __shared__ double sm[4];
     constexpr int K = np_stage_k(STAGE), NS = STAGE == STAGE_MAX ? 1 : STAGE == STAGE_EXP ? 2 : STAGE == STAGE_MOM ? 2 + MAX_DIM : MAX_DIM;
-    const int r = blockIdx.y, ndim = a.v.ndim;
+    const int r = blockIdx.y, ndim = a.ndim;
     const NpRun R = a.runs[r];
     const int64_t leaf = STAGE == STAGE_COV ? blockIdx.x / ndim : blockIdx.x;
     const int ca = STAGE == STAGE_COV ? (int)(blockIdx.x - leaf * ndim) : 0;
@@ -130,13 +124,13 @@ __global__ __launch_bounds__(NP_BLOCK) void k_np_leaf(const NpArgs a)
             a.w[g] = p;
             s[0] = add(s[0], p);
             s[1] = add(s[1], square(p));
-            const double* x = a.theta + g * ndim;
+            const double* x = a.theta + (R.toff + i) * ndim;
 #pragma unroll
             for (int c = 0; c < MAX_DIM; ++c)
                 if (c < ndim) s[2 + c] = add(s[2 + c], term_mean(p, x[c]));
         } else {
             const double p = a.w[g];
-            const double* x = a.theta + g * ndim;
+            const double* x = a.theta + (R.toff + i) * ndim;
             const double xa = x[ca];
 #pragma unroll
             for (int c = 0; c < MAX_DIM; ++c)
@@ -160,7 +154,7 @@ __global__ __launch_bounds__(NP_BLOCK) void k_np_run(const NpArgs a)
     __shared__ double sm[4];
     __shared__ double res[MAX_DIM * MAX_DIM];
     constexpr int K = np_stage_k(STAGE);
-    const int r = blockIdx.x, ndim = a.v.ndim, tid = threadIdx.x;
+    const int r = blockIdx.x, ndim = a.ndim, tid = threadIdx.x;
     const NpRun R = a.runs[r];
     double* st = a.stat + (size_t)r * NP_STAT;
     if (R.n == 0) {                                                    // no posterior
@@ -188,11 +182,11 @@ __global__ __launch_bounds__(NP_BLOCK) void k_np_run(const NpArgs a)
         if (tid == 0) { st[ST_S] = res[0]; st[ST_S2] = res[1]; st[ST_ESS] = kish_ess(res[0], res[1]); }
     } else if (STAGE == STAGE_MOM) {
         if (tid == 0) { st[ST_SP] = res[0]; st[ST_SP2] = res[1]; st[ST_FACT] = cov_factor(res[0], res[1]); }
-        if (tid < ndim) a.mean[r * MAX_DIM + tid] = a.v.slot[tid] < 0 ? a.theta[R.off * ndim + tid] : div(res[2 + tid], res[0]);
+        if (tid < ndim) a.mean[r * MAX_DIM + tid] = a.fixed[tid] ? a.theta[R.toff * ndim + tid] : div(res[2 + tid], res[0]);
     } else {
         const int ca = tid / MAX_DIM, cb = tid % MAX_DIM;
         if (ca < ndim && cb < ndim)
-            a.cov[(size_t)r * MAX_DIM * MAX_DIM + tid] = (a.v.slot[ca] < 0 || a.v.slot[cb] < 0) ? 0.0 : div(res[tid], st[ST_FACT]);
+            a.cov[(size_t)r * MAX_DIM * MAX_DIM + tid] = (a.fixed[ca] || a.fixed[cb]) ? 0.0 : div(res[tid], st[ST_FACT]);
     }
 }
 
@@ -287,7 +281,7 @@ __global__ __launch_bounds__(NP_BLOCK) void k_np_resample(const NpArgs a, int64_
     if (k >= N) return;
     const NpRun R = a.runs[r];
     int64_t idx = -1;
-    if (R.n > 0) idx = resample_index(a.C + R.off, R.n, resample_t(k, resample_offset(a.v.seed, a.v.d_run_ids[r]), N));
+    if (R.n > 0) idx = resample_index(a.C + R.off, R.n, resample_t(k, resample_offset(a.seed, a.ids[r]), N));
     index[(int64_t)r * N + k] = idx;
 }
 
@@ -296,7 +290,7 @@ __global__ __launch_bounds__(NP_BLOCK) void k_np_resample(const NpArgs a, int64_
 __global__ __launch_bounds__(NP_BLOCK) void k_np_rows(const NpArgs a, int64_t N, const int64_t* __restrict__ index, int run0, int width,
                                                       int first, double* __restrict__ out)
 {
-    const int r = run0 + blockIdx.y, ndim = a.v.ndim;
+    const int r = run0 + blockIdx.y, ndim = a.ndim;
     const int64_t e = (int64_t)blockIdx.x * NP_BLOCK + threadIdx.x;
     if (e >= N * width) return;
     const int64_t k = e / width;
@@ -304,13 +298,54 @@ __global__ __launch_bounds__(NP_BLOCK) void k_np_rows(const NpArgs a, int64_t N,
     const int64_t idx = index[(int64_t)r * N + k];
     double* dst = out + ((int64_t)r * N) * width + e;
     if (idx < 0) *dst = nan();
-    else if (c >= first) *dst = a.theta[(a.runs[r].off + idx) * ndim + (c - first)];
+    else if (c >= first) *dst = a.theta[(a.runs[r].toff + idx) * ndim + (c - first)];
 }
 
+}  // namespace
+
+// ---- gf_weights.h: the launches, for this file's runs and for gf_reweight.hip's ---------------------------------------------------
+hipError_t gf_weights_launch(const GfWeightArgs& a, int R, bool moments, bool prefix, hipStream_t st)
+{
+    const dim3 leaves((unsigned)a.maxleaves, (unsigned)R), runs((unsigned)R);
+    hipLaunchKernelGGL(k_np_leaf<STAGE_MAX>, leaves, dim3(NP_BLOCK), 0, st, a);
+    hipLaunchKernelGGL(k_np_run<STAGE_MAX>, runs, dim3(NP_BLOCK), 0, st, a);
+    hipLaunchKernelGGL(k_np_leaf<STAGE_EXP>, leaves, dim3(NP_BLOCK), 0, st, a);
+    hipLaunchKernelGGL(k_np_run<STAGE_EXP>, runs, dim3(NP_BLOCK), 0, st, a);
+    hipLaunchKernelGGL(k_np_leaf<STAGE_MOM>, leaves, dim3(NP_BLOCK), 0, st, a);
+    hipLaunchKernelGGL(k_np_run<STAGE_MOM>, runs, dim3(NP_BLOCK), 0, st, a);
+    if (moments) {
+        hipLaunchKernelGGL(k_np_leaf<STAGE_COV>, dim3((unsigned)(a.maxleaves * a.ndim), (unsigned)R), dim3(NP_BLOCK), 0, st, a);
+        hipLaunchKernelGGL(k_np_run<STAGE_COV>, runs, dim3(NP_BLOCK), 0, st, a);
+    }
+    if (prefix) {
+        hipLaunchKernelGGL(k_np_scan_totals, leaves, dim3(NP_WAVE), 0, st, a);
+        hipLaunchKernelGGL(k_np_scan_prefix, runs, dim3(NP_WAVE), 0, st, a);
+        hipLaunchKernelGGL(k_np_scan_add, leaves, dim3(NP_WAVE), 0, st, a);
+    }
+    return hipGetLastError();
+}
+
+hipError_t gf_weights_resample(const GfWeightArgs& a, int R, int64_t N, int64_t* d_index, hipStream_t st)
+{
+    const unsigned blocks = (unsigned)((N + NP_BLOCK - 1) / NP_BLOCK);
+    hipLaunchKernelGGL(k_np_resample, dim3(blocks, (unsigned)R), dim3(NP_BLOCK), 0, st, a, N, d_index);
+    return hipGetLastError();
+}
+
+hipError_t gf_weights_rows(const GfWeightArgs& a, int64_t N, const int64_t* d_index, int run0, int nruns, int width, int first, double* d_out,
+                           hipStream_t st)
+{
+    const unsigned blocks = (unsigned)((N * width + NP_BLOCK - 1) / NP_BLOCK);
+    hipLaunchKernelGGL(k_np_rows, dim3(blocks, (unsigned)nruns), dim3(NP_BLOCK), 0, st, a, N, d_index, run0, width, first, d_out);
+    return hipGetLastError();
+}
+
+namespace {
 // ---- host --------------------------------------------------------------------------------------------------------------------------
 struct NpWork {
     GfScratch buf;
     NpArgs a = {};
+    GfNestedView v = {};
     std::vector<GfNestedRunState> state;
     std::vector<NpRun> runs;
     int64_t total = 0, maxn = 0;
@@ -334,65 +369,55 @@ bool np_get(NpWork& w, T** p, size_t bytes, size_t* failed)
 int np_prepare(gf_nested* s, NpWork& w, bool moments, bool prefix, const char* who)
 {
     NpArgs& a = w.a;
-    int rc = gf_internal_nested_view(s, &a.v, nullptr);
+    GfNestedView& v = w.v;
+    int rc = gf_internal_nested_view(s, &v, nullptr);
     if (rc != GF_OK) return rc;
-    const int R = a.v.nruns;
+    const int R = v.nruns;
     w.state.resize(R);
     w.runs.resize(R);
-    rc = gf_internal_nested_view(s, &a.v, w.state.data());
+    rc = gf_internal_nested_view(s, &v, w.state.data());
     if (rc != GF_OK) return rc;
     for (int r = 0; r < R; ++r) {
         const GfNestedRunState& x = w.state[r];
         NpRun& q = w.runs[r];
         const bool ok = x.done && !x.failed && x.lnz > -HUGE_VAL;
-        q.off = w.total;
-        q.nd = ok ? x.iter * a.v.batch : 0;
-        q.n = ok ? q.nd + a.v.nlive : 0;
-        q.lnw0 = x.lnx - std::log((double)a.v.nlive);          // gf_nested_get_dead's expression
+        q.off = q.toff = w.total;
+        q.nd = ok ? x.iter * v.batch : 0;
+        q.n = ok ? q.nd + v.nlive : 0;
+        q.lnw0 = x.lnx - std::log((double)v.nlive);          // gf_nested_get_dead's expression
         w.total += q.n;
         w.maxn = std::max(w.maxn, q.n);
     }
+    a.ndim = v.ndim;
+    for (int c = 0; c < MAX_DIM; ++c) a.fixed[c] = v.slot[c] < 0;
+    a.seed = v.seed;
+    a.ids = v.d_run_ids;
     a.maxleaves = std::max<int64_t>(1, (w.maxn + LEAF - 1) / LEAF);
-    if (a.maxleaves * std::max(1, a.v.ndim) > 0x7fffffffll) return gf_fail_msg(GF_ERR_UNSUPPORTED, "%s: too many points per run", who);
+    if (a.maxleaves * std::max(1, v.ndim) > 0x7fffffffll) return gf_fail_msg(GF_ERR_UNSUPPORTED, "%s: too many points per run", who);
     const size_t T = (size_t)w.total, K = moments ? MAX_DIM * MAX_DIM : 2 + MAX_DIM;
     NpRun* d_runs = nullptr;
+    double *d_lnw = nullptr, *d_theta = nullptr;
     size_t bad = 0;
-    const bool got = np_get(w, &d_runs, sizeof(NpRun) * R, &bad) && np_get(w, &a.lnw, sizeof(double) * T, &bad) &&
-                     np_get(w, &a.theta, sizeof(double) * T * a.v.ndim, &bad) && np_get(w, &a.w, sizeof(double) * T, &bad) &&
+    const bool got = np_get(w, &d_runs, sizeof(NpRun) * R, &bad) && np_get(w, &d_lnw, sizeof(double) * T, &bad) &&
+                     np_get(w, &d_theta, sizeof(double) * T * v.ndim, &bad) && np_get(w, &a.w, sizeof(double) * T, &bad) &&
                      np_get(w, &a.part, sizeof(double) * R * a.maxleaves * K, &bad) && np_get(w, &a.stat, sizeof(double) * R * NP_STAT, &bad) &&
                      np_get(w, &a.mean, sizeof(double) * R * MAX_DIM, &bad) && np_get(w, &a.cov, sizeof(double) * R * MAX_DIM * MAX_DIM, &bad) &&
                      (!prefix || (np_get(w, &a.C, sizeof(double) * T, &bad) && np_get(w, &a.tot, sizeof(double) * R * a.maxleaves * NP_WAVE, &bad)));
     if (!got) return np_alloc_fail(who, bad);
     a.runs = d_runs;
-    hipStream_t st = a.v.stream;
+    a.lnw = d_lnw;
+    a.theta = d_theta;
+    hipStream_t st = v.stream;
     GF_HIP(hipMemcpyAsync(d_runs, w.runs.data(), sizeof(NpRun) * R, hipMemcpyHostToDevice, st));
-    const dim3 leaves((unsigned)a.maxleaves, (unsigned)R), runs((unsigned)R);
-    const unsigned gblocks = (unsigned)std::max<int64_t>(1, (w.maxn * a.v.ndim + NP_BLOCK - 1) / NP_BLOCK);
-    hipLaunchKernelGGL(k_np_gather, dim3(gblocks, (unsigned)R), dim3(NP_BLOCK), 0, st, a);
-    hipLaunchKernelGGL(k_np_leaf<STAGE_MAX>, leaves, dim3(NP_BLOCK), 0, st, a);
-    hipLaunchKernelGGL(k_np_run<STAGE_MAX>, runs, dim3(NP_BLOCK), 0, st, a);
-    hipLaunchKernelGGL(k_np_leaf<STAGE_EXP>, leaves, dim3(NP_BLOCK), 0, st, a);
-    hipLaunchKernelGGL(k_np_run<STAGE_EXP>, runs, dim3(NP_BLOCK), 0, st, a);
-    hipLaunchKernelGGL(k_np_leaf<STAGE_MOM>, leaves, dim3(NP_BLOCK), 0, st, a);
-    hipLaunchKernelGGL(k_np_run<STAGE_MOM>, runs, dim3(NP_BLOCK), 0, st, a);
-    if (moments) {
-        hipLaunchKernelGGL(k_np_leaf<STAGE_COV>, dim3((unsigned)(a.maxleaves * a.v.ndim), (unsigned)R), dim3(NP_BLOCK), 0, st, a);
-        hipLaunchKernelGGL(k_np_run<STAGE_COV>, runs, dim3(NP_BLOCK), 0, st, a);
-    }
-    if (prefix) {
-        hipLaunchKernelGGL(k_np_scan_totals, leaves, dim3(NP_WAVE), 0, st, a);
-        hipLaunchKernelGGL(k_np_scan_prefix, runs, dim3(NP_WAVE), 0, st, a);
-        hipLaunchKernelGGL(k_np_scan_add, leaves, dim3(NP_WAVE), 0, st, a);
-    }
-    GF_HIP(hipGetLastError());
+    const unsigned gblocks = (unsigned)std::max<int64_t>(1, (w.maxn * v.ndim + NP_BLOCK - 1) / NP_BLOCK);
+    hipLaunchKernelGGL(k_np_gather, dim3(gblocks, (unsigned)R), dim3(NP_BLOCK), 0, st, a, v, d_lnw, d_theta);
+    GF_HIP(gf_weights_launch(a, R, moments, prefix, st));
     return GF_OK;
 }
 
 hipError_t np_launch_rows(const NpWork& w, int64_t N, const int64_t* d_index, int run0, int nruns, int width, int first, double* d_out)
 {
-    const unsigned blocks = (unsigned)((N * width + NP_BLOCK - 1) / NP_BLOCK);
-    hipLaunchKernelGGL(k_np_rows, dim3(blocks, (unsigned)nruns), dim3(NP_BLOCK), 0, w.a.v.stream, w.a, N, d_index, run0, width, first, d_out);
-    return hipGetLastError();
+    return gf_weights_rows(w.a, N, d_index, run0, nruns, width, first, d_out, w.v.stream);
 }
 
 // Every run's N theta rows into d_theta [R][N][ndim] (d_index [R][N] filled), then run r's slice propagated with its model into
@@ -402,11 +427,9 @@ template <class After, class AfterNone>
 int np_propagated(gf_nested* s, NpWork& w, int64_t N, int64_t* d_index, double* d_theta, double* d_fr, int32_t* d_st, bool per_run, const char* who,
                   After after, AfterNone after_none)
 {
-    const GfNestedView& v = w.a.v;
+    const GfNestedView& v = w.v;
     hipStream_t st = v.stream;
-    const unsigned blocks = (unsigned)((N + NP_BLOCK - 1) / NP_BLOCK);
-    hipLaunchKernelGGL(k_np_resample, dim3(blocks, (unsigned)v.nruns), dim3(NP_BLOCK), 0, st, w.a, N, d_index);
-    hipError_t e = hipGetLastError();
+    hipError_t e = gf_weights_resample(w.a, v.nruns, N, d_index, st);
     if (e == hipSuccess) e = np_launch_rows(w, N, d_index, 0, v.nruns, v.ndim, 0, d_theta);
     int rc = GF_OK;
     gf_internal_full_arbitration_grids(v.device, st, 1);              // the runs of a scan differ (gf_postprocess.hip for_each_chain)
@@ -431,15 +454,13 @@ int np_rows(gf_nested* s, int64_t N, int with_fr, double* d_rows, int64_t* d_ind
     NpWork w;
     int rc = np_prepare(s, w, false, true, who);
     if (rc != GF_OK) return rc;
-    const GfNestedView& v = w.a.v;
+    const GfNestedView& v = w.v;
     hipStream_t st = v.stream;
     const size_t RN = (size_t)v.nruns * N;
     size_t bad = 0;
     if (!d_index && !np_get(w, &d_index, sizeof(int64_t) * RN, &bad)) return np_alloc_fail(who, bad);
     if (!with_fr) {
-        const unsigned blocks = (unsigned)((N + NP_BLOCK - 1) / NP_BLOCK);
-        hipLaunchKernelGGL(k_np_resample, dim3(blocks, (unsigned)v.nruns), dim3(NP_BLOCK), 0, st, w.a, N, d_index);
-        hipError_t e = hipGetLastError();
+        hipError_t e = gf_weights_resample(w.a, v.nruns, N, d_index, st);
         if (e == hipSuccess) e = np_launch_rows(w, N, d_index, 0, v.nruns, v.ndim, 0, d_rows);
         const hipError_t e2 = hipStreamSynchronize(st);
         if (e != hipSuccess || e2 != hipSuccess) return gf_hip_fail(e != hipSuccess ? e : e2, who);
@@ -468,7 +489,7 @@ int gf_nested_posterior(gf_nested* s, int64_t* npoints, double* ess, double* lnz
     NpWork w;
     const int rc = np_prepare(s, w, true, false, "gf_nested_posterior");
     if (rc != GF_OK) return rc;
-    const GfNestedView& v = w.a.v;
+    const GfNestedView& v = w.v;
     const int R = v.nruns, nd = v.ndim;
     std::vector<double> h_stat((size_t)R * NP_STAT), h_mean((size_t)R * MAX_DIM), h_cov((size_t)R * MAX_DIM * MAX_DIM);
     hipError_t e = hipMemcpyAsync(h_stat.data(), w.a.stat, sizeof(double) * h_stat.size(), hipMemcpyDeviceToHost, v.stream);
@@ -565,7 +586,7 @@ int gf_nested_spectrum(gf_nested* s, int64_t nrows, const gf_spectrum_spec* spec
     NpWork w;
     rc = np_prepare(s, w, false, true, "gf_nested_spectrum");
     if (rc != GF_OK) return rc;
-    const GfNestedView& v = w.a.v;
+    const GfNestedView& v = w.v;
     hipStream_t st = v.stream;
     const size_t RN = (size_t)v.nruns * nrows;
     int64_t* d_index = nullptr; double *d_theta = nullptr, *d_slab = nullptr; int32_t* d_st = nullptr;
@@ -632,7 +653,7 @@ int gf_nested_regions(gf_nested* s, int64_t nrows, int nbins, int radius, const 
     }
     int rc = np_prepare(s, w, false, true, who);
     if (rc != GF_OK) return rc;
-    const GfNestedView& v = w.a.v;
+    const GfNestedView& v = w.v;
     hipStream_t st = v.stream;
     const size_t RN = (size_t)v.nruns * nrows, nbin3 = (size_t)nbins * nbins * nbins;
     int64_t* d_index = nullptr;

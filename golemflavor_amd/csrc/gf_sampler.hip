@@ -1661,7 +1661,8 @@ int64_t gf_sampler_iterations(const gf_sampler* s) { return s ? s->steps_since_r
 int gf_internal_sampler_chain_view(const gf_sampler* s, GfChainView* v)
 {
     if (!s || !v) return GF_ERR_INVALID_ARG;
-    *v = GfChainView{s->device, s->stream, s->cus, s->nchains, s->nwalkers, s->ndim, s->nstored, s->nstore_cap, s->d_chain, s->model, s->models};
+    *v = GfChainView{s->device, s->stream, s->cus, s->nchains, s->nwalkers, s->ndim, s->nstored, s->nstore_cap, s->d_chain, s->model, s->models,
+                     s->d_lnp_chain, s->seed, s->d_stream_ids};
     return GF_OK;
 }
 

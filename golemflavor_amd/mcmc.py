@@ -731,6 +731,20 @@ class DeviceEnsembleSampler:
         res = sp.run_spectrum_call(call, "gf_sampler_spectrum", self.nchains, prep)
         return res[0] if self.nchains == 1 else res
 
+    def reweight(self, targets, seed=None, on_nonunitary="raise"):
+        """The stored chains under other targets, without sampling again (`reweight.Reweighted`: .summary(), .lnw(chain), .rows(N,
+        with_fr, return_index), .marginals(N, ...), .intervals(N, ...), .regions(N, nbins, coverage, ...)): every stored sample is
+        weighted by exp(ln_prob_target - ln_prob_sampled) on the device.  targets: one list applied to every chain, or one list per
+        chain, of `reweight.Measurement` (the chain's own Gaussian measurement with another composition / smearing / offset: the
+        chain is propagated once for all targets) or of Model / LnProb (any posterior over the same columns); at most 64 per chain.
+        Rows and every returned index are in the device's storage order, i = step * nwalkers + walker (`flat_steps()`), not emcee's
+        walker-major `flatchain`.  seed: of the systematic resampling (default: the sampler's).  on_nonunitary="raise":
+        AssertionError if a row is non-unitary under a target, "-inf": such rows get zero weight.  Nothing stored: ValueError."""
+        from .reweight import Reweighted
+        if self.nstored == 0:
+            raise ValueError("no stored samples: run_mcmc(..., storechain=True) first")
+        return Reweighted(self, targets, seed=seed, on_nonunitary=on_nonunitary)
+
     def close(self):
         if getattr(self, "_h", None) is not None:
             self._L.gf_sampler_destroy(self._h)

@@ -429,6 +429,64 @@ class IntervalWriter:
         INTERVAL_STATS.update({"percentiles": self.percentiles, "points": self.points, "seconds": round(self.seconds, 4), "status_not_ok": self.not_ok})
 
 
+REWEIGHT_STATS = {}   # the last run_points call with --reweight-injected: what it computed on this rank (reported by main)
+
+
+def reweight_targets(injected, smearings):
+    """--reweight-injected R G B [R G B ...] and --reweight-smearing S ...: every (injected, smearing) pair, injected-major, as
+    (normalised composition, smearing); an omitted smearing list means the scan's own value (None).  ValueError on a bad list."""
+    v = [float(x) for x in (injected or [])]
+    if not v or len(v) % 3:
+        raise ValueError("--reweight-injected takes triples R G B")
+    sm = [float(x) for x in smearings] if smearings else [None]
+    if any(x is not None and not x > 0. for x in sm):
+        raise ValueError("--reweight-smearing takes positive values")
+    out = []
+    for k in range(0, len(v), 3):
+        tot = v[k] + v[k + 1] + v[k + 2]
+        if min(v[k:k + 3]) < 0. or not tot > 0.:
+            raise ValueError("an injected ratio has non-negative components and a positive sum")
+        out += [((v[k] / tot, v[k + 1] / tot, v[k + 2] / tot), x) for x in sm]
+    if len(out) > _lib.GF_REWEIGHT_MAX_TARGETS:
+        raise ValueError("at most %d (injected, smearing) pairs" % _lib.GF_REWEIGHT_MAX_TARGETS)
+    return out
+
+
+class ReweightWriter:
+    """--reweight-injected: every grid point's chain reweighted to other measurements (`DeviceEnsembleSampler.reweight` with
+    `reweight.Measurement` targets), computed while the point's sampler still holds its chain and saved as reweight_<point file
+    name>.npz beside the chain file: the summary (ess, lnz_ratio, mean, cov), the counts (n, bad_base, nonunitary, outside) and the
+    targets (target_bestfit_fr, target_smearing, target_offset).  nrows (--reweight-rows): the marginals of that many equal-weight
+    rows per target as well, reweight_marginals_<point file name>_t<target>.npz, with --marginals' spec."""
+
+    def __init__(self, datadir, name_of, targets, nrows=None, marginal_kw=None):
+        self.datadir, self.name_of, self.targets, self.nrows = datadir, name_of, list(targets), nrows
+        self.kw = dict(marginal_kw or {})
+        self.seconds, self.points, self.without_posterior = 0.0, 0, 0
+
+    def take(self, sampler, models, order):
+        from .reweight import Measurement
+        t0 = time.perf_counter()
+        r = sampler.reweight([Measurement(bestfit_fr=bf, smearing=sm) for bf, sm in self.targets], on_nonunitary="-inf")
+        summ = r._summary
+        marg = r.marginals(self.nrows, **self.kw) if self.nrows else None
+        os.makedirs(self.datadir, exist_ok=True)
+        for k, g in enumerate(order):
+            arrays = {f: v[k] for f, v in summ.items()}
+            arrays.update(target_bestfit_fr=r.bestfit_fr[k], target_smearing=r.smearing[k], target_offset=r.offset[k])
+            with open(os.path.join(self.datadir, "reweight_%s.npz" % self.name_of(g)), "wb") as f:
+                np.savez(f, **arrays)
+            if marg is not None:
+                for t, m in enumerate(marg if len(order) == 1 else marg[k]):
+                    m.save(os.path.join(self.datadir, "reweight_marginals_%s_t%d.npz" % (self.name_of(g), t)))
+            self.points += 1
+            self.without_posterior += int(np.count_nonzero(summ["ess"][k] == 0.0))
+        self.seconds += time.perf_counter() - t0
+        REWEIGHT_STATS.clear()
+        REWEIGHT_STATS.update({"targets": len(self.targets), "points": self.points, "seconds": round(self.seconds, 4), "rows": self.nrows,
+                               "targets_without_posterior": self.without_posterior})
+
+
 class _Takers:
     """several writers behind the one `regions` argument of run_points"""
 
@@ -869,6 +927,16 @@ def main(argv=None):
                     help="also save every grid point's composition per energy bin (mean, covariance, percentiles Q -- default 5 16 50 "
                          "84 95 -- and histograms), spectrum_<point>.npz beside the chain file; needs --datadir and a BSM configuration")
     ap.add_argument("--spectrum-bins", type=int, default=50, help="histogram bins per flavour over [0, 1] of --spectrum")
+    ap.add_argument("--reweight-injected", type=float, nargs="+", default=None, metavar="F",
+                    help="also reweight every grid point's chain to these measured compositions, triples R G B [R G B ...] (normalised), "
+                         "without sampling again: summary, counts and targets as reweight_<point>.npz beside the chain file; needs "
+                         "--datadir and chains sampled under a measurement (--config C5)")
+    ap.add_argument("--reweight-smearing", type=float, nargs="+", default=None, metavar="S",
+                    help="with --reweight-injected: the targets are every (injected, smearing) pair; default: the scan's own smearing")
+    ap.add_argument("--reweight-rows", type=int, default=None, metavar="N",
+                    help="with --reweight-injected: also save the marginals of N equal-weight rows per target, with --marginals' bins, "
+                         "coverages and percentiles and, as --marginals for this configuration, over the sampled columns alone (the rows "
+                         "a C5 scan saves carry no composition), reweight_marginals_<point>_t<target>.npz")
     ap.add_argument("--marginal-bins-1d", type=int, default=100)
     ap.add_argument("--marginal-bins-2d", type=int, default=50)
     ap.add_argument("--marginal-coverage", type=float, nargs="+", default=[90., 99.], metavar="COVERAGE")
@@ -899,6 +967,22 @@ def main(argv=None):
             ap.error("--marginal-coverage takes 1 to 8 coverages in (0, 100]")
         if not 1 <= len(a.marginal_percentiles) <= 8 or not all(0. <= q <= 100. for q in a.marginal_percentiles):
             ap.error("--marginal-percentiles takes 1 to 8 percentiles in [0, 100]")
+    rw_targets = None
+    if a.reweight_injected is not None:
+        if not a.datadir:
+            ap.error("--reweight-injected needs --datadir (the results are saved beside the chain files)")
+        if a.config != "C5":
+            ap.error("--reweight-injected needs chains sampled under a measurement (--config C5); the chains of --config C4 sample the "
+                     "priors only: put a measurement on them from Python with model targets, "
+                     "DeviceEnsembleSampler.reweight([Model(...), ...])")
+        try:
+            rw_targets = reweight_targets(a.reweight_injected, a.reweight_smearing)
+        except ValueError as exc:
+            ap.error(str(exc))
+        if a.reweight_rows is not None and a.reweight_rows < 1:
+            ap.error("--reweight-rows must be at least 1")
+    elif a.reweight_smearing is not None or a.reweight_rows is not None:
+        ap.error("--reweight-smearing and --reweight-rows need --reweight-injected")
     if a.regions is not None:
         if not a.datadir:
             ap.error("--regions needs --datadir (the regions are saved beside the chain files)")
@@ -962,8 +1046,14 @@ def main(argv=None):
     spectrum_writer = None
     if a.spectrum is not None:
         spectrum_writer = SpectrumWriter(a.datadir, lambda g: point_filename(a.config, pts[g], a), a.spectrum, a.spectrum_bins)
-    if marginal_writer is not None or diagnostics_writer is not None or interval_writer is not None or spectrum_writer is not None:
-        regions = _Takers([t for t in (regions, marginal_writer, diagnostics_writer, interval_writer, spectrum_writer) if t is not None])
+    reweight_writer = None
+    if rw_targets is not None:
+        reweight_writer = ReweightWriter(a.datadir, lambda g: point_filename(a.config, pts[g], a), rw_targets, a.reweight_rows,
+                                         dict(bins_1d=a.marginal_bins_1d, bins_2d=a.marginal_bins_2d, coverage=a.marginal_coverage,
+                                              percentiles=a.marginal_percentiles))
+    if any(t is not None for t in (marginal_writer, diagnostics_writer, interval_writer, spectrum_writer, reweight_writer)):
+        regions = _Takers([t for t in (regions, marginal_writer, diagnostics_writer, interval_writer, spectrum_writer, reweight_writer)
+                           if t is not None])
     if a.datadir and not want_gather:
         local = run_points(pts, mine, make, a.burnin, a.nsteps, stacked=stacked, regions=regions)
         gather_name = "none: every rank saved its own files (--datadir)"
@@ -1022,7 +1112,8 @@ def main(argv=None):
                           **({"marginals": MARGINAL_STATS} if marginal_writer is not None else {}),
                           **({"diagnostics": DIAGNOSTIC_STATS} if diagnostics_writer is not None else {}),
                           **({"intervals": INTERVAL_STATS} if interval_writer is not None else {}),
-                          **({"spectrum": SPECTRUM_STATS} if spectrum_writer is not None else {})}), flush=True)
+                          **({"spectrum": SPECTRUM_STATS} if spectrum_writer is not None else {}),
+                          **({"reweight": REWEIGHT_STATS} if reweight_writer is not None else {})}), flush=True)
     control.barrier()
     control.close()
     if rccl_err is not None:

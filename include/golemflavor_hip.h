@@ -642,6 +642,61 @@ int gf_sampler_spectrum(gf_sampler* s, gf_model* const* models, const gf_spectru
  * has nvalid 0 and NaN moments */
 int gf_nested_spectrum(gf_nested* s, int64_t nrows, const gf_spectrum_spec* spec, const gf_spectrum_out* out);
 
+/* ---- every stored chain reweighted to other targets (csrc/gf_reweight.hpp holds the rules for lnw) ------------------- */
+/* Chain c's rows are its stored samples in the device's order, i = step * nwalkers + walker, n = nstored * nwalkers (NOT emcee's
+ * walker-major flatchain; every index below refers to this order), l0_i their stored ln_prob.  Every chain has ntargets targets t.
+ *   model targets        models != NULL: l_t and the row's status are models[c][t]'s lnprob (the kernels of gf_lnprob_batch_device) on
+ *                        the rows in place; lnw = l_t - l0, one rounded subtraction.  Each model has the sampler's ndim and device.
+ *   measurement targets  models == NULL: target (c, t) is the chain's own sampling model with bestfit_fr, smearing and offset replaced;
+ *                        the sampling model must be GF_MODE_SM_GAUSS or GF_MODE_BSM_GAUSS (else GF_ERR_INVALID_ARG).  The chain is
+ *                        propagated ONCE; lnw = mg(fr_i; target) - mg(fr_i; sampling model), mg the Gaussian block of lnprob (the
+ *                        priors cancel).  smearing must be > 0 and bestfit_fr finite.
+ * lnw = -inf, counted once under the first rule that holds: bad_base[c] (l0, or the sampling model's mg, is not finite),
+ * nonunitary[c][t] (the row's status under the target is GF_ST_NON_UNITARY), outside[c][t] (l_t is -inf or NaN).
+ * From lnw on it is gf_nested_posterior's arithmetic unchanged, with no fixed columns: ess (Kish), mean, cov, the prefix C, and
+ * equal-weight rows at t_k = (k + u) / nrows with u = Philox(seed; stream_id(c) * GF_REWEIGHT_MAX_TARGETS + t), seed the sampler's
+ * unless use_sampler_seed == 0 -- so the rows of (c, t) do not depend on which other chains or targets share the call.
+ * lnz_ratio = m + log(S) - log(n), a diagnostic that estimates ln(Z_t / Z_0); it is a Bayes factor only for model targets on the same
+ * data.  A target all of whose weights are zero has no posterior: ess 0, lnz_ratio, mean, cov and rows NaN, index -1.
+ * Chains go one after another on the sampler's stream; scratch per chain is its compositions and status plus three doubles per (target,
+ * row), cut into batches of targets to stay under 2 GiB (GF_REWEIGHT_SCRATCH_BYTES overrides; no result depends on it).  Synchronous;
+ * the sampler is only read.  Nothing stored, ntargets outside [1, GF_REWEIGHT_MAX_TARGETS]: GF_ERR_INVALID_ARG. */
+#define GF_REWEIGHT_MAX_TARGETS 64
+typedef struct gf_reweight_spec {
+    int32_t ntargets;
+    int32_t use_sampler_seed;            /* != 0: `seed` is ignored */
+    uint64_t seed;
+    gf_model* const* models;             /* [nchains][ntargets], or NULL: measurement targets */
+    const double* bestfit_fr;            /* [nchains][ntargets][3] */
+    const double* smearing;              /* [nchains][ntargets] */
+    const double* offset;                /* [nchains][ntargets] */
+} gf_reweight_spec;
+typedef struct gf_reweight_out {         /* host; every pointer may be NULL */
+    double *ess, *lnz_ratio;             /* [nchains][ntargets] */
+    double* mean;                        /* [nchains][ntargets][ndim] */
+    double* cov;                         /* [nchains][ntargets][ndim][ndim] */
+    int64_t* bad_base;                   /* [nchains] */
+    int64_t *nonunitary, *outside;       /* [nchains][ntargets] */
+    int64_t* n;                          /* [nchains] */
+} gf_reweight_out;
+int gf_sampler_reweight(gf_sampler* s, const gf_reweight_spec* spec, const gf_reweight_out* out);
+/* the log-weights of one chain, lnw [ntargets][n] on the host: for tests and for estimators of the caller's own */
+int gf_sampler_reweight_lnw(gf_sampler* s, const gf_reweight_spec* spec, int chain, double* lnw);
+/* d_rows [nchains][ntargets][nrows][(with_fr ? 3 : 0) + ndim] on the device; with_fr puts the row's composition under the target in
+ * front (measurement targets: gathered from the chain's one propagation; model targets: the nrows rows propagated with the target) */
+int gf_sampler_reweight_rows_device(gf_sampler* s, const gf_reweight_spec* spec, int64_t nrows, int with_fr, double* d_rows);
+/* the same rows in host memory, and index [nchains][ntargets][nrows] (NULL = skip): the row of the chain each came from */
+int gf_sampler_reweight_rows(gf_sampler* s, const gf_reweight_spec* spec, int64_t nrows, int with_fr, double* rows, int64_t* index);
+/* the reductions of those rows, which stay on the device, with nchains * ntargets in place of nchains: gf_marginals_device,
+ * gf_column_intervals_device, and gf_sampler_regions' outputs of the rows' compositions */
+int gf_sampler_reweight_marginals(gf_sampler* s, const gf_reweight_spec* rw, int64_t nrows, int with_fr, const gf_marginal_spec* spec,
+                                  const gf_marginal_out* out);
+int gf_sampler_reweight_intervals(gf_sampler* s, const gf_reweight_spec* rw, int64_t nrows, int with_fr, const gf_interval_spec* spec,
+                                  const gf_interval_out* out);
+int gf_sampler_reweight_regions(gf_sampler* s, const gf_reweight_spec* rw, int64_t nrows, int nbins, int radius, const double* weights,
+                                const double* coverage, int ncov, int64_t cap, int64_t* thres, int32_t* saturated, double* level_in,
+                                double* level_out, double* mass, int32_t* cells, double* density);
+
 #ifdef __cplusplus
 }
 #endif
