@@ -1,7 +1,8 @@
 // Host pieces shared by the C ABI of the device samplers, of chain post-processing and of read-back (gf_sampler.hip, gf_postprocess.hip,
-// gf_readback.hip, gf_nested.hip, gf_simplex.hip, gf_region.hip, gf_marginal.hip, gf_elements.hip): the library's internal functions
-// (gf_internal.h), the error helpers that publish a message through gf_last_hip_error(), the holder of a call's scratch buffers, and
-// the allocation of the arbitration queue the settle kernels share.
+// gf_readback.hip, gf_nested.hip, gf_nested_post.hip, gf_reweight.hip, gf_simplex.hip, gf_region.hip, gf_marginal.hip, gf_elements.hip):
+// the library's internal functions (gf_internal.h), the error helpers that publish a message through gf_last_hip_error(), the holder
+// of a call's scratch buffers with the way an entry point reports a refused request of its own (GfScratch::take), and the allocation
+// of the arbitration queue the settle kernels share.  What the three sample sources share for their reductions is in gf_rowsets.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -44,6 +45,7 @@ __attribute__((format(printf, 2, 3))) inline int gf_fail_msg(int rc, const char*
 // hipMalloc / hipFree are the including file's (gf_devcache.h's where that comes first).
 struct GfScratch {
     std::vector<void*> p;
+    int failed = GF_OK;                 // the first refused take's code
     template <typename T>
     hipError_t get(T** out, size_t bytes)
     {
@@ -52,6 +54,16 @@ struct GfScratch {
         if (e == hipSuccess) p.push_back(q);
         *out = static_cast<T*>(q);
         return e;
+    }
+    // get() for an entry point `who`.  A refused request clears HIP's last error (the next hipGetLastError() after a launch must not see
+    // it), publishes the size and is GF_ERR_ALLOC; the takes after it do nothing and return the same, so a run of takes is checked once,
+    // at its last one or through `failed`
+    template <typename T>
+    int take(T** out, size_t bytes, const char* who)
+    {
+        if (failed != GF_OK || get(out, bytes) == hipSuccess) return failed;
+        (void)hipGetLastError();
+        return failed = gf_fail_msg(GF_ERR_ALLOC, "%s: %zu bytes of device scratch were not granted", who, bytes);
     }
     ~GfScratch() { for (void* q : p) (void)hipFree(q); }
 };

@@ -1,17 +1,15 @@
 // gf_postprocess.hip -- a sampler's STORED chain turned into what the scripts save: compositions, flavor histograms, the scan's rows,
-// credible regions, marginals and convergence diagnostics.  Host code only; the sampler is seen through a GfChainView (gf_internal.h), and every entry point
-// works in order on the sampler's stream, the one the chain was written on.
+// credible regions, marginals, intervals, the energy-resolved composition and convergence diagnostics.  Host code only; the sampler is
+// seen through a GfChainView (gf_internal.h), and every entry point works in order on the sampler's stream, the one the chain was
+// written on.  The chain is one of the three sources of gf_rowsets.h: chain_rows says where its rows are (the chain itself, or the
+// rows a scan saves in scratch), the reducers, the region counts, the spectrum step and the propagate loop are that header's.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "gf_devcache.h"                // the scratch buffers of a scan's post-processing are the multi-gigabyte allocations the cache exists for
 #include "gf_host.h"                    // (after gf_devcache.h: GfScratch allocates through the cache)
-#include "gf_region.h"
-#include "gf_marginal.h"
-#include "gf_elements.h"
+#include "gf_rowsets.h"
 #include "gf_diag.h"
-#include "gf_interval.h"
-#include "gf_spectrum.h"
 
 namespace {
 
@@ -33,26 +31,52 @@ int check_chain_models(const GfChainView& v, gf_model* const* models, int* cus =
 const double* chain_theta(const GfChainView& v, int ch) { return v.d_chain + (size_t)ch * v.nstore_cap * v.nwalkers * v.ndim; }
 inline hipError_t first_error(hipError_t a, hipError_t b) { return a != hipSuccess ? a : b; }
 
-// for every chain: propagate it with its model on v.stream, then *e = after(ch, d_theta, d_fr_ch, d_st_ch); stops at the first failure
-// of either (returns the propagation's code); nothing for an empty chain.  per_chain_scratch: chain ch has its own part of d_fr [.][3]
-// and d_st (may be NULL), else all go through the same one.  full_grids: the chains are enqueued faster than they run, so the arbitration
-// grid of each would follow what some EARLIER chain found, and the chains of a scan differ (its high-scale grid points sit in the failing
-// region, the others have empty queues): full grids throughout, ~30 us per chain (measured: the hint left 57 of 64 chains of the C4 scan
-// on a sixth of the GPU, 114 ms of arbitration instead of ~20)
+// gf_propagate_sets (gf_rowsets.h) over the stored chains, chain ch with its model; nothing for an empty chain
 template <class After>
 int for_each_chain(const GfChainView& v, gf_model* const* models, double* d_fr, int32_t* d_st, bool per_chain_scratch, bool full_grids,
                    hipError_t* e, After after)
 {
-    const int64_t per_chain = v.nstored * v.nwalkers;
-    int rc = GF_OK;
-    if (full_grids) gf_internal_full_arbitration_grids(v.device, v.stream, 1);
-    for (int ch = 0; ch < v.nchains && rc == GF_OK && *e == hipSuccess && per_chain > 0; ++ch) {
-        const size_t at = per_chain_scratch ? (size_t)ch * per_chain : 0;
-        rc = gf_model_propagate_on(chain_model(v, models, ch), v.stream, chain_theta(v, ch), GF_LAYOUT_AOS, per_chain, d_fr + at * 3, d_st ? d_st + at : nullptr);
-        if (rc == GF_OK) *e = after(ch, chain_theta(v, ch), d_fr + at * 3, d_st ? d_st + at : nullptr);
+    return gf_propagate_sets(v.device, v.stream, v.nchains, v.nstored * v.nwalkers, d_fr, d_st, per_chain_scratch, full_grids, e,
+                             [&](int ch, const double** th) { *th = chain_theta(v, ch); return chain_model(v, models, ch); }, after, [](int) { return hipSuccess; });
+}
+
+// the stored chain itself as row sets: no copy, nothing enqueued
+GfRowSets chain_as_rows(const GfChainView& v)
+{
+    return GfRowSets{const_cast<double*>(v.d_chain), v.nstore_cap * v.nwalkers * v.ndim, v.nchains, v.nstored * v.nwalkers, v.ndim, v.device, v.stream, v.cus};
+}
+
+// The rows of every stored chain for a reducer.  with_fr = 0 (and an empty chain): the chain itself once the stream has drained;
+// with_fr = 1: the rows a scan saves, assembled in scratch (gf_sampler_postprocess_rows_device).  They never leave the device.
+int chain_rows(gf_sampler* s, const GfChainView& v, gf_model* const* models, int with_fr, GfScratch& buf, const char* who, GfRowSets* r)
+{
+    *r = chain_as_rows(v);
+    if (!with_fr || r->n == 0) {
+        GF_HIP(hipStreamSynchronize(v.stream));
+        if (with_fr) { r->stride = 0; r->width = 3 + v.ndim; }
+        return GF_OK;
     }
-    if (full_grids) gf_internal_full_arbitration_grids(v.device, v.stream, 0);
-    return rc;
+    const int rc = gf_rowsets_take(buf, *r, 3 + v.ndim, who, r);
+    return rc != GF_OK ? rc : gf_sampler_postprocess_rows_device(s, models, r->d_rows);
+}
+
+// A reducer (gf_rowsets_reduce: marginals or intervals, by the spec's type) over chain_rows' rows, or (elements) over the stored chains
+// pushed through `plan` into a buffer of the library's cache (gf_elements.hip: the stored chain is only read, models play no part)
+template <class Spec, class Out>
+int chain_reduce(gf_sampler* s, gf_model* const* models, int with_fr, bool elements, const gf_element_plan* plan, const Spec* spec, const Out* out,
+                 const char* who)
+{
+    GfChainView v; if (gf_internal_sampler_chain_view(s, &v) != GF_OK) return GF_ERR_INVALID_ARG;
+    const int width = elements ? gf_element_plan_width(plan, v.ndim) : (with_fr ? 3 : 0) + v.ndim;
+    if (width < 0) return GF_ERR_INVALID_ARG;
+    int rc = gf_rowsets_check(v.nchains, v.nstored * v.nwalkers, width, spec);
+    if (rc != GF_OK) return rc;
+    if (!elements && check_chain_models(v, models) != GF_OK) return GF_ERR_INVALID_ARG;
+    GF_HIP(hipSetDevice(v.device));
+    GfScratch buf; GfRowSets r;
+    if (!elements) rc = chain_rows(s, v, models, with_fr, buf, who, &r);
+    else if ((rc = gf_rowsets_take(buf, chain_as_rows(v), width, who, &r)) == GF_OK) rc = gf_rowsets_elements(chain_as_rows(v), plan, r, who);
+    return rc != GF_OK ? rc : gf_rowsets_reduce(r, spec, out);
 }
 
 }  // namespace
@@ -87,9 +111,12 @@ int gf_sampler_postprocess_with(gf_sampler* s, gf_model* const* models, double* 
     const size_t nbin3 = counts ? (size_t)nbins * nbins * nbins : 0;
     GfScratch buf;
     double* d_fr = nullptr; int32_t* d_st = nullptr; uint64_t* d_c = nullptr;
-    hipError_t e = buf.get(&d_fr, sizeof(double) * 3 * per_chain);
-    if (e == hipSuccess && status) e = buf.get(&d_st, sizeof(int32_t) * per_chain);
-    if (e == hipSuccess && counts) e = buf.get(&d_c, sizeof(uint64_t) * nbin3);
+    const char* who = "gf_sampler_postprocess";
+    buf.take(&d_fr, sizeof(double) * 3 * per_chain, who);             // sticky (gf_host.h): a run of takes is checked once
+    if (status) buf.take(&d_st, sizeof(int32_t) * per_chain, who);
+    if (counts) buf.take(&d_c, sizeof(uint64_t) * nbin3, who);
+    if (buf.failed != GF_OK) return buf.failed;
+    hipError_t e = hipSuccess;
     // propagate, histogram, copies back; the scratch buffers are reused chain after chain, one sync at the end.
     // Not under full arbitration grids, alone among the entry points: inherited, not decided (it sizes grids, so it is a speed question)
     const int rc = for_each_chain(v, models, d_fr, d_st, false, false, &e, [&](int ch, const double*, double*, int32_t*) {
@@ -105,7 +132,7 @@ int gf_sampler_postprocess_with(gf_sampler* s, gf_model* const* models, double* 
     });
     e = first_error(e, hipStreamSynchronize(st));
     if (rc != GF_OK) return rc;
-    if (e != hipSuccess) return gf_hip_fail(e, "gf_sampler_postprocess");
+    if (e != hipSuccess) return gf_hip_fail(e, who);
     return status ? gf_internal_check_overflow(v.device, st) : GF_OK;
 }
 
@@ -135,8 +162,8 @@ int gf_sampler_postprocess_rows_device(gf_sampler* s, gf_model* const* models, d
     if (per_chain == 0) { GF_HIP(hipStreamSynchronize(st)); return GF_OK; }
     GfScratch buf;
     double* d_fr = nullptr; int32_t* d_st = nullptr;
-    GF_HIP(buf.get(&d_fr, sizeof(double) * 3 * per_chain * v.nchains));
-    GF_HIP(buf.get(&d_st, sizeof(int32_t) * per_chain * v.nchains));
+    buf.take(&d_fr, sizeof(double) * 3 * per_chain * v.nchains, "gf_sampler_postprocess_rows_device");
+    if (buf.take(&d_st, sizeof(int32_t) * per_chain * v.nchains, "gf_sampler_postprocess_rows_device") != GF_OK) return buf.failed;
     const int rc = gf_sampler_postprocess_device(s, models, d_fr, d_st);
     hipError_t e = hipSuccess;
     for (int ch = 0; ch < v.nchains && rc == GF_OK && e == hipSuccess; ++ch)
@@ -168,10 +195,12 @@ int gf_sampler_postprocess_rows(gf_sampler* s, gf_model* const* models, double* 
     double *d_fr = nullptr, *d_rows = nullptr; int32_t* d_st = nullptr;
     void* copy_stream = nullptr;
     hipEvent_t ev[MAX_GROUPS] = {};
-    int rc = GF_OK;
-    hipError_t e = buf.get(&d_fr, sizeof(double) * 3 * per_chain * v.nchains);
-    if (e == hipSuccess) e = buf.get(&d_st, sizeof(int32_t) * per_chain * v.nchains);
-    if (e == hipSuccess) e = buf.get(&d_rows, chain_bytes * v.nchains);
+    const char* who = "gf_sampler_postprocess_rows";
+    buf.take(&d_fr, sizeof(double) * 3 * per_chain * v.nchains, who);
+    buf.take(&d_st, sizeof(int32_t) * per_chain * v.nchains, who);
+    int rc = buf.take(&d_rows, chain_bytes * v.nchains, who);
+    if (rc != GF_OK) return rc;
+    hipError_t e = hipSuccess;
     for (int g = 0; g < ngroups && e == hipSuccess; ++g) e = hipEventCreateWithFlags(&ev[g], hipEventDisableTiming);
     if (e == hipSuccess) rc = gf_internal_borrow_copy_stream(v.device, &copy_stream);
     if (e == hipSuccess && rc == GF_OK) {
@@ -199,7 +228,7 @@ int gf_sampler_postprocess_rows(gf_sampler* s, gf_model* const* models, double* 
     if (copy_stream) { (void)hipStreamSynchronize((hipStream_t)copy_stream); gf_internal_return_copy_stream(v.device, copy_stream); }
     for (int g = 0; g < ngroups; ++g) if (ev[g]) (void)hipEventDestroy(ev[g]);
     if (rc != GF_OK) return rc;
-    if (e != hipSuccess) return gf_hip_fail(e, "gf_sampler_postprocess_rows");
+    if (e != hipSuccess) return gf_hip_fail(e, who);
     return gf_internal_check_overflow(v.device, st);
 }
 
@@ -209,6 +238,7 @@ int gf_sampler_regions(gf_sampler* s, gf_model* const* models, int nbins, int ra
                        int ncov, int64_t cap, int64_t* thres, int32_t* saturated, double* level_in, double* level_out, double* mass,
                        int32_t* cells, double* density)
 {
+    const char* who = "gf_sampler_regions";
     GfChainView v; if (gf_internal_sampler_chain_view(s, &v) != GF_OK) return GF_ERR_INVALID_ARG;
     int rc = gf_region_check_args(v.nchains, nbins, radius, weights, coverage, ncov, cap);
     if (rc != GF_OK) return rc;
@@ -217,70 +247,30 @@ int gf_sampler_regions(gf_sampler* s, gf_model* const* models, int nbins, int ra
     GF_HIP(hipSetDevice(v.device));
     hipStream_t st = v.stream;
     const int64_t per_chain = v.nstored * v.nwalkers;
-    const size_t nbin3 = (size_t)nbins * nbins * nbins;
-    GfScratch buf;
-    double* d_fr = nullptr; int32_t* d_st = nullptr; uint64_t* d_c = nullptr;
-    hipError_t e = buf.get(&d_c, sizeof(uint64_t) * nbin3 * v.nchains);
-    if (e == hipSuccess) e = hipMemsetAsync(d_c, 0, sizeof(uint64_t) * nbin3 * v.nchains, st);
-    if (e == hipSuccess && per_chain > 0) e = buf.get(&d_fr, sizeof(double) * 3 * per_chain);
-    if (e == hipSuccess && per_chain > 0) e = buf.get(&d_st, sizeof(int32_t) * per_chain);
-    if (e == hipSuccess && per_chain > 0)
-        rc = for_each_chain(v, models, d_fr, d_st, false, true, &e, [&](int ch, const double*, double*, int32_t*) {
-            const hipError_t ea = gf_launch_mask_fr(d_fr, d_st, per_chain, st);
-            return ea != hipSuccess ? ea : gf_launch_flavor_hist(d_fr, per_chain, nbins, (unsigned long long*)(d_c + (size_t)ch * nbin3), cus, st);
-        });
+    GfScratch buf; GfRegionSets sets; double* d_fr = nullptr; int32_t* d_st = nullptr;
+    rc = sets.begin(buf, v.nchains, nbins, cus, st, who);
+    if (rc == GF_OK && per_chain > 0) { buf.take(&d_fr, sizeof(double) * 3 * per_chain, who); rc = buf.take(&d_st, sizeof(int32_t) * per_chain, who); }
+    hipError_t e = hipSuccess;
+    if (rc == GF_OK && per_chain > 0)
+        rc = for_each_chain(v, models, d_fr, d_st, false, true, &e, [&](int ch, const double*, double*, int32_t*) { return sets.add(ch, d_fr, d_st, per_chain); });
     if (e == hipSuccess && rc == GF_OK)
-        rc = gf_region_run(st, d_c, v.nchains, nbins, radius, weights, coverage, ncov, cap, thres, saturated, level_in, level_out, mass, cells,
-                           density, nullptr);
+        rc = sets.run(radius, weights, coverage, ncov, cap, thres, saturated, level_in, level_out, mass, cells, density);
     else
-        (void)hipStreamSynchronize(st);
+        (void)hipStreamSynchronize(st);             // a refused take included: the counts' memset may be pending when they are released
     if (rc != GF_OK) return rc;
-    if (e != hipSuccess) return gf_hip_fail(e, "gf_sampler_regions");
+    if (e != hipSuccess) return gf_hip_fail(e, who);
     return per_chain > 0 ? gf_internal_check_overflow(v.device, st) : GF_OK;
 }
 
-// The marginals of every stored chain (gf_marginal.hip).  with_fr: the rows a scan saves are assembled first
-// (gf_sampler_postprocess_rows_device) and reduced in place of the chain; either way the rows never leave the device.
+// The marginals of every stored chain (gf_marginal.hip), and of every stored chain in element space
 int gf_sampler_marginals(gf_sampler* s, gf_model* const* models, int with_fr, const gf_marginal_spec* spec, const gf_marginal_out* out)
 {
-    GfChainView v; if (gf_internal_sampler_chain_view(s, &v) != GF_OK || !out) return GF_ERR_INVALID_ARG;
-    const int width = (with_fr ? 3 : 0) + v.ndim;
-    const int64_t per_chain = v.nstored * v.nwalkers;
-    int rc = gf_marginal_check_args(v.nchains, per_chain, width, spec);
-    if (rc != GF_OK) return rc;
-    if (check_chain_models(v, models) != GF_OK) return GF_ERR_INVALID_ARG;
-    GF_HIP(hipSetDevice(v.device));
-    hipStream_t st = v.stream;
-    if (!with_fr || per_chain == 0) {
-        GF_HIP(hipStreamSynchronize(st));
-        return gf_marginal_run(st, v.d_chain, with_fr ? 0 : v.nstore_cap * v.nwalkers * v.ndim, v.nchains, per_chain, width, spec, out);
-    }
-    GfScratch buf;
-    double* d_rows = nullptr;
-    GF_HIP(buf.get(&d_rows, sizeof(double) * (size_t)per_chain * width * v.nchains));
-    rc = gf_sampler_postprocess_rows_device(s, models, d_rows);
-    return rc != GF_OK ? rc : gf_marginal_run(st, d_rows, per_chain * width, v.nchains, per_chain, width, spec, out);
+    return out ? chain_reduce(s, models, with_fr, false, nullptr, spec, out, "gf_sampler_marginals") : GF_ERR_INVALID_ARG;
 }
 
-// The marginals of every stored chain in element space (gf_elements.hip): the chains are transformed into a buffer of the
-// library's cache, which is reduced in place of the chain; the stored chain is only read and the rows never leave the device.
 int gf_sampler_element_marginals(gf_sampler* s, const gf_element_plan* plan, const gf_marginal_spec* spec, const gf_marginal_out* out)
 {
-    GfChainView v; if (gf_internal_sampler_chain_view(s, &v) != GF_OK || !out) return GF_ERR_INVALID_ARG;
-    const int width = gf_element_plan_width(plan, v.ndim);
-    if (width < 0) return GF_ERR_INVALID_ARG;
-    const int64_t per_chain = v.nstored * v.nwalkers;
-    const int rc = gf_marginal_check_args(v.nchains, per_chain, width, spec);
-    if (rc != GF_OK) return rc;
-    GF_HIP(hipSetDevice(v.device));
-    hipStream_t st = v.stream;
-    GfScratch buf;
-    double* d_rows = nullptr;
-    GF_HIP(buf.get(&d_rows, sizeof(double) * (size_t)per_chain * width * v.nchains));
-    const hipError_t e = gf_element_run(st, v.d_chain, v.nstore_cap * v.nwalkers * v.ndim, v.nchains, per_chain, v.ndim, plan, d_rows,
-                                        per_chain * width, v.cus);
-    if (e != hipSuccess) return gf_hip_fail(e, "gf_sampler_element_marginals");
-    return gf_marginal_run(st, d_rows, per_chain * width, v.nchains, per_chain, width, spec, out);
+    return out ? chain_reduce(s, nullptr, 0, true, plan, spec, out, "gf_sampler_element_marginals") : GF_ERR_INVALID_ARG;
 }
 
 // The convergence diagnostics of every stored chain (gf_diag.hip); the stored chain is only read and only the results come back.
@@ -294,82 +284,46 @@ int gf_sampler_diagnostics(gf_sampler* s, const gf_diag_spec* spec, const gf_dia
     return gf_diag_run(v.stream, v.d_chain, v.nstore_cap * v.nwalkers * v.ndim, v.nchains, v.nstored, v.nwalkers, v.ndim, spec, out);
 }
 
-// The column intervals of every stored chain (gf_interval.hip) over gf_sampler_marginals' rows, which never leave the device.
+// The column intervals of every stored chain (gf_interval.hip), and of every stored chain in element space
 int gf_sampler_intervals(gf_sampler* s, gf_model* const* models, int with_fr, const gf_interval_spec* spec, const gf_interval_out* out)
 {
-    GfChainView v; if (gf_internal_sampler_chain_view(s, &v) != GF_OK || !spec || !out) return GF_ERR_INVALID_ARG;
-    const int width = (with_fr ? 3 : 0) + v.ndim;
-    const int64_t per_chain = v.nstored * v.nwalkers;
-    int rc = gf_interval_check_args(v.nchains, per_chain, width, spec);
-    if (rc != GF_OK) return rc;
-    if (check_chain_models(v, models) != GF_OK) return GF_ERR_INVALID_ARG;
-    GF_HIP(hipSetDevice(v.device));
-    hipStream_t st = v.stream;
-    if (!with_fr) {
-        GF_HIP(hipStreamSynchronize(st));
-        return gf_interval_run(st, v.d_chain, v.nstore_cap * v.nwalkers * v.ndim, v.nchains, per_chain, width, spec, out, nullptr);
-    }
-    GfScratch buf;
-    double* d_rows = nullptr;
-    GF_HIP(buf.get(&d_rows, sizeof(double) * (size_t)per_chain * width * v.nchains));
-    rc = gf_sampler_postprocess_rows_device(s, models, d_rows);
-    return rc != GF_OK ? rc : gf_interval_run(st, d_rows, per_chain * width, v.nchains, per_chain, width, spec, out, nullptr);
+    return spec && out ? chain_reduce(s, models, with_fr, false, nullptr, spec, out, "gf_sampler_intervals") : GF_ERR_INVALID_ARG;
 }
 
-// The column intervals of every stored chain in element space: gf_sampler_element_marginals' rows.
 int gf_sampler_element_intervals(gf_sampler* s, const gf_element_plan* plan, const gf_interval_spec* spec, const gf_interval_out* out)
 {
-    GfChainView v; if (gf_internal_sampler_chain_view(s, &v) != GF_OK || !spec || !out) return GF_ERR_INVALID_ARG;
-    const int width = gf_element_plan_width(plan, v.ndim);
-    if (width < 0) return GF_ERR_INVALID_ARG;
-    const int64_t per_chain = v.nstored * v.nwalkers;
-    const int rc = gf_interval_check_args(v.nchains, per_chain, width, spec);
-    if (rc != GF_OK) return rc;
-    GF_HIP(hipSetDevice(v.device));
-    hipStream_t st = v.stream;
-    GfScratch buf;
-    double* d_rows = nullptr;
-    GF_HIP(buf.get(&d_rows, sizeof(double) * (size_t)per_chain * width * v.nchains));
-    const hipError_t e = gf_element_run(st, v.d_chain, v.nstore_cap * v.nwalkers * v.ndim, v.nchains, per_chain, v.ndim, plan, d_rows,
-                                        per_chain * width, v.cus);
-    if (e != hipSuccess) return gf_hip_fail(e, "gf_sampler_element_intervals");
-    return gf_interval_run(st, d_rows, per_chain * width, v.nchains, per_chain, width, spec, out, nullptr);
+    return spec && out ? chain_reduce(s, nullptr, 0, true, plan, spec, out, "gf_sampler_element_intervals") : GF_ERR_INVALID_ARG;
 }
 
 // The energy-resolved composition of every stored chain (gf_spectrum.hip).  Chain after chain through one bin-major slab: the
-// propagation leaves the verdict in d_st (its compositions go to the head of the slab and are overwritten), k_bsm_bins fills the slab,
-// gf_marginal_run reduces it with the energy bins as its chains (synchronous, so the slab is free for the next chain).
+// propagation leaves the verdict in d_st (its compositions go to the head of the slab and are overwritten), gf_spectrum_set fills the
+// slab and reduces it with the energy bins as its chains (synchronous, so the slab is free for the next chain).
 int gf_sampler_spectrum(gf_sampler* s, gf_model* const* models, const gf_spectrum_spec* spec, const gf_spectrum_out* out)
 {
+    const char* who = "gf_sampler_spectrum";
     GfChainView v; if (gf_internal_sampler_chain_view(s, &v) != GF_OK) return GF_ERR_INVALID_ARG;
     const int64_t per_chain = v.nstored * v.nwalkers;
     if (check_chain_models(v, models) != GF_OK) return GF_ERR_INVALID_ARG;
     int nbins_e = -1;
-    for (int ch = 0; ch < v.nchains; ++ch) {
-        const int nb = gf_model_nbins(chain_model(v, models, ch));
-        if (nb < 1) return GF_ERR_UNSUPPORTED;
-        if (nbins_e >= 0 && nb != nbins_e) return gf_fail_msg(GF_ERR_INVALID_ARG, "spectrum: chain %d has %d energy bins, chain 0 has %d", ch, nb, nbins_e);
-        nbins_e = nb;
-    }
-    int rc = gf_spectrum_check_args(nbins_e, per_chain, spec, out);
+    int rc = gf_spectrum_common_nbins(v.nchains, [&](int ch) { return chain_model(v, models, ch); }, "chain", &nbins_e);
+    if (rc == GF_OK) rc = gf_spectrum_check_args(nbins_e, per_chain, spec, out);
     if (rc != GF_OK) return rc;
     GF_HIP(hipSetDevice(v.device));
     hipStream_t st = v.stream;
     GfScratch buf;
     double* d_slab = nullptr; int32_t* d_st = nullptr;
-    hipError_t e = buf.get(&d_slab, sizeof(double) * 3 * (size_t)per_chain * nbins_e);
-    if (e == hipSuccess) e = buf.get(&d_st, sizeof(int32_t) * (size_t)per_chain);
-    if (e != hipSuccess) return gf_hip_fail(e, "gf_sampler_spectrum: scratch");
+    buf.take(&d_slab, sizeof(double) * 3 * (size_t)per_chain * nbins_e, who);
+    if (buf.take(&d_st, sizeof(int32_t) * (size_t)per_chain, who) != GF_OK) return buf.failed;
     int rs = GF_OK;
+    hipError_t e = hipSuccess;
     rc = for_each_chain(v, models, d_slab, d_st, false, true, &e, [&](int ch, const double* d_theta, double*, int32_t*) {
-        rs = gf_model_bins_on(chain_model(v, models, ch), st, d_theta, GF_LAYOUT_AOS, per_chain, d_slab, 1, d_st);
-        if (rs == GF_OK) rs = gf_spectrum_reduce(st, d_slab, nbins_e, per_chain, spec, out, ch);
+        rs = gf_spectrum_set(chain_model(v, models, ch), st, d_theta, per_chain, d_slab, d_st, nbins_e, spec, out, ch);
         return rs == GF_OK ? hipSuccess : hipErrorUnknown;
     });
     e = first_error(e, hipStreamSynchronize(st));
     if (rc != GF_OK) return rc;
     if (rs != GF_OK) return rs;
-    if (e != hipSuccess) return gf_hip_fail(e, "gf_sampler_spectrum");
+    if (e != hipSuccess) return gf_hip_fail(e, who);
     return gf_internal_check_overflow(v.device, st);
 }
 

@@ -1,6 +1,7 @@
 // gf_reweight.hip -- every stored chain of a sampler reweighted to other targets: the log-weights lnw = l_t - l0 of the
-// chain's rows under each target by gf_reweight.hpp's rules, then gf_nested_post.hip's weight pipeline (gf_weights.h) with the T
-// targets of a chain as T runs that share one theta, the chain's rows in place.
+// chain's rows under each target by gf_reweight.hpp's rules, then the weight pipeline (gf_weights.h, gf_weights.hip) with the T
+// targets of a chain as T runs that share one theta, the chain's rows in place.  The equal-weight rows [nchains * T][N][width] are
+// one of the three sources of gf_rowsets.h (rw_row_sets) for the reductions.
 //   k_rw_gauss   measurement targets: a lane per row; the row's composition and status (one propagation of the chain) are read once,
 //                the Gaussian block of lnprob is evaluated for the sampling model and for every target (constants in the kernel
 //                arguments), lnw [t][i] is written target by target, consecutive lanes on consecutive rows
@@ -21,10 +22,8 @@
 
 #include "gf_devcache.h"
 #include "gf_host.h"                    // (after gf_devcache.h: GfScratch allocates through the cache)
+#include "gf_rowsets.h"
 #include "gf_device.hpp"
-#include "gf_interval.h"
-#include "gf_marginal.h"
-#include "gf_region.h"
 #include "gf_reweight.hpp"
 #include "gf_weights.h"
 
@@ -157,11 +156,6 @@ size_t rw_scratch_cap()
     return (size_t)GF_REWEIGHT_SCRATCH_DEFAULT;
 }
 
-int rw_alloc_fail(const char* who, size_t bytes)
-{
-    return gf_fail_msg(GF_ERR_ALLOC, "%s: %zu bytes of device scratch were not granted", who, bytes);
-}
-
 gf_model* rw_chain_model(const GfChainView& v, int ch) { return v.models ? v.models[ch] : v.model; }
 
 // what a call wants of the engine
@@ -234,36 +228,32 @@ int rw_run(gf_sampler* s, const gf_reweight_spec* spec, const RwWant& want, cons
     const int width = (want.with_fr ? 3 : 0) + nd;
 
     GfScratch buf;
-    size_t bad = 0;
-    auto get = [&](auto** p, size_t bytes) {
-        if (buf.get(p, bytes) == hipSuccess) return true;
-        (void)hipGetLastError();
-        bad = bytes;
-        return false;
-    };
     double *d_fr = nullptr, *d_lnw = nullptr, *d_stat = nullptr, *d_mean = nullptr, *d_cov = nullptr, *d_thN = nullptr, *d_frN = nullptr;
     int32_t *d_st = nullptr, *d_stN = nullptr;
     GfWeightRun* d_runs = nullptr;
     uint64_t* d_ids = nullptr;
     unsigned long long* d_cnt = nullptr;
     int64_t* d_index = want.d_index;
-    bool got = get(&d_st, sizeof(int32_t) * n) && (!measured || get(&d_fr, sizeof(double) * 3 * n)) && get(&d_lnw, sizeof(double) * Tb * n) &&
-               get(&a.w, sizeof(double) * Tb * n) && get(&a.part, sizeof(double) * Tb * a.maxleaves * K) && get(&d_stat, sizeof(double) * CT * GF_WEIGHT_STAT) &&
-               get(&d_mean, sizeof(double) * CT * GF_MAX_DIM) && get(&d_cov, sizeof(double) * CT * GF_MAX_DIM * GF_MAX_DIM) &&
-               get(&d_runs, sizeof(GfWeightRun) * Tb) && get(&d_ids, sizeof(uint64_t) * Tb) && get(&d_cnt, sizeof(unsigned long long) * nch * ncnt);
-    if (got && prefix)
-        got = get(&a.C, sizeof(double) * Tb * n) && get(&a.tot, sizeof(double) * Tb * a.maxleaves * GF_WEIGHT_TOT_PER_LEAF) &&
-              (d_index || get(&d_index, sizeof(int64_t) * CT * N));
-    if (got && prefix && want.with_fr && !measured)
-        got = get(&d_thN, sizeof(double) * Tb * N * nd) && get(&d_frN, sizeof(double) * 3 * N) && get(&d_stN, sizeof(int32_t) * N);
-    if (!got) return rw_alloc_fail(who, bad);
+    buf.take(&d_st, sizeof(int32_t) * n, who);                        // sticky (gf_host.h): the run of takes is checked once, below
+    if (measured) buf.take(&d_fr, sizeof(double) * 3 * n, who);
+    buf.take(&d_lnw, sizeof(double) * Tb * n, who); buf.take(&a.w, sizeof(double) * Tb * n, who);
+    buf.take(&a.part, sizeof(double) * Tb * a.maxleaves * K, who); buf.take(&d_stat, sizeof(double) * CT * GF_WEIGHT_STAT, who);
+    buf.take(&d_mean, sizeof(double) * CT * GF_MAX_DIM, who); buf.take(&d_cov, sizeof(double) * CT * GF_MAX_DIM * GF_MAX_DIM, who);
+    buf.take(&d_runs, sizeof(GfWeightRun) * Tb, who); buf.take(&d_ids, sizeof(uint64_t) * Tb, who);
+    buf.take(&d_cnt, sizeof(unsigned long long) * nch * ncnt, who);
+    if (prefix) { buf.take(&a.C, sizeof(double) * Tb * n, who); buf.take(&a.tot, sizeof(double) * Tb * a.maxleaves * GF_WEIGHT_TOT_PER_LEAF, who); }
+    if (prefix && !d_index) buf.take(&d_index, sizeof(int64_t) * CT * N, who);
+    if (prefix && want.with_fr && !measured) {
+        buf.take(&d_thN, sizeof(double) * Tb * N * nd, who); buf.take(&d_frN, sizeof(double) * 3 * N, who); buf.take(&d_stN, sizeof(int32_t) * N, who);
+    }
+    if (buf.failed != GF_OK) return buf.failed;
     a.lnw = d_lnw;
     a.runs = d_runs;
     a.ids = d_ids;
 
     hipError_t e = hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long) * nch * ncnt, st);
     std::vector<unsigned long long> h_cnt((size_t)nch * ncnt, 0);
-    gf_internal_full_arbitration_grids(v.device, st, 1);             // the chains of a scan differ (gf_postprocess.hip for_each_chain)
+    gf_internal_full_arbitration_grids(v.device, st, 1);             // the chains of a scan differ (gf_rowsets.h gf_propagate_sets)
     for (int ch = c0; ch < c1 && rc == GF_OK && e == hipSuccess; ++ch) {
         const double* theta = v.d_chain + (size_t)ch * v.nstore_cap * v.nwalkers * nd;
         const double* l0 = v.d_lnp_chain + (size_t)ch * v.nstore_cap * v.nwalkers;
@@ -377,15 +367,36 @@ int rw_run(gf_sampler* s, const gf_reweight_spec* spec, const RwWant& want, cons
     return GF_OK;
 }
 
-// the equal-weight rows of every (chain, target) into a scratch buffer of `buf`: *d_rows [nchains * T][N][width]
-int rw_rows_scratch(gf_sampler* s, const gf_reweight_spec* rw, int64_t N, int with_fr, GfScratch& buf, const GfChainView& v, double** d_rows,
-                    const char* who)
+// what the rows and reduction entry points ask first
+bool rw_view(gf_sampler* s, const gf_reweight_spec* rw, int64_t nrows, GfChainView* v)
 {
-    const size_t bytes = sizeof(double) * (size_t)v.nchains * rw->ntargets * N * ((with_fr ? 3 : 0) + v.ndim);
-    if (buf.get(d_rows, bytes) != hipSuccess) { (void)hipGetLastError(); return rw_alloc_fail(who, bytes); }
-    RwWant w;
-    w.N = N; w.with_fr = with_fr; w.d_rows = *d_rows;
-    return rw_run(s, rw, w, who);
+    return gf_internal_sampler_chain_view(s, v) == GF_OK && rw && rw->ntargets >= 1 && rw->ntargets <= GF_REWEIGHT_MAX_TARGETS && nrows >= 1;
+}
+
+// The equal-weight rows of every (chain, target) for a reducer, in a buffer of buf: *r [nchains * T][N][(with_fr ? 3 : 0) + ndim].
+// check: what the reducer's check_args says of (nchains * T, N, width), before any device work
+template <class Check>
+int rw_row_sets(gf_sampler* s, const gf_reweight_spec* rw, int64_t N, int with_fr, Check check, GfScratch& buf, const char* who, GfRowSets* r)
+{
+    GfChainView v;
+    if (!rw_view(s, rw, N, &v)) return GF_ERR_INVALID_ARG;
+    const int width = (with_fr ? 3 : 0) + v.ndim, batch = v.nchains * rw->ntargets;
+    int rc = check(batch, N, width);
+    if (rc != GF_OK) return rc;
+    GF_HIP(hipSetDevice(v.device));
+    RwWant w; w.N = N; w.with_fr = with_fr;
+    rc = gf_rowsets_take(buf, GfRowSets{nullptr, 0, batch, N, 0, v.device, v.stream, v.cus}, width, who, r);
+    w.d_rows = r->d_rows;
+    return rc != GF_OK ? rc : rw_run(s, rw, w, who);
+}
+
+// a reducer (gf_rowsets_reduce: marginals or intervals, by the spec's type) over rw_row_sets' rows
+template <class Spec, class Out>
+int rw_reduce(gf_sampler* s, const gf_reweight_spec* rw, int64_t nrows, int with_fr, const Spec* spec, const Out* out, const char* who)
+{
+    GfScratch buf; GfRowSets r;
+    const int rc = rw_row_sets(s, rw, nrows, with_fr, [&](int nsets, int64_t n, int width) { return gf_rowsets_check(nsets, n, width, spec); }, buf, who, &r);
+    return rc != GF_OK ? rc : gf_rowsets_reduce(r, spec, out);
 }
 
 }  // namespace
@@ -421,16 +432,13 @@ int gf_sampler_reweight_rows(gf_sampler* s, const gf_reweight_spec* spec, int64_
 {
     const char* who = "gf_sampler_reweight_rows";
     GfChainView v;
-    if (gf_internal_sampler_chain_view(s, &v) != GF_OK || !spec || spec->ntargets < 1 || spec->ntargets > GF_REWEIGHT_MAX_TARGETS || nrows < 1 || !rows)
-        return GF_ERR_INVALID_ARG;
+    if (!rw_view(s, spec, nrows, &v) || !rows) return GF_ERR_INVALID_ARG;
     GF_HIP(hipSetDevice(v.device));
     const size_t RN = (size_t)v.nchains * spec->ntargets * nrows, width = (with_fr ? 3 : 0) + (size_t)v.ndim;
-    GfScratch buf;
-    RwWant w;
-    w.N = nrows; w.with_fr = with_fr;
-    if (buf.get(&w.d_rows, sizeof(double) * RN * width) != hipSuccess) { (void)hipGetLastError(); return rw_alloc_fail(who, sizeof(double) * RN * width); }
-    if (buf.get(&w.d_index, sizeof(int64_t) * RN) != hipSuccess) { (void)hipGetLastError(); return rw_alloc_fail(who, sizeof(int64_t) * RN); }
-    int rc = rw_run(s, spec, w, who);
+    GfScratch buf; RwWant w; w.N = nrows; w.with_fr = with_fr;
+    buf.take(&w.d_rows, sizeof(double) * RN * width, who);
+    int rc = buf.take(&w.d_index, sizeof(int64_t) * RN, who);
+    if (rc == GF_OK) rc = rw_run(s, spec, w, who);
     if (rc == GF_OK) rc = gf_internal_d2h(v.device, v.stream, rows, w.d_rows, sizeof(double) * RN * width);
     if (rc == GF_OK && index) {
         GF_HIP(hipMemcpyAsync(index, w.d_index, sizeof(int64_t) * RN, hipMemcpyDeviceToHost, v.stream));
@@ -442,33 +450,13 @@ int gf_sampler_reweight_rows(gf_sampler* s, const gf_reweight_spec* spec, int64_
 int gf_sampler_reweight_marginals(gf_sampler* s, const gf_reweight_spec* rw, int64_t nrows, int with_fr, const gf_marginal_spec* spec,
                                   const gf_marginal_out* out)
 {
-    GfChainView v;
-    if (gf_internal_sampler_chain_view(s, &v) != GF_OK || !rw || rw->ntargets < 1 || rw->ntargets > GF_REWEIGHT_MAX_TARGETS || nrows < 1 || !out)
-        return GF_ERR_INVALID_ARG;
-    const int width = (with_fr ? 3 : 0) + v.ndim, batch = v.nchains * rw->ntargets;
-    int rc = gf_marginal_check_args(batch, nrows, width, spec);
-    if (rc != GF_OK) return rc;
-    GF_HIP(hipSetDevice(v.device));
-    GfScratch buf;
-    double* d_rows = nullptr;
-    rc = rw_rows_scratch(s, rw, nrows, with_fr, buf, v, &d_rows, "gf_sampler_reweight_marginals");
-    return rc != GF_OK ? rc : gf_marginal_run(v.stream, d_rows, nrows * width, batch, nrows, width, spec, out);
+    return out ? rw_reduce(s, rw, nrows, with_fr, spec, out, "gf_sampler_reweight_marginals") : GF_ERR_INVALID_ARG;
 }
 
 int gf_sampler_reweight_intervals(gf_sampler* s, const gf_reweight_spec* rw, int64_t nrows, int with_fr, const gf_interval_spec* spec,
                                   const gf_interval_out* out)
 {
-    GfChainView v;
-    if (gf_internal_sampler_chain_view(s, &v) != GF_OK || !rw || rw->ntargets < 1 || rw->ntargets > GF_REWEIGHT_MAX_TARGETS || nrows < 1 || !spec || !out)
-        return GF_ERR_INVALID_ARG;
-    const int width = (with_fr ? 3 : 0) + v.ndim, batch = v.nchains * rw->ntargets;
-    int rc = gf_interval_check_args(batch, nrows, width, spec);
-    if (rc != GF_OK) return rc;
-    GF_HIP(hipSetDevice(v.device));
-    GfScratch buf;
-    double* d_rows = nullptr;
-    rc = rw_rows_scratch(s, rw, nrows, with_fr, buf, v, &d_rows, "gf_sampler_reweight_intervals");
-    return rc != GF_OK ? rc : gf_interval_run(v.stream, d_rows, nrows * width, batch, nrows, width, spec, out, nullptr);
+    return spec && out ? rw_reduce(s, rw, nrows, with_fr, spec, out, "gf_sampler_reweight_intervals") : GF_ERR_INVALID_ARG;
 }
 
 // the rows with their compositions, the compositions alone, a histogram per (chain, target), the regions of all of them at once
@@ -477,32 +465,19 @@ int gf_sampler_reweight_regions(gf_sampler* s, const gf_reweight_spec* rw, int64
                                 double* level_out, double* mass, int32_t* cells, double* density)
 {
     const char* who = "gf_sampler_reweight_regions";
-    GfChainView v;
-    if (gf_internal_sampler_chain_view(s, &v) != GF_OK || !rw || rw->ntargets < 1 || rw->ntargets > GF_REWEIGHT_MAX_TARGETS || nrows < 1)
-        return GF_ERR_INVALID_ARG;
-    const int width = 3 + v.ndim, batch = v.nchains * rw->ntargets;
-    int rc = gf_region_check_args(batch, nbins, radius, weights, coverage, ncov, cap);
+    GfScratch buf; GfRowSets r;
+    int rc = rw_row_sets(s, rw, nrows, 1, [&](int nsets, int64_t, int) { return gf_region_check_args(nsets, nbins, radius, weights, coverage, ncov, cap); },
+                         buf, who, &r);
     if (rc != GF_OK) return rc;
-    GF_HIP(hipSetDevice(v.device));
-    hipStream_t st = v.stream;
-    GfScratch buf;
-    double *d_rows = nullptr, *d_fr3 = nullptr;
-    uint64_t* d_c = nullptr;
-    const size_t nbin3 = (size_t)nbins * nbins * nbins;
-    rc = rw_rows_scratch(s, rw, nrows, 1, buf, v, &d_rows, who);
+    double* d_fr3 = nullptr; GfRegionSets sets;
+    buf.take(&d_fr3, sizeof(double) * 3 * (size_t)r.nsets * nrows, who);
+    rc = sets.begin(buf, r.nsets, nbins, r.cus, r.stream, who);
     if (rc != GF_OK) return rc;
-    if (buf.get(&d_fr3, sizeof(double) * 3 * (size_t)batch * nrows) != hipSuccess) { (void)hipGetLastError(); return rw_alloc_fail(who, sizeof(double) * 3 * (size_t)batch * nrows); }
-    if (buf.get(&d_c, sizeof(uint64_t) * nbin3 * batch) != hipSuccess) { (void)hipGetLastError(); return rw_alloc_fail(who, sizeof(uint64_t) * nbin3 * batch); }
-    hipError_t e = hipMemsetAsync(d_c, 0, sizeof(uint64_t) * nbin3 * batch, st);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_rw_fr3, dim3(rw_blocks((int64_t)batch * nrows * 3)), dim3(RW_BLOCK), 0, st, d_rows, (int64_t)batch * nrows, width, d_fr3);
-        e = hipGetLastError();
-    }
-    for (int r = 0; r < batch && e == hipSuccess; ++r)
-        e = gf_launch_flavor_hist(d_fr3 + (size_t)r * nrows * 3, nrows, nbins, (unsigned long long*)(d_c + (size_t)r * nbin3), v.cus, st);
-    if (e != hipSuccess) { (void)hipStreamSynchronize(st); return gf_hip_fail(e, who); }
-    return gf_region_run(st, d_c, batch, nbins, radius, weights, coverage, ncov, cap, thres, saturated, level_in, level_out, mass, cells, density,
-                         nullptr);
+    hipLaunchKernelGGL(k_rw_fr3, dim3(rw_blocks((int64_t)r.nsets * nrows * 3)), dim3(RW_BLOCK), 0, r.stream, r.d_rows, (int64_t)r.nsets * nrows, r.width, d_fr3);
+    hipError_t e = hipGetLastError();
+    for (int k = 0; k < r.nsets && e == hipSuccess; ++k) e = sets.add(k, d_fr3 + (size_t)k * nrows * 3, nullptr, nrows);
+    if (e != hipSuccess) { (void)hipStreamSynchronize(r.stream); return gf_hip_fail(e, who); }
+    return sets.run(radius, weights, coverage, ncov, cap, thres, saturated, level_in, level_out, mass, cells, density);
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
-// Internal interface of the weighted-sample pipeline of gf_nested_post.hip (weights from log-weights, Kish ESS, weighted
-// mean and covariance, the fixed-order prefix, systematic resampling into equal-weight rows) for the callers that bring their own
-// log-weights: the posterior of a nested sampler's runs (gf_nested_post.hip itself) and the reweighting of a stored chain
-// (gf_reweight.hip).  A caller fills the runs and the arrays; the kernels are the same ones, in the same order.
+// Internal interface of the weighted-sample pipeline of gf_weights.hip (weights from log-weights, Kish ESS, weighted mean
+// and covariance, the fixed-order prefix, systematic resampling into equal-weight rows) for the callers that bring their own
+// log-weights: the posterior of a nested sampler's runs (gf_nested_post.hip) and the reweighting of a stored chain (gf_reweight.hip).
+// A caller fills the runs and the arrays; the kernels are the same ones, in the same order.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

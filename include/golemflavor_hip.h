@@ -290,7 +290,14 @@ int gf_sampler_walker_mean(gf_sampler* s, double* mean);
 /* Chain post-processing on the device (scripts/mc_unitary.py:189-193, scripts/mc_texture.py:216-221,
  * golemflavor/plot.py:365-370): composition of every stored sample and/or its [nbins]^3 histogram per
  * chain.  fr [nchains][nstored][nwalkers][3], status [nchains][nstored][nwalkers],
- * counts [nchains][nbins]^3; NULL = skip. */
+ * counts [nchains][nbins]^3; NULL = skip.
+ * Scratch: where a request for the entry point's OWN device scratch is not granted, this entry point and
+ * every other one that takes a sampler's stored chain (gf_sampler_postprocess*, _regions, _marginals,
+ * _intervals, _element_marginals, _element_intervals, _spectrum) return GF_ERR_ALLOC with a message naming
+ * the entry point and the size; earlier builds of these stored-chain entry points returned GF_ERR_HIP
+ * with the failed call's text there.  The nested-posterior and reweighting entry points report it the same way.
+ * The reducers underneath (marginals, intervals, elements, regions, the energy bins) still report a
+ * refused request of theirs as GF_ERR_HIP. */
 int gf_sampler_postprocess(gf_sampler* s, double* fr, int32_t* status, int nbins, uint64_t* counts);
 /* same, chain ch propagated with models[ch] (NULL: the sampling models): scripts/mc_texture.py samples the
  * priors (:148-170) and pushes every sample through flux_averaged_BSMu of the grid point (:216-221) */

@@ -8,11 +8,16 @@ import pytest
 from common import BIN_EDGES, notebook_sets, uniform_theta
 from golemflavor_amd import _lib
 from golemflavor_amd import configs as Cf
+from golemflavor_amd import diagnostics as dg
+from golemflavor_amd import elements as el
+from golemflavor_amd import intervals as iv
 from golemflavor_amd import llh as llh_utils
 from golemflavor_amd import mcmc as mcmc_utils
 from golemflavor_amd.descriptor import compile_model
 from golemflavor_amd.enums import Texture
 from golemflavor_amd.model import Model
+from golemflavor_amd import spectrum as sp
+from golemflavor_amd.reweight import Measurement, Reweighted
 
 pytestmark = pytest.mark.gpu
 
@@ -99,6 +104,58 @@ def observe(s, f, ps, models):
     return out
 
 
+def interval_digest(res):
+    return {k: digest(res[k]) for k in iv.FIELDS}
+
+
+class _NoSummary(Reweighted):
+    """a Reweighted whose making calls nothing: the entry points are called one by one below"""
+
+    def _run_summary(self):
+        return {"nonunitary": np.zeros((self.nchains, self.ntargets), np.int64)}
+
+
+def observe_more(s, f, ps):
+    """the entry points added since `observe` was written, once each on sampler s with the sampling models: {name: [return code, what
+    it returned]}.  They are called below the wrappers that refuse an empty chain in Python."""
+    L, h, m = _lib.lib(), s._h, f.model
+    ns = s.nstored
+    out = {}
+    for with_fr in (0, 1):
+        rc, res = rc_of(lambda: iv.run_interval_call(lambda spec, o: L.gf_sampler_intervals(h, None, with_fr, spec, o), "gf_sampler_intervals",
+                                                     NCHAINS, 3 * with_fr + NDIM, (68., 90.)))
+        out["gf_sampler_intervals with_fr=%d" % with_fr] = [rc, interval_digest(res) if res is not None else None]
+    plan, pnames, _ = el.element_plan(ps)
+    rc, res = rc_of(lambda: iv.run_interval_call(lambda spec, o: L.gf_sampler_element_intervals(h, C.byref(plan), spec, o),
+                                                 "gf_sampler_element_intervals", NCHAINS, len(pnames), (68., 90.)))
+    out["gf_sampler_element_intervals"] = [rc, interval_digest(res) if res is not None else None]
+    prep = sp.prepare(sp.model_edges(m), (16., 84.), 4)
+    rc, res = rc_of(lambda: sp.run_spectrum_call(lambda spec, o: L.gf_sampler_spectrum(h, None, spec, o), "gf_sampler_spectrum", NCHAINS, prep))
+    out["gf_sampler_spectrum"] = [rc, {k: digest(np.stack([getattr(r, k) for r in res])) for k in ("nvalid", "mean", "cov", "order_ranks",
+                                                                                                  "order_stats", "counts")} if res is not None else None]
+    a = dict(tau=np.full((NCHAINS, NDIM), -7.0), tau_mean=np.full((NCHAINS, NDIM), -7.0), rhat=np.full((NCHAINS, NDIM), -7.0),
+             window=np.full((NCHAINS, NDIM), -7, np.int64), window_mean=np.full((NCHAINS, NDIM), -7, np.int64),
+             nexcluded=np.full((NCHAINS, NDIM), -7, np.int32))
+    ptr = {np.dtype(np.int64): _lib._lp, np.dtype(np.int32): _lib._ip, np.dtype(np.float64): _lib._dp}
+    dout = _lib.GfDiagOut(**{name: a[name].ctypes.data_as(ptr[a[name].dtype]) for name, _ in _lib.GfDiagOut._fields_ if name in a})
+    rc = L.gf_sampler_diagnostics(h, C.byref(_lib.GfDiagSpec(5.0, -1)), C.byref(dout))
+    out["gf_sampler_diagnostics"] = [rc, {k: digest(v) for k, v in a.items()} if rc == _lib.GF_OK else None]
+    r = _NoSummary(s, [Measurement(bestfit_fr=(0.30, 0.36, 0.34)), Measurement(bestfit_fr=(1 / 3,) * 3, smearing=0.05)], seed=7, on_nonunitary="-inf")
+    rc, res = rc_of(lambda: Reweighted._run_summary(r))
+    out["gf_sampler_reweight"] = [rc, {k: digest(v) for k, v in res.items()} if res is not None else None]
+    d_rows = m.alloc(NCHAINS * 2 * 5 * 8 * (3 + NDIM))
+    out["gf_sampler_reweight_rows_device"] = [L.gf_sampler_reweight_rows_device(h, C.byref(r._spec), 5, 1, d_rows.ptr), None]
+    d_rows.free()
+    rc, res = rc_of(lambda: r.marginals(5, **MARGINAL_KW))
+    out["gf_sampler_reweight_marginals"] = [rc, marginal_digest([x for per in res for x in per]) if res is not None else None]
+    rc, res = rc_of(lambda: r.intervals(5))
+    out["gf_sampler_reweight_intervals"] = [rc, interval_digest(res) if res is not None else None]
+    rc, res = rc_of(lambda: r.regions(5, NBINS - 1, [90., 99.]))
+    out["gf_sampler_reweight_regions"] = [rc, region_digest([x for per in res for x in per]) if res is not None else None]
+    assert ns == s.nstored
+    return out
+
+
 # What commit 7c9bd98 (the parent of the change that moved these entry points into gf_postprocess.hip and onto one chain loop)
 # returned for a sampler that has stored nothing: the return code of every entry point, and for regions and marginals the arrays.
 def _empty_marginals(w):
@@ -126,6 +183,22 @@ EMPTY_CHAIN_7C9BD98 = {
     "gf_sampler_element_marginals": [0, _empty_marginals(12)],          # 9 moduli, logLam, the two mass splittings
 }
 
+# What commit 2dc3ca1 (the parent of the change that put these entry points on one row-set layer) returned for the entry points that
+# were added after the table above was written, observed the same way.
+# All of them refuse an empty chain (1 = GF_ERR_INVALID_ARG) before they write anything.
+EMPTY_CHAIN_2DC3CA1 = {
+    "gf_sampler_intervals with_fr=0": [1, None],
+    "gf_sampler_intervals with_fr=1": [1, None],
+    "gf_sampler_element_intervals": [1, None],
+    "gf_sampler_spectrum": [1, None],
+    "gf_sampler_diagnostics": [1, None],
+    "gf_sampler_reweight": [1, None],
+    "gf_sampler_reweight_rows_device": [1, None],
+    "gf_sampler_reweight_marginals": [1, None],
+    "gf_sampler_reweight_intervals": [1, None],
+    "gf_sampler_reweight_regions": [1, None],
+}
+
 
 def test_empty_chain(bsm7):
     ps, f = bsm7
@@ -136,10 +209,14 @@ def test_empty_chain(bsm7):
         for k, v in got.items():
             print(k, v)
         assert got == EMPTY_CHAIN_7C9BD98
+        more = observe_more(s, f, ps)
+        for k, v in more.items():
+            print(k, v)
+        assert more == EMPTY_CHAIN_2DC3CA1
         # with stored=0 after a run the chain is as empty as before it
         p0 = np.stack([uniform_theta(ps, NWALKERS, np.random.default_rng(5 + c), seeds=True) for c in range(NCHAINS)])
         s.run_mcmc(p0, 3, storechain=False)
-        assert s.nstored == 0 and observe(s, f, ps, None) == EMPTY_CHAIN_7C9BD98
+        assert s.nstored == 0 and observe(s, f, ps, None) == EMPTY_CHAIN_7C9BD98 and observe_more(s, f, ps) == EMPTY_CHAIN_2DC3CA1
     finally:
         s.close()
 
