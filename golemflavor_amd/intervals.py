@@ -49,10 +49,6 @@ def run_interval_call(call, what, nchains, width, percentiles):
     return a
 
 
-def _squeeze(res, single):
-    return {k: (v[0] if single and k != "percentiles" else v) for k, v in res.items()}
-
-
 def chain_intervals(rows, *, model, percentiles=(68., 90.)):
     """The intervals of host rows (n, width) -- or (nchains, n, width), all chains in one call: a dict of low, up, status
     (width, npct), center, nbins, nunique (width,) [leading chain axis for stacked rows] and `percentiles`.
@@ -68,7 +64,8 @@ def chain_intervals(rows, *, model, percentiles=(68., 90.)):
     if single:
         def call(spec, out):
             return model._L.gf_column_intervals(model._h, x.ctypes.data_as(_lib._dp), n, W, spec, out)
-        return _squeeze(run_interval_call(call, "gf_column_intervals", 1, W, percentiles), True)
+        res = run_interval_call(call, "gf_column_intervals", 1, W, percentiles)
+        return {k: (v if k == "percentiles" else v[0]) for k, v in res.items()}
     d_rows = model.alloc(x.nbytes)
     try:
         d_rows.upload(x)

@@ -23,6 +23,7 @@ import sys
 
 import numpy as np
 
+from . import rowsets
 from .diagnostics import sokal_window
 
 
@@ -184,7 +185,7 @@ class EnsembleSampler:
         return results
 
 
-class DeviceEnsembleSampler:
+class DeviceEnsembleSampler(rowsets.RowSetSource):
     """The same sampler, resident on the GPU (`gf_sampler_*` in include/golemflavor_hip.h).
 
     Proposal, lnprob and accept/reject of a half-ensemble run in ONE kernel launch and the walkers
@@ -226,11 +227,10 @@ class DeviceEnsembleSampler:
         self.models = models if multi else None               # one posterior per chain (kept alive here)
         h = C.c_void_p()
         if multi:
-            handles = (C.c_void_p * self.nchains)(*[m._h.value if hasattr(m._h, "value") else m._h for m in models])
-            _lib.check(self._L.gf_sampler_create_multi(handles, self.nchains, self.k, int(seed), self.a, C.byref(h)),
-                       "gf_sampler_create_multi")
+            _lib.check(self._L.gf_sampler_create_multi(rowsets.model_handles(models, self.nchains), self.nchains, self.k, int(seed),
+                                                       self.a, C.byref(h)), "gf_sampler_create_multi")
         else:
-            _lib.check(self._L.gf_sampler_create(model._h, self.nchains, self.k, int(seed), self.a, C.byref(h)),
+            _lib.check(self._L.gf_sampler_create(rowsets.handle(model), self.nchains, self.k, int(seed), self.a, C.byref(h)),
                        "gf_sampler_create")
         self._h = h
         self._have_state = False
@@ -243,6 +243,22 @@ class DeviceEnsembleSampler:
                 raise ValueError("stream_ids must hold one id per chain (%d), got %s" % (self.nchains, ids.shape))
             _lib.check(self._L.gf_sampler_set_stream_ids(self._h, ids.ctypes.data_as(C.POINTER(C.c_uint64))),
                        "gf_sampler_set_stream_ids")
+
+    # -- what this source of row sets says about itself (rowsets.RowSetSource) ---------------
+    _prefix, _sets = "gf_sampler_", "chains"
+    _nsets = property(lambda self: self.nchains)
+    _ncols = property(lambda self: self.dim)
+
+    def _desc0(self):
+        return self.model.desc
+
+    def _lead(self, models=None, space="theta"):
+        """element space propagates nothing: its entry points take no models"""
+        return (self._h,) if space == "elements" else (self._h, rowsets.model_handles(models, self.nchains))
+
+    def _shape(self, per_chain):
+        """a list over the chains, or an array with a leading chain axis: a single chain has neither"""
+        return per_chain[0] if self.nchains == 1 else per_chain
 
     # -- control ------------------------------------------------------------------------
     def _set_state(self, p0):
@@ -442,8 +458,7 @@ class DeviceEnsembleSampler:
     @property
     def chain(self):
         """(nwalkers, nsteps, ndim) like emcee-2 [(nchains, nwalkers, nsteps, ndim) when nchains > 1]."""
-        c = np.ascontiguousarray(self._fetch(chain=True)[0].transpose(0, 2, 1, 3))
-        return c[0] if self.nchains == 1 else c
+        return self._shape(np.ascontiguousarray(self._fetch(chain=True)[0].transpose(0, 2, 1, 3)))
 
     @property
     def flatchain(self):
@@ -452,13 +467,11 @@ class DeviceEnsembleSampler:
 
     @property
     def lnprobability(self):
-        lp = np.ascontiguousarray(self._fetch(lnprob=True)[1].transpose(0, 2, 1))
-        return lp[0] if self.nchains == 1 else lp
+        return self._shape(np.ascontiguousarray(self._fetch(lnprob=True)[1].transpose(0, 2, 1)))
 
     @property
     def acceptance_fraction(self):
-        nacc = self._fetch(naccepted=True)[2].astype(np.float64) / max(self.iterations, 1)
-        return nacc[0] if self.nchains == 1 else nacc
+        return self._shape(self._fetch(naccepted=True)[2].astype(np.float64) / max(self.iterations, 1))
 
     def postprocess(self, want_fr=True, want_status=False, nbins=None, models=None, step_major=False):
         """Chain post-processing on the device: the measured composition of every stored sample
@@ -475,25 +488,19 @@ class DeviceEnsembleSampler:
         fr = empty_for_download((self.nchains, ns, self.k, 3)) if want_fr else None
         st = empty_for_download((self.nchains, ns, self.k), dtype=np.int32) if want_status else None
         hist = np.zeros((self.nchains, nbins, nbins, nbins), dtype=np.uint64) if nbins else None
-        handles = None
-        if models is not None:
-            ms = [getattr(m, "model", m) for m in models]
-            if len(ms) != self.nchains:
-                raise ValueError("%d post-processing models for %d chains" % (len(ms), self.nchains))
-            handles = (C.c_void_p * self.nchains)(*[m._h.value if hasattr(m._h, "value") else m._h for m in ms])
         self._lib.check(self._L.gf_sampler_postprocess_with(
-            self._h, handles, fr.ctypes.data_as(self._lib._dp) if want_fr else None,
+            *self._lead(models), fr.ctypes.data_as(self._lib._dp) if want_fr else None,
             st.ctypes.data_as(self._lib._ip) if want_status else None, int(nbins or 0),
             hist.ctypes.data_as(C.POINTER(C.c_uint64)) if nbins else None), "gf_sampler_postprocess_with")
         out = {}
         if want_fr:
             f = fr if step_major else np.ascontiguousarray(fr.transpose(0, 2, 1, 3))
-            out["fr"] = f[0] if self.nchains == 1 else f
+            out["fr"] = self._shape(f)
         if want_status:
             t = st if step_major else np.ascontiguousarray(st.transpose(0, 2, 1))
-            out["status"] = t[0] if self.nchains == 1 else t
+            out["status"] = self._shape(t)
         if nbins:
-            out["hist"] = hist[0] if self.nchains == 1 else hist
+            out["hist"] = self._shape(hist)
         return out
 
     def regions(self, nbins, coverage, hist_smooth=0.05, oversample=1., models=None, truncate=4.0, cap=None):
@@ -503,21 +510,7 @@ class DeviceEnsembleSampler:
         histograms stay on the device, only the regions come back.  coverage: a number or up to 8; returns a
         `contour.RegionResult` (a list of them for several coverages), with a leading list level over the chains when
         nchains > 1.  models as in `postprocess`; a sample the reference would have raised on is left out."""
-        from . import contour
-        C = self._C
-        handles = None
-        if models is not None:
-            ms = [getattr(m, "model", m) for m in models]
-            if len(ms) != self.nchains:
-                raise ValueError("%d post-processing models for %d chains" % (len(ms), self.nchains))
-            handles = (C.c_void_p * self.nchains)(*[m._h.value if hasattr(m._h, "value") else m._h for m in ms])
-        nb = int(nbins * oversample) + 1
-        scalar, _ = contour._coverages(coverage)
-
-        def call(*args):
-            return self._L.gf_sampler_regions(self._h, handles, nb, *args)
-        res = contour.run_region_call(call, "gf_sampler_regions", self.nchains, nb, coverage, hist_smooth, truncate, cap)
-        return contour.shape_results(res, scalar, self.nchains == 1)
+        return self._regions(self._lead(models), nbins, coverage, hist_smooth, oversample, truncate, cap)
 
     def marginals(self, ranges=None, with_fr=False, models=None, names=None, space="theta", llh_paramset=None, round32=True, **kw):
         """The posterior marginals of the stored samples (`marginals.chain_marginals`'s reduction and keyword arguments:
@@ -533,49 +526,7 @@ class DeviceEnsembleSampler:
         ranges default to the plan's; with_fr does not combine with it."""
         if space not in ("theta", "elements"):
             raise ValueError("space must be 'theta' or 'elements'")
-        if space == "elements":
-            return self._element_marginals(ranges, with_fr, models, names, llh_paramset, round32, kw)
-        from . import marginals as mg
-        C = self._C
-        handles = None
-        if models is not None:
-            ms = [getattr(m, "model", m) for m in models]
-            if len(ms) != self.nchains:
-                raise ValueError("%d post-processing models for %d chains" % (len(ms), self.nchains))
-            handles = (C.c_void_p * self.nchains)(*[m._h.value if hasattr(m._h, "value") else m._h for m in ms])
-        width = (3 if with_fr else 0) + self.dim
-        if ranges is None:
-            d = self.model.desc
-            ranges = ([(0., 1.)] * 3 if with_fr else []) + [(d.lo[c], d.hi[c]) for c in range(self.dim)]
-        if names is None:
-            names = (["fr_e", "fr_mu", "fr_tau"] if with_fr else []) + ["theta%d" % c for c in range(self.dim)]
-        cap_2d = kw.pop("cap_2d", None)
-        prep = mg.prepare(width, ranges, names, **kw)
-
-        def call(spec, out):
-            return self._L.gf_sampler_marginals(self._h, handles, int(bool(with_fr)), spec, out)
-        res = mg.run_marginal_call(call, "gf_sampler_marginals", self.nchains, prep, cap_2d)
-        return res[0] if self.nchains == 1 else res
-
-    def _element_marginals(self, ranges, with_fr, models, names, llh_paramset, round32, kw):
-        from . import elements as el
-        from . import marginals as mg
-        if with_fr:
-            raise ValueError("space='elements' does not combine with with_fr: the element-space row carries the source composition")
-        if models is not None:
-            raise ValueError("space='elements' propagates nothing: it takes no post-processing models")
-        if llh_paramset is None:
-            raise ValueError("space='elements' needs llh_paramset, the set the chain was sampled over")
-        if len(llh_paramset) != self.dim:
-            raise ValueError("llh_paramset has %d parameters, the chain %d columns" % (len(llh_paramset), self.dim))
-        plan, pnames, pranges = el.element_plan(llh_paramset, round32)
-        cap_2d = kw.pop("cap_2d", None)
-        prep = mg.prepare(len(pnames), pranges if ranges is None else ranges, pnames if names is None else names, **kw)
-
-        def call(spec, out):
-            return self._L.gf_sampler_element_marginals(self._h, self._C.byref(plan), spec, out)
-        res = mg.run_marginal_call(call, "gf_sampler_element_marginals", self.nchains, prep, cap_2d)
-        return res[0] if self.nchains == 1 else res
+        return self._marginals(self._lead(models, space), ranges, names, with_fr, kw, space == "elements" and (llh_paramset, round32, models))
 
     @property
     def nstored(self):
@@ -588,37 +539,23 @@ class DeviceEnsembleSampler:
 
     def postprocess_to_device(self, d_fr, d_status=None, models=None):
         """`postprocess` with device destinations: d_fr [nchains][nstored][nwalkers][3], d_status optional."""
-        C = self._C
-        handles = None
-        if models is not None:
-            ms = [getattr(m, "model", m) for m in models]
-            handles = (C.c_void_p * self.nchains)(*[m._h.value if hasattr(m._h, "value") else m._h for m in ms])
-        self._lib.check(self._L.gf_sampler_postprocess_device(self._h, handles, d_fr, d_status), "gf_sampler_postprocess_device")
+        self._lib.check(self._L.gf_sampler_postprocess_device(*self._lead(models), d_fr, d_status), "gf_sampler_postprocess_device")
 
     def postprocess_rows_to_device(self, d_rows, models=None):
         """The rows a scan saves -- composition (NaN where the reference would have raised) then the sample -- assembled
         on the device: d_rows [nchains][nstored][nwalkers][3 + ndim]."""
-        C = self._C
-        handles = None
-        if models is not None:
-            ms = [getattr(m, "model", m) for m in models]
-            handles = (C.c_void_p * self.nchains)(*[m._h.value if hasattr(m._h, "value") else m._h for m in ms])
-        self._lib.check(self._L.gf_sampler_postprocess_rows_device(self._h, handles, d_rows), "gf_sampler_postprocess_rows_device")
+        self._lib.check(self._L.gf_sampler_postprocess_rows_device(*self._lead(models), d_rows), "gf_sampler_postprocess_rows_device")
 
     def postprocess_rows(self, models=None, out=None):
         """The same rows on the host, (nchains, nstored * nwalkers, 3 + ndim): the finished chains cross PCIe while the later
         ones are still being post-processed."""
-        C = self._C
-        handles = None
-        if models is not None:
-            ms = [getattr(m, "model", m) for m in models]
-            handles = (C.c_void_p * self.nchains)(*[m._h.value if hasattr(m._h, "value") else m._h for m in ms])
+        lead = self._lead(models)
         ns = int(self._L.gf_sampler_nstored(self._h))
         if out is None:
             out = np.empty((self.nchains, ns * self.k, 3 + self.dim))
         if out.shape != (self.nchains, ns * self.k, 3 + self.dim) or out.dtype != np.float64 or not out.flags.c_contiguous:
             raise ValueError("out must be a C-contiguous float64 array of shape %r" % ((self.nchains, ns * self.k, 3 + self.dim),))
-        self._lib.check(self._L.gf_sampler_postprocess_rows(self._h, handles, out.ctypes.data_as(self._lib._dp)),
+        self._lib.check(self._L.gf_sampler_postprocess_rows(*lead, out.ctypes.data_as(self._lib._dp)),
                         "gf_sampler_postprocess_rows")
         return out
 
@@ -626,9 +563,7 @@ class DeviceEnsembleSampler:
         """The stored samples in the order the device holds them, (nsteps*nwalkers, ndim) [leading chain axis
         when nchains > 1]: `flatchain` without the transposition to emcee's walker-major order -- for
         consumers that treat the chain as a bag of samples (histograms, post-processing)."""
-        c = self._fetch(chain=True)[0]
-        c = c.reshape(self.nchains, -1, self.dim)
-        return c[0] if self.nchains == 1 else c
+        return self._shape(self._fetch(chain=True)[0].reshape(self.nchains, -1, self.dim))
 
     @property
     def acor(self):
@@ -640,7 +575,7 @@ class DeviceEnsembleSampler:
         ns = int(self._L.gf_sampler_nstored(self._h))
         out = np.empty((self.nchains, ns, self.dim))
         self._lib.check(self._L.gf_sampler_walker_mean(self._h, out.ctypes.data_as(self._lib._dp)), "gf_sampler_walker_mean")
-        return out[0] if self.nchains == 1 else out
+        return self._shape(out)
 
     def get_autocorr_time(self, c=5, tol=50):
         m = self.walker_mean()                                 # emcee-2: acor of the ensemble-averaged chain
@@ -665,7 +600,7 @@ class DeviceEnsembleSampler:
         acc = np.atleast_2d(self.acceptance_fraction)
         for ch, r in enumerate(res):
             r.acceptance_fraction = acc[ch]
-        return res[0] if self.nchains == 1 else res
+        return self._shape(res)
 
     def intervals(self, percentiles=(68., 90.), with_fr=False, models=None, space="theta", llh_paramset=None, round32=True):
         """The reference's shortest interval around the mode (`misc.interval`) of every column of the stored samples, and each
@@ -673,35 +608,11 @@ class DeviceEnsembleSampler:
         dict (low, up, status (width, npct), center, nbins, nunique (width,), percentiles), with a leading chain axis when
         nchains > 1.  with_fr, models: the rows a scan saves, as in `marginals`; space="elements": the chain in element space
         (`elements.element_plan(llh_paramset, round32)`), which takes neither.  Nothing stored: ValueError."""
-        from . import intervals as iv
         if space not in ("theta", "elements"):
             raise ValueError("space must be 'theta' or 'elements'")
         if self.nstored == 0:
             raise ValueError("no stored samples: run_mcmc(..., storechain=True) first")
-        C = self._C
-        if space == "elements":
-            from . import elements as el
-            if with_fr or models is not None:
-                raise ValueError("space='elements' takes neither with_fr nor post-processing models")
-            if llh_paramset is None or len(llh_paramset) != self.dim:
-                raise ValueError("space='elements' needs llh_paramset, the set of the chain's %d columns" % self.dim)
-            plan, pnames, _ = el.element_plan(llh_paramset, round32)
-
-            def call(spec, out):
-                return self._L.gf_sampler_element_intervals(self._h, C.byref(plan), spec, out)
-            res = iv.run_interval_call(call, "gf_sampler_element_intervals", self.nchains, len(pnames), percentiles)
-            return iv._squeeze(res, self.nchains == 1)
-        handles = None
-        if models is not None:
-            ms = [getattr(m, "model", m) for m in models]
-            if len(ms) != self.nchains:
-                raise ValueError("%d post-processing models for %d chains" % (len(ms), self.nchains))
-            handles = (C.c_void_p * self.nchains)(*[m._h.value if hasattr(m._h, "value") else m._h for m in ms])
-
-        def call(spec, out):
-            return self._L.gf_sampler_intervals(self._h, handles, int(bool(with_fr)), spec, out)
-        res = iv.run_interval_call(call, "gf_sampler_intervals", self.nchains, (3 if with_fr else 0) + self.dim, percentiles)
-        return iv._squeeze(res, self.nchains == 1)
+        return self._intervals(self._lead(models, space), percentiles, with_fr, space == "elements" and (llh_paramset, round32, models))
 
     def spectrum(self, percentiles=(5, 16, 50, 84, 95), bins=50, models=None):
         """The composition at every energy bin of the stored samples, reduced on the device (`spectrum.SpectrumResult`: nvalid,
@@ -709,27 +620,12 @@ class DeviceEnsembleSampler:
         nchains > 1.  Chain ch is evaluated with models[ch] (None: the sampling models), as in `marginals`; every model must be a
         BSM model with the same binning.  A sample the reference would have raised on has no composition at any energy.  Nothing
         stored, or a model without energy bins: ValueError."""
-        from . import spectrum as sp
         if self.nstored == 0:
             raise ValueError("no stored samples: run_mcmc(..., storechain=True) first")
-        C = self._C
-        handles = None
-        if models is not None:
-            ms = [getattr(m, "model", m) for m in models]
-            if len(ms) != self.nchains:
-                raise ValueError("%d post-processing models for %d chains" % (len(ms), self.nchains))
-            handles = (C.c_void_p * self.nchains)(*[m._h.value if hasattr(m._h, "value") else m._h for m in ms])
-        else:
-            ms = list(self.models) if self.models is not None else [self.model]
-        edges = [sp.model_edges(m) for m in ms]
-        if any(not np.array_equal(e, edges[0]) for e in edges[1:]):
-            raise ValueError("the chains' models differ in their energy binning")
-        prep = sp.prepare(edges[0], percentiles, bins)
-
-        def call(spec, out):
-            return self._L.gf_sampler_spectrum(self._h, handles, spec, out)
-        res = sp.run_spectrum_call(call, "gf_sampler_spectrum", self.nchains, prep)
-        return res[0] if self.nchains == 1 else res
+        lead = self._lead(models)
+        if models is None:
+            models = self.models if self.models is not None else [self.model]
+        return self._spectrum(lead, models, percentiles, bins)
 
     def reweight(self, targets, seed=None, on_nonunitary="raise"):
         """The stored chains under other targets, without sampling again (`reweight.Reweighted`: .summary(), .lnw(chain), .rows(N,

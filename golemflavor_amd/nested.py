@@ -25,6 +25,7 @@ import numpy as np
 from . import _lib
 from . import configs as Cf
 from . import fr as fr_utils
+from . import rowsets
 from .descriptor import compile_model
 from .enums import ParamTag
 from .model import Model
@@ -36,11 +37,6 @@ BAYES_K = 1.0                 # golemflavor/plot.py: Bayes factor threshold 10^K
 DEFAULT_NLIVE = 3000          # mn.py:51-53 --mn-live-points
 DEFAULT_TOL = 0.01            # mn.py:55-57 --mn-tolerance
 DEFAULT_WALKS = 25
-
-
-def _handle(m):
-    model = getattr(m, "model", m)          # an LnProb or a Model
-    return model._h
 
 
 class _CubeRuns:
@@ -62,14 +58,14 @@ class _CubeRuns:
         self.nruns = len(self.models)
         self.cols = np.ascontiguousarray(cols, dtype=np.int32)
         self.nscan = len(self.cols)
-        ndim = self._L.gf_model_ndim(_handle(self.models[0]))
+        ndim = self._L.gf_model_ndim(rowsets.handle(self.models[0]))
         b = np.asarray(bases, dtype=np.float64)
         if b.ndim == 1:
             b = np.tile(b, (self.nruns, 1))
         self.bases = np.ascontiguousarray(b.reshape(self.nruns, ndim))
         self.on_nonunitary = on_nonunitary
         self.labels = list(labels) if labels is not None else list(range(self.nruns))
-        return (C.c_void_p * self.nruns)(*[_handle(m) for m in self.models])
+        return rowsets.model_handles(self.models, self.nruns)
 
     def _set_run_ids(self, run_ids):
         if run_ids is not None:
@@ -102,7 +98,7 @@ class _CubeRuns:
             pass
 
 
-class NestedSampler(_CubeRuns):
+class NestedSampler(_CubeRuns, rowsets.RowSetSource):
     """`nruns` independent nested-sampling runs (_CubeRuns: models, cols, bases, run_ids, labels)."""
     _abi, _what = "nested", "nested run"
 
@@ -160,12 +156,19 @@ class NestedSampler(_CubeRuns):
         return dict(lnl=lnl, lnw=lnw, cube=cube, theta=theta, nlive_seq=seq, ndead=ndead)
 
     # ---- the posterior of every run, computed on the device from the points dead() would read back -------------
-    def _desc(self, run=0):
-        return getattr(self.models[run], "model", self.models[run]).desc
-
     @property
     def ndim(self):
         return self.bases.shape[1]
+
+    # rowsets.RowSetSource: one row set per run, the defaults of run 0's model, the run axis never dropped
+    _prefix, _sets, _ncols = "gf_nested_", "runs", ndim
+    _nsets = property(lambda self: self.nruns)
+
+    def _desc0(self):
+        return getattr(self.models[0], "model", self.models[0]).desc
+
+    def _shape(self, per_run):
+        return per_run
 
     def posterior(self):
         """Per run: dict(npoints, ess (Kish), lnz_check (= max lnw + log sum exp, a diagnostic), mean (nruns, ndim), cov (nruns,
@@ -193,70 +196,28 @@ class NestedSampler(_CubeRuns):
         keyword arguments: bins_1d, bins_2d, coverage, percentiles, ranks, hist_smooth, truncate; cap_2d).  space="angles": the
         theta columns (with_fr: the composition in front), ranges default to the box of the run-0 model and (0, 1);
         space="elements": `elements.element_plan(llh_paramset, round32)`'s row, names and ranges the plan's."""
-        from . import marginals as mg
         if space not in ("angles", "elements"):
             raise ValueError("space must be 'angles' or 'elements'")
-        cap_2d = prepare_kwargs.pop("cap_2d", None)
-        if space == "elements":
-            from . import elements as el
-            if with_fr:
-                raise ValueError("space='elements' does not combine with with_fr: the element-space row carries the source composition")
-            if llh_paramset is None or len(llh_paramset) != self.ndim:
-                raise ValueError("space='elements' needs llh_paramset, the set of the runs' %d columns" % self.ndim)
-            plan, pnames, pranges = el.element_plan(llh_paramset, round32)
-            prep = mg.prepare(len(pnames), pranges if ranges is None else ranges, pnames if names is None else names, **prepare_kwargs)
-
-            def call(spec, out):
-                return self._L.gf_nested_element_marginals(self._h, int(nrows), C.byref(plan), spec, out)
-            return mg.run_marginal_call(call, "gf_nested_element_marginals", self.nruns, prep, cap_2d)
-        d = self._desc()
-        if ranges is None:
-            ranges = ([(0., 1.)] * 3 if with_fr else []) + [(d.lo[c], d.hi[c]) for c in range(self.ndim)]
-        if names is None:
-            names = (["fr_e", "fr_mu", "fr_tau"] if with_fr else []) + ["theta%d" % c for c in range(self.ndim)]
-        prep = mg.prepare((3 if with_fr else 0) + self.ndim, ranges, names, **prepare_kwargs)
-
-        def call(spec, out):
-            return self._L.gf_nested_marginals(self._h, int(nrows), int(bool(with_fr)), spec, out)
-        return mg.run_marginal_call(call, "gf_nested_marginals", self.nruns, prep, cap_2d)
+        return self._marginals((self._h, int(nrows)), ranges, names, with_fr, prepare_kwargs, space == "elements" and (llh_paramset, round32, None))
 
     def intervals(self, nrows, percentiles=(68., 90.), with_fr=False):
         """The reference's shortest interval around the mode (`misc.interval`) of every column of every run's `nrows` equal-weight
         rows, which stay on the device: `intervals.chain_intervals`'s dict with a leading run axis.  A run without a posterior has
         NaN rows: status 1."""
-        from . import intervals as iv
-
-        def call(spec, out):
-            return self._L.gf_nested_intervals(self._h, int(nrows), int(bool(with_fr)), spec, out)
-        return iv.run_interval_call(call, "gf_nested_intervals", self.nruns, (3 if with_fr else 0) + self.ndim, percentiles)
+        return self._intervals((self._h, int(nrows)), percentiles, with_fr)
 
     def spectrum(self, nrows, percentiles=(5, 16, 50, 84, 95), bins=50):
         """The composition at every energy bin of every run's `nrows` equal-weight rows, reduced on the device: one
         `spectrum.SpectrumResult` per run.  A run without a posterior has nvalid 0 and NaN moments.  Models without energy bins:
         ValueError."""
-        from . import spectrum as sp
-        edges = [sp.model_edges(m) for m in self.models]
-        if any(not np.array_equal(e, edges[0]) for e in edges[1:]):
-            raise ValueError("the runs' models differ in their energy binning")
         if int(nrows) < 1:
             raise ValueError("nrows must be at least 1")
-        prep = sp.prepare(edges[0], percentiles, bins)
-
-        def call(spec, out):
-            return self._L.gf_nested_spectrum(self._h, int(nrows), spec, out)
-        return sp.run_spectrum_call(call, "gf_nested_spectrum", self.nruns, prep)
+        return self._spectrum((self._h, int(nrows)), self.models, percentiles, bins)
 
     def regions(self, nrows, nbins, coverage, hist_smooth=0.05, oversample=1., truncate=4.0, cap=None):
         """The flavor-triangle credible regions (`DeviceEnsembleSampler.regions`'s reduction) of every run's `nrows` equal-weight
         rows propagated with the run's model: [run] of `contour.RegionResult` (of lists of them for several coverages)."""
-        from . import contour
-        nb = int(nbins * oversample) + 1
-        scalar, _ = contour._coverages(coverage)
-
-        def call(*args):
-            return self._L.gf_nested_regions(self._h, int(nrows), nb, *args)
-        res = contour.run_region_call(call, "gf_nested_regions", self.nruns, nb, coverage, hist_smooth, truncate, cap)
-        return contour.shape_results(res, scalar, False)
+        return self._regions((self._h, int(nrows)), nbins, coverage, hist_smooth, oversample, truncate, cap)
 
 
 def _logaddexp(x, y):

@@ -11,7 +11,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _lib, rowsets
 from ._lib import GF_REWEIGHT_MAX_TARGETS, GF_ST_NON_UNITARY, GfReweightOut, GfReweightSpec
 
 
@@ -111,7 +111,7 @@ def reweight_host(rows, lnprob, lnprob_target, status=None, nrows=None, u=0.5):
     return out
 
 
-class Reweighted:
+class Reweighted(rowsets.RowSetSource):
     """What `DeviceEnsembleSampler.reweight` returns: the chains of `sampler` under `targets`.  Everything is computed on the device
     while the sampler holds the chain; the object keeps the sampler and the targets alive.  Layouts are those of the sampler's chain
     methods with a target axis after the chain axis (the chain axis is dropped when nchains == 1).
@@ -135,7 +135,7 @@ class Reweighted:
             for m in ms:
                 if m.ndim != self.ndim:
                     raise AssertionError("a target has %d parameters, the chain %d columns" % (m.ndim, self.ndim))
-            self._keep = (C.c_void_p * len(ms))(*[m._h.value if hasattr(m._h, "value") else m._h for m in ms])
+            self._keep = rowsets.model_handles(ms, len(ms))
             self._spec.models = self._keep
         else:
             own = sampler.models if sampler.models is not None else [sampler.model] * self.nchains
@@ -153,8 +153,26 @@ class Reweighted:
         if on_nonunitary == "raise" and self._summary["nonunitary"].sum():
             raise AssertionError("Matrix is not unitary! (%d rows under the targets)" % int(self._summary["nonunitary"].sum()))
 
+    # rowsets.RowSetSource: one row set per (chain, target), chain-major; the defaults of the sampler's model
+    _prefix = "gf_sampler_reweight_"
+    _nsets = property(lambda self: self.nchains * self.ntargets)
+    _ncols = property(lambda self: self.ndim)
+
+    def _desc0(self):
+        return self.sampler.model.desc
+
+    def _lead(self, N):
+        return (self.sampler._h, C.byref(self._spec), int(N))
+
     def _sq(self, a):
         return a[0] if self.nchains == 1 else a
+
+    def _shape(self, per_set):
+        """[chain][target] of a per-set list, (nchains, ntargets) leading in an array; the chain level dropped for a single chain"""
+        T = self.ntargets
+        if isinstance(per_set, np.ndarray):
+            return self._sq(per_set.reshape((self.nchains, T) + per_set.shape[1:]))
+        return self._sq([per_set[c * T:(c + 1) * T] for c in range(self.nchains)])
 
     def _run_summary(self):
         nc, T, d = self.nchains, self.ntargets, self.ndim
@@ -192,45 +210,16 @@ class Reweighted:
                                                     rows.ctypes.data_as(_lib._dp), index.ctypes.data_as(_lib._lp)), "gf_sampler_reweight_rows")
         return (self._sq(rows), self._sq(index)) if return_index else self._sq(rows)
 
-    def _nest(self, flat):
-        res = [flat[c * self.ntargets:(c + 1) * self.ntargets] for c in range(self.nchains)]
-        return res[0] if self.nchains == 1 else res
-
     def marginals(self, N, ranges=None, with_fr=False, names=None, **kw):
         """`DeviceEnsembleSampler.marginals`' reduction of the N equal-weight rows of every (chain, target), which stay on the device:
         [chain][target] `marginals.MarginalResult`."""
-        from . import marginals as mg
-        width = (3 if with_fr else 0) + self.ndim
-        if ranges is None:
-            d = self.sampler.model.desc
-            ranges = ([(0., 1.)] * 3 if with_fr else []) + [(d.lo[c], d.hi[c]) for c in range(self.ndim)]
-        if names is None:
-            names = (["fr_e", "fr_mu", "fr_tau"] if with_fr else []) + ["theta%d" % c for c in range(self.ndim)]
-        cap_2d = kw.pop("cap_2d", None)
-        prep = mg.prepare(width, ranges, names, **kw)
-
-        def call(spec, out):
-            return self._L.gf_sampler_reweight_marginals(self.sampler._h, C.byref(self._spec), int(N), int(bool(with_fr)), spec, out)
-        return self._nest(mg.run_marginal_call(call, "gf_sampler_reweight_marginals", self.nchains * self.ntargets, prep, cap_2d))
+        return self._marginals(self._lead(N), ranges, names, with_fr, kw)
 
     def intervals(self, N, percentiles=(68., 90.), with_fr=False):
         """`DeviceEnsembleSampler.intervals`' dict for the N equal-weight rows, with (nchains, ntargets) leading."""
-        from . import intervals as iv
-        width = (3 if with_fr else 0) + self.ndim
-
-        def call(spec, out):
-            return self._L.gf_sampler_reweight_intervals(self.sampler._h, C.byref(self._spec), int(N), int(bool(with_fr)), spec, out)
-        res = iv.run_interval_call(call, "gf_sampler_reweight_intervals", self.nchains * self.ntargets, width, percentiles)
-        return {k: (v if k == "percentiles" else self._sq(v.reshape((self.nchains, self.ntargets) + v.shape[1:]))) for k, v in res.items()}
+        return self._intervals(self._lead(N), percentiles, with_fr)
 
     def regions(self, N, nbins, coverage, hist_smooth=0.05, oversample=1., truncate=4.0, cap=None):
         """`DeviceEnsembleSampler.regions`' reduction of the compositions of the N equal-weight rows: [chain][target]
         `contour.RegionResult` (lists of them for several coverages)."""
-        from . import contour
-        nb = int(nbins * oversample) + 1
-        scalar, _ = contour._coverages(coverage)
-
-        def call(*args):
-            return self._L.gf_sampler_reweight_regions(self.sampler._h, C.byref(self._spec), int(N), nb, *args)
-        res = contour.run_region_call(call, "gf_sampler_reweight_regions", self.nchains * self.ntargets, nb, coverage, hist_smooth, truncate, cap)
-        return self._nest(contour.shape_results(res, scalar, False))
+        return self._regions(self._lead(N), nbins, coverage, hist_smooth, oversample, truncate, cap)

@@ -257,39 +257,75 @@ GATHER_STATS = {}     # the last DeviceGather.run: bytes and seconds by phase
 LAST_NONUNITARY = {}  # the last stacked run_points call: proposals the reference would have raised on, and how they were settled
 
 
-REGION_STATS = {}     # the last run_points call with regions: what --regions computed on this rank (reported by main)
+def per_point(res, order):
+    """What a sampler's reduction returned for the chains of grid points `order`, as one entry per point.  The only place that
+    knows that a sampler of a single chain returns its result unwrapped: a list over the chains (of results, or of per-target lists)
+    stays one, `intervals`' dict of arrays with a leading chain axis becomes one dict per chain (`percentiles` is not split); None
+    (nothing was reduced) is None for every point."""
+    if len(order) == 1 or res is None:
+        return [res] * len(order)
+    if isinstance(res, dict):
+        return [{f: (v if f == "percentiles" else v[k]) for f, v in res.items()} for k in range(len(order))]
+    return res
 
 
-class RegionWriter:
-    """--regions: the credible regions of every grid point's compositions (golemflavor/plot.py:365-392, `DeviceEnsembleSampler.regions`),
-    computed while the point's sampler still holds its chain and saved as contour_region_<point file name>.npz beside the chain
-    file.  The regions of one point are nested -- each is a prefix of the same ordering of the cells -- so a file holds the cells
-    and densities of the largest region once: `cells` (n, 3), `density` (n,), and per coverage `coverage`, `thres` (region q is
-    cells[:thres[q]]), `level_in`, `level_out`, `mass`, `saturated`; `nbins` is the number of bins per axis."""
+class PointWriter:
+    """What the writers below share.  Each reduces every grid point's chain while the point's sampler still holds it and saves one
+    <stem>_<point file name>.npz per point beside the chain file; `take` times the work and counts the points, `stats` is what the
+    scan's JSON line reports under `key`.  A writer says which sampler method it calls, what it saves and what it counts (`write`,
+    `_stats`)."""
+    key = None
 
-    def __init__(self, datadir, name_of, coverage, nbins=25, oversample=5., smooth=0.05):
+    def __init__(self, datadir, name_of):
         self.datadir, self.name_of = datadir, name_of
-        self.coverage = [float(c) for c in coverage]
-        self.nbins, self.oversample, self.smooth = int(nbins), float(oversample), float(smooth)
-        self.seconds, self.thres = 0.0, []
+        self.seconds, self.points = 0.0, 0
 
     def take(self, sampler, models, order):
         """sampler: the chains of grid points `order`; models: their post-processing models (None: the sampled posteriors)."""
         t0 = time.perf_counter()
+        self.write(sampler, models, order)
+        self.points += len(order)
+        self.seconds += time.perf_counter() - t0
+
+    def each(self, res, order):
+        """(grid index, its part of `res`) for every point, the directory made"""
+        os.makedirs(self.datadir, exist_ok=True)
+        return zip(order, per_point(res, order))
+
+    def file(self, stem, g, suffix=""):
+        return os.path.join(self.datadir, "%s_%s%s.npz" % (stem, self.name_of(g), suffix))
+
+    def stats(self):
+        return self._stats(points=self.points, seconds=round(self.seconds, 4)) if self.points else {}
+
+
+class RegionWriter(PointWriter):
+    """--regions: the credible regions of every grid point's compositions (golemflavor/plot.py:365-392, `DeviceEnsembleSampler.regions`),
+    saved as contour_region_<point file name>.npz.  The regions of one point are nested -- each is a prefix of the same ordering of
+    the cells -- so a file holds the cells and densities of the largest region once: `cells` (n, 3), `density` (n,), and per coverage
+    `coverage`, `thres` (region q is cells[:thres[q]]), `level_in`, `level_out`, `mass`, `saturated`; `nbins` is the number of bins
+    per axis."""
+    key = "regions"
+
+    def __init__(self, datadir, name_of, coverage, nbins=25, oversample=5., smooth=0.05):
+        super().__init__(datadir, name_of)
+        self.coverage = [float(c) for c in coverage]
+        self.nbins, self.oversample, self.smooth = int(nbins), float(oversample), float(smooth)
+        self.thres = []
+
+    def write(self, sampler, models, order):
         res = sampler.regions(self.nbins, self.coverage, hist_smooth=self.smooth, oversample=self.oversample, models=models)
-        for g, row in zip(order, [res] if len(order) == 1 else res):
+        for g, row in self.each(res, order):
             big = max(row, key=lambda r: len(r.flat_cells))
-            os.makedirs(self.datadir, exist_ok=True)
-            np.savez(os.path.join(self.datadir, "contour_region_%s.npz" % self.name_of(g)), cells=big.cells, density=big.density,
+            np.savez(self.file("contour_region", g), cells=big.cells, density=big.density,
                      coverage=np.array([r.coverage for r in row]), thres=np.array([r.thres for r in row], dtype=np.int64),
                      level_in=np.array([r.level_in for r in row]), level_out=np.array([r.level_out for r in row]),
                      mass=np.array([r.mass for r in row]), saturated=np.array([r.saturated for r in row]), nbins=np.int64(big.nbins))
             self.thres.append([r.thres for r in row])
-        self.seconds += time.perf_counter() - t0
-        REGION_STATS.clear()
-        REGION_STATS.update({"coverage": self.coverage, "bins_per_axis": int(self.nbins * self.oversample) + 1, "hist_smooth": self.smooth,
-                             "points": len(self.thres), "seconds": round(self.seconds, 4),
-                             "thres_min": np.min(self.thres, axis=0).tolist(), "thres_max": np.max(self.thres, axis=0).tolist()})
+
+    def _stats(self, **timing):
+        return {"coverage": self.coverage, "bins_per_axis": int(self.nbins * self.oversample) + 1, "hist_smooth": self.smooth, **timing,
+                "thres_min": np.min(self.thres, axis=0).tolist(), "thres_max": np.max(self.thres, axis=0).tolist()}
 
 
 def _point_paramset(a, pts):
@@ -299,137 +335,108 @@ def _point_paramset(a, pts):
     return lambda g: _SensPoint.descriptor(pts[g])[0]
 
 
-MARGINAL_STATS = {}   # the last run_points call with marginals: what --marginals computed on this rank (reported by main)
-
-
-class MarginalWriter:
+class MarginalWriter(PointWriter):
     """--marginals: the posterior marginals of every grid point's saved rows (`DeviceEnsembleSampler.marginals`: 1-D and 2-D
     histograms over the sampled model's box, (0, 1) for the composition columns, their credible regions, percentiles, mean and
-    covariance), computed while the point's sampler still holds its chain and saved as marginals_<point file name>.npz beside the
-    chain file; the arrays are `marginals.MarginalResult.as_arrays()`.  elements (--elements): a function grid index -> the
-    paramset the point's chain is sampled over; the marginals of the chain in element space (`elements.element_plan` of the
-    point's own paramset, ranges included) are then saved as marginals_elements_<point file name>.npz as well."""
+    covariance), saved as marginals_<point file name>.npz; the arrays are `marginals.MarginalResult.as_arrays()`.  elements
+    (--elements): a function grid index -> the paramset the point's chain is sampled over; the marginals of the chain in element
+    space (`elements.element_plan` of the point's own paramset, ranges included) are then saved as
+    marginals_elements_<point file name>.npz as well."""
+    key = "marginals"
 
     def __init__(self, datadir, name_of, bins_1d=100, bins_2d=50, coverage=(90., 99.), percentiles=(5., 50., 95.), elements=None):
-        self.datadir, self.name_of, self.elements = datadir, name_of, elements
+        super().__init__(datadir, name_of)
+        self.elements = elements
         self.kw = dict(bins_1d=int(bins_1d), bins_2d=int(bins_2d), coverage=[float(c) for c in coverage],
                        percentiles=[float(q) for q in percentiles])
-        self.seconds, self.points = 0.0, 0
 
-    def take(self, sampler, models, order):
-        t0 = time.perf_counter()
-        res = sampler.marginals(with_fr=models is not None, models=models, **self.kw)
-        os.makedirs(self.datadir, exist_ok=True)
-        for g, r in zip(order, [res] if len(order) == 1 else res):
-            r.save(os.path.join(self.datadir, "marginals_%s.npz" % self.name_of(g)))
-            self.points += 1
+    def write(self, sampler, models, order):
+        for g, r in self.each(sampler.marginals(with_fr=models is not None, models=models, **self.kw), order):
+            r.save(self.file("marginals", g))
         if self.elements is not None:
             # one call per distinct set of ranges among the sampler's chains (a stacked C5 scan holds dimension-3 and dimension-6
             # points, whose logLam ranges differ); every call reduces all chains, a point's file comes from its own set's call
             sets = {}
-            for k, g in enumerate(order):
+            for g in order:
                 ps = self.elements(g)
-                sets.setdefault(tuple(map(tuple, ps.ranges)), (ps, []))[1].append((k, g))
+                sets.setdefault(tuple(map(tuple, ps.ranges)), (ps, []))[1].append(g)
             for ps, members in sets.values():
-                res = sampler.marginals(space="elements", llh_paramset=ps, **self.kw)
-                res = [res] if len(order) == 1 else res
-                for k, g in members:
-                    res[k].save(os.path.join(self.datadir, "marginals_elements_%s.npz" % self.name_of(g)))
-        self.seconds += time.perf_counter() - t0
-        MARGINAL_STATS.clear()
-        MARGINAL_STATS.update({"bins": [self.kw["bins_1d"], self.kw["bins_2d"]], "points": self.points, "seconds": round(self.seconds, 4)})
+                for g, r in self.each(sampler.marginals(space="elements", llh_paramset=ps, **self.kw), order):
+                    if g in members:
+                        r.save(self.file("marginals_elements", g))
+
+    def _stats(self, **timing):
+        return {"bins": [self.kw["bins_1d"], self.kw["bins_2d"]], **timing}
 
 
-SPECTRUM_STATS = {}   # the last run_points call with --spectrum: what it computed on this rank (reported by main)
-
-
-class SpectrumWriter:
+class SpectrumWriter(PointWriter):
     """--spectrum: the composition at every energy bin of every grid point's chain (`DeviceEnsembleSampler.spectrum`: nvalid, mean,
-    covariance, percentiles and histograms per energy bin and flavour), computed while the point's sampler still holds its chain
-    and saved as spectrum_<point file name>.npz beside the chain file: `spectrum.SpectrumResult.as_arrays()`."""
+    covariance, percentiles and histograms per energy bin and flavour), saved as spectrum_<point file name>.npz:
+    `spectrum.SpectrumResult.as_arrays()`."""
+    key = "spectrum"
 
     def __init__(self, datadir, name_of, percentiles=(5., 16., 50., 84., 95.), bins=50):
-        self.datadir, self.name_of, self.percentiles, self.bins = datadir, name_of, [float(q) for q in percentiles], int(bins)
-        self.seconds, self.points, self.no_composition = 0.0, 0, 0
+        super().__init__(datadir, name_of)
+        self.percentiles, self.bins, self.no_composition = [float(q) for q in percentiles], int(bins), 0
 
-    def take(self, sampler, models, order):
-        t0 = time.perf_counter()
+    def write(self, sampler, models, order):
         res = sampler.spectrum(percentiles=self.percentiles, bins=self.bins, models=models)
         per_chain = sampler.nstored * sampler.k
-        os.makedirs(self.datadir, exist_ok=True)
-        for g, r in zip(order, [res] if len(order) == 1 else res):
-            r.save(os.path.join(self.datadir, "spectrum_%s.npz" % self.name_of(g)))
-            self.points += 1
+        for g, r in self.each(res, order):
+            r.save(self.file("spectrum", g))
             self.no_composition += per_chain - int(r.nvalid[0])
-        self.seconds += time.perf_counter() - t0
-        SPECTRUM_STATS.clear()
-        SPECTRUM_STATS.update({"percentiles": self.percentiles, "bins": self.bins, "points": self.points, "seconds": round(self.seconds, 4),
-                               "samples_without_composition": self.no_composition})
+
+    def _stats(self, **timing):
+        return {"percentiles": self.percentiles, "bins": self.bins, **timing, "samples_without_composition": self.no_composition}
 
 
-DIAGNOSTIC_STATS = {}   # the last run_points call with --diagnostics: what it computed on this rank (reported by main)
-
-
-class DiagnosticsWriter:
+class DiagnosticsWriter(PointWriter):
     """--diagnostics: the convergence diagnostics of every grid point's chain (`DeviceEnsembleSampler.diagnostics`: tau and window
-    of the walker-averaged autocorrelation function and of the ensemble-mean series, split R-hat, excluded walker series),
-    computed while the point's sampler still holds its chain and saved as diagnostics_<point file name>.npz beside the chain
-    file: `diagnostics.ChainDiagnostics.as_arrays()` plus the mean and the minimum acceptance fraction and the number of walkers
-    that never moved."""
+    of the walker-averaged autocorrelation function and of the ensemble-mean series, split R-hat, excluded walker series), saved
+    as diagnostics_<point file name>.npz: `diagnostics.ChainDiagnostics.as_arrays()` plus the mean and the minimum acceptance
+    fraction and the number of walkers that never moved."""
+    key = "diagnostics"
 
     def __init__(self, datadir, name_of, tol=50):
-        self.datadir, self.name_of, self.tol = datadir, name_of, tol
-        self.seconds, self.points, self.not_converged = 0.0, 0, 0
+        super().__init__(datadir, name_of)
+        self.tol, self.not_converged = tol, 0
 
-    def take(self, sampler, models, order):
-        t0 = time.perf_counter()
-        res = sampler.diagnostics()
-        os.makedirs(self.datadir, exist_ok=True)
-        for g, r in zip(order, [res] if len(order) == 1 else res):
+    def write(self, sampler, models, order):
+        for g, r in self.each(sampler.diagnostics(), order):
             arrays = r.as_arrays()
             acc = arrays["acceptance_fraction"]
             arrays.update(acceptance_mean=np.float64(acc.mean()), acceptance_min=np.float64(acc.min()), never_moved=np.int64((acc == 0).sum()))
-            with open(os.path.join(self.datadir, "diagnostics_%s.npz" % self.name_of(g)), "wb") as f:
+            with open(self.file("diagnostics", g), "wb") as f:
                 np.savez(f, **arrays)
-            self.points += 1
             self.not_converged += not r.converged(self.tol)
-        self.seconds += time.perf_counter() - t0
-        DIAGNOSTIC_STATS.clear()
-        DIAGNOSTIC_STATS.update({"points": self.points, "seconds": round(self.seconds, 4), "tol": self.tol, "not_converged": self.not_converged})
+
+    def _stats(self, **timing):
+        return {**timing, "tol": self.tol, "not_converged": self.not_converged}
 
 
-INTERVAL_STATS = {}   # the last run_points call with --intervals: what it computed on this rank (reported by main)
-
-
-class IntervalWriter:
+class IntervalWriter(PointWriter):
     """--intervals: the reference's shortest interval around the mode (`misc.interval`, the number `plot.chainer_plot` prints per
     panel and as the scale's 90 % interval) of every column of every grid point's saved rows, and each column's number of distinct
-    values (`DeviceEnsembleSampler.intervals`), computed while the point's sampler still holds its chain and saved as
-    intervals_<point file name>.npz beside the chain file: low, up, status (width, npct), center, nbins, nunique (width,),
-    percentiles, names."""
+    values (`DeviceEnsembleSampler.intervals`), saved as intervals_<point file name>.npz: low, up, status (width, npct), center,
+    nbins, nunique (width,), percentiles, names."""
+    key = "intervals"
 
     def __init__(self, datadir, name_of, percentiles=(68., 90.)):
-        self.datadir, self.name_of, self.percentiles = datadir, name_of, [float(p) for p in percentiles]
-        self.seconds, self.points, self.not_ok = 0.0, 0, 0
+        super().__init__(datadir, name_of)
+        self.percentiles, self.not_ok = [float(p) for p in percentiles], 0
 
-    def take(self, sampler, models, order):
+    def write(self, sampler, models, order):
         from . import intervals as iv
-        t0 = time.perf_counter()
+        from .rowsets import sample_columns
         with_fr = models is not None
         res = sampler.intervals(percentiles=self.percentiles, with_fr=with_fr, models=models)
-        names = (["fr_e", "fr_mu", "fr_tau"] if with_fr else []) + ["theta%d" % c for c in range(sampler.dim)]
-        os.makedirs(self.datadir, exist_ok=True)
-        for k, g in enumerate(order):
-            r = res if len(order) == 1 else {f: (v if f == "percentiles" else v[k]) for f, v in res.items()}
-            iv.save(os.path.join(self.datadir, "intervals_%s.npz" % self.name_of(g)), r, names)
-            self.points += 1
+        names, _ = sample_columns(sampler.model.desc, sampler.dim, with_fr)
+        for g, r in self.each(res, order):
+            iv.save(self.file("intervals", g), r, names)
             self.not_ok += int(np.count_nonzero(r["status"]))
-        self.seconds += time.perf_counter() - t0
-        INTERVAL_STATS.clear()
-        INTERVAL_STATS.update({"percentiles": self.percentiles, "points": self.points, "seconds": round(self.seconds, 4), "status_not_ok": self.not_ok})
 
-
-REWEIGHT_STATS = {}   # the last run_points call with --reweight-injected: what it computed on this rank (reported by main)
+    def _stats(self, **timing):
+        return {"percentiles": self.percentiles, **timing, "status_not_ok": self.not_ok}
 
 
 def reweight_targets(injected, smearings):
@@ -452,50 +459,32 @@ def reweight_targets(injected, smearings):
     return out
 
 
-class ReweightWriter:
+class ReweightWriter(PointWriter):
     """--reweight-injected: every grid point's chain reweighted to other measurements (`DeviceEnsembleSampler.reweight` with
-    `reweight.Measurement` targets), computed while the point's sampler still holds its chain and saved as reweight_<point file
-    name>.npz beside the chain file: the summary (ess, lnz_ratio, mean, cov), the counts (n, bad_base, nonunitary, outside) and the
-    targets (target_bestfit_fr, target_smearing, target_offset).  nrows (--reweight-rows): the marginals of that many equal-weight
-    rows per target as well, reweight_marginals_<point file name>_t<target>.npz, with --marginals' spec."""
+    `reweight.Measurement` targets), saved as reweight_<point file name>.npz: the summary (ess, lnz_ratio, mean, cov), the counts
+    (n, bad_base, nonunitary, outside) and the targets (target_bestfit_fr, target_smearing, target_offset).  nrows
+    (--reweight-rows): the marginals of that many equal-weight rows per target as well,
+    reweight_marginals_<point file name>_t<target>.npz, with --marginals' spec."""
+    key = "reweight"
 
     def __init__(self, datadir, name_of, targets, nrows=None, marginal_kw=None):
-        self.datadir, self.name_of, self.targets, self.nrows = datadir, name_of, list(targets), nrows
-        self.kw = dict(marginal_kw or {})
-        self.seconds, self.points, self.without_posterior = 0.0, 0, 0
+        super().__init__(datadir, name_of)
+        self.targets, self.nrows, self.kw, self.without_posterior = list(targets), nrows, dict(marginal_kw or {}), 0
 
-    def take(self, sampler, models, order):
+    def write(self, sampler, models, order):
         from .reweight import Measurement
-        t0 = time.perf_counter()
         r = sampler.reweight([Measurement(bestfit_fr=bf, smearing=sm) for bf, sm in self.targets], on_nonunitary="-inf")
-        summ = r._summary
+        summ = dict(r._summary, target_bestfit_fr=r.bestfit_fr, target_smearing=r.smearing, target_offset=r.offset)    # chain axis kept
         marg = r.marginals(self.nrows, **self.kw) if self.nrows else None
-        os.makedirs(self.datadir, exist_ok=True)
-        for k, g in enumerate(order):
-            arrays = {f: v[k] for f, v in summ.items()}
-            arrays.update(target_bestfit_fr=r.bestfit_fr[k], target_smearing=r.smearing[k], target_offset=r.offset[k])
-            with open(os.path.join(self.datadir, "reweight_%s.npz" % self.name_of(g)), "wb") as f:
-                np.savez(f, **arrays)
-            if marg is not None:
-                for t, m in enumerate(marg if len(order) == 1 else marg[k]):
-                    m.save(os.path.join(self.datadir, "reweight_marginals_%s_t%d.npz" % (self.name_of(g), t)))
-            self.points += 1
+        for k, (g, per_target) in enumerate(self.each(marg, order)):
+            with open(self.file("reweight", g), "wb") as f:
+                np.savez(f, **{name: v[k] for name, v in summ.items()})
+            for t, m in enumerate(per_target or ()):
+                m.save(self.file("reweight_marginals", g, "_t%d" % t))
             self.without_posterior += int(np.count_nonzero(summ["ess"][k] == 0.0))
-        self.seconds += time.perf_counter() - t0
-        REWEIGHT_STATS.clear()
-        REWEIGHT_STATS.update({"targets": len(self.targets), "points": self.points, "seconds": round(self.seconds, 4), "rows": self.nrows,
-                               "targets_without_posterior": self.without_posterior})
 
-
-class _Takers:
-    """several writers behind the one `regions` argument of run_points"""
-
-    def __init__(self, takers):
-        self.takers = takers
-
-    def take(self, sampler, models, order):
-        for t in self.takers:
-            t.take(sampler, models, order)
+    def _stats(self, **timing):
+        return {"targets": len(self.targets), **timing, "rows": self.nrows, "targets_without_posterior": self.without_posterior}
 
 
 def _post_models(jobs, order):
@@ -503,7 +492,7 @@ def _post_models(jobs, order):
     return [jobs[g].post_model for g in order] if getattr(first, "post_model", None) is not None else None
 
 
-def run_points(points, indices, make, burnin, nsteps, stacked=True, seed=25, gather=None, regions=None):
+def run_points(points, indices, make, burnin, nsteps, stacked=True, seed=25, gather=None, writers=()):
     """All of this rank's grid points advance together.  stacked (default): one sampler, one ensemble per
     grid point's posterior, every half-step of every chain in one launch; chain g draws from random stream g (its
     GLOBAL grid index), so that a grid point's chain does not depend on the number of ranks.  Otherwise one sampler per
@@ -512,7 +501,7 @@ def run_points(points, indices, make, burnin, nsteps, stacked=True, seed=25, gat
     gather: None -> {grid index: collected array} of this rank's points (host);
             a `DeviceGather` -> every grid point's array, in grid order, on rank 0 (None elsewhere): the chain blocks
             go from the sampler's device buffer through RCCL and cross PCIe once.
-    regions: a `RegionWriter` -> every point's credible regions are computed and saved while its sampler holds the chain."""
+    writers: `PointWriter`s -> each reduces and saves every point's chain, in this order, while its sampler holds the chain."""
     t0 = time.perf_counter()
     jobs = {g: make(points[g], g) for g in indices}
     if not jobs:
@@ -562,8 +551,8 @@ def run_points(points, indices, make, burnin, nsteps, stacked=True, seed=25, gat
             times = sampler.run_to_host_times()
             if times is not None:
                 LAST_NONUNITARY["host_thread_times"] = times
-        if regions is not None:
-            regions.take(sampler, _post_models(jobs, order), order)
+        for w in writers:
+            w.take(sampler, _post_models(jobs, order), order)
         t0 = time.perf_counter()
         if gather is not None:
             out = gather.run(sampler, jobs, order, len(points), streamed=streamed)
@@ -599,8 +588,8 @@ def run_points(points, indices, make, burnin, nsteps, stacked=True, seed=25, gat
     out = {}
     for g, sm in samplers.items():
         sm.wait()
-        if regions is not None:
-            regions.take(sm, _post_models(jobs, [g]), [g])
+        for w in writers:
+            w.take(sm, _post_models(jobs, [g]), [g])
         flat = sm.flat_steps()                                    # the stacked paths' row order (module docstring)
         sm.close()
         out[g] = jobs[g].collect(flat)
@@ -1032,44 +1021,37 @@ def main(argv=None):
         rccl, rccl_err, stuck = gdist.open_device_gather(rank, world, device, control, timeout=float(os.environ.get("GF_RCCL_TIMEOUT", "60")))
     device_gather = want_gather and can_deliver and not shared and (rccl is not None or world == 1)
     gather_name, chains, local = "local", None, None
-    regions = None
+    name_of = lambda g: point_filename(a.config, pts[g], a)  # noqa: E731
+    marginal_kw = dict(bins_1d=a.marginal_bins_1d, bins_2d=a.marginal_bins_2d, coverage=a.marginal_coverage, percentiles=a.marginal_percentiles)
+    writers = []
     if a.regions is not None:
-        regions = RegionWriter(a.datadir, lambda g: point_filename(a.config, pts[g], a), a.regions, nbins=a.region_nbins,
-                               oversample=a.region_oversample, smooth=a.region_smooth)
-    marginal_writer = None
+        writers.append(RegionWriter(a.datadir, name_of, a.regions, nbins=a.region_nbins, oversample=a.region_oversample, smooth=a.region_smooth))
     if a.marginals:
-        marginal_writer = MarginalWriter(a.datadir, lambda g: point_filename(a.config, pts[g], a), a.marginal_bins_1d, a.marginal_bins_2d,
-                                         a.marginal_coverage, a.marginal_percentiles, elements=_point_paramset(a, pts) if a.elements else None)
-    region_stats_wanted = regions is not None
-    diagnostics_writer = DiagnosticsWriter(a.datadir, lambda g: point_filename(a.config, pts[g], a)) if a.diagnostics else None
-    interval_writer = IntervalWriter(a.datadir, lambda g: point_filename(a.config, pts[g], a), a.intervals) if a.intervals is not None else None
-    spectrum_writer = None
+        writers.append(MarginalWriter(a.datadir, name_of, **marginal_kw, elements=_point_paramset(a, pts) if a.elements else None))
+    if a.diagnostics:
+        writers.append(DiagnosticsWriter(a.datadir, name_of))
+    if a.intervals is not None:
+        writers.append(IntervalWriter(a.datadir, name_of, a.intervals))
     if a.spectrum is not None:
-        spectrum_writer = SpectrumWriter(a.datadir, lambda g: point_filename(a.config, pts[g], a), a.spectrum, a.spectrum_bins)
-    reweight_writer = None
+        writers.append(SpectrumWriter(a.datadir, name_of, a.spectrum, a.spectrum_bins))
     if rw_targets is not None:
-        reweight_writer = ReweightWriter(a.datadir, lambda g: point_filename(a.config, pts[g], a), rw_targets, a.reweight_rows,
-                                         dict(bins_1d=a.marginal_bins_1d, bins_2d=a.marginal_bins_2d, coverage=a.marginal_coverage,
-                                              percentiles=a.marginal_percentiles))
-    if any(t is not None for t in (marginal_writer, diagnostics_writer, interval_writer, spectrum_writer, reweight_writer)):
-        regions = _Takers([t for t in (regions, marginal_writer, diagnostics_writer, interval_writer, spectrum_writer, reweight_writer)
-                           if t is not None])
+        writers.append(ReweightWriter(a.datadir, name_of, rw_targets, a.reweight_rows, marginal_kw))
     if a.datadir and not want_gather:
-        local = run_points(pts, mine, make, a.burnin, a.nsteps, stacked=stacked, regions=regions)
+        local = run_points(pts, mine, make, a.burnin, a.nsteps, stacked=stacked, writers=writers)
         gather_name = "none: every rank saved its own files (--datadir)"
     elif shared:
         g = SharedHostGather(control, rank, world, arena=arena)
-        chains = run_points(pts, mine, make, a.burnin, a.nsteps, stacked=True, gather=g, regions=regions)
+        chains = run_points(pts, mine, make, a.burnin, a.nsteps, stacked=True, gather=g, writers=writers)
         gather_name = g.stats.get("delivery", g.kind)
         g.release()
     elif device_gather:
         stage = Model(compile_model(Cf.unitary_paramset(), "PRIOR_ONLY", source_ratio=(1, 2, 0)), device=device)
         chains = run_points(pts, mine, make, a.burnin, a.nsteps, stacked=True,
-                            gather=DeviceGather(rccl, rank, world, stage, control=control), regions=regions)
+                            gather=DeviceGather(rccl, rank, world, stage, control=control), writers=writers)
         stage.close()
         gather_name = ("%s device gather to rank 0" % rccl.kind) if rccl is not None else "device -> host"
     else:
-        local = run_points(pts, mine, make, a.burnin, a.nsteps, stacked=stacked, regions=regions)
+        local = run_points(pts, mine, make, a.burnin, a.nsteps, stacked=stacked, writers=writers)
         t1 = time.perf_counter()
         chains = gdist.gather_chains_to_root(local, len(pts), control)
         PHASES["gather"] = time.perf_counter() - t1
@@ -1108,12 +1090,7 @@ def main(argv=None):
                           "chains_shape": chains_shape, "seconds": dt,
                           "phases": {k: round(v, 4) for k, v in PHASES.items()},
                           "evals_per_s": len(pts) * evals_per_point / dt,
-                          "finite_fraction": finite, **({"regions": REGION_STATS} if region_stats_wanted else {}),
-                          **({"marginals": MARGINAL_STATS} if marginal_writer is not None else {}),
-                          **({"diagnostics": DIAGNOSTIC_STATS} if diagnostics_writer is not None else {}),
-                          **({"intervals": INTERVAL_STATS} if interval_writer is not None else {}),
-                          **({"spectrum": SPECTRUM_STATS} if spectrum_writer is not None else {}),
-                          **({"reweight": REWEIGHT_STATS} if reweight_writer is not None else {})}), flush=True)
+                          "finite_fraction": finite, **{w.key: w.stats() for w in writers}}), flush=True)
     control.barrier()
     control.close()
     if rccl_err is not None:

@@ -272,3 +272,47 @@ def test_fused_entry_point_equals_rows_then_reducer(source, reduction, variant, 
         nested_cell(request.getfixturevalue("runs"), reduction)
     else:
         reweight_cell(request.getfixturevalue("reweighted"), reduction, variant)
+
+
+def test_one_chain_is_chain_zero_of_three_without_the_chain_axis(chain):
+    """The single-chain rule on the device path.  A sampler of one chain and chain 0 of a sampler of three, on the same random stream
+    from the same start, hold the same chain; every reduction of the one-chain sampler is then that of chain 0 bit for bit, NaNs in
+    place, and carries no chain axis: a result where the other has a list of results, arrays one dimension short."""
+    _, f, ps, post, _ = chain
+    p0 = np.stack([uniform_theta(ps, NWALKERS, np.random.default_rng(5 + c), seeds=True) for c in range(NCHAINS)])
+    one = mcmc_utils.DeviceEnsembleSampler(NWALKERS, NDIM, f, nchains=1, seed=3, stream_ids=[7])
+    three = mcmc_utils.DeviceEnsembleSampler(NWALKERS, NDIM, f, nchains=NCHAINS, seed=3, stream_ids=[7, 8, 9])
+    try:
+        one.run_mcmc(p0[0], NSTEPS)
+        three.run_mcmc(p0, NSTEPS)
+        assert one.flat_steps().shape == (4160, NDIM) and same(one.flat_steps(), three.flat_steps()[0])
+        assert not same(three.flat_steps()[0], three.flat_steps()[1])
+        spectra = 0
+        for which, m1, m3 in (("own", None, None), ("post", post[:1], post)):
+            a, b = one.marginals(with_fr=True, models=m1, **MKW), three.marginals(with_fr=True, models=m3, **MKW)
+            assert isinstance(a, mg.MarginalResult) and isinstance(b, list) and len(b) == NCHAINS
+            same_marginals([a], b[:1], "marginals, %s models" % which)
+            a, b = one.intervals(percentiles=PCT, with_fr=True, models=m1), three.intervals(percentiles=PCT, with_fr=True, models=m3)
+            assert a["low"].shape == (3 + NDIM, 2) and b["low"].shape == (NCHAINS, 3 + NDIM, 2) and same(a["percentiles"], b["percentiles"])
+            same_intervals(a, {k: b[k][0] for k in iv.FIELDS}, "intervals, %s models" % which)
+            a, b = one.regions(RBINS, RCOV, models=m1), three.regions(RBINS, RCOV, models=m3)
+            assert isinstance(a[0], contour.RegionResult) and len(b) == NCHAINS
+            same_regions([a], b[:1], "regions, %s models" % which)
+            a, b = one.regions(RBINS, 90., models=m1), three.regions(RBINS, 90., models=m3)       # one coverage: no coverage level either
+            assert isinstance(a, contour.RegionResult) and isinstance(b[0], contour.RegionResult)
+            same_regions([[a] * 2], [[b[0]] * 2], "regions at one coverage, %s models" % which)
+            a, b = one.spectrum(percentiles=(16, 50, 84), bins=20, models=m1), three.spectrum(percentiles=(16, 50, 84), bins=20, models=m3)
+            assert not isinstance(a, list) and len(b) == NCHAINS
+            for k, v in a.as_arrays().items():
+                assert same(v, b[0].as_arrays()[k]), ("spectrum", which, k)
+                spectra += 1
+        assert spectra == 2 * 13
+        a, b = one.marginals(space="elements", llh_paramset=ps, **MKW), three.marginals(space="elements", llh_paramset=ps, **MKW)
+        assert isinstance(a, mg.MarginalResult) and len(b) == NCHAINS
+        same_marginals([a], b[:1], "element marginals")
+        a, b = one.intervals(percentiles=PCT, space="elements", llh_paramset=ps), three.intervals(percentiles=PCT, space="elements", llh_paramset=ps)
+        assert a["low"].shape == b["low"].shape[1:] and b["low"].shape[0] == NCHAINS
+        same_intervals(a, {k: b[k][0] for k in iv.FIELDS}, "element intervals")
+    finally:
+        one.close()
+        three.close()
