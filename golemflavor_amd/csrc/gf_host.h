@@ -22,7 +22,7 @@ namespace {
 // "what: <HIP's message>" as the last error; returns GF_ERR_HIP
 inline int gf_hip_fail(hipError_t e, const char* what)
 {
-    char msg[256];
+    char msg[512];
     std::snprintf(msg, sizeof(msg), "%s: %s", what, hipGetErrorString(e));
     gf_internal_set_error(msg);
     return GF_ERR_HIP;
@@ -31,7 +31,7 @@ inline int gf_hip_fail(hipError_t e, const char* what)
 // a printf-style message as the last error; returns rc
 __attribute__((format(printf, 2, 3))) inline int gf_fail_msg(int rc, const char* fmt, ...)
 {
-    char msg[256];
+    char msg[512];
     va_list ap;
     va_start(ap, fmt);
     std::vsnprintf(msg, sizeof(msg), fmt, ap);

@@ -9,15 +9,20 @@
 #include "../../include/golemflavor_hip.h"
 #include "gf_consts.h"
 
-constexpr int POOL_MAX_DEVICES = 64;     // devices the per-device pools (gf_capi.hip) and read-back rings (gf_readback.hip) have room for
+constexpr int POOL_MAX_DEVICES = 64;     // devices the per-device pools (gf_pool.hip) and read-back rings (gf_readback.hip) have room for
 
 extern "C" {
 // gf_capi.hip
 const char* gf_internal_env(const char* name, int affects_results);   // getenv with a record
 void gf_internal_set_error(const char* msg);                          // the text gf_last_hip_error() returns
-// gf_model is private to gf_capi.hip: its constants, and (gf_model_internal: sets the device, gives the model a stream) its stream
+
+// gf_model.hip
+// gf_model is private to gf_model.hip and gf_capi.hip (gf_model.h): its constants, and (gf_model_internal: sets the device, gives the
+// model a stream) its stream
 int gf_model_internal(gf_model* m, const GfCommon** c, const GfBsm** d_bsm, const double** d_ptab, void** stream, int* device);
 int gf_model_constants(gf_model* m, const GfCommon** c, const GfBsm** d_bsm, const double** d_ptab, int* device, int* cus, int* nbins);
+// the model's device and the stream it has (NULL: none yet, and it is given none); not exported from the library
+__attribute__((visibility("hidden"))) void gf_model_peek_stream(const gf_model* m, int* device, void** stream);
 // the constants of multi_gaussian for cov = smearing^2 I, as gf_model_create derives them: logpdf = fma(mh, |fr - bf|^2, k)
 void gf_internal_gauss_consts(double smearing, double* inv_smear, double* c0, double* mh, double* k);
 // the model's kernels on a stream of the caller's
@@ -26,6 +31,8 @@ int gf_model_propagate_on(gf_model* m, void* stream, const double* d_theta, int 
 // k_bsm_bins (gf_spectrum.hip): d_fr_bins [n][nbins][3], or [nbins][n][3] with bin_major; BSM models only (else GF_ERR_UNSUPPORTED)
 int gf_model_bins_on(gf_model* m, void* stream, const double* d_theta, int layout, int64_t n, double* d_fr_bins, int bin_major,
                      const int32_t* d_status);
+
+// gf_pool.hip
 // streams of the device's pool (copy stream: for a large read-back that overlaps another stream's kernels); returned idle
 int gf_internal_borrow_stream(int device, void** stream);
 void gf_internal_return_stream(int device, void* stream);

@@ -1,4 +1,4 @@
-// Internal launch interface between the C ABI (gf_capi.hip) and the kernels (gf_kernels.hip,
+// Internal launch interface between the C ABI (gf_capi.hip, gf_model.hip) and the kernels (gf_kernels.hip,
 // gf_bsm.hip).  All launches are asynchronous on `s`.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,5 +1,5 @@
 // Internal interface of gf_spectrum.hip (the energy-resolved composition of include/golemflavor_hip.h) for the files
-// that own what it works on: gf_capi.hip (the model's constants), gf_postprocess.hip (a sampler's stored chain) and
+// that own what it works on: gf_model.hip (the model's constants), gf_postprocess.hip (a sampler's stored chain) and
 // gf_nested_post.hip (a nested sampler's posterior rows).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -7,7 +7,7 @@ set -e
 cd "$(dirname "$0")/../golemflavor_amd/csrc"
 T=$(mktemp -d)
 printf "%-110s %6s %6s %8s %8s %7s\n" kernel vgpr sgpr scratch lds spills
-for f in ${@:-gf_kernels gf_bsm gf_unitarity gf_sampler gf_capi gf_nested gf_simplex gf_region gf_marginal}; do
+for f in ${@:-gf_kernels gf_bsm gf_unitarity gf_sampler gf_nested gf_simplex gf_region gf_marginal}; do
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -c $f.hip -o $T/$f.o -save-temps=obj 2>/dev/null
   S=$T/$f-hip-amdgcn-amd-amdhsa-gfx950.s
   [ -f $S ] || continue
