@@ -315,6 +315,17 @@ def device_trim(device=0):
     return int(n.value)
 
 
+def pass_items(model_handle):
+    """gf_internal_pass_items (gf_internal.h; not part of the public header, hence not in SIGNATURES): the work items one pass of a
+    bulk launch's capped grid covers on the model's device, compute units x blocks per compute unit x lanes per block.  A single
+    launch of more walkers takes the kernels' tile loops round again."""
+    fn = lib().gf_internal_pass_items
+    fn.restype, fn.argtypes = C.c_int, [_vp, _lp]
+    n = C.c_int64(0)
+    check(fn(model_handle, C.byref(n)), "gf_internal_pass_items")
+    return int(n.value)
+
+
 def device_count():
     n = C.c_int(0)
     check(lib().gf_device_count(C.byref(n)), "gf_device_count")

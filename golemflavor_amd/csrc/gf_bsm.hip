@@ -291,14 +291,7 @@ __global__ __launch_bounds__(GF_BLOCK, GF_T2_WAVES) void k_bsm_tier2(const GfBsm
     // and an atomic per block here)
 }
 
-inline int grid_for(int64_t work_items, int per_block, int cus)
-{
-    int64_t blocks = (work_items + per_block - 1) / per_block;
-    const int64_t cap = (int64_t)cus * 8;
-    if (blocks > cap) blocks = cap;
-    if (blocks < 1) blocks = 1;
-    return (int)blocks;
-}
+static_assert(GF_BLOCK == GF_LAUNCH_BLOCK, "gf_pass_items counts blocks of GF_BLOCK lanes");
 
 // Lanes per walker for a batch of n walkers, from a sweep on MI355X (profiles/r01/bsm_lanes_per_walker_sweep.txt:
 // 12-column posterior, 20 bins; 16 lanes win up to 4096 walkers, 4 lanes up to 32768, one lane beyond): the widest split
@@ -322,7 +315,7 @@ template <int NDIM, int LPW>
 hipError_t launch_nl(const GfCommon& c, const GfCommon* d_common, const GfBsm* d_bsm, int nbins, const double* ptab, const double* theta, int layout,
                      int64_t n, int with_llh, double* lnprob, double* fr, int32_t* status, GfArbQueue* uq, GfUniQueue* wq, double* t2sn, int cus, hipStream_t s)
 {
-    const int grid = grid_for(n * LPW, GF_BLOCK, cus);
+    const int grid = gf_grid_for(n * LPW, GF_BLOCK, cus);
     const size_t lds = LPW > 1 ? (size_t)(GF_BLOCK / LPW) * GF_FGRP_DOUBLES(nbins, LPW) * sizeof(double) : 0;
     // status requested: tiers 1-2 inline (wq == NULL) or deferred to k_bsm_tier2 (large batches, one lane per walker)
     const int mode = status == nullptr ? UNI_NONE : (wq != nullptr && LPW == 1 ? UNI_DEFER : UNI_INLINE);
@@ -332,7 +325,7 @@ hipError_t launch_nl(const GfCommon& c, const GfCommon* d_common, const GfBsm* d
 #undef GF_GO
     hipError_t e = hipGetLastError();
     if (e == hipSuccess && mode == UNI_DEFER) {
-        const int g2 = grid_for(n / 4 + 1, GF_BLOCK, cus);
+        const int g2 = gf_grid_for(n / 4 + 1, GF_BLOCK, cus);
         hipLaunchKernelGGL(k_bsm_tier2, dim3(g2), dim3(GF_BLOCK), 0, s, d_bsm, t2sn, n, with_llh ? lnprob : nullptr, status, uq, wq);
         e = hipGetLastError();
     }
@@ -380,7 +373,10 @@ hipError_t gf_launch_bsm(const GfCommon& c, const GfCommon* d_common, const GfBs
     // diagnostics only (needs GF_DIAGNOSTICS=1): pieces four times what the queues hold, to exercise the overflow report
     static const bool overcommit = gf_internal_env("GF_DIAG_UQ_OVERCOMMIT", 1) != nullptr;
     if (overcommit) piece *= 4;
-    if (piece > 64) piece &= ~(int64_t)63;                               // whole tiles: every piece starts 16-B aligned like the batch
+    // a batch that is cut is cut into whole tiles: every piece starts 16-B aligned like the batch.  One that fits is not rounded: queues
+    // of exactly n walkers (a first batch on the stream, or any SoA batch that grows them) with a ragged n would otherwise leave the
+    // last n % 64 rows to a second piece, which SoA columns cannot have
+    if (piece < n && piece > 64) piece &= ~(int64_t)63;
     if (piece < 1) piece = 1;
     if (layout != 0 && piece < n) return hipErrorInvalidValue;          // SoA columns cannot be cut: the caller sizes the queue for n
     for (int64_t w0 = 0; w0 < n; w0 += piece) {

@@ -21,6 +21,8 @@ void gf_internal_set_error(const char* msg);                          // the tex
 // model a stream) its stream
 int gf_model_internal(gf_model* m, const GfCommon** c, const GfBsm** d_bsm, const double** d_ptab, void** stream, int* device);
 int gf_model_constants(gf_model* m, const GfCommon** c, const GfBsm** d_bsm, const double** d_ptab, int* device, int* cus, int* nbins);
+// work items one pass of a bulk launch covers on the model's device: cus x GF_BLOCKS_PER_CU x GF_BLOCK (gf_launch.h gf_pass_items)
+int gf_internal_pass_items(gf_model* m, int64_t* items);
 // the model's device and the stream it has (NULL: none yet, and it is given none); not exported from the library
 __attribute__((visibility("hidden"))) void gf_model_peek_stream(const gf_model* m, int* device, void** stream);
 // the constants of multi_gaussian for cov = smearing^2 I, as gf_model_create derives them: logpdf = fma(mh, |fr - bf|^2, k)

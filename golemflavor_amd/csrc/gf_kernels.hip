@@ -411,27 +411,25 @@ struct CubeMap {
 __global__ __launch_bounds__(GF_BLOCK) void k_cube_to_theta(const CubeMap cm, const double* __restrict__ cube, int64_t n,
                                                             double* __restrict__ theta)
 {
+    // plain operators under contract(off): the HIP headers' __dmul_rn / __dadd_rn are operators that carry the contract flag of the
+    // header's own context into this function, and the pair was fused into one v_fma_f64
+#pragma clang fp contract(off)
     const int64_t total = n * cm.ndim;
     for (int64_t i = (int64_t)blockIdx.x * GF_BLOCK + threadIdx.x; i < total; i += (int64_t)gridDim.x * GF_BLOCK) {
         const int64_t w = i / cm.ndim;
         const int col = (int)(i - w * cm.ndim);
         const int sl = cm.slot[col];
         // product, then sum, each rounded (mn.py:36 is a Python expression): no fused multiply-add here
-        theta[i] = sl >= 0 ? __dadd_rn(__dmul_rn(cm.span[col], cube[w * cm.nscan + sl]), cm.lo[col]) : cm.base[col];
+        double v = cm.base[col];
+        if (sl >= 0) {
+            const double prod = cm.span[col] * cube[w * cm.nscan + sl];
+            v = prod + cm.lo[col];
+        }
+        theta[i] = v;
     }
 }
 
-#ifndef GF_BLOCKS_PER_CU
-#define GF_BLOCKS_PER_CU 8
-#endif
-inline int grid_for(int64_t work_items, int per_block, int cus)
-{
-    int64_t blocks = (work_items + per_block - 1) / per_block;
-    const int64_t cap = (int64_t)cus * GF_BLOCKS_PER_CU;   // 256-thread blocks per CU that keep the chip full
-    if (blocks > cap) blocks = cap;
-    if (blocks < 1) blocks = 1;
-    return (int)blocks;
-}
+static_assert(GF_BLOCK == GF_LAUNCH_BLOCK, "gf_pass_items counts blocks of GF_BLOCK lanes");
 
 template <int NDIM, int MODE>
 hipError_t launch_lnprob_sm_nm(const GfCommon& c, const double* ptab, const double* theta, int layout, int64_t n,
@@ -443,7 +441,7 @@ hipError_t launch_lnprob_sm_nm(const GfCommon& c, const double* ptab, const doub
         // a small ragged batch (emcee's half-ensembles) is one launch of the generic kernel, not fast + tail
         if (n <= 2048 && n % GF_WAVE != 0) nfull = 0;
         if (layout == 0 && nfull > 0) {
-            const int grid = grid_for(nfull * GF_WAVE, GF_BLOCK, cus);
+            const int grid = gf_grid_for(nfull * GF_WAVE, GF_BLOCK, cus);
             const bool sampled = c.idx_sm[0] >= 0 && c.idx_sm[1] >= 0 && c.idx_sm[2] >= 0 && c.idx_sm[3] >= 0 &&
                                  c.idx_src[0] >= 0 && c.idx_src[1] >= 0;
             const bool canon = sampled && NDIM >= 6 && c.idx_sm[0] == 0 && c.idx_sm[1] == 1 && c.idx_sm[2] == 2 &&
@@ -463,7 +461,7 @@ hipError_t launch_lnprob_sm_nm(const GfCommon& c, const double* ptab, const doub
         const bool canon = NDIM >= 6 && c.idx_sm[0] == 0 && c.idx_sm[1] == 1 && c.idx_sm[2] == 2 && c.idx_sm[3] == 3 &&
                            c.idx_src[0] == 4 && c.idx_src[1] == 5;
         if (layout == 1 && nfull > 0 && (MODE == MODE_PRIOR_ONLY || canon)) {
-            const int grid = grid_for(nfull * GF_WAVE, GF_BLOCK, cus);
+            const int grid = gf_grid_for(nfull * GF_WAVE, GF_BLOCK, cus);
 #define GF_GOS(S, F) hipLaunchKernelGGL((k_lnprob_sm_soa<NDIM, MODE, S, F>), dim3(grid), dim3(GF_BLOCK), 0, s, c, ptab, theta, n, nfull, lnprob, fr, status)
             if (MODE == MODE_PRIOR_ONLY) { if (fr) GF_GOS(0, true); else GF_GOS(0, false); }
             else                         { if (fr) GF_GOS(2, true); else GF_GOS(2, false); }
@@ -472,7 +470,7 @@ hipError_t launch_lnprob_sm_nm(const GfCommon& c, const double* ptab, const doub
         }
     }
     if (first < n) {
-        const int grid = grid_for(n - first, GF_BLOCK, cus);
+        const int grid = gf_grid_for(n - first, GF_BLOCK, cus);
         hipLaunchKernelGGL((k_lnprob_sm_gen<NDIM, MODE>), dim3(grid), dim3(GF_BLOCK), 0, s, c, ptab, theta, layout, first, n,
                            lnprob, fr, status);
     }
@@ -492,7 +490,7 @@ template <int NDIM>
 hipError_t launch_propagate_sm_n(const GfCommon& c, const double* theta, int layout, int64_t n, double* fr,
                                  int32_t* status, int cus, hipStream_t s)
 {
-    const int grid = grid_for(n, GF_BLOCK, cus);
+    const int grid = gf_grid_for(n, GF_BLOCK, cus);
     hipLaunchKernelGGL((k_propagate_sm<NDIM>), dim3(grid), dim3(GF_BLOCK), 0, s, c, theta, layout, n, fr, status);
     return hipGetLastError();
 }
@@ -523,7 +521,7 @@ hipError_t gf_launch_cube_to_theta(const GfCommon& c, int nscan, const int32_t* 
         cm.lo[cols[k]] = c.lo[cols[k]];
         cm.span[cols[k]] = c.hi[cols[k]] - c.lo[cols[k]];            // mn.py:36 (hi - lo) * cube + lo
     }
-    const int grid = grid_for(n * c.ndim, GF_BLOCK, cus);
+    const int grid = gf_grid_for(n * c.ndim, GF_BLOCK, cus);
     hipLaunchKernelGGL(k_cube_to_theta, dim3(grid), dim3(GF_BLOCK), 0, s, cm, cube, n, theta);
     return hipGetLastError();
 }
@@ -541,14 +539,14 @@ hipError_t gf_launch_propagate_sm(const GfCommon& c, const double* theta, int la
 hipError_t gf_launch_join_rows(const double* fr, const int32_t* status, const double* theta, int ndim, int64_t n, double* out,
                                int cus, hipStream_t s)
 {
-    const int grid = grid_for(n * (3 + ndim), GF_BLOCK, cus);
+    const int grid = gf_grid_for(n * (3 + ndim), GF_BLOCK, cus);
     hipLaunchKernelGGL(k_join_rows, dim3(grid), dim3(GF_BLOCK), 0, s, fr, status, theta, ndim, n, out);
     return hipGetLastError();
 }
 
 hipError_t gf_launch_flavor_hist(const double* fr, int64_t n, int nb, unsigned long long* counts, int cus, hipStream_t s)
 {
-    const int grid = grid_for(n, GF_BLOCK, cus);
+    const int grid = gf_grid_for(n, GF_BLOCK, cus);
     hipLaunchKernelGGL(k_flavor_hist, dim3(grid), dim3(GF_BLOCK), 0, s, fr, n, nb, counts);
     return hipGetLastError();
 }
@@ -556,7 +554,7 @@ hipError_t gf_launch_flavor_hist(const double* fr, int64_t n, int nb, unsigned l
 hipError_t gf_launch_haar(const GfCommon& c, uint64_t seed, int64_t first, int64_t n, double* angles, double* fr,
                           int cus, hipStream_t s)
 {
-    const int grid = grid_for(n, GF_BLOCK, cus);
+    const int grid = gf_grid_for(n, GF_BLOCK, cus);
     hipLaunchKernelGGL(k_haar, dim3(grid), dim3(GF_BLOCK), 0, s, c, seed, first, n, angles, fr);
     return hipGetLastError();
 }

@@ -6,6 +6,23 @@
 
 #include "gf_consts.h"
 
+// Grid of a bulk launch: one block of `per_block` work items each, capped at GF_BLOCKS_PER_CU blocks per CU (256-thread blocks
+// that keep the chip full); beyond the cap the kernels stride.  One pass of a capped grid of GF_LAUNCH_BLOCK-lane blocks covers
+// gf_pass_items(cus) work items (gf_internal_pass_items: the tests size their multi-pass batches from it).
+#ifndef GF_BLOCKS_PER_CU
+#define GF_BLOCKS_PER_CU 8
+#endif
+constexpr int GF_LAUNCH_BLOCK = 256;               // lanes per block of the bulk kernels (GF_BLOCK, gf_device.hpp)
+inline int gf_grid_for(int64_t work_items, int per_block, int cus)
+{
+    int64_t blocks = (work_items + per_block - 1) / per_block;
+    const int64_t cap = (int64_t)cus * GF_BLOCKS_PER_CU;
+    if (blocks > cap) blocks = cap;
+    if (blocks < 1) blocks = 1;
+    return (int)blocks;
+}
+inline int64_t gf_pass_items(int cus) { return (int64_t)cus * GF_BLOCKS_PER_CU * GF_LAUNCH_BLOCK; }
+
 // `ptab`: device table [GF_MAX_DIM][4] = {lo, hi, loc, 1/sigma} per column (GfModel::d_ptab)
 hipError_t gf_launch_lnprob_sm(const GfCommon& c, const double* ptab, const double* theta, int layout, int64_t n,
                                double* lnprob, double* fr, int32_t* status, int cus, hipStream_t s);

@@ -413,6 +413,15 @@ int gf_model_constants(gf_model* m, const GfCommon** c, const GfBsm** d_bsm, con
     return GF_OK;
 }
 
+// the work items one pass of a bulk launch's capped grid covers on the model's device (gf_grid_for): a launch of more takes the
+// kernels' stride loops round again.  The tests of those loops size their batches from this.
+int gf_internal_pass_items(gf_model* m, int64_t* items)
+{
+    if (!m || !items) return GF_ERR_INVALID_ARG;
+    *items = gf_pass_items(m->cus);
+    return GF_OK;
+}
+
 void gf_model_peek_stream(const gf_model* m, int* device, void** stream)
 {
     *device = m->device;
