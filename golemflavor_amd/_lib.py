@@ -257,6 +257,8 @@ SIGNATURES = {
     "gf_sampler_reweight_intervals": (C.c_int, [_vp, C.POINTER(GfReweightSpec), C.c_int64, C.c_int, C.POINTER(GfIntervalSpec), C.POINTER(GfIntervalOut)]),
     "gf_sampler_reweight_regions": (C.c_int, [_vp, C.POINTER(GfReweightSpec), C.c_int64, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int64, _lp, _ip, _dp, _dp,
                                               _dp, _ip, _dp]),
+    "gf_model_set_binned_measurement": (C.c_int, [_vp, C.c_int, _dp, _dp]),
+    "gf_model_is_binned": (C.c_int, [_vp]),
 }
 
 _lib = None

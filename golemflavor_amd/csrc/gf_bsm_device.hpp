@@ -507,6 +507,71 @@ __device__ __forceinline__ void flux_average(const GfCommon& c, const GfBsm* __r
     fr[0] = a0 * inv; fr[1] = a1 * inv; fr[2] = a2 * inv;
 }
 
+// ---- the energy-resolved Gaussian likelihood ------------------------------------------------
+// A model's binned measurement (gf_consts.h: GF_BINNED_STRIDE doubles per energy bin) lives in device memory per model; the
+// kernels stage it in LDS beside the other eval tables.
+
+// no barrier here, the caller syncs (as load_eval_tables)
+__device__ __forceinline__ void load_binned_table(double* btab, const double* __restrict__ src, int nbins)
+{
+    for (int j = threadIdx.x; j < GF_BINNED_STRIDE * nbins; j += blockDim.x) btab[j] = src[j];
+}
+
+// sum_k multi_gaussian(fr_k, m_k, sigma_k, offset = 0) for one walker, one lane: flux_average's prologue and bin loop -- fr_k is bit for
+// bit what k_bsm_bins stores for bin k -- with the width-weighted accumulation replaced by the Gaussian term of the bin, formed as
+// gauss_llh forms it (underflow wall included), and the running sum of the terms: ascending k from 0.0, one rounding per add.  A bin
+// at -inf makes the sum -inf.  UNI_NONE: values only; UNI_INLINE: tiers 1 and 2 as flux_average<UNI_INLINE> runs them -- the verdict
+// does not depend on the measurement.
+template <int UNI_MODE>
+__device__ __forceinline__ double binned_llh(const GfCommon& c, const GfBsm* __restrict__ tb, const double* ttab, const double* btab,
+                                             const double* row, UniAcc& acc)
+{
+    static_assert(UNI_MODE == UNI_NONE || UNI_MODE == UNI_INLINE, "binned_llh: values, or values with tiers 1 and 2");
+    Herm3 S, N;
+    hamiltonian_terms(c, tb, ttab, row, S, N);
+    if (UNI_MODE == UNI_INLINE) {
+        const double trS = (S.d0 + S.d1) + S.d2, trN = (N.d0 + N.d1) + N.d2;
+        acc.a_min = fast_rcp(fma(tb->rho_max, trN * fast_rcp(trS), 1.0));
+    }
+    Herm3 Sn, Nn;
+    BinInv w;
+    bin_invariants(S, N, Sn, Nn, w);
+    const double isrc = fast_rcp(c.src_fixed_sum);
+    const double s2 = c.src_fixed[2] * isrc;
+    const double ds0 = fma(c.src_fixed[0], isrc, -s2), ds1 = fma(c.src_fixed[1], isrc, -s2);
+    double sum = 0.0;
+    const int nb = tb->nbins;
+    for (int k = 0; k < nb; ++k) {
+        double p[3][3];
+        bin_moduli<UNI_MODE>(w, Sn, Nn, tb->rho[k], p, acc, k, tb);
+        const double p02 = (1.0 - p[0][0]) - p[0][1], p12 = (1.0 - p[1][0]) - p[1][1];
+        const double w0 = fma(ds1, p[1][0], fma(ds0, p[0][0], s2));
+        const double w1 = fma(ds1, p[1][1], fma(ds0, p[0][1], s2));
+        const double w2 = fma(ds1, p12, fma(ds0, p02, s2));
+        const double dw0 = w0 - w2, dw1 = w1 - w2;
+        const double f0 = fma(p[0][1], dw1, fma(p[0][0], dw0, w2));
+        const double f1 = fma(p[1][1], dw1, fma(p[1][0], dw0, w2));
+        const double f2 = (1.0 - f0) - f1;                                // as k_bsm_bins: sum(src / sum src) = 1
+        const double* b = btab + GF_BINNED_STRIDE * k;
+        const double d0 = f0 - b[0], d1 = f1 - b[1], d2 = f2 - b[2];
+        const double r2 = fma(d2, d2, fma(d1, d1, d0 * d0));
+        sum = sum + log_of_exp(fma(b[3], r2, b[4]));
+    }
+    // second phase, as flux_average<UNI_INLINE>: tier 2 for the walkers tier 1 does not clear, terms rebuilt from the row
+    if (UNI_MODE == UNI_INLINE && __builtin_expect(acc.a_min < tb->uni_a_ok, 0)) {
+        int opaque = 0;
+        asm volatile("" : "+v"(opaque));
+        const double* row2 = row + opaque;
+        Herm3 S2, N2;
+        hamiltonian_terms(c, tb, ttab, row2, S2, N2);
+        Herm3 Sn2, Nn2;
+        BinInv w2;
+        bin_invariants(S2, N2, Sn2, Nn2, w2);
+        tier2_bins(tb, w2, Sn2, Nn2, acc);
+    }
+    return sum;
+}
+
 // box + priors from the LDS constant table (same layout as the SM kernels: {lo, hi, loc, 1/sigma} per
 // column), branch-free
 template <int NDIM>

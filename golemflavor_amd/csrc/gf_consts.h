@@ -73,6 +73,11 @@ struct GfBsm {
     double wsum;                    // sum_k weight[k] (fp64, in index order)
 };
 
+// The binned measurement of a BSM model, one row per energy bin: {m_k[0], m_k[1], m_k[2], mh_k, k_k}, the last two the
+// constants of multi_gaussian for sigma_k (gf_internal_gauss_consts): logpdf_k = fma(mh_k, |fr_k - m_k|^2, k_k)
+#define GF_BINNED_STRIDE 5
+#define GF_BINNED_DOUBLES (GF_BINNED_STRIDE * GF_MAX_BINS)
+
 // Work queue of the unitarity arbitration (gf_unitarity.hip): the WALKERS whose verdict the fp64 estimate of the reference's
 // unitarity residual cannot settle, each with the set of its undecided energy bins.  The arbitration kernel takes a walker's
 // bins from the highest energy down and stops at the first that fails (a walker is non-unitary as soon as ONE bin is,

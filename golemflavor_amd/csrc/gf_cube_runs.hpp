@@ -17,6 +17,7 @@ struct GfCubeRuns {
     const GfCommon* commons;        // [R]
     const GfBsm* const* tbs;        // [R]
     const double* const* ptabs;     // [R]
+    const double* const* btabs;     // [R] the runs' binned measurements (gf_consts.h), NULL: the runs have none
     const uint64_t* run_ids;        // [R] Philox counter word 0
     const double* bases;            // [R][GF_MAX_DIM] values of the columns that are not scanned
     GfArbQueue* pq;                 // BSM: parked proposals, capacity = the proposals of one step
@@ -31,10 +32,12 @@ struct GfCubeRunsHost {
     gf_model** models = nullptr;        // [nruns]; models[0]'s stream carries every launch
     hipStream_t stream = nullptr;
     int device = 0, cus = 256, mode = 0;
+    int binned = 0;                     // every run's model carries a binned measurement: the kernels' MODE_BSM_BINNED instance
     int initialised = 0;
     GfCommon* d_commons = nullptr;
     const GfBsm** d_tbs = nullptr;
     const double** d_ptabs = nullptr;
+    const double** d_btabs = nullptr;
     uint64_t* d_run_ids = nullptr;
     double* d_bases = nullptr;
     GfStepState* d_state = nullptr;     // the settle kernel's step state: zeros (no stored chain)
@@ -54,17 +57,36 @@ __device__ __forceinline__ void cube_uniform2(const GfCubeRuns& a, int r, uint32
     out[1] = ((double)(q[2] >> 5) * 67108864.0 + (double)(q[3] >> 6)) * (1.0 / 9007199254740992.0);
 }
 
-// theta of cube point u for run r (as k_cube_to_theta)
+// (hi - lo) u + lo with the product and the sum each rounded, as mn.py:36 and k_cube_to_theta (gf_kernels.hip) form it: plain operators
+// under contract(off).  The HIP headers' __dmul_rn / __dadd_rn are operators that carry the contract flag of their own context, and the
+// pair below is fused into one v_fma_f64.
+__device__ __forceinline__ double cube_affine_unfused(double span, double u, double lo)
+{
+#pragma clang fp contract(off)
+    const double prod = span * u;
+    return prod + lo;
+}
+
+// theta of cube point u for run r.  UNFUSED = false, the instances that predate the binned likelihood: the product and the sum are
+// fused, so a scanned coordinate can be one ulp off the theta k_cube_to_theta and the host form from the same cube point, and a
+// stored lnprob off the bulk lnprob of that theta by about as much (a few per cent of the points, mostly one ulp); their results are
+// left as they are.  UNFUSED = true (a binned run set): theta is k_cube_to_theta's bit for bit, and with it a stored lnprob is the bulk
+// kernel's of the same cube point.
+template <bool UNFUSED = false>
 __device__ __forceinline__ void cube_to_theta(const GfCubeRuns& a, const GfCommon& c, int r, const double* u, double* row)
 {
     for (int d = 0; d < a.ndim; ++d) {
         const int sl = a.slot[d];
-        row[d] = sl >= 0 ? __dadd_rn(__dmul_rn(c.hi[d] - c.lo[d], u[sl]), c.lo[d]) : a.bases[r * GF_MAX_DIM + d];
+        if constexpr (UNFUSED)
+            row[d] = sl >= 0 ? cube_affine_unfused(c.hi[d] - c.lo[d], u[sl], c.lo[d]) : a.bases[r * GF_MAX_DIM + d];
+        else
+            row[d] = sl >= 0 ? __dadd_rn(__dmul_rn(c.hi[d] - c.lo[d], u[sl]), c.lo[d]) : a.bases[r * GF_MAX_DIM + d];
     }
 }
 
 // n cube points per run (blockIdx.y), drawn uniformly (counter (run id, it, point, pair of coordinates)) into u [R][n][nscan]
 // and mapped to theta [R][n][ndim]
+template <bool UNFUSED>
 __global__ __launch_bounds__(GF_BLOCK) void k_cube_draw(const GfCubeRuns a, uint32_t it, int n, double* u, double* theta)
 {
     const int r = blockIdx.y;
@@ -79,11 +101,11 @@ __global__ __launch_bounds__(GF_BLOCK) void k_cube_draw(const GfCubeRuns a, uint
     }
     double* dst = u + ((int64_t)r * n + i) * a.nscan;
     for (int d = 0; d < a.nscan; ++d) dst[d] = v[d];
-    cube_to_theta(a, a.commons[r], r, v, theta + ((int64_t)r * n + i) * a.ndim);
+    cube_to_theta<UNFUSED>(a, a.commons[r], r, v, theta + ((int64_t)r * n + i) * a.ndim);
 }
 
-// An evaluation kernel's instances: PRIOR_ONLY and SM_GAUSS at one lane per point, BSM at 1, 4 or 16.  `launch` is called with
-// std::integral_constant<int, MODE> and <int, LPW>.
+// An evaluation kernel's instances: PRIOR_ONLY, SM_GAUSS and BSM_BINNED at one lane per point, BSM at 1, 4 or 16.  `launch` is called
+// with std::integral_constant<int, MODE> and <int, LPW>.
 template <class Launch>
 hipError_t launch_mode_lpw(int mode, int lpw, Launch launch)
 {
@@ -91,6 +113,7 @@ hipError_t launch_mode_lpw(int mode, int lpw, Launch launch)
     switch (mode) {
     case MODE_PRIOR_ONLY: return launch(std::integral_constant<int, MODE_PRIOR_ONLY>(), std::integral_constant<int, 1>());
     case MODE_SM_GAUSS: return launch(std::integral_constant<int, MODE_SM_GAUSS>(), std::integral_constant<int, 1>());
+    case MODE_BSM_BINNED: return launch(std::integral_constant<int, MODE_BSM_BINNED>(), std::integral_constant<int, 1>());
     default:
         switch (lpw) {
         case 4: return launch(M(), std::integral_constant<int, 4>());
@@ -115,9 +138,9 @@ void cube_runs_free(GfCubeRunsHost& h, GfCubeRuns& a)
 {
     (void)hipSetDevice(h.device);
     if (h.stream) (void)hipStreamSynchronize(h.stream);
-    void* ptrs[] = {h.d_commons, (void*)h.d_tbs, (void*)h.d_ptabs, h.d_run_ids, h.d_bases, h.d_state, h.d_ctl, a.pq, a.pend_rows};
+    void* ptrs[] = {h.d_commons, (void*)h.d_tbs, (void*)h.d_ptabs, (void*)h.d_btabs, h.d_run_ids, h.d_bases, h.d_state, h.d_ctl, a.pq, a.pend_rows};
     for (void* p : ptrs) if (p) (void)hipFree(p);
-    h.d_commons = nullptr; h.d_tbs = nullptr; h.d_ptabs = nullptr; h.d_run_ids = nullptr; h.d_bases = nullptr;
+    h.d_commons = nullptr; h.d_tbs = nullptr; h.d_ptabs = nullptr; h.d_btabs = nullptr; h.d_run_ids = nullptr; h.d_bases = nullptr;
     h.d_state = nullptr; h.d_ctl = nullptr; a.pq = nullptr; a.pend_rows = nullptr;
     delete[] h.models;
     h.models = nullptr;
@@ -138,7 +161,8 @@ int cube_runs_create(GfCubeRunsHost& h, GfCubeRuns& a, gf_model* const* models, 
     }
     std::vector<GfCommon> hc(nruns);
     std::vector<const GfBsm*> htb(nruns);
-    std::vector<const double*> hpt(nruns);
+    std::vector<const double*> hpt(nruns), hbt(nruns);
+    int nbinned = 0;
     std::vector<double> hb((size_t)nruns * GF_MAX_DIM, 0.0);
     int cus = 256, nbins_max = 0;
     for (int r = 0; r < nruns; ++r) {
@@ -147,13 +171,16 @@ int cube_runs_create(GfCubeRunsHost& h, GfCubeRuns& a, gf_model* const* models, 
             c->ndim != ndim || c->mode != c0->mode)
             return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: every model must share device, ndim and mode with model 0", who);
         hc[r] = *c;
+        nbinned += gf_model_binned(models[r], &hbt[r]);
         if (nb > nbins_max) nbins_max = nb;
         for (int d = 0; d < ndim; ++d) hb[(size_t)r * GF_MAX_DIM + d] = bases[(size_t)r * ndim + d];
     }
+    if (nbinned != 0 && nbinned != nruns)
+        return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: %d of the %d models carry a binned measurement; all of a set must, or none", who, nbinned, nruns);
     h.models = new (std::nothrow) gf_model*[nruns];
     if (!h.models) return GF_ERR_ALLOC;
     for (int r = 0; r < nruns; ++r) h.models[r] = models[r];
-    h.stream = (hipStream_t)stream0; h.device = device0; h.cus = cus; h.mode = c0->mode;
+    h.stream = (hipStream_t)stream0; h.device = device0; h.cus = cus; h.mode = c0->mode; h.binned = nbinned != 0;
     a.seed = seed;
     a.nruns = nruns; a.nscan = nscan; a.ndim = ndim; a.nbins_max = nbins_max;
     for (int d = 0; d < GF_MAX_DIM; ++d) a.slot[d] = slot[d];
@@ -169,18 +196,20 @@ int cube_runs_create(GfCubeRunsHost& h, GfCubeRuns& a, gf_model* const* models, 
     al((void**)&h.d_commons, sizeof(GfCommon) * R);
     al((void**)&h.d_tbs, sizeof(void*) * R);
     al((void**)&h.d_ptabs, sizeof(void*) * R);
+    if (h.binned) al((void**)&h.d_btabs, sizeof(void*) * R);
     al((void**)&h.d_run_ids, sizeof(uint64_t) * R);
     al((void**)&h.d_bases, sizeof(double) * R * GF_MAX_DIM);
     al((void**)&h.d_state, sizeof(GfStepState));
     up(h.d_commons, hc.data(), sizeof(GfCommon) * R);
     up((void*)h.d_tbs, htb.data(), sizeof(void*) * R);
     up((void*)h.d_ptabs, hpt.data(), sizeof(void*) * R);
+    if (h.binned) up((void*)h.d_btabs, hbt.data(), sizeof(void*) * R);
     up(h.d_run_ids, ids.data(), sizeof(uint64_t) * R);
     up(h.d_bases, hb.data(), sizeof(double) * R * GF_MAX_DIM);
     up(h.d_state, &hs, sizeof(hs));
     if (e == hipSuccess) e = hipStreamSynchronize(h.stream);              // the host vectors go out of scope
     if (e != hipSuccess) { const int rc = gf_hip_fail(e, who); cube_runs_free(h, a); return rc; }
-    a.commons = h.d_commons; a.tbs = h.d_tbs; a.ptabs = h.d_ptabs; a.run_ids = h.d_run_ids; a.bases = h.d_bases;
+    a.commons = h.d_commons; a.tbs = h.d_tbs; a.ptabs = h.d_ptabs; a.btabs = h.d_btabs; a.run_ids = h.d_run_ids; a.bases = h.d_bases;
     return GF_OK;
 }
 
@@ -192,6 +221,9 @@ hipError_t cube_runs_alloc_queue(GfCubeRunsHost& h, GfCubeRuns& a, size_t w)
 }
 
 // the settle kernel's arguments common to both variants: run r is its chain r, `nwalkers` / 2 proposals each
+// the MODE of the evaluation kernels' instance: the models' mode, or MODE_BSM_BINNED for a binned set
+inline int cube_runs_eval_mode(const GfCubeRunsHost& h) { return h.binned ? MODE_BSM_BINNED : h.mode; }
+
 void cube_runs_settle_args(const GfCubeRunsHost& h, const GfCubeRuns& a, int nwalkers, GfSettleArgs& sa)
 {
     sa.state = h.d_state; sa.pq = a.pq; sa.pend_rows = a.pend_rows; sa.ctl = h.d_ctl;
@@ -214,7 +246,8 @@ int cube_runs_draw(const GfCubeRunsHost& h, const GfCubeRuns& a, uint32_t it, in
                    int32_t* status)
 {
     const dim3 grid((unsigned)((n + GF_BLOCK - 1) / GF_BLOCK), a.nruns);
-    hipLaunchKernelGGL(k_cube_draw, grid, dim3(GF_BLOCK), 0, h.stream, a, it, n, u, theta);
+    if (h.binned) hipLaunchKernelGGL(k_cube_draw<true>, grid, dim3(GF_BLOCK), 0, h.stream, a, it, n, u, theta);
+    else hipLaunchKernelGGL(k_cube_draw<false>, grid, dim3(GF_BLOCK), 0, h.stream, a, it, n, u, theta);
     GF_HIP(hipGetLastError());
     for (int r = 0; r < a.nruns; ++r) {
         const int rc = gf_model_lnprob_on(h.models[r], h.stream, theta + (size_t)r * n * a.ndim, GF_LAYOUT_AOS, n,

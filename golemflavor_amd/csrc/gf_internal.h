@@ -27,6 +27,9 @@ int gf_internal_pass_items(gf_model* m, int64_t* items);
 __attribute__((visibility("hidden"))) void gf_model_peek_stream(const gf_model* m, int* device, void** stream);
 // the constants of multi_gaussian for cov = smearing^2 I, as gf_model_create derives them: logpdf = fma(mh, |fr - bf|^2, k)
 void gf_internal_gauss_consts(double smearing, double* inv_smear, double* c0, double* mh, double* k);
+// 1 if the model carries a binned measurement (gf_model_set_binned_measurement), else 0; *d_btab <- its device table
+// [nbins][5] = {m_k[3], mh_k, k_k} (NULL without one).  The table's address does not change when the measurement is replaced.
+int gf_model_binned(gf_model* m, const double** d_btab);
 // the model's kernels on a stream of the caller's
 int gf_model_lnprob_on(gf_model* m, void* stream, const double* d_theta, int layout, int64_t n, double* d_lnprob, double* d_fr, int32_t* d_status);
 int gf_model_propagate_on(gf_model* m, void* stream, const double* d_theta, int layout, int64_t n, double* d_fr, int32_t* d_status);

@@ -38,6 +38,12 @@ hipError_t gf_launch_haar(const GfCommon& c, uint64_t seed, int64_t first, int64
 hipError_t gf_launch_bsm(const GfCommon& c, const GfCommon* d_common, const GfBsm* d_bsm, int nbins, const double* ptab, const double* theta, int layout,
                          int64_t n, int with_llh, double* lnprob, double* fr, int32_t* status, GfArbQueue* uq, int64_t uq_cap, GfUniQueue* wq, int64_t wq_cap,
                          double* t2sn, unsigned int* seen, int cus, hipStream_t s);
+// gf_binned.hip: lnprior + the energy-resolved Gaussian likelihood of a BSM model that carries a binned measurement;
+// `btab`: its device table [nbins][5] = {m_k[3], mh_k, k_k}.  `status` (may be NULL): in, the verdict the propagate launch left for
+// the same rows on `s`; out, the row's status as the flux-averaged lnprob gives it.  `fr` (may be NULL): that launch's compositions,
+// set to NaN for the rows outside the prior box
+hipError_t gf_launch_bsm_binned(const GfCommon& c, const GfCommon* d_common, const GfBsm* d_bsm, int nbins, const double* ptab, const double* btab,
+                                const double* theta, int layout, int64_t n, double* lnprob, double* fr, int32_t* status, int cus, hipStream_t s);
 // gf_unitarity.hip: settles the walkers queued by the evaluation kernels in emulated x87 arithmetic, bin by bin from the highest
 // energy down; a bin the reference would raise on turns status[walker] into NON_UNITARY and lnprob[walker] (if given) into NaN
 // and ends that walker.  `max_items` (walkers) bounds the grid; the item count itself is read on the device.  `seen` (pinned host memory, may be NULL): the item count

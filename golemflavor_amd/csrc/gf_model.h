@@ -32,6 +32,8 @@ struct gf_model {
     hipEvent_t ev_up[2] = {nullptr, nullptr}, ev_down[2] = {nullptr, nullptr};   // the chunk pipeline's slot events
     double* d_cube = nullptr;    // gf_lnprob_cube_batch: the unit-cube rows on the device
     size_t cube_cap = 0;
+    double* d_btab = nullptr;    // gf_model_set_binned_measurement: [GF_MAX_BINS][GF_BINNED_STRIDE], allocated by the first call and kept
+    int binned = 0;              // ... and from then on lnprob is the energy-resolved likelihood; c.mode stays BSM_GAUSS
     std::mutex call_mu;          // serialises the entry points that use the model's staging buffers / the stream's unitarity workspace
 };
 

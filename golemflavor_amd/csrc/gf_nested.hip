@@ -283,7 +283,10 @@ __global__ __launch_bounds__(GF_BLOCK) void k_ns_walk(const NsArgs a)
     const GfBsm* tb = a.tbs[r];
     const double* ptab = a.ptabs[r];
     double* ttab = ctab + GF_MAX_DIM * 4;
-    load_eval_tables(ctab, ptab, tb, MODE == MODE_BSM_GAUSS);
+    constexpr bool BSM = MODE == MODE_BSM_GAUSS || MODE == MODE_BSM_BINNED;
+    __shared__ __attribute__((aligned(16))) double btab[MODE == MODE_BSM_BINNED ? GF_BINNED_DOUBLES : 1];   // the run's binned measurement
+    load_eval_tables(ctab, ptab, tb, BSM);
+    if constexpr (MODE == MODE_BSM_BINNED) load_binned_table(btab, a.btabs[r], tb->nbins);
     __syncthreads();
     const int t = blockIdx.x * GF_BLOCK + threadIdx.x;
     const int k = t / LPW, sub = t % LPW;
@@ -315,12 +318,12 @@ __global__ __launch_bounds__(GF_BLOCK) void k_ns_walk(const NsArgs a)
     if (!inside) return;                                     // rejected without evaluating
     const int lane = threadIdx.x & (GF_WAVE - 1);
     double* row = tiles[threadIdx.x / GF_WAVE] + lane * GF_MAX_DIM;
-    cube_to_theta(a, c, r, u, row);
+    cube_to_theta<MODE == MODE_BSM_BINNED>(a, c, r, u, row);
     int st;
     unsigned long long pending;
-    const double lnq = proposal_lnprob<0, MODE, LPW>(c, tb, ctab, ttab, row, a.ndim, st, sub, fgrp, pending);
+    const double lnq = proposal_lnprob<0, MODE, LPW>(c, tb, ctab, ttab, row, a.ndim, st, sub, fgrp, pending, btab);
     if (LPW > 1 && sub != 0) return;                         // the group's results are identical: one writer
-    if (MODE == MODE_BSM_GAUSS && pending != 0ull) {
+    if (BSM && pending != 0ull) {
         // undecided unitarity: park; k_stretch_settle<Team9, true> settles and completes this step
         for (int d = 0; d < D; ++d) a.prop_u[w * D + d] = u[d];
         park_proposal(a.pq, a.pend_rows, w, row, a.ndim, lnq, pending);
@@ -510,7 +513,7 @@ int gf_nested_run(gf_nested* s, int64_t max_iter)
     GF_HIP(hipSetDevice(s->rs.device));
     NsArgs& a = s->a;
     if (!s->rs.initialised) { const int rc = ns_init(s); if (rc != GF_OK) return rc; }
-    const int lpw = gf_propose_lanes_per_walker(s->rs.mode, (int64_t)a.nruns * a.batch, a.nbins_max, s->rs.cus, "GF_NESTED_LPW");
+    const int lpw = gf_propose_lanes_per_walker(cube_runs_eval_mode(s->rs), (int64_t)a.nruns * a.batch, a.nbins_max, s->rs.cus, "GF_NESTED_LPW");
     constexpr int check = 4;
     std::vector<NsRun> hr(a.nruns);
     for (;;) {
@@ -528,7 +531,7 @@ int gf_nested_run(gf_nested* s, int64_t max_iter)
             GF_HIP(hipGetLastError());
             for (int step = 0; step < a.walks; ++step) {
                 a.step = step;
-                GF_HIP(launch_walk_any(s->rs.mode, lpw, a, s->rs.stream));
+                GF_HIP(launch_walk_any(cube_runs_eval_mode(s->rs), lpw, a, s->rs.stream));
                 if (s->rs.mode == MODE_BSM_GAUSS) GF_HIP(gf_launch_nested_settle(s->sa, s->rs.cus, s->rs.stream));
             }
             hipLaunchKernelGGL(k_ns_commit, dim3(a.nruns), dim3(GF_BLOCK), 0, s->rs.stream, a);

@@ -34,14 +34,31 @@ __device__ __forceinline__ void philox_block(uint32_t c0, uint32_t c1, uint32_t 
 // Such a proposal is not decided here: the half-step kernel parks it and k_stretch_settle (gf_unitarity.hip), next in stream
 // order, takes the exact (emulated x87) verdict and completes the walker's update -- so that no sample enters the chain
 // that the reference would have died on.
+// MODE_BSM_BINNED (a model with a measurement per energy bin; one lane per point only): the same prior, verdict and
+// `pending` logic around binned_llh<UNI_INLINE>, which reads the model's table from `btab` (LDS).  The other instances do not see it.
 template <int NDIM, int MODE, int LPW>
 __device__ __forceinline__ double proposal_lnprob(const GfCommon& c, const GfBsm* tb, const double* ctab,
                                                   const double* ttab, const double* row, int ndim, int& st, int sub,
-                                                  double* fgrp, unsigned long long& pending)
+                                                  double* fgrp, unsigned long long& pending, const double* btab = nullptr)
 {
     pending = 0ull;
     double val, fr[3];
-    if (MODE == MODE_BSM_GAUSS) {
+    if constexpr (MODE == MODE_BSM_BINNED) {
+        static_assert(LPW == 1, "the binned likelihood runs one lane per point");
+        double lp;
+        const bool inbox = lnprior_tab<NDIM>(ctab, row, ndim, c.prior_const, lp);
+        asm volatile("" : "+v"(lp));       // keeps the prior sum ahead of the bin loop (see k_bsm, gf_bsm.hip)
+        val = -gf_inf();
+        st = ST_OUT_OF_PRIOR;
+        if (inbox) {
+            UniAcc acc = {0.0, 0.0, 0ull, 2.0};
+            const double lnl = binned_llh<UNI_INLINE>(c, tb, ttab, btab, row, acc) + c.offset;
+            st = (acc.clear_max < tb->uni_hi) ? ST_OK : ST_NON_UNITARY;       // tiers 1 and 2 (gf_bsm_device.hpp)
+            pending = st == ST_OK ? uni_arbitration_mask(acc.amb, tb) : 0ull;
+            val = lp + lnl;
+            if (val != val && st == ST_OK) st = ST_NAN;
+        }
+    } else if (MODE == MODE_BSM_GAUSS) {
         double lp;
         const bool inbox = lnprior_tab<NDIM>(ctab, row, ndim, c.prior_const, lp);
         asm volatile("" : "+v"(lp));       // keeps the prior sum ahead of the bin loop (see k_bsm, gf_bsm.hip)

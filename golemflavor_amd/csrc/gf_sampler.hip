@@ -977,6 +977,10 @@ int sampler_create(gf_model* const* models, bool multi, int nchains, int nwalker
         if (gf_model_constants(models[ch], &cm, &htb[ch], &hpt[ch], &dev, &cus, &nbins) != GF_OK || dev != device ||
             cm->ndim != c->ndim || cm->mode != c->mode)
             return gf_fail_msg(GF_ERR_INVALID_ARG, "gf_sampler_create_multi: model %d differs from model 0 in device, ndim or mode", ch);
+        // the stretch kernels evaluate the flux-averaged likelihood: never silently for a model whose lnprob is another
+        if (gf_model_binned(models[ch], nullptr))
+            return gf_fail_msg(GF_ERR_UNSUPPORTED, "gf_sampler_create: model %d carries a binned measurement; sample the flux-averaged model and reweight "
+                               "the chain to this one", ch);
         hc[ch] = *cm;
         if (multi) keep[ch] = models[ch];
         if (ch == 0) cus0 = cus;

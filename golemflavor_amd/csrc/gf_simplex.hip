@@ -206,7 +206,10 @@ __global__ __launch_bounds__(GF_BLOCK) void k_sx_eval(const SxArgs a)
     const GfBsm* tb = a.tbs[r];
     const double* ptab = a.ptabs[r];
     double* ttab = ctab + GF_MAX_DIM * 4;
-    load_eval_tables(ctab, ptab, tb, MODE == MODE_BSM_GAUSS);
+    constexpr bool BSM = MODE == MODE_BSM_GAUSS || MODE == MODE_BSM_BINNED;
+    __shared__ __attribute__((aligned(16))) double btab[MODE == MODE_BSM_BINNED ? GF_BINNED_DOUBLES : 1];   // the run's binned measurement
+    load_eval_tables(ctab, ptab, tb, BSM);
+    if constexpr (MODE == MODE_BSM_BINNED) load_binned_table(btab, a.btabs[r], tb->nbins);
     __syncthreads();
     const int t = blockIdx.x * GF_BLOCK + threadIdx.x;
     const int k = t / LPW, sub = t % LPW;
@@ -218,12 +221,12 @@ __global__ __launch_bounds__(GF_BLOCK) void k_sx_eval(const SxArgs a)
     const int64_t w = s * a.Q + p;
     const int lane = threadIdx.x & (GF_WAVE - 1);
     double* row = tiles[threadIdx.x / GF_WAVE] + lane * GF_MAX_DIM;
-    cube_to_theta(a, c, r, a.pts + w * a.nscan, row);
+    cube_to_theta<MODE == MODE_BSM_BINNED>(a, c, r, a.pts + w * a.nscan, row);
     int status;
     unsigned long long pending;
-    const double lnq = proposal_lnprob<0, MODE, LPW>(c, tb, ctab, ttab, row, a.ndim, status, sub, fgrp, pending);
+    const double lnq = proposal_lnprob<0, MODE, LPW>(c, tb, ctab, ttab, row, a.ndim, status, sub, fgrp, pending, btab);
     if (LPW > 1 && sub != 0) return;                         // the group's results are identical: one writer
-    if (MODE == MODE_BSM_GAUSS && pending != 0ull) {
+    if (BSM && pending != 0ull) {
         // undecided unitarity: park; k_stretch_settle<Team9, false, true> writes lnq and the verdict
         a.pst[w] = SX_PARKED;
         atomicAdd(&a.runs[r].parked, 1u);
@@ -556,7 +559,7 @@ int gf_simplex_run(gf_simplex* s, int64_t max_rounds)
         if (rc != GF_OK) return rc;
     }
     if (a.S == 0) return GF_OK;
-    const int lpw = gf_propose_lanes_per_walker(s->rs.mode, (int64_t)a.nruns * a.S * a.Q, a.nbins_max, s->rs.cus, "GF_SIMPLEX_LPW");
+    const int lpw = gf_propose_lanes_per_walker(cube_runs_eval_mode(s->rs), (int64_t)a.nruns * a.S * a.Q, a.nbins_max, s->rs.cus, "GF_SIMPLEX_LPW");
     constexpr int check = 4;
     std::vector<SxRun> hr(a.nruns);
     const dim3 sgrid((unsigned)((a.S + SX_STEP_BLOCK - 1) / SX_STEP_BLOCK), a.nruns);
@@ -569,7 +572,7 @@ int gf_simplex_run(gf_simplex* s, int64_t max_rounds)
         if (all) break;
         if (done_here >= max_rounds) return GF_OK;                      // stepping: the caller asked for this many rounds
         for (int i = 0; i < check && done_here < max_rounds; ++i, ++done_here) {
-            GF_HIP(launch_eval_any(s->rs.mode, lpw, a, s->rs.stream));
+            GF_HIP(launch_eval_any(cube_runs_eval_mode(s->rs), lpw, a, s->rs.stream));
             if (s->rs.mode == MODE_BSM_GAUSS) GF_HIP(gf_launch_simplex_settle(s->sa, s->rs.cus, s->rs.stream));
             hipLaunchKernelGGL(k_sx_step, sgrid, dim3(SX_STEP_BLOCK), 0, s->rs.stream, a);
             GF_HIP(hipGetLastError());

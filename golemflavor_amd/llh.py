@@ -17,7 +17,74 @@ from .enums import ParamTag, Texture
 from .model import Model
 
 __all__ = ["LnProb", "CubeLnProb", "notebook_ln_prob", "tutorial_ln_prob", "bsm_ln_prob", "prior_ln_prob", "lnprior",
-           "ln_prob", "triangle_llh", "multi_gaussian"]
+           "ln_prob", "triangle_llh", "multi_gaussian", "BinnedMeasurement", "equal_information_smearing"]
+
+
+def equal_information_smearing(smearing, binning):
+    """The per-bin widths that make the energy-resolved likelihood comparable with the flux-averaged one of width `smearing`:
+    sigma_k = smearing / sqrt(w_k) with w_k = width_k / (E_max - E_min), the flux average's own weight of bin k (`binning`: the bin
+    edges).  Then sum_k w_k^2 sigma_k^2 = smearing^2: the flux-weighted mean of the per-bin measurements has exactly the width the
+    flux-averaged likelihood assumes."""
+    if not float(smearing) > 0.0 or not np.isfinite(float(smearing)):
+        raise ValueError("smearing must be positive and finite")
+    b = np.asarray(binning, dtype=np.float64)
+    if b.ndim != 1 or len(b) < 2 or not np.all(np.isfinite(b)):
+        raise ValueError("binning must be a 1-D array of at least two finite bin edges")
+    widths = np.abs(np.diff(b))
+    if not np.all(widths > 0.0):
+        raise ValueError("every energy bin needs a positive width")
+    w = widths / np.abs(b[-1] - b[0])
+    return float(smearing) / np.sqrt(w)
+
+
+class BinnedMeasurement:
+    """A measurement per energy bin for the energy-resolved Gaussian likelihood: `fr_bins` (K, 3) the measured
+    composition m_k of every bin, `sigma` (K,) its width.  `smearing`: K values are the widths themselves; ONE value is the width
+    of the flux-averaged likelihood this one is to be comparable with and needs `binning` (the K + 1 bin edges of the model):
+    sigma_k = `equal_information_smearing(smearing, binning)`.  ValueError on a wrong shape, a non-finite composition, a width that
+    is not positive or a number of smearings that is neither 1 nor K."""
+
+    def __init__(self, fr_bins, smearing, binning=None):
+        f = np.array(fr_bins, dtype=np.float64)
+        if f.ndim != 2 or f.shape[1] != 3 or f.shape[0] < 1:
+            raise ValueError("fr_bins has shape (K, 3): one composition per energy bin")
+        if f.shape[0] > _lib.GF_MAX_BINS:
+            raise ValueError("at most %d energy bins" % _lib.GF_MAX_BINS)
+        if not np.all(np.isfinite(f)):
+            raise ValueError("the measured compositions must be finite")
+        K = f.shape[0]
+        edges = None
+        if binning is not None:
+            edges = np.asarray(binning, dtype=np.float64)
+            if edges.ndim != 1 or len(edges) != K + 1:
+                raise ValueError("%d compositions for a binning of %d bins" % (K, max(len(np.atleast_1d(edges)) - 1, 0)))
+        sm = np.atleast_1d(np.asarray(smearing, dtype=np.float64))
+        if sm.ndim != 1 or (len(sm) != 1 and len(sm) != K):
+            raise ValueError("smearing takes one value (the equal-information rule) or one per energy bin (%d), got %d" % (K, sm.size))
+        if not np.all(np.isfinite(sm)) or not np.all(sm > 0.0):
+            raise ValueError("every smearing must be positive and finite")
+        if len(sm) == 1 and (K > 1 or edges is not None):
+            if edges is None:
+                raise ValueError("one smearing for %d bins needs the binning: sigma_k = smearing / sqrt(w_k)" % K)
+            sigma = equal_information_smearing(float(sm[0]), edges)
+        else:
+            sigma = sm.copy()
+        self.fr_bins = np.ascontiguousarray(f)
+        self.sigma = np.ascontiguousarray(sigma, dtype=np.float64)
+        self.binning = edges
+
+    @property
+    def nbins(self):
+        return self.fr_bins.shape[0]
+
+    @classmethod
+    def constant(cls, fr, smearing, binning):
+        """The same composition `fr` in every bin of `binning` (what a source without new physics gives)."""
+        b = np.asarray(binning, dtype=np.float64)
+        return cls(np.tile(np.asarray(fr, dtype=np.float64).reshape(1, 3), (len(b) - 1, 1)), smearing, binning=b)
+
+    def __repr__(self):
+        return "BinnedMeasurement(nbins=%d)" % self.nbins
 
 
 class LnProb:
@@ -75,17 +142,26 @@ def tutorial_ln_prob(asimov_paramset, llh_paramset, device=0):
     return LnProb(desc, device=device)
 
 
-def bsm_ln_prob(args, asimov_paramset, llh_paramset, smearing=0.02, device=0, **kw):
+def bsm_ln_prob(args, asimov_paramset, llh_paramset, smearing=0.02, device=0, binned=None, **kw):
     """golemflavor/llh.py:121-130 `ln_prob(theta, args, asimov_paramset, llh_paramset)` with the
     GolemFit likelihood replaced by the Gaussian substitute the README sanctions
     (README.md:70-74): multi_gaussian(measured, angles_to_fr(asimov BESTFIT angles), smearing).
     `args` needs: source_ratio, dimension, texture, binning (edges); `args.no_bsm` (fr.py:437-438) is honoured:
-    the posterior is then lnprior + the Gaussian around u_to_fr(source_ratio, sm_u) (descriptor.compile_model)."""
+    the posterior is then lnprior + the Gaussian around u_to_fr(source_ratio, sm_u) (descriptor.compile_model).
+    `binned` (a `BinnedMeasurement`): the posterior is the energy-resolved one, lnprior + the sum over the energy
+    bins of multi_gaussian(composition at the bin, m_k, sigma_k); the flux-averaged bestfit and `smearing` are then not read."""
     bf = fr_utils.angles_to_fr(asimov_paramset.from_tag(ParamTag.BESTFIT, values=True))
     desc = compile_model(llh_paramset, "BSM_GAUSS", bestfit_fr=bf, smearing=smearing,
                          source_ratio=args.source_ratio, texture=args.texture,
                          dimension=args.dimension, binning=args.binning, no_bsm=bool(getattr(args, "no_bsm", False)))
-    return LnProb(desc, device=device, **kw)
+    f = LnProb(desc, device=device, **kw)
+    if binned is not None:
+        try:
+            f.model.set_binned_measurement(binned)
+        except BaseException:
+            f.close()
+            raise
+    return f
 
 
 def prior_ln_prob(llh_paramset, device=0, flat_llh=1.0):

@@ -222,6 +222,26 @@ class Model:
         """Energy bins of a BSM model, 0 for the other modes."""
         return int(self._L.gf_model_nbins(self._h))
 
+    def set_binned_measurement(self, meas):
+        """Attach a measurement per energy bin (`llh.BinnedMeasurement`, or anything with fr_bins (K, 3) and sigma (K,)): from now on
+        every lnprob of this model -- lnprob, lnprob_cube, lnprob_device, a nested run, a profile scan, a reweight target -- is the
+        energy-resolved Gaussian likelihood.  propagate, propagate_bins and the status are unchanged.  It can be
+        replaced, not removed.  A model without energy bins, or K != nbins: GolemHipError (GF_ERR_UNSUPPORTED / GF_ERR_INVALID_ARG),
+        the model unchanged.  The device ensemble sampler refuses such a model: reweight its chain to it."""
+        f = np.ascontiguousarray(meas.fr_bins, dtype=np.float64)
+        sg = np.ascontiguousarray(meas.sigma, dtype=np.float64)
+        if f.ndim != 2 or f.shape[1] != 3 or sg.shape != (f.shape[0],):
+            raise ValueError("a binned measurement has fr_bins (K, 3) and sigma (K,)")
+        check(self._L.gf_model_set_binned_measurement(self._h, int(f.shape[0]), f.ctypes.data_as(_lib._dp), sg.ctypes.data_as(_lib._dp)),
+              "gf_model_set_binned_measurement")
+        self.binned = meas
+        return self
+
+    @property
+    def is_binned(self):
+        """True once a binned measurement is attached."""
+        return int(self._L.gf_model_is_binned(self._h)) == 1
+
     def propagate_bins(self, theta, want_status=True):
         """theta (n, ndim) -> the composition at every energy bin (n, nbins, 3) [, status (n,)]: the terms flux_averaged_BSMu
         (fr.py:441-457) averages, at the bin centres `spectrum.bin_tables(spectrum.model_edges(self))[0]`.  The status is

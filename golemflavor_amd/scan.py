@@ -487,6 +487,42 @@ class ReweightWriter(PointWriter):
         return {"targets": len(self.targets), **timing, "rows": self.nrows, "targets_without_posterior": self.without_posterior}
 
 
+class BinnedReweightWriter(PointWriter):
+    """--reweight-binned FILE.npy: every grid point's chain reweighted to its own model with a measurement per energy bin (the
+    energy-resolved likelihood; a model target of `DeviceEnsembleSampler.reweight`), saved as
+    reweight_binned_<point file name>.npz: the summary (ess, lnz_ratio, mean, cov), the counts and the target (target_fr_bins,
+    target_sigma).  One smearing -- the point's own unless given -- means the equal-information rule."""
+    key = "reweight_binned"
+
+    def __init__(self, datadir, name_of, fr_bins, smearing=None):
+        super().__init__(datadir, name_of)
+        self.fr_bins, self.smearing, self.without_posterior = np.asarray(fr_bins, dtype=np.float64), smearing, 0
+
+    def write(self, sampler, models, order):
+        from . import spectrum
+        from .llh import BinnedMeasurement
+        own = sampler.models if sampler.models is not None else [sampler.model] * sampler.nchains
+        targets, meas = [], []
+        try:
+            for m in own:
+                sm = self.smearing if self.smearing is not None else float(m.desc.smearing)
+                meas.append(BinnedMeasurement(self.fr_bins, sm, binning=spectrum.model_edges(m)))
+                targets.append(Model(m.desc, device=m.device))
+                targets[-1].set_binned_measurement(meas[-1])
+            r = sampler.reweight([[t] for t in targets], on_nonunitary="-inf")
+            summ = dict(r._summary, target_fr_bins=np.stack([x.fr_bins for x in meas]), target_sigma=np.stack([x.sigma for x in meas]))
+        finally:
+            for t in targets:
+                t.close()
+        for k, (g, _) in enumerate(self.each(None, order)):
+            with open(self.file("reweight_binned", g), "wb") as f:
+                np.savez(f, **{name: v[k] for name, v in summ.items()})
+            self.without_posterior += int(np.count_nonzero(summ["ess"][k] == 0.0))
+
+    def _stats(self, **timing):
+        return {"energy_bins": int(self.fr_bins.shape[0]), **timing, "targets_without_posterior": self.without_posterior}
+
+
 def _post_models(jobs, order):
     first = jobs[order[0]]
     return [jobs[g].post_model for g in order] if getattr(first, "post_model", None) is not None else None
@@ -922,6 +958,10 @@ def main(argv=None):
                          "--datadir and chains sampled under a measurement (--config C5)")
     ap.add_argument("--reweight-smearing", type=float, nargs="+", default=None, metavar="S",
                     help="with --reweight-injected: the targets are every (injected, smearing) pair; default: the scan's own smearing")
+    ap.add_argument("--reweight-binned", type=str, default=None, metavar="FILE.npy",
+                    help="also reweight every grid point's chain to its own model with a measurement per energy bin (FILE.npy: [K, 3], "
+                         "the energy-resolved likelihood; widths by the equal-information rule from --reweight-smearing's single value or "
+                         "the scan's own smearing): reweight_binned_<point>.npz beside the chain file; needs --datadir and --config C5")
     ap.add_argument("--reweight-rows", type=int, default=None, metavar="N",
                     help="with --reweight-injected: also save the marginals of N equal-weight rows per target, with --marginals' bins, "
                          "coverages and percentiles and, as --marginals for this configuration, over the sampled columns alone (the rows "
@@ -970,8 +1010,20 @@ def main(argv=None):
             ap.error(str(exc))
         if a.reweight_rows is not None and a.reweight_rows < 1:
             ap.error("--reweight-rows must be at least 1")
-    elif a.reweight_smearing is not None or a.reweight_rows is not None:
+    elif a.reweight_rows is not None or (a.reweight_smearing is not None and a.reweight_binned is None):
         ap.error("--reweight-smearing and --reweight-rows need --reweight-injected")
+    rw_binned = None
+    if a.reweight_binned is not None:
+        if not a.datadir or a.config != "C5":
+            ap.error("--reweight-binned needs --datadir and chains sampled under a measurement (--config C5)")
+        if a.reweight_smearing is not None and a.reweight_injected is None and len(a.reweight_smearing) != 1:
+            ap.error("--reweight-binned takes one --reweight-smearing value (the equal-information rule)")
+        try:
+            rw_binned = np.load(a.reweight_binned)
+            if rw_binned.ndim != 2 or rw_binned.shape[1] != 3 or not np.all(np.isfinite(rw_binned)):
+                raise ValueError("%s does not hold a finite [K, 3] array" % a.reweight_binned)
+        except (OSError, ValueError) as exc:
+            ap.error(str(exc))
     if a.regions is not None:
         if not a.datadir:
             ap.error("--regions needs --datadir (the regions are saved beside the chain files)")
@@ -1036,6 +1088,9 @@ def main(argv=None):
         writers.append(SpectrumWriter(a.datadir, name_of, a.spectrum, a.spectrum_bins))
     if rw_targets is not None:
         writers.append(ReweightWriter(a.datadir, name_of, rw_targets, a.reweight_rows, marginal_kw))
+    if rw_binned is not None:
+        one = a.reweight_smearing[0] if a.reweight_smearing is not None and len(a.reweight_smearing) == 1 else None
+        writers.append(BinnedReweightWriter(a.datadir, name_of, rw_binned, smearing=one))
     if a.datadir and not want_gather:
         local = run_points(pts, mine, make, a.burnin, a.nsteps, stacked=stacked, writers=writers)
         gather_name = "none: every rank saved its own files (--datadir)"

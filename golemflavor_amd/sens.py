@@ -6,7 +6,9 @@ README.md:70-74), same scale list ([-100] + linspace over SCALE_BOUNDARIES[d] in
 same two output arrays, {datadir}/{stat_method}/{data}/fr_stat{identifier}.npy and fr_maxllh{identifier}.npy of shape
 (segments, 2) -- (1, 2) with --eval-segment, whose files carry `_scale_{10^scale:.0E}` (sens.py:232-258).  All scales run in
 one device call.  Prints one JSON summary line.  --posterior also writes every scale's posterior summary and marginals,
-posterior_<identifier>_scale_<10^scale:.0E>.npz beside the arrays (INTEGRATION.md has the layout).  The frequentist arrays hold [scale, profile max lnL] in both files: the
+posterior_<identifier>_scale_<10^scale:.0E>.npz beside the arrays (INTEGRATION.md has the layout).  --energy-resolved (or
+--binned-measurement FILE.npy, --binned-smearing) fits the composition of every energy bin instead of the flux average; every
+file name then carries `_ebins` behind the identifier.  The frequentist arrays hold [scale, profile max lnL] in both files: the
 statistic golemflavor/plot.py:605-608 (plot_statistic) receives.
 """
 import argparse
@@ -20,7 +22,8 @@ from . import configs as Cf
 from . import fr as fr_utils
 from . import nested
 from . import profile_llh
-from .enums import DataType, StatCateg, Texture
+from .enums import DataType, ParamTag, StatCateg, Texture
+from .llh import BinnedMeasurement
 from .mcmc import chain_identifier
 
 
@@ -80,7 +83,23 @@ def parse_args(argv=None):
     ap.add_argument("--posterior-spectrum", type=float, nargs="*", default=None, metavar="Q",
                     help="with --posterior: also save every scale's composition per energy bin (mean, covariance, percentiles Q -- "
                          "default 5 16 50 84 95 -- and histograms of the equal-weight rows), posterior_spectrum_<...>.npz")
+    ap.add_argument("--energy-resolved", action="store_true",
+                    help="fit the composition of every energy bin (the energy-resolved Gaussian likelihood) instead of the flux "
+                         "average: the measurement of every bin is the injected ratio, the null truth; the output files carry _ebins")
+    ap.add_argument("--binned-measurement", type=str, default=None, metavar="FILE.npy",
+                    help="energy-resolved with this measurement: an array [K, 3], one composition per energy bin of --binning")
+    ap.add_argument("--binned-smearing", type=float, nargs="+", default=None, metavar="S",
+                    help="energy-resolved: ONE value is the width of the flux-averaged likelihood to be comparable with, "
+                         "sigma_k = S / sqrt(w_k) (default: --smearing); K values are the widths of the bins themselves")
     args = ap.parse_args(argv)
+    if args.binned_measurement is not None:
+        args.energy_resolved = True
+    if args.binned_smearing is not None:
+        if not args.energy_resolved:
+            ap.error("--binned-smearing needs --energy-resolved or --binned-measurement")
+        K = int(args.binning[2])
+        if len(args.binned_smearing) not in (1, K) or not all(s > 0. for s in args.binned_smearing):
+            ap.error("--binned-smearing takes one positive value or one per energy bin (%d)" % K)
     if args.posterior_elements and not args.posterior:
         ap.error("--posterior-elements needs --posterior (it adds the element-space marginals to it)")
     if args.posterior_spectrum is not None:
@@ -108,10 +127,30 @@ def parse_args(argv=None):
     return args
 
 
+def identifier(args):
+    """The reference's file-name stem (`chain_identifier`); `_ebins` appended for the energy-resolved likelihood, whose results never
+    overwrite the flux-averaged ones."""
+    return chain_identifier(args) + ("_ebins" if getattr(args, "energy_resolved", False) else "")
+
+
+def binned_measurement(args, asimov_paramset):
+    """The `BinnedMeasurement` of --energy-resolved / --binned-measurement / --binned-smearing, None without them.  Without a file the
+    measurement of every bin is the composition the flux-averaged likelihood is centred on (the injected ratio: the null truth)."""
+    if not getattr(args, "energy_resolved", False):
+        return None
+    edges = np.asarray(args.binning, dtype=np.float64)
+    sm = args.binned_smearing if getattr(args, "binned_smearing", None) is not None else [args.smearing]
+    sm = sm[0] if len(sm) == 1 else sm
+    if getattr(args, "binned_measurement", None) is not None:
+        return BinnedMeasurement(np.load(args.binned_measurement), sm, binning=edges)
+    bf = fr_utils.angles_to_fr(asimov_paramset.from_tag(ParamTag.BESTFIT, values=True))
+    return BinnedMeasurement.constant(bf, sm, edges)
+
+
 def output_paths(args, scales=None):
     """sens.py:235-240, 247-250: (fr_stat, fr_maxllh) file names without '.npy'."""
     base = os.path.join(args.datadir, args.stat_method.name.lower(), args.data.name.lower())
-    ident = chain_identifier(args)
+    ident = identifier(args)
     stat, llh = os.path.join(base, "fr_stat" + ident), os.path.join(base, "fr_maxllh" + ident)
     if args.eval_segment is not None:
         sc = (scales if scales is not None else nested.sens_scales(args.dimension, args.segments))[args.eval_segment]
@@ -123,14 +162,14 @@ def output_paths(args, scales=None):
 def posterior_path(args, scale, elements=False):
     """posterior[_elements]<identifier>_scale_<10^scale:.0E>.npz beside fr_stat<identifier>.npy."""
     base = os.path.join(args.datadir, args.stat_method.name.lower(), args.data.name.lower())
-    return os.path.join(base, "posterior{0}{1}_scale_{2:.0E}.npz".format("_elements" if elements else "", chain_identifier(args),
+    return os.path.join(base, "posterior{0}{1}_scale_{2:.0E}.npz".format("_elements" if elements else "", identifier(args),
                                                                        np.power(10., scale)))
 
 
 def spectrum_path(args, scale):
     """posterior_spectrum<identifier>_scale_<10^scale:.0E>.npz beside the posterior files."""
     base = os.path.join(args.datadir, args.stat_method.name.lower(), args.data.name.lower())
-    return os.path.join(base, "posterior_spectrum{0}_scale_{1:.0E}.npz".format(chain_identifier(args), np.power(10., scale)))
+    return os.path.join(base, "posterior_spectrum{0}_scale_{1:.0E}.npz".format(identifier(args), np.power(10., scale)))
 
 
 def save_spectra(args, scales, res):
@@ -175,13 +214,18 @@ def main(argv=None):
             return 0
     idx = np.arange(len(scales)) if args.eval_segment is None else np.array([args.eval_segment])
     asimov, llh_ps = Cf.sens_paramsets(args.dimension, args.injected_ratio, data=args.data)
+    try:
+        binned = binned_measurement(args, asimov)
+    except ValueError as exc:
+        print("golemflavor_amd.sens: %s" % exc, file=sys.stderr)
+        return 2
     if args.stat_method is StatCateg.FREQUENTIST:
-        return _frequentist(args, scales, idx, asimov, llh_ps, outfile, outfile_llh)
+        return _frequentist(args, scales, idx, asimov, llh_ps, outfile, outfile_llh, binned)
     post = dict(nrows=args.posterior_rows, elements=args.posterior_elements) if args.posterior else None
     if post is not None and args.posterior_spectrum is not None:
         post["spectrum"] = args.posterior_spectrum
     res = nested.evidence_scan(args, asimov, llh_ps, scales[idx], run_ids=idx, on_nonunitary=args.on_nonunitary,
-                               device=args.device, posterior=post)
+                               device=args.device, posterior=post, binned=binned)
     evidence_arr = np.stack([scales[idx], res["lnz"]], axis=1)
     maxllh_arr = np.stack([scales[idx], res["max_lnl"]], axis=1)
     for f, arr in ((outfile, evidence_arr), (outfile_llh, maxllh_arr)):
@@ -192,6 +236,7 @@ def main(argv=None):
         posterior_files += save_spectra(args, scales[idx], res)
     print(json.dumps({
         **({"posterior": posterior_files} if posterior_files is not None else {}),
+        **({"likelihood": "energy-resolved"} if binned is not None else {}),
         "tool": "golemflavor_amd.sens", "dimension": args.dimension, "texture": args.texture.name,
         "segments": args.segments, "nlive": args.mn_live_points, "scales": scales[idx].tolist(),
         "lnz": res["lnz"].tolist(), "lnz_err": res["lnz_err"].tolist(), "max_lnl": res["max_lnl"].tolist(),
@@ -201,9 +246,9 @@ def main(argv=None):
     return 0
 
 
-def _frequentist(args, scales, idx, asimov, llh_ps, outfile, outfile_llh):
+def _frequentist(args, scales, idx, asimov, llh_ps, outfile, outfile_llh, binned=None):
     res = profile_llh.profile_scan(args, asimov, llh_ps, scales[idx], run_ids=idx, on_nonunitary=args.on_nonunitary,
-                                   device=args.device)
+                                   device=args.device, binned=binned)
     arr = np.stack([scales[idx], res["max_lnl"]], axis=1)
     for f in (outfile, outfile_llh):
         os.makedirs(os.path.dirname(f) or ".", exist_ok=True)
@@ -213,6 +258,7 @@ def _frequentist(args, scales, idx, asimov, llh_ps, outfile, outfile_llh):
     ts = (-2 * (ml - ml[null[0]])).tolist() if len(null) and np.isfinite(ml[null[0]]) else None
     limit = profile_llh.profile_likelihood_limit(scales[idx], ml) if args.eval_segment is None else None
     print(json.dumps({
+        **({"likelihood": "energy-resolved"} if binned is not None else {}),
         "tool": "golemflavor_amd.sens", "stat_method": "FREQUENTIST", "dimension": args.dimension,
         "texture": args.texture.name, "segments": args.segments, "scales": scales[idx].tolist(), "max_lnl": ml.tolist(),
         "ts": ts, "limit": None if limit is None else float(limit), "starts": res["nstarts"].tolist(),

@@ -649,6 +649,22 @@ int gf_sampler_spectrum(gf_sampler* s, gf_model* const* models, const gf_spectru
  * has nvalid 0 and NaN moments */
 int gf_nested_spectrum(gf_nested* s, int64_t nrows, const gf_spectrum_spec* spec, const gf_spectrum_out* out);
 
+/* ---- the energy-resolved Gaussian likelihood: a measurement per energy bin (this package's own definition) ------------- */
+/* A GF_MODE_BSM_GAUSS model with K = gf_model_nbins(m) energy bins takes a composition m_k[3] and a width sigma_k > 0 per bin.  From
+ * then on every lnprob the model gives -- gf_lnprob_batch[_device], gf_lnprob_cube_batch, the nested sampler, the maximiser, a model
+ * target of gf_sampler_reweight* -- is
+ *     lnprior + offset + sum_{k = 0..K-1} multi_gaussian(fr_k(theta), m_k, sigma_k, offset = 0),
+ * fr_k being bin k of gf_propagate_bins, each term the reference's multi_gaussian (llh.py:32-54) with its underflow wall, the terms
+ * added in ascending k from 0.0; one bin at -inf makes the sum -inf.  The status of a row, and the value of a row the reference would
+ * have raised on, are those of the same model without the measurement.  Propagation, the spectrum and post-processing are unchanged
+ * (the mode stays GF_MODE_BSM_GAUSS, bestfit_fr and smearing stay in the model and are not read by lnprob).
+ * fr_bins [nbins][3] finite, sigma [nbins] > 0 and finite, nbins == gf_model_nbins(m): else GF_ERR_INVALID_ARG; a model of another
+ * mode: GF_ERR_UNSUPPORTED; either way the model is unchanged.  A measurement can be replaced (no launch of the model may be in flight
+ * on a stream other than its own) but not removed.  gf_sampler_create[_multi] refuses such a model (GF_ERR_UNSUPPORTED): the ensemble
+ * sampler's posterior under this likelihood is reached by reweighting its chain to the model. */
+int gf_model_set_binned_measurement(gf_model* m, int nbins, const double* fr_bins, const double* sigma);
+int gf_model_is_binned(const gf_model* m);   /* 1 with a binned measurement, 0 without, -1 for NULL */
+
 /* ---- every stored chain reweighted to other targets (csrc/gf_reweight.hpp holds the rules for lnw) ------------------- */
 /* Chain c's rows are its stored samples in the device's order, i = step * nwalkers + walker, n = nstored * nwalkers (NOT emcee's
  * walker-major flatchain; every index below refers to this order), l0_i their stored ln_prob.  Every chain has ntargets targets t.
