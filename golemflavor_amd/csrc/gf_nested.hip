@@ -513,7 +513,7 @@ int gf_nested_run(gf_nested* s, int64_t max_iter)
     GF_HIP(hipSetDevice(s->rs.device));
     NsArgs& a = s->a;
     if (!s->rs.initialised) { const int rc = ns_init(s); if (rc != GF_OK) return rc; }
-    const int lpw = gf_propose_lanes_per_walker(cube_runs_eval_mode(s->rs), (int64_t)a.nruns * a.batch, a.nbins_max, s->rs.cus, "GF_NESTED_LPW");
+    const int lpw = lanes_per_walker(cube_runs_eval_mode(s->rs), (int64_t)a.nruns * a.batch, a.nbins_max, s->rs.cus, {false, 32 * 1024, "GF_NESTED_LPW"});
     constexpr int check = 4;
     std::vector<NsRun> hr(a.nruns);
     for (;;) {

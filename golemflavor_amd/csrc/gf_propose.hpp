@@ -1,7 +1,6 @@
 // Device pieces shared by the ensemble sampler (gf_sampler.hip), the nested sampler (gf_nested.hip) and the maximiser
 // (gf_simplex.hip): the Philox4x32-10 block behind the random streams, the evaluation of one proposal with its unitarity verdict,
-// the parking of an undecided one (the nested sampler and the maximiser; stretch_body keeps its own copy, which also writes the
-// acceptance threshold), and the lanes-per-walker rule of the nested sampler's and the maximiser's evaluation kernels.
+// the parking of an undecided one, and the lanes-per-walker rule of their evaluation kernels.
 #pragma once
 #include <cstdlib>
 
@@ -34,8 +33,8 @@ __device__ __forceinline__ void philox_block(uint32_t c0, uint32_t c1, uint32_t 
 // Such a proposal is not decided here: the half-step kernel parks it and k_stretch_settle (gf_unitarity.hip), next in stream
 // order, takes the exact (emulated x87) verdict and completes the walker's update -- so that no sample enters the chain
 // that the reference would have died on.
-// MODE_BSM_BINNED (a model with a measurement per energy bin; one lane per point only): the same prior, verdict and
-// `pending` logic around binned_llh<UNI_INLINE>, which reads the model's table from `btab` (LDS).  The other instances do not see it.
+// MODE_BSM_BINNED (a model with a measurement per energy bin; one lane per point only): the same body around
+// binned_llh<UNI_INLINE>, which reads the model's table from `btab` (LDS).  The other instances do not see it.
 template <int NDIM, int MODE, int LPW>
 __device__ __forceinline__ double proposal_lnprob(const GfCommon& c, const GfBsm* tb, const double* ctab,
                                                   const double* ttab, const double* row, int ndim, int& st, int sub,
@@ -43,8 +42,8 @@ __device__ __forceinline__ double proposal_lnprob(const GfCommon& c, const GfBsm
 {
     pending = 0ull;
     double val, fr[3];
-    if constexpr (MODE == MODE_BSM_BINNED) {
-        static_assert(LPW == 1, "the binned likelihood runs one lane per point");
+    if constexpr (MODE == MODE_BSM_BINNED || MODE == MODE_BSM_GAUSS) {
+        static_assert(MODE != MODE_BSM_BINNED || LPW == 1, "the binned likelihood runs one lane per point");
         double lp;
         const bool inbox = lnprior_tab<NDIM>(ctab, row, ndim, c.prior_const, lp);
         asm volatile("" : "+v"(lp));       // keeps the prior sum ahead of the bin loop (see k_bsm, gf_bsm.hip)
@@ -52,24 +51,15 @@ __device__ __forceinline__ double proposal_lnprob(const GfCommon& c, const GfBsm
         st = ST_OUT_OF_PRIOR;
         if (inbox) {
             UniAcc acc = {0.0, 0.0, 0ull, 2.0};
-            const double lnl = binned_llh<UNI_INLINE>(c, tb, ttab, btab, row, acc) + c.offset;
+            // the two BSM instances differ in the likelihood alone; gauss_llh stays behind the verdict lines, where the flux-averaged
+            // instance has always had it (moved ahead of them it changes the instances' code)
+            double lnl = 0.0;
+            if constexpr (MODE == MODE_BSM_BINNED) lnl = binned_llh<UNI_INLINE>(c, tb, ttab, btab, row, acc) + c.offset;
+            else flux_average<UNI_INLINE, LPW>(c, tb, ttab, row, fr, acc, sub, fgrp);
             st = (acc.clear_max < tb->uni_hi) ? ST_OK : ST_NON_UNITARY;       // tiers 1 and 2 (gf_bsm_device.hpp)
             pending = st == ST_OK ? uni_arbitration_mask(acc.amb, tb) : 0ull;
+            if constexpr (MODE != MODE_BSM_BINNED) lnl = gauss_llh(c, fr);
             val = lp + lnl;
-            if (val != val && st == ST_OK) st = ST_NAN;
-        }
-    } else if (MODE == MODE_BSM_GAUSS) {
-        double lp;
-        const bool inbox = lnprior_tab<NDIM>(ctab, row, ndim, c.prior_const, lp);
-        asm volatile("" : "+v"(lp));       // keeps the prior sum ahead of the bin loop (see k_bsm, gf_bsm.hip)
-        val = -gf_inf();
-        st = ST_OUT_OF_PRIOR;
-        if (inbox) {
-            UniAcc acc = {0.0, 0.0, 0ull, 2.0};
-            flux_average<UNI_INLINE, LPW>(c, tb, ttab, row, fr, acc, sub, fgrp);
-            st = (acc.clear_max < tb->uni_hi) ? ST_OK : ST_NON_UNITARY;       // tiers 1 and 2 (gf_bsm_device.hpp)
-            pending = st == ST_OK ? uni_arbitration_mask(acc.amb, tb) : 0ull;
-            val = lp + gauss_llh(c, fr);
             if (val != val && st == ST_OK) st = ST_NAN;
         }
     } else {
@@ -78,14 +68,23 @@ __device__ __forceinline__ double proposal_lnprob(const GfCommon& c, const GfBsm
     return val;
 }
 
-// Parks a proposal whose unitarity verdict the in-kernel tiers cannot settle: theta and its lnprob go to row t of `pend_rows`,
-// {t, undecided bins} onto `pq`, for the settle kernel next in stream order
+// A parked proposal's row: theta [GF_MAX_DIM] | lnprob | ln(z^(ndim-1) / u3) (GF_PEND_STRIDE, gf_launch.h).  Writes theta.
+__device__ __forceinline__ void park_row(double* dst, const double* row, int ndim)
+{
+    for (int d = 0; d < ndim; ++d) dst[d] = row[d];
+}
+
+// Parks a proposal whose unitarity verdict the in-kernel tiers cannot settle: theta, its lnprob and -- the stretch move, whose settle
+// step takes the accept test -- the test's left side `lhs` go to row t of `pend_rows`, {t, undecided bins} onto `pq`, for the
+// settle kernel next in stream order
+template <bool WITH_LHS = false>
 __device__ __forceinline__ void park_proposal(GfArbQueue* pq, double* pend_rows, int64_t t, const double* row, int ndim, double lnq,
-                                              unsigned long long pending)
+                                              unsigned long long pending, double lhs = 0.0)
 {
     double* dst = pend_rows + (size_t)t * GF_PEND_STRIDE;
-    for (int d = 0; d < ndim; ++d) dst[d] = row[d];
+    park_row(dst, row, ndim);
     dst[GF_MAX_DIM] = lnq;
+    if (WITH_LHS) dst[GF_MAX_DIM + 1] = lhs;
     const unsigned int at = atomicAdd(&pq->count, 1u);
     if (at < pq->cap) {
         GfArbItem it;
@@ -97,25 +96,40 @@ __device__ __forceinline__ void park_proposal(GfArbQueue* pq, double* pend_rows,
     }
 }
 
-// Lanes per walker of a step of `walkers` BSM walkers (the cost model of gf_sampler.hip's lanes_per_walker, restricted to the
-// instances the nested sampler and the maximiser compile); the environment variable `force_env` forces one.  Any choice gives
-// the same bits.
-inline int gf_propose_lanes_per_walker(int mode, int64_t walkers, int nbins_max, int cus, const char* force_env)
+// Lanes per walker for a BSM step of `walkers` proposals.  Splitting a walker's bins over L lanes shortens its critical path from
+// nbins to nbins / L bin evaluations but repeats the per-walker prologue on every lane and multiplies the waves: small ensembles (a
+// latency: one walker's chain on a GPU that is mostly idle) want the widest split, large ones the narrowest that still keeps more
+// than one wave on a SIMD.  A cost model instead of a table (round 4; tools/c5_lpw_ab.py, tools/lpw_model_check.py): a lane runs
+// P + ceil(nbins / L) B instructions (P ~ 2000: prologue + the tier-2 terms of the chains that need them, B ~ 400 per bin), a SIMD
+// with w resident waves gives each an issue slot every max(7, 4 w) cycles, and waves beyond what is resident (three per SIMD by
+// registers; two at L = 2, whose 128 group buffers per block take more LDS) queue for another round.  C5's half-step of 65 536
+// proposals: L = 2 (one round of two waves per SIMD) -- measured 79 us per half-step against 84 at L = 4, 94 at L = 1, 122 at
+// L = 16; ensembles of a few thousand proposals keep 16.  Any choice gives the same bits.
+// What a caller's kernels allow: L from {1, 2, 4, 16} (`with2`: the ensemble sampler) or {1, 4, 16}, the LDS its lane-group buffers
+// may take beside the tiles, and the environment variable that forces a choice (diagnostics / A-B, read per call)
+struct GfLpwRule {
+    bool with2;
+    size_t lds_cap;
+    const char* force_env;
+};
+inline int lanes_per_walker(int mode, int64_t walkers, int nbins_max, int cus, const GfLpwRule& rule)
 {
     if (mode != MODE_BSM_GAUSS || nbins_max < 2) return 1;
-    const char* force = gf_internal_env(force_env, 0);
-    if (force) { const int f = std::atoi(force); if (f == 1 || f == 4 || f == 16) return f; }
+    const char* force = gf_internal_env(rule.force_env, 0);
+    if (force) { const int f = std::atoi(force); if (f == 1 || (f == 2 && rule.with2) || f == 4 || f == 16) return f; }
     const int64_t simds = (int64_t)(cus > 0 ? cus : 256) * 4;
     int best = 1;
     double best_cost = 0.0;
-    for (int lpw : {1, 4, 16}) {
+    for (int lpw : {1, 2, 4, 16}) {
+        if (lpw == 2 && !rule.with2) continue;
         const size_t lds = (size_t)(GF_BLOCK / lpw) * GF_FGRP_DOUBLES(nbins_max, lpw) * sizeof(double);
-        if (lpw > 1 && lds > 32 * 1024) continue;
+        if (lpw > 1 && lds > rule.lds_cap) continue;                         // group buffers no longer fit beside the tiles
         const int64_t waves = (walkers * lpw + GF_WAVE - 1) / GF_WAVE;
+        const int64_t wmax = lpw == 2 ? 2 : 3;
         const int64_t per_simd = (waves + simds - 1) / simds;
-        const int64_t wv = per_simd < 3 ? per_simd : 3;
-        const int64_t rounds = (waves + simds * 3 - 1) / (simds * 3);
-        const double interval = 4.0 * (double)wv > 7.0 ? 4.0 * (double)wv : 7.0;
+        const int64_t w = per_simd < wmax ? per_simd : wmax;
+        const int64_t rounds = (waves + simds * wmax - 1) / (simds * wmax);
+        const double interval = 4.0 * (double)w > 7.0 ? 4.0 * (double)w : 7.0;
         const double cost = (double)rounds * (2000.0 + 400.0 * (double)((nbins_max + lpw - 1) / lpw)) * interval;
         if (lpw == 1 || cost < best_cost) { best = lpw; best_cost = cost; }
     }

@@ -31,7 +31,8 @@
 #include "gf_bsm_device.hpp"
 #include "gf_launch.h"
 #include "gf_unitarity_teams.hpp"      // Team9: the reference's unitarity chain on nine lanes (k_stretch_chain settles its own parked proposals)
-#include "gf_propose.hpp"               // philox_block, proposal_lnprob: shared with the nested sampler (gf_nested.hip)
+#include "gf_propose.hpp"               // proposal_lnprob, park_proposal, lanes_per_walker: shared with the nested sampler (gf_nested.hip) and the maximiser
+#include "gf_stretch.hpp"               // the move itself: draw, accept test's left side, row -- one definition for the launch shapes below
 
 namespace {
 using namespace gfdev;
@@ -39,10 +40,9 @@ using namespace gfdev;
 // Step counters live on the device so that a captured hipGraph of GRAPH_STEPS steps can be replayed with
 // constant kernel arguments: each kernel node carries its own frozen `step_offset`; the base counters
 // are advanced once per replay by k_tick (one extra 1-thread launch per GRAPH_STEPS steps).  (GfStepState: gf_launch.h)
-typedef GfStepState StepState;
 
 struct StretchArgs {
-    StepState* state;
+    GfStepState* state;
     double* pos;            // [nchains][nwalkers][ndim]
     double* lnp;            // [nchains][nwalkers]
     uint32_t* naccept;      // [nchains][nwalkers]
@@ -76,7 +76,7 @@ __global__ void k_fix_start(const int32_t* __restrict__ status, int64_t n, doubl
         if (status[i] == ST_NON_UNITARY) { lnp[i] = -gf_inf(); atomicAdd(flags, 1u); }
 }
 
-__global__ void k_tick(StepState* st, int nsteps)
+__global__ void k_tick(GfStepState* st, int nsteps)
 {
     st->iteration_base += (uint64_t)nsteps;
     st->run_step_base += nsteps;
@@ -115,50 +115,21 @@ __device__ __forceinline__ void stretch_body(const GfCommon& c, const GfBsm* __r
     const int w = s.half * nhalf + k;                        // this walker, in the active half
     const int cbase = (1 - s.half) * nhalf;                  // complementary half
 
-    uint32_t r[4];
-    philox_block((uint32_t)g, (uint32_t)(g >> 32), (uint32_t)(2 * iteration + s.half),
-                 (uint32_t)((2 * iteration + s.half) >> 32), (uint32_t)s.seed, (uint32_t)(s.seed >> 32), r);
-    const double u1 = ((double)(r[0] >> 5) * 67108864.0 + (double)(r[1] >> 6)) * (1.0 / 9007199254740992.0);
-    const int j = (int)(((uint64_t)r[2] * (uint64_t)nhalf) >> 32);
-    const double u3 = ((double)r[3] + 0.5) * (1.0 / 4294967296.0);
-    const double zr = fma(s.a - 1.0, u1, 1.0);
-    const double z = zr * zr / s.a;
-
+    double z, u3;
+    int j;
+    stretch_draw(s.seed, g, 2 * iteration + s.half, nhalf, s.a, z, j, u3);
     const double* sk = s.pos + ((int64_t)chain * s.nwalkers + w) * ndim;
     const double* cj = s.pos + ((int64_t)chain * s.nwalkers + cbase + j) * ndim;
-#pragma unroll
-    for (int d = 0; d < ND; ++d) {
-        if (!NDIM && d >= ndim) break;
-        const double cv = cj[d];
-        row[d] = fma(-z, cv - sk[d], cv);                    // q = c_j - z (c_j - s_k)
-    }
+    stretch_row<NDIM>(row, cj, sk, z, ndim);
     int st;
     unsigned long long pending;
     const double lnq = proposal_lnprob<NDIM, MODE, LPW>(c, tb, ctab, ttab, row, ndim, st, sub, fgrp, pending);
     const int64_t wi = (int64_t)chain * s.nwalkers + w;
     const double lnk = s.lnp[wi];
-    // z^(ndim-1) / u3
-    double zp = 1.0;
-    for (int d = 1; d < ndim; ++d) zp *= z;
-    const double lhs = log(zp / u3);
+    const double lhs = stretch_lhs(z, u3, ndim);
     if (MODE == MODE_BSM_GAUSS && pending != 0ull) {
         // undecided unitarity: park the proposal; k_stretch_settle completes this walker's half-step
-        if (sub == 0) {
-            const int64_t t = (int64_t)chain * nhalf + k;
-            double* dst = s.pend_rows + (size_t)t * GF_PEND_STRIDE;
-            for (int d = 0; d < ndim; ++d) dst[d] = row[d];
-            dst[GF_MAX_DIM] = lnq;
-            dst[GF_MAX_DIM + 1] = lhs;
-            const unsigned int at = atomicAdd(&s.pq->count, 1u);
-            if (at < s.pq->cap) {
-                GfArbItem it;
-                it.walker = (unsigned long long)t;
-                it.mask = pending;
-                s.pq->items[at] = it;
-            } else {
-                s.pq->overflow = 1u;                             // capacity = every proposal of a half-step: cannot happen
-            }
-        }
+        if (sub == 0) park_proposal<true>(s.pq, s.pend_rows, (int64_t)chain * nhalf + k, row, ndim, lnq, pending, lhs);
         return;
     }
     bool accept = lhs > lnk - lnq;                           // false for NaN and for lnq = -inf
@@ -167,6 +138,7 @@ __device__ __forceinline__ void stretch_body(const GfCommon& c, const GfBsm* __r
         if (sub == 0) atomicAdd(s.flags, 1u);
     }
     if (LPW > 1 && sub != 0) return;                         // the group's results are identical: one writer
+    // (written out, as in chain_propose, k_stretch_chain and k_stretch_settle: one shared function moves these kernels' register figures)
     if (accept) {
         double* dst = s.pos + wi * ndim;
 #pragma unroll
@@ -216,38 +188,6 @@ __global__ __launch_bounds__(GF_BLOCK, GF_STRETCH_WAVES) void k_stretch_multi(co
     const int t = blockIdx.x * GF_BLOCK + threadIdx.x;
     const int k = t / LPW;
     stretch_body<NDIM, MODE, LPW>(s.commons[chain], s.tbs[chain], s.ptabs[chain], s, chain, k, k < s.nwalkers / 2, t % LPW);
-}
-
-// Lanes per walker for a BSM half-step of `walkers` proposals, from {1, 2, 4, 16}.  Splitting a walker's bins over L lanes shortens
-// its critical path from nbins to nbins / L bin evaluations but repeats the per-walker prologue on every lane and multiplies the
-// waves: small ensembles (a latency: one walker's chain on a GPU that is mostly idle) want the widest split, large ones the
-// narrowest that still keeps more than one wave on a SIMD.  A cost model instead of a table (round 4; tools/c5_lpw_ab.py): a lane
-// runs P + ceil(nbins / L) B instructions (P ~ 2000: prologue + the tier-2 terms of the chains that need them, B ~ 400 per bin),
-// a SIMD with w resident waves gives each an issue slot every max(7, 4 w) cycles, and waves beyond what is resident (three per
-// SIMD by registers; two at L = 2, whose 128 group buffers per block take more LDS) queue for another round.  C5's half-step of
-// 65 536 proposals: L = 2 (one round of two waves per SIMD) -- measured 79 us per half-step against 84 at L = 4, 94 at L = 1,
-// 122 at L = 16; ensembles of a few thousand proposals keep 16.
-inline int lanes_per_walker(int mode, int64_t walkers, int nbins_max, int cus)
-{
-    if (mode != MODE_BSM_GAUSS || nbins_max < 2) return 1;
-    const char* force = gf_internal_env("GF_SAMPLER_LPW", 0);                 // diagnostics / A-B, read per run
-    if (force) { const int f = std::atoi(force); if (f == 1 || f == 2 || f == 4 || f == 16) return f; }
-    const int64_t simds = (int64_t)(cus > 0 ? cus : 256) * 4;
-    int best = 1;
-    double best_cost = 0.0;
-    for (int lpw : {1, 2, 4, 16}) {
-        const size_t lds = (size_t)(GF_BLOCK / lpw) * GF_FGRP_DOUBLES(nbins_max, lpw) * sizeof(double);
-        if (lpw > 1 && lds > 48 * 1024) continue;                            // group buffers no longer fit beside the tiles
-        const int64_t waves = (walkers * lpw + GF_WAVE - 1) / GF_WAVE;
-        const int64_t wmax = lpw == 2 ? 2 : 3;
-        const int64_t per_simd = (waves + simds - 1) / simds;
-        const int64_t w = per_simd < wmax ? per_simd : wmax;
-        const int64_t rounds = (waves + simds * wmax - 1) / (simds * wmax);
-        const double interval = 4.0 * (double)w > 7.0 ? 4.0 * (double)w : 7.0;
-        const double cost = (double)rounds * (2000.0 + 400.0 * (double)((nbins_max + lpw - 1) / lpw)) * interval;
-        if (lpw == 1 || cost < best_cost) { best = lpw; best_cost = cost; }
-    }
-    return best;
 }
 
 template <int NDIM, int MODE, int LPW>
@@ -328,21 +268,12 @@ __global__ __launch_bounds__(MAXT) void k_stretch_persist(const PersistArgs s)
     for (int i = threadIdx.x; i < nw * ndim; i += nt) pos[i] = s.pos[cw * ndim + i];
     for (int i = threadIdx.x; i < nw; i += nt) { lnp[i] = s.lnp[cw + i]; nacc[i] = s.naccept[cw + i]; }
     double* row = rows + (size_t)(producer ? 0 : threadIdx.x) * ndim;
-    const uint32_t k0 = (uint32_t)s.seed, k1 = (uint32_t)(s.seed >> 32);
     const uint64_t gbase = (s.stream_ids ? s.stream_ids[chain] : (uint64_t)chain) * (uint64_t)nhalf;
     // the draws of walker slot k at half-step counter ctr
     auto draw = [&](int k, uint64_t ctr, double& z, int& j, double& lhs) {
-        const uint64_t g = gbase + (uint64_t)k;
-        uint32_t r[4];
-        philox_block((uint32_t)g, (uint32_t)(g >> 32), (uint32_t)ctr, (uint32_t)(ctr >> 32), k0, k1, r);
-        const double u1 = ((double)(r[0] >> 5) * 67108864.0 + (double)(r[1] >> 6)) * (1.0 / 9007199254740992.0);
-        j = (int)(((uint64_t)r[2] * (uint64_t)nhalf) >> 32);
-        const double u3 = ((double)r[3] + 0.5) * (1.0 / 4294967296.0);
-        const double zr = fma(s.a - 1.0, u1, 1.0);
-        z = zr * zr / s.a;
-        double zp = 1.0;
-        for (int d = 1; d < ndim; ++d) zp *= z;
-        lhs = log(zp / u3);
+        double u3;
+        stretch_draw(s.seed, gbase + (uint64_t)k, ctr, nhalf, s.a, z, j, u3);
+        lhs = stretch_lhs(z, u3, ndim);
     };
     const uint64_t ctr_first = 2 * s.iteration_base, ctr_end = ctr_first + 2 * (uint64_t)s.nsteps;
     if (producer && s.nsteps > 0)
@@ -377,12 +308,7 @@ __global__ __launch_bounds__(MAXT) void k_stretch_persist(const PersistArgs s)
                 else draw(k, ctr, z, j, lhs);
                 double* sk = pos + (size_t)w * ndim;
                 const double* cj = pos + (size_t)(cbase + j) * ndim;
-#pragma unroll
-                for (int d = 0; d < ND; ++d) {
-                    if (!NDIM && d >= ndim) break;
-                    const double cv = cj[d];
-                    row[d] = fma(-z, cv - sk[d], cv);
-                }
+                stretch_row<NDIM>(row, cj, sk, z, ndim);
                 int st;
                 unsigned long long pending;
                 const double lnq = proposal_lnprob<NDIM, MODE, 1>(c, nullptr, ctab, nullptr, row, ndim, st, 0, nullptr, pending);
@@ -511,7 +437,7 @@ typedef __attribute__((address_space(3))) unsigned int* LdsU;
 typedef __attribute__((address_space(3))) int* LdsI;
 typedef __attribute__((address_space(3))) unsigned long long* LdsL;
 
-// One walker's proposal of k_stretch_chain -- exactly as stretch_body makes it -- as a function of its own: the kernel around it holds
+// One walker's proposal of k_stretch_chain (the pieces of gf_stretch.hpp, as in stretch_body) as a function of its own: the kernel around it holds
 // the nine-lane teams' code (~210 VGPRs of its own), and compiled as one body for eight waves per CU (256 VGPRs) the allocator spilled
 // inside the evaluation's bin loop (36 us per pass instead of 24).  Out of line, each side has the whole budget.
 template <int NDIM>
@@ -527,74 +453,62 @@ __device__ __attribute__((noinline)) void chain_propose(const ChainArgs& s, cons
     const int ndim = NDIM ? NDIM : c.ndim;
     const int nw = s.nwalkers, nhalf = nw / 2;
     const int cbase = (1 - half) * nhalf;
-    const uint32_t k0s = (uint32_t)s.seed, k1s = (uint32_t)(s.seed >> 32);
-    {
-        // ---- the proposal, exactly as stretch_body makes it
-        const uint64_t g = sid * (uint64_t)nhalf + (uint64_t)k;
-        const int w = half * nhalf + k;
-        uint32_t r[4];
-        philox_block((uint32_t)g, (uint32_t)(g >> 32), (uint32_t)(2 * iteration + half),
-                     (uint32_t)((2 * iteration + half) >> 32), k0s, k1s, r);
-        const double u1 = ((double)(r[0] >> 5) * 67108864.0 + (double)(r[1] >> 6)) * (1.0 / 9007199254740992.0);
-        const int j = (int)(((uint64_t)r[2] * (uint64_t)nhalf) >> 32);
-        const double u3 = ((double)r[3] + 0.5) * (1.0 / 4294967296.0);
-        const double zr = fma(s.a - 1.0, u1, 1.0);
-        const double z = zr * zr / s.a;
-        const int64_t wi = (int64_t)chain * nw + w;
-        const double* sk = s.pos + wi * ndim;
-        const double* cj = s.pos + ((int64_t)chain * nw + cbase + j) * ndim;
-    #pragma unroll
-        for (int d = 0; d < ND; ++d) {
-            if (!NDIM && d >= ndim) break;
-            const double cv = cj[d];
-            row[d] = fma(-z, cv - sk[d], cv);
+    const uint64_t g = sid * (uint64_t)nhalf + (uint64_t)k;
+    const int w = half * nhalf + k;
+    double z, u3;
+    int j;
+    stretch_draw(s.seed, g, 2 * iteration + half, nhalf, s.a, z, j, u3);
+    const int64_t wi = (int64_t)chain * nw + w;
+    const double* sk = s.pos + wi * ndim;
+    const double* cj = s.pos + ((int64_t)chain * nw + cbase + j) * ndim;
+#pragma unroll
+    for (int d = 0; d < ND; ++d) {                        // (not stretch_row: with it k_stretch_chain's spill counts move)
+        if (!NDIM && d >= ndim) break;
+        const double cv = cj[d];
+        row[d] = fma(-z, cv - sk[d], cv);
+    }
+    int st;
+    unsigned long long pending;
+    const double lnq = proposal_lnprob<NDIM, MODE_BSM_GAUSS, 1>(c, tb, ctab, ttab, row, ndim, st, 0, nullptr, pending);
+    const double lnk = s.lnp[wi];
+    const double lhs = stretch_lhs(z, u3, ndim);
+    bool accept = lhs > lnk - lnq;                        // false for NaN and for lnq = -inf
+    if (pending != 0ull && accept) {
+        // undecided unitarity and the verdict DECIDES: park it; this workgroup settles it below, before anybody
+        // reads this walker again
+        double* dst = my_pend + (size_t)k * GF_PEND_STRIDE;
+        park_row(dst, row, ndim);
+        dst[GF_MAX_DIM] = lnq;
+        dst[GF_MAX_DIM + 1] = lhs;
+        const unsigned int at = atomicAdd((unsigned int*)pk_n, 1u);
+        pk_k[at] = k;
+        pk_mask[at] = pending;
+    } else {
+        if (pending != 0ull) {
+            // undecided, but rejected either way: only the count wants the verdict -- later
+            const unsigned int at = atomicAdd((unsigned int*)lz_n, 1u);
+            park_row(lz_rows + (size_t)at * GF_PEND_STRIDE, row, ndim);
+            lz_mask[at] = pending;
         }
-        int st;
-        unsigned long long pending;
-        const double lnq = proposal_lnprob<NDIM, MODE_BSM_GAUSS, 1>(c, tb, ctab, ttab, row, ndim, st, 0, nullptr, pending);
-        const double lnk = s.lnp[wi];
-        double zp = 1.0;
-        for (int d = 1; d < ndim; ++d) zp *= z;
-        const double lhs = log(zp / u3);
-        bool accept = lhs > lnk - lnq;                    // false for NaN and for lnq = -inf
-        if (pending != 0ull && accept) {
-            // undecided unitarity and the verdict DECIDES: park it; this workgroup settles it below, before anybody
-            // reads this walker again
-            double* dst = my_pend + (size_t)k * GF_PEND_STRIDE;
-            for (int d = 0; d < ndim; ++d) dst[d] = row[d];
-            dst[GF_MAX_DIM] = lnq;
-            dst[GF_MAX_DIM + 1] = lhs;
-            const unsigned int at = atomicAdd((unsigned int*)pk_n, 1u);
-            pk_k[at] = k;
-            pk_mask[at] = pending;
-        } else {
-            if (pending != 0ull) {
-                // undecided, but rejected either way: only the count wants the verdict -- later
-                const unsigned int at = atomicAdd((unsigned int*)lz_n, 1u);
-                double* dst = lz_rows + (size_t)at * GF_PEND_STRIDE;
-                for (int d = 0; d < ndim; ++d) dst[d] = row[d];
-                lz_mask[at] = pending;
+        if (st == ST_NON_UNITARY) { accept = false; atomicAdd(s.flags, 1u); }      // the reference raises inside ln_prob here
+        if (accept) {
+            double* dst = s.pos + wi * ndim;
+#pragma unroll
+            for (int d = 0; d < ND; ++d) {
+                if (!NDIM && d >= ndim) break;
+                dst[d] = row[d];
             }
-            if (st == ST_NON_UNITARY) { accept = false; atomicAdd(s.flags, 1u); }      // the reference raises inside ln_prob here
-            if (accept) {
-                double* dst = s.pos + wi * ndim;
-    #pragma unroll
-                for (int d = 0; d < ND; ++d) {
-                    if (!NDIM && d >= ndim) break;
-                    dst[d] = row[d];
-                }
-                s.lnp[wi] = lnq;
-                s.naccept[wi] += 1u;
+            s.lnp[wi] = lnq;
+            s.naccept[wi] += 1u;
+        }
+        if (store_now) {
+            double* dst = s.chain + (((int64_t)chain * s.nstore_cap + store_index) * nw + w) * ndim;
+#pragma unroll
+            for (int d = 0; d < ND; ++d) {
+                if (!NDIM && d >= ndim) break;
+                dst[d] = accept ? row[d] : sk[d];
             }
-            if (store_now) {
-                double* dst = s.chain + (((int64_t)chain * s.nstore_cap + store_index) * nw + w) * ndim;
-    #pragma unroll
-                for (int d = 0; d < ND; ++d) {
-                    if (!NDIM && d >= ndim) break;
-                    dst[d] = accept ? row[d] : sk[d];
-                }
-                if (s.lnp_chain) s.lnp_chain[((int64_t)chain * s.nstore_cap + store_index) * nw + w] = accept ? lnq : lnk;
-            }
+            if (s.lnp_chain) s.lnp_chain[((int64_t)chain * s.nstore_cap + store_index) * nw + w] = accept ? lnq : lnk;
         }
     }
 }
@@ -734,7 +648,6 @@ __global__ __launch_bounds__(CH_BLOCK) void k_stretch_chain(const ChainArgs s)
     const int lane = threadIdx.x & (GF_WAVE - 1), wave = threadIdx.x / GF_WAVE;
     const int nw = s.nwalkers, nhalf = nw / 2;
     const uint64_t sid = s.stream_ids ? s.stream_ids[chain] : (uint64_t)chain;
-    const uint32_t k0s = (uint32_t)s.seed, k1s = (uint32_t)(s.seed >> 32);
     double* row = uni + (size_t)wave * GF_WAVE * ND + (size_t)lane * ndim;          // (stretch_body: tiles[wave] + lane * ndim)
     double* const my_pend = s.pend_rows + (size_t)chain * nhalf * GF_PEND_STRIDE;    // this chain's parked rows, by walker slot
     // proposals that are REJECTED WHATEVER THEIR VERDICT (the accept test fails even if they are unitary): the chain does not wait
@@ -768,7 +681,6 @@ __global__ __launch_bounds__(CH_BLOCK) void k_stretch_chain(const ChainArgs s)
         const bool store_now = s.store != 0 && s.chain != nullptr && (run_step % s.thin) == 0;
         const int64_t store_index = s.store_base + (run_step + s.thin - 1) / s.thin;
         for (int half = 0; half < 2; ++half) {
-            const int cbase = (1 - half) * nhalf;
             for (int kb = 0; kb < nhalf; kb += CH_BLOCK) {
                 if (lz_n + (unsigned int)(nhalf < CH_BLOCK ? nhalf : CH_BLOCK) > (unsigned int)s.lazy_cap) flush_lazy();   // (uniform: lz_n is stable between barriers)
                 if (threadIdx.x == 0) { pk_n = 0u; pk_head = 0u; }
@@ -920,8 +832,8 @@ struct gf_sampler {
     int64_t nstore_cap = 0, nstored = 0;
     int64_t steps_since_reset = 0;
     uint64_t* d_stream_ids = nullptr;   // per-chain random stream ids (gf_sampler_set_stream_ids), else null
-    StepState* d_state = nullptr;
-    StepState h_state = {};
+    GfStepState* d_state = nullptr;
+    GfStepState h_state = {};
     // captured graph of GRAPH_STEPS steps (2 nodes per step + one tick), valid for the chain pointers it was built with
     hipGraphExec_t graph = nullptr;
     double* graph_chain = nullptr;
@@ -1002,8 +914,8 @@ int sampler_create(gf_model* const* models, bool multi, int nchains, int nwalker
     if (e == hipSuccess) e = hipMalloc((void**)&s->d_flags, sizeof(uint32_t) * 4);
     if (e == hipSuccess && c->mode == MODE_BSM_GAUSS)
         e = gf_alloc_arb_queue((size_t)nchains * (nwalkers / 2), st0, &s->d_pq, &s->d_pend_rows, &s->d_pend_ctl);
-    if (e == hipSuccess) e = hipMalloc((void**)&s->d_state, sizeof(StepState));
-    if (e == hipSuccess) e = hipMemsetAsync(s->d_state, 0, sizeof(StepState), st0);
+    if (e == hipSuccess) e = hipMalloc((void**)&s->d_state, sizeof(GfStepState));
+    if (e == hipSuccess) e = hipMemsetAsync(s->d_state, 0, sizeof(GfStepState), st0);
     if (e == hipSuccess) e = hipMemsetAsync(s->d_naccept, 0, sizeof(uint32_t) * nw, st0);
     if (e == hipSuccess) e = hipMemsetAsync(s->d_flags, 0, sizeof(uint32_t) * 4, st0);
     if (e == hipSuccess) e = hipMalloc((void**)&s->d_commons, sizeof(GfCommon) * nm);
@@ -1534,7 +1446,7 @@ int gf_sampler_run(gf_sampler* s, int64_t nsteps, int thin, int store)
         if (rc != GF_OK) return rc;
     }
     // device-side step counters for this run
-    StepState& hs = s->h_state;                   // member: outlives the asynchronous upload
+    GfStepState& hs = s->h_state;                   // member: outlives the asynchronous upload
     hs.iteration_base = s->iteration; hs.run_step_base = 0; hs.store_base = s->nstored;
     hs.store = store ? 1 : 0; hs.thin = thin;
     GF_HIP(hipStreamSynchronize(st));          // earlier runs must be done with the counters
@@ -1543,7 +1455,8 @@ int gf_sampler_run(gf_sampler* s, int64_t nsteps, int thin, int store)
 
     // the launch shape; the overrides are read in this order, once per run
     Run r = {s, nsteps, thin, store ? 1 : 0, 0};
-    GridSteps g = grid_steps(s, r.store, lanes_per_walker(s->c->mode, (int64_t)s->nchains * (s->nwalkers / 2), s->nbins_max, s->cus));
+    GridSteps g = grid_steps(s, r.store, lanes_per_walker(s->c->mode, (int64_t)s->nchains * (s->nwalkers / 2), s->nbins_max, s->cus,
+                                                           {true, 48 * 1024, "GF_SAMPLER_LPW"}));
     int threads = 0, workers = 0;
     size_t lds = 0;
     persist_geometry(s->nwalkers, s->ndim, &threads, &lds, &workers, s->nchains, s->cus);

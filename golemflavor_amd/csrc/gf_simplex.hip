@@ -559,7 +559,7 @@ int gf_simplex_run(gf_simplex* s, int64_t max_rounds)
         if (rc != GF_OK) return rc;
     }
     if (a.S == 0) return GF_OK;
-    const int lpw = gf_propose_lanes_per_walker(cube_runs_eval_mode(s->rs), (int64_t)a.nruns * a.S * a.Q, a.nbins_max, s->rs.cus, "GF_SIMPLEX_LPW");
+    const int lpw = lanes_per_walker(cube_runs_eval_mode(s->rs), (int64_t)a.nruns * a.S * a.Q, a.nbins_max, s->rs.cus, {false, 32 * 1024, "GF_SIMPLEX_LPW"});
     constexpr int check = 4;
     std::vector<SxRun> hr(a.nruns);
     const dim3 sgrid((unsigned)((a.S + SX_STEP_BLOCK - 1) / SX_STEP_BLOCK), a.nruns);

@@ -1,4 +1,4 @@
-"""Does `lanes_per_walker`'s cost model pick well?  Stacked C5 samplers of 16 / 32 / 64 / 128 / 256 chains x 512 walkers (every second ... grid
+"""Does `lanes_per_walker`'s cost model (csrc/gf_propose.hpp) pick well?  Stacked C5 samplers of 16 / 32 / 64 / 128 / 256 chains x 512 walkers (every second ... grid
 point, so that each size has its share of chains in the failing region), 100 + 200 steps, lanes per walker forced to 1 / 2 / 4 / 16 and
 left to the library.  One process per setting (the switch is read per run, but the graph is captured once)."""
 import json
