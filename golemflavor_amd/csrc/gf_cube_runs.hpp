@@ -57,9 +57,9 @@ __device__ __forceinline__ void cube_uniform2(const GfCubeRuns& a, int r, uint32
     out[1] = ((double)(q[2] >> 5) * 67108864.0 + (double)(q[3] >> 6)) * (1.0 / 9007199254740992.0);
 }
 
-// (hi - lo) u + lo with the product and the sum each rounded, as mn.py:36 and k_cube_to_theta (gf_kernels.hip) form it: plain operators
-// under contract(off).  The HIP headers' __dmul_rn / __dadd_rn are operators that carry the contract flag of their own context, and the
-// pair below is fused into one v_fma_f64.
+// (hi - lo) u + lo with the product and the sum each rounded, as mn.py:36, the host (NestedSampler.dead, SimplexMaximizer.cube_to_theta,
+// gf_nested_post.hpp) and k_cube_to_theta (gf_kernels.hip) form it: plain operators under contract(off).  The HIP headers' __dmul_rn /
+// __dadd_rn are operators that carry the contract flag of their own context, and such a pair is fused into one v_fma_f64.
 __device__ __forceinline__ double cube_affine_unfused(double span, double u, double lo)
 {
 #pragma clang fp contract(off)
@@ -67,26 +67,20 @@ __device__ __forceinline__ double cube_affine_unfused(double span, double u, dou
     return prod + lo;
 }
 
-// theta of cube point u for run r.  UNFUSED = false, the instances that predate the binned likelihood: the product and the sum are
-// fused, so a scanned coordinate can be one ulp off the theta k_cube_to_theta and the host form from the same cube point, and a
-// stored lnprob off the bulk lnprob of that theta by about as much (a few per cent of the points, mostly one ulp); their results are
-// left as they are.  UNFUSED = true (a binned run set): theta is k_cube_to_theta's bit for bit, and with it a stored lnprob is the bulk
-// kernel's of the same cube point.
-template <bool UNFUSED = false>
+// theta of cube point u for run r: cube_affine_unfused on the scanned columns, the run's base value elsewhere.  Every instance of the
+// walk and simplex kernels forms it so, and with it theta is the host's and k_cube_to_theta's bit for bit: a stored lnprob is the bulk
+// kernel's at the theta the package reports for the same cube point.  (A fused map is one ulp off in a scanned coordinate on up to 40 per
+// cent of the draws of a box that does not start at 0, and the stored lnprob then belongs to a neighbouring theta.)
 __device__ __forceinline__ void cube_to_theta(const GfCubeRuns& a, const GfCommon& c, int r, const double* u, double* row)
 {
     for (int d = 0; d < a.ndim; ++d) {
         const int sl = a.slot[d];
-        if constexpr (UNFUSED)
-            row[d] = sl >= 0 ? cube_affine_unfused(c.hi[d] - c.lo[d], u[sl], c.lo[d]) : a.bases[r * GF_MAX_DIM + d];
-        else
-            row[d] = sl >= 0 ? __dadd_rn(__dmul_rn(c.hi[d] - c.lo[d], u[sl]), c.lo[d]) : a.bases[r * GF_MAX_DIM + d];
+        row[d] = sl >= 0 ? cube_affine_unfused(c.hi[d] - c.lo[d], u[sl], c.lo[d]) : a.bases[r * GF_MAX_DIM + d];
     }
 }
 
 // n cube points per run (blockIdx.y), drawn uniformly (counter (run id, it, point, pair of coordinates)) into u [R][n][nscan]
 // and mapped to theta [R][n][ndim]
-template <bool UNFUSED>
 __global__ __launch_bounds__(GF_BLOCK) void k_cube_draw(const GfCubeRuns a, uint32_t it, int n, double* u, double* theta)
 {
     const int r = blockIdx.y;
@@ -101,7 +95,7 @@ __global__ __launch_bounds__(GF_BLOCK) void k_cube_draw(const GfCubeRuns a, uint
     }
     double* dst = u + ((int64_t)r * n + i) * a.nscan;
     for (int d = 0; d < a.nscan; ++d) dst[d] = v[d];
-    cube_to_theta<UNFUSED>(a, a.commons[r], r, v, theta + ((int64_t)r * n + i) * a.ndim);
+    cube_to_theta(a, a.commons[r], r, v, theta + ((int64_t)r * n + i) * a.ndim);
 }
 
 // An evaluation kernel's instances: PRIOR_ONLY, SM_GAUSS and BSM_BINNED at one lane per point, BSM at 1, 4 or 16.  `launch` is called
@@ -246,8 +240,7 @@ int cube_runs_draw(const GfCubeRunsHost& h, const GfCubeRuns& a, uint32_t it, in
                    int32_t* status)
 {
     const dim3 grid((unsigned)((n + GF_BLOCK - 1) / GF_BLOCK), a.nruns);
-    if (h.binned) hipLaunchKernelGGL(k_cube_draw<true>, grid, dim3(GF_BLOCK), 0, h.stream, a, it, n, u, theta);
-    else hipLaunchKernelGGL(k_cube_draw<false>, grid, dim3(GF_BLOCK), 0, h.stream, a, it, n, u, theta);
+    hipLaunchKernelGGL(k_cube_draw, grid, dim3(GF_BLOCK), 0, h.stream, a, it, n, u, theta);
     GF_HIP(hipGetLastError());
     for (int r = 0; r < a.nruns; ++r) {
         const int rc = gf_model_lnprob_on(h.models[r], h.stream, theta + (size_t)r * n * a.ndim, GF_LAYOUT_AOS, n,

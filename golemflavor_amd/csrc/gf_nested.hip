@@ -318,7 +318,7 @@ __global__ __launch_bounds__(GF_BLOCK) void k_ns_walk(const NsArgs a)
     if (!inside) return;                                     // rejected without evaluating
     const int lane = threadIdx.x & (GF_WAVE - 1);
     double* row = tiles[threadIdx.x / GF_WAVE] + lane * GF_MAX_DIM;
-    cube_to_theta<MODE == MODE_BSM_BINNED>(a, c, r, u, row);
+    cube_to_theta(a, c, r, u, row);
     int st;
     unsigned long long pending;
     const double lnq = proposal_lnprob<0, MODE, LPW>(c, tb, ctab, ttab, row, a.ndim, st, sub, fgrp, pending, btab);

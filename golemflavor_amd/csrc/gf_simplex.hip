@@ -221,7 +221,7 @@ __global__ __launch_bounds__(GF_BLOCK) void k_sx_eval(const SxArgs a)
     const int64_t w = s * a.Q + p;
     const int lane = threadIdx.x & (GF_WAVE - 1);
     double* row = tiles[threadIdx.x / GF_WAVE] + lane * GF_MAX_DIM;
-    cube_to_theta<MODE == MODE_BSM_BINNED>(a, c, r, a.pts + w * a.nscan, row);
+    cube_to_theta(a, c, r, a.pts + w * a.nscan, row);
     int status;
     unsigned long long pending;
     const double lnq = proposal_lnprob<0, MODE, LPW>(c, tb, ctab, ttab, row, a.ndim, status, sub, fgrp, pending, btab);

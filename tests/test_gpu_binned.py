@@ -398,10 +398,11 @@ def test_nested_dead_points_equal_the_bulk_lnprob():
     """Two scales, nlive 64: every dead point's stored lnL is Model.lnprob of the same theta bit for bit -- the walk kernel's binned
     instance against the bulk kernel.
 
-    What it holds in place: a binned run set maps the cube onto theta with the product and the sum each rounded, as the host and
-    k_cube_to_theta do (cube_to_theta<true>, gf_cube_runs.hpp).  With the fused multiply-add of the older instances a scanned
-    coordinate is one ulp off the host's theta now and then, and 44 of 1096 and 34 of 1072 dead points of these two runs then
-    differed from the bulk lnprob of the theta the host forms, by up to 38 and 148 ulps."""
+    What it holds in place: a run set maps the cube onto theta with the product and the sum each rounded, as the host and
+    k_cube_to_theta do (cube_to_theta, gf_cube_runs.hpp).  With a fused multiply-add, which every instance but the binned one once
+    had, a scanned coordinate is one ulp off the host's theta now and then, and 44 of 1096 and 34 of 1072 dead points of these two
+    runs then differed from the bulk lnprob of the theta the host forms, by up to 38 and 148 ulps.  test_gpu_cube_runs.py holds the
+    same for the other instances, on boxes that see the map far more often than these."""
     res = nested_run(True)
     try:
         for r, m in enumerate(res["models"]):
