@@ -259,6 +259,7 @@ SIGNATURES = {
                                               _dp, _ip, _dp]),
     "gf_model_set_binned_measurement": (C.c_int, [_vp, C.c_int, _dp, _dp]),
     "gf_model_is_binned": (C.c_int, [_vp]),
+    "gf_sampler_create_binned": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_double, C.POINTER(_vp)]),
 }
 
 _lib = None

@@ -46,7 +46,7 @@ struct StretchArgs {
     double* pos;            // [nchains][nwalkers][ndim]
     double* lnp;            // [nchains][nwalkers]
     uint32_t* naccept;      // [nchains][nwalkers]
-    uint32_t* flags;        // [0]: proposals the reference would have raised on (NON_UNITARY), whichever tier found out
+    uint32_t* flags;        // [0]: proposals the reference would have raised on (NON_UNITARY), whichever tier found out; [2]: see stretch_body
     GfArbQueue* pq;         // BSM: proposals whose verdict the in-kernel tiers cannot settle are parked here ...
     double* pend_rows;      // ... with their row [GF_PEND_STRIDE] (theta | lnprob | ln(z^(ndim-1)/u)), for k_stretch_settle
     double* chain;          // [nchains][nstore_cap][nwalkers][ndim] or null
@@ -66,6 +66,9 @@ struct StretchArgs {
     // A scan hands in the GLOBAL grid index, so that a grid point's chain does not depend on which rank runs it or on
     // how many other points share its sampler.
     const uint64_t* stream_ids;
+    // a sampler of the energy-resolved likelihood (gf_sampler_create_binned): [nmodels] the models' binned measurements
+    // (gf_consts.h: GF_BINNED_STRIDE x nbins doubles each), chain ch reads btabs[ch] (one model: btabs[0]); NULL for every other sampler
+    const double* const* btabs;
 };
 
 // start positions the reference would have died on (fr.py:493-498, raised while emcee evaluates p0): -inf and counted, so
@@ -86,17 +89,23 @@ __global__ void k_tick(GfStepState* st, int nsteps)
 // index in the active half (`valid` false for the padding threads of the last block of a chain).
 // LPW > 1 (BSM posteriors on small ensembles): LPW adjacent lanes hold the same walker and split its energy
 // bins (flux_average); everything else they compute redundantly and identically, lane `sub == 0` writes.
+// MODE_BSM_BINNED (one lane per walker): the block stages its chain's binned measurement `btab_g` in LDS beside ctab; everything
+// around the likelihood -- verdict tiers, parking, k_stretch_settle behind the half-step -- is the flux-averaged BSM instance's.
 template <int NDIM, int MODE, int LPW>
 __device__ __forceinline__ void stretch_body(const GfCommon& c, const GfBsm* __restrict__ tb, const double* __restrict__ ptab,
-                                             const StretchArgs& s, const int chain, const int k, const bool valid, const int sub)
+                                             const StretchArgs& s, const int chain, const int k, const bool valid, const int sub,
+                                             const double* __restrict__ btab_g = nullptr)
 {
+    constexpr bool BSM = MODE == MODE_BSM_GAUSS || MODE == MODE_BSM_BINNED;
     extern __shared__ __attribute__((aligned(16))) double fdyn[];    // LPW > 1: per lane group [nbins_max][3] + [LPW]
     double* fgrp = LPW > 1 ? fdyn + (threadIdx.x / LPW) * GF_FGRP_DOUBLES(s.nbins_max, LPW) : nullptr;
     constexpr int ND = NDIM ? NDIM : GF_MAX_DIM;
     __shared__ __attribute__((aligned(16))) double tiles[GF_WAVES_PER_BLOCK][GF_WAVE * ND];
     __shared__ __attribute__((aligned(16))) double ctab[GF_MAX_DIM * 4 + 20];
+    __shared__ __attribute__((aligned(16))) double btab[MODE == MODE_BSM_BINNED ? GF_BINNED_DOUBLES : 1];   // the chain's binned measurement
     double* ttab = ctab + GF_MAX_DIM * 4;
-    load_eval_tables(ctab, ptab, tb, MODE == MODE_BSM_GAUSS);
+    load_eval_tables(ctab, ptab, tb, BSM);
+    if constexpr (MODE == MODE_BSM_BINNED) load_binned_table(btab, btab_g, tb->nbins);
     __syncthreads();
 
     const int ndim = NDIM ? NDIM : c.ndim;
@@ -123,13 +132,14 @@ __device__ __forceinline__ void stretch_body(const GfCommon& c, const GfBsm* __r
     stretch_row<NDIM>(row, cj, sk, z, ndim);
     int st;
     unsigned long long pending;
-    const double lnq = proposal_lnprob<NDIM, MODE, LPW>(c, tb, ctab, ttab, row, ndim, st, sub, fgrp, pending);
+    const double lnq = proposal_lnprob<NDIM, MODE, LPW>(c, tb, ctab, ttab, row, ndim, st, sub, fgrp, pending, btab);
     const int64_t wi = (int64_t)chain * s.nwalkers + w;
     const double lnk = s.lnp[wi];
     const double lhs = stretch_lhs(z, u3, ndim);
-    if (MODE == MODE_BSM_GAUSS && pending != 0ull) {
+    if (BSM && pending != 0ull) {
         // undecided unitarity: park the proposal; k_stretch_settle completes this walker's half-step
         if (sub == 0) park_proposal<true>(s.pq, s.pend_rows, (int64_t)chain * nhalf + k, row, ndim, lnq, pending, lhs);
+        if constexpr (MODE == MODE_BSM_BINNED) atomicAdd(s.flags + 2, 1u);      // census: proposals k_stretch_settle completed (gf_internal_sampler_parked)
         return;
     }
     bool accept = lhs > lnk - lnq;                           // false for NaN and for lnq = -inf
@@ -176,7 +186,8 @@ __global__ __launch_bounds__(GF_BLOCK, GF_STRETCH_WAVES) void k_stretch(const Gf
     const bool valid = g < (int64_t)s.nchains * nhalf;
     const int chain = valid ? (int)(g / nhalf) : 0;
     const int k = valid ? (int)(g - (int64_t)chain * nhalf) : 0;
-    stretch_body<NDIM, MODE, LPW>(c, tb, ptab, s, chain, k, valid, (int)(t % LPW));
+    if constexpr (MODE == MODE_BSM_BINNED) stretch_body<NDIM, MODE, LPW>(c, tb, ptab, s, chain, k, valid, 0, s.btabs[0]);
+    else stretch_body<NDIM, MODE, LPW>(c, tb, ptab, s, chain, k, valid, (int)(t % LPW));
 }
 
 // one posterior per ensemble (grid scans, SURVEY.md 8(e) "all chains of a GPU stacked into one launch"):
@@ -187,7 +198,9 @@ __global__ __launch_bounds__(GF_BLOCK, GF_STRETCH_WAVES) void k_stretch_multi(co
     const int chain = blockIdx.y;
     const int t = blockIdx.x * GF_BLOCK + threadIdx.x;
     const int k = t / LPW;
-    stretch_body<NDIM, MODE, LPW>(s.commons[chain], s.tbs[chain], s.ptabs[chain], s, chain, k, k < s.nwalkers / 2, t % LPW);
+    if constexpr (MODE == MODE_BSM_BINNED)
+        stretch_body<NDIM, MODE, LPW>(s.commons[chain], s.tbs[chain], s.ptabs[chain], s, chain, k, k < s.nwalkers / 2, 0, s.btabs[chain]);
+    else stretch_body<NDIM, MODE, LPW>(s.commons[chain], s.tbs[chain], s.ptabs[chain], s, chain, k, k < s.nwalkers / 2, t % LPW);
 }
 
 template <int NDIM, int MODE, int LPW>
@@ -783,6 +796,12 @@ hipError_t launch_stretch_n(const GfCommon& c, const GfBsm* tb, const double* pt
 
 hipError_t launch_stretch(const GfCommon& c, const GfBsm* tb, const double* ptab, const StretchArgs& a, hipStream_t st)
 {
+    if (a.btabs)                            // the energy-resolved likelihood: one lane per walker, the row widths of the BSM posteriors
+        switch (c.ndim) {
+        case 7: return launch_stretch_nml<7, MODE_BSM_BINNED, 1>(c, tb, ptab, a, st);
+        case 12: return launch_stretch_nml<12, MODE_BSM_BINNED, 1>(c, tb, ptab, a, st);
+        default: return launch_stretch_nml<0, MODE_BSM_BINNED, 1>(c, tb, ptab, a, st);
+        }
     switch (c.ndim) {
     case 4: return launch_stretch_n<4>(c, tb, ptab, a, st);
     case 6: return launch_stretch_n<6>(c, tb, ptab, a, st);
@@ -807,6 +826,7 @@ struct gf_sampler {
     GfCommon* d_commons = nullptr;      // device copies of every model's constants, [nchains] or [1] (the kernels that take them by pointer)
     const GfBsm** d_tbs = nullptr;
     const double** d_ptabs = nullptr;
+    const double** d_btabs = nullptr;   // gf_sampler_create_binned: the models' binned measurements (device), [nchains] or [1]; else null
     int nchains = 0, nwalkers = 0, ndim = 0;
     int cus = 256, nbins_max = 0;
     uint64_t seed = 0, iteration = 0;
@@ -869,8 +889,9 @@ double g_last_run_prologue[4] = {};             // the last gf_sampler_run: [0] 
 
 namespace {
 // gf_sampler_create (multi false: every chain samples models[0]) and gf_sampler_create_multi (multi true: chain ch samples
-// models[ch]): the constant tables are allocated once, with one entry per model
-int sampler_create(gf_model* const* models, bool multi, int nchains, int nwalkers, uint64_t seed, double a, gf_sampler** out)
+// models[ch]): the constant tables are allocated once, with one entry per model.  binned (gf_sampler_create_binned): every model
+// carries a binned measurement and the sampler evaluates the energy-resolved likelihood; else none may.
+int sampler_create(gf_model* const* models, bool multi, int nchains, int nwalkers, uint64_t seed, double a, gf_sampler** out, bool binned = false)
 {
     if (!out || nchains < 1 || nwalkers < 2 || (nwalkers & 1) || !(a > 1.0)) return GF_ERR_INVALID_ARG;
     *out = nullptr;
@@ -882,7 +903,8 @@ int sampler_create(gf_model* const* models, bool multi, int nchains, int nwalker
     std::unique_ptr<const GfBsm*[]> htb(new (std::nothrow) const GfBsm*[nmodels]);
     std::unique_ptr<const double*[]> hpt(new (std::nothrow) const double*[nmodels]);
     std::unique_ptr<gf_model*[]> keep(multi ? new (std::nothrow) gf_model*[nmodels] : nullptr);
-    if (!hc || !htb || !hpt || (multi && !keep)) return GF_ERR_ALLOC;
+    std::unique_ptr<const double*[]> hbt(binned ? new (std::nothrow) const double*[nmodels] : nullptr);
+    if (!hc || !htb || !hpt || (multi && !keep) || (binned && !hbt)) return GF_ERR_ALLOC;
     int cus0 = 256, nbins_max = 0;
     for (int ch = 0; ch < nmodels; ++ch) {
         const GfCommon* cm; int dev, cus, nbins;
@@ -890,7 +912,11 @@ int sampler_create(gf_model* const* models, bool multi, int nchains, int nwalker
             cm->ndim != c->ndim || cm->mode != c->mode)
             return gf_fail_msg(GF_ERR_INVALID_ARG, "gf_sampler_create_multi: model %d differs from model 0 in device, ndim or mode", ch);
         // the stretch kernels evaluate the flux-averaged likelihood: never silently for a model whose lnprob is another
-        if (gf_model_binned(models[ch], nullptr))
+        if (binned) {
+            // the table's address is the model's for good: a measurement set later lands in the same table
+            if (!gf_model_binned(models[ch], &hbt[ch]))
+                return gf_fail_msg(GF_ERR_INVALID_ARG, "gf_sampler_create_binned: model %d carries no binned measurement; all of a sampler's models must", ch);
+        } else if (gf_model_binned(models[ch], nullptr))
             return gf_fail_msg(GF_ERR_UNSUPPORTED, "gf_sampler_create: model %d carries a binned measurement; sample the flux-averaged model and reweight "
                                "the chain to this one", ch);
         hc[ch] = *cm;
@@ -924,9 +950,12 @@ int sampler_create(gf_model* const* models, bool multi, int nchains, int nwalker
     if (e == hipSuccess) e = hipMemcpyAsync(s->d_commons, hc.get(), sizeof(GfCommon) * nm, hipMemcpyHostToDevice, st0);
     if (e == hipSuccess) e = hipMemcpyAsync((void*)s->d_tbs, htb.get(), sizeof(void*) * nm, hipMemcpyHostToDevice, st0);
     if (e == hipSuccess) e = hipMemcpyAsync((void*)s->d_ptabs, hpt.get(), sizeof(void*) * nm, hipMemcpyHostToDevice, st0);
+    if (e == hipSuccess && binned) e = hipMalloc((void**)&s->d_btabs, sizeof(void*) * nm);
+    if (e == hipSuccess && binned) e = hipMemcpyAsync((void*)s->d_btabs, hbt.get(), sizeof(void*) * nm, hipMemcpyHostToDevice, st0);
+    if (binned) s->shape = 2;                                         // one launch shape: the per-half-step grid kernels
     if (e == hipSuccess) e = hipStreamSynchronize(st0);               // the host tables are freed on return
     if (e != hipSuccess) {
-        const int rc = gf_hip_fail(e, multi ? "gf_sampler_create_multi" : "gf_sampler_create");
+        const int rc = gf_hip_fail(e, binned ? "gf_sampler_create_binned" : multi ? "gf_sampler_create_multi" : "gf_sampler_create");
         gf_sampler_destroy(s);
         return rc;
     }
@@ -1085,6 +1114,7 @@ GridSteps grid_steps(gf_sampler* s, int store, int lpw)
     a.commons = s->models ? s->d_commons : nullptr; a.tbs = s->d_tbs; a.ptabs = s->d_ptabs;
     a.nbins_max = s->nbins_max;
     a.stream_ids = s->d_stream_ids;
+    a.btabs = s->d_btabs;
     a.lpw = lpw;
     GfSettleArgs& sa = g.sa;
     sa = {};
@@ -1341,6 +1371,34 @@ int gf_sampler_create_multi(gf_model* const* models, int nchains, int nwalkers, 
     return sampler_create(models, true, nchains, nwalkers, seed, a, out);
 }
 
+// A sampler of the energy-resolved likelihood: every model carries a binned measurement
+// (gf_model_set_binned_measurement).  nmodels == 1: every chain samples models[0]; nmodels == nchains: chain ch samples
+// models[ch], as gf_sampler_create_multi.  The tables' addresses are taken here and stay the models' own: a measurement set
+// between two runs is the one the next run samples.
+int gf_sampler_create_binned(gf_model* const* models, int nmodels, int nchains, int nwalkers, uint64_t seed, double a, gf_sampler** out)
+{
+    if (!models || !out || nchains < 1 || nchains > 65535 || (nmodels != 1 && nmodels != nchains)) return GF_ERR_INVALID_ARG;
+    *out = nullptr;
+    for (int ch = 0; ch < nmodels; ++ch)
+        if (!models[ch]) return GF_ERR_INVALID_ARG;
+    return sampler_create(models, nmodels == nchains && nchains > 1, nchains, nwalkers, seed, a, out, true);
+}
+
+// diagnostics (not part of the ABI): proposals since the last reset that the half-step kernel parked and k_stretch_settle completed;
+// counted by the energy-resolved instance alone, GF_ERR_UNSUPPORTED for every other sampler
+int gf_internal_sampler_parked(gf_sampler* s, uint32_t* out)
+{
+    if (!s || !out) return GF_ERR_INVALID_ARG;
+    if (!s->d_btabs) return GF_ERR_UNSUPPORTED;
+    GF_HIP(hipSetDevice(s->device));
+    GF_HIP(hipMemcpyAsync(out, s->d_flags + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+    GF_HIP(hipStreamSynchronize(s->stream));
+    return GF_OK;
+}
+
+// internal (gf_reweight.hip): 1 for a sampler of the energy-resolved likelihood, whose chains have no single Gaussian measurement
+int gf_internal_sampler_binned(const gf_sampler* s) { return s && s->d_btabs ? 1 : 0; }
+
 void gf_sampler_destroy(gf_sampler* s)
 {
     if (!s) return;
@@ -1367,6 +1425,7 @@ void gf_sampler_destroy(gf_sampler* s)
     if (s->d_stream_ids) (void)hipFree(s->d_stream_ids);
     if (s->d_tbs) (void)hipFree((void*)s->d_tbs);
     if (s->d_ptabs) (void)hipFree((void*)s->d_ptabs);
+    if (s->d_btabs) (void)hipFree((void*)s->d_btabs);
     delete[] s->models;
     delete s;
 }
@@ -1455,8 +1514,10 @@ int gf_sampler_run(gf_sampler* s, int64_t nsteps, int thin, int store)
 
     // the launch shape; the overrides are read in this order, once per run
     Run r = {s, nsteps, thin, store ? 1 : 0, 0};
-    GridSteps g = grid_steps(s, r.store, lanes_per_walker(s->c->mode, (int64_t)s->nchains * (s->nwalkers / 2), s->nbins_max, s->cus,
-                                                           {true, 48 * 1024, "GF_SAMPLER_LPW"}));
+    // (a sampler of the energy-resolved likelihood has one shape, the grid kernels at one lane per walker: no override is read for it)
+    const bool binned = s->d_btabs != nullptr;
+    GridSteps g = grid_steps(s, r.store, binned ? 1 : lanes_per_walker(s->c->mode, (int64_t)s->nchains * (s->nwalkers / 2), s->nbins_max, s->cus,
+                                                                        {true, 48 * 1024, "GF_SAMPLER_LPW"}));
     int threads = 0, workers = 0;
     size_t lds = 0;
     persist_geometry(s->nwalkers, s->ndim, &threads, &lds, &workers, s->nchains, s->cus);
@@ -1467,7 +1528,7 @@ int gf_sampler_run(gf_sampler* s, int64_t nsteps, int thin, int store)
         rc = run_persistent(r, threads, lds, workers);
     } else {
         bool grid = true;
-        if (bsm && s->nwalkers / 2 <= 512) rc = run_per_chain(r, g, &grid);
+        if (bsm && !binned && s->nwalkers / 2 <= 512) rc = run_per_chain(r, g, &grid);
         if (rc == GF_OK && grid) rc = run_grid(r, g);
     }
     if (rc != GF_OK) return rc;

@@ -196,9 +196,15 @@ class DeviceEnsembleSampler(rowsets.RowSetSource):
     `acceptance_fraction`, `acor`); with `nchains > 1` the arrays gain a leading chain axis.
     Random numbers come from Philox4x32-10 keyed by `seed` (reproducible, independent of launch
     geometry), not from numpy's global state.
+
+    energy_resolved=True: every posterior carries a measurement per energy bin (`Model.set_binned_measurement`) and
+    the sampler evaluates that likelihood in its half-step kernel (`gf_sampler_create_binned`): the stored lnprob is bit for bit
+    `Model.lnprob` of the stored sample.  ValueError if a posterior carries none.  Without it such a posterior is refused (the
+    library's GF_ERR_UNSUPPORTED).  Everything that reads the chain works as for any sampler; `reweight` takes model targets only.
+    A measurement set on a model between two runs is the one the next run samples.
     """
 
-    def __init__(self, nwalkers, dim, lnpostfn, a=2.0, nchains=1, seed=0, threads=1, stream_ids=None):
+    def __init__(self, nwalkers, dim, lnpostfn, a=2.0, nchains=1, seed=0, threads=1, stream_ids=None, energy_resolved=False):
         import ctypes as C
         from . import _lib
         multi = isinstance(lnpostfn, (list, tuple))
@@ -215,6 +221,12 @@ class DeviceEnsembleSampler(rowsets.RowSetSource):
                 raise TypeError("DeviceEnsembleSampler needs a golemflavor_amd LnProb / Model")
             if model.ndim != dim:
                 raise AssertionError("dim %d does not match the model's %d parameters" % (dim, model.ndim))
+        self.energy_resolved = bool(energy_resolved)
+        if self.energy_resolved:
+            for k, model in enumerate(models):
+                if getattr(model, "binned", None) is None:
+                    raise ValueError("energy_resolved=True, but posterior %d carries no binned measurement "
+                                     "(Model.set_binned_measurement)" % k)
         model, lnpostfn = models[0], fns[0]
         if nwalkers % 2:
             raise AssertionError("The number of walkers must be even.")
@@ -226,7 +238,11 @@ class DeviceEnsembleSampler(rowsets.RowSetSource):
         self.k, self.dim, self.a, self.nchains = int(nwalkers), int(dim), float(a), int(nchains)
         self.models = models if multi else None               # one posterior per chain (kept alive here)
         h = C.c_void_p()
-        if multi:
+        if self.energy_resolved:
+            nmodels = self.nchains if multi else 1
+            _lib.check(self._L.gf_sampler_create_binned(rowsets.model_handles(models, nmodels), nmodels, self.nchains, self.k, int(seed),
+                                                        self.a, C.byref(h)), "gf_sampler_create_binned")
+        elif multi:
             _lib.check(self._L.gf_sampler_create_multi(rowsets.model_handles(models, self.nchains), self.nchains, self.k, int(seed),
                                                        self.a, C.byref(h)), "gf_sampler_create_multi")
         else:
@@ -370,6 +386,17 @@ class DeviceEnsembleSampler(rowsets.RowSetSource):
             return None
         return {"propose_s": out[:, 0] * 1e-9, "settle_s": out[:, 1] * 1e-9, "bulk_s": out[:, 2] * 1e-9, "waited_for": out[:, 3],
                 "passes_that_waited": out[:, 4], "settled_in_bulk": out[:, 5], "passes": out[:, 6], "bulk_settlements": out[:, 7]}
+
+    @property
+    def parked_proposals(self):
+        """Diagnostics: proposals since the last reset whose unitarity verdict the half-step kernel could not settle and
+        k_stretch_settle completed.  Counted by an energy-resolved sampler; None for any other."""
+        fn = getattr(self._L, "gf_internal_sampler_parked", None)
+        if fn is None:
+            return None
+        n = self._C.c_uint32(0)
+        fn.restype, fn.argtypes = self._C.c_int, [self._C.c_void_p, self._C.POINTER(self._C.c_uint32)]
+        return int(n.value) if fn(self._h, self._C.byref(n)) == 0 else None
 
     def launch_shape(self):
         """Diagnostics: how a BSM sampler on small ensembles launches its steps -- {"shape": "per chain" | "grid" | "undecided",
@@ -660,7 +687,7 @@ def element_marginals_file(outfile):
 
 
 def mcmc(p0, ln_prob, ndim, nwalkers, burnin, nsteps, threads=1, device_resident=None, seed=None, plot_elements=False,
-         llh_paramset=None, outfile=None):
+         llh_paramset=None, outfile=None, energy_resolved=False):
     """Run the MCMC: burn-in, reset, production; returns samples reshaped to (-1, ndim).
 
     Same signature, prints and return as golemflavor/mcmc.py:27-53.  When `ln_prob` is a
@@ -669,7 +696,8 @@ def mcmc(p0, ln_prob, ndim, nwalkers, burnin, nsteps, threads=1, device_resident
     forces the host-driven sampler (one launch + PCIe round trip per half-ensemble), which is also
     what any plain Python callable gets.  `seed` keys the device sampler's Philox stream (default:
     drawn from numpy's global RNG, so `np.random.seed(args.seed)` makes runs reproducible as in the
-    reference's scripts).
+    reference's scripts).  energy_resolved: `DeviceEnsembleSampler`'s keyword, for a device-resident run of a posterior with a
+    measurement per energy bin (the host-driven sampler evaluates `ln_prob` itself and takes any).
 
     plot_elements (args.plot_elements) with llh_paramset and outfile: where the device-resident sampler ran, the marginals of the
     chain in element space (`DeviceEnsembleSampler.marginals(space="elements")`, the numbers behind the triangle plot.chainer_plot
@@ -681,7 +709,7 @@ def mcmc(p0, ln_prob, ndim, nwalkers, burnin, nsteps, threads=1, device_resident
     if seed is None:
         seed = int(np.random.randint(0, 2 ** 31 - 1))
     if device_resident:
-        sampler = DeviceEnsembleSampler(nwalkers, ndim, ln_prob, seed=seed)
+        sampler = DeviceEnsembleSampler(nwalkers, ndim, ln_prob, seed=seed, energy_resolved=energy_resolved)
     else:
         # (emcee seeds its RandomState from the OS; keyed by the global RNG instead, a host-driven run is as reproducible
         # under np.random.seed as a device-resident one)

@@ -14,6 +14,10 @@ RANK / WORLD_SIZE / LOCAL_RANK / MASTER_ADDR / MASTER_PORT works, torch.distribu
 
     python -m golemflavor_amd.scan --config C4 [--nwalkers 2048 --burnin 100 --nsteps 200]
     python -m torch.distributed.run --nproc-per-node 8 ... -m golemflavor_amd.scan --config C5
+    python -m golemflavor_amd.scan --config C5 --energy-resolved [--binned-measurement FILE.npy] [--binned-smearing S ...]
+
+--energy-resolved samples every C5 grid point under the energy-resolved Gaussian likelihood (sens.py's flags, with
+their meanings): the chain files and every writer's files carry `_ebins` behind the point's stem.
 
 Row order.  A grid point's result holds one row per stored sample, in the order the device stores them: row
 step * nwalkers + walker, so `rows.reshape(nsteps, nwalkers, -1)` recovers the chain (step, walker, column).  Every delivery
@@ -139,10 +143,16 @@ class _SensPoint:
     """One grid point of the 12-dim posterior (scripts/fr.py:62-104 paramset, llh.py:121-130 with the
     Gaussian substitute): logLam seeded around the point's scale; result: the flat chain (.., 12)."""
 
-    def __init__(self, point, g, *, nwalkers, device, seed=25, smearing=0.02):
+    def __init__(self, point, g, *, nwalkers, device, seed=25, smearing=0.02, binned=None):
         dim, tex, source, scale = point
         ps, box, desc = self.descriptor(point, smearing)
         self.f = llh_utils.LnProb(desc, device=device, on_nonunitary="-inf")
+        if binned is not None:                                # --energy-resolved: a measurement per energy bin (DESIGN.md 6i)
+            try:
+                self.f.model.set_binned_measurement(binned)
+            except BaseException:
+                self.f.close()
+                raise
         rng = np.random.default_rng(seed + g)
         self.p0 = rng.uniform(box[:, 0], box[:, 1], size=(nwalkers, 12))
         lo, hi = Cf.SCALE_BOUNDARIES[dim]
@@ -166,6 +176,12 @@ class _SensPoint:
             cls._paramsets[key] = (asimov, ps, np.array(ps.seeds, dtype=float), template)
         asimov, ps, box, template = cls._paramsets[key]
         return ps, box, _patched(template, source_ratio=source, texture=tex)
+
+    @classmethod
+    def asimov(cls, dim, smearing=0.02):
+        """the Asimov paramset the points of dimension `dim` are centred on"""
+        cls.descriptor((dim, Texture.OET, (1.0, 0.0, 0.0), 0.0), smearing)
+        return cls._paramsets[(dim, smearing)][0]
 
     @staticmethod
     def assemble(samples, frs, status):
@@ -528,7 +544,7 @@ def _post_models(jobs, order):
     return [jobs[g].post_model for g in order] if getattr(first, "post_model", None) is not None else None
 
 
-def run_points(points, indices, make, burnin, nsteps, stacked=True, seed=25, gather=None, writers=()):
+def run_points(points, indices, make, burnin, nsteps, stacked=True, seed=25, gather=None, writers=(), energy_resolved=False):
     """All of this rank's grid points advance together.  stacked (default): one sampler, one ensemble per
     grid point's posterior, every half-step of every chain in one launch; chain g draws from random stream g (its
     GLOBAL grid index), so that a grid point's chain does not depend on the number of ranks.  Otherwise one sampler per
@@ -537,7 +553,10 @@ def run_points(points, indices, make, burnin, nsteps, stacked=True, seed=25, gat
     gather: None -> {grid index: collected array} of this rank's points (host);
             a `DeviceGather` -> every grid point's array, in grid order, on rank 0 (None elsewhere): the chain blocks
             go from the sampler's device buffer through RCCL and cross PCIe once.
-    writers: `PointWriter`s -> each reduces and saves every point's chain, in this order, while its sampler holds the chain."""
+    writers: `PointWriter`s -> each reduces and saves every point's chain, in this order, while its sampler holds the chain.
+    energy_resolved: every point's posterior carries a measurement per energy bin and is sampled under it
+    (`DeviceEnsembleSampler(energy_resolved=True)`); the unstacked samplers then draw from the stacked run's streams -- `seed`,
+    stream g -- so that a point's chain is the same either way."""
     t0 = time.perf_counter()
     jobs = {g: make(points[g], g) for g in indices}
     if not jobs:
@@ -549,7 +568,7 @@ def run_points(points, indices, make, burnin, nsteps, stacked=True, seed=25, gat
     if stacked:
         t0 = time.perf_counter()
         sampler = mcmc_utils.DeviceEnsembleSampler(first.nwalkers, first.ndim, [jobs[g].f for g in order], seed=seed,
-                                                   stream_ids=order)
+                                                   stream_ids=order, energy_resolved=energy_resolved)
         sampler.on_nonunitary = "-inf"
         PHASES["sampling: sampler created"] = time.perf_counter() - t0
         # burn-in: enqueued, and only then -- while the GPU works through it and this thread has nothing to launch or allocate --
@@ -612,7 +631,11 @@ def run_points(points, indices, make, burnin, nsteps, stacked=True, seed=25, gat
                for i, g in enumerate(order)}
         PHASES["collect"] = time.perf_counter() - t0
         return out
-    samplers = {g: mcmc_utils.DeviceEnsembleSampler(j.nwalkers, j.ndim, j.f, seed=j.seed) for g, j in jobs.items()}
+    if energy_resolved:
+        samplers = {g: mcmc_utils.DeviceEnsembleSampler(j.nwalkers, j.ndim, j.f, seed=seed, stream_ids=[g], energy_resolved=True)
+                    for g, j in jobs.items()}
+    else:
+        samplers = {g: mcmc_utils.DeviceEnsembleSampler(j.nwalkers, j.ndim, j.f, seed=j.seed) for g, j in jobs.items()}
     for g, sm in samplers.items():
         sm.on_nonunitary = "-inf"
         sm.run_async(jobs[g].p0, burnin, storechain=False)
@@ -913,7 +936,21 @@ def point_filename(config, point, a):
         return "mc_texture%s_logLam%+.3f" % (mcmc_utils.chain_identifier(ns), scale)
     dim, tex, source, scale = point
     ns = argparse.Namespace(dimension=dim, source_ratio=source, texture=tex)
-    return "fr%s_logLam%+.3f" % (mcmc_utils.chain_identifier(ns), scale)
+    ebins = "_ebins" if getattr(a, "energy_resolved", False) else ""       # never over a flux-averaged result (as sens.identifier)
+    return "fr%s_logLam%+.3f%s" % (mcmc_utils.chain_identifier(ns), scale, ebins)
+
+
+def binned_measurements(a, dims):
+    """{dimension: the `BinnedMeasurement` of --energy-resolved / --binned-measurement / --binned-smearing} for the C5 points'
+    dimensions: `sens.binned_measurement` over this scan's binning, smearing and Asimov paramsets.  ValueError / OSError on a file
+    that does not fit."""
+    from .sens import binned_measurement
+    ns = argparse.Namespace(energy_resolved=True, binning=_BIN_EDGES, smearing=C5_SMEARING, binned_smearing=a.binned_smearing,
+                            binned_measurement=a.binned_measurement)
+    return {dim: binned_measurement(ns, _SensPoint.asimov(dim, C5_SMEARING)) for dim in dims}
+
+
+C5_SMEARING = 0.02       # the width of the C5 points' flux-averaged likelihood (_SensPoint)
 
 
 def main(argv=None):
@@ -966,11 +1003,35 @@ def main(argv=None):
                     help="with --reweight-injected: also save the marginals of N equal-weight rows per target, with --marginals' bins, "
                          "coverages and percentiles and, as --marginals for this configuration, over the sampled columns alone (the rows "
                          "a C5 scan saves carry no composition), reweight_marginals_<point>_t<target>.npz")
+    ap.add_argument("--energy-resolved", action="store_true",
+                    help="--config C5: sample every grid point under the energy-resolved Gaussian likelihood (a measurement per energy "
+                         "bin; without a file the injected ratio in every bin) instead of the flux average; the chain files and every "
+                         "writer's files carry _ebins")
+    ap.add_argument("--binned-measurement", type=str, default=None, metavar="FILE.npy",
+                    help="energy-resolved with this measurement: an array [K, 3], one composition per energy bin of the scan's binning")
+    ap.add_argument("--binned-smearing", type=float, nargs="+", default=None, metavar="S",
+                    help="energy-resolved: ONE value is the width of the flux-averaged likelihood to be comparable with, "
+                         "sigma_k = S / sqrt(w_k) (default: the scan's smearing, %g); K values are the widths of the bins themselves" % C5_SMEARING)
     ap.add_argument("--marginal-bins-1d", type=int, default=100)
     ap.add_argument("--marginal-bins-2d", type=int, default=50)
     ap.add_argument("--marginal-coverage", type=float, nargs="+", default=[90., 99.], metavar="COVERAGE")
     ap.add_argument("--marginal-percentiles", type=float, nargs="+", default=[5., 50., 95.], metavar="Q")
     a = ap.parse_args(argv)
+    if a.binned_measurement is not None:
+        a.energy_resolved = True
+    if a.binned_smearing is not None:
+        if not a.energy_resolved:
+            ap.error("--binned-smearing needs --energy-resolved or --binned-measurement")
+        K = len(_BIN_EDGES) - 1
+        if len(a.binned_smearing) not in (1, K) or not all(s > 0. for s in a.binned_smearing):
+            ap.error("--binned-smearing takes one positive value or one per energy bin (%d)" % K)
+    if a.energy_resolved:
+        if a.config != "C5":
+            ap.error("--energy-resolved needs chains sampled under a measurement (--config C5); the chains of --config C4 sample the "
+                     "priors only")
+        if a.reweight_injected is not None:
+            ap.error("--reweight-injected does not combine with --energy-resolved: its targets replace the chain's own Gaussian "
+                     "measurement, and an energy-resolved chain has no single one (--reweight-binned, a model target, does)")
     if a.elements and not a.marginals:
         ap.error("--elements needs --marginals (it adds the element-space marginals to them)")
     if a.diagnostics and not a.datadir:
@@ -1047,7 +1108,13 @@ def main(argv=None):
     else:
         pts = sens_grid()[:a.points]
         nw = a.nwalkers or 512
-        make = lambda p, g: _SensPoint(p, g, nwalkers=nw, device=device)  # noqa: E731
+        meas = {}
+        if a.energy_resolved:                  # every rank from its own command line: nothing is broadcast
+            try:
+                meas = binned_measurements(a, sorted({p[0] for p in pts}))
+            except (OSError, ValueError) as exc:
+                ap.error(str(exc))
+        make = lambda p, g: _SensPoint(p, g, nwalkers=nw, device=device, binned=meas.get(p[0]))  # noqa: E731
         evals_per_point = nw * (a.burnin + a.nsteps)
     mine = gdist.shard(len(pts), rank, world)
     stacked = not a.no_stack
@@ -1092,21 +1159,21 @@ def main(argv=None):
         one = a.reweight_smearing[0] if a.reweight_smearing is not None and len(a.reweight_smearing) == 1 else None
         writers.append(BinnedReweightWriter(a.datadir, name_of, rw_binned, smearing=one))
     if a.datadir and not want_gather:
-        local = run_points(pts, mine, make, a.burnin, a.nsteps, stacked=stacked, writers=writers)
+        local = run_points(pts, mine, make, a.burnin, a.nsteps, stacked=stacked, writers=writers, energy_resolved=a.energy_resolved)
         gather_name = "none: every rank saved its own files (--datadir)"
     elif shared:
         g = SharedHostGather(control, rank, world, arena=arena)
-        chains = run_points(pts, mine, make, a.burnin, a.nsteps, stacked=True, gather=g, writers=writers)
+        chains = run_points(pts, mine, make, a.burnin, a.nsteps, stacked=True, gather=g, writers=writers, energy_resolved=a.energy_resolved)
         gather_name = g.stats.get("delivery", g.kind)
         g.release()
     elif device_gather:
         stage = Model(compile_model(Cf.unitary_paramset(), "PRIOR_ONLY", source_ratio=(1, 2, 0)), device=device)
         chains = run_points(pts, mine, make, a.burnin, a.nsteps, stacked=True,
-                            gather=DeviceGather(rccl, rank, world, stage, control=control), writers=writers)
+                            gather=DeviceGather(rccl, rank, world, stage, control=control), writers=writers, energy_resolved=a.energy_resolved)
         stage.close()
         gather_name = ("%s device gather to rank 0" % rccl.kind) if rccl is not None else "device -> host"
     else:
-        local = run_points(pts, mine, make, a.burnin, a.nsteps, stacked=stacked, writers=writers)
+        local = run_points(pts, mine, make, a.burnin, a.nsteps, stacked=stacked, writers=writers, energy_resolved=a.energy_resolved)
         t1 = time.perf_counter()
         chains = gdist.gather_chains_to_root(local, len(pts), control)
         PHASES["gather"] = time.perf_counter() - t1
@@ -1139,6 +1206,7 @@ def main(argv=None):
             mcmc_utils.save_chains(np.stack(chains), a.outfile)
         print(json.dumps({"config": a.config, "grid_points": len(pts), "ranks": world, "walkers": nw, "burnin": a.burnin,
                           "nsteps": a.nsteps, "stacked": stacked, "gather": gather_name,
+                          **({"likelihood": "energy-resolved"} if a.energy_resolved else {}),
                           "rccl_error": rccl_err, "librccl": gdist.rccl_library_info(),
                           "diagnostic_overrides": _lib.diagnostic_overrides(),
                           "gather_stats": GATHER_STATS, "nonunitary": LAST_NONUNITARY,

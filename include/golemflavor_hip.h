@@ -255,6 +255,15 @@ int gf_sampler_create(gf_model* m, int nchains, int nwalkers, uint64_t seed, dou
  * grid point; here all of a GPU's grid points advance in one launch per half-step).  Chain ch samples the
  * posterior of models[ch]; the models share device, ndim and mode and must outlive the sampler. */
 int gf_sampler_create_multi(gf_model* const* models, int nchains, int nwalkers, uint64_t seed, double a, gf_sampler** out);
+/* A sampler of the energy-resolved Gaussian likelihood: every model carries a binned measurement
+ * (gf_model_set_binned_measurement; GF_ERR_INVALID_ARG naming the first model that carries none).  nmodels == 1: every chain
+ * samples models[0]; nmodels == nchains: chain ch samples models[ch], under gf_sampler_create_multi's conditions.  The two calls
+ * above refuse such a model (GF_ERR_UNSUPPORTED): this is the explicit way in.  The stored lnprob is bit for bit gf_lnprob_batch's of
+ * the same model.  One launch shape, one launch per half-ensemble update.  The models' tables are taken here and keep their
+ * addresses: a measurement set between two runs is what the next run samples.  Everything that reads a stored chain works as
+ * for any sampler, except gf_sampler_reweight* with measurement targets (bestfit_fr / smearing / offset): GF_ERR_UNSUPPORTED,
+ * such a chain has no single Gaussian measurement to replace; model targets work. */
+int gf_sampler_create_binned(gf_model* const* models, int nmodels, int nchains, int nwalkers, uint64_t seed, double a, gf_sampler** out);
 /* Random stream of each chain, ids [nchains] (default: the chain's index in this sampler).  A grid scan passes the
  * global grid index, so that a grid point's chain is the same whichever rank runs it and whatever else shares its
  * sampler (the reference's jobs are seeded per job, scripts/mc_texture.py:137-138).  Before the first run. */
