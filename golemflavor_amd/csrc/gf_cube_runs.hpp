@@ -3,6 +3,7 @@
 // the sum each rounded), the run's base value on every other column.  Random numbers: Philox4x32-10, key = seed, counter =
 // (run id, iteration word, point, step): a run's result does not depend on the other runs of the launch or on the launch shape.
 #pragma once
+#include <cmath>
 #include <cstring>
 #include <cstddef>
 #include <new>
@@ -46,6 +47,10 @@ struct GfCubeRunsHost {
 
 namespace {
 using namespace gfdev;
+
+// iteration word of the seeding draws of the maximiser (gf_simplex.hip) and of a realisation ensemble's shared seeding (gf_toys.hip):
+// the same points for the same run id; the nested sampler's initial draws take 0xFFFFFFFF
+constexpr uint32_t SX_SEED_ITER = 0xFFFFFFFEu;
 
 // two uniform doubles in [0, 1), 53 bits each, of counter (run id, it, point, step)
 __device__ __forceinline__ void cube_uniform2(const GfCubeRuns& a, int r, uint32_t it, uint32_t point, uint32_t step, double out[2])
@@ -231,6 +236,38 @@ int cube_runs_set_ids(GfCubeRunsHost& h, const GfCubeRuns& a, const uint64_t* id
     GF_HIP(hipSetDevice(h.device));
     GF_HIP(hipMemcpyAsync(h.d_run_ids, ids, sizeof(uint64_t) * (size_t)a.nruns, hipMemcpyHostToDevice, h.stream));
     GF_HIP(hipStreamSynchronize(h.stream));
+    return GF_OK;
+}
+
+// A measurement of its own for every run: bf [R][3] and smearing [R] replace bf, inv_smear, gauss_c0, gauss_mh and
+// gauss_k of d_commons[r], the constants by gf_internal_gauss_consts as gf_model_create derives them -- the run's kernels, which read
+// the measurement from d_commons alone, then evaluate what a model compiled with that measurement evaluates.  The models themselves,
+// and with them the bulk path of cube_runs_draw, keep theirs.  Flux-averaged Gaussian likelihoods only; `who` names the call.
+int cube_runs_set_measurements(GfCubeRunsHost& h, const GfCubeRuns& a, const double* bf, const double* smearing, const char* who)
+{
+    if (h.initialised) return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: before the first run", who);
+    if (h.binned)
+        return gf_fail_msg(GF_ERR_UNSUPPORTED, "%s: the runs' models carry a binned measurement; a run's own measurement replaces the flux-averaged one only", who);
+    if (h.mode != MODE_SM_GAUSS && h.mode != MODE_BSM_GAUSS)
+        return gf_fail_msg(GF_ERR_UNSUPPORTED, "%s: the models have no Gaussian measurement (mode %d)", who, h.mode);
+    const size_t R = a.nruns;
+    std::vector<GfCommon> hc(R);
+    for (size_t r = 0; r < R; ++r) {
+        const double sm = smearing[r];
+        if (!(sm > 0.0) || !std::isfinite(sm) || !std::isfinite(bf[3 * r]) || !std::isfinite(bf[3 * r + 1]) || !std::isfinite(bf[3 * r + 2]))
+            return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: run %zu needs a finite measurement and a smearing > 0", who, r);
+        const GfCommon* c; const GfBsm* tb; const double* pt; int device, cus, nb;
+        const int rc = gf_model_constants(h.models[r], &c, &tb, &pt, &device, &cus, &nb);
+        if (rc != GF_OK) return rc;
+        hc[r] = *c;
+        for (int k = 0; k < 3; ++k) hc[r].bf[k] = bf[3 * r + k];
+        gf_internal_gauss_consts(sm, &hc[r].inv_smear, &hc[r].gauss_c0, &hc[r].gauss_mh, &hc[r].gauss_k);
+        if (!std::isfinite(hc[r].gauss_mh) || !std::isfinite(hc[r].gauss_k))
+            return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: the smearing of run %zu is outside the range of the Gaussian's constants", who, r);
+    }
+    GF_HIP(hipSetDevice(h.device));
+    GF_HIP(hipMemcpyAsync(h.d_commons, hc.data(), sizeof(GfCommon) * R, hipMemcpyHostToDevice, h.stream));
+    GF_HIP(hipStreamSynchronize(h.stream));                              // hc goes out of scope
     return GF_OK;
 }
 

@@ -34,7 +34,6 @@
 
 namespace {
 
-constexpr uint32_t SX_SEED_ITER = 0xFFFFFFFEu;     // iteration word of the seeding draws (the nested sampler's is 0xFFFFFFFF)
 constexpr int SX_PICK_BLOCK = 256;
 constexpr int SX_STEP_BLOCK = 64;
 constexpr int32_t SX_PARKED = -1;                  // status of a candidate waiting for the settle kernel
@@ -190,6 +189,20 @@ __global__ __launch_bounds__(SX_PICK_BLOCK) void k_sx_pick(const SxArgs a)
         st.done = 1; st.npend = 0;
     }
     if (tid == 0) { a.runs[r].nstarts = nf + a.nuser; a.runs[r].active = nf + a.nuser; }
+}
+
+// Realisation ensembles (gf_toys.hip): run r keeps the first counts[r] of its caller's starts, the rest become unused, as the starts
+// behind a run's finite seeds are -- right behind k_sx_pick, before the first evaluation round.  One workgroup per run.
+__global__ __launch_bounds__(SX_PICK_BLOCK) void k_sx_trim(const SxArgs a, const int32_t* __restrict__ counts)
+{
+    const int r = blockIdx.x;
+    if (a.runs[r].failed) return;
+    const int c = counts[r] < a.S ? counts[r] : a.S;                 // (a later gf_simplex_set_starts may have given fewer starts)
+    for (int j = c + threadIdx.x; j < a.S; j += SX_PICK_BLOCK) {
+        SxStart& st = a.starts[(int64_t)r * a.S + j];
+        st.done = 1; st.npend = 0; st.used = 0;
+    }
+    if (threadIdx.x == 0) { a.runs[r].nstarts = c; a.runs[r].active = c; }
 }
 
 // every pending point of every live start (blockIdx.y = run); LPW lanes per point as in the nested sampler's walk
@@ -413,6 +426,7 @@ struct gf_simplex {
     SxArgs a = {};
     GfSettleArgs sa = {};
     double* d_ustart = nullptr;
+    int32_t* d_counts = nullptr;        // gf_toys_set_start_counts: [nruns], NULL: every run keeps all of the caller's starts
 };
 
 namespace {
@@ -443,6 +457,10 @@ int sx_init(gf_simplex* s)
     }
     hipLaunchKernelGGL(k_sx_pick, dim3(a.nruns), dim3(SX_PICK_BLOCK), 0, s->rs.stream, a);
     GF_HIP(hipGetLastError());
+    if (s->d_counts) {
+        hipLaunchKernelGGL(k_sx_trim, dim3(a.nruns), dim3(SX_PICK_BLOCK), 0, s->rs.stream, a, s->d_counts);
+        GF_HIP(hipGetLastError());
+    }
     s->rs.initialised = 1;
     return GF_OK;
 }
@@ -506,6 +524,32 @@ int gf_simplex_set_starts(gf_simplex* s, int nuser, const double* cube)
     return GF_OK;
 }
 
+int gf_toys_set_measurements(gf_simplex* s, const double* bf, const double* smearing)
+{
+    if (!s || !bf || !smearing) return GF_ERR_INVALID_ARG;
+    // the set's own seeding goes through the models' bulk path (cube_runs_draw): it would score under the models' measurement
+    if (s->a.nseed > 0)
+        return gf_fail_msg(GF_ERR_INVALID_ARG, "gf_toys_set_measurements: the set draws %d seed points per run, which its models would score; "
+                           "give the starts (nseed = 0, gf_simplex_set_starts)", s->a.nseed);
+    return cube_runs_set_measurements(s->rs, s->a, bf, smearing, "gf_toys_set_measurements");
+}
+
+int gf_toys_set_start_counts(gf_simplex* s, const int32_t* counts)
+{
+    if (!s || !counts) return GF_ERR_INVALID_ARG;
+    if (s->rs.initialised) return gf_fail_msg(GF_ERR_INVALID_ARG, "gf_toys_set_start_counts: before the first run");
+    if (s->a.nstarts != 0)
+        return gf_fail_msg(GF_ERR_INVALID_ARG, "gf_toys_set_start_counts: the set picks %d starts of its own per run; the counts are of the caller's starts alone", s->a.nstarts);
+    for (int r = 0; r < s->a.nruns; ++r)
+        if (counts[r] < 0 || counts[r] > s->a.nuser)
+            return gf_fail_msg(GF_ERR_INVALID_ARG, "gf_toys_set_start_counts: run %d keeps %d of %d starts", r, counts[r], s->a.nuser);
+    GF_HIP(hipSetDevice(s->rs.device));
+    if (!s->d_counts) GF_HIP(hipMalloc((void**)&s->d_counts, sizeof(int32_t) * (size_t)s->a.nruns));
+    GF_HIP(hipMemcpyAsync(s->d_counts, counts, sizeof(int32_t) * (size_t)s->a.nruns, hipMemcpyHostToDevice, s->rs.stream));
+    GF_HIP(hipStreamSynchronize(s->rs.stream));
+    return GF_OK;
+}
+
 int gf_simplex_set_options(gf_simplex* s, double xatol, double fatol, int maxiter, int adaptive, int restarts)
 {
     if (!s || !(xatol >= 0.0) || !(fatol >= 0.0) || maxiter < 1 || (adaptive != 0 && adaptive != 1) || restarts < 0)
@@ -522,7 +566,7 @@ void gf_simplex_destroy(gf_simplex* s)
     if (!s) return;
     SxArgs& a = s->a;
     cube_runs_free(s->rs, a);
-    void* ptrs[] = {s->d_ustart, a.runs, a.starts, a.sim, a.fsim, a.tmp, a.pts, a.lnq, a.pst, a.seed_u, a.seed_l, a.seed_st, a.theta};
+    void* ptrs[] = {s->d_ustart, s->d_counts, a.runs, a.starts, a.sim, a.fsim, a.tmp, a.pts, a.lnq, a.pst, a.seed_u, a.seed_l, a.seed_st, a.theta};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     delete s;
 }

@@ -190,12 +190,15 @@ def nelder_mead_speculative(f_batch, x0, xatol=DEFAULT_XATOL, fatol=DEFAULT_FATO
 class SimplexMaximizer(_CubeRuns):
     """`nruns` independent maximisations of ln_prob (nested._CubeRuns: models, cols, bases, run_ids, labels).  Starts: the
     `nstarts` best finite points of `nseed` uniform cube points per run, then `starts` ([nruns][k][nscan] or [k][nscan] cube
-    points; optional).  Options as scipy's Nelder-Mead (xatol, fatol, maxiter = 200 n by default, adaptive) plus `restarts`."""
+    points; optional).  Options as scipy's Nelder-Mead (xatol, fatol, maxiter = 200 n by default, adaptive) plus `restarts`.
+    `measurements` = (bestfit_fr [nruns][3], smearing [nruns] or one value): run r maximises under that Gaussian measurement in place
+    of its model's (needs nseed = 0, the flux-averaged likelihood).  `start_counts` [nruns] (with nstarts = 0): run r keeps
+    the first start_counts[r] of `starts` only."""
     _abi, _what = "simplex", "profile run"
 
     def __init__(self, models, cols, bases, nstarts=DEFAULT_STARTS, nseed=DEFAULT_SEED_POINTS, seed=0, starts=None,
                  on_nonunitary="raise", xatol=DEFAULT_XATOL, fatol=DEFAULT_FATOL, maxiter=None, adaptive=False,
-                 restarts=DEFAULT_RESTARTS, run_ids=None, labels=None):
+                 restarts=DEFAULT_RESTARTS, run_ids=None, labels=None, measurements=None, start_counts=None):
         hs = self._open(models, cols, bases, on_nonunitary, labels)
         self.nstarts, self.nseed, self.seed = int(nstarts), int(nseed), int(seed)
         self.maxiter = int(maxiter) if maxiter is not None else 200 * self.nscan
@@ -217,6 +220,19 @@ class SimplexMaximizer(_CubeRuns):
             self.nuser = st.shape[1]
             _lib.check(self._L.gf_simplex_set_starts(self._h, self.nuser, st.ctypes.data_as(_lib._dp)), "gf_simplex_set_starts")
         self._set_run_ids(run_ids)
+        if measurements is not None:
+            self.set_measurements(*measurements)
+        if start_counts is not None:
+            cnt = np.ascontiguousarray(np.broadcast_to(np.asarray(start_counts, dtype=np.int32), (self.nruns,)))
+            _lib.check(self._L.gf_toys_set_start_counts(self._h, cnt.ctypes.data_as(_lib._ip)), "gf_toys_set_start_counts")
+
+    def set_measurements(self, bestfit_fr, smearing):
+        """A Gaussian measurement of its own for every run, before the first run(): bestfit_fr [nruns][3], smearing [nruns] or one
+        value.  Run r then evaluates what a Model compiled with (bestfit_fr[r], smearing[r]) evaluates."""
+        bf = np.ascontiguousarray(np.broadcast_to(np.asarray(bestfit_fr, dtype=np.float64), (self.nruns, 3)))
+        sm = np.ascontiguousarray(np.broadcast_to(np.asarray(smearing, dtype=np.float64), (self.nruns,)))
+        _lib.check(self._L.gf_toys_set_measurements(self._h, bf.ctypes.data_as(_lib._dp), sm.ctypes.data_as(_lib._dp)),
+                   "gf_toys_set_measurements")
 
     def max_rounds(self):
         """Evaluation rounds after which every start has finished: per minimize call one round for the initial simplex and at

@@ -1,0 +1,301 @@
+"""Realisation ensembles: the profile likelihood of many mock measurements at every new-physics scale in one call (DESIGN.md 6j;
+gf_toys.hip, include/golemflavor_hip.h gf_toys_*, gf_toys_set_measurements).
+
+The frequentist statistic of scripts/sens.py is -2 (max lnL(scale) - max lnL(null)); the reference cuts its Asimov curve at a chi2
+quantile (Wilks' theorem) and notes that the statistic's distribution "can be approximated by generating mock data or realisations of
+the null hypothesis", which it finds computationally difficult (docs/source/statistics.rst:95-110).  Here a realisation of the
+Gaussian measurement (bf, smearing) is m = bf + smearing z, z ~ N(0, I_3) -- the generative model of multi_gaussian's isotropic
+Gaussian, not projected onto the simplex -- and every realisation is profiled at every scale: the scales' seed points are drawn and
+propagated once, ranked under every realisation on the device, and the best K of each (scale, realisation) polished by the device
+Nelder-Mead maximiser under that realisation's measurement.
+
+    draw_realisations      m = bf + smearing z on the host (numpy's default_rng): bring your own instead if you like
+    ToySeeds               the shared seeding: the seeds of every scale, their selection under realisations
+    realisation_scan       max lnL and the test statistic of every (realisation, scale), the limit of every realisation
+    sensitivity_band       quantiles of the limits: the median expected limit with its one- and two-sigma band
+    ts_quantiles           the empirical critical value of the statistic per scale, to hold against chi2.ppf(0.95, 1)
+    save_realisations      the scan's arrays as one .npz
+"""
+import ctypes as C
+import time
+
+import numpy as np
+
+from . import _lib
+from . import fr as fr_utils
+from . import rowsets
+from .enums import ParamTag
+from .nested import _opt, _scan_models
+from .profile_llh import (DEFAULT_FATOL, DEFAULT_RESTARTS, DEFAULT_SEED_POINTS, DEFAULT_XATOL, SimplexMaximizer,
+                          profile_likelihood_limit)
+
+__all__ = ["draw_realisations", "ToySeeds", "realisation_scan", "sensitivity_band", "ts_quantiles", "save_realisations",
+           "DEFAULT_TOY_STARTS", "MAX_TOY_STARTS", "MAX_RUNS"]
+
+DEFAULT_TOY_STARTS = 8
+MAX_TOY_STARTS = _lib.GF_TOY_MAX_STARTS
+MAX_RUNS = 65535              # runs of one maximiser (gf_simplex_create)
+BAND_QUANTILES = (2.5, 16., 50., 84., 97.5)
+
+
+def draw_realisations(bf, smearing, n, seed=0):
+    """`n` realisations m = bf + smearing z of the Gaussian measurement (bf [3], smearing), z ~ N(0, I_3) from
+    np.random.default_rng(seed): [n][3].  Not projected onto the simplex: the likelihood's own generative model."""
+    bf = np.asarray(bf, dtype=np.float64).reshape(3)
+    if not (float(smearing) > 0.0 and np.isfinite(smearing)):
+        raise ValueError("smearing must be positive and finite")
+    z = np.random.default_rng(seed).standard_normal((int(n), 3))
+    return bf + float(smearing) * z
+
+
+class ToySeeds:
+    """The shared seeding of a realisation ensemble: `nseed` uniform cube points per scale (models, cols, bases, run_ids as for
+    SimplexMaximizer -- the points its seeding draws for the same seed and run id), evaluated once by each scale model's bulk path.
+    `nonunitary_seeds` [nscales]: the seeds the reference would have raised on."""
+
+    def __init__(self, models, cols, bases, nseed=DEFAULT_SEED_POINTS, seed=0, run_ids=None):
+        self._L = _lib.lib()
+        self.models = list(models)
+        self.nscales = len(self.models)
+        self.cols = np.ascontiguousarray(cols, dtype=np.int32)
+        self.nscan, self.nseed = len(self.cols), int(nseed)
+        ndim = self._L.gf_model_ndim(rowsets.handle(self.models[0]))
+        b = np.asarray(bases, dtype=np.float64)
+        if b.ndim == 1:
+            b = np.tile(b, (self.nscales, 1))
+        self.bases = np.ascontiguousarray(b.reshape(self.nscales, ndim))
+        h = C.c_void_p()
+        _lib.check(self._L.gf_toys_create(rowsets.model_handles(self.models, self.nscales), self.nscales, self.nscan,
+                                          self.cols.ctypes.data_as(_lib._ip), self.bases.ctypes.data_as(_lib._dp), self.nseed,
+                                          int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(h)), "gf_toys_create")
+        self._h = h
+        try:
+            if run_ids is not None:
+                ids = np.ascontiguousarray(run_ids, dtype=np.uint64)
+                _lib.check(self._L.gf_toys_set_run_ids(self._h, ids.ctypes.data_as(C.POINTER(C.c_uint64))), "gf_toys_set_run_ids")
+            nu = np.zeros(self.nscales, np.uint32)
+            _lib.check(self._L.gf_toys_seed(self._h, nu.ctypes.data_as(C.POINTER(C.c_uint32))), "gf_toys_seed")
+            self.nonunitary_seeds = nu
+        except BaseException:
+            self.close()
+            raise
+
+    def _measurements(self, bestfit_fr, smearing):
+        bf = np.ascontiguousarray(bestfit_fr, dtype=np.float64)
+        if bf.ndim not in (2, 3) or bf.shape[-1] != 3 or (bf.ndim == 3 and bf.shape[0] != self.nscales):
+            raise ValueError("measurements must be [T][3] or [nscales][T][3]")
+        T = bf.shape[-2]
+        sm = np.ascontiguousarray(np.broadcast_to(np.asarray(smearing, dtype=np.float64), (T,)))
+        return bf, sm, T
+
+    def select(self, bestfit_fr, smearing, K):
+        """The starts of every (scale, realisation): the K best seeds under score = lp + gauss(m_t, fr), score descending then seed
+        index ascending, finite scores only.  bestfit_fr [T][3] (shared by the scales) or [nscales][T][3]; smearing [T] or one value.
+        Returns dict(cube [nscales][T][K][nscan] (NaN behind the count), index, score [nscales][T][K] (-1, -inf), count [nscales][T])."""
+        bf, sm, T = self._measurements(bestfit_fr, smearing)
+        K = int(K)
+        S = self.nscales
+        out = dict(cube=np.empty((S, T, max(K, 0), self.nscan)), index=np.empty((S, T, max(K, 0)), np.int32),
+                   score=np.empty((S, T, max(K, 0))), count=np.empty((S, T), np.int32))
+        _lib.check(self._L.gf_toys_select(self._h, bf.ctypes.data_as(_lib._dp), int(bf.ndim == 3), sm.ctypes.data_as(_lib._dp), T, K,
+                                          out["cube"].ctypes.data_as(_lib._dp), out["index"].ctypes.data_as(_lib._ip),
+                                          out["score"].ctypes.data_as(_lib._dp), out["count"].ctypes.data_as(_lib._ip)), "gf_toys_select")
+        return out
+
+    def scores(self, bestfit_fr, smearing):
+        """Every score the selection ranks, [nscales][T][nseed]."""
+        bf, sm, T = self._measurements(bestfit_fr, smearing)
+        out = np.empty((self.nscales, T, self.nseed))
+        _lib.check(self._L.gf_toys_scores(self._h, bf.ctypes.data_as(_lib._dp), int(bf.ndim == 3), sm.ctypes.data_as(_lib._dp), T,
+                                          out.ctypes.data_as(_lib._dp)), "gf_toys_scores")
+        return out
+
+    def seeds(self, scale=0):
+        """Scale `scale`'s seeds: dict(cube [nseed][nscan], theta [nseed][ndim] (the device's map: product and sum each rounded),
+        lnprob (the scale model's own), lp (the prior sum, -inf outside the box), fr [nseed][3], status)."""
+        M = self.nseed
+        out = dict(cube=np.empty((M, self.nscan)), lnprob=np.empty(M), lp=np.empty(M), fr=np.empty((M, 3)), status=np.empty(M, np.int32))
+        _lib.check(self._L.gf_toys_get_seeds(self._h, int(scale), *[out[k].ctypes.data_as(_lib._dp) for k in ("cube", "lnprob", "lp", "fr")],
+                                             out["status"].ctypes.data_as(_lib._ip)), "gf_toys_get_seeds")
+        desc = getattr(self.models[scale], "model", self.models[scale]).desc
+        lo, hi = np.asarray(desc.lo)[self.cols], np.asarray(desc.hi)[self.cols]
+        theta = np.tile(self.bases[scale], (M, 1))
+        theta[:, self.cols] = (hi - lo) * out["cube"] + lo
+        out["theta"] = theta
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.gf_toys_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def toy_select(lp, fr, status, bestfit_fr, smearing, offset, K, device=0):
+    """gf_toy_select: the selection alone on host arrays (one seed set: lp [M], fr [M][3], status [M]; bestfit_fr [T][3], smearing
+    [T] or one value).  Returns (index [T][K], score [T][K], count [T])."""
+    lp = np.ascontiguousarray(lp, dtype=np.float64)
+    fr = np.ascontiguousarray(fr, dtype=np.float64).reshape(len(lp), 3)
+    status = np.ascontiguousarray(status, dtype=np.int32)
+    bf = np.ascontiguousarray(bestfit_fr, dtype=np.float64).reshape(-1, 3)
+    T, K = len(bf), int(K)
+    sm = np.ascontiguousarray(np.broadcast_to(np.asarray(smearing, dtype=np.float64), (T,)))
+    index, score, count = np.empty((T, max(K, 0)), np.int32), np.empty((T, max(K, 0))), np.empty(T, np.int32)
+    _lib.check(_lib.lib().gf_toy_select(int(device), lp.ctypes.data_as(_lib._dp), fr.ctypes.data_as(_lib._dp), status.ctypes.data_as(_lib._ip),
+                                        len(lp), bf.ctypes.data_as(_lib._dp), sm.ctypes.data_as(_lib._dp), float(offset), T, K,
+                                        index.ctypes.data_as(_lib._ip), score.ctypes.data_as(_lib._dp), count.ctypes.data_as(_lib._ip)),
+               "gf_toy_select")
+    return index, score, count
+
+
+def realisation_scan(args, asimov_paramset, llh_paramset, scales, measurements=None, ntoys=None, toy_seed=0, smearings=None,
+                     nstarts=DEFAULT_TOY_STARTS, nseed=None, run_ids=None, xatol=None, fatol=None, maxiter=None, restarts=None,
+                     adaptive=None, seed=None, on_nonunitary="raise", smearing=None, device=0, batch=None, threshold=None, check=True,
+                     binned=None):
+    """The profile likelihood of T realisations at every scale, with profile_scan's conventions (its --pl-* options, its scanned
+    columns, its seed points per scale for the same `seed` and `run_ids`).
+
+    measurements: [T][3], shared by all scales, or [S][T][3], per scale (throws under a scale's own hypothesis); None: `ntoys`
+    realisations of the model's own measurement by draw_realisations(bf, smearing, ntoys, toy_seed).  smearings: [T], default the
+    model's.  nstarts = K <= 16 starts per (realisation, scale): the best seeds under that realisation.  batch: realisations per
+    maximiser (default: as many as keep its runs within 65535); no result depends on it.
+
+    For realisation t and scale s, max_lnl[t, s] is the maximum of ln_prob over every column but the scale under (m_t, smearing_t),
+    and ts[t, s] = -2 (max_lnl[t, s] - max_lnl[t, null]), the null the row of the smallest scale.  Returns dict(scales, measurements,
+    smearings, max_lnl [T][S], ts [T][S], argmax_theta [T][S][ndim], nstarts, nfev, niter, nonunitary (points the polish counted),
+    parked, failed [T][S], start_cube [T][S][K][nscan], start_score [T][S][K] and start_count [T][S] (the selected seeds: NaN and -inf
+    behind the count), nonunitary_seeds [S], limits [T] (profile_likelihood_limit per realisation at `threshold`, NaN where it
+    gives None), seconds, seconds_seed, seconds_select, seconds_polish).  on_nonunitary == 'raise': a non-unitary seed fails every
+    run of its scale, as it fails profile_scan's run; AssertionError when `check`."""
+    if binned is not None:
+        raise ValueError("realisations are of the flux-averaged Gaussian likelihood; the energy-resolved one is not supported")
+    if on_nonunitary not in ("raise", "-inf"):
+        raise ValueError("on_nonunitary must be 'raise' or '-inf'")
+    K = int(nstarts)
+    if not 1 <= K <= MAX_TOY_STARTS:
+        raise ValueError("nstarts must be 1 to %d, the starts the shared seeding selects" % MAX_TOY_STARTS)
+    scales = np.asarray(scales, dtype=np.float64)
+    S = len(scales)
+    sm0 = float(smearing if smearing is not None else _opt(args, "smearing", 0.02))
+    if measurements is None:
+        if ntoys is None:
+            raise ValueError("give measurements or ntoys")
+        bf0 = fr_utils.angles_to_fr(asimov_paramset.from_tag(ParamTag.BESTFIT, values=True))
+        measurements = draw_realisations(bf0, sm0, ntoys, toy_seed)
+    meas = np.ascontiguousarray(measurements, dtype=np.float64)
+    if meas.ndim not in (2, 3) or meas.shape[-1] != 3 or (meas.ndim == 3 and meas.shape[0] != S):
+        raise ValueError("measurements must be [T][3] or [S][T][3]")
+    T = meas.shape[-2]
+    sms = np.ascontiguousarray(np.broadcast_to(np.asarray(sm0 if smearings is None else smearings, dtype=np.float64), (T,)))
+    per_run = MAX_RUNS // S if batch is None else int(batch)
+    if per_run < 1 or per_run * S > MAX_RUNS:
+        raise ValueError("batch must keep batch * len(scales) within %d runs" % MAX_RUNS)
+
+    def pick(v, name, default):
+        return v if v is not None else _opt(args, name, default)
+
+    cols, models, bases, labels = _scan_models(args, asimov_paramset, llh_paramset, scales, sm0, device)
+    try:
+        ndim = len(bases[0])
+        t0 = time.perf_counter()
+        with ToySeeds(models, cols, bases, nseed=int(pick(nseed, "pl_seed_points", DEFAULT_SEED_POINTS)),
+                      seed=int(seed if seed is not None else _opt(args, "seed", 0)), run_ids=run_ids) as seeds:
+            t1 = time.perf_counter()
+            sel = seeds.select(meas, sms, K)
+            nu_seeds = seeds.nonunitary_seeds.copy()
+        t2 = time.perf_counter()
+        res = dict(max_lnl=np.full((T, S), -np.inf), argmax_theta=np.full((T, S, ndim), np.nan), nstarts=np.zeros((T, S), np.int32),
+                   nfev=np.zeros((T, S), np.int64), niter=np.zeros((T, S), np.int64), nonunitary=np.zeros((T, S), np.uint32),
+                   parked=np.zeros((T, S), np.uint32), failed=np.zeros((T, S), bool))
+        dead = (nu_seeds > 0) if on_nonunitary == "raise" else np.zeros(S, bool)
+        res["failed"][:, dead] = True
+        opts = dict(xatol=float(pick(xatol, "pl_xatol", DEFAULT_XATOL)), fatol=float(pick(fatol, "pl_fatol", DEFAULT_FATOL)),
+                    maxiter=pick(maxiter, "pl_maxiter", None), adaptive=bool(pick(adaptive, "pl_adaptive", True)),
+                    restarts=int(pick(restarts, "pl_restarts", DEFAULT_RESTARTS)), on_nonunitary=on_nonunitary)
+        count = sel["count"]                                              # [S][T]
+        for lo in range(0, T, per_run):
+            hi = min(T, lo + per_run)
+            ss, tt = np.nonzero(np.broadcast_to(~dead[:, None], (S, hi - lo)))
+            if len(ss) == 0:
+                continue
+            tt = tt + lo
+            order = np.lexsort((ss, tt))                                  # realisation by realisation, its scales in order
+            ss, tt = ss[order], tt[order]
+            bf_runs = meas[ss, tt] if meas.ndim == 3 else meas[tt]
+            # a run with fewer than K finite seeds keeps that many starts; the rows behind them are never evaluated
+            with SimplexMaximizer([models[s] for s in ss], cols, [bases[s] for s in ss], nstarts=0, nseed=0,
+                                  starts=np.nan_to_num(sel["cube"][ss, tt], nan=0.5), start_counts=count[ss, tt],
+                                  measurements=(bf_runs, sms[tt]),
+                                  labels=["realisation %d, %s" % (t, labels[s]) for s, t in zip(ss, tt)], **opts) as mx:
+                r = mx.run(check=False)
+            for k in res:
+                res[k][tt, ss] = r[k]
+        t3 = time.perf_counter()
+    finally:
+        for m in models:
+            m.close()
+    if check and on_nonunitary == "raise" and res["failed"].any():
+        t, s = np.argwhere(res["failed"])[0]
+        what = "a seed point of" if dead[s] else "realisation %d," % t
+        raise AssertionError("Matrix is not unitary! ({0} {1})".format(what, labels[s]))
+    null = int(np.argmin(scales))
+    with np.errstate(invalid="ignore"):
+        ts = -2.0 * (res["max_lnl"] - res["max_lnl"][:, null:null + 1])
+    limits = np.full(T, np.nan)
+    for t in range(T):
+        lim = profile_likelihood_limit(scales, res["max_lnl"][t], threshold)
+        if lim is not None:
+            limits[t] = lim
+    res.update(scales=scales, measurements=meas, smearings=sms, ts=ts, limits=limits, nonunitary_seeds=nu_seeds,
+               start_cube=np.ascontiguousarray(sel["cube"].transpose(1, 0, 2, 3)), start_score=np.ascontiguousarray(sel["score"].transpose(1, 0, 2)),
+               start_count=np.ascontiguousarray(count.T),
+               seconds=t3 - t0, seconds_seed=t1 - t0, seconds_select=t2 - t1, seconds_polish=t3 - t2)
+    return res
+
+
+def sensitivity_band(limits, quantiles=BAND_QUANTILES):
+    """The band of the limits over realisations: dict(quantiles, limits (np.percentile of the realisations that have a limit; NaN
+    when none has), n, n_without_limit).  `limits`: realisation_scan's, NaN or None where a realisation sets no limit."""
+    lim = np.array([np.nan if v is None else v for v in np.asarray(limits, dtype=object).ravel()], dtype=np.float64)
+    have = lim[np.isfinite(lim)]
+    q = np.asarray(quantiles, dtype=np.float64)
+    vals = np.percentile(have, q) if len(have) else np.full(len(q), np.nan)
+    return dict(quantiles=q, limits=vals, n=int(len(lim)), n_without_limit=int(len(lim) - len(have)))
+
+
+def ts_quantiles(ts, q=95.):
+    """The empirical critical value of the test statistic per scale: the q-th percentile (q a number or a list) over the realisations
+    (axis 0) whose statistic is finite there; NaN for a scale without one.  [S], or [len(q)][S].  To hold against Wilks' chi2.ppf(0.95, 1)
+    = 3.84, profile_likelihood_limit's default threshold, which this replaces for nobody: pass it as `threshold` if you want it."""
+    ts = np.asarray(ts, dtype=np.float64)
+    qq = np.atleast_1d(np.asarray(q, dtype=np.float64))
+    out = np.full((len(qq), ts.shape[1]), np.nan)
+    for s in range(ts.shape[1]):
+        col = ts[:, s][np.isfinite(ts[:, s])]
+        if len(col):
+            out[:, s] = np.percentile(col, qq)
+    return out if np.ndim(q) else out[0]
+
+
+SAVED = ("scales", "measurements", "smearings", "max_lnl", "ts", "argmax_theta", "nstarts", "nfev", "niter", "nonunitary",
+         "nonunitary_seeds", "failed", "limits")
+
+
+def save_realisations(path, res, quantiles=BAND_QUANTILES):
+    """realisation_scan's arrays plus the band (band_quantiles, band_limits, band_without_limit) as one .npz; returns the band."""
+    band = sensitivity_band(res["limits"], quantiles)
+    with open(path, "wb") as fh:
+        np.savez(fh, band_quantiles=band["quantiles"], band_limits=band["limits"], band_without_limit=np.int64(band["n_without_limit"]),
+                 seconds=np.float64(res["seconds"]), **{k: res[k] for k in SAVED})
+    return band

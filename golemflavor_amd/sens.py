@@ -9,7 +9,8 @@ one device call.  Prints one JSON summary line.  --posterior also writes every s
 posterior_<identifier>_scale_<10^scale:.0E>.npz beside the arrays (INTEGRATION.md has the layout).  --energy-resolved (or
 --binned-measurement FILE.npy, --binned-smearing) fits the composition of every energy bin instead of the flux average; every
 file name then carries `_ebins` behind the identifier.  The frequentist arrays hold [scale, profile max lnL] in both files: the
-statistic golemflavor/plot.py:605-608 (plot_statistic) receives.
+statistic golemflavor/plot.py:605-608 (plot_statistic) receives.  --stat-method frequentist --realisations T also profiles T mock
+measurements thrown around the injected composition and writes fr_realisations{identifier}.npz beside fr_maxllh.
 """
 import argparse
 import json
@@ -22,6 +23,7 @@ from . import configs as Cf
 from . import fr as fr_utils
 from . import nested
 from . import profile_llh
+from . import realisations as realisations_mod
 from .enums import DataType, ParamTag, StatCateg, Texture
 from .llh import BinnedMeasurement
 from .mcmc import chain_identifier
@@ -70,6 +72,13 @@ def parse_args(argv=None):
     ap.add_argument("--pl-restarts", type=int, default=profile_llh.DEFAULT_RESTARTS,
                     help="frequentist: restarts of a converged start from its best vertex")
     ap.add_argument("--pl-adaptive", type=_bool, default=True, help="frequentist: scipy's adaptive coefficients")
+    ap.add_argument("--realisations", type=int, default=None, metavar="T",
+                    help="frequentist: also profile T mock measurements m = injected composition + smearing z, z ~ N(0, I), at every "
+                         "scale, and write fr_realisations<identifier>.npz (max lnL, the statistic and the limit of every realisation, "
+                         "the band of the limits)")
+    ap.add_argument("--realisation-seed", type=int, default=0, help="with --realisations: the seed the realisations are thrown with")
+    ap.add_argument("--realisation-starts", type=int, default=realisations_mod.DEFAULT_TOY_STARTS,
+                    help="with --realisations: Nelder-Mead starts per (realisation, scale), 1 to %d" % realisations_mod.MAX_TOY_STARTS)
     ap.add_argument("--on-nonunitary", choices=["raise", "-inf"], default="raise")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--posterior", action="store_true",
@@ -100,6 +109,15 @@ def parse_args(argv=None):
         K = int(args.binning[2])
         if len(args.binned_smearing) not in (1, K) or not all(s > 0. for s in args.binned_smearing):
             ap.error("--binned-smearing takes one positive value or one per energy bin (%d)" % K)
+    if args.realisations is not None:
+        if args.stat_method is not StatCateg.FREQUENTIST:
+            ap.error("--realisations needs --stat-method frequentist (it profiles mock measurements)")
+        if args.realisations < 1 or not 1 <= args.realisation_starts <= realisations_mod.MAX_TOY_STARTS:
+            ap.error("--realisations takes T >= 1 and --realisation-starts 1 to %d" % realisations_mod.MAX_TOY_STARTS)
+        if args.energy_resolved:
+            ap.error("--realisations are of the flux-averaged likelihood: it does not combine with --energy-resolved")
+        if args.eval_segment.lower() != "all":
+            ap.error("--realisations needs every scale (a limit per realisation): it does not combine with --eval-segment")
     if args.posterior_elements and not args.posterior:
         ap.error("--posterior-elements needs --posterior (it adds the element-space marginals to it)")
     if args.posterior_spectrum is not None:
@@ -246,6 +264,26 @@ def main(argv=None):
     return 0
 
 
+def realisations_path(args):
+    """fr_realisations<identifier>.npz beside fr_maxllh<identifier>.npy."""
+    base = os.path.join(args.datadir, args.stat_method.name.lower(), args.data.name.lower())
+    return os.path.join(base, "fr_realisations" + identifier(args) + ".npz")
+
+
+def _realisations(args, scales, idx, asimov, llh_ps):
+    """--realisations: the scan, its file, and what the JSON line says of it."""
+    res = realisations_mod.realisation_scan(args, asimov, llh_ps, scales[idx], ntoys=args.realisations, toy_seed=args.realisation_seed,
+                                            nstarts=args.realisation_starts, run_ids=idx, on_nonunitary=args.on_nonunitary,
+                                            device=args.device)
+    f = realisations_path(args)
+    os.makedirs(os.path.dirname(f) or ".", exist_ok=True)
+    band = realisations_mod.save_realisations(f, res)
+    crit = realisations_mod.ts_quantiles(res["ts"], 95.)
+    return {"file": f, "n": args.realisations, "seed": args.realisation_seed, "starts": args.realisation_starts,
+            "band_quantiles": band["quantiles"].tolist(), "band_limits": band["limits"].tolist(),
+            "without_limit": band["n_without_limit"], "ts_q95": crit.tolist(), "seconds": round(res["seconds"], 4)}
+
+
 def _frequentist(args, scales, idx, asimov, llh_ps, outfile, outfile_llh, binned=None):
     res = profile_llh.profile_scan(args, asimov, llh_ps, scales[idx], run_ids=idx, on_nonunitary=args.on_nonunitary,
                                    device=args.device, binned=binned)
@@ -257,7 +295,9 @@ def _frequentist(args, scales, idx, asimov, llh_ps, outfile, outfile_llh, binned
     null = np.flatnonzero(scales[idx] == scales[0])
     ts = (-2 * (ml - ml[null[0]])).tolist() if len(null) and np.isfinite(ml[null[0]]) else None
     limit = profile_llh.profile_likelihood_limit(scales[idx], ml) if args.eval_segment is None else None
+    toys = _realisations(args, scales, idx, asimov, llh_ps) if getattr(args, "realisations", None) is not None else None
     print(json.dumps({
+        **({"realisations": toys} if toys is not None else {}),
         **({"likelihood": "energy-resolved"} if binned is not None else {}),
         "tool": "golemflavor_amd.sens", "stat_method": "FREQUENTIST", "dimension": args.dimension,
         "texture": args.texture.name, "segments": args.segments, "scales": scales[idx].tolist(), "max_lnl": ml.tolist(),

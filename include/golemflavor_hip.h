@@ -729,6 +729,51 @@ int gf_sampler_reweight_regions(gf_sampler* s, const gf_reweight_spec* rw, int64
                                 const double* coverage, int ncov, int64_t cap, int64_t* thres, int32_t* saturated, double* level_in,
                                 double* level_out, double* mass, int32_t* cells, double* density);
 
+/* ---- realisation ensembles: the shared seeding of many mock measurements --------------------------------- */
+/* A realisation of a Gaussian measurement (bf, smearing) is m = bf + smearing z, z ~ N(0, I_3) (thrown by the caller).  Profiling T of
+ * them at S scales needs S * T maximisations, but a seed point's composition, prior sum and unitarity verdict do not depend on the
+ * measurement: gf_toys draws and evaluates the nseed seed points of every scale once (the points gf_simplex_create's seeding draws for
+ * the same seed and run id, evaluated by the scale model's bulk path), and gf_toys_select ranks them under every realisation:
+ *   score(t, i) = lp_i + gauss(m_t, fr_i), lnprob's own two operations, -inf for a seed the reference would have raised on and for NaN;
+ *   the starts of (scale, t) are the K <= GF_TOY_MAX_STARTS best seeds with a score > -inf, score descending then seed index ascending.
+ * The polish is gf_simplex with nstarts = 0, nseed = 0, the scale's model once per realisation, the selected cube points as the
+ * caller's starts and gf_toys_set_measurements.  Models as for gf_simplex_create (one per scale); flux-averaged Gaussian
+ * likelihoods only (binned measurement, PRIOR_ONLY: GF_ERR_UNSUPPORTED), one likelihood offset for all. */
+#define GF_TOY_MAX_STARTS 16
+/* A measurement of its own for every run of a maximiser: bf [nruns][3] and smearing [nruns] replace the Gaussian measurement of run r's
+ * model in that run's kernels, with the constants gf_model_create derives, so the run evaluates exactly what a model compiled with
+ * (bf_r, smearing_r) evaluates.  Before the first gf_simplex_run.  Refused: a smearing that is not positive and finite, a bf that is not
+ * finite, models with a binned measurement or without a Gaussian one (GF_ERR_UNSUPPORTED), and a maximiser created with nseed > 0 --
+ * its seeding goes through the models' own lnprob and would score under their measurement. */
+int gf_toys_set_measurements(gf_simplex* s, const double* bf, const double* smearing);
+/* counts [nruns], each 0 .. nuser: run r keeps the first counts[r] of its caller's starts (gf_simplex_set_starts; the rows behind them
+ * are read but never evaluated, give them any finite value) -- a realisation with fewer finite seeds than K has fewer starts.  For a
+ * maximiser created with nstarts = 0; after gf_simplex_set_starts (should a later gf_simplex_set_starts give fewer starts, a run keeps at
+ * most those), before the first gf_simplex_run. */
+int gf_toys_set_start_counts(gf_simplex* s, const int32_t* counts);
+typedef struct gf_toys gf_toys;
+int gf_toys_create(gf_model* const* models, int nscales, int nscan, const int32_t* cols, const double* bases, int nseed, uint64_t seed,
+                   gf_toys** out);
+void gf_toys_destroy(gf_toys* t);
+/* run ids [nscales] (default: the index): the Philox stream of each scale's seeds.  Before gf_toys_seed. */
+int gf_toys_set_run_ids(gf_toys* t, const uint64_t* ids);
+/* Draws and evaluates the seeds, once.  nonunitary [nscales] (NULL = skip): the seeds the reference would have raised on.  Synchronous. */
+int gf_toys_seed(gf_toys* t, uint32_t* nonunitary);
+/* scale `scale`'s seeds (NULL = skip): cube [nseed][nscan], the scale model's own lnprob [nseed], prior sum lp [nseed] (-inf outside the
+ * box), composition fr [nseed][3], status [nseed] */
+int gf_toys_get_seeds(gf_toys* t, int scale, double* cube, double* lnprob, double* lp, double* fr, int32_t* status);
+/* The starts of every (scale, realisation).  bf [ntoys][3] shared by the scales (per_scale == 0) or [nscales][ntoys][3]; smearing
+ * [ntoys].  Out (NULL = skip): cube [nscales][ntoys][K][nscan] the selected seeds' cube points (NaN behind the count), index and score
+ * [nscales][ntoys][K] (-1 and -inf behind the count), count [nscales][ntoys].  The seeds stay on the device; synchronous. */
+int gf_toys_select(gf_toys* t, const double* bf, int per_scale, const double* smearing, int ntoys, int K, double* cube, int32_t* index,
+                   double* score, int32_t* count);
+/* every score the selection ranks, scores [nscales][ntoys][nseed] (ntoys <= 65535): for tests and estimators of the caller's own */
+int gf_toys_scores(gf_toys* t, const double* bf, int per_scale, const double* smearing, int ntoys, double* scores);
+/* The selection alone on host arrays, on `device`: lp [nseed], fr [nseed][3], status [nseed]; bf [ntoys][3], smearing [ntoys], one
+ * offset; out_index and out_score [ntoys][K], out_count [ntoys]. */
+int gf_toy_select(int device, const double* lp, const double* fr, const int32_t* status, int nseed, const double* bf,
+                  const double* smearing, double offset, int ntoys, int K, int32_t* out_index, double* out_score, int32_t* out_count);
+
 #ifdef __cplusplus
 }
 #endif
