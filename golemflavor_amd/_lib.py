@@ -271,6 +271,7 @@ SIGNATURES = {
     "gf_toys_select": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp, _ip, _dp, _ip]),
     "gf_toys_scores": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, _dp]),
     "gf_toy_select": (C.c_int, [C.c_int, _dp, _dp, _ip, C.c_int, _dp, _dp, C.c_double, C.c_int, C.c_int, _ip, _dp, _ip]),
+    "gf_nested_toys_evidence": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _lp]),
 }
 
 _lib = None

@@ -98,4 +98,13 @@ struct GfNestedRunState { int64_t iter; double lnx, lnz; int32_t done, failed; }
 // the view, and (state != NULL: [nruns], read back once on the sampler's stream, which is synchronised) where every run stands; a
 // sampler that has not drawn its live points yet reports every run with done = 0
 int gf_internal_nested_view(gf_nested* s, GfNestedView* v, GfNestedRunState* state);
+
+// gf_nested_post.hip
+// The points of every run as the posterior takes them, for the evidence under other measurements (gf_ns_toys.hip).  _runs: the view
+// and runs [nruns] (gf_weights.h: a run that has not finished, failed or has ln Z = -inf has n = 0), the points of all runs and of the
+// largest; the sampler's stream is synchronised.  _gather: k_np_gather enqueued on the view's stream: d_runs [nruns] <- runs (which
+// stay the caller's until the stream is synchronised), d_lnw [total], d_theta [total][ndim].
+struct GfWeightRun;
+int gf_internal_nested_runs(gf_nested* s, GfNestedView* v, GfWeightRun* runs, int64_t* total, int64_t* maxn);
+int gf_internal_nested_gather(const GfNestedView* v, const GfWeightRun* runs, int64_t maxn, GfWeightRun* d_runs, double* d_lnw, double* d_theta);
 }

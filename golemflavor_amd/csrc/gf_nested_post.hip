@@ -61,10 +61,9 @@ struct NpWork {
     int64_t total = 0, maxn = 0;
 };
 
-// gather, weights and (moments) mean and covariance, (prefix) C.  Everything is enqueued on the sampler's stream; no sync at the end.
-int np_prepare(gf_nested* s, NpWork& w, bool moments, bool prefix, const char* who)
+// the view, where every run stands, and the runs' points: w.v, w.state, w.runs, w.total, w.maxn
+int np_runs(gf_nested* s, NpWork& w)
 {
-    NpArgs& a = w.a;
     GfNestedView& v = w.v;
     int rc = gf_internal_nested_view(s, &v, nullptr);
     if (rc != GF_OK) return rc;
@@ -84,6 +83,29 @@ int np_prepare(gf_nested* s, NpWork& w, bool moments, bool prefix, const char* w
         w.total += q.n;
         w.maxn = std::max(w.maxn, q.n);
     }
+    return GF_OK;
+}
+
+// the gather of the runs' points on the view's stream; h_runs stays the caller's until the stream is synchronised
+int np_gather(const GfNestedView& v, const NpRun* h_runs, int64_t maxn, NpRun* d_runs, double* d_lnw, double* d_theta)
+{
+    NpArgs a = {};
+    a.runs = d_runs;
+    GF_HIP(hipMemcpyAsync(d_runs, h_runs, sizeof(NpRun) * v.nruns, hipMemcpyHostToDevice, v.stream));
+    const unsigned gblocks = (unsigned)std::max<int64_t>(1, (maxn * v.ndim + NP_BLOCK - 1) / NP_BLOCK);
+    hipLaunchKernelGGL(k_np_gather, dim3(gblocks, (unsigned)v.nruns), dim3(NP_BLOCK), 0, v.stream, a, v, d_lnw, d_theta);
+    GF_HIP(hipGetLastError());
+    return GF_OK;
+}
+
+// gather, weights and (moments) mean and covariance, (prefix) C.  Everything is enqueued on the sampler's stream; no sync at the end.
+int np_prepare(gf_nested* s, NpWork& w, bool moments, bool prefix, const char* who)
+{
+    NpArgs& a = w.a;
+    GfNestedView& v = w.v;
+    int rc = np_runs(s, w);
+    if (rc != GF_OK) return rc;
+    const int R = v.nruns;
     a.ndim = v.ndim;
     for (int c = 0; c < MAX_DIM; ++c) a.fixed[c] = v.slot[c] < 0;
     a.seed = v.seed;
@@ -101,11 +123,9 @@ int np_prepare(gf_nested* s, NpWork& w, bool moments, bool prefix, const char* w
     if (prefix) { buf.take(&a.C, sizeof(double) * T, who); buf.take(&a.tot, sizeof(double) * R * a.maxleaves * GF_WEIGHT_TOT_PER_LEAF, who); }
     if (buf.failed != GF_OK) return buf.failed;
     a.runs = d_runs; a.lnw = d_lnw; a.theta = d_theta;
-    hipStream_t st = v.stream;
-    GF_HIP(hipMemcpyAsync(d_runs, w.runs.data(), sizeof(NpRun) * R, hipMemcpyHostToDevice, st));
-    const unsigned gblocks = (unsigned)std::max<int64_t>(1, (w.maxn * v.ndim + NP_BLOCK - 1) / NP_BLOCK);
-    hipLaunchKernelGGL(k_np_gather, dim3(gblocks, (unsigned)R), dim3(NP_BLOCK), 0, st, a, v, d_lnw, d_theta);
-    GF_HIP(gf_weights_launch(a, R, moments, prefix, st));
+    rc = np_gather(v, w.runs.data(), w.maxn, d_runs, d_lnw, d_theta);
+    if (rc != GF_OK) return rc;
+    GF_HIP(gf_weights_launch(a, R, moments, prefix, v.stream));
     return GF_OK;
 }
 
@@ -180,6 +200,26 @@ int np_reduce(gf_nested* s, int64_t nrows, int with_fr, bool elements, const gf_
 }  // namespace
 
 extern "C" {
+
+// gf_internal.h: the runs' points for gf_ns_toys.hip
+int gf_internal_nested_runs(gf_nested* s, GfNestedView* v, GfWeightRun* runs, int64_t* total, int64_t* maxn)
+{
+    if (!s || !v || !runs || !total || !maxn) return GF_ERR_INVALID_ARG;
+    NpWork w;
+    const int rc = np_runs(s, w);
+    if (rc != GF_OK) return rc;
+    *v = w.v;
+    for (int r = 0; r < w.v.nruns; ++r) runs[r] = w.runs[r];
+    *total = w.total;
+    *maxn = w.maxn;
+    return GF_OK;
+}
+
+int gf_internal_nested_gather(const GfNestedView* v, const GfWeightRun* runs, int64_t maxn, GfWeightRun* d_runs, double* d_lnw, double* d_theta)
+{
+    if (!v || !runs || !d_runs || !d_lnw || !d_theta) return GF_ERR_INVALID_ARG;
+    return np_gather(*v, runs, maxn, d_runs, d_lnw, d_theta);
+}
 
 int gf_nested_posterior(gf_nested* s, int64_t* npoints, double* ess, double* lnz_check, double* mean, double* cov)
 {

@@ -10,7 +10,8 @@ Points of zero likelihood (lnL = -inf) are never replaced by such points, so the
 live points, whatever the batch (nlive_sequence; Fowlie, Handley & Su 2021).
 
     NestedSampler          the device sampler over several posteriors (one run each)
-                           and their posterior: posterior(), posterior_rows(), marginals(), regions() (gf_nested_post.hip)
+                           and their posterior: posterior(), posterior_rows(), marginals(), regions() (gf_nested_post.hip);
+                           reweight_evidence(): every run's evidence under other Gaussian measurements (gf_ns_toys.hip)
     mn_evidence            mn.py:71-108, same name and return: (ln Z, max ln L)
     evidence_scan          sens.py's loop over scales in one device call
     evidence_from_dead     the accounting restated on the host (the tests' reference for the device accumulators)
@@ -30,7 +31,7 @@ from .descriptor import compile_model
 from .enums import ParamTag
 from .model import Model
 
-__all__ = ["NestedSampler", "mn_evidence", "evidence_scan", "evidence_from_dead", "nlive_sequence", "bayes_factor_limit",
+__all__ = ["NestedSampler", "mn_evidence", "evidence_scan", "evidence_from_dead", "evidence_lnz", "nlive_sequence", "bayes_factor_limit",
            "sens_scales", "BAYES_K"]
 
 BAYES_K = 1.0                 # golemflavor/plot.py: Bayes factor threshold 10^K
@@ -180,6 +181,32 @@ class NestedSampler(_CubeRuns, rowsets.RowSetSource):
                                                for k in ("ess", "lnz_check", "mean", "cov")]), "gf_nested_posterior")
         return out
 
+    def reweight_evidence(self, measurements, smearings=None):
+        """The evidence of every run under other Gaussian measurements, from the points the runs keep (DESIGN.md 6k;
+        gf_nested_toys_evidence): ln Z_t = ln sum_i exp(lnw_i + l_t(fr_i) - l_0(fr_i)) over dead()'s points, l_0 the Gaussian of the
+        run's own measurement, l_t that of realisation t.  measurements: [T][3], shared by the runs, or [nruns][T][3]; smearings: [T]
+        or one value, default the runs' models' own (which they must then share, as a scan's do).  Returns dict(lnz, ess (Kish), kept (the
+        points that carry weight), max_x), each [T][nruns].  A realisation equal to a run's own measurement gives posterior()'s
+        lnz_check and ess bit for bit; the error of lnz is the run's own lnz_err, shared by all its realisations.  No kept point:
+        lnz -inf, ess 0.  A run without a posterior (not run, failed, ln Z = -inf): lnz NaN, ess 0, kept 0."""
+        bf = np.ascontiguousarray(measurements, dtype=np.float64)
+        if bf.ndim not in (2, 3) or bf.shape[-1] != 3 or bf.shape[-2] < 1 or (bf.ndim == 3 and bf.shape[0] != self.nruns):
+            raise ValueError("measurements must be [T][3] or [nruns][T][3]")
+        T = bf.shape[-2]
+        if smearings is None:
+            own = {float(getattr(getattr(m, "model", m).desc, "smearing", np.nan)) for m in self.models}
+            if len(own) != 1 or not np.isfinite(next(iter(own))):
+                raise ValueError("the runs' models do not share one smearing: give smearings")
+            smearings = own.pop()
+        sm = np.ascontiguousarray(np.broadcast_to(np.asarray(smearings, dtype=np.float64), (T,)))
+        n = self.nruns
+        m, s, s2, ess = (np.empty((n, T)) for _ in range(4))
+        kept = np.empty((n, T), np.int64)
+        _lib.check(self._L.gf_nested_toys_evidence(self._h, bf.ctypes.data_as(_lib._dp), sm.ctypes.data_as(_lib._dp), T, int(bf.ndim == 3),
+                                                   *[a.ctypes.data_as(_lib._dp) for a in (m, s, s2, ess)], kept.ctypes.data_as(_lib._lp)),
+                   "gf_nested_toys_evidence")
+        return dict(lnz=evidence_lnz(m, s).T.copy(), ess=ess.T.copy(), kept=kept.T.copy(), max_x=m.T.copy())
+
     def posterior_rows(self, nrows, with_fr=False, return_index=False):
         """`nrows` equal-weight rows per run by systematic resampling, (nruns, nrows, ndim) -- with_fr: (nruns, nrows, 3 + ndim),
         the composition of the run's model in front, NaN where the reference would have raised.  return_index: also (nruns, nrows)
@@ -227,6 +254,20 @@ def _logaddexp(x, y):
         return x
     m = x if x > y else y
     return m + math.log1p(math.exp(-abs(x - y)))
+
+
+def evidence_lnz(max_x, s):
+    """ln Z = max_x + log(s) elementwise with the C library's log (math.log), the expression gf_nested_posterior forms lnz_check
+    with; s = 0 (no point carries weight) gives -inf, a NaN gives NaN."""
+    max_x, s = np.asarray(max_x, dtype=np.float64), np.asarray(s, dtype=np.float64)
+    out = np.full(s.shape, np.nan)
+    flat = out.reshape(-1)
+    for i, (m, v) in enumerate(zip(max_x.reshape(-1).tolist(), s.reshape(-1).tolist())):
+        if v > 0.0:
+            flat[i] = m + math.log(v)
+        elif v == 0.0:
+            flat[i] = -math.inf
+    return out
 
 
 def nlive_sequence(lnl_dead, nlive, batch):

@@ -15,6 +15,13 @@ Nelder-Mead maximiser under that realisation's measurement.
     sensitivity_band       quantiles of the limits: the median expected limit with its one- and two-sigma band
     ts_quantiles           the empirical critical value of the statistic per scale, to hold against chi2.ppf(0.95, 1)
     save_realisations      the scan's arrays as one .npz
+
+The Bayesian statistic has the same ensembles without a run per realisation (gf_ns_toys.hip): one evidence scan keeps
+its dead points, and the evidence of every realisation at every scale is a reweighting of them.
+
+    evidence_realisation_scan    ln Z of every (realisation, scale), the Bayes-factor limit of every realisation
+    evidence_limits              bayes_factor_limit row by row: the limits, and which realisations "discovered" new physics
+    save_evidence_realisations   the scan's arrays and the band as one .npz
 """
 import ctypes as C
 import time
@@ -25,11 +32,13 @@ from . import _lib
 from . import fr as fr_utils
 from . import rowsets
 from .enums import ParamTag
+from . import nested
 from .nested import _opt, _scan_models
 from .profile_llh import (DEFAULT_FATOL, DEFAULT_RESTARTS, DEFAULT_SEED_POINTS, DEFAULT_XATOL, SimplexMaximizer,
                           profile_likelihood_limit)
 
 __all__ = ["draw_realisations", "ToySeeds", "realisation_scan", "sensitivity_band", "ts_quantiles", "save_realisations",
+           "evidence_realisation_scan", "evidence_limits", "save_evidence_realisations",
            "DEFAULT_TOY_STARTS", "MAX_TOY_STARTS", "MAX_RUNS"]
 
 DEFAULT_TOY_STARTS = 8
@@ -298,4 +307,101 @@ def save_realisations(path, res, quantiles=BAND_QUANTILES):
     with open(path, "wb") as fh:
         np.savez(fh, band_quantiles=band["quantiles"], band_limits=band["limits"], band_without_limit=np.int64(band["n_without_limit"]),
                  seconds=np.float64(res["seconds"]), **{k: res[k] for k in SAVED})
+    return band
+
+
+def evidence_limits(scales, lnz, k=nested.BAYES_K, ess_fraction=None, min_ess_fraction=None):
+    """nested.bayes_factor_limit(scales, lnz[t], k) for every realisation t of lnz [T][S]: dict(limits [T] (NaN where it returns None
+    or raises 'Discovered LV!'), discovered [T] (it raised), low_ess [T]).  min_ess_fraction (a user's cut, off by default) with
+    ess_fraction [T][S]: a realisation with any scale below it gets limit NaN and is flagged in low_ess.  A row that holds a NaN or an
+    infinity (a run without a posterior, a realisation no point carries weight under) has no limit."""
+    scales = np.asarray(scales, dtype=np.float64)
+    lnz = np.asarray(lnz, dtype=np.float64)
+    T = lnz.shape[0]
+    limits, discovered, low = np.full(T, np.nan), np.zeros(T, bool), np.zeros(T, bool)
+    if min_ess_fraction is not None:
+        with np.errstate(invalid="ignore"):
+            low = ~(np.asarray(ess_fraction, dtype=np.float64) >= float(min_ess_fraction)).all(axis=1)
+    for t in range(T):
+        if low[t] or not np.all(np.isfinite(lnz[t])):
+            continue
+        try:
+            lim = nested.bayes_factor_limit(scales, lnz[t], k)
+        except AssertionError as exc:
+            if "Discovered LV!" not in str(exc):
+                raise
+            discovered[t] = True
+            continue
+        if lim is not None:
+            limits[t] = lim
+    return dict(limits=limits, discovered=discovered, low_ess=low)
+
+
+def evidence_realisation_scan(args, asimov_paramset, llh_paramset, scales, measurements=None, ntoys=None, toy_seed=0, smearings=None,
+                              k=nested.BAYES_K, min_ess_fraction=None, run_ids=None, nlive=None, tol=None, batch=None, walks=None, seed=None,
+                              on_nonunitary="raise", smearing=None, device=0, max_iter=100000, posterior=None, binned=None):
+    """The evidence of T realisations at every scale from ONE evidence scan (`nested.evidence_scan`, whose nested options these are):
+    the scan's runs keep their points, and `NestedSampler.reweight_evidence` gives ln Z of every (realisation, scale) from them
+    (DESIGN.md 6k).
+
+    measurements: [T][3], shared by all scales, or [S][T][3]; None: `ntoys` realisations of the model's own measurement by
+    draw_realisations(bf, smearing, ntoys, toy_seed), as realisation_scan draws them for the same seed.  smearings: [T], default the
+    model's.  Returns dict(scales, measurements, smearings, lnz [T][S], ess [T][S], ess_fraction (ess over the run's own posterior()
+    ESS), kept [T][S], max_x [T][S], lnz_run, lnz_err_run, ess_run [S] (the Asimov run), bayes [T][S] = lnz - lnz[:, null] (the null
+    the smallest scale), limits [T] (nested.bayes_factor_limit(scales, lnz[t], k); NaN where it returns None or raises 'Discovered
+    LV!'), discovered [T] (it raised), low_ess [T] and n_low_ess (min_ess_fraction: evidence_limits), asimov (evidence_scan's own
+    result), seconds, seconds_nested, seconds_reweight).  Every realisation of a scale shares that run's compression error lnz_err_run:
+    their lnz are correlated through it, and the band of the limits does not include it."""
+    if binned is not None:
+        raise ValueError("realisations are of the flux-averaged Gaussian likelihood; the energy-resolved one is not supported")
+    scales = np.asarray(scales, dtype=np.float64)
+    S = len(scales)
+    sm0 = float(smearing if smearing is not None else _opt(args, "smearing", 0.02))
+    if measurements is None:
+        if ntoys is None:
+            raise ValueError("give measurements or ntoys")
+        bf0 = fr_utils.angles_to_fr(asimov_paramset.from_tag(ParamTag.BESTFIT, values=True))
+        measurements = draw_realisations(bf0, sm0, ntoys, toy_seed)
+    meas = np.ascontiguousarray(measurements, dtype=np.float64)
+    if meas.ndim not in (2, 3) or meas.shape[-1] != 3 or (meas.ndim == 3 and meas.shape[0] != S):
+        raise ValueError("measurements must be [T][3] or [S][T][3]")
+    T = meas.shape[-2]
+    sms = np.ascontiguousarray(np.broadcast_to(np.asarray(sm0 if smearings is None else smearings, dtype=np.float64), (T,)))
+    t0 = time.perf_counter()
+    run = nested.evidence_scan(args, asimov_paramset, llh_paramset, scales, run_ids=run_ids, nlive=nlive, tol=tol, batch=batch, walks=walks,
+                               seed=seed, on_nonunitary=on_nonunitary, smearing=sm0, device=device, max_iter=max_iter, return_sampler=True,
+                               posterior=posterior)
+    sampler, models = run.pop("sampler"), run.pop("models")
+    try:
+        t1 = time.perf_counter()
+        rw = sampler.reweight_evidence(meas, sms)
+        t2 = time.perf_counter()
+        ess_run = sampler.posterior()["ess"]
+    finally:
+        sampler.close()
+        for m in models:
+            m.close()
+    null = int(np.argmin(scales))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        bayes = rw["lnz"] - rw["lnz"][:, null:null + 1]
+        frac = rw["ess"] / ess_run[None, :]
+    lim = evidence_limits(scales, rw["lnz"], k, frac, min_ess_fraction)
+    return dict(scales=scales, measurements=meas, smearings=sms, lnz=rw["lnz"], ess=rw["ess"], ess_fraction=frac, kept=rw["kept"],
+                max_x=rw["max_x"], lnz_run=run["lnz"], lnz_err_run=run["lnz_err"], ess_run=ess_run, bayes=bayes, limits=lim["limits"],
+                discovered=lim["discovered"], low_ess=lim["low_ess"], n_low_ess=int(lim["low_ess"].sum()), asimov=run,
+                seconds=t2 - t0, seconds_nested=t1 - t0, seconds_reweight=t2 - t1)
+
+
+EVIDENCE_SAVED = ("scales", "measurements", "smearings", "lnz", "ess", "ess_fraction", "kept", "lnz_run", "lnz_err_run", "ess_run", "bayes",
+                  "limits", "discovered", "low_ess")
+
+
+def save_evidence_realisations(path, res, quantiles=BAND_QUANTILES):
+    """evidence_realisation_scan's arrays plus the band of the limits (band_quantiles, band_limits, band_without_limit) as one .npz;
+    returns the band."""
+    band = sensitivity_band(res["limits"], quantiles)
+    with open(path, "wb") as fh:
+        np.savez(fh, band_quantiles=band["quantiles"], band_limits=band["limits"], band_without_limit=np.int64(band["n_without_limit"]),
+                 seconds=np.float64(res["seconds"]), seconds_nested=np.float64(res["seconds_nested"]),
+                 seconds_reweight=np.float64(res["seconds_reweight"]), **{k: res[k] for k in EVIDENCE_SAVED})
     return band

@@ -11,6 +11,8 @@ posterior_<identifier>_scale_<10^scale:.0E>.npz beside the arrays (INTEGRATION.m
 file name then carries `_ebins` behind the identifier.  The frequentist arrays hold [scale, profile max lnL] in both files: the
 statistic golemflavor/plot.py:605-608 (plot_statistic) receives.  --stat-method frequentist --realisations T also profiles T mock
 measurements thrown around the injected composition and writes fr_realisations{identifier}.npz beside fr_maxllh.
+--evidence-realisations T (the Bayesian method) reweights the evidence scan's own points to T such measurements and
+writes fr_evidence_realisations{identifier}.npz beside fr_stat; the Asimov arrays are what the command writes without the option.
 """
 import argparse
 import json
@@ -76,7 +78,13 @@ def parse_args(argv=None):
                     help="frequentist: also profile T mock measurements m = injected composition + smearing z, z ~ N(0, I), at every "
                          "scale, and write fr_realisations<identifier>.npz (max lnL, the statistic and the limit of every realisation, "
                          "the band of the limits)")
-    ap.add_argument("--realisation-seed", type=int, default=0, help="with --realisations: the seed the realisations are thrown with")
+    ap.add_argument("--realisation-seed", type=int, default=0,
+                    help="with --realisations or --evidence-realisations: the seed the realisations are thrown with")
+    ap.add_argument("--evidence-realisations", type=int, default=None, metavar="T",
+                    help="bayesian: also give the evidence of T mock measurements m = injected composition + smearing z, z ~ N(0, I), at "
+                         "every scale by reweighting the scan's own dead points (no further nested runs), and write "
+                         "fr_evidence_realisations<identifier>.npz (ln Z, ESS and the Bayes-factor limit of every realisation, the band "
+                         "of the limits)")
     ap.add_argument("--realisation-starts", type=int, default=realisations_mod.DEFAULT_TOY_STARTS,
                     help="with --realisations: Nelder-Mead starts per (realisation, scale), 1 to %d" % realisations_mod.MAX_TOY_STARTS)
     ap.add_argument("--on-nonunitary", choices=["raise", "-inf"], default="raise")
@@ -118,6 +126,16 @@ def parse_args(argv=None):
             ap.error("--realisations are of the flux-averaged likelihood: it does not combine with --energy-resolved")
         if args.eval_segment.lower() != "all":
             ap.error("--realisations needs every scale (a limit per realisation): it does not combine with --eval-segment")
+    if args.evidence_realisations is not None:
+        if args.stat_method is not StatCateg.BAYESIAN:
+            ap.error("--evidence-realisations needs the Bayesian method (it reweights the nested runs' points); "
+                     "--stat-method frequentist has --realisations")
+        if args.evidence_realisations < 1:
+            ap.error("--evidence-realisations takes T >= 1")
+        if args.energy_resolved:
+            ap.error("--evidence-realisations are of the flux-averaged likelihood: it does not combine with --energy-resolved")
+        if args.eval_segment.lower() != "all":
+            ap.error("--evidence-realisations needs every scale (a limit per realisation): it does not combine with --eval-segment")
     if args.posterior_elements and not args.posterior:
         ap.error("--posterior-elements needs --posterior (it adds the element-space marginals to it)")
     if args.posterior_spectrum is not None:
@@ -242,8 +260,16 @@ def main(argv=None):
     post = dict(nrows=args.posterior_rows, elements=args.posterior_elements) if args.posterior else None
     if post is not None and args.posterior_spectrum is not None:
         post["spectrum"] = args.posterior_spectrum
-    res = nested.evidence_scan(args, asimov, llh_ps, scales[idx], run_ids=idx, on_nonunitary=args.on_nonunitary,
-                               device=args.device, posterior=post, binned=binned)
+    toys = None
+    if getattr(args, "evidence_realisations", None) is not None:
+        ens = realisations_mod.evidence_realisation_scan(args, asimov, llh_ps, scales[idx], ntoys=args.evidence_realisations,
+                                                         toy_seed=args.realisation_seed, run_ids=idx, on_nonunitary=args.on_nonunitary,
+                                                         device=args.device, posterior=post)
+        res = ens["asimov"]
+        toys = _evidence_realisations(args, ens)
+    else:
+        res = nested.evidence_scan(args, asimov, llh_ps, scales[idx], run_ids=idx, on_nonunitary=args.on_nonunitary,
+                                   device=args.device, posterior=post, binned=binned)
     evidence_arr = np.stack([scales[idx], res["lnz"]], axis=1)
     maxllh_arr = np.stack([scales[idx], res["max_lnl"]], axis=1)
     for f, arr in ((outfile, evidence_arr), (outfile_llh, maxllh_arr)):
@@ -253,6 +279,7 @@ def main(argv=None):
     if posterior_files is not None and "spectrum" in res:
         posterior_files += save_spectra(args, scales[idx], res)
     print(json.dumps({
+        **({"evidence_realisations": toys} if toys is not None else {}),
         **({"posterior": posterior_files} if posterior_files is not None else {}),
         **({"likelihood": "energy-resolved"} if binned is not None else {}),
         "tool": "golemflavor_amd.sens", "dimension": args.dimension, "texture": args.texture.name,
@@ -262,6 +289,27 @@ def main(argv=None):
         "seconds": round(res["seconds"], 4), "evals_per_s": float(res["nevals"].sum() / max(res["seconds"], 1e-12)),
         "fr_stat": outfile + ".npy", "fr_maxllh": outfile_llh + ".npy"}))
     return 0
+
+
+def evidence_realisations_path(args):
+    """fr_evidence_realisations<identifier>.npz beside fr_stat<identifier>.npy (the evidence array)."""
+    base = os.path.join(args.datadir, args.stat_method.name.lower(), args.data.name.lower())
+    return os.path.join(base, "fr_evidence_realisations" + identifier(args) + ".npz")
+
+
+def _evidence_realisations(args, ens):
+    """--evidence-realisations: the ensemble's file, and what the JSON line says of it."""
+    f = evidence_realisations_path(args)
+    os.makedirs(os.path.dirname(f) or ".", exist_ok=True)
+    band = realisations_mod.save_evidence_realisations(f, ens)
+
+    def clean(a):
+        return [None if not np.isfinite(v) else float(v) for v in np.asarray(a, dtype=np.float64).ravel()]
+
+    return {"file": f, "n": args.evidence_realisations, "seed": args.realisation_seed, "band_quantiles": band["quantiles"].tolist(),
+            "band_limits": clean(band["limits"]), "without_limit": band["n_without_limit"], "discovered": int(ens["discovered"].sum()),
+            "lowest_ess_fraction": clean([np.min(np.where(np.isnan(ens["ess_fraction"]), np.inf, ens["ess_fraction"]))])[0], "seconds_nested": round(ens["seconds_nested"], 4),
+            "seconds_reweight": round(ens["seconds_reweight"], 4)}
 
 
 def realisations_path(args):

@@ -583,6 +583,27 @@ int gf_nested_regions(gf_nested* s, int64_t nrows, int nbins, int radius, const 
                       int64_t cap, int64_t* thres, int32_t* saturated, double* level_in, double* level_out, double* mass, int32_t* cells,
                       double* density);
 
+/* ---- the evidence of every run under other Gaussian measurements (csrc/gf_ns_toys.hpp holds the arithmetic) ---------- */
+/* Additive under ABI 5.  The runs' points (gf_nested_get_dead's rows in its order) reweighted to `ntoys` realisations of the runs'
+ * Gaussian measurement: Z_t = sum_i exp(x_ti), x_ti = lnw_i + (l_t(fr_i) - l_0(fr_i)), with fr_i the composition of point i under the
+ * run's own model (one propagation of all points), l_0 the Gaussian block of ln_prob under the run's own measurement and l_t the same
+ * function under realisation t (bf, smearing; the constants by the rule of gf_model_create), the likelihood offset the run's.  A point
+ * carries no weight (x = -inf) where lnw_i = -inf, where the reference would have raised on it (GF_ST_NON_UNITARY), where l_0 is not
+ * finite, or where l_t is NaN or -inf.  Per (run, realisation): m = max_i x, s = sum exp(x - m), s2 = sum exp(x - m)^2 along
+ * gf_nested_posterior's tree, ess = s^2 / s2 (Kish), kept = the points with a finite x; ln Z_t = m + log(s) is the caller's.  A
+ * realisation whose (bf, smearing) are the run's own reproduces gf_nested_posterior's lnz_check and ess bit for bit.  No kept point:
+ * m = -inf, s = s2 = 0, ess = 0.  A run without points (not run to its end, failed in raise mode, ln Z = -inf): m, s, s2 NaN, ess 0,
+ * kept 0.
+ *   bf        [ntoys][3] shared by the runs, or [nruns][ntoys][3] with per_run = 1
+ *   smearing  [ntoys]
+ *   outputs   [nruns][ntoys] each; NULL = skip
+ * Models without a flux-averaged Gaussian measurement (PRIOR_ONLY, a binned measurement): GF_ERR_UNSUPPORTED; a measurement that is
+ * not finite or a smearing that is not positive and finite: GF_ERR_INVALID_ARG.  The realisations go through the device in batches
+ * whose partial sums stay under 256 MiB of scratch (GF_NS_TOYS_SCRATCH_BYTES overrides); no result depends on the batching, on
+ * ntoys or on the runs that share the sampler.  Synchronous, on the sampler's stream; the sampler's state is only read. */
+int gf_nested_toys_evidence(gf_nested* s, const double* bf, const double* smearing, int ntoys, int per_run, double* m, double* sum,
+                            double* sum2, double* ess, int64_t* kept);
+
 /* ---- the shortest interval around the mode of every column (golemflavor/misc.py:174-213) ------------------------- */
 /* Per chain and column of rows [nrows][width], with s the sorted column and n = nrows (csrc/gf_interval.hpp states every operation):
  *   nbins    = floor((s[n-1] - s[0]) / (2 * n**(-1/3) * (p75 - p25))), p25 / p75 np.percentile's default (calc_nbins)
