@@ -271,6 +271,15 @@ SIGNATURES = {
     "gf_toys_select": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp, _ip, _dp, _ip]),
     "gf_toys_scores": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, _dp]),
     "gf_toy_select": (C.c_int, [C.c_int, _dp, _dp, _ip, C.c_int, _dp, _dp, C.c_double, C.c_int, C.c_int, _ip, _dp, _ip]),
+    "gf_toys_create_binned": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, _ip, _dp, C.c_int, C.c_uint64, C.POINTER(_vp)]),
+    "gf_toys_destroy_binned": (None, [_vp]),
+    "gf_toys_set_run_ids_binned": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+    "gf_toys_seed_binned": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
+    "gf_toys_get_seeds_binned": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, _dp, _ip]),
+    "gf_toys_select_binned": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, _ip, _dp, _ip]),
+    "gf_toys_scores_binned": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp]),
+    "gf_toy_select_binned": (C.c_int, [C.c_int, _dp, _dp, _ip, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_double, C.c_int, C.c_int, _ip, _dp, _ip]),
+    "gf_toys_set_binned_measurements": (C.c_int, [_vp, C.c_int, _dp, _dp]),
     "gf_nested_toys_evidence": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _lp]),
 }
 

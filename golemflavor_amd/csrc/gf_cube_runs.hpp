@@ -39,6 +39,7 @@ struct GfCubeRunsHost {
     const GfBsm** d_tbs = nullptr;
     const double** d_ptabs = nullptr;
     const double** d_btabs = nullptr;
+    double* d_btab_runs = nullptr;      // cube_runs_set_binned_measurements: [nruns][nbins][GF_BINNED_STRIDE], the runs' own tables
     uint64_t* d_run_ids = nullptr;
     double* d_bases = nullptr;
     GfStepState* d_state = nullptr;     // the settle kernel's step state: zeros (no stored chain)
@@ -137,9 +138,9 @@ void cube_runs_free(GfCubeRunsHost& h, GfCubeRuns& a)
 {
     (void)hipSetDevice(h.device);
     if (h.stream) (void)hipStreamSynchronize(h.stream);
-    void* ptrs[] = {h.d_commons, (void*)h.d_tbs, (void*)h.d_ptabs, (void*)h.d_btabs, h.d_run_ids, h.d_bases, h.d_state, h.d_ctl, a.pq, a.pend_rows};
+    void* ptrs[] = {h.d_commons, (void*)h.d_tbs, (void*)h.d_ptabs, (void*)h.d_btabs, h.d_btab_runs, h.d_run_ids, h.d_bases, h.d_state, h.d_ctl, a.pq, a.pend_rows};
     for (void* p : ptrs) if (p) (void)hipFree(p);
-    h.d_commons = nullptr; h.d_tbs = nullptr; h.d_ptabs = nullptr; h.d_btabs = nullptr; h.d_run_ids = nullptr; h.d_bases = nullptr;
+    h.d_commons = nullptr; h.d_tbs = nullptr; h.d_ptabs = nullptr; h.d_btabs = nullptr; h.d_btab_runs = nullptr; h.d_run_ids = nullptr; h.d_bases = nullptr;
     h.d_state = nullptr; h.d_ctl = nullptr; a.pq = nullptr; a.pend_rows = nullptr;
     delete[] h.models;
     h.models = nullptr;
@@ -268,6 +269,47 @@ int cube_runs_set_measurements(GfCubeRunsHost& h, const GfCubeRuns& a, const dou
     GF_HIP(hipSetDevice(h.device));
     GF_HIP(hipMemcpyAsync(h.d_commons, hc.data(), sizeof(GfCommon) * R, hipMemcpyHostToDevice, h.stream));
     GF_HIP(hipStreamSynchronize(h.stream));                              // hc goes out of scope
+    return GF_OK;
+}
+
+// A binned measurement of its own for every run: fr_bins [R][nbins][3] and sigma [R][nbins] become one device buffer
+// [R][nbins][GF_BINNED_STRIDE], built the way gf_model_set_binned_measurement builds a model's table, and d_btabs[r] points into it --
+// the run's kernels, which read the binned measurement from a.btabs[r] alone, then evaluate what a model given that measurement
+// evaluates.  The models keep theirs.  Binned sets only; `who` names the call.
+int cube_runs_set_binned_measurements(GfCubeRunsHost& h, const GfCubeRuns& a, int nbins, const double* fr_bins, const double* sigma,
+                                      const char* who)
+{
+    if (h.initialised) return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: before the first run", who);
+    if (!h.binned)
+        return gf_fail_msg(GF_ERR_UNSUPPORTED, "%s: the runs' models carry no binned measurement; a run's own binned measurement replaces a model's", who);
+    const size_t R = a.nruns, nb = nbins > 0 ? nbins : 0;
+    for (size_t r = 0; r < R; ++r) {
+        const GfCommon* c; const GfBsm* tb; const double* pt; int device, cus, mnb;
+        const int rc = gf_model_constants(h.models[r], &c, &tb, &pt, &device, &cus, &mnb);
+        if (rc != GF_OK) return rc;
+        if (nbins != mnb) return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: %d bins given, the model of run %zu has %d", who, nbins, r, mnb);
+    }
+    std::vector<double> tab(R * nb * GF_BINNED_STRIDE);
+    std::vector<const double*> hbt(R);
+    for (size_t r = 0; r < R; ++r)
+        for (size_t k = 0; k < nb; ++k) {
+            const double* f = fr_bins + (r * nb + k) * 3;
+            const double sg = sigma[r * nb + k];
+            if (!std::isfinite(f[0]) || !std::isfinite(f[1]) || !std::isfinite(f[2]) || !(sg > 0.0) || !std::isfinite(sg))
+                return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: bin %zu of run %zu needs a finite composition and a width > 0", who, k, r);
+            double inv_smear, c0;
+            double* t = tab.data() + (r * nb + k) * GF_BINNED_STRIDE;
+            t[0] = f[0]; t[1] = f[1]; t[2] = f[2];
+            gf_internal_gauss_consts(sg, &inv_smear, &c0, &t[3], &t[4]);
+            if (!std::isfinite(t[3]) || !std::isfinite(t[4]))
+                return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: the width of bin %zu of run %zu is outside the range of the Gaussian's constants", who, k, r);
+        }
+    GF_HIP(hipSetDevice(h.device));
+    if (!h.d_btab_runs) GF_HIP(hipMalloc((void**)&h.d_btab_runs, sizeof(double) * tab.size()));
+    for (size_t r = 0; r < R; ++r) hbt[r] = h.d_btab_runs + r * nb * GF_BINNED_STRIDE;
+    GF_HIP(hipMemcpyAsync(h.d_btab_runs, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, h.stream));
+    GF_HIP(hipMemcpyAsync((void*)h.d_btabs, hbt.data(), sizeof(void*) * R, hipMemcpyHostToDevice, h.stream));
+    GF_HIP(hipStreamSynchronize(h.stream));                              // the host vectors go out of scope
     return GF_OK;
 }
 

@@ -534,6 +534,16 @@ int gf_toys_set_measurements(gf_simplex* s, const double* bf, const double* smea
     return cube_runs_set_measurements(s->rs, s->a, bf, smearing, "gf_toys_set_measurements");
 }
 
+int gf_toys_set_binned_measurements(gf_simplex* s, int nbins, const double* fr_bins, const double* sigma)
+{
+    if (!s || !fr_bins || !sigma) return GF_ERR_INVALID_ARG;
+    // as gf_toys_set_measurements: the set's own seeding would score under the models' measurement
+    if (s->a.nseed > 0)
+        return gf_fail_msg(GF_ERR_INVALID_ARG, "gf_toys_set_binned_measurements: the set draws %d seed points per run, which its models would score; "
+                           "give the starts (nseed = 0, gf_simplex_set_starts)", s->a.nseed);
+    return cube_runs_set_binned_measurements(s->rs, s->a, nbins, fr_bins, sigma, "gf_toys_set_binned_measurements");
+}
+
 int gf_toys_set_start_counts(gf_simplex* s, const int32_t* counts)
 {
     if (!s || !counts) return GF_ERR_INVALID_ARG;

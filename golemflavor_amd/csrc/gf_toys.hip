@@ -6,7 +6,7 @@
 //   k_cube_draw     nseed cube points of Philox counter (the scale's run id, SX_SEED_ITER, point, pair of coordinates): the points
 //                   gf_simplex.hip's seeding draws for that run id
 //   the bulk path   gf_model_lnprob_on with compositions and status: the verdicts with the bulk path's own arbitration
-//   k_toy_prior     the prior sum lp_i of every seed by the evaluation kernels' own device function (lnprior / lnprior_tab), -inf
+//   k_toy_prior     (gf_toys_prior.hpp) the prior sum lp_i of every seed by the evaluation kernels' own device function (lnprior / lnprior_tab), -inf
 //                   outside the box; counts the seeds the reference would have raised on, once per scale
 // and per (scale, realisation):
 //   k_toy_select    a lane owns a realisation (its constants in registers); the workgroup streams a part of the seed range through
@@ -25,6 +25,7 @@
 #include "gf_cube_runs.hpp"
 #include "gf_pool.h"
 #include "gf_toys.hpp"
+#include "gf_toys_prior.hpp"
 
 namespace {
 using namespace gftoy;
@@ -38,34 +39,6 @@ static_assert(CHUNK % TOY_TILE == 0, "a part of the seed range is whole tiles");
 struct DevLogOfExp {
     __device__ __forceinline__ double operator()(double x) const { return gfdev::log_of_exp(x); }
 };
-
-// lp [R][n]: the prior sum of every seed of every scale (blockIdx.y), -inf outside the box; nonunit [R] += the scale's seeds whose
-// status is GF_ST_NON_UNITARY.  theta [R][n][ndim], status [R][n]
-template <bool BSM>
-__global__ __launch_bounds__(GF_BLOCK) void k_toy_prior(const GfCubeRuns a, int n, const double* __restrict__ theta,
-                                                        const int32_t* __restrict__ status, double* __restrict__ lp, unsigned int* nonunit)
-{
-    __shared__ __attribute__((aligned(16))) double ctab[GF_MAX_DIM * 4 + 20];
-    const int r = blockIdx.y;
-    if (BSM) {
-        load_eval_tables(ctab, a.ptabs[r], a.tbs[r], false);
-        __syncthreads();
-    }
-    const int i = blockIdx.x * GF_BLOCK + threadIdx.x;
-    bool nu = false;
-    if (i < n) {
-        const int64_t at = (int64_t)r * n + i;
-        const double* row = theta + at * a.ndim;
-        double s;
-        bool inbox;
-        if constexpr (BSM) inbox = lnprior_tab<0>(ctab, row, a.ndim, a.commons[r].prior_const, s);
-        else inbox = lnprior<0>(a.commons[r], row, s);
-        lp[at] = inbox ? s : -gf_inf();
-        nu = status[at] == ST_NON_UNITARY;
-    }
-    const unsigned long long b = __ballot(nu);
-    if ((threadIdx.x & (GF_WAVE - 1)) == 0 && b) atomicAdd(&nonunit[r], (unsigned int)__popcll(b));
-}
 
 struct ToySelArgs {
     const double* lp;                   // [S][M]

@@ -193,12 +193,14 @@ class SimplexMaximizer(_CubeRuns):
     points; optional).  Options as scipy's Nelder-Mead (xatol, fatol, maxiter = 200 n by default, adaptive) plus `restarts`.
     `measurements` = (bestfit_fr [nruns][3], smearing [nruns] or one value): run r maximises under that Gaussian measurement in place
     of its model's (needs nseed = 0, the flux-averaged likelihood).  `start_counts` [nruns] (with nstarts = 0): run r keeps
-    the first start_counts[r] of `starts` only."""
+    the first start_counts[r] of `starts` only.  `binned_measurements` = (fr_bins [nruns][nb][3], sigma [nruns][nb] or [nb]): run r
+    maximises under that binned measurement in place of its model's (needs nseed = 0 and models with a binned measurement)."""
     _abi, _what = "simplex", "profile run"
 
     def __init__(self, models, cols, bases, nstarts=DEFAULT_STARTS, nseed=DEFAULT_SEED_POINTS, seed=0, starts=None,
                  on_nonunitary="raise", xatol=DEFAULT_XATOL, fatol=DEFAULT_FATOL, maxiter=None, adaptive=False,
-                 restarts=DEFAULT_RESTARTS, run_ids=None, labels=None, measurements=None, start_counts=None):
+                 restarts=DEFAULT_RESTARTS, run_ids=None, labels=None, measurements=None, start_counts=None,
+                 binned_measurements=None):
         hs = self._open(models, cols, bases, on_nonunitary, labels)
         self.nstarts, self.nseed, self.seed = int(nstarts), int(nseed), int(seed)
         self.maxiter = int(maxiter) if maxiter is not None else 200 * self.nscan
@@ -222,6 +224,8 @@ class SimplexMaximizer(_CubeRuns):
         self._set_run_ids(run_ids)
         if measurements is not None:
             self.set_measurements(*measurements)
+        if binned_measurements is not None:
+            self.set_binned_measurements(*binned_measurements)
         if start_counts is not None:
             cnt = np.ascontiguousarray(np.broadcast_to(np.asarray(start_counts, dtype=np.int32), (self.nruns,)))
             _lib.check(self._L.gf_toys_set_start_counts(self._h, cnt.ctypes.data_as(_lib._ip)), "gf_toys_set_start_counts")
@@ -233,6 +237,16 @@ class SimplexMaximizer(_CubeRuns):
         sm = np.ascontiguousarray(np.broadcast_to(np.asarray(smearing, dtype=np.float64), (self.nruns,)))
         _lib.check(self._L.gf_toys_set_measurements(self._h, bf.ctypes.data_as(_lib._dp), sm.ctypes.data_as(_lib._dp)),
                    "gf_toys_set_measurements")
+
+    def set_binned_measurements(self, fr_bins, sigma):
+        """A binned measurement of its own for every run, before the first run(): fr_bins [nruns][nb][3], sigma [nruns][nb] or [nb].
+        Run r then evaluates what a Model with set_binned_measurement(BinnedMeasurement(fr_bins[r], sigma[r])) evaluates."""
+        f = np.ascontiguousarray(fr_bins, dtype=np.float64)
+        if f.ndim != 3 or f.shape[0] != self.nruns or f.shape[2] != 3:
+            raise ValueError("fr_bins must be [nruns][nb][3]")
+        sg = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma, dtype=np.float64), f.shape[:2]))
+        _lib.check(self._L.gf_toys_set_binned_measurements(self._h, int(f.shape[1]), f.ctypes.data_as(_lib._dp), sg.ctypes.data_as(_lib._dp)),
+                   "gf_toys_set_binned_measurements")
 
     def max_rounds(self):
         """Evaluation rounds after which every start has finished: per minimize call one round for the initial simplex and at

@@ -16,6 +16,14 @@ Nelder-Mead maximiser under that realisation's measurement.
     ts_quantiles           the empirical critical value of the statistic per scale, to hold against chi2.ppf(0.95, 1)
     save_realisations      the scan's arrays as one .npz
 
+The energy-resolved likelihood has the frequentist ensembles too (gf_toys_binned.hip): a realisation of a
+`BinnedMeasurement` (m_k, sigma_k) is m_{t,k} = m_k + sigma_k z_{t,k}, independent per energy bin, the seeds carry their composition at
+every bin, and the polish runs under a binned measurement per run.
+
+    draw_binned_realisations   m_k + sigma_k z on the host
+    BinnedToySeeds             the shared seeding with per-bin compositions, their selection under binned realisations
+    binned_realisation_scan    realisation_scan for the energy-resolved likelihood: the same dict, for sensitivity_band and ts_quantiles
+
 The Bayesian statistic has the same ensembles without a run per realisation (gf_ns_toys.hip): one evidence scan keeps
 its dead points, and the evidence of every realisation at every scale is a reweighting of them.
 
@@ -38,6 +46,7 @@ from .profile_llh import (DEFAULT_FATOL, DEFAULT_RESTARTS, DEFAULT_SEED_POINTS, 
                           profile_likelihood_limit)
 
 __all__ = ["draw_realisations", "ToySeeds", "realisation_scan", "sensitivity_band", "ts_quantiles", "save_realisations",
+           "draw_binned_realisations", "BinnedToySeeds", "toy_select_binned", "binned_realisation_scan",
            "evidence_realisation_scan", "evidence_limits", "save_evidence_realisations",
            "DEFAULT_TOY_STARTS", "MAX_TOY_STARTS", "MAX_RUNS"]
 
@@ -168,6 +177,135 @@ def toy_select(lp, fr, status, bestfit_fr, smearing, offset, K, device=0):
     return index, score, count
 
 
+def draw_binned_realisations(binned, n, seed=0):
+    """`n` realisations m_{t,k} = m_k + sigma_k z_{t,k} of the `llh.BinnedMeasurement` `binned`, z from
+    np.random.default_rng(seed).standard_normal((n, nb, 3)): [n][nb][3].  Independent per energy bin and not projected onto the simplex:
+    the generative model of the likelihood's own sum of isotropic Gaussians."""
+    z = np.random.default_rng(seed).standard_normal((int(n), binned.nbins, 3))
+    return binned.fr_bins[None] + binned.sigma[None, :, None] * z
+
+
+class BinnedToySeeds:
+    """The shared seeding of a realisation ensemble of the energy-resolved likelihood: ToySeeds over models that carry a
+    binned measurement (`Model.set_binned_measurement`), the seeds keeping their composition at every energy bin.  The compositions take
+    24 * nscales * nseed * nbins bytes on the device."""
+
+    def __init__(self, models, cols, bases, nseed=DEFAULT_SEED_POINTS, seed=0, run_ids=None):
+        self._L = _lib.lib()
+        self.models = list(models)
+        self.nscales = len(self.models)
+        self.cols = np.ascontiguousarray(cols, dtype=np.int32)
+        self.nscan, self.nseed = len(self.cols), int(nseed)
+        ndim = self._L.gf_model_ndim(rowsets.handle(self.models[0]))
+        self.nbins = int(self._L.gf_model_nbins(rowsets.handle(self.models[0])))
+        b = np.asarray(bases, dtype=np.float64)
+        if b.ndim == 1:
+            b = np.tile(b, (self.nscales, 1))
+        self.bases = np.ascontiguousarray(b.reshape(self.nscales, ndim))
+        h = C.c_void_p()
+        _lib.check(self._L.gf_toys_create_binned(rowsets.model_handles(self.models, self.nscales), self.nscales, self.nscan,
+                                                 self.cols.ctypes.data_as(_lib._ip), self.bases.ctypes.data_as(_lib._dp), self.nseed,
+                                                 int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(h)), "gf_toys_create_binned")
+        self._h = h
+        try:
+            if run_ids is not None:
+                ids = np.ascontiguousarray(run_ids, dtype=np.uint64)
+                _lib.check(self._L.gf_toys_set_run_ids_binned(self._h, ids.ctypes.data_as(C.POINTER(C.c_uint64))), "gf_toys_set_run_ids_binned")
+            nu = np.zeros(self.nscales, np.uint32)
+            _lib.check(self._L.gf_toys_seed_binned(self._h, nu.ctypes.data_as(C.POINTER(C.c_uint32))), "gf_toys_seed_binned")
+            self.nonunitary_seeds = nu
+        except BaseException:
+            self.close()
+            raise
+
+    def _measurements(self, meas, sigma):
+        m = np.ascontiguousarray(meas, dtype=np.float64)
+        if m.ndim not in (3, 4) or m.shape[-2:] != (self.nbins, 3) or (m.ndim == 4 and m.shape[0] != self.nscales):
+            raise ValueError("measurements must be [T][%d][3] or [nscales][T][%d][3]" % (self.nbins, self.nbins))
+        T = m.shape[-3]
+        sg = np.ascontiguousarray(sigma, dtype=np.float64)
+        if sg.shape not in ((self.nbins,), (T, self.nbins)):
+            raise ValueError("widths must be [%d], shared by the realisations, or [T][%d]" % (self.nbins, self.nbins))
+        return m, sg, T
+
+    def select(self, meas, sigma, K):
+        """The starts of every (scale, realisation): the K best seeds under the binned score, score descending then seed index ascending,
+        finite scores only.  meas [T][nb][3] (shared by the scales) or [nscales][T][nb][3]; sigma [nb] or [T][nb].  Returns ToySeeds.select's
+        dict."""
+        m, sg, T = self._measurements(meas, sigma)
+        K = int(K)
+        S = self.nscales
+        out = dict(cube=np.empty((S, T, max(K, 0), self.nscan)), index=np.empty((S, T, max(K, 0)), np.int32),
+                   score=np.empty((S, T, max(K, 0))), count=np.empty((S, T), np.int32))
+        _lib.check(self._L.gf_toys_select_binned(self._h, m.ctypes.data_as(_lib._dp), int(m.ndim == 4), sg.ctypes.data_as(_lib._dp), int(sg.ndim == 2),
+                                                 T, K, out["cube"].ctypes.data_as(_lib._dp), out["index"].ctypes.data_as(_lib._ip),
+                                                 out["score"].ctypes.data_as(_lib._dp), out["count"].ctypes.data_as(_lib._ip)),
+                   "gf_toys_select_binned")
+        return out
+
+    def scores(self, meas, sigma):
+        """Every score the selection ranks, [nscales][T][nseed]."""
+        m, sg, T = self._measurements(meas, sigma)
+        out = np.empty((self.nscales, T, self.nseed))
+        _lib.check(self._L.gf_toys_scores_binned(self._h, m.ctypes.data_as(_lib._dp), int(m.ndim == 4), sg.ctypes.data_as(_lib._dp), int(sg.ndim == 2),
+                                                 T, out.ctypes.data_as(_lib._dp)), "gf_toys_scores_binned")
+        return out
+
+    def seeds(self, scale=0):
+        """Scale `scale`'s seeds: ToySeeds.seeds' dict (lnprob: the scale model's own, under its binned measurement; fr: the flux-averaged
+        composition) and fr_bins [nseed][nb][3], NaN for a seed whose status is not GF_ST_OK."""
+        M = self.nseed
+        out = dict(cube=np.empty((M, self.nscan)), lnprob=np.empty(M), lp=np.empty(M), fr=np.empty((M, 3)), fr_bins=np.empty((M, self.nbins, 3)),
+                   status=np.empty(M, np.int32))
+        _lib.check(self._L.gf_toys_get_seeds_binned(self._h, int(scale), *[out[k].ctypes.data_as(_lib._dp) for k in ("cube", "lnprob", "lp", "fr", "fr_bins")],
+                                                    out["status"].ctypes.data_as(_lib._ip)), "gf_toys_get_seeds_binned")
+        desc = getattr(self.models[scale], "model", self.models[scale]).desc
+        lo, hi = np.asarray(desc.lo)[self.cols], np.asarray(desc.hi)[self.cols]
+        theta = np.tile(self.bases[scale], (M, 1))
+        theta[:, self.cols] = (hi - lo) * out["cube"] + lo
+        out["theta"] = theta
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.gf_toys_destroy_binned(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def toy_select_binned(lp, fr_bins, status, meas, sigma, offset, K, device=0):
+    """gf_toy_select_binned: the selection alone on host arrays (one seed set: lp [M], fr_bins [M][nb][3], status [M]; meas [T][nb][3],
+    sigma [nb] or [T][nb]).  Returns (index [T][K], score [T][K], count [T])."""
+    lp = np.ascontiguousarray(lp, dtype=np.float64)
+    fb = np.ascontiguousarray(fr_bins, dtype=np.float64)
+    nb = fb.shape[-2] if fb.ndim == 3 else 0
+    status = np.ascontiguousarray(status, dtype=np.int32)
+    m = np.ascontiguousarray(meas, dtype=np.float64)
+    if fb.ndim != 3 or fb.shape != (len(lp), nb, 3) or m.ndim != 3 or m.shape[1:] != (nb, 3):
+        raise ValueError("fr_bins must be [M][nb][3] and meas [T][nb][3]")
+    T, K = len(m), int(K)
+    sg = np.ascontiguousarray(sigma, dtype=np.float64)
+    if sg.shape not in ((nb,), (T, nb)):
+        raise ValueError("widths must be [nb] or [T][nb]")
+    index, score, count = np.empty((T, max(K, 0)), np.int32), np.empty((T, max(K, 0))), np.empty(T, np.int32)
+    _lib.check(_lib.lib().gf_toy_select_binned(int(device), lp.ctypes.data_as(_lib._dp), fb.ctypes.data_as(_lib._dp), status.ctypes.data_as(_lib._ip),
+                                               len(lp), nb, m.ctypes.data_as(_lib._dp), sg.ctypes.data_as(_lib._dp), int(sg.ndim == 2), float(offset),
+                                               T, K, index.ctypes.data_as(_lib._ip), score.ctypes.data_as(_lib._dp),
+                                               count.ctypes.data_as(_lib._ip)), "gf_toy_select_binned")
+    return index, score, count
+
+
 def realisation_scan(args, asimov_paramset, llh_paramset, scales, measurements=None, ntoys=None, toy_seed=0, smearings=None,
                      nstarts=DEFAULT_TOY_STARTS, nseed=None, run_ids=None, xatol=None, fatol=None, maxiter=None, restarts=None,
                      adaptive=None, seed=None, on_nonunitary="raise", smearing=None, device=0, batch=None, threshold=None, check=True,
@@ -211,64 +349,143 @@ def realisation_scan(args, asimov_paramset, llh_paramset, scales, measurements=N
     if per_run < 1 or per_run * S > MAX_RUNS:
         raise ValueError("batch must keep batch * len(scales) within %d runs" % MAX_RUNS)
 
-    def pick(v, name, default):
-        return v if v is not None else _opt(args, name, default)
-
+    opts = _polish_options(args, xatol, fatol, maxiter, adaptive, restarts, on_nonunitary)
     cols, models, bases, labels = _scan_models(args, asimov_paramset, llh_paramset, scales, sm0, device)
     try:
-        ndim = len(bases[0])
         t0 = time.perf_counter()
-        with ToySeeds(models, cols, bases, nseed=int(pick(nseed, "pl_seed_points", DEFAULT_SEED_POINTS)),
+        with ToySeeds(models, cols, bases, nseed=int(nseed if nseed is not None else _opt(args, "pl_seed_points", DEFAULT_SEED_POINTS)),
                       seed=int(seed if seed is not None else _opt(args, "seed", 0)), run_ids=run_ids) as seeds:
             t1 = time.perf_counter()
             sel = seeds.select(meas, sms, K)
             nu_seeds = seeds.nonunitary_seeds.copy()
         t2 = time.perf_counter()
-        res = dict(max_lnl=np.full((T, S), -np.inf), argmax_theta=np.full((T, S, ndim), np.nan), nstarts=np.zeros((T, S), np.int32),
-                   nfev=np.zeros((T, S), np.int64), niter=np.zeros((T, S), np.int64), nonunitary=np.zeros((T, S), np.uint32),
-                   parked=np.zeros((T, S), np.uint32), failed=np.zeros((T, S), bool))
-        dead = (nu_seeds > 0) if on_nonunitary == "raise" else np.zeros(S, bool)
-        res["failed"][:, dead] = True
-        opts = dict(xatol=float(pick(xatol, "pl_xatol", DEFAULT_XATOL)), fatol=float(pick(fatol, "pl_fatol", DEFAULT_FATOL)),
-                    maxiter=pick(maxiter, "pl_maxiter", None), adaptive=bool(pick(adaptive, "pl_adaptive", True)),
-                    restarts=int(pick(restarts, "pl_restarts", DEFAULT_RESTARTS)), on_nonunitary=on_nonunitary)
-        count = sel["count"]                                              # [S][T]
-        for lo in range(0, T, per_run):
-            hi = min(T, lo + per_run)
-            ss, tt = np.nonzero(np.broadcast_to(~dead[:, None], (S, hi - lo)))
-            if len(ss) == 0:
-                continue
-            tt = tt + lo
-            order = np.lexsort((ss, tt))                                  # realisation by realisation, its scales in order
-            ss, tt = ss[order], tt[order]
-            bf_runs = meas[ss, tt] if meas.ndim == 3 else meas[tt]
-            # a run with fewer than K finite seeds keeps that many starts; the rows behind them are never evaluated
-            with SimplexMaximizer([models[s] for s in ss], cols, [bases[s] for s in ss], nstarts=0, nseed=0,
-                                  starts=np.nan_to_num(sel["cube"][ss, tt], nan=0.5), start_counts=count[ss, tt],
-                                  measurements=(bf_runs, sms[tt]),
-                                  labels=["realisation %d, %s" % (t, labels[s]) for s, t in zip(ss, tt)], **opts) as mx:
-                r = mx.run(check=False)
-            for k in res:
-                res[k][tt, ss] = r[k]
+
+        def measurement_of(ss, tt):
+            return dict(measurements=(meas[ss, tt] if meas.ndim == 3 else meas[tt], sms[tt]))
+        res, dead = _polish(models, cols, bases, labels, sel, nu_seeds, T, per_run, opts, measurement_of)
         t3 = time.perf_counter()
     finally:
         for m in models:
             m.close()
-    if check and on_nonunitary == "raise" and res["failed"].any():
+    _statistic(res, dead, labels, scales, threshold, check and on_nonunitary == "raise")
+    res.update(scales=scales, measurements=meas, smearings=sms, nonunitary_seeds=nu_seeds, **_starts_of(sel),
+               seconds=t3 - t0, seconds_seed=t1 - t0, seconds_select=t2 - t1, seconds_polish=t3 - t2)
+    return res
+
+
+def _polish_options(args, xatol, fatol, maxiter, adaptive, restarts, on_nonunitary):
+    """the maximiser's options of a realisation scan: the keyword, else args' --pl-* option, else the default"""
+    def pick(v, name, default):
+        return v if v is not None else _opt(args, name, default)
+    return dict(xatol=float(pick(xatol, "pl_xatol", DEFAULT_XATOL)), fatol=float(pick(fatol, "pl_fatol", DEFAULT_FATOL)),
+                maxiter=pick(maxiter, "pl_maxiter", None), adaptive=bool(pick(adaptive, "pl_adaptive", True)),
+                restarts=int(pick(restarts, "pl_restarts", DEFAULT_RESTARTS)), on_nonunitary=on_nonunitary)
+
+
+def _polish(models, cols, bases, labels, sel, nu_seeds, T, per_run, opts, measurement_of):
+    """The selected seeds of every (scale, realisation) polished, `per_run` realisations per maximiser: measurement_of(ss, tt) gives the
+    maximiser's keyword that carries the runs' own measurements.  Returns (res [T][S] arrays, dead [S])."""
+    S, ndim = len(models), len(bases[0])
+    res = dict(max_lnl=np.full((T, S), -np.inf), argmax_theta=np.full((T, S, ndim), np.nan), nstarts=np.zeros((T, S), np.int32),
+               nfev=np.zeros((T, S), np.int64), niter=np.zeros((T, S), np.int64), nonunitary=np.zeros((T, S), np.uint32),
+               parked=np.zeros((T, S), np.uint32), failed=np.zeros((T, S), bool))
+    dead = (nu_seeds > 0) if opts["on_nonunitary"] == "raise" else np.zeros(S, bool)
+    res["failed"][:, dead] = True
+    count = sel["count"]                                              # [S][T]
+    for lo in range(0, T, per_run):
+        hi = min(T, lo + per_run)
+        ss, tt = np.nonzero(np.broadcast_to(~dead[:, None], (S, hi - lo)))
+        if len(ss) == 0:
+            continue
+        tt = tt + lo
+        order = np.lexsort((ss, tt))                                  # realisation by realisation, its scales in order
+        ss, tt = ss[order], tt[order]
+        # a run with fewer than K finite seeds keeps that many starts; the rows behind them are never evaluated
+        with SimplexMaximizer([models[s] for s in ss], cols, [bases[s] for s in ss], nstarts=0, nseed=0,
+                              starts=np.nan_to_num(sel["cube"][ss, tt], nan=0.5), start_counts=count[ss, tt],
+                              labels=["realisation %d, %s" % (t, labels[s]) for s, t in zip(ss, tt)], **measurement_of(ss, tt), **opts) as mx:
+            r = mx.run(check=False)
+        for k in res:
+            res[k][tt, ss] = r[k]
+    return res, dead
+
+
+def _statistic(res, dead, labels, scales, threshold, check):
+    """ts and limits of a polished scan into `res`; AssertionError for a failed run when `check`"""
+    if check and res["failed"].any():
         t, s = np.argwhere(res["failed"])[0]
         what = "a seed point of" if dead[s] else "realisation %d," % t
         raise AssertionError("Matrix is not unitary! ({0} {1})".format(what, labels[s]))
     null = int(np.argmin(scales))
     with np.errstate(invalid="ignore"):
-        ts = -2.0 * (res["max_lnl"] - res["max_lnl"][:, null:null + 1])
+        res["ts"] = -2.0 * (res["max_lnl"] - res["max_lnl"][:, null:null + 1])
+    T = len(res["max_lnl"])
     limits = np.full(T, np.nan)
     for t in range(T):
         lim = profile_likelihood_limit(scales, res["max_lnl"][t], threshold)
         if lim is not None:
             limits[t] = lim
-    res.update(scales=scales, measurements=meas, smearings=sms, ts=ts, limits=limits, nonunitary_seeds=nu_seeds,
-               start_cube=np.ascontiguousarray(sel["cube"].transpose(1, 0, 2, 3)), start_score=np.ascontiguousarray(sel["score"].transpose(1, 0, 2)),
-               start_count=np.ascontiguousarray(count.T),
+    res["limits"] = limits
+
+
+def _starts_of(sel):
+    """the selection as a scan reports it: [T][S] first"""
+    return dict(start_cube=np.ascontiguousarray(sel["cube"].transpose(1, 0, 2, 3)), start_score=np.ascontiguousarray(sel["score"].transpose(1, 0, 2)),
+                start_count=np.ascontiguousarray(sel["count"].T))
+
+
+def binned_realisation_scan(args, asimov_paramset, llh_paramset, scales, binned, measurements=None, ntoys=None, toy_seed=0, sigmas=None,
+                            nstarts=DEFAULT_TOY_STARTS, nseed=None, run_ids=None, xatol=None, fatol=None, maxiter=None, restarts=None,
+                            adaptive=None, seed=None, on_nonunitary="raise", smearing=None, device=0, batch=None, threshold=None, check=True):
+    """realisation_scan for the energy-resolved likelihood: the profile likelihood of T realisations of the
+    `llh.BinnedMeasurement` `binned` at every scale, with profile_scan(binned=...)'s conventions and seed points.
+
+    measurements: [T][nb][3], shared by all scales, or [S][T][nb][3]; None: `ntoys` realisations by
+    draw_binned_realisations(binned, ntoys, toy_seed).  sigmas: [nb], shared by the realisations (default: binned.sigma), or [T][nb].
+    Everything else, and the dict returned, as realisation_scan: max_lnl[t, s] is the maximum under (m_t, sigma_t), `measurements` is
+    [T][nb][3] (or [S][T][nb][3]) and `sigmas` [T][nb] takes the place of `smearings`."""
+    if on_nonunitary not in ("raise", "-inf"):
+        raise ValueError("on_nonunitary must be 'raise' or '-inf'")
+    K = int(nstarts)
+    if not 1 <= K <= MAX_TOY_STARTS:
+        raise ValueError("nstarts must be 1 to %d, the starts the shared seeding selects" % MAX_TOY_STARTS)
+    scales = np.asarray(scales, dtype=np.float64)
+    S, nb = len(scales), binned.nbins
+    if measurements is None:
+        if ntoys is None:
+            raise ValueError("give measurements or ntoys")
+        measurements = draw_binned_realisations(binned, ntoys, toy_seed)
+    meas = np.ascontiguousarray(measurements, dtype=np.float64)
+    if meas.ndim not in (3, 4) or meas.shape[-2:] != (nb, 3) or (meas.ndim == 4 and meas.shape[0] != S):
+        raise ValueError("measurements must be [T][%d][3] or [S][T][%d][3]" % (nb, nb))
+    T = meas.shape[-3]
+    sg = np.asarray(binned.sigma if sigmas is None else sigmas, dtype=np.float64)
+    if sg.shape not in ((nb,), (T, nb)):
+        raise ValueError("sigmas must be [%d], shared by the realisations, or [T][%d]" % (nb, nb))
+    sgs = np.ascontiguousarray(np.broadcast_to(sg, (T, nb)))
+    per_run = MAX_RUNS // S if batch is None else int(batch)
+    if per_run < 1 or per_run * S > MAX_RUNS:
+        raise ValueError("batch must keep batch * len(scales) within %d runs" % MAX_RUNS)
+    opts = _polish_options(args, xatol, fatol, maxiter, adaptive, restarts, on_nonunitary)
+    cols, models, bases, labels = _scan_models(args, asimov_paramset, llh_paramset, scales, smearing, device, binned=binned)
+    try:
+        t0 = time.perf_counter()
+        with BinnedToySeeds(models, cols, bases, nseed=int(nseed if nseed is not None else _opt(args, "pl_seed_points", DEFAULT_SEED_POINTS)),
+                            seed=int(seed if seed is not None else _opt(args, "seed", 0)), run_ids=run_ids) as seeds:
+            t1 = time.perf_counter()
+            sel = seeds.select(meas, sgs, K)
+            nu_seeds = seeds.nonunitary_seeds.copy()
+        t2 = time.perf_counter()
+
+        def measurement_of(ss, tt):
+            return dict(binned_measurements=(meas[ss, tt] if meas.ndim == 4 else meas[tt], sgs[tt]))
+        res, dead = _polish(models, cols, bases, labels, sel, nu_seeds, T, per_run, opts, measurement_of)
+        t3 = time.perf_counter()
+    finally:
+        for m in models:
+            m.close()
+    _statistic(res, dead, labels, scales, threshold, check and on_nonunitary == "raise")
+    res.update(scales=scales, measurements=meas, sigmas=sgs, smearings=sgs, nonunitary_seeds=nu_seeds, **_starts_of(sel),
                seconds=t3 - t0, seconds_seed=t1 - t0, seconds_select=t2 - t1, seconds_polish=t3 - t2)
     return res
 

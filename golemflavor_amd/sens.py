@@ -10,7 +10,8 @@ posterior_<identifier>_scale_<10^scale:.0E>.npz beside the arrays (INTEGRATION.m
 --binned-measurement FILE.npy, --binned-smearing) fits the composition of every energy bin instead of the flux average; every
 file name then carries `_ebins` behind the identifier.  The frequentist arrays hold [scale, profile max lnL] in both files: the
 statistic golemflavor/plot.py:605-608 (plot_statistic) receives.  --stat-method frequentist --realisations T also profiles T mock
-measurements thrown around the injected composition and writes fr_realisations{identifier}.npz beside fr_maxllh.
+measurements thrown around the injected composition (with --energy-resolved a throw per energy bin) and
+writes fr_realisations{identifier}.npz beside fr_maxllh.
 --evidence-realisations T (the Bayesian method) reweights the evidence scan's own points to T such measurements and
 writes fr_evidence_realisations{identifier}.npz beside fr_stat; the Asimov arrays are what the command writes without the option.
 """
@@ -77,7 +78,7 @@ def parse_args(argv=None):
     ap.add_argument("--realisations", type=int, default=None, metavar="T",
                     help="frequentist: also profile T mock measurements m = injected composition + smearing z, z ~ N(0, I), at every "
                          "scale, and write fr_realisations<identifier>.npz (max lnL, the statistic and the limit of every realisation, "
-                         "the band of the limits)")
+                         "the band of the limits); with --energy-resolved a mock measurement of every energy bin, m_k + sigma_k z")
     ap.add_argument("--realisation-seed", type=int, default=0,
                     help="with --realisations or --evidence-realisations: the seed the realisations are thrown with")
     ap.add_argument("--evidence-realisations", type=int, default=None, metavar="T",
@@ -122,8 +123,6 @@ def parse_args(argv=None):
             ap.error("--realisations needs --stat-method frequentist (it profiles mock measurements)")
         if args.realisations < 1 or not 1 <= args.realisation_starts <= realisations_mod.MAX_TOY_STARTS:
             ap.error("--realisations takes T >= 1 and --realisation-starts 1 to %d" % realisations_mod.MAX_TOY_STARTS)
-        if args.energy_resolved:
-            ap.error("--realisations are of the flux-averaged likelihood: it does not combine with --energy-resolved")
         if args.eval_segment.lower() != "all":
             ap.error("--realisations needs every scale (a limit per realisation): it does not combine with --eval-segment")
     if args.evidence_realisations is not None:
@@ -318,11 +317,14 @@ def realisations_path(args):
     return os.path.join(base, "fr_realisations" + identifier(args) + ".npz")
 
 
-def _realisations(args, scales, idx, asimov, llh_ps):
-    """--realisations: the scan, its file, and what the JSON line says of it."""
-    res = realisations_mod.realisation_scan(args, asimov, llh_ps, scales[idx], ntoys=args.realisations, toy_seed=args.realisation_seed,
-                                            nstarts=args.realisation_starts, run_ids=idx, on_nonunitary=args.on_nonunitary,
-                                            device=args.device)
+def _realisations(args, scales, idx, asimov, llh_ps, binned=None):
+    """--realisations: the scan (of the energy-resolved likelihood with `binned`), its file, and what the JSON line says of it."""
+    kw = dict(ntoys=args.realisations, toy_seed=args.realisation_seed, nstarts=args.realisation_starts, run_ids=idx,
+              on_nonunitary=args.on_nonunitary, device=args.device)
+    if binned is not None:
+        res = realisations_mod.binned_realisation_scan(args, asimov, llh_ps, scales[idx], binned, **kw)
+    else:
+        res = realisations_mod.realisation_scan(args, asimov, llh_ps, scales[idx], **kw)
     f = realisations_path(args)
     os.makedirs(os.path.dirname(f) or ".", exist_ok=True)
     band = realisations_mod.save_realisations(f, res)
@@ -343,7 +345,7 @@ def _frequentist(args, scales, idx, asimov, llh_ps, outfile, outfile_llh, binned
     null = np.flatnonzero(scales[idx] == scales[0])
     ts = (-2 * (ml - ml[null[0]])).tolist() if len(null) and np.isfinite(ml[null[0]]) else None
     limit = profile_llh.profile_likelihood_limit(scales[idx], ml) if args.eval_segment is None else None
-    toys = _realisations(args, scales, idx, asimov, llh_ps) if getattr(args, "realisations", None) is not None else None
+    toys = _realisations(args, scales, idx, asimov, llh_ps, binned) if getattr(args, "realisations", None) is not None else None
     print(json.dumps({
         **({"realisations": toys} if toys is not None else {}),
         **({"likelihood": "energy-resolved"} if binned is not None else {}),

@@ -795,6 +795,46 @@ int gf_toys_scores(gf_toys* t, const double* bf, int per_scale, const double* sm
 int gf_toy_select(int device, const double* lp, const double* fr, const int32_t* status, int nseed, const double* bf,
                   const double* smearing, double offset, int ntoys, int K, int32_t* out_index, double* out_score, int32_t* out_count);
 
+/* ---- realisation ensembles of the energy-resolved likelihood (csrc/gf_toys_binned.hpp holds the arithmetic) - */
+/* A realisation of a binned measurement (m_k, sigma_k), k < nbins, is m_{t,k} = m_k + sigma_k z_{t,k}, z ~ N(0, I_3) independent per bin
+ * (thrown by the caller).  A seed's prior sum, verdict and composition at every energy bin do not depend on the measurement, so the seeds
+ * of every scale are drawn and propagated once -- the points gf_simplex_create's seeding draws for the same seed and run id -- and
+ * ranked under every realisation:
+ *   score(t, i) = lp_i + (sum_k log_of_exp(fma(mh_{t,k}, |fr_{i,k} - m_{t,k}|^2, k_{t,k})) + offset), the binned lnprob's own operations
+ *   in their order (the sum ascends in k); -inf for a seed the reference would have raised on and for NaN;
+ *   order, starts and GF_TOY_MAX_STARTS as in 6j.
+ * Models as for gf_simplex_create (one per scale), every one with a binned measurement (gf_model_set_binned_measurement; else
+ * GF_ERR_UNSUPPORTED), one number of energy bins and one likelihood offset for all.  The per-bin compositions take
+ * 24 * nscales * nseed * nbins bytes of device memory. */
+typedef struct gf_toys_binned gf_toys_binned;
+int gf_toys_create_binned(gf_model* const* models, int nscales, int nscan, const int32_t* cols, const double* bases, int nseed, uint64_t seed,
+                          gf_toys_binned** out);
+void gf_toys_destroy_binned(gf_toys_binned* t);
+/* run ids [nscales] (default: the index).  Before gf_toys_seed_binned. */
+int gf_toys_set_run_ids_binned(gf_toys_binned* t, const uint64_t* ids);
+/* Draws and evaluates the seeds, once.  nonunitary [nscales] (NULL = skip).  Synchronous. */
+int gf_toys_seed_binned(gf_toys_binned* t, uint32_t* nonunitary);
+/* scale `scale`'s seeds (NULL = skip): as gf_toys_get_seeds (lnprob: the scale model's own, under its binned measurement; fr: the
+ * flux-averaged composition), and fr_bins [nseed][nbins][3], NaN for a seed whose status is not GF_ST_OK */
+int gf_toys_get_seeds_binned(gf_toys_binned* t, int scale, double* cube, double* lnprob, double* lp, double* fr, double* fr_bins, int32_t* status);
+/* The starts of every (scale, realisation).  meas [ntoys][nbins][3] shared by the scales (per_scale == 0) or [nscales][ntoys][nbins][3];
+ * sigma [nbins] shared by the realisations (per_toy_sigma == 0) or [ntoys][nbins].  Out as gf_toys_select. */
+int gf_toys_select_binned(gf_toys_binned* t, const double* meas, int per_scale, const double* sigma, int per_toy_sigma, int ntoys, int K,
+                          double* cube, int32_t* index, double* score, int32_t* count);
+/* every score the selection ranks, scores [nscales][ntoys][nseed] (ntoys <= 65535) */
+int gf_toys_scores_binned(gf_toys_binned* t, const double* meas, int per_scale, const double* sigma, int per_toy_sigma, int ntoys, double* scores);
+/* The selection alone on host arrays, on `device`: lp [nseed], fr_bins [nseed][nbins][3], status [nseed]; meas [ntoys][nbins][3], sigma
+ * [nbins] or [ntoys][nbins], one offset; out_index and out_score [ntoys][K], out_count [ntoys]. */
+int gf_toy_select_binned(int device, const double* lp, const double* fr_bins, const int32_t* status, int nseed, int nbins, const double* meas,
+                         const double* sigma, int per_toy_sigma, double offset, int ntoys, int K, int32_t* out_index, double* out_score,
+                         int32_t* out_count);
+/* A binned measurement of its own for every run of a maximiser over models with a binned measurement: fr_bins [nruns][nbins][3] and sigma
+ * [nruns][nbins] become the table run r's kernels read in place of its model's, built as gf_model_set_binned_measurement builds it, so
+ * the run evaluates exactly what a model given (fr_bins_r, sigma_r) evaluates.  Before the first gf_simplex_run; may be called again
+ * before it.  Refused: models without a binned measurement (GF_ERR_UNSUPPORTED), a maximiser created with nseed > 0, another nbins than
+ * the models', a composition that is not finite, a width that is not positive and finite or whose constants are not finite. */
+int gf_toys_set_binned_measurements(gf_simplex* s, int nbins, const double* fr_bins, const double* sigma);
+
 #ifdef __cplusplus
 }
 #endif
