@@ -25,6 +25,7 @@ GF_INTERVAL_MAX_BINS = 1 << 20
 GF_INTERVAL_MAX_PERCENTILES = 8
 GF_REWEIGHT_MAX_TARGETS = 64
 GF_TOY_MAX_STARTS = 16
+GF_TABLE_MAX_NSIDE = 2048
 
 GF_OK, GF_ERR_INVALID_ARG, GF_ERR_NO_DEVICE, GF_ERR_HIP, GF_ERR_ALLOC, GF_ERR_COMM, GF_ERR_UNSUPPORTED, GF_ERR_QUEUE_OVERFLOW = range(8)
 GF_ST_OK, GF_ST_OUT_OF_PRIOR, GF_ST_NON_UNITARY, GF_ST_NAN = range(4)
@@ -260,6 +261,8 @@ SIGNATURES = {
                                               _dp, _ip, _dp]),
     "gf_model_set_binned_measurement": (C.c_int, [_vp, C.c_int, _dp, _dp]),
     "gf_model_is_binned": (C.c_int, [_vp]),
+    "gf_model_set_table_likelihood": (C.c_int, [_vp, C.c_int, _dp]),
+    "gf_model_table_nside": (C.c_int, [_vp]),
     "gf_sampler_create_binned": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_double, C.POINTER(_vp)]),
     "gf_toys_set_measurements": (C.c_int, [_vp, _dp, _dp]),
     "gf_toys_set_start_counts": (C.c_int, [_vp, _ip]),

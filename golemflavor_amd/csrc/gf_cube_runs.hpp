@@ -19,6 +19,8 @@ struct GfCubeRuns {
     const GfBsm* const* tbs;        // [R]
     const double* const* ptabs;     // [R]
     const double* const* btabs;     // [R] the runs' binned measurements (gf_consts.h), NULL: the runs have none
+    const double* const* ttabs;     // [R] the runs' tabulated likelihoods (gf_table.hpp), NULL: the runs have none
+    const int32_t* tsides;          // [R] ... and their sides
     const uint64_t* run_ids;        // [R] Philox counter word 0
     const double* bases;            // [R][GF_MAX_DIM] values of the columns that are not scanned
     GfArbQueue* pq;                 // BSM: parked proposals, capacity = the proposals of one step
@@ -34,11 +36,14 @@ struct GfCubeRunsHost {
     hipStream_t stream = nullptr;
     int device = 0, cus = 256, mode = 0;
     int binned = 0;                     // every run's model carries a binned measurement: the kernels' MODE_BSM_BINNED instance
+    int table = 0;                      // every run's model carries a tabulated likelihood: the MODE_BSM_TABLE instance
     int initialised = 0;
     GfCommon* d_commons = nullptr;
     const GfBsm** d_tbs = nullptr;
     const double** d_ptabs = nullptr;
     const double** d_btabs = nullptr;
+    const double** d_ttabs = nullptr;
+    int32_t* d_tsides = nullptr;
     double* d_btab_runs = nullptr;      // cube_runs_set_binned_measurements: [nruns][nbins][GF_BINNED_STRIDE], the runs' own tables
     uint64_t* d_run_ids = nullptr;
     double* d_bases = nullptr;
@@ -104,7 +109,7 @@ __global__ __launch_bounds__(GF_BLOCK) void k_cube_draw(const GfCubeRuns a, uint
     cube_to_theta(a, a.commons[r], r, v, theta + ((int64_t)r * n + i) * a.ndim);
 }
 
-// An evaluation kernel's instances: PRIOR_ONLY, SM_GAUSS and BSM_BINNED at one lane per point, BSM at 1, 4 or 16.  `launch` is called
+// An evaluation kernel's instances: PRIOR_ONLY, SM_GAUSS, BSM_BINNED and BSM_TABLE at one lane per point, BSM at 1, 4 or 16.  `launch` is called
 // with std::integral_constant<int, MODE> and <int, LPW>.
 template <class Launch>
 hipError_t launch_mode_lpw(int mode, int lpw, Launch launch)
@@ -114,6 +119,7 @@ hipError_t launch_mode_lpw(int mode, int lpw, Launch launch)
     case MODE_PRIOR_ONLY: return launch(std::integral_constant<int, MODE_PRIOR_ONLY>(), std::integral_constant<int, 1>());
     case MODE_SM_GAUSS: return launch(std::integral_constant<int, MODE_SM_GAUSS>(), std::integral_constant<int, 1>());
     case MODE_BSM_BINNED: return launch(std::integral_constant<int, MODE_BSM_BINNED>(), std::integral_constant<int, 1>());
+    case MODE_BSM_TABLE: return launch(std::integral_constant<int, MODE_BSM_TABLE>(), std::integral_constant<int, 1>());
     default:
         switch (lpw) {
         case 4: return launch(M(), std::integral_constant<int, 4>());
@@ -138,9 +144,9 @@ void cube_runs_free(GfCubeRunsHost& h, GfCubeRuns& a)
 {
     (void)hipSetDevice(h.device);
     if (h.stream) (void)hipStreamSynchronize(h.stream);
-    void* ptrs[] = {h.d_commons, (void*)h.d_tbs, (void*)h.d_ptabs, (void*)h.d_btabs, h.d_btab_runs, h.d_run_ids, h.d_bases, h.d_state, h.d_ctl, a.pq, a.pend_rows};
+    void* ptrs[] = {h.d_commons, (void*)h.d_tbs, (void*)h.d_ptabs, (void*)h.d_btabs, (void*)h.d_ttabs, h.d_tsides, h.d_btab_runs, h.d_run_ids, h.d_bases, h.d_state, h.d_ctl, a.pq, a.pend_rows};
     for (void* p : ptrs) if (p) (void)hipFree(p);
-    h.d_commons = nullptr; h.d_tbs = nullptr; h.d_ptabs = nullptr; h.d_btabs = nullptr; h.d_btab_runs = nullptr; h.d_run_ids = nullptr; h.d_bases = nullptr;
+    h.d_commons = nullptr; h.d_tbs = nullptr; h.d_ptabs = nullptr; h.d_btabs = nullptr; h.d_ttabs = nullptr; h.d_tsides = nullptr; h.d_btab_runs = nullptr; h.d_run_ids = nullptr; h.d_bases = nullptr;
     h.d_state = nullptr; h.d_ctl = nullptr; a.pq = nullptr; a.pend_rows = nullptr;
     delete[] h.models;
     h.models = nullptr;
@@ -161,8 +167,9 @@ int cube_runs_create(GfCubeRunsHost& h, GfCubeRuns& a, gf_model* const* models, 
     }
     std::vector<GfCommon> hc(nruns);
     std::vector<const GfBsm*> htb(nruns);
-    std::vector<const double*> hpt(nruns), hbt(nruns);
-    int nbinned = 0;
+    std::vector<const double*> hpt(nruns), hbt(nruns), htt(nruns);
+    std::vector<int32_t> hts(nruns);
+    int nbinned = 0, ntable = 0;
     std::vector<double> hb((size_t)nruns * GF_MAX_DIM, 0.0);
     int cus = 256, nbins_max = 0;
     for (int r = 0; r < nruns; ++r) {
@@ -172,15 +179,19 @@ int cube_runs_create(GfCubeRunsHost& h, GfCubeRuns& a, gf_model* const* models, 
             return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: every model must share device, ndim and mode with model 0", who);
         hc[r] = *c;
         nbinned += gf_model_binned(models[r], &hbt[r]);
+        hts[r] = gf_model_table(models[r], &htt[r]);
+        ntable += hts[r] > 0;
         if (nb > nbins_max) nbins_max = nb;
         for (int d = 0; d < ndim; ++d) hb[(size_t)r * GF_MAX_DIM + d] = bases[(size_t)r * ndim + d];
     }
     if (nbinned != 0 && nbinned != nruns)
         return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: %d of the %d models carry a binned measurement; all of a set must, or none", who, nbinned, nruns);
+    if (ntable != 0 && ntable != nruns)
+        return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: %d of the %d models carry a tabulated likelihood; all of a set must, or none", who, ntable, nruns);
     h.models = new (std::nothrow) gf_model*[nruns];
     if (!h.models) return GF_ERR_ALLOC;
     for (int r = 0; r < nruns; ++r) h.models[r] = models[r];
-    h.stream = (hipStream_t)stream0; h.device = device0; h.cus = cus; h.mode = c0->mode; h.binned = nbinned != 0;
+    h.stream = (hipStream_t)stream0; h.device = device0; h.cus = cus; h.mode = c0->mode; h.binned = nbinned != 0; h.table = ntable != 0;
     a.seed = seed;
     a.nruns = nruns; a.nscan = nscan; a.ndim = ndim; a.nbins_max = nbins_max;
     for (int d = 0; d < GF_MAX_DIM; ++d) a.slot[d] = slot[d];
@@ -197,6 +208,7 @@ int cube_runs_create(GfCubeRunsHost& h, GfCubeRuns& a, gf_model* const* models, 
     al((void**)&h.d_tbs, sizeof(void*) * R);
     al((void**)&h.d_ptabs, sizeof(void*) * R);
     if (h.binned) al((void**)&h.d_btabs, sizeof(void*) * R);
+    if (h.table) { al((void**)&h.d_ttabs, sizeof(void*) * R); al((void**)&h.d_tsides, sizeof(int32_t) * R); }
     al((void**)&h.d_run_ids, sizeof(uint64_t) * R);
     al((void**)&h.d_bases, sizeof(double) * R * GF_MAX_DIM);
     al((void**)&h.d_state, sizeof(GfStepState));
@@ -204,12 +216,13 @@ int cube_runs_create(GfCubeRunsHost& h, GfCubeRuns& a, gf_model* const* models, 
     up((void*)h.d_tbs, htb.data(), sizeof(void*) * R);
     up((void*)h.d_ptabs, hpt.data(), sizeof(void*) * R);
     if (h.binned) up((void*)h.d_btabs, hbt.data(), sizeof(void*) * R);
+    if (h.table) { up((void*)h.d_ttabs, htt.data(), sizeof(void*) * R); up(h.d_tsides, hts.data(), sizeof(int32_t) * R); }
     up(h.d_run_ids, ids.data(), sizeof(uint64_t) * R);
     up(h.d_bases, hb.data(), sizeof(double) * R * GF_MAX_DIM);
     up(h.d_state, &hs, sizeof(hs));
     if (e == hipSuccess) e = hipStreamSynchronize(h.stream);              // the host vectors go out of scope
     if (e != hipSuccess) { const int rc = gf_hip_fail(e, who); cube_runs_free(h, a); return rc; }
-    a.commons = h.d_commons; a.tbs = h.d_tbs; a.ptabs = h.d_ptabs; a.btabs = h.d_btabs; a.run_ids = h.d_run_ids; a.bases = h.d_bases;
+    a.commons = h.d_commons; a.tbs = h.d_tbs; a.ptabs = h.d_ptabs; a.btabs = h.d_btabs; a.ttabs = h.d_ttabs; a.tsides = h.d_tsides; a.run_ids = h.d_run_ids; a.bases = h.d_bases;
     return GF_OK;
 }
 
@@ -221,8 +234,8 @@ hipError_t cube_runs_alloc_queue(GfCubeRunsHost& h, GfCubeRuns& a, size_t w)
 }
 
 // the settle kernel's arguments common to both variants: run r is its chain r, `nwalkers` / 2 proposals each
-// the MODE of the evaluation kernels' instance: the models' mode, or MODE_BSM_BINNED for a binned set
-inline int cube_runs_eval_mode(const GfCubeRunsHost& h) { return h.binned ? MODE_BSM_BINNED : h.mode; }
+// the MODE of the evaluation kernels' instance: the models' mode, MODE_BSM_BINNED for a binned set, MODE_BSM_TABLE for a table set
+inline int cube_runs_eval_mode(const GfCubeRunsHost& h) { return h.table ? MODE_BSM_TABLE : h.binned ? MODE_BSM_BINNED : h.mode; }
 
 void cube_runs_settle_args(const GfCubeRunsHost& h, const GfCubeRuns& a, int nwalkers, GfSettleArgs& sa)
 {
@@ -247,6 +260,8 @@ int cube_runs_set_ids(GfCubeRunsHost& h, const GfCubeRuns& a, const uint64_t* id
 int cube_runs_set_measurements(GfCubeRunsHost& h, const GfCubeRuns& a, const double* bf, const double* smearing, const char* who)
 {
     if (h.initialised) return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: before the first run", who);
+    if (h.table)
+        return gf_fail_msg(GF_ERR_UNSUPPORTED, "%s: the runs' models carry a tabulated likelihood, which has no Gaussian measurement to replace", who);
     if (h.binned)
         return gf_fail_msg(GF_ERR_UNSUPPORTED, "%s: the runs' models carry a binned measurement; a run's own measurement replaces the flux-averaged one only", who);
     if (h.mode != MODE_SM_GAUSS && h.mode != MODE_BSM_GAUSS)
@@ -280,6 +295,8 @@ int cube_runs_set_binned_measurements(GfCubeRunsHost& h, const GfCubeRuns& a, in
                                       const char* who)
 {
     if (h.initialised) return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: before the first run", who);
+    if (h.table)
+        return gf_fail_msg(GF_ERR_UNSUPPORTED, "%s: the runs' models carry a tabulated likelihood, which has no binned measurement to replace", who);
     if (!h.binned)
         return gf_fail_msg(GF_ERR_UNSUPPORTED, "%s: the runs' models carry no binned measurement; a run's own binned measurement replaces a model's", who);
     const size_t R = a.nruns, nb = nbins > 0 ? nbins : 0;

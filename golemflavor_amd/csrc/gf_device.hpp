@@ -24,6 +24,8 @@ constexpr int MODE_PRIOR_ONLY = 0, MODE_SM_GAUSS = 1, MODE_BSM_GAUSS = 2;
 // internal, never a GfCommon::mode: a BSM model that carries a measurement per energy bin, as the nested sampler's and the
 // maximiser's evaluation kernels instantiate proposal_lnprob for it
 constexpr int MODE_BSM_BINNED = 3;
+// likewise internal: a BSM model that carries a tabulated flavour-plane likelihood
+constexpr int MODE_BSM_TABLE = 4;
 
 __device__ __forceinline__ double gf_inf() { return __longlong_as_double(0x7ff0000000000000LL); }
 __device__ __forceinline__ double gf_nan() { return __longlong_as_double(0x7ff8000000000000LL); }

@@ -30,6 +30,9 @@ void gf_internal_gauss_consts(double smearing, double* inv_smear, double* c0, do
 // 1 if the model carries a binned measurement (gf_model_set_binned_measurement), else 0; *d_btab <- its device table
 // [nbins][5] = {m_k[3], mh_k, k_k} (NULL without one).  The table's address does not change when the measurement is replaced.
 int gf_model_binned(gf_model* m, const double** d_btab);
+// the side of the model's tabulated likelihood (gf_model_set_table_likelihood), 0 without one; *d_table <- its device
+// table (NULL without one).  A replacement of another side moves the table.
+int gf_model_table(gf_model* m, const double** d_table);
 // the model's kernels on a stream of the caller's
 int gf_model_lnprob_on(gf_model* m, void* stream, const double* d_theta, int layout, int64_t n, double* d_lnprob, double* d_fr, int32_t* d_status);
 int gf_model_propagate_on(gf_model* m, void* stream, const double* d_theta, int layout, int64_t n, double* d_fr, int32_t* d_status);

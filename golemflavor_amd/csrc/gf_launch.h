@@ -44,6 +44,11 @@ hipError_t gf_launch_bsm(const GfCommon& c, const GfCommon* d_common, const GfBs
 // set to NaN for the rows outside the prior box
 hipError_t gf_launch_bsm_binned(const GfCommon& c, const GfCommon* d_common, const GfBsm* d_bsm, int nbins, const double* ptab, const double* btab,
                                 const double* theta, int layout, int64_t n, double* lnprob, double* fr, int32_t* status, int cus, hipStream_t s);
+// gf_table.hip: lnprior + the tabulated flavour-plane likelihood of a BSM model that carries a table; `table`: its device
+// table of side `nside` (gf_table.hpp).  `status` as for gf_launch_bsm_binned; `fr` (may be NULL): out, the composition looked up, NaN
+// for the rows outside the prior box
+hipError_t gf_launch_bsm_table(const GfCommon& c, const GfCommon* d_common, const GfBsm* d_bsm, const double* ptab, const double* table, int nside,
+                               const double* theta, int layout, int64_t n, double* lnprob, double* fr, int32_t* status, int cus, hipStream_t s);
 // gf_unitarity.hip: settles the walkers queued by the evaluation kernels in emulated x87 arithmetic, bin by bin from the highest
 // energy down; a bin the reference would raise on turns status[walker] into NON_UNITARY and lnprob[walker] (if given) into NaN
 // and ends that walker.  `max_items` (walkers) bounds the grid; the item count itself is read on the device.  `seen` (pinned host memory, may be NULL): the item count

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include <mutex>
+#include <vector>
 
 #include "gf_consts.h"
 #include "gf_pool.h"
@@ -34,6 +35,11 @@ struct gf_model {
     size_t cube_cap = 0;
     double* d_btab = nullptr;    // gf_model_set_binned_measurement: [GF_MAX_BINS][GF_BINNED_STRIDE], allocated by the first call and kept
     int binned = 0;              // ... and from then on lnprob is the energy-resolved likelihood; c.mode stays BSM_GAUSS
+    double* d_table = nullptr;   // gf_model_set_table_likelihood: ln L at the nodes of a lattice of side table_nside (gf_table.hpp)
+    int table_nside = 0;         // ... and while > 0 lnprob is lnprior + the table's value; c.mode stays BSM_GAUSS
+    int64_t table_cap = 0;       // nodes d_table has room for: a replacement that fits is written in place
+    std::vector<double*> tables_retired;   // tables a larger replacement outgrew, kept until the model goes: a run set created
+                                           // before the replacement still reads its own (gf_cube_runs.hpp)
     std::mutex call_mu;          // serialises the entry points that use the model's staging buffers / the stream's unitarity workspace
 };
 

@@ -14,8 +14,10 @@
 #include "gf_host.h"
 #include "gf_model.h"
 #include "gf_spectrum.h"
+#include "gf_table.hpp"
 
 static_assert(GF_MAX_DIM == 16 && GF_MAX_BINS == 64, "header / device constant mismatch");
+static_assert(GF_TABLE_MAX_NSIDE == GF_TABLE_NSIDE_LIMIT, "header / gf_table.hpp mismatch");
 
 namespace {
 
@@ -309,6 +311,17 @@ int launch_lnprob(gf_model* m, hipStream_t st, const double* d_theta, int layout
                   int32_t* d_status)
 {
     if (n == 0) return GF_OK;
+    if (m->table_nside > 0) {
+        // DESIGN.md 6m.  The verdict is the propagate launch's, first on the same stream as for a binned model; k_bsm_table reads the
+        // status it left and writes the composition it looks up (the propagate launch's, bit for bit) over that launch's
+        if (d_status) {
+            const int rc = launch_bsm_on(m, st, d_theta, layout, n, 0, nullptr, d_fr, d_status, "table lnprob: propagate launch");
+            if (rc != GF_OK) return rc;
+        }
+        const hipError_t e = gf_launch_bsm_table(m->c, m->d_common, m->d_bsm, m->d_ptab, m->d_table, m->table_nside, d_theta, layout, n, d_lnprob,
+                                                 d_fr, d_status, m->cus, st);
+        return e != hipSuccess ? gf_hip_fail(e, "table lnprob launch") : GF_OK;
+    }
     if (m->binned) {
         // DESIGN.md 6i.  The verdict (and the flux-averaged composition, if asked for) is the propagate launch's, first on the same
         // stream as in gf_propagate_bins; k_bsm_binned reads the status it left and turns it into lnprob's
@@ -400,6 +413,8 @@ void gf_model_destroy(gf_model* m)
     }
     if (m->d_cube) (void)hipFree(m->d_cube);
     if (m->d_btab) (void)hipFree(m->d_btab);
+    if (m->d_table) (void)hipFree(m->d_table);
+    for (double* t : m->tables_retired) (void)hipFree(t);
     delete m;
 }
 
@@ -415,6 +430,8 @@ int gf_model_set_binned_measurement(gf_model* m, int nbins, const double* fr_bin
     gf_internal_set_error("");
     if (m->c.mode != GF_MODE_BSM_GAUSS)
         return gf_fail_msg(GF_ERR_UNSUPPORTED, "gf_model_set_binned_measurement: the model has no energy bins (mode %d)", m->c.mode);
+    if (m->table_nside > 0)
+        return gf_fail_msg(GF_ERR_UNSUPPORTED, "gf_model_set_binned_measurement: the model carries a tabulated likelihood (side %d)", m->table_nside);
     if (nbins != m->hb.nbins)
         return gf_fail_msg(GF_ERR_INVALID_ARG, "gf_model_set_binned_measurement: %d bins given, the model has %d", nbins, m->hb.nbins);
     double tab[GF_BINNED_STRIDE * GF_MAX_BINS];
@@ -453,6 +470,64 @@ int gf_model_binned(gf_model* m, const double** d_btab)
 {
     if (d_btab) *d_btab = m && m->binned ? m->d_btab : nullptr;
     return m && m->binned ? 1 : 0;
+}
+
+// ln L at the nodes of the flavour triangle's lattice of side `nside` (gf_table.hpp).  Everything is validated before the
+// model is touched; the upload is stream-ordered on a pool stream behind whatever the model's own stream still has in flight.
+int gf_model_set_table_likelihood(gf_model* m, int nside, const double* values)
+{
+    if (!m || !values) return GF_ERR_INVALID_ARG;
+    gf_internal_set_error("");
+    if (m->c.mode != GF_MODE_BSM_GAUSS)
+        return gf_fail_msg(GF_ERR_UNSUPPORTED, "gf_model_set_table_likelihood: a table replaces the flux-averaged (BSM) Gaussian only (mode %d)", m->c.mode);
+    if (m->binned)
+        return gf_fail_msg(GF_ERR_UNSUPPORTED, "gf_model_set_table_likelihood: the model carries a binned measurement");
+    if (nside < 1 || nside > GF_TABLE_MAX_NSIDE)
+        return gf_fail_msg(GF_ERR_INVALID_ARG, "gf_model_set_table_likelihood: side %d outside 1 .. %d", nside, GF_TABLE_MAX_NSIDE);
+    const int64_t nodes = gftab::node_count(nside);
+    bool any_finite = false;
+    for (int64_t k = 0; k < nodes; ++k) {
+        const double v = values[k];
+        if (v != v || v == HUGE_VAL)
+            return gf_fail_msg(GF_ERR_INVALID_ARG, "gf_model_set_table_likelihood: node %lld is %s; a node is finite or -inf", (long long)k,
+                               v != v ? "NaN" : "+inf");
+        any_finite = any_finite || v != -HUGE_VAL;
+    }
+    if (!any_finite) return gf_fail_msg(GF_ERR_INVALID_ARG, "gf_model_set_table_likelihood: every node is -inf");
+    std::lock_guard<std::mutex> lk(m->call_mu);
+    GF_HIP(hipSetDevice(m->device));
+    if (m->stream) GF_HIP(hipStreamSynchronize(m->stream));              // a replaced table may still be read there
+    double* d = m->d_table;
+    const bool grow = nodes > m->table_cap;
+    if (grow) {
+        d = nullptr;
+        GF_HIP(hipMalloc((void**)&d, sizeof(double) * (size_t)nodes));
+    }
+    hipStream_t up = nullptr;
+    hipError_t e = pool_stream(m->device, &up);
+    if (e == hipSuccess) e = hipMemcpyAsync(d, values, sizeof(double) * (size_t)nodes, hipMemcpyHostToDevice, up);
+    if (e == hipSuccess) e = hipStreamSynchronize(up);                   // `values` is the caller's
+    if (up) pool_release(m->device, up, nullptr);
+    if (e != hipSuccess) {
+        if (grow) (void)hipFree(d);
+        return gf_hip_fail(e, "gf_model_set_table_likelihood");
+    }
+    if (grow) {
+        if (m->d_table) m->tables_retired.push_back(m->d_table);
+        m->d_table = d;
+        m->table_cap = nodes;
+    }
+    m->table_nside = nside;
+    return GF_OK;
+}
+
+int gf_model_table_nside(const gf_model* m) { return m ? m->table_nside : 0; }
+
+int gf_model_table(gf_model* m, const double** d_table)
+{
+    const int ns = m ? m->table_nside : 0;
+    if (d_table) *d_table = ns > 0 ? m->d_table : nullptr;
+    return ns;
 }
 
 // internal (not in the public header): gf_sampler.hip reaches the model's constants and stream through these

@@ -283,10 +283,14 @@ __global__ __launch_bounds__(GF_BLOCK) void k_ns_walk(const NsArgs a)
     const GfBsm* tb = a.tbs[r];
     const double* ptab = a.ptabs[r];
     double* ttab = ctab + GF_MAX_DIM * 4;
-    constexpr bool BSM = MODE == MODE_BSM_GAUSS || MODE == MODE_BSM_BINNED;
+    constexpr bool BSM = MODE == MODE_BSM_GAUSS || MODE == MODE_BSM_BINNED || MODE == MODE_BSM_TABLE;
     __shared__ __attribute__((aligned(16))) double btab[MODE == MODE_BSM_BINNED ? GF_BINNED_DOUBLES : 1];   // the run's binned measurement
     load_eval_tables(ctab, ptab, tb, BSM);
     if constexpr (MODE == MODE_BSM_BINNED) load_binned_table(btab, a.btabs[r], tb->nbins);
+    // the run's tabulated likelihood stays in global memory: the table instance alone reads the two arrays
+    const double* ltab = btab;
+    int tside = 0;
+    if constexpr (MODE == MODE_BSM_TABLE) { ltab = a.ttabs[r]; tside = a.tsides[r]; }
     __syncthreads();
     const int t = blockIdx.x * GF_BLOCK + threadIdx.x;
     const int k = t / LPW, sub = t % LPW;
@@ -321,7 +325,7 @@ __global__ __launch_bounds__(GF_BLOCK) void k_ns_walk(const NsArgs a)
     cube_to_theta(a, c, r, u, row);
     int st;
     unsigned long long pending;
-    const double lnq = proposal_lnprob<0, MODE, LPW>(c, tb, ctab, ttab, row, a.ndim, st, sub, fgrp, pending, btab);
+    const double lnq = proposal_lnprob<0, MODE, LPW>(c, tb, ctab, ttab, row, a.ndim, st, sub, fgrp, pending, ltab, tside);
     if (LPW > 1 && sub != 0) return;                         // the group's results are identical: one writer
     if (BSM && pending != 0ull) {
         // undecided unitarity: park; k_stretch_settle<Team9, true> settles and completes this step

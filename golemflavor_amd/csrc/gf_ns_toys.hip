@@ -259,6 +259,8 @@ int gf_nested_toys_evidence(gf_nested* s, const double* bf, const double* smeari
         const GfCommon* c; const GfBsm* tb; const double* pt; const double* bt; int device, cus, nb;
         if (gf_model_constants(v.models[r], &c, &tb, &pt, &device, &cus, &nb) != GF_OK) return GF_ERR_INVALID_ARG;
         binned += gf_model_binned(v.models[r], &bt);
+        if (gf_model_table(v.models[r], nullptr) > 0)
+            return gf_fail_msg(GF_ERR_UNSUPPORTED, "%s: the runs' models carry a tabulated likelihood; a realisation of a table is not defined", who);
         if (c->mode != GF_MODE_SM_GAUSS && c->mode != GF_MODE_BSM_GAUSS)
             return gf_fail_msg(GF_ERR_UNSUPPORTED, "%s: the models have no Gaussian measurement (mode %d)", who, c->mode);
     }

@@ -7,6 +7,7 @@
 #include "gf_device.hpp"
 #include "gf_bsm_device.hpp"
 #include "gf_launch.h"
+#include "gf_table.hpp"
 
 namespace {
 using namespace gfdev;
@@ -35,14 +36,32 @@ __device__ __forceinline__ void philox_block(uint32_t c0, uint32_t c1, uint32_t 
 // that the reference would have died on.
 // MODE_BSM_BINNED (a model with a measurement per energy bin; one lane per point only): the same body around
 // binned_llh<UNI_INLINE>, which reads the model's table from `btab` (LDS).  The other instances do not see it.
+// MODE_BSM_TABLE (a model with a tabulated flavour-plane likelihood; one lane per point only): the MODE_BSM_GAUSS body with
+// gf_table.hpp's lookup in place of gauss_llh; `btab` is then the model's table in global memory and `tside` its side.
 template <int NDIM, int MODE, int LPW>
 __device__ __forceinline__ double proposal_lnprob(const GfCommon& c, const GfBsm* tb, const double* ctab,
                                                   const double* ttab, const double* row, int ndim, int& st, int sub,
-                                                  double* fgrp, unsigned long long& pending, const double* btab = nullptr)
+                                                  double* fgrp, unsigned long long& pending, const double* btab = nullptr,
+                                                  int tside = 0)
 {
     pending = 0ull;
     double val, fr[3];
-    if constexpr (MODE == MODE_BSM_BINNED || MODE == MODE_BSM_GAUSS) {
+    if constexpr (MODE == MODE_BSM_TABLE) {
+        static_assert(LPW == 1, "the tabulated likelihood runs one lane per point");
+        double lp;
+        const bool inbox = lnprior_tab<NDIM>(ctab, row, ndim, c.prior_const, lp);
+        asm volatile("" : "+v"(lp));       // keeps the prior sum ahead of the bin loop (see k_bsm, gf_bsm.hip)
+        val = -gf_inf();
+        st = ST_OUT_OF_PRIOR;
+        if (inbox) {
+            UniAcc acc = {0.0, 0.0, 0ull, 2.0};
+            flux_average<UNI_INLINE, 1>(c, tb, ttab, row, fr, acc, sub, fgrp);
+            st = (acc.clear_max < tb->uni_hi) ? ST_OK : ST_NON_UNITARY;       // tiers 1 and 2 (gf_bsm_device.hpp)
+            pending = st == ST_OK ? uni_arbitration_mask(acc.amb, tb) : 0ull;
+            val = lp + gftab::lookup(btab, tside, fr[0], fr[1]);
+            if (val != val && st == ST_OK) st = ST_NAN;
+        }
+    } else if constexpr (MODE == MODE_BSM_BINNED || MODE == MODE_BSM_GAUSS) {
         static_assert(MODE != MODE_BSM_BINNED || LPW == 1, "the binned likelihood runs one lane per point");
         double lp;
         const bool inbox = lnprior_tab<NDIM>(ctab, row, ndim, c.prior_const, lp);

@@ -911,7 +911,10 @@ int sampler_create(gf_model* const* models, bool multi, int nchains, int nwalker
         if (gf_model_constants(models[ch], &cm, &htb[ch], &hpt[ch], &dev, &cus, &nbins) != GF_OK || dev != device ||
             cm->ndim != c->ndim || cm->mode != c->mode)
             return gf_fail_msg(GF_ERR_INVALID_ARG, "gf_sampler_create_multi: model %d differs from model 0 in device, ndim or mode", ch);
-        // the stretch kernels evaluate the flux-averaged likelihood: never silently for a model whose lnprob is another (DESIGN.md 6i)
+        // the stretch kernels evaluate the flux-averaged likelihood: never silently for a model whose lnprob is another (DESIGN.md 6i, 6m)
+        if (gf_model_table(models[ch], nullptr) > 0)
+            return gf_fail_msg(GF_ERR_UNSUPPORTED, "gf_sampler_create: model %d carries a tabulated likelihood; sample the flux-averaged model and reweight "
+                               "the chain to this one", ch);
         if (binned) {
             // the table's address is the model's for good: a measurement set later lands in the same table
             if (!gf_model_binned(models[ch], &hbt[ch]))

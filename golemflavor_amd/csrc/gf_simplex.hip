@@ -219,10 +219,14 @@ __global__ __launch_bounds__(GF_BLOCK) void k_sx_eval(const SxArgs a)
     const GfBsm* tb = a.tbs[r];
     const double* ptab = a.ptabs[r];
     double* ttab = ctab + GF_MAX_DIM * 4;
-    constexpr bool BSM = MODE == MODE_BSM_GAUSS || MODE == MODE_BSM_BINNED;
+    constexpr bool BSM = MODE == MODE_BSM_GAUSS || MODE == MODE_BSM_BINNED || MODE == MODE_BSM_TABLE;
     __shared__ __attribute__((aligned(16))) double btab[MODE == MODE_BSM_BINNED ? GF_BINNED_DOUBLES : 1];   // the run's binned measurement
     load_eval_tables(ctab, ptab, tb, BSM);
     if constexpr (MODE == MODE_BSM_BINNED) load_binned_table(btab, a.btabs[r], tb->nbins);
+    // the run's tabulated likelihood stays in global memory: the table instance alone reads the two arrays
+    const double* ltab = btab;
+    int tside = 0;
+    if constexpr (MODE == MODE_BSM_TABLE) { ltab = a.ttabs[r]; tside = a.tsides[r]; }
     __syncthreads();
     const int t = blockIdx.x * GF_BLOCK + threadIdx.x;
     const int k = t / LPW, sub = t % LPW;
@@ -237,7 +241,7 @@ __global__ __launch_bounds__(GF_BLOCK) void k_sx_eval(const SxArgs a)
     cube_to_theta(a, c, r, a.pts + w * a.nscan, row);
     int status;
     unsigned long long pending;
-    const double lnq = proposal_lnprob<0, MODE, LPW>(c, tb, ctab, ttab, row, a.ndim, status, sub, fgrp, pending, btab);
+    const double lnq = proposal_lnprob<0, MODE, LPW>(c, tb, ctab, ttab, row, a.ndim, status, sub, fgrp, pending, ltab, tside);
     if (LPW > 1 && sub != 0) return;                         // the group's results are identical: one writer
     if (BSM && pending != 0ull) {
         // undecided unitarity: park; k_stretch_settle<Team9, false, true> writes lnq and the verdict
@@ -528,6 +532,8 @@ int gf_toys_set_measurements(gf_simplex* s, const double* bf, const double* smea
 {
     if (!s || !bf || !smearing) return GF_ERR_INVALID_ARG;
     // the set's own seeding goes through the models' bulk path (cube_runs_draw): it would score under the models' measurement
+    if (s->rs.table)
+        return gf_fail_msg(GF_ERR_UNSUPPORTED, "gf_toys_set_measurements: the runs' models carry a tabulated likelihood, which has no Gaussian measurement to replace");
     if (s->a.nseed > 0)
         return gf_fail_msg(GF_ERR_INVALID_ARG, "gf_toys_set_measurements: the set draws %d seed points per run, which its models would score; "
                            "give the starts (nseed = 0, gf_simplex_set_starts)", s->a.nseed);
@@ -537,6 +543,8 @@ int gf_toys_set_measurements(gf_simplex* s, const double* bf, const double* smea
 int gf_toys_set_binned_measurements(gf_simplex* s, int nbins, const double* fr_bins, const double* sigma)
 {
     if (!s || !fr_bins || !sigma) return GF_ERR_INVALID_ARG;
+    if (s->rs.table)
+        return gf_fail_msg(GF_ERR_UNSUPPORTED, "gf_toys_set_binned_measurements: the runs' models carry a tabulated likelihood, which has no binned measurement to replace");
     // as gf_toys_set_measurements: the set's own seeding would score under the models' measurement
     if (s->a.nseed > 0)
         return gf_fail_msg(GF_ERR_INVALID_ARG, "gf_toys_set_binned_measurements: the set draws %d seed points per run, which its models would score; "

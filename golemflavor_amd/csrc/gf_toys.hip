@@ -248,7 +248,9 @@ int gf_toys_create(gf_model* const* models, int nscales, int nscan, const int32_
     if (!t) return GF_ERR_ALLOC;
     int rc = cube_runs_create(t->rs, t->a, models, nscales, nscan, cols, bases, seed, "gf_toys_create");
     if (rc != GF_OK) { delete t; return rc; }
-    if (t->rs.binned)
+    if (t->rs.table)
+        rc = gf_fail_msg(GF_ERR_UNSUPPORTED, "gf_toys_create: the models carry a tabulated likelihood; a realisation of a table is not defined");
+    else if (t->rs.binned)
         rc = gf_fail_msg(GF_ERR_UNSUPPORTED, "gf_toys_create: the models carry a binned measurement; realisations are of the flux-averaged Gaussian likelihood");
     else if (t->rs.mode != MODE_SM_GAUSS && t->rs.mode != MODE_BSM_GAUSS)
         rc = gf_fail_msg(GF_ERR_UNSUPPORTED, "gf_toys_create: the models have no Gaussian measurement (mode %d)", t->rs.mode);

@@ -279,7 +279,9 @@ int gf_toys_create_binned(gf_model* const* models, int nscales, int nscan, const
     if (!t) return GF_ERR_ALLOC;
     int rc = cube_runs_create(t->rs, t->a, models, nscales, nscan, cols, bases, seed, "gf_toys_create_binned");
     if (rc != GF_OK) { delete t; return rc; }
-    if (!t->rs.binned)
+    if (t->rs.table)
+        rc = gf_fail_msg(GF_ERR_UNSUPPORTED, "gf_toys_create_binned: the models carry a tabulated likelihood; a realisation of a table is not defined");
+    else if (!t->rs.binned)
         rc = gf_fail_msg(GF_ERR_UNSUPPORTED, "gf_toys_create_binned: the models carry no binned measurement; gf_toys_create seeds the flux-averaged Gaussian likelihood");
     t->nseed = nseed;
     for (int r = 0; r < nscales && rc == GF_OK; ++r) {

@@ -17,7 +17,7 @@ from .enums import ParamTag, Texture
 from .model import Model
 
 __all__ = ["LnProb", "CubeLnProb", "notebook_ln_prob", "tutorial_ln_prob", "bsm_ln_prob", "prior_ln_prob", "lnprior",
-           "ln_prob", "triangle_llh", "multi_gaussian", "BinnedMeasurement", "equal_information_smearing"]
+           "ln_prob", "triangle_llh", "multi_gaussian", "BinnedMeasurement", "equal_information_smearing", "TabulatedLikelihood"]
 
 
 def equal_information_smearing(smearing, binning):
@@ -87,6 +87,151 @@ class BinnedMeasurement:
         return "BinnedMeasurement(nbins=%d)" % self.nbins
 
 
+class TabulatedLikelihood:
+    """A likelihood surface over the flavour triangle: ln L at the (N + 1)(N + 2) / 2 nodes (i, j), 0 <= j <= N - i, of
+    the triangular lattice of side N -- node (i, j) is the composition (i, j, N - i - j) / N and lies at values[i (2N + 3 - i) / 2 + j].
+    Between the nodes ln L is linear in the triangle of the lattice that holds the composition.  `values`: the flat array, its length
+    fixes N.  Every value is finite or -inf and at least one is finite: else ValueError."""
+
+    def __init__(self, values):
+        v = np.array(values, dtype=np.float64)
+        if v.ndim != 1 or v.size < 3:
+            raise ValueError("values is the flat array of the (N + 1)(N + 2) / 2 node values of a table of side N >= 1")
+        n = (int(np.sqrt(8 * v.size + 1)) - 3) // 2
+        while (n + 1) * (n + 2) // 2 < v.size:
+            n += 1
+        if (n + 1) * (n + 2) // 2 != v.size:
+            raise ValueError("%d values are not (N + 1)(N + 2) / 2 for any side N" % v.size)
+        if n > _lib.GF_TABLE_MAX_NSIDE:
+            raise ValueError("side %d beyond the largest table side %d" % (n, _lib.GF_TABLE_MAX_NSIDE))
+        if np.any(np.isnan(v)) or np.any(v == np.inf):
+            raise ValueError("a node value is finite or -inf: NaN or +inf in the table")
+        if not np.any(np.isfinite(v)):
+            raise ValueError("every node of the table is -inf")
+        self.values = np.ascontiguousarray(v)
+        self.nside = n
+
+    @staticmethod
+    def node_count(nside):
+        return (int(nside) + 1) * (int(nside) + 2) // 2
+
+    @staticmethod
+    def node_index(nside, i, j):
+        """where node (i, j) of a table of side `nside` lies (arrays allowed)"""
+        i = np.asarray(i, dtype=np.int64)
+        return i * (2 * int(nside) + 3 - i) // 2 + np.asarray(j, dtype=np.int64)
+
+    @staticmethod
+    def node_ij(nside):
+        """(i, j) of every node in storage order: two int64 arrays"""
+        n = int(nside)
+        i = np.repeat(np.arange(n + 1), np.arange(n + 1, 0, -1))
+        j = np.concatenate([np.arange(n + 1 - k) for k in range(n + 1)])
+        return i.astype(np.int64), j.astype(np.int64)
+
+    def node_fr(self):
+        """the compositions of the nodes, [n][3] in storage order"""
+        i, j = self.node_ij(self.nside)
+        n = float(self.nside)
+        return np.stack([i / n, j / n, (self.nside - i - j) / n], axis=1)
+
+    @classmethod
+    def from_function(cls, f, nside):
+        """ln L = f(fr) at every node; f takes the [n][3] compositions of the nodes and returns [n] values"""
+        nside = int(nside)
+        if nside < 1 or nside > _lib.GF_TABLE_MAX_NSIDE:
+            raise ValueError("nside outside 1 .. %d" % _lib.GF_TABLE_MAX_NSIDE)
+        i, j = cls.node_ij(nside)
+        n = float(nside)
+        return cls(np.asarray(f(np.stack([i / n, j / n, (nside - i - j) / n], axis=1)), dtype=np.float64))
+
+    @classmethod
+    def from_gaussian(cls, bf, smearing, nside, offset=0.):
+        """the Gaussian around `bf` of width `smearing`, node by node with `multi_gaussian`'s arithmetic"""
+        return cls.from_function(lambda fr: multi_gaussian(fr, bf, smearing, offset=offset), nside)
+
+    @classmethod
+    def from_ternary(cls, d, scale):
+        """From the dictionary `plot.heatmap` draws (golemflavor/plot.py:216-228): {(i, j, k): value} with i + j + k = scale, i
+        counting fr_e and j fr_mu ((i, j) keys are taken too).  Every node of the lattice must be present."""
+        scale = int(scale)
+        if scale < 1 or scale > _lib.GF_TABLE_MAX_NSIDE:
+            raise ValueError("scale outside 1 .. %d" % _lib.GF_TABLE_MAX_NSIDE)
+        v = np.full(cls.node_count(scale), np.nan)
+        for key, val in d.items():
+            key = tuple(int(x) for x in key)
+            if len(key) not in (2, 3):
+                raise ValueError("a key is (i, j, k) or (i, j): %r" % (key,))
+            i, j = key[0], key[1]
+            if i < 0 or j < 0 or i + j > scale or (len(key) == 3 and key[2] != scale - i - j):
+                raise ValueError("key %r is no node of a lattice of scale %d" % (key, scale))
+            v[int(cls.node_index(scale, i, j))] = float(np.asarray(val, dtype=np.float64))
+        missing = int(np.count_nonzero(np.isnan(v)))
+        if missing:
+            raise ValueError("%d of the %d nodes are missing from the dictionary (or NaN)" % (missing, v.size))
+        return cls(v)
+
+    def to_ternary(self):
+        """the {(i, j, k): value} dictionary of the table"""
+        i, j = self.node_ij(self.nside)
+        return {(int(a), int(b), int(self.nside - a - b)): float(x) for a, b, x in zip(i, j, self.values)}
+
+    def save(self, path):
+        """the flat values as .npy"""
+        with open(path, "wb") as fh:
+            np.save(fh, self.values)
+
+    @classmethod
+    def load(cls, path):
+        return cls(np.load(path, allow_pickle=False))
+
+    def cell(self, fr):
+        """(i, j, fu, fv, up, nan) of every composition: the cell the lookup takes (csrc/gf_table.hpp `locate`)"""
+        fr = np.atleast_2d(np.asarray(fr, dtype=np.float64))
+        N = self.nside
+        n = float(N)
+        with np.errstate(invalid="ignore", over="ignore"):
+            u = fr[:, 0] * n
+            v = fr[:, 1] * n
+            nan = np.isnan(u) | np.isnan(v)
+            u = np.where(nan, 0.0, u)
+            v = np.where(nan, 0.0, v)
+            u = np.where(u < 0.0, 0.0, np.where(u > n, n, u))
+            vmax = n - u
+            v = np.where(v < 0.0, 0.0, np.where(v > vmax, vmax, v))
+            i = np.minimum(np.floor(u).astype(np.int64), N - 1)
+            j = np.minimum(np.floor(v).astype(np.int64), N - 1 - i)
+            fu = u - i
+            fv = v - j
+            up = (fu + fv <= 1.0) | (j == N - 1 - i)
+        return i, j, fu, fv, up, nan
+
+    def lnl(self, fr):
+        """ln L of the compositions fr (n, 3) (or (3,): a float): the definition restated in numpy, operation by operation in the
+        header's order, so that it is the device's value bit for bit"""
+        single = np.ndim(fr) == 1
+        i, j, fu, fv, up, nan = self.cell(fr)
+        N = self.nside
+        T = self.values
+        a00 = self.node_index(N, i, j)
+        a10 = a00 + (N + 1 - i)
+        # upward: (i, j), (i + 1, j), (i, j + 1); downward: (i + 1, j + 1), (i, j + 1), (i + 1, j) with 1 - fu, 1 - fv
+        ia = np.where(up, a00, a10 + 1)
+        ib = np.where(up, a10, a00 + 1)
+        ic = np.where(up, a00 + 1, a10)
+        ta, tb, tc = T[ia], T[ib], T[ic]
+        with np.errstate(invalid="ignore", over="ignore"):
+            gu = np.where(up, fu, 1.0 - fu)
+            gv = np.where(up, fv, 1.0 - fv)
+            out = (ta + gu * (tb - ta)) + gv * (tc - ta)
+        out = np.where(np.isneginf(ta) | np.isneginf(tb) | np.isneginf(tc), -np.inf, out)
+        out = np.where(nan, np.nan, out)
+        return float(out[0]) if single else out
+
+    def __repr__(self):
+        return "TabulatedLikelihood(nside=%d)" % self.nside
+
+
 class LnProb:
     vectorized = True          # tells golemflavor_amd.mcmc.EnsembleSampler to batch the ensemble
 
@@ -142,22 +287,29 @@ def tutorial_ln_prob(asimov_paramset, llh_paramset, device=0):
     return LnProb(desc, device=device)
 
 
-def bsm_ln_prob(args, asimov_paramset, llh_paramset, smearing=0.02, device=0, binned=None, **kw):
+def bsm_ln_prob(args, asimov_paramset, llh_paramset, smearing=0.02, device=0, binned=None, table=None, **kw):
     """golemflavor/llh.py:121-130 `ln_prob(theta, args, asimov_paramset, llh_paramset)` with the
     GolemFit likelihood replaced by the Gaussian substitute the README sanctions
     (README.md:70-74): multi_gaussian(measured, angles_to_fr(asimov BESTFIT angles), smearing).
     `args` needs: source_ratio, dimension, texture, binning (edges); `args.no_bsm` (fr.py:437-438) is honoured:
     the posterior is then lnprior + the Gaussian around u_to_fr(source_ratio, sm_u) (descriptor.compile_model).
     `binned` (a `BinnedMeasurement`): the posterior is the energy-resolved one, lnprior + the sum over the energy
-    bins of multi_gaussian(composition at the bin, m_k, sigma_k); the flux-averaged bestfit and `smearing` are then not read."""
+    bins of multi_gaussian(composition at the bin, m_k, sigma_k); the flux-averaged bestfit and `smearing` are then not read.
+    `table` (a `TabulatedLikelihood`): the posterior is lnprior + the table's value at the flux-averaged composition (DESIGN.md 6m);
+    not together with `binned`."""
+    if binned is not None and table is not None:
+        raise ValueError("binned and table are two likelihoods: give one")
     bf = fr_utils.angles_to_fr(asimov_paramset.from_tag(ParamTag.BESTFIT, values=True))
     desc = compile_model(llh_paramset, "BSM_GAUSS", bestfit_fr=bf, smearing=smearing,
                          source_ratio=args.source_ratio, texture=args.texture,
                          dimension=args.dimension, binning=args.binning, no_bsm=bool(getattr(args, "no_bsm", False)))
     f = LnProb(desc, device=device, **kw)
-    if binned is not None:
+    if binned is not None or table is not None:
         try:
-            f.model.set_binned_measurement(binned)
+            if binned is not None:
+                f.model.set_binned_measurement(binned)
+            else:
+                f.model.set_table_likelihood(table)
         except BaseException:
             f.close()
             raise

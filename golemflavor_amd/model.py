@@ -242,6 +242,30 @@ class Model:
         """True once a binned measurement is attached."""
         return int(self._L.gf_model_is_binned(self._h)) == 1
 
+    def set_table_likelihood(self, table):
+        """Attach a tabulated flavour-plane likelihood (`llh.TabulatedLikelihood`, or a flat array of node values): from now on every
+        lnprob of this model -- lnprob, lnprob_cube, lnprob_device, a nested run, a profile scan, a reweight target -- is lnprior + the
+        table's value at the flux-averaged composition; the model's offset is not added.  propagate, propagate_bins and
+        the status are unchanged.  It can be replaced, not removed.  A model of another mode or with a binned measurement, or a bad
+        table: GolemHipError (GF_ERR_UNSUPPORTED / GF_ERR_INVALID_ARG), the model unchanged.  The device ensemble sampler and the
+        realisation ensembles refuse such a model."""
+        v = np.ascontiguousarray(getattr(table, "values", table), dtype=np.float64)
+        if v.ndim != 1:
+            raise ValueError("a table is the flat array of its node values")
+        n = (int(np.sqrt(8 * v.size + 1)) - 3) // 2
+        while (n + 1) * (n + 2) // 2 < v.size:
+            n += 1
+        if n < 1 or (n + 1) * (n + 2) // 2 != v.size:
+            raise ValueError("%d values are not (N + 1)(N + 2) / 2 for any side N >= 1" % v.size)
+        check(self._L.gf_model_set_table_likelihood(self._h, n, v.ctypes.data_as(_lib._dp)), "gf_model_set_table_likelihood")
+        self.table = table
+        return self
+
+    @property
+    def table_nside(self):
+        """The side of the attached tabulated likelihood, 0 without one."""
+        return int(self._L.gf_model_table_nside(self._h))
+
     def propagate_bins(self, theta, want_status=True):
         """theta (n, ndim) -> the composition at every energy bin (n, nbins, 3) [, status (n,)]: the terms flux_averaged_BSMu
         (fr.py:441-457) averages, at the bin centres `spectrum.bin_tables(spectrum.model_edges(self))[0]`.  The status is

@@ -371,11 +371,14 @@ def _opt(args, name, default):
     return default if v is None else v
 
 
-def _scan_models(args, asimov_paramset, llh_paramset, scales, smearing, device, binned=None):
+def _scan_models(args, asimov_paramset, llh_paramset, scales, smearing, device, binned=None, table=None):
     """The per-scale set-up of sens.py's scans: the scanned columns are every column but the scale (sens.py:217-218), the scale
     column is fixed at each scale with its box lowered for the null point, one Model per scale.  Returns (cols, models, bases,
     labels); a model that cannot be built closes the ones before it.  `binned` (`llh.BinnedMeasurement`): attached to every scale's
-    model, whose lnprob is then the energy-resolved likelihood."""
+    model, whose lnprob is then the energy-resolved likelihood.  `table` (`llh.TabulatedLikelihood`): likewise, the
+    tabulated flavour-plane likelihood; not together with `binned`."""
+    if binned is not None and table is not None:
+        raise ValueError("binned and table are two likelihoods: give one")
     names = list(llh_paramset.names)
     scale_col = names.index(llh_paramset.from_tag(ParamTag.SCALE)[0].name)
     cols = [i for i in range(len(names)) if i != scale_col]
@@ -387,6 +390,8 @@ def _scan_models(args, asimov_paramset, llh_paramset, scales, smearing, device, 
             models.append(Model(_bsm_desc(args, asimov_paramset, ps, smearing), device=device))
             if binned is not None:
                 models[-1].set_binned_measurement(binned)
+            if table is not None:
+                models[-1].set_table_likelihood(table)
             bases.append(np.array(ps.values, dtype=np.float64))
     except BaseException:
         for m in models:
@@ -398,7 +403,7 @@ def _scan_models(args, asimov_paramset, llh_paramset, scales, smearing, device, 
 
 def evidence_scan(args, asimov_paramset, llh_paramset, scales, run_ids=None, nlive=None, tol=None, batch=None, walks=None,
                   seed=None, on_nonunitary="raise", smearing=None, device=0, max_iter=100000, return_sampler=False, posterior=None,
-                  binned=None):
+                  binned=None, table=None):
     """sens.py:231-303 for every scale at once: the scanned columns are every column but the scale (sens.py:217-218), the scale
     column is fixed at each scale (with its box lowered for the null point), one device call.  `args` as for bsm_ln_prob
     (source_ratio, dimension, texture, binning) plus the --mn-* options.  Returns dict(scales, lnz, lnz_err, max_lnl, niter,
@@ -406,10 +411,11 @@ def evidence_scan(args, asimov_paramset, llh_paramset, scales, run_ids=None, nli
     the result also carries "posterior" (`NestedSampler.posterior()`), "marginals" ([scale] MarginalResult over llh_paramset's
     columns) and, with elements, "marginals_elements"; spectrum=[percentiles] adds "spectrum" ([scale] `spectrum.SpectrumResult`); all
     computed before the sampler is closed.  binned (`llh.BinnedMeasurement`): the evidence of the energy-resolved likelihood
-     -- the measurement is attached to every scale's model."""
+     -- the measurement is attached to every scale's model.  table (`llh.TabulatedLikelihood`): the evidence of the
+    tabulated flavour-plane likelihood, attached to every scale's model."""
     import time
     scales = np.asarray(scales, dtype=np.float64)
-    cols, models, bases, labels = _scan_models(args, asimov_paramset, llh_paramset, scales, smearing, device, binned=binned)
+    cols, models, bases, labels = _scan_models(args, asimov_paramset, llh_paramset, scales, smearing, device, binned=binned, table=table)
     try:
         s = NestedSampler(models, cols, bases, nlive=int(nlive or _opt(args, "mn_live_points", DEFAULT_NLIVE)),
                           batch=batch if batch is not None else _opt(args, "mn_batch", None),

@@ -297,15 +297,15 @@ class SimplexMaximizer(_CubeRuns):
 
 def profile_scan(args, asimov_paramset, llh_paramset, scales, run_ids=None, nstarts=None, nseed=None, xatol=None, fatol=None,
                  maxiter=None, restarts=None, adaptive=None, seed=None, on_nonunitary="raise", smearing=None, device=0,
-                 return_maximizer=False, binned=None):
+                 return_maximizer=False, binned=None, table=None):
     """The profile likelihood at every scale in one device call, with evidence_scan's conventions: the scanned columns are every
     column but the scale (sens.py:217-218), the scale column is fixed at each scale with its box lowered for the null point.
     `args` as for evidence_scan plus the --pl-* options.  Returns dict(scales, max_lnl, argmax_theta, nstarts, nfev, nevals,
     niter, nonunitary, seconds, starts_agreeing: the starts whose final lnL is within AGREE_TOL of the run's best).
     binned (`llh.BinnedMeasurement`): the profile of the energy-resolved likelihood -- the measurement is attached to
-    every scale's model."""
+    every scale's model.  table (`llh.TabulatedLikelihood`): the profile of the tabulated flavour-plane likelihood."""
     scales = np.asarray(scales, dtype=np.float64)
-    cols, models, bases, labels = _scan_models(args, asimov_paramset, llh_paramset, scales, smearing, device, binned=binned)
+    cols, models, bases, labels = _scan_models(args, asimov_paramset, llh_paramset, scales, smearing, device, binned=binned, table=table)
 
     def pick(v, name, default):
         return v if v is not None else _opt(args, name, default)

@@ -28,7 +28,7 @@ from . import nested
 from . import profile_llh
 from . import realisations as realisations_mod
 from .enums import DataType, ParamTag, StatCateg, Texture
-from .llh import BinnedMeasurement
+from .llh import BinnedMeasurement, TabulatedLikelihood
 from .mcmc import chain_identifier
 
 
@@ -109,7 +109,16 @@ def parse_args(argv=None):
     ap.add_argument("--binned-smearing", type=float, nargs="+", default=None, metavar="S",
                     help="energy-resolved: ONE value is the width of the flux-averaged likelihood to be comparable with, "
                          "sigma_k = S / sqrt(w_k) (default: --smearing); K values are the widths of the bins themselves")
+    ap.add_argument("--likelihood-table", type=str, default=None, metavar="FILE.npy",
+                    help="a tabulated flavour-plane likelihood in place of the Gaussian: the flat array of ln L at the (N + 1)(N + 2) / 2 "
+                         "nodes of the flavour triangle's lattice (llh.TabulatedLikelihood.save); the output files carry _ltab")
     args = ap.parse_args(argv)
+    if args.likelihood_table is not None:
+        if args.energy_resolved or args.binned_measurement is not None or args.binned_smearing is not None:
+            ap.error("--likelihood-table replaces the flux-averaged likelihood: it does not combine with --energy-resolved")
+        if args.realisations is not None or args.evidence_realisations is not None:
+            ap.error("a realisation of a table is not defined: --likelihood-table does not combine with --realisations or "
+                     "--evidence-realisations")
     if args.binned_measurement is not None:
         args.energy_resolved = True
     if args.binned_smearing is not None:
@@ -165,7 +174,15 @@ def parse_args(argv=None):
 def identifier(args):
     """The reference's file-name stem (`chain_identifier`); `_ebins` appended for the energy-resolved likelihood, whose results never
     overwrite the flux-averaged ones."""
-    return chain_identifier(args) + ("_ebins" if getattr(args, "energy_resolved", False) else "")
+    return (chain_identifier(args) + ("_ebins" if getattr(args, "energy_resolved", False) else "")
+            + ("_ltab" if getattr(args, "likelihood_table", None) is not None else ""))
+
+
+def likelihood_table(args):
+    """The `TabulatedLikelihood` of --likelihood-table, None without it."""
+    if getattr(args, "likelihood_table", None) is None:
+        return None
+    return TabulatedLikelihood.load(args.likelihood_table)
 
 
 def binned_measurement(args, asimov_paramset):
@@ -251,11 +268,12 @@ def main(argv=None):
     asimov, llh_ps = Cf.sens_paramsets(args.dimension, args.injected_ratio, data=args.data)
     try:
         binned = binned_measurement(args, asimov)
-    except ValueError as exc:
+        table = likelihood_table(args)
+    except (ValueError, OSError) as exc:
         print("golemflavor_amd.sens: %s" % exc, file=sys.stderr)
         return 2
     if args.stat_method is StatCateg.FREQUENTIST:
-        return _frequentist(args, scales, idx, asimov, llh_ps, outfile, outfile_llh, binned)
+        return _frequentist(args, scales, idx, asimov, llh_ps, outfile, outfile_llh, binned, table)
     post = dict(nrows=args.posterior_rows, elements=args.posterior_elements) if args.posterior else None
     if post is not None and args.posterior_spectrum is not None:
         post["spectrum"] = args.posterior_spectrum
@@ -268,7 +286,7 @@ def main(argv=None):
         toys = _evidence_realisations(args, ens)
     else:
         res = nested.evidence_scan(args, asimov, llh_ps, scales[idx], run_ids=idx, on_nonunitary=args.on_nonunitary,
-                                   device=args.device, posterior=post, binned=binned)
+                                   device=args.device, posterior=post, binned=binned, **({"table": table} if table is not None else {}))
     evidence_arr = np.stack([scales[idx], res["lnz"]], axis=1)
     maxllh_arr = np.stack([scales[idx], res["max_lnl"]], axis=1)
     for f, arr in ((outfile, evidence_arr), (outfile_llh, maxllh_arr)):
@@ -281,6 +299,7 @@ def main(argv=None):
         **({"evidence_realisations": toys} if toys is not None else {}),
         **({"posterior": posterior_files} if posterior_files is not None else {}),
         **({"likelihood": "energy-resolved"} if binned is not None else {}),
+        **({"likelihood": "table", "table_nside": table.nside} if table is not None else {}),
         "tool": "golemflavor_amd.sens", "dimension": args.dimension, "texture": args.texture.name,
         "segments": args.segments, "nlive": args.mn_live_points, "scales": scales[idx].tolist(),
         "lnz": res["lnz"].tolist(), "lnz_err": res["lnz_err"].tolist(), "max_lnl": res["max_lnl"].tolist(),
@@ -334,9 +353,9 @@ def _realisations(args, scales, idx, asimov, llh_ps, binned=None):
             "without_limit": band["n_without_limit"], "ts_q95": crit.tolist(), "seconds": round(res["seconds"], 4)}
 
 
-def _frequentist(args, scales, idx, asimov, llh_ps, outfile, outfile_llh, binned=None):
+def _frequentist(args, scales, idx, asimov, llh_ps, outfile, outfile_llh, binned=None, table=None):
     res = profile_llh.profile_scan(args, asimov, llh_ps, scales[idx], run_ids=idx, on_nonunitary=args.on_nonunitary,
-                                   device=args.device, binned=binned)
+                                   device=args.device, binned=binned, **({"table": table} if table is not None else {}))
     arr = np.stack([scales[idx], res["max_lnl"]], axis=1)
     for f in (outfile, outfile_llh):
         os.makedirs(os.path.dirname(f) or ".", exist_ok=True)
@@ -349,6 +368,7 @@ def _frequentist(args, scales, idx, asimov, llh_ps, outfile, outfile_llh, binned
     print(json.dumps({
         **({"realisations": toys} if toys is not None else {}),
         **({"likelihood": "energy-resolved"} if binned is not None else {}),
+        **({"likelihood": "table", "table_nside": table.nside} if table is not None else {}),
         "tool": "golemflavor_amd.sens", "stat_method": "FREQUENTIST", "dimension": args.dimension,
         "texture": args.texture.name, "segments": args.segments, "scales": scales[idx].tolist(), "max_lnl": ml.tolist(),
         "ts": ts, "limit": None if limit is None else float(limit), "starts": res["nstarts"].tolist(),

@@ -695,6 +695,26 @@ int gf_nested_spectrum(gf_nested* s, int64_t nrows, const gf_spectrum_spec* spec
 int gf_model_set_binned_measurement(gf_model* m, int nbins, const double* fr_bins, const double* sigma);
 int gf_model_is_binned(const gf_model* m);   /* 1 with a binned measurement, 0 without, -1 for NULL */
 
+/* ---- the tabulated flavour-plane likelihood: bring your own likelihood surface (this package's own definition) -------- */
+/* A GF_MODE_BSM_GAUSS model takes ln L at the (nside + 1)(nside + 2) / 2 nodes (i, j), 0 <= j <= nside - i, of the flavour triangle's
+ * lattice -- node (i, j) is (fr_e, fr_mu) = (i, j) / nside and lies at values[i (2 nside + 3 - i) / 2 + j].  From then on every lnprob the
+ * model gives -- gf_lnprob_batch[_device], gf_lnprob_cube_batch, the nested sampler, the maximiser, a model target of gf_sampler_reweight*
+ * -- is lnprior + the table's value at the flux-averaged composition, linearly interpolated in the triangle of the lattice that holds it
+ * (csrc/gf_table.hpp holds the operations and their order); a triangle with a node at -inf gives -inf, a NaN composition NaN.  The
+ * model's offset is not added.  The status of a row, the composition, and the value of a row the reference would have raised on are those
+ * of the same model without the table (the mode stays GF_MODE_BSM_GAUSS, bestfit_fr and smearing stay in the model and are not read by
+ * lnprob).
+ * 1 <= nside <= GF_TABLE_MAX_NSIDE, every value finite or -inf and one of them finite: else GF_ERR_INVALID_ARG.  A model of another mode,
+ * or one with a binned measurement: GF_ERR_UNSUPPORTED (and gf_model_set_binned_measurement refuses a model with a table); either way
+ * the model is unchanged.  A table can be replaced (no launch of the model may be in flight on a stream other than its own; a nested
+ * sampler or maximiser created earlier keeps reading the table it was created with) but not removed.  Refused with GF_ERR_UNSUPPORTED:
+ * gf_sampler_create* (sampling a table in the ensemble sampler is out of scope: reweight a Gaussian chain to the model), and what sets
+ * or reweights to a Gaussian measurement -- gf_toys_create*, gf_toys_set_measurements, gf_toys_set_binned_measurements,
+ * gf_nested_toys_evidence.  Of the models of one nested sampler or maximiser all carry a table or none; the sides may differ. */
+#define GF_TABLE_MAX_NSIDE 2048
+int gf_model_set_table_likelihood(gf_model* m, int nside, const double* values);
+int gf_model_table_nside(const gf_model* m);   /* the table's side, 0 without one (and for NULL) */
+
 /* ---- every stored chain reweighted to other targets (csrc/gf_reweight.hpp holds the rules for lnw) ------------------- */
 /* Chain c's rows are its stored samples in the device's order, i = step * nwalkers + walker, n = nstored * nwalkers (NOT emcee's
  * walker-major flatchain; every index below refers to this order), l0_i their stored ln_prob.  Every chain has ntargets targets t.
