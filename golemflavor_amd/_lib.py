@@ -264,6 +264,7 @@ SIGNATURES = {
     "gf_model_set_table_likelihood": (C.c_int, [_vp, C.c_int, _dp]),
     "gf_model_table_nside": (C.c_int, [_vp]),
     "gf_sampler_create_binned": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_double, C.POINTER(_vp)]),
+    "gf_sampler_create_table": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_double, C.POINTER(_vp)]),
     "gf_toys_set_measurements": (C.c_int, [_vp, _dp, _dp]),
     "gf_toys_set_start_counts": (C.c_int, [_vp, _ip]),
     "gf_toys_create": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, _ip, _dp, C.c_int, C.c_uint64, C.POINTER(_vp)]),

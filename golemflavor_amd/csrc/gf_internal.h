@@ -80,6 +80,8 @@ struct GfChainView {              // the stored chain of a sampler, as post-proc
 int gf_internal_sampler_chain_view(const gf_sampler* s, GfChainView* v);
 // 1 for a sampler of the energy-resolved likelihood (gf_sampler_create_binned), else 0
 int gf_internal_sampler_binned(const gf_sampler* s);
+// 1 for a sampler of the tabulated flavour-plane likelihood (gf_sampler_create_table), else 0
+int gf_internal_sampler_table(const gf_sampler* s);
 // k_walker_mean on `stream`: chain [nchains][cap][nwalkers][ndim] -> mean [nchains][nstored][ndim], the ensemble mean of every step
 hipError_t gf_launch_walker_mean(const double* d_chain, int64_t cap, int64_t nstored, int nchains, int nwalkers, int ndim, double* d_mean,
                                  hipStream_t stream);

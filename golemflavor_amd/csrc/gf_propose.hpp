@@ -36,8 +36,10 @@ __device__ __forceinline__ void philox_block(uint32_t c0, uint32_t c1, uint32_t 
 // that the reference would have died on.
 // MODE_BSM_BINNED (a model with a measurement per energy bin; one lane per point only): the same body around
 // binned_llh<UNI_INLINE>, which reads the model's table from `btab` (LDS).  The other instances do not see it.
-// MODE_BSM_TABLE (a model with a tabulated flavour-plane likelihood; one lane per point only): the MODE_BSM_GAUSS body with
-// gf_table.hpp's lookup in place of gauss_llh; `btab` is then the model's table in global memory and `tside` its side.
+// MODE_BSM_TABLE (a model with a tabulated flavour-plane likelihood): the MODE_BSM_GAUSS body with gf_table.hpp's lookup
+// in place of gauss_llh; `btab` is then the model's table in global memory and `tside` its side.  The table is looked up at the
+// flux-averaged composition, so the instance splits a point's bins over LPW lanes as the flux-averaged one does: every lane of the
+// group holds the group's identical `fr` behind flux_average and makes the same lookup.
 template <int NDIM, int MODE, int LPW>
 __device__ __forceinline__ double proposal_lnprob(const GfCommon& c, const GfBsm* tb, const double* ctab,
                                                   const double* ttab, const double* row, int ndim, int& st, int sub,
@@ -47,7 +49,6 @@ __device__ __forceinline__ double proposal_lnprob(const GfCommon& c, const GfBsm
     pending = 0ull;
     double val, fr[3];
     if constexpr (MODE == MODE_BSM_TABLE) {
-        static_assert(LPW == 1, "the tabulated likelihood runs one lane per point");
         double lp;
         const bool inbox = lnprior_tab<NDIM>(ctab, row, ndim, c.prior_const, lp);
         asm volatile("" : "+v"(lp));       // keeps the prior sum ahead of the bin loop (see k_bsm, gf_bsm.hip)
@@ -55,7 +56,7 @@ __device__ __forceinline__ double proposal_lnprob(const GfCommon& c, const GfBsm
         st = ST_OUT_OF_PRIOR;
         if (inbox) {
             UniAcc acc = {0.0, 0.0, 0ull, 2.0};
-            flux_average<UNI_INLINE, 1>(c, tb, ttab, row, fr, acc, sub, fgrp);
+            flux_average<UNI_INLINE, LPW>(c, tb, ttab, row, fr, acc, sub, fgrp);
             st = (acc.clear_max < tb->uni_hi) ? ST_OK : ST_NON_UNITARY;       // tiers 1 and 2 (gf_bsm_device.hpp)
             pending = st == ST_OK ? uni_arbitration_mask(acc.amb, tb) : 0ull;
             val = lp + gftab::lookup(btab, tside, fr[0], fr[1]);

@@ -210,6 +210,9 @@ int rw_run(gf_sampler* s, const gf_reweight_spec* spec, const RwWant& want, cons
     if (!spec->models && gf_internal_sampler_binned(s))
         return gf_fail_msg(GF_ERR_UNSUPPORTED, "%s: the sampler's chains were sampled under the energy-resolved likelihood, which has no single "
                            "Gaussian measurement to replace; give model targets", who);
+    if (!spec->models && gf_internal_sampler_table(s))
+        return gf_fail_msg(GF_ERR_UNSUPPORTED, "%s: the sampler's chains were sampled under a tabulated likelihood, which has no Gaussian measurement "
+                           "to replace; give model targets", who);
     const int T = spec->ntargets, nd = v.ndim, nch = v.nchains;
     const int64_t n = v.nstored * v.nwalkers, N = want.N;
     const bool measured = !spec->models, moments = want.out && (want.out->mean || want.out->cov), prefix = N > 0;

@@ -69,6 +69,11 @@ struct StretchArgs {
     // a sampler of the energy-resolved likelihood (gf_sampler_create_binned): [nmodels] the models' binned measurements
     // (gf_consts.h: GF_BINNED_STRIDE x nbins doubles each), chain ch reads btabs[ch] (one model: btabs[0]); NULL for every other sampler
     const double* const* btabs;
+    // a sampler of the tabulated flavour-plane likelihood (gf_sampler_create_table): [nmodels] the models' tables in
+    // global memory and their sides, chain ch reads entry ch (one model: entry 0); NULL for every other sampler.  The arrays are the
+    // sampler's for good; gf_sampler_run rewrites their entries when a model's table was replaced.
+    const double* const* ttabs;
+    const int32_t* tsides;
 };
 
 // start positions the reference would have died on (fr.py:493-498, raised while emcee evaluates p0): -inf and counted, so
@@ -91,12 +96,14 @@ __global__ void k_tick(GfStepState* st, int nsteps)
 // bins (flux_average); everything else they compute redundantly and identically, lane `sub == 0` writes.
 // MODE_BSM_BINNED (one lane per walker): the block stages its chain's binned measurement `btab_g` in LDS beside ctab; everything
 // around the likelihood -- verdict tiers, parking, k_stretch_settle behind the half-step -- is the flux-averaged BSM instance's.
+// MODE_BSM_TABLE (LPW lanes per walker, as the flux-averaged instance): `btab_g` is the chain's table of side `tside` and stays in
+// global memory (up to 16.8 MB); both are block-uniform, so the lookup's addresses start from scalar registers.
 template <int NDIM, int MODE, int LPW>
 __device__ __forceinline__ void stretch_body(const GfCommon& c, const GfBsm* __restrict__ tb, const double* __restrict__ ptab,
                                              const StretchArgs& s, const int chain, const int k, const bool valid, const int sub,
-                                             const double* __restrict__ btab_g = nullptr)
+                                             const double* __restrict__ btab_g = nullptr, const int tside = 0)
 {
-    constexpr bool BSM = MODE == MODE_BSM_GAUSS || MODE == MODE_BSM_BINNED;
+    constexpr bool BSM = MODE == MODE_BSM_GAUSS || MODE == MODE_BSM_BINNED || MODE == MODE_BSM_TABLE;
     extern __shared__ __attribute__((aligned(16))) double fdyn[];    // LPW > 1: per lane group [nbins_max][3] + [LPW]
     double* fgrp = LPW > 1 ? fdyn + (threadIdx.x / LPW) * GF_FGRP_DOUBLES(s.nbins_max, LPW) : nullptr;
     constexpr int ND = NDIM ? NDIM : GF_MAX_DIM;
@@ -132,7 +139,9 @@ __device__ __forceinline__ void stretch_body(const GfCommon& c, const GfBsm* __r
     stretch_row<NDIM>(row, cj, sk, z, ndim);
     int st;
     unsigned long long pending;
-    const double lnq = proposal_lnprob<NDIM, MODE, LPW>(c, tb, ctab, ttab, row, ndim, st, sub, fgrp, pending, btab);
+    double lnq;
+    if constexpr (MODE == MODE_BSM_TABLE) lnq = proposal_lnprob<NDIM, MODE, LPW>(c, tb, ctab, ttab, row, ndim, st, sub, fgrp, pending, btab_g, tside);
+    else lnq = proposal_lnprob<NDIM, MODE, LPW>(c, tb, ctab, ttab, row, ndim, st, sub, fgrp, pending, btab);
     const int64_t wi = (int64_t)chain * s.nwalkers + w;
     const double lnk = s.lnp[wi];
     const double lhs = stretch_lhs(z, u3, ndim);
@@ -140,6 +149,7 @@ __device__ __forceinline__ void stretch_body(const GfCommon& c, const GfBsm* __r
         // undecided unitarity: park the proposal; k_stretch_settle completes this walker's half-step
         if (sub == 0) park_proposal<true>(s.pq, s.pend_rows, (int64_t)chain * nhalf + k, row, ndim, lnq, pending, lhs);
         if constexpr (MODE == MODE_BSM_BINNED) atomicAdd(s.flags + 2, 1u);      // census: proposals k_stretch_settle completed (gf_internal_sampler_parked)
+        if constexpr (MODE == MODE_BSM_TABLE) { if (sub == 0) atomicAdd(s.flags + 2, 1u); }      // (one count per lane group)
         return;
     }
     bool accept = lhs > lnk - lnq;                           // false for NaN and for lnq = -inf
@@ -187,6 +197,7 @@ __global__ __launch_bounds__(GF_BLOCK, GF_STRETCH_WAVES) void k_stretch(const Gf
     const int chain = valid ? (int)(g / nhalf) : 0;
     const int k = valid ? (int)(g - (int64_t)chain * nhalf) : 0;
     if constexpr (MODE == MODE_BSM_BINNED) stretch_body<NDIM, MODE, LPW>(c, tb, ptab, s, chain, k, valid, 0, s.btabs[0]);
+    else if constexpr (MODE == MODE_BSM_TABLE) stretch_body<NDIM, MODE, LPW>(c, tb, ptab, s, chain, k, valid, (int)(t % LPW), s.ttabs[0], s.tsides[0]);
     else stretch_body<NDIM, MODE, LPW>(c, tb, ptab, s, chain, k, valid, (int)(t % LPW));
 }
 
@@ -200,6 +211,9 @@ __global__ __launch_bounds__(GF_BLOCK, GF_STRETCH_WAVES) void k_stretch_multi(co
     const int k = t / LPW;
     if constexpr (MODE == MODE_BSM_BINNED)
         stretch_body<NDIM, MODE, LPW>(s.commons[chain], s.tbs[chain], s.ptabs[chain], s, chain, k, k < s.nwalkers / 2, 0, s.btabs[chain]);
+    else if constexpr (MODE == MODE_BSM_TABLE)
+        stretch_body<NDIM, MODE, LPW>(s.commons[chain], s.tbs[chain], s.ptabs[chain], s, chain, k, k < s.nwalkers / 2, t % LPW, s.ttabs[chain],
+                                      s.tsides[chain]);
     else stretch_body<NDIM, MODE, LPW>(s.commons[chain], s.tbs[chain], s.ptabs[chain], s, chain, k, k < s.nwalkers / 2, t % LPW);
 }
 
@@ -794,8 +808,26 @@ hipError_t launch_stretch_n(const GfCommon& c, const GfBsm* tb, const double* pt
     }
 }
 
+// the tabulated likelihood: the flux-averaged instance's lane counts
+template <int NDIM>
+hipError_t launch_stretch_table(const GfCommon& c, const GfBsm* tb, const double* ptab, const StretchArgs& a, hipStream_t st)
+{
+    switch (a.lpw) {
+    case 2: return launch_stretch_nml<NDIM, MODE_BSM_TABLE, 2>(c, tb, ptab, a, st);
+    case 4: return launch_stretch_nml<NDIM, MODE_BSM_TABLE, 4>(c, tb, ptab, a, st);
+    case 16: return launch_stretch_nml<NDIM, MODE_BSM_TABLE, 16>(c, tb, ptab, a, st);
+    default: return launch_stretch_nml<NDIM, MODE_BSM_TABLE, 1>(c, tb, ptab, a, st);
+    }
+}
+
 hipError_t launch_stretch(const GfCommon& c, const GfBsm* tb, const double* ptab, const StretchArgs& a, hipStream_t st)
 {
+    if (a.ttabs)                            // the tabulated likelihood: the row widths of the BSM posteriors, then the lanes per walker
+        switch (c.ndim) {
+        case 7: return launch_stretch_table<7>(c, tb, ptab, a, st);
+        case 12: return launch_stretch_table<12>(c, tb, ptab, a, st);
+        default: return launch_stretch_table<0>(c, tb, ptab, a, st);
+        }
     if (a.btabs)                            // the energy-resolved likelihood: one lane per walker, the row widths of the BSM posteriors
         switch (c.ndim) {
         case 7: return launch_stretch_nml<7, MODE_BSM_BINNED, 1>(c, tb, ptab, a, st);
@@ -827,6 +859,13 @@ struct gf_sampler {
     const GfBsm** d_tbs = nullptr;
     const double** d_ptabs = nullptr;
     const double** d_btabs = nullptr;   // gf_sampler_create_binned: the models' binned measurements (device), [nchains] or [1]; else null
+    // gf_sampler_create_table: the models' tabulated likelihoods (device), [nchains] or [1], else null; h_ttabs / h_tsides are what the
+    // device arrays hold (members: they outlive the asynchronous upload), compared with the models at the start of every run
+    const double** d_ttabs = nullptr;
+    int32_t* d_tsides = nullptr;
+    const double** h_ttabs = nullptr;
+    int32_t* h_tsides = nullptr;
+    int last_lpw = 0;                   // lanes per walker of the last run's grid kernels, 0 before the first (gf_internal_sampler_lpw)
     int nchains = 0, nwalkers = 0, ndim = 0;
     int cus = 256, nbins_max = 0;
     uint64_t seed = 0, iteration = 0;
@@ -890,8 +929,10 @@ double g_last_run_prologue[4] = {};             // the last gf_sampler_run: [0] 
 namespace {
 // gf_sampler_create (multi false: every chain samples models[0]) and gf_sampler_create_multi (multi true: chain ch samples
 // models[ch]): the constant tables are allocated once, with one entry per model.  binned (gf_sampler_create_binned): every model
-// carries a binned measurement and the sampler evaluates the energy-resolved likelihood; else none may.
-int sampler_create(gf_model* const* models, bool multi, int nchains, int nwalkers, uint64_t seed, double a, gf_sampler** out, bool binned = false)
+// carries a binned measurement and the sampler evaluates the energy-resolved likelihood; else none may.  table
+// (gf_sampler_create_table): every model carries a tabulated likelihood and the sampler evaluates that one; else none may.
+int sampler_create(gf_model* const* models, bool multi, int nchains, int nwalkers, uint64_t seed, double a, gf_sampler** out, bool binned = false,
+                   bool table = false)
 {
     if (!out || nchains < 1 || nwalkers < 2 || (nwalkers & 1) || !(a > 1.0)) return GF_ERR_INVALID_ARG;
     *out = nullptr;
@@ -904,7 +945,9 @@ int sampler_create(gf_model* const* models, bool multi, int nchains, int nwalker
     std::unique_ptr<const double*[]> hpt(new (std::nothrow) const double*[nmodels]);
     std::unique_ptr<gf_model*[]> keep(multi ? new (std::nothrow) gf_model*[nmodels] : nullptr);
     std::unique_ptr<const double*[]> hbt(binned ? new (std::nothrow) const double*[nmodels] : nullptr);
-    if (!hc || !htb || !hpt || (multi && !keep) || (binned && !hbt)) return GF_ERR_ALLOC;
+    std::unique_ptr<const double*[]> htt(table ? new (std::nothrow) const double*[nmodels] : nullptr);
+    std::unique_ptr<int32_t[]> hts(table ? new (std::nothrow) int32_t[nmodels] : nullptr);
+    if (!hc || !htb || !hpt || (multi && !keep) || (binned && !hbt) || (table && (!htt || !hts))) return GF_ERR_ALLOC;
     int cus0 = 256, nbins_max = 0;
     for (int ch = 0; ch < nmodels; ++ch) {
         const GfCommon* cm; int dev, cus, nbins;
@@ -912,14 +955,19 @@ int sampler_create(gf_model* const* models, bool multi, int nchains, int nwalker
             cm->ndim != c->ndim || cm->mode != c->mode)
             return gf_fail_msg(GF_ERR_INVALID_ARG, "gf_sampler_create_multi: model %d differs from model 0 in device, ndim or mode", ch);
         // the stretch kernels evaluate the flux-averaged likelihood: never silently for a model whose lnprob is another
-        if (gf_model_table(models[ch], nullptr) > 0)
+        if (table) {
+            // pointer and side are the model's of now: gf_sampler_run takes them again at the start of every run
+            hts[ch] = gf_model_table(models[ch], &htt[ch]);
+            if (hts[ch] <= 0)
+                return gf_fail_msg(GF_ERR_INVALID_ARG, "gf_sampler_create_table: model %d carries no tabulated likelihood; all of a sampler's models must", ch);
+        } else if (gf_model_table(models[ch], nullptr) > 0)
             return gf_fail_msg(GF_ERR_UNSUPPORTED, "gf_sampler_create: model %d carries a tabulated likelihood; sample the flux-averaged model and reweight "
                                "the chain to this one", ch);
         if (binned) {
             // the table's address is the model's for good: a measurement set later lands in the same table
             if (!gf_model_binned(models[ch], &hbt[ch]))
                 return gf_fail_msg(GF_ERR_INVALID_ARG, "gf_sampler_create_binned: model %d carries no binned measurement; all of a sampler's models must", ch);
-        } else if (gf_model_binned(models[ch], nullptr))
+        } else if (!table && gf_model_binned(models[ch], nullptr))       // (a model that carries a table carries no binned measurement)
             return gf_fail_msg(GF_ERR_UNSUPPORTED, "gf_sampler_create: model %d carries a binned measurement; sample the flux-averaged model and reweight "
                                "the chain to this one", ch);
         hc[ch] = *cm;
@@ -955,14 +1003,40 @@ int sampler_create(gf_model* const* models, bool multi, int nchains, int nwalker
     if (e == hipSuccess) e = hipMemcpyAsync((void*)s->d_ptabs, hpt.get(), sizeof(void*) * nm, hipMemcpyHostToDevice, st0);
     if (e == hipSuccess && binned) e = hipMalloc((void**)&s->d_btabs, sizeof(void*) * nm);
     if (e == hipSuccess && binned) e = hipMemcpyAsync((void*)s->d_btabs, hbt.get(), sizeof(void*) * nm, hipMemcpyHostToDevice, st0);
-    if (binned) s->shape = 2;                                         // one launch shape: the per-half-step grid kernels
+    if (e == hipSuccess && table) e = hipMalloc((void**)&s->d_ttabs, sizeof(void*) * nm);
+    if (e == hipSuccess && table) e = hipMalloc((void**)&s->d_tsides, sizeof(int32_t) * nm);
+    if (e == hipSuccess && table) e = hipMemcpyAsync((void*)s->d_ttabs, htt.get(), sizeof(void*) * nm, hipMemcpyHostToDevice, st0);
+    if (e == hipSuccess && table) e = hipMemcpyAsync(s->d_tsides, hts.get(), sizeof(int32_t) * nm, hipMemcpyHostToDevice, st0);
+    if (binned || table) s->shape = 2;                                // one launch shape: the per-half-step grid kernels
     if (e == hipSuccess) e = hipStreamSynchronize(st0);               // the host tables are freed on return
     if (e != hipSuccess) {
-        const int rc = gf_hip_fail(e, binned ? "gf_sampler_create_binned" : multi ? "gf_sampler_create_multi" : "gf_sampler_create");
+        const int rc = gf_hip_fail(e, table ? "gf_sampler_create_table" : binned ? "gf_sampler_create_binned" : multi ? "gf_sampler_create_multi" : "gf_sampler_create");
         gf_sampler_destroy(s);
         return rc;
     }
+    s->h_ttabs = htt.release(); s->h_tsides = hts.release();
     *out = s;
+    return GF_OK;
+}
+
+// A table sampler's device arrays follow its models: a table set on a model since the arrays were written (gf_model_set_table_likelihood
+// moves the table when it grows, and may change its side) is uploaded on the sampler's stream, ahead of the run's first kernel.  The
+// arrays' own addresses never change, so a captured graph stays valid; an outgrown table is retired by its model, not freed.  Called
+// with the stream idle.
+int refresh_tables(gf_sampler* s)
+{
+    if (!s->d_ttabs) return GF_OK;
+    const int nm = s->models ? s->nchains : 1;
+    bool changed = false;
+    for (int ch = 0; ch < nm; ++ch) {
+        const double* d = nullptr;
+        const int side = gf_model_table(s->models ? s->models[ch] : s->model, &d);
+        if (side <= 0) return gf_fail_msg(GF_ERR_INVALID_ARG, "gf_sampler_run: model %d no longer carries a tabulated likelihood", ch);
+        if (d != s->h_ttabs[ch] || side != s->h_tsides[ch]) { s->h_ttabs[ch] = d; s->h_tsides[ch] = side; changed = true; }
+    }
+    if (!changed) return GF_OK;
+    GF_HIP(hipMemcpyAsync((void*)s->d_ttabs, s->h_ttabs, sizeof(void*) * (size_t)nm, hipMemcpyHostToDevice, s->stream));
+    GF_HIP(hipMemcpyAsync(s->d_tsides, s->h_tsides, sizeof(int32_t) * (size_t)nm, hipMemcpyHostToDevice, s->stream));
     return GF_OK;
 }
 
@@ -1118,6 +1192,7 @@ GridSteps grid_steps(gf_sampler* s, int store, int lpw)
     a.nbins_max = s->nbins_max;
     a.stream_ids = s->d_stream_ids;
     a.btabs = s->d_btabs;
+    a.ttabs = s->d_ttabs; a.tsides = s->d_tsides;
     a.lpw = lpw;
     GfSettleArgs& sa = g.sa;
     sa = {};
@@ -1387,12 +1462,24 @@ int gf_sampler_create_binned(gf_model* const* models, int nmodels, int nchains, 
     return sampler_create(models, nmodels == nchains && nchains > 1, nchains, nwalkers, seed, a, out, true);
 }
 
+// A sampler of the tabulated flavour-plane likelihood: every model carries a table (gf_model_set_table_likelihood).
+// nmodels == 1: every chain samples models[0]; nmodels == nchains: chain ch samples models[ch], as gf_sampler_create_multi; the sides
+// may differ from chain to chain.  The sampler keeps its models and takes each one's table again at the start of every run.
+int gf_sampler_create_table(gf_model* const* models, int nmodels, int nchains, int nwalkers, uint64_t seed, double a, gf_sampler** out)
+{
+    if (!models || !out || nchains < 1 || nchains > 65535 || (nmodels != 1 && nmodels != nchains)) return GF_ERR_INVALID_ARG;
+    *out = nullptr;
+    for (int ch = 0; ch < nmodels; ++ch)
+        if (!models[ch]) return GF_ERR_INVALID_ARG;
+    return sampler_create(models, nmodels == nchains && nchains > 1, nchains, nwalkers, seed, a, out, false, true);
+}
+
 // diagnostics (not part of the ABI): proposals since the last reset that the half-step kernel parked and k_stretch_settle completed;
-// counted by the energy-resolved instance alone, GF_ERR_UNSUPPORTED for every other sampler
+// counted by the energy-resolved and the tabulated instances alone, GF_ERR_UNSUPPORTED for every other sampler
 int gf_internal_sampler_parked(gf_sampler* s, uint32_t* out)
 {
     if (!s || !out) return GF_ERR_INVALID_ARG;
-    if (!s->d_btabs) return GF_ERR_UNSUPPORTED;
+    if (!s->d_btabs && !s->d_ttabs) return GF_ERR_UNSUPPORTED;
     GF_HIP(hipSetDevice(s->device));
     GF_HIP(hipMemcpyAsync(out, s->d_flags + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
     GF_HIP(hipStreamSynchronize(s->stream));
@@ -1401,6 +1488,10 @@ int gf_internal_sampler_parked(gf_sampler* s, uint32_t* out)
 
 // internal (gf_reweight.hip): 1 for a sampler of the energy-resolved likelihood, whose chains have no single Gaussian measurement
 int gf_internal_sampler_binned(const gf_sampler* s) { return s && s->d_btabs ? 1 : 0; }
+// ... and 1 for a sampler of the tabulated likelihood, whose chains have no Gaussian measurement at all
+int gf_internal_sampler_table(const gf_sampler* s) { return s && s->d_ttabs ? 1 : 0; }
+// diagnostics: lanes per walker of the last run's grid kernels (0: no run yet, or the run took another launch shape)
+int gf_internal_sampler_lpw(const gf_sampler* s) { return s ? s->last_lpw : 0; }
 
 void gf_sampler_destroy(gf_sampler* s)
 {
@@ -1429,6 +1520,10 @@ void gf_sampler_destroy(gf_sampler* s)
     if (s->d_tbs) (void)hipFree((void*)s->d_tbs);
     if (s->d_ptabs) (void)hipFree((void*)s->d_ptabs);
     if (s->d_btabs) (void)hipFree((void*)s->d_btabs);
+    if (s->d_ttabs) (void)hipFree((void*)s->d_ttabs);
+    if (s->d_tsides) (void)hipFree(s->d_tsides);
+    delete[] s->h_ttabs;
+    delete[] s->h_tsides;
     delete[] s->models;
     delete s;
 }
@@ -1514,11 +1609,16 @@ int gf_sampler_run(gf_sampler* s, int64_t nsteps, int thin, int store)
     GF_HIP(hipStreamSynchronize(st));          // earlier runs must be done with the counters
     s->flight_enq = s->flight_done = 0;         // (so nothing of an earlier run is in flight either)
     GF_HIP(hipMemcpyAsync(s->d_state, &hs, sizeof(hs), hipMemcpyHostToDevice, st));
+    {
+        const int rc = refresh_tables(s);       // a table sampler: the models' tables of now
+        if (rc != GF_OK) return rc;
+    }
 
     // the launch shape; the overrides are read in this order, once per run
     Run r = {s, nsteps, thin, store ? 1 : 0, 0};
-    // (a sampler of the energy-resolved likelihood has one shape, the grid kernels at one lane per walker: no override is read for it)
-    const bool binned = s->d_btabs != nullptr;
+    // (a sampler of the energy-resolved likelihood has one shape, the grid kernels at one lane per walker: no override is read for it;
+    // a sampler of the tabulated likelihood has the grid kernels too, at the lanes per walker the flux-averaged rule gives)
+    const bool binned = s->d_btabs != nullptr, table = s->d_ttabs != nullptr;
     GridSteps g = grid_steps(s, r.store, binned ? 1 : lanes_per_walker(s->c->mode, (int64_t)s->nchains * (s->nwalkers / 2), s->nbins_max, s->cus,
                                                                         {true, 48 * 1024, "GF_SAMPLER_LPW"}));
     int threads = 0, workers = 0;
@@ -1531,7 +1631,8 @@ int gf_sampler_run(gf_sampler* s, int64_t nsteps, int thin, int store)
         rc = run_persistent(r, threads, lds, workers);
     } else {
         bool grid = true;
-        if (bsm && !binned && s->nwalkers / 2 <= 512) rc = run_per_chain(r, g, &grid);
+        if (bsm && !binned && !table && s->nwalkers / 2 <= 512) rc = run_per_chain(r, g, &grid);
+        s->last_lpw = grid ? g.a.lpw : 0;
         if (rc == GF_OK && grid) rc = run_grid(r, g);
     }
     if (rc != GF_OK) return rc;

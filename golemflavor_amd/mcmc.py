@@ -202,9 +202,17 @@ class DeviceEnsembleSampler(rowsets.RowSetSource):
     `Model.lnprob` of the stored sample.  ValueError if a posterior carries none.  Without it such a posterior is refused (the
     library's GF_ERR_UNSUPPORTED).  Everything that reads the chain works as for any sampler; `reweight` takes model targets only.
     A measurement set on a model between two runs is the one the next run samples.
+
+    tabulated=True: every posterior carries a tabulated flavour-plane likelihood (`Model.set_table_likelihood`) and the
+    sampler evaluates that one (`gf_sampler_create_table`): the stored lnprob is bit for bit `Model.lnprob` of the stored sample.
+    ValueError if a posterior carries none, or together with energy_resolved=True.  Without it such a posterior is refused
+    (GF_ERR_UNSUPPORTED).  Everything that reads the chain works as for any sampler; `reweight` takes model targets only.  A table
+    set on a model between two runs, of any side, is the one the next run samples; the walkers keep the lnprob they hold (the old
+    table's) until they move -- pass the positions to `run_mcmc` again to have them evaluated under the new table.
     """
 
-    def __init__(self, nwalkers, dim, lnpostfn, a=2.0, nchains=1, seed=0, threads=1, stream_ids=None, energy_resolved=False):
+    def __init__(self, nwalkers, dim, lnpostfn, a=2.0, nchains=1, seed=0, threads=1, stream_ids=None, energy_resolved=False,
+                 tabulated=False):
         import ctypes as C
         from . import _lib
         multi = isinstance(lnpostfn, (list, tuple))
@@ -221,12 +229,19 @@ class DeviceEnsembleSampler(rowsets.RowSetSource):
                 raise TypeError("DeviceEnsembleSampler needs a golemflavor_amd LnProb / Model")
             if model.ndim != dim:
                 raise AssertionError("dim %d does not match the model's %d parameters" % (dim, model.ndim))
-        self.energy_resolved = bool(energy_resolved)
+        self.energy_resolved, self.tabulated = bool(energy_resolved), bool(tabulated)
+        if self.energy_resolved and self.tabulated:
+            raise ValueError("tabulated=True and energy_resolved=True: a posterior carries a table or a binned measurement, not both")
         if self.energy_resolved:
             for k, model in enumerate(models):
                 if getattr(model, "binned", None) is None:
                     raise ValueError("energy_resolved=True, but posterior %d carries no binned measurement "
                                      "(Model.set_binned_measurement)" % k)
+        if self.tabulated:
+            for k, model in enumerate(models):
+                if not getattr(model, "table_nside", 0):
+                    raise ValueError("tabulated=True, but posterior %d carries no tabulated likelihood "
+                                     "(Model.set_table_likelihood)" % k)
         model, lnpostfn = models[0], fns[0]
         if nwalkers % 2:
             raise AssertionError("The number of walkers must be even.")
@@ -242,6 +257,10 @@ class DeviceEnsembleSampler(rowsets.RowSetSource):
             nmodels = self.nchains if multi else 1
             _lib.check(self._L.gf_sampler_create_binned(rowsets.model_handles(models, nmodels), nmodels, self.nchains, self.k, int(seed),
                                                         self.a, C.byref(h)), "gf_sampler_create_binned")
+        elif self.tabulated:
+            nmodels = self.nchains if multi else 1
+            _lib.check(self._L.gf_sampler_create_table(rowsets.model_handles(models, nmodels), nmodels, self.nchains, self.k, int(seed),
+                                                       self.a, C.byref(h)), "gf_sampler_create_table")
         elif multi:
             _lib.check(self._L.gf_sampler_create_multi(rowsets.model_handles(models, self.nchains), self.nchains, self.k, int(seed),
                                                        self.a, C.byref(h)), "gf_sampler_create_multi")
@@ -390,7 +409,7 @@ class DeviceEnsembleSampler(rowsets.RowSetSource):
     @property
     def parked_proposals(self):
         """Diagnostics: proposals since the last reset whose unitarity verdict the half-step kernel could not settle and
-        k_stretch_settle completed.  Counted by an energy-resolved sampler; None for any other."""
+        k_stretch_settle completed.  Counted by an energy-resolved and by a tabulated sampler; None for any other."""
         fn = getattr(self._L, "gf_internal_sampler_parked", None)
         if fn is None:
             return None
@@ -401,7 +420,9 @@ class DeviceEnsembleSampler(rowsets.RowSetSource):
     def launch_shape(self):
         """Diagnostics: how a BSM sampler on small ensembles launches its steps -- {"shape": "per chain" | "grid" | "undecided",
         "probe_us_per_16_steps": {"per chain": .., "grid": ..}} -- decided at the start of every run of 128 steps or more by timing a block of
-        each on its own chains (gf_sampler_run); GF_SAMPLER_CHAIN=1 / 0 forces one.  The chain is the same bit for bit either way."""
+        each on its own chains (gf_sampler_run); GF_SAMPLER_CHAIN=1 / 0 forces one.  The chain is the same bit for bit either way.
+        "lanes_per_walker": the lanes that split a walker's energy bins in the last run's grid kernels (0: no run yet, or the run took
+        another shape); an energy-resolved or tabulated sampler has the grid shape alone."""
         fn = getattr(self._L, "gf_internal_sampler_shape", None)
         if fn is None:
             return None
@@ -409,7 +430,12 @@ class DeviceEnsembleSampler(rowsets.RowSetSource):
         fn.restype, fn.argtypes = self._C.c_int, [self._C.c_void_p, self._C.POINTER(self._C.c_double)]
         if fn(self._h, out) != 0:
             return None
-        return {"shape": ("undecided", "per chain", "grid")[int(out[0])], "probe_us_per_16_steps": {"per chain": float(out[1]), "grid": float(out[2])}}
+        shape = {"shape": ("undecided", "per chain", "grid")[int(out[0])], "probe_us_per_16_steps": {"per chain": float(out[1]), "grid": float(out[2])}}
+        lpw = getattr(self._L, "gf_internal_sampler_lpw", None)
+        if lpw is not None:
+            lpw.restype, lpw.argtypes = self._C.c_int, [self._C.c_void_p]
+            shape["lanes_per_walker"] = int(lpw(self._h))
+        return shape
 
     def run_to_host_times(self):
         """Diagnostics: where the host thread's time went in the process's last `run_mcmc_to_host` -- seconds issuing the blocks'
@@ -687,7 +713,7 @@ def element_marginals_file(outfile):
 
 
 def mcmc(p0, ln_prob, ndim, nwalkers, burnin, nsteps, threads=1, device_resident=None, seed=None, plot_elements=False,
-         llh_paramset=None, outfile=None, energy_resolved=False):
+         llh_paramset=None, outfile=None, energy_resolved=False, tabulated=False):
     """Run the MCMC: burn-in, reset, production; returns samples reshaped to (-1, ndim).
 
     Same signature, prints and return as golemflavor/mcmc.py:27-53.  When `ln_prob` is a
@@ -697,7 +723,8 @@ def mcmc(p0, ln_prob, ndim, nwalkers, burnin, nsteps, threads=1, device_resident
     what any plain Python callable gets.  `seed` keys the device sampler's Philox stream (default:
     drawn from numpy's global RNG, so `np.random.seed(args.seed)` makes runs reproducible as in the
     reference's scripts).  energy_resolved: `DeviceEnsembleSampler`'s keyword, for a device-resident run of a posterior with a
-    measurement per energy bin (the host-driven sampler evaluates `ln_prob` itself and takes any).
+    measurement per energy bin (the host-driven sampler evaluates `ln_prob` itself and takes any).  tabulated: likewise, for a
+    posterior with a tabulated flavour-plane likelihood.
 
     plot_elements (args.plot_elements) with llh_paramset and outfile: where the device-resident sampler ran, the marginals of the
     chain in element space (`DeviceEnsembleSampler.marginals(space="elements")`, the numbers behind the triangle plot.chainer_plot
@@ -709,7 +736,7 @@ def mcmc(p0, ln_prob, ndim, nwalkers, burnin, nsteps, threads=1, device_resident
     if seed is None:
         seed = int(np.random.randint(0, 2 ** 31 - 1))
     if device_resident:
-        sampler = DeviceEnsembleSampler(nwalkers, ndim, ln_prob, seed=seed, energy_resolved=energy_resolved)
+        sampler = DeviceEnsembleSampler(nwalkers, ndim, ln_prob, seed=seed, energy_resolved=energy_resolved, tabulated=tabulated)
     else:
         # (emcee seeds its RandomState from the OS; keyed by the global RNG instead, a host-driven run is as reproducible
         # under np.random.seed as a device-resident one)

@@ -247,8 +247,8 @@ class Model:
         lnprob of this model -- lnprob, lnprob_cube, lnprob_device, a nested run, a profile scan, a reweight target -- is lnprior + the
         table's value at the flux-averaged composition; the model's offset is not added.  propagate, propagate_bins and
         the status are unchanged.  It can be replaced, not removed.  A model of another mode or with a binned measurement, or a bad
-        table: GolemHipError (GF_ERR_UNSUPPORTED / GF_ERR_INVALID_ARG), the model unchanged.  The device ensemble sampler and the
-        realisation ensembles refuse such a model."""
+        table: GolemHipError (GF_ERR_UNSUPPORTED / GF_ERR_INVALID_ARG), the model unchanged.  The device ensemble sampler takes such a model with
+        `tabulated=True` alone; the realisation ensembles refuse it."""
         v = np.ascontiguousarray(getattr(table, "values", table), dtype=np.float64)
         if v.ndim != 1:
             raise ValueError("a table is the flat array of its node values")

@@ -15,7 +15,10 @@ RANK / WORLD_SIZE / LOCAL_RANK / MASTER_ADDR / MASTER_PORT works, torch.distribu
     python -m golemflavor_amd.scan --config C4 [--nwalkers 2048 --burnin 100 --nsteps 200]
     python -m torch.distributed.run --nproc-per-node 8 ... -m golemflavor_amd.scan --config C5
     python -m golemflavor_amd.scan --config C5 --energy-resolved [--binned-measurement FILE.npy] [--binned-smearing S ...]
+    python -m golemflavor_amd.scan --config C5 --likelihood-table FILE.npy
 
+--likelihood-table samples every C5 grid point under a tabulated flavour-plane likelihood (`llh.TabulatedLikelihood.save`
+writes the file): the chain files and every writer's files carry `_ltab` behind the point's stem.
 --energy-resolved samples every C5 grid point under the energy-resolved Gaussian likelihood (sens.py's flags, with
 their meanings): the chain files and every writer's files carry `_ebins` behind the point's stem.
 
@@ -143,13 +146,19 @@ class _SensPoint:
     """One grid point of the 12-dim posterior (scripts/fr.py:62-104 paramset, llh.py:121-130 with the
     Gaussian substitute): logLam seeded around the point's scale; result: the flat chain (.., 12)."""
 
-    def __init__(self, point, g, *, nwalkers, device, seed=25, smearing=0.02, binned=None):
+    def __init__(self, point, g, *, nwalkers, device, seed=25, smearing=0.02, binned=None, table=None):
         dim, tex, source, scale = point
         ps, box, desc = self.descriptor(point, smearing)
         self.f = llh_utils.LnProb(desc, device=device, on_nonunitary="-inf")
         if binned is not None:                                # --energy-resolved: a measurement per energy bin (DESIGN.md 6i)
             try:
                 self.f.model.set_binned_measurement(binned)
+            except BaseException:
+                self.f.close()
+                raise
+        if table is not None:                                 # --likelihood-table: a tabulated flavour-plane likelihood (DESIGN.md 6m)
+            try:
+                self.f.model.set_table_likelihood(table)
             except BaseException:
                 self.f.close()
                 raise
@@ -544,7 +553,8 @@ def _post_models(jobs, order):
     return [jobs[g].post_model for g in order] if getattr(first, "post_model", None) is not None else None
 
 
-def run_points(points, indices, make, burnin, nsteps, stacked=True, seed=25, gather=None, writers=(), energy_resolved=False):
+def run_points(points, indices, make, burnin, nsteps, stacked=True, seed=25, gather=None, writers=(), energy_resolved=False,
+               tabulated=False):
     """All of this rank's grid points advance together.  stacked (default): one sampler, one ensemble per
     grid point's posterior, every half-step of every chain in one launch; chain g draws from random stream g (its
     GLOBAL grid index), so that a grid point's chain does not depend on the number of ranks.  Otherwise one sampler per
@@ -556,7 +566,9 @@ def run_points(points, indices, make, burnin, nsteps, stacked=True, seed=25, gat
     writers: `PointWriter`s -> each reduces and saves every point's chain, in this order, while its sampler holds the chain.
     energy_resolved: every point's posterior carries a measurement per energy bin and is sampled under it
     (`DeviceEnsembleSampler(energy_resolved=True)`); the unstacked samplers then draw from the stacked run's streams -- `seed`,
-    stream g -- so that a point's chain is the same either way."""
+    stream g -- so that a point's chain is the same either way.
+    tabulated: every point's posterior carries a tabulated flavour-plane likelihood and is sampled under it
+    (`DeviceEnsembleSampler(tabulated=True)`); the unstacked samplers draw from the stacked run's streams, as for energy_resolved."""
     t0 = time.perf_counter()
     jobs = {g: make(points[g], g) for g in indices}
     if not jobs:
@@ -568,7 +580,7 @@ def run_points(points, indices, make, burnin, nsteps, stacked=True, seed=25, gat
     if stacked:
         t0 = time.perf_counter()
         sampler = mcmc_utils.DeviceEnsembleSampler(first.nwalkers, first.ndim, [jobs[g].f for g in order], seed=seed,
-                                                   stream_ids=order, energy_resolved=energy_resolved)
+                                                   stream_ids=order, energy_resolved=energy_resolved, tabulated=tabulated)
         sampler.on_nonunitary = "-inf"
         PHASES["sampling: sampler created"] = time.perf_counter() - t0
         # burn-in: enqueued, and only then -- while the GPU works through it and this thread has nothing to launch or allocate --
@@ -631,8 +643,9 @@ def run_points(points, indices, make, burnin, nsteps, stacked=True, seed=25, gat
                for i, g in enumerate(order)}
         PHASES["collect"] = time.perf_counter() - t0
         return out
-    if energy_resolved:
-        samplers = {g: mcmc_utils.DeviceEnsembleSampler(j.nwalkers, j.ndim, j.f, seed=seed, stream_ids=[g], energy_resolved=True)
+    if energy_resolved or tabulated:
+        samplers = {g: mcmc_utils.DeviceEnsembleSampler(j.nwalkers, j.ndim, j.f, seed=seed, stream_ids=[g], energy_resolved=energy_resolved,
+                                                        tabulated=tabulated)
                     for g, j in jobs.items()}
     else:
         samplers = {g: mcmc_utils.DeviceEnsembleSampler(j.nwalkers, j.ndim, j.f, seed=j.seed) for g, j in jobs.items()}
@@ -937,7 +950,8 @@ def point_filename(config, point, a):
     dim, tex, source, scale = point
     ns = argparse.Namespace(dimension=dim, source_ratio=source, texture=tex)
     ebins = "_ebins" if getattr(a, "energy_resolved", False) else ""       # never over a flux-averaged result (as sens.identifier)
-    return "fr%s_logLam%+.3f%s" % (mcmc_utils.chain_identifier(ns), scale, ebins)
+    ltab = "_ltab" if getattr(a, "likelihood_table", None) else ""         # ... nor over a Gaussian one (--likelihood-table)
+    return "fr%s_logLam%+.3f%s%s" % (mcmc_utils.chain_identifier(ns), scale, ebins, ltab)
 
 
 def binned_measurements(a, dims):
@@ -1012,6 +1026,10 @@ def main(argv=None):
     ap.add_argument("--binned-smearing", type=float, nargs="+", default=None, metavar="S",
                     help="energy-resolved: ONE value is the width of the flux-averaged likelihood to be comparable with, "
                          "sigma_k = S / sqrt(w_k) (default: the scan's smearing, %g); K values are the widths of the bins themselves" % C5_SMEARING)
+    ap.add_argument("--likelihood-table", type=str, default=None, metavar="FILE.npy",
+                    help="--config C5: sample every grid point under this tabulated flavour-plane likelihood (the flat node values "
+                         "llh.TabulatedLikelihood.save writes, DESIGN.md 6m) instead of the Gaussian; the chain files and every writer's "
+                         "files carry _ltab")
     ap.add_argument("--marginal-bins-1d", type=int, default=100)
     ap.add_argument("--marginal-bins-2d", type=int, default=50)
     ap.add_argument("--marginal-coverage", type=float, nargs="+", default=[90., 99.], metavar="COVERAGE")
@@ -1032,6 +1050,21 @@ def main(argv=None):
         if a.reweight_injected is not None:
             ap.error("--reweight-injected does not combine with --energy-resolved: its targets replace the chain's own Gaussian "
                      "measurement, and an energy-resolved chain has no single one (--reweight-binned, a model target, does)")
+    table = None
+    if a.likelihood_table is not None:
+        if a.config != "C5":
+            ap.error("--likelihood-table needs chains sampled under a measurement (--config C5); the chains of --config C4 sample the "
+                     "priors only")
+        if a.energy_resolved:
+            ap.error("--likelihood-table does not combine with --energy-resolved / --binned-measurement / --binned-smearing: a posterior "
+                     "carries a table or a measurement per energy bin, not both")
+        if a.reweight_injected is not None:
+            ap.error("--reweight-injected does not combine with --likelihood-table: its targets replace the chain's own Gaussian "
+                     "measurement, and a chain sampled under a table has none (--reweight-binned, a model target, does)")
+        try:
+            table = llh_utils.TabulatedLikelihood.load(a.likelihood_table)
+        except (OSError, ValueError) as e:
+            ap.error("--likelihood-table: %s" % e)
     if a.elements and not a.marginals:
         ap.error("--elements needs --marginals (it adds the element-space marginals to them)")
     if a.diagnostics and not a.datadir:
@@ -1114,7 +1147,7 @@ def main(argv=None):
                 meas = binned_measurements(a, sorted({p[0] for p in pts}))
             except (OSError, ValueError) as exc:
                 ap.error(str(exc))
-        make = lambda p, g: _SensPoint(p, g, nwalkers=nw, device=device, binned=meas.get(p[0]))  # noqa: E731
+        make = lambda p, g: _SensPoint(p, g, nwalkers=nw, device=device, binned=meas.get(p[0]), table=table)  # noqa: E731
         evals_per_point = nw * (a.burnin + a.nsteps)
     mine = gdist.shard(len(pts), rank, world)
     stacked = not a.no_stack
@@ -1159,21 +1192,25 @@ def main(argv=None):
         one = a.reweight_smearing[0] if a.reweight_smearing is not None and len(a.reweight_smearing) == 1 else None
         writers.append(BinnedReweightWriter(a.datadir, name_of, rw_binned, smearing=one))
     if a.datadir and not want_gather:
-        local = run_points(pts, mine, make, a.burnin, a.nsteps, stacked=stacked, writers=writers, energy_resolved=a.energy_resolved)
+        local = run_points(pts, mine, make, a.burnin, a.nsteps, stacked=stacked, writers=writers, energy_resolved=a.energy_resolved,
+                            tabulated=table is not None)
         gather_name = "none: every rank saved its own files (--datadir)"
     elif shared:
         g = SharedHostGather(control, rank, world, arena=arena)
-        chains = run_points(pts, mine, make, a.burnin, a.nsteps, stacked=True, gather=g, writers=writers, energy_resolved=a.energy_resolved)
+        chains = run_points(pts, mine, make, a.burnin, a.nsteps, stacked=True, gather=g, writers=writers, energy_resolved=a.energy_resolved,
+                            tabulated=table is not None)
         gather_name = g.stats.get("delivery", g.kind)
         g.release()
     elif device_gather:
         stage = Model(compile_model(Cf.unitary_paramset(), "PRIOR_ONLY", source_ratio=(1, 2, 0)), device=device)
         chains = run_points(pts, mine, make, a.burnin, a.nsteps, stacked=True,
-                            gather=DeviceGather(rccl, rank, world, stage, control=control), writers=writers, energy_resolved=a.energy_resolved)
+                            gather=DeviceGather(rccl, rank, world, stage, control=control), writers=writers, energy_resolved=a.energy_resolved,
+                            tabulated=table is not None)
         stage.close()
         gather_name = ("%s device gather to rank 0" % rccl.kind) if rccl is not None else "device -> host"
     else:
-        local = run_points(pts, mine, make, a.burnin, a.nsteps, stacked=stacked, writers=writers, energy_resolved=a.energy_resolved)
+        local = run_points(pts, mine, make, a.burnin, a.nsteps, stacked=stacked, writers=writers, energy_resolved=a.energy_resolved,
+                            tabulated=table is not None)
         t1 = time.perf_counter()
         chains = gdist.gather_chains_to_root(local, len(pts), control)
         PHASES["gather"] = time.perf_counter() - t1
@@ -1207,6 +1244,7 @@ def main(argv=None):
         print(json.dumps({"config": a.config, "grid_points": len(pts), "ranks": world, "walkers": nw, "burnin": a.burnin,
                           "nsteps": a.nsteps, "stacked": stacked, "gather": gather_name,
                           **({"likelihood": "energy-resolved"} if a.energy_resolved else {}),
+                          **({"likelihood": "tabulated"} if table is not None else {}),
                           "rccl_error": rccl_err, "librccl": gdist.rccl_library_info(),
                           "diagnostic_overrides": _lib.diagnostic_overrides(),
                           "gather_stats": GATHER_STATS, "nonunitary": LAST_NONUNITARY,

@@ -264,6 +264,18 @@ int gf_sampler_create_multi(gf_model* const* models, int nchains, int nwalkers, 
  * for any sampler, except gf_sampler_reweight* with measurement targets (bestfit_fr / smearing / offset): GF_ERR_UNSUPPORTED,
  * such a chain has no single Gaussian measurement to replace; model targets work. */
 int gf_sampler_create_binned(gf_model* const* models, int nmodels, int nchains, int nwalkers, uint64_t seed, double a, gf_sampler** out);
+/* A sampler of the tabulated flavour-plane likelihood: every model carries a table (gf_model_set_table_likelihood;
+ * GF_ERR_INVALID_ARG naming the first model that carries none).  nmodels == 1: every chain samples models[0]; nmodels == nchains: chain
+ * ch samples models[ch], under gf_sampler_create_multi's conditions; the tables' sides may differ from chain to chain.  The three calls
+ * above refuse such a model (GF_ERR_UNSUPPORTED): this is the explicit way in.  The stored lnprob is bit for bit gf_lnprob_batch's of the
+ * same model.  One launch shape, one launch per half-ensemble update; the lanes per walker follow the flux-averaged sampler's rule
+ * (GF_SAMPLER_LPW forces a choice; any choice gives the same bits).  The tables stay in device memory.  The sampler keeps its models and
+ * takes each one's table again at the start of every gf_sampler_run: a table set between two runs, of any side, is what the next run
+ * samples (a table a larger one replaced is kept by its model until the model goes).  The walkers' stored lnprob is NOT recomputed then:
+ * they hold the old table's values until they move or gf_sampler_set_state is called again.  Everything that reads a stored chain works
+ * as for any sampler, except gf_sampler_reweight* with measurement targets: GF_ERR_UNSUPPORTED, such a chain has no Gaussian measurement
+ * to replace; model targets work. */
+int gf_sampler_create_table(gf_model* const* models, int nmodels, int nchains, int nwalkers, uint64_t seed, double a, gf_sampler** out);
 /* Random stream of each chain, ids [nchains] (default: the chain's index in this sampler).  A grid scan passes the
  * global grid index, so that a grid point's chain is the same whichever rank runs it and whatever else shares its
  * sampler (the reference's jobs are seeded per job, scripts/mc_texture.py:137-138).  Before the first run. */
@@ -707,9 +719,10 @@ int gf_model_is_binned(const gf_model* m);   /* 1 with a binned measurement, 0 w
  * 1 <= nside <= GF_TABLE_MAX_NSIDE, every value finite or -inf and one of them finite: else GF_ERR_INVALID_ARG.  A model of another mode,
  * or one with a binned measurement: GF_ERR_UNSUPPORTED (and gf_model_set_binned_measurement refuses a model with a table); either way
  * the model is unchanged.  A table can be replaced (no launch of the model may be in flight on a stream other than its own; a nested
- * sampler or maximiser created earlier keeps reading the table it was created with) but not removed.  Refused with GF_ERR_UNSUPPORTED:
- * gf_sampler_create* (sampling a table in the ensemble sampler is out of scope: reweight a Gaussian chain to the model), and what sets
- * or reweights to a Gaussian measurement -- gf_toys_create*, gf_toys_set_measurements, gf_toys_set_binned_measurements,
+ * sampler or maximiser created earlier keeps reading the table it was created with; an ensemble sampler of gf_sampler_create_table reads
+ * the new one from its next run on) but not removed.  The ensemble sampler samples such a model through gf_sampler_create_table alone.
+ * Refused with GF_ERR_UNSUPPORTED: gf_sampler_create, gf_sampler_create_multi and gf_sampler_create_binned (their kernels evaluate another
+ * likelihood), and what sets or reweights to a Gaussian measurement -- gf_toys_create*, gf_toys_set_measurements, gf_toys_set_binned_measurements,
  * gf_nested_toys_evidence.  Of the models of one nested sampler or maximiser all carry a table or none; the sides may differ. */
 #define GF_TABLE_MAX_NSIDE 2048
 int gf_model_set_table_likelihood(gf_model* m, int nside, const double* values);
