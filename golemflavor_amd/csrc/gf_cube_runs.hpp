@@ -54,7 +54,7 @@ struct GfCubeRunsHost {
 namespace {
 using namespace gfdev;
 
-// iteration word of the seeding draws of the maximiser (gf_simplex.hip) and of a realisation ensemble's shared seeding (gf_toys.hip):
+// iteration word of the seeding draws of the maximiser (gf_simplex.hip) and of a realisation ensemble's shared seeding (gf_toys_common.hip):
 // the same points for the same run id; the nested sampler's initial draws take 0xFFFFFFFF
 constexpr uint32_t SX_SEED_ITER = 0xFFFFFFFEu;
 

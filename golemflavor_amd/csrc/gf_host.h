@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstddef>
 #include <cstdio>
@@ -38,6 +39,20 @@ __attribute__((format(printf, 2, 3))) inline int gf_fail_msg(int rc, const char*
     va_end(ap);
     gf_internal_set_error(msg);
     return rc;
+}
+
+// The Gaussian constants of one mock measurement (bf [3], smearing sm) for the entry point `who`, whose messages call it realisation
+// `label`: m [3] <- bf, *mh and *k by gf_internal_gauss_consts (gf_toys.hip, gf_ns_toys.hip)
+inline int gf_gauss_realisation(const double* bf, double sm, size_t label, const char* who, double* m, double* mh, double* k)
+{
+    if (!(sm > 0.0) || !std::isfinite(sm) || !std::isfinite(bf[0]) || !std::isfinite(bf[1]) || !std::isfinite(bf[2]))
+        return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: realisation %zu needs a finite measurement and a smearing > 0", who, label);
+    double inv_smear, c0;
+    for (int d = 0; d < 3; ++d) m[d] = bf[d];
+    gf_internal_gauss_consts(sm, &inv_smear, &c0, mh, k);
+    if (!std::isfinite(*mh) || !std::isfinite(*k))
+        return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: the smearing of realisation %zu is outside the range of the Gaussian's constants", who, label);
+    return GF_OK;
 }
 
 // The device scratch buffers of one call, released together when the holder goes out of scope, in the order they were taken (the

@@ -227,18 +227,9 @@ size_t nt_scratch_cap()
 int nt_measurements(const double* bf, const double* smearing, size_t n, size_t ntoys, std::vector<Consts>& out, const char* who)
 {
     out.resize(n);
-    for (size_t k = 0; k < n; ++k) {
-        const double sm = smearing[k % ntoys];
-        if (!(sm > 0.0) || !std::isfinite(sm) || !std::isfinite(bf[3 * k]) || !std::isfinite(bf[3 * k + 1]) || !std::isfinite(bf[3 * k + 2]))
-            return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: realisation %zu needs a finite measurement and a smearing > 0", who, k % ntoys);
-        Consts& g = out[k];
-        double inv_smear, c0;
-        for (int d = 0; d < 3; ++d) g.m[d] = bf[3 * k + d];
-        gf_internal_gauss_consts(sm, &inv_smear, &c0, &g.mh, &g.k);
-        if (!std::isfinite(g.mh) || !std::isfinite(g.k))
-            return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: the smearing of realisation %zu is outside the range of the Gaussian's constants", who, k % ntoys);
-    }
-    return GF_OK;
+    int rc = GF_OK;
+    for (size_t k = 0; k < n && rc == GF_OK; ++k) rc = gf_gauss_realisation(bf + 3 * k, smearing[k % ntoys], k % ntoys, who, out[k].m, &out[k].mh, &out[k].k);
+    return rc;
 }
 
 }  // namespace

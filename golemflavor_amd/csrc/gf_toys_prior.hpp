@@ -1,5 +1,5 @@
 // gf_toys_prior.hpp -- the prior sum of a realisation ensemble's seed points (DESIGN.md sections 6j and 6l): one kernel, instantiated by
-// the flux-averaged seeding (gf_toys.hip) and the energy-resolved one (gf_toys_binned.hip).
+// the seeding both ensembles share (gf_toys_common.hip).
 #pragma once
 #include "gf_cube_runs.hpp"
 

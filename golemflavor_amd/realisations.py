@@ -1,5 +1,5 @@
 """Realisation ensembles: the profile likelihood of many mock measurements at every new-physics scale in one call (DESIGN.md 6j;
-gf_toys.hip, include/golemflavor_hip.h gf_toys_*, gf_toys_set_measurements).
+gf_toys_common.hip, gf_toys.hip, include/golemflavor_hip.h gf_toys_*, gf_toys_set_measurements).
 
 The frequentist statistic of scripts/sens.py is -2 (max lnL(scale) - max lnL(null)); the reference cuts its Asimov curve at a chi2
 quantile (Wilks' theorem) and notes that the statistic's distribution "can be approximated by generating mock data or realisations of
@@ -66,10 +66,11 @@ def draw_realisations(bf, smearing, n, seed=0):
     return bf + float(smearing) * z
 
 
-class ToySeeds:
-    """The shared seeding of a realisation ensemble: `nseed` uniform cube points per scale (models, cols, bases, run_ids as for
-    SimplexMaximizer -- the points its seeding draws for the same seed and run id), evaluated once by each scale model's bulk path.
-    `nonunitary_seeds` [nscales]: the seeds the reference would have raised on."""
+class _SeedSet:
+    """What ToySeeds and BinnedToySeeds share (the device's one seed set, csrc/gf_toys_common.hip): the construction, the lifetime and
+    the seeds' theta.  A subclass names its entry points by `_SUFFIX` (gf_toys_create<_SUFFIX>, ...) and has its own _measurements,
+    the arguments and docstrings of select and scores, and the arrays its seeds() fetches."""
+    _SUFFIX = ""
 
     def __init__(self, models, cols, bases, nseed=DEFAULT_SEED_POINTS, seed=0, run_ids=None):
         self._L = _lib.lib()
@@ -82,69 +83,51 @@ class ToySeeds:
         if b.ndim == 1:
             b = np.tile(b, (self.nscales, 1))
         self.bases = np.ascontiguousarray(b.reshape(self.nscales, ndim))
-        h = C.c_void_p()
-        _lib.check(self._L.gf_toys_create(rowsets.model_handles(self.models, self.nscales), self.nscales, self.nscan,
-                                          self.cols.ctypes.data_as(_lib._ip), self.bases.ctypes.data_as(_lib._dp), self.nseed,
-                                          int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(h)), "gf_toys_create")
-        self._h = h
+        self._h = C.c_void_p()
+        self._call("gf_toys_create", rowsets.model_handles(self.models, self.nscales), self.nscales, self.nscan,
+                   self.cols.ctypes.data_as(_lib._ip), self.bases.ctypes.data_as(_lib._dp), self.nseed, int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(self._h))
         try:
             if run_ids is not None:
-                ids = np.ascontiguousarray(run_ids, dtype=np.uint64)
-                _lib.check(self._L.gf_toys_set_run_ids(self._h, ids.ctypes.data_as(C.POINTER(C.c_uint64))), "gf_toys_set_run_ids")
-            nu = np.zeros(self.nscales, np.uint32)
-            _lib.check(self._L.gf_toys_seed(self._h, nu.ctypes.data_as(C.POINTER(C.c_uint32))), "gf_toys_seed")
-            self.nonunitary_seeds = nu
+                self._call("gf_toys_set_run_ids", self._h, np.ascontiguousarray(run_ids, dtype=np.uint64).ctypes.data_as(C.POINTER(C.c_uint64)))
+            self.nonunitary_seeds = np.zeros(self.nscales, np.uint32)
+            self._call("gf_toys_seed", self._h, self.nonunitary_seeds.ctypes.data_as(C.POINTER(C.c_uint32)))
         except BaseException:
             self.close()
             raise
 
-    def _measurements(self, bestfit_fr, smearing):
-        bf = np.ascontiguousarray(bestfit_fr, dtype=np.float64)
-        if bf.ndim not in (2, 3) or bf.shape[-1] != 3 or (bf.ndim == 3 and bf.shape[0] != self.nscales):
-            raise ValueError("measurements must be [T][3] or [nscales][T][3]")
-        T = bf.shape[-2]
-        sm = np.ascontiguousarray(np.broadcast_to(np.asarray(smearing, dtype=np.float64), (T,)))
-        return bf, sm, T
+    def _call(self, name, *args):
+        """the entry point `name` of this class's handle, checked"""
+        _lib.check(getattr(self._L, name + self._SUFFIX)(*args), name + self._SUFFIX)
 
-    def select(self, bestfit_fr, smearing, K):
-        """The starts of every (scale, realisation): the K best seeds under score = lp + gauss(m_t, fr), score descending then seed
-        index ascending, finite scores only.  bestfit_fr [T][3] (shared by the scales) or [nscales][T][3]; smearing [T] or one value.
-        Returns dict(cube [nscales][T][K][nscan] (NaN behind the count), index, score [nscales][T][K] (-1, -inf), count [nscales][T])."""
-        bf, sm, T = self._measurements(bestfit_fr, smearing)
-        K = int(K)
-        S = self.nscales
-        out = dict(cube=np.empty((S, T, max(K, 0), self.nscan)), index=np.empty((S, T, max(K, 0)), np.int32),
-                   score=np.empty((S, T, max(K, 0))), count=np.empty((S, T), np.int32))
-        _lib.check(self._L.gf_toys_select(self._h, bf.ctypes.data_as(_lib._dp), int(bf.ndim == 3), sm.ctypes.data_as(_lib._dp), T, K,
-                                          out["cube"].ctypes.data_as(_lib._dp), out["index"].ctypes.data_as(_lib._ip),
-                                          out["score"].ctypes.data_as(_lib._dp), out["count"].ctypes.data_as(_lib._ip)), "gf_toys_select")
+    def _select(self, T, head, K):
+        """select() for the measurements `head`, the entry point's arguments in front of T (from _measurements)"""
+        S, K, Kc = self.nscales, int(K), max(int(K), 0)
+        out = dict(cube=np.empty((S, T, Kc, self.nscan)), index=np.empty((S, T, Kc), np.int32), score=np.empty((S, T, Kc)),
+                   count=np.empty((S, T), np.int32))
+        self._call("gf_toys_select", self._h, *head, T, K, out["cube"].ctypes.data_as(_lib._dp), out["index"].ctypes.data_as(_lib._ip),
+                   out["score"].ctypes.data_as(_lib._dp), out["count"].ctypes.data_as(_lib._ip))
         return out
 
-    def scores(self, bestfit_fr, smearing):
-        """Every score the selection ranks, [nscales][T][nseed]."""
-        bf, sm, T = self._measurements(bestfit_fr, smearing)
+    def _scores(self, T, head):
         out = np.empty((self.nscales, T, self.nseed))
-        _lib.check(self._L.gf_toys_scores(self._h, bf.ctypes.data_as(_lib._dp), int(bf.ndim == 3), sm.ctypes.data_as(_lib._dp), T,
-                                          out.ctypes.data_as(_lib._dp)), "gf_toys_scores")
+        self._call("gf_toys_scores", self._h, *head, T, out.ctypes.data_as(_lib._dp))
         return out
 
-    def seeds(self, scale=0):
-        """Scale `scale`'s seeds: dict(cube [nseed][nscan], theta [nseed][ndim] (the device's map: product and sum each rounded),
-        lnprob (the scale model's own), lp (the prior sum, -inf outside the box), fr [nseed][3], status)."""
+    def _seeds(self, scale, shapes):
+        """seeds(): the arrays of `shapes` (name: a seed's shape, in the entry point's order), status and theta"""
         M = self.nseed
-        out = dict(cube=np.empty((M, self.nscan)), lnprob=np.empty(M), lp=np.empty(M), fr=np.empty((M, 3)), status=np.empty(M, np.int32))
-        _lib.check(self._L.gf_toys_get_seeds(self._h, int(scale), *[out[k].ctypes.data_as(_lib._dp) for k in ("cube", "lnprob", "lp", "fr")],
-                                             out["status"].ctypes.data_as(_lib._ip)), "gf_toys_get_seeds")
+        out = {k: np.empty((M,) + tuple(shape)) for k, shape in shapes.items()}
+        out["status"] = np.empty(M, np.int32)
+        self._call("gf_toys_get_seeds", self._h, int(scale), *[out[k].ctypes.data_as(_lib._dp) for k in shapes], out["status"].ctypes.data_as(_lib._ip))
         desc = getattr(self.models[scale], "model", self.models[scale]).desc
         lo, hi = np.asarray(desc.lo)[self.cols], np.asarray(desc.hi)[self.cols]
-        theta = np.tile(self.bases[scale], (M, 1))
+        theta = out["theta"] = np.tile(self.bases[scale], (M, 1))
         theta[:, self.cols] = (hi - lo) * out["cube"] + lo
-        out["theta"] = theta
         return out
 
     def close(self):
         if getattr(self, "_h", None):
-            self._L.gf_toys_destroy(self._h)
+            getattr(self._L, "gf_toys_destroy" + self._SUFFIX)(self._h)
             self._h = None
 
     def __enter__(self):
@@ -158,6 +141,35 @@ class ToySeeds:
             self.close()
         except Exception:
             pass
+
+
+class ToySeeds(_SeedSet):
+    """The shared seeding of a realisation ensemble: `nseed` uniform cube points per scale (models, cols, bases, run_ids as for
+    SimplexMaximizer -- the points its seeding draws for the same seed and run id), evaluated once by each scale model's bulk path.
+    `nonunitary_seeds` [nscales]: the seeds the reference would have raised on."""
+
+    def _measurements(self, bestfit_fr, smearing):
+        bf = np.ascontiguousarray(bestfit_fr, dtype=np.float64)
+        if bf.ndim not in (2, 3) or bf.shape[-1] != 3 or (bf.ndim == 3 and bf.shape[0] != self.nscales):
+            raise ValueError("measurements must be [T][3] or [nscales][T][3]")
+        T = bf.shape[-2]
+        sm = np.ascontiguousarray(np.broadcast_to(np.asarray(smearing, dtype=np.float64), (T,)))
+        return T, (bf.ctypes.data_as(_lib._dp), int(bf.ndim == 3), sm.ctypes.data_as(_lib._dp))
+
+    def select(self, bestfit_fr, smearing, K):
+        """The starts of every (scale, realisation): the K best seeds under score = lp + gauss(m_t, fr), score descending then seed
+        index ascending, finite scores only.  bestfit_fr [T][3] (shared by the scales) or [nscales][T][3]; smearing [T] or one value.
+        Returns dict(cube [nscales][T][K][nscan] (NaN behind the count), index, score [nscales][T][K] (-1, -inf), count [nscales][T])."""
+        return self._select(*self._measurements(bestfit_fr, smearing), K)
+
+    def scores(self, bestfit_fr, smearing):
+        """Every score the selection ranks, [nscales][T][nseed]."""
+        return self._scores(*self._measurements(bestfit_fr, smearing))
+
+    def seeds(self, scale=0):
+        """Scale `scale`'s seeds: dict(cube [nseed][nscan], theta [nseed][ndim] (the device's map: product and sum each rounded),
+        lnprob (the scale model's own), lp (the prior sum, -inf outside the box), fr [nseed][3], status)."""
+        return self._seeds(scale, dict(cube=(self.nscan,), lnprob=(), lp=(), fr=(3,)))
 
 
 def toy_select(lp, fr, status, bestfit_fr, smearing, offset, K, device=0):
@@ -185,38 +197,15 @@ def draw_binned_realisations(binned, n, seed=0):
     return binned.fr_bins[None] + binned.sigma[None, :, None] * z
 
 
-class BinnedToySeeds:
+class BinnedToySeeds(_SeedSet):
     """The shared seeding of a realisation ensemble of the energy-resolved likelihood: ToySeeds over models that carry a
     binned measurement (`Model.set_binned_measurement`), the seeds keeping their composition at every energy bin.  The compositions take
     24 * nscales * nseed * nbins bytes on the device."""
+    _SUFFIX = "_binned"
 
     def __init__(self, models, cols, bases, nseed=DEFAULT_SEED_POINTS, seed=0, run_ids=None):
-        self._L = _lib.lib()
-        self.models = list(models)
-        self.nscales = len(self.models)
-        self.cols = np.ascontiguousarray(cols, dtype=np.int32)
-        self.nscan, self.nseed = len(self.cols), int(nseed)
-        ndim = self._L.gf_model_ndim(rowsets.handle(self.models[0]))
+        super().__init__(models, cols, bases, nseed, seed, run_ids)
         self.nbins = int(self._L.gf_model_nbins(rowsets.handle(self.models[0])))
-        b = np.asarray(bases, dtype=np.float64)
-        if b.ndim == 1:
-            b = np.tile(b, (self.nscales, 1))
-        self.bases = np.ascontiguousarray(b.reshape(self.nscales, ndim))
-        h = C.c_void_p()
-        _lib.check(self._L.gf_toys_create_binned(rowsets.model_handles(self.models, self.nscales), self.nscales, self.nscan,
-                                                 self.cols.ctypes.data_as(_lib._ip), self.bases.ctypes.data_as(_lib._dp), self.nseed,
-                                                 int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(h)), "gf_toys_create_binned")
-        self._h = h
-        try:
-            if run_ids is not None:
-                ids = np.ascontiguousarray(run_ids, dtype=np.uint64)
-                _lib.check(self._L.gf_toys_set_run_ids_binned(self._h, ids.ctypes.data_as(C.POINTER(C.c_uint64))), "gf_toys_set_run_ids_binned")
-            nu = np.zeros(self.nscales, np.uint32)
-            _lib.check(self._L.gf_toys_seed_binned(self._h, nu.ctypes.data_as(C.POINTER(C.c_uint32))), "gf_toys_seed_binned")
-            self.nonunitary_seeds = nu
-        except BaseException:
-            self.close()
-            raise
 
     def _measurements(self, meas, sigma):
         m = np.ascontiguousarray(meas, dtype=np.float64)
@@ -226,62 +215,22 @@ class BinnedToySeeds:
         sg = np.ascontiguousarray(sigma, dtype=np.float64)
         if sg.shape not in ((self.nbins,), (T, self.nbins)):
             raise ValueError("widths must be [%d], shared by the realisations, or [T][%d]" % (self.nbins, self.nbins))
-        return m, sg, T
+        return T, (m.ctypes.data_as(_lib._dp), int(m.ndim == 4), sg.ctypes.data_as(_lib._dp), int(sg.ndim == 2))
 
     def select(self, meas, sigma, K):
         """The starts of every (scale, realisation): the K best seeds under the binned score, score descending then seed index ascending,
         finite scores only.  meas [T][nb][3] (shared by the scales) or [nscales][T][nb][3]; sigma [nb] or [T][nb].  Returns ToySeeds.select's
         dict."""
-        m, sg, T = self._measurements(meas, sigma)
-        K = int(K)
-        S = self.nscales
-        out = dict(cube=np.empty((S, T, max(K, 0), self.nscan)), index=np.empty((S, T, max(K, 0)), np.int32),
-                   score=np.empty((S, T, max(K, 0))), count=np.empty((S, T), np.int32))
-        _lib.check(self._L.gf_toys_select_binned(self._h, m.ctypes.data_as(_lib._dp), int(m.ndim == 4), sg.ctypes.data_as(_lib._dp), int(sg.ndim == 2),
-                                                 T, K, out["cube"].ctypes.data_as(_lib._dp), out["index"].ctypes.data_as(_lib._ip),
-                                                 out["score"].ctypes.data_as(_lib._dp), out["count"].ctypes.data_as(_lib._ip)),
-                   "gf_toys_select_binned")
-        return out
+        return self._select(*self._measurements(meas, sigma), K)
 
     def scores(self, meas, sigma):
         """Every score the selection ranks, [nscales][T][nseed]."""
-        m, sg, T = self._measurements(meas, sigma)
-        out = np.empty((self.nscales, T, self.nseed))
-        _lib.check(self._L.gf_toys_scores_binned(self._h, m.ctypes.data_as(_lib._dp), int(m.ndim == 4), sg.ctypes.data_as(_lib._dp), int(sg.ndim == 2),
-                                                 T, out.ctypes.data_as(_lib._dp)), "gf_toys_scores_binned")
-        return out
+        return self._scores(*self._measurements(meas, sigma))
 
     def seeds(self, scale=0):
         """Scale `scale`'s seeds: ToySeeds.seeds' dict (lnprob: the scale model's own, under its binned measurement; fr: the flux-averaged
         composition) and fr_bins [nseed][nb][3], NaN for a seed whose status is not GF_ST_OK."""
-        M = self.nseed
-        out = dict(cube=np.empty((M, self.nscan)), lnprob=np.empty(M), lp=np.empty(M), fr=np.empty((M, 3)), fr_bins=np.empty((M, self.nbins, 3)),
-                   status=np.empty(M, np.int32))
-        _lib.check(self._L.gf_toys_get_seeds_binned(self._h, int(scale), *[out[k].ctypes.data_as(_lib._dp) for k in ("cube", "lnprob", "lp", "fr", "fr_bins")],
-                                                    out["status"].ctypes.data_as(_lib._ip)), "gf_toys_get_seeds_binned")
-        desc = getattr(self.models[scale], "model", self.models[scale]).desc
-        lo, hi = np.asarray(desc.lo)[self.cols], np.asarray(desc.hi)[self.cols]
-        theta = np.tile(self.bases[scale], (M, 1))
-        theta[:, self.cols] = (hi - lo) * out["cube"] + lo
-        out["theta"] = theta
-        return out
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.gf_toys_destroy_binned(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._seeds(scale, dict(cube=(self.nscan,), lnprob=(), lp=(), fr=(3,), fr_bins=(self.nbins, 3)))
 
 
 def toy_select_binned(lp, fr_bins, status, meas, sigma, offset, K, device=0):
@@ -327,64 +276,73 @@ def realisation_scan(args, asimov_paramset, llh_paramset, scales, measurements=N
     run of its scale, as it fails profile_scan's run; AssertionError when `check`."""
     if binned is not None:
         raise ValueError("realisations are of the flux-averaged Gaussian likelihood; the energy-resolved one is not supported")
+    K, opts = _scan_options(args, nstarts, xatol, fatol, maxiter, adaptive, restarts, on_nonunitary)
+    scales = np.asarray(scales, dtype=np.float64)
+    sm0, meas, sms = _gaussian_measurements(args, asimov_paramset, len(scales), measurements, ntoys, toy_seed, smearings, smearing)
+    return _scan(ToySeeds, "measurements", meas, sms, meas.ndim == 3, {}, args, asimov_paramset, llh_paramset, scales, K, nseed, run_ids,
+                 opts, seed, sm0, device, batch, threshold, check)
+
+
+def _gaussian_measurements(args, asimov_paramset, S, measurements, ntoys, toy_seed, smearings, smearing):
+    """Gaussian measurements given or drawn, validated: (the model's smearing, measurements [T][3] or [S][T][3], smearings [T])"""
+    sm0 = float(smearing if smearing is not None else _opt(args, "smearing", 0.02))
+    if measurements is None:
+        if ntoys is None:
+            raise ValueError("give measurements or ntoys")
+        measurements = draw_realisations(fr_utils.angles_to_fr(asimov_paramset.from_tag(ParamTag.BESTFIT, values=True)), sm0, ntoys, toy_seed)
+    meas = np.ascontiguousarray(measurements, dtype=np.float64)
+    if meas.ndim not in (2, 3) or meas.shape[-1] != 3 or (meas.ndim == 3 and meas.shape[0] != S):
+        raise ValueError("measurements must be [T][3] or [S][T][3]")
+    return sm0, meas, np.ascontiguousarray(np.broadcast_to(np.asarray(sm0 if smearings is None else smearings, dtype=np.float64), (meas.shape[-2],)))
+
+
+def _scan(seed_class, keyword, meas, widths, per_scale, extra, args, asimov_paramset, llh_paramset, scales, K, nseed, run_ids, opts, seed,
+          smearing, device, batch, threshold, check, binned=None):
+    """The body of a realisation scan over validated measurements (`meas` per scale when `per_scale`, `widths` [T] first): the seeds of
+    `seed_class`, their selection, the polish with the runs' measurements under the maximiser's `keyword`, the statistic, and the
+    result with the `extra` keys."""
+    S, T = len(scales), len(widths)
+    per_run = MAX_RUNS // S if batch is None else int(batch)
+    if per_run < 1 or per_run * S > MAX_RUNS:
+        raise ValueError("batch must keep batch * len(scales) within %d runs" % MAX_RUNS)
+    cols, models, bases, labels = _scan_models(args, asimov_paramset, llh_paramset, scales, smearing, device, binned=binned)
+    try:
+        t0 = time.perf_counter()
+        with seed_class(models, cols, bases, nseed=int(nseed if nseed is not None else _opt(args, "pl_seed_points", DEFAULT_SEED_POINTS)),
+                        seed=int(seed if seed is not None else _opt(args, "seed", 0)), run_ids=run_ids) as seeds:
+            t1 = time.perf_counter()
+            sel = seeds.select(meas, widths, K)
+            nu_seeds = seeds.nonunitary_seeds.copy()
+        t2 = time.perf_counter()
+        res, dead = _polish(models, cols, bases, labels, sel, nu_seeds, T, per_run, opts, keyword, meas, widths, per_scale)
+        t3 = time.perf_counter()
+    finally:
+        for m in models:
+            m.close()
+    _statistic(res, dead, labels, scales, threshold, check and opts["on_nonunitary"] == "raise")
+    res.update(scales=scales, measurements=meas, smearings=widths, nonunitary_seeds=nu_seeds, **extra, **_starts_of(sel),
+               seconds=t3 - t0, seconds_seed=t1 - t0, seconds_select=t2 - t1, seconds_polish=t3 - t2)
+    return res
+
+
+def _scan_options(args, nstarts, xatol, fatol, maxiter, adaptive, restarts, on_nonunitary):
+    """(K, the maximiser's options) of a realisation scan: the keyword, else args' --pl-* option, else the default"""
     if on_nonunitary not in ("raise", "-inf"):
         raise ValueError("on_nonunitary must be 'raise' or '-inf'")
     K = int(nstarts)
     if not 1 <= K <= MAX_TOY_STARTS:
         raise ValueError("nstarts must be 1 to %d, the starts the shared seeding selects" % MAX_TOY_STARTS)
-    scales = np.asarray(scales, dtype=np.float64)
-    S = len(scales)
-    sm0 = float(smearing if smearing is not None else _opt(args, "smearing", 0.02))
-    if measurements is None:
-        if ntoys is None:
-            raise ValueError("give measurements or ntoys")
-        bf0 = fr_utils.angles_to_fr(asimov_paramset.from_tag(ParamTag.BESTFIT, values=True))
-        measurements = draw_realisations(bf0, sm0, ntoys, toy_seed)
-    meas = np.ascontiguousarray(measurements, dtype=np.float64)
-    if meas.ndim not in (2, 3) or meas.shape[-1] != 3 or (meas.ndim == 3 and meas.shape[0] != S):
-        raise ValueError("measurements must be [T][3] or [S][T][3]")
-    T = meas.shape[-2]
-    sms = np.ascontiguousarray(np.broadcast_to(np.asarray(sm0 if smearings is None else smearings, dtype=np.float64), (T,)))
-    per_run = MAX_RUNS // S if batch is None else int(batch)
-    if per_run < 1 or per_run * S > MAX_RUNS:
-        raise ValueError("batch must keep batch * len(scales) within %d runs" % MAX_RUNS)
 
-    opts = _polish_options(args, xatol, fatol, maxiter, adaptive, restarts, on_nonunitary)
-    cols, models, bases, labels = _scan_models(args, asimov_paramset, llh_paramset, scales, sm0, device)
-    try:
-        t0 = time.perf_counter()
-        with ToySeeds(models, cols, bases, nseed=int(nseed if nseed is not None else _opt(args, "pl_seed_points", DEFAULT_SEED_POINTS)),
-                      seed=int(seed if seed is not None else _opt(args, "seed", 0)), run_ids=run_ids) as seeds:
-            t1 = time.perf_counter()
-            sel = seeds.select(meas, sms, K)
-            nu_seeds = seeds.nonunitary_seeds.copy()
-        t2 = time.perf_counter()
-
-        def measurement_of(ss, tt):
-            return dict(measurements=(meas[ss, tt] if meas.ndim == 3 else meas[tt], sms[tt]))
-        res, dead = _polish(models, cols, bases, labels, sel, nu_seeds, T, per_run, opts, measurement_of)
-        t3 = time.perf_counter()
-    finally:
-        for m in models:
-            m.close()
-    _statistic(res, dead, labels, scales, threshold, check and on_nonunitary == "raise")
-    res.update(scales=scales, measurements=meas, smearings=sms, nonunitary_seeds=nu_seeds, **_starts_of(sel),
-               seconds=t3 - t0, seconds_seed=t1 - t0, seconds_select=t2 - t1, seconds_polish=t3 - t2)
-    return res
-
-
-def _polish_options(args, xatol, fatol, maxiter, adaptive, restarts, on_nonunitary):
-    """the maximiser's options of a realisation scan: the keyword, else args' --pl-* option, else the default"""
     def pick(v, name, default):
         return v if v is not None else _opt(args, name, default)
-    return dict(xatol=float(pick(xatol, "pl_xatol", DEFAULT_XATOL)), fatol=float(pick(fatol, "pl_fatol", DEFAULT_FATOL)),
+    return K, dict(xatol=float(pick(xatol, "pl_xatol", DEFAULT_XATOL)), fatol=float(pick(fatol, "pl_fatol", DEFAULT_FATOL)),
                 maxiter=pick(maxiter, "pl_maxiter", None), adaptive=bool(pick(adaptive, "pl_adaptive", True)),
                 restarts=int(pick(restarts, "pl_restarts", DEFAULT_RESTARTS)), on_nonunitary=on_nonunitary)
 
 
-def _polish(models, cols, bases, labels, sel, nu_seeds, T, per_run, opts, measurement_of):
-    """The selected seeds of every (scale, realisation) polished, `per_run` realisations per maximiser: measurement_of(ss, tt) gives the
-    maximiser's keyword that carries the runs' own measurements.  Returns (res [T][S] arrays, dead [S])."""
+def _polish(models, cols, bases, labels, sel, nu_seeds, T, per_run, opts, keyword, meas, widths, per_scale):
+    """The selected seeds of every (scale, realisation) polished, `per_run` realisations per maximiser, whose `keyword` carries the runs'
+    own measurements (`meas` per scale when `per_scale`, `widths` [T] first).  Returns (res [T][S] arrays, dead [S])."""
     S, ndim = len(models), len(bases[0])
     res = dict(max_lnl=np.full((T, S), -np.inf), argmax_theta=np.full((T, S, ndim), np.nan), nstarts=np.zeros((T, S), np.int32),
                nfev=np.zeros((T, S), np.int64), niter=np.zeros((T, S), np.int64), nonunitary=np.zeros((T, S), np.uint32),
@@ -403,7 +361,8 @@ def _polish(models, cols, bases, labels, sel, nu_seeds, T, per_run, opts, measur
         # a run with fewer than K finite seeds keeps that many starts; the rows behind them are never evaluated
         with SimplexMaximizer([models[s] for s in ss], cols, [bases[s] for s in ss], nstarts=0, nseed=0,
                               starts=np.nan_to_num(sel["cube"][ss, tt], nan=0.5), start_counts=count[ss, tt],
-                              labels=["realisation %d, %s" % (t, labels[s]) for s, t in zip(ss, tt)], **measurement_of(ss, tt), **opts) as mx:
+                              labels=["realisation %d, %s" % (t, labels[s]) for s, t in zip(ss, tt)],
+                              **{keyword: (meas[ss, tt] if per_scale else meas[tt], widths[tt])}, **opts) as mx:
             r = mx.run(check=False)
         for k in res:
             res[k][tt, ss] = r[k]
@@ -419,9 +378,8 @@ def _statistic(res, dead, labels, scales, threshold, check):
     null = int(np.argmin(scales))
     with np.errstate(invalid="ignore"):
         res["ts"] = -2.0 * (res["max_lnl"] - res["max_lnl"][:, null:null + 1])
-    T = len(res["max_lnl"])
-    limits = np.full(T, np.nan)
-    for t in range(T):
+    limits = np.full(len(res["max_lnl"]), np.nan)
+    for t in range(len(limits)):
         lim = profile_likelihood_limit(scales, res["max_lnl"][t], threshold)
         if lim is not None:
             limits[t] = lim
@@ -444,11 +402,7 @@ def binned_realisation_scan(args, asimov_paramset, llh_paramset, scales, binned,
     draw_binned_realisations(binned, ntoys, toy_seed).  sigmas: [nb], shared by the realisations (default: binned.sigma), or [T][nb].
     Everything else, and the dict returned, as realisation_scan: max_lnl[t, s] is the maximum under (m_t, sigma_t), `measurements` is
     [T][nb][3] (or [S][T][nb][3]) and `sigmas` [T][nb] takes the place of `smearings`."""
-    if on_nonunitary not in ("raise", "-inf"):
-        raise ValueError("on_nonunitary must be 'raise' or '-inf'")
-    K = int(nstarts)
-    if not 1 <= K <= MAX_TOY_STARTS:
-        raise ValueError("nstarts must be 1 to %d, the starts the shared seeding selects" % MAX_TOY_STARTS)
+    K, opts = _scan_options(args, nstarts, xatol, fatol, maxiter, adaptive, restarts, on_nonunitary)
     scales = np.asarray(scales, dtype=np.float64)
     S, nb = len(scales), binned.nbins
     if measurements is None:
@@ -463,31 +417,8 @@ def binned_realisation_scan(args, asimov_paramset, llh_paramset, scales, binned,
     if sg.shape not in ((nb,), (T, nb)):
         raise ValueError("sigmas must be [%d], shared by the realisations, or [T][%d]" % (nb, nb))
     sgs = np.ascontiguousarray(np.broadcast_to(sg, (T, nb)))
-    per_run = MAX_RUNS // S if batch is None else int(batch)
-    if per_run < 1 or per_run * S > MAX_RUNS:
-        raise ValueError("batch must keep batch * len(scales) within %d runs" % MAX_RUNS)
-    opts = _polish_options(args, xatol, fatol, maxiter, adaptive, restarts, on_nonunitary)
-    cols, models, bases, labels = _scan_models(args, asimov_paramset, llh_paramset, scales, smearing, device, binned=binned)
-    try:
-        t0 = time.perf_counter()
-        with BinnedToySeeds(models, cols, bases, nseed=int(nseed if nseed is not None else _opt(args, "pl_seed_points", DEFAULT_SEED_POINTS)),
-                            seed=int(seed if seed is not None else _opt(args, "seed", 0)), run_ids=run_ids) as seeds:
-            t1 = time.perf_counter()
-            sel = seeds.select(meas, sgs, K)
-            nu_seeds = seeds.nonunitary_seeds.copy()
-        t2 = time.perf_counter()
-
-        def measurement_of(ss, tt):
-            return dict(binned_measurements=(meas[ss, tt] if meas.ndim == 4 else meas[tt], sgs[tt]))
-        res, dead = _polish(models, cols, bases, labels, sel, nu_seeds, T, per_run, opts, measurement_of)
-        t3 = time.perf_counter()
-    finally:
-        for m in models:
-            m.close()
-    _statistic(res, dead, labels, scales, threshold, check and on_nonunitary == "raise")
-    res.update(scales=scales, measurements=meas, sigmas=sgs, smearings=sgs, nonunitary_seeds=nu_seeds, **_starts_of(sel),
-               seconds=t3 - t0, seconds_seed=t1 - t0, seconds_select=t2 - t1, seconds_polish=t3 - t2)
-    return res
+    return _scan(BinnedToySeeds, "binned_measurements", meas, sgs, meas.ndim == 4, dict(sigmas=sgs), args, asimov_paramset, llh_paramset, scales,
+                 K, nseed, run_ids, opts, seed, smearing, device, batch, threshold, check, binned=binned)
 
 
 def sensitivity_band(limits, quantiles=BAND_QUANTILES):
@@ -572,18 +503,7 @@ def evidence_realisation_scan(args, asimov_paramset, llh_paramset, scales, measu
     if binned is not None:
         raise ValueError("realisations are of the flux-averaged Gaussian likelihood; the energy-resolved one is not supported")
     scales = np.asarray(scales, dtype=np.float64)
-    S = len(scales)
-    sm0 = float(smearing if smearing is not None else _opt(args, "smearing", 0.02))
-    if measurements is None:
-        if ntoys is None:
-            raise ValueError("give measurements or ntoys")
-        bf0 = fr_utils.angles_to_fr(asimov_paramset.from_tag(ParamTag.BESTFIT, values=True))
-        measurements = draw_realisations(bf0, sm0, ntoys, toy_seed)
-    meas = np.ascontiguousarray(measurements, dtype=np.float64)
-    if meas.ndim not in (2, 3) or meas.shape[-1] != 3 or (meas.ndim == 3 and meas.shape[0] != S):
-        raise ValueError("measurements must be [T][3] or [S][T][3]")
-    T = meas.shape[-2]
-    sms = np.ascontiguousarray(np.broadcast_to(np.asarray(sm0 if smearings is None else smearings, dtype=np.float64), (T,)))
+    sm0, meas, sms = _gaussian_measurements(args, asimov_paramset, len(scales), measurements, ntoys, toy_seed, smearings, smearing)
     t0 = time.perf_counter()
     run = nested.evidence_scan(args, asimov_paramset, llh_paramset, scales, run_ids=run_ids, nlive=nlive, tol=tol, batch=batch, walks=walks,
                                seed=seed, on_nonunitary=on_nonunitary, smearing=sm0, device=device, max_iter=max_iter, return_sampler=True,

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import toys_binned_harness as H
+from test_gpu_realisations import check_handle_against_standalone
 from test_gpu_realisations import model_bf, oeu_scale, sens_args, sens_desc  # noqa: F401  (oeu_scale is a fixture)
 from golemflavor_amd import _lib
 from golemflavor_amd import configs as Cf
@@ -188,6 +189,44 @@ def test_selection_equals_the_host_build(host, K):
     # the host test's own case
     lp, frb, status, meas, sigma, off = H.crafted(700, 130, 5, seed=3, per_toy_sigma=True)
     check_selection(host, lp, frb, status, meas, sigma, off, K, "host case")
+
+
+@pytest.mark.parametrize("K", [1, 5])
+def test_handle_selection_equals_the_standalone_selection(oeu_scale, K):
+    """The two routes through the selection, at 3 energy bins: BinnedToySeeds.select over two scales, with shared and with per-scale
+    measurements, against toy_select_binned per scale on that scale's seeds() arrays and the set's offset.  CHUNK + 1 seeds are two
+    parts of the seed range, the second of one seed; 65 realisations are two workgroups of the select kernel, the second with one live
+    lane.  The last two realisations have one narrow bin: thrown so that the wall leaves scale 0 three finite seeds, and so far that no
+    scale keeps any."""
+    args = oeu_args(3)
+    asimov, _ = Cf.sens_paramsets(6, (1., 1., 1.))
+    binned = own_measurement(args, asimov)
+    M, T, nb = CHUNK + 1, 65, 3
+    cols, models, bases, _ = scale_models(args, [oeu_scale - 0.5, oeu_scale], binned)
+    try:
+        off = float(getattr(models[0], "model", models[0]).desc.offset)
+        with R.BinnedToySeeds(models, cols, bases, nseed=M, seed=11) as seeds:
+            sd = [seeds.seeds(s) for s in range(2)]
+            b, c, cross = wall_crossings(sd[0]["fr_bins"][sd[0]["status"] == _lib.GF_ST_OK], 0.01)
+            cross = np.sort(cross[np.isfinite(cross)])
+            sig = np.broadcast_to(binned.sigma, (T, nb)).copy()
+            sig[-2:, b] = 0.01
+            shared = R.draw_binned_realisations(binned, T, seed=21)
+            shared[-2, b], shared[-1, b] = c + 0.5 * (cross[-4] + cross[-3]) * U, c + 2.0 * U
+            other = R.draw_binned_realisations(binned, T, seed=22)
+            other[-1, b] = c + 2.0 * U
+            for meas in (shared, np.stack([shared, other])):
+                sel = seeds.select(meas, sig, K)
+                assert sel["cube"].shape == (2, T, K, len(cols))
+                check_handle_against_standalone(sel, sd, lambda s: R.toy_select_binned(sd[s]["lp"], sd[s]["fr_bins"], sd[s]["status"],
+                                                                                       meas[s] if meas.ndim == 4 else meas, sig, off, K), K)
+                print("K = %d, %s measurements: counts of the narrow realisations %s" % (K, "per-scale" if meas.ndim == 4 else "shared",
+                                                                                         sel["count"][:, -2:].tolist()))
+                # conditions on the inputs: full lists, a list cut short by the wall, and empty ones
+                assert np.any(sel["count"] == K) and sel["count"][0, -2] == min(K, 3) and np.all(sel["count"][:, -1] == 0)
+    finally:
+        for m in models:
+            m.close()
 
 
 # ---- 3. the anchor ---------------------------------------------------------------------------------------------------------------------

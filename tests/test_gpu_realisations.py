@@ -106,6 +106,60 @@ def test_selection_equals_the_host_build(host, K):
             assert np.all(count == 0) and np.all(index == -1)
 
 
+def check_handle_against_standalone(sel, sd, standalone, K):
+    """A seed set's select() (sel; sd: its scales' seeds()) against standalone(s), the stand-alone selection of scale s's seeds under the
+    same measurements: index, score and count bit for bit, and the cube points gathered from the selected seeds, NaN behind the count."""
+    for s in range(len(sd)):
+        index, score, count = standalone(s)
+        assert np.array_equal(sel["index"][s], index) and H.same_bits(sel["score"][s], score) and np.array_equal(sel["count"][s], count), s
+        have = np.arange(K)[None, :] < count[:, None]
+        assert np.array_equal(index >= 0, have) and np.all(index[~have] == -1) and np.all(score[~have] == -np.inf)
+        assert H.same_bits(sel["cube"][s][have], sd[s]["cube"][index[have]]) and np.isnan(sel["cube"][s][~have]).all(), s
+
+
+@pytest.mark.parametrize("K", [1, 5])
+def test_handle_selection_equals_the_standalone_selection(oeu_scale, K):
+    """The two routes through the selection: ToySeeds.select over two scales, with shared and with per-scale measurements, against
+    toy_select per scale on that scale's seeds() arrays and the set's offset.  CHUNK + 1 seeds are two parts of the seed range, the second
+    of one seed; 65 realisations are two workgroups of the select kernel, the second with one live lane.  The last two realisations are
+    narrow: one leaves scale 0 a few finite seeds, the other leaves no scale any."""
+    args = sens_args(texture=Texture.OEU, smearing=0.05)
+    asimov, ps = Cf.sens_paramsets(6, (1., 1., 1.))
+    M, T, sm = CHUNK + 1, 65, 0.008
+    cols, models, bases, _ = nested._scan_models(args, asimov, ps, np.array([oeu_scale - 0.5, oeu_scale]), 0.05, 0)
+    try:
+        off = float(getattr(models[0], "model", models[0]).desc.offset)
+        with R.ToySeeds(models, cols, bases, nseed=M, seed=11) as seeds:
+            sd = [seeds.seeds(s) for s in range(2)]
+            fr = sd[0]["fr"][sd[0]["status"] == _lib.GF_ST_OK]
+            mh, k = H.gauss_consts(sm)
+            centre, u = fr.mean(axis=0), np.array([1., -1., 0.]) / np.sqrt(2.)
+            # a measurement centre + D u leaves seed i above the underflow wall (-1075 ln 2) exactly when D < cross_i, for D of that size
+            q = (fr - centre) @ u
+            with np.errstate(invalid="ignore"):
+                cross = q + np.sqrt((-745.1332191019411 - k) / mh - (np.sum((fr - centre) ** 2, axis=1) - q * q))
+            cross = np.sort(cross[np.isfinite(cross)])
+            few = 0.5 * (cross[-4] + cross[-3])
+            sms = np.full(T, 0.05)
+            sms[-2:] = sm
+            shared = R.draw_realisations(model_bf(asimov), 0.05, T, seed=21)
+            shared[-2:] = centre + few * u, centre + 2.0 * u
+            other = R.draw_realisations(model_bf(asimov), 0.05, T, seed=22)
+            other[-1] = centre + 2.0 * u
+            for meas in (shared, np.stack([shared, other])):
+                sel = seeds.select(meas, sms, K)
+                assert sel["cube"].shape == (2, T, K, len(cols))
+                check_handle_against_standalone(sel, sd, lambda s: R.toy_select(sd[s]["lp"], sd[s]["fr"], sd[s]["status"],
+                                                                                meas[s] if meas.ndim == 3 else meas, sms, off, K), K)
+                print("K = %d, %s measurements: counts of the narrow realisations %s" % (K, "per-scale" if meas.ndim == 3 else "shared",
+                                                                                         sel["count"][:, -2:].tolist()))
+                # conditions on the inputs: full lists, a list cut short by the wall, and empty ones
+                assert np.any(sel["count"] == K) and sel["count"][0, -2] == min(K, 3) and np.all(sel["count"][:, -1] == 0)
+    finally:
+        for m in models:
+            m.close()
+
+
 # ---- 2. the score ----------------------------------------------------------------------------------------------------------------------
 def check_scores(seeds, make_model, meas, sms, what):
     """seeds: a ToySeeds of one scale.  scores[t] against the bulk lnprob of a model compiled with (meas[t], sms[t]) at the seeds' theta,

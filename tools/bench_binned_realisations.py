@@ -3,7 +3,7 @@ the sens.py frequentist scan at its defaults with --energy-resolved (d = 6, text
 per scale, scipy's tolerances, one restart, adaptive coefficients): T realisations, K starts each, against what it replaces -- one
 profile_scan(binned=realisation) per realisation at the same K and seed points, each drawing and propagating its own seeds
 (--parent-toys realisations of it; its seconds per realisation are what compares).  Also the seeding, the selection call
-(k_toyb_select, k_toyb_merge and the copies of its inputs and outputs; repeated --select-repeats times) and the polish on their own.
+(k_toyb_select, k_toy_merge and the copies of its inputs and outputs; repeated --select-repeats times) and the polish on their own.
 Host clocks around synchronous calls; the first scan is a warm-up.  One JSON line; --out also writes it to a file
 (profiles/binned_realisations/)."""
 import argparse
