@@ -81,7 +81,7 @@ const char* gf_strerror(int err)
 
 const char* gf_last_hip_error(void) { return g_err; }
 
-// internal (gf_sampler.hip, gf_comm.hip): one thread-local error text for the whole library
+// internal (gf_sampler_host.hip, gf_comm.hip): one thread-local error text for the whole library
 void gf_internal_set_error(const char* msg) { std::snprintf(g_err, sizeof(g_err), "%s", msg ? msg : ""); }
 
 size_t gf_sizeof_model_desc(void) { return sizeof(gf_model_desc); }

@@ -2,7 +2,10 @@
 // gf_model) over the unit cube of its scanned columns: theta_i = (hi_i - lo_i) u_i + lo_i there (mn.py:35-39, the product and
 // the sum each rounded), the run's base value on every other column.  Random numbers: Philox4x32-10, key = seed, counter =
 // (run id, iteration word, point, step): a run's result does not depend on the other runs of the launch or on the launch shape.
+// The runs' models, their per-model device arrays and the likelihood they carry are a GfModelSet (gf_modelset.h), the layer the
+// ensemble sampler builds on too; what is the cube runs' own -- slot map, bases, run ids, step state -- is here.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <cstddef>
@@ -11,6 +14,7 @@
 #include <vector>
 
 #include "gf_host.h"
+#include "gf_modelset.h"
 #include "gf_propose.hpp"
 
 // the kernels' view: NsArgs and SxArgs start with it
@@ -30,20 +34,11 @@ struct GfCubeRuns {
     int32_t nruns, nbins_max, ndim, nscan;     // last: a kernel loads nscan with the counters that follow it (k_sx_pick)
 };
 
-// the host's: the models, their stream, and the buffers behind GfCubeRuns and the settle kernel's arguments
+// the host's: the runs' models as a set (gf_modelset.h: model r is run r's; its stream carries every launch, its kind picks the
+// kernels' instance), and the buffers behind the rest of GfCubeRuns and the settle kernel's arguments
 struct GfCubeRunsHost {
-    gf_model** models = nullptr;        // [nruns]; models[0]'s stream carries every launch
-    hipStream_t stream = nullptr;
-    int device = 0, cus = 256, mode = 0;
-    int binned = 0;                     // every run's model carries a binned measurement: the kernels' MODE_BSM_BINNED instance
-    int table = 0;                      // every run's model carries a tabulated likelihood: the MODE_BSM_TABLE instance
+    GfModelSet set;
     int initialised = 0;
-    GfCommon* d_commons = nullptr;
-    const GfBsm** d_tbs = nullptr;
-    const double** d_ptabs = nullptr;
-    const double** d_btabs = nullptr;
-    const double** d_ttabs = nullptr;
-    int32_t* d_tsides = nullptr;
     double* d_btab_runs = nullptr;      // cube_runs_set_binned_measurements: [nruns][nbins][GF_BINNED_STRIDE], the runs' own tables
     uint64_t* d_run_ids = nullptr;
     double* d_bases = nullptr;
@@ -139,117 +134,86 @@ hipError_t launch_points(Kernel kernel, const Args& a, int lpw, int64_t points, 
     return hipGetLastError();
 }
 
-// the shared buffers and the model list; the stream is synchronised first
+// the shared buffers and the model set; the stream is synchronised first
 void cube_runs_free(GfCubeRunsHost& h, GfCubeRuns& a)
 {
-    (void)hipSetDevice(h.device);
-    if (h.stream) (void)hipStreamSynchronize(h.stream);
-    void* ptrs[] = {h.d_commons, (void*)h.d_tbs, (void*)h.d_ptabs, (void*)h.d_btabs, (void*)h.d_ttabs, h.d_tsides, h.d_btab_runs, h.d_run_ids, h.d_bases, h.d_state, h.d_ctl, a.pq, a.pend_rows};
+    gf_modelset_free(&h.set);
+    void* ptrs[] = {h.d_btab_runs, h.d_run_ids, h.d_bases, h.d_state, h.d_ctl, a.pq, a.pend_rows};
     for (void* p : ptrs) if (p) (void)hipFree(p);
-    h.d_commons = nullptr; h.d_tbs = nullptr; h.d_ptabs = nullptr; h.d_btabs = nullptr; h.d_ttabs = nullptr; h.d_tsides = nullptr; h.d_btab_runs = nullptr; h.d_run_ids = nullptr; h.d_bases = nullptr;
+    h.d_btab_runs = nullptr; h.d_run_ids = nullptr; h.d_bases = nullptr;
     h.d_state = nullptr; h.d_ctl = nullptr; a.pq = nullptr; a.pend_rows = nullptr;
-    delete[] h.models;
-    h.models = nullptr;
 }
 
-// Validates the models against models[0] (device, ndim, mode; `who` names the call in the error), builds the slot map of
-// `cols`, and uploads every run's constants: fills `a` but pq and pend_rows.  On failure nothing stays allocated.
+// The runs' model set (every model shares device, ndim and mode with models[0], and all of them carry a binned measurement / a
+// tabulated likelihood, or none; `who` names the call in the error), the slot map of `cols`, and every run's id, base and step
+// state: fills `a` but pq and pend_rows.  On failure nothing stays allocated.
 int cube_runs_create(GfCubeRunsHost& h, GfCubeRuns& a, gf_model* const* models, int nruns, int nscan, const int32_t* cols,
                      const double* bases, uint64_t seed, const char* who)
 {
-    const GfCommon* c0; const GfBsm* tb0; const double* pt0; void* stream0; int device0;
-    if (!models[0] || gf_model_internal(models[0], &c0, &tb0, &pt0, &stream0, &device0) != GF_OK) return GF_ERR_INVALID_ARG;
-    const int ndim = c0->ndim;
-    std::vector<int32_t> slot(GF_MAX_DIM, -1);
-    for (int k = 0; k < nscan; ++k) {
-        if (cols[k] < 0 || cols[k] >= ndim || slot[cols[k]] >= 0) return GF_ERR_INVALID_ARG;
-        slot[cols[k]] = k;
+    const GfModelSet& set = h.set;
+    int rc = gf_modelset_create(&h.set, models, nruns, who);
+    const int ndim = set.ndim;
+    for (int d = 0; d < GF_MAX_DIM; ++d) a.slot[d] = -1;
+    bool cols_ok = ndim > 0;                                              // (0: models[0] is unusable)
+    for (int k = 0; k < nscan && cols_ok; ++k) {
+        cols_ok = cols[k] >= 0 && cols[k] < ndim && a.slot[cols[k]] < 0;
+        if (cols_ok) a.slot[cols[k]] = k;
     }
-    std::vector<GfCommon> hc(nruns);
-    std::vector<const GfBsm*> htb(nruns);
-    std::vector<const double*> hpt(nruns), hbt(nruns), htt(nruns);
-    std::vector<int32_t> hts(nruns);
-    int nbinned = 0, ntable = 0;
-    std::vector<double> hb((size_t)nruns * GF_MAX_DIM, 0.0);
-    int cus = 256, nbins_max = 0;
-    for (int r = 0; r < nruns; ++r) {
-        const GfCommon* c; int device, nb;
-        if (!models[r] || gf_model_constants(models[r], &c, &htb[r], &hpt[r], &device, &cus, &nb) != GF_OK || device != device0 ||
-            c->ndim != ndim || c->mode != c0->mode)
-            return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: every model must share device, ndim and mode with model 0", who);
-        hc[r] = *c;
-        nbinned += gf_model_binned(models[r], &hbt[r]);
-        hts[r] = gf_model_table(models[r], &htt[r]);
-        ntable += hts[r] > 0;
-        if (nb > nbins_max) nbins_max = nb;
-        for (int d = 0; d < ndim; ++d) hb[(size_t)r * GF_MAX_DIM + d] = bases[(size_t)r * ndim + d];
+    if (!cols_ok) rc = GF_ERR_INVALID_ARG;
+    else if (set.differs >= 0) rc = gf_fail_msg(GF_ERR_INVALID_ARG, "%s: every model must share device, ndim and mode with model 0", who);
+    else if (set.kind == GF_LLH_MIXED) {
+        const int nbinned = (int)std::count(set.carries.begin(), set.carries.end(), (int)GF_LLH_BINNED);
+        const int ntable = (int)std::count(set.carries.begin(), set.carries.end(), (int)GF_LLH_TABLE);
+        rc = nbinned ? gf_fail_msg(GF_ERR_INVALID_ARG, "%s: %d of the %d models carry a binned measurement; all of a set must, or none", who, nbinned, nruns)
+                     : gf_fail_msg(GF_ERR_INVALID_ARG, "%s: %d of the %d models carry a tabulated likelihood; all of a set must, or none", who, ntable, nruns);
     }
-    if (nbinned != 0 && nbinned != nruns)
-        return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: %d of the %d models carry a binned measurement; all of a set must, or none", who, nbinned, nruns);
-    if (ntable != 0 && ntable != nruns)
-        return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: %d of the %d models carry a tabulated likelihood; all of a set must, or none", who, ntable, nruns);
-    h.models = new (std::nothrow) gf_model*[nruns];
-    if (!h.models) return GF_ERR_ALLOC;
-    for (int r = 0; r < nruns; ++r) h.models[r] = models[r];
-    h.stream = (hipStream_t)stream0; h.device = device0; h.cus = cus; h.mode = c0->mode; h.binned = nbinned != 0; h.table = ntable != 0;
+    if (rc != GF_OK) { cube_runs_free(h, a); return rc; }
     a.seed = seed;
-    a.nruns = nruns; a.nscan = nscan; a.ndim = ndim; a.nbins_max = nbins_max;
-    for (int d = 0; d < GF_MAX_DIM; ++d) a.slot[d] = slot[d];
+    a.nruns = nruns; a.nscan = nscan; a.ndim = ndim; a.nbins_max = set.nbins_max;
     const size_t R = nruns;
+    std::vector<double> hb(R * GF_MAX_DIM, 0.0);
+    for (size_t r = 0; r < R; ++r)
+        for (int d = 0; d < ndim; ++d) hb[r * GF_MAX_DIM + d] = bases[r * ndim + d];
     std::vector<uint64_t> ids(R);
     for (size_t r = 0; r < R; ++r) ids[r] = r;
-    GfStepState hs;
-    std::memset(&hs, 0, sizeof(hs));
+    GfStepState hs = {};
     hs.thin = 1;
-    hipError_t e = hipSetDevice(device0);
-    auto al = [&](void** p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes); };
-    auto up = [&](void* dst, const void* src, size_t bytes) { if (e == hipSuccess) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h.stream); };
-    al((void**)&h.d_commons, sizeof(GfCommon) * R);
-    al((void**)&h.d_tbs, sizeof(void*) * R);
-    al((void**)&h.d_ptabs, sizeof(void*) * R);
-    if (h.binned) al((void**)&h.d_btabs, sizeof(void*) * R);
-    if (h.table) { al((void**)&h.d_ttabs, sizeof(void*) * R); al((void**)&h.d_tsides, sizeof(int32_t) * R); }
-    al((void**)&h.d_run_ids, sizeof(uint64_t) * R);
-    al((void**)&h.d_bases, sizeof(double) * R * GF_MAX_DIM);
-    al((void**)&h.d_state, sizeof(GfStepState));
-    up(h.d_commons, hc.data(), sizeof(GfCommon) * R);
-    up((void*)h.d_tbs, htb.data(), sizeof(void*) * R);
-    up((void*)h.d_ptabs, hpt.data(), sizeof(void*) * R);
-    if (h.binned) up((void*)h.d_btabs, hbt.data(), sizeof(void*) * R);
-    if (h.table) { up((void*)h.d_ttabs, htt.data(), sizeof(void*) * R); up(h.d_tsides, hts.data(), sizeof(int32_t) * R); }
-    up(h.d_run_ids, ids.data(), sizeof(uint64_t) * R);
-    up(h.d_bases, hb.data(), sizeof(double) * R * GF_MAX_DIM);
-    up(h.d_state, &hs, sizeof(hs));
-    if (e == hipSuccess) e = hipStreamSynchronize(h.stream);              // the host vectors go out of scope
-    if (e != hipSuccess) { const int rc = gf_hip_fail(e, who); cube_runs_free(h, a); return rc; }
-    a.commons = h.d_commons; a.tbs = h.d_tbs; a.ptabs = h.d_ptabs; a.btabs = h.d_btabs; a.ttabs = h.d_ttabs; a.tsides = h.d_tsides; a.run_ids = h.d_run_ids; a.bases = h.d_bases;
+    hipError_t e = hipSetDevice(set.device);
+    auto put = [&](void** d, const void* src, size_t bytes) {
+        if (e == hipSuccess) e = hipMalloc(d, bytes);
+        if (e == hipSuccess) e = hipMemcpyAsync(*d, src, bytes, hipMemcpyHostToDevice, set.stream);
+    };
+    put((void**)&h.d_run_ids, ids.data(), sizeof(uint64_t) * R);
+    put((void**)&h.d_bases, hb.data(), sizeof(double) * R * GF_MAX_DIM);
+    put((void**)&h.d_state, &hs, sizeof(hs));
+    if (e == hipSuccess) e = hipStreamSynchronize(set.stream);            // the host vectors go out of scope
+    if (e != hipSuccess) { rc = gf_hip_fail(e, who); cube_runs_free(h, a); return rc; }
+    a.commons = set.d_commons; a.tbs = set.d_tbs; a.ptabs = set.d_ptabs; a.btabs = set.d_btabs; a.ttabs = set.d_ttabs; a.tsides = set.d_tsides;
+    a.run_ids = h.d_run_ids; a.bases = h.d_bases;
     return GF_OK;
 }
 
 // BSM: the arbitration queue for `w` proposals a step, their pend rows and the settle kernel's counters, all empty
 hipError_t cube_runs_alloc_queue(GfCubeRunsHost& h, GfCubeRuns& a, size_t w)
 {
-    if (h.mode != MODE_BSM_GAUSS) return hipSuccess;
-    return gf_alloc_arb_queue(w, h.stream, &a.pq, &a.pend_rows, &h.d_ctl);
+    if (h.set.mode != MODE_BSM_GAUSS) return hipSuccess;
+    return gf_alloc_arb_queue(w, h.set.stream, &a.pq, &a.pend_rows, &h.d_ctl);
 }
 
 // the settle kernel's arguments common to both variants: run r is its chain r, `nwalkers` / 2 proposals each
-// the MODE of the evaluation kernels' instance: the models' mode, MODE_BSM_BINNED for a binned set, MODE_BSM_TABLE for a table set
-inline int cube_runs_eval_mode(const GfCubeRunsHost& h) { return h.table ? MODE_BSM_TABLE : h.binned ? MODE_BSM_BINNED : h.mode; }
-
 void cube_runs_settle_args(const GfCubeRunsHost& h, const GfCubeRuns& a, int nwalkers, GfSettleArgs& sa)
 {
     sa.state = h.d_state; sa.pq = a.pq; sa.pend_rows = a.pend_rows; sa.ctl = h.d_ctl;
-    sa.nchains = a.nruns; sa.nwalkers = nwalkers; sa.ndim = a.ndim; sa.commons = h.d_commons; sa.tbs = h.d_tbs; sa.multi = 1;
+    sa.nchains = a.nruns; sa.nwalkers = nwalkers; sa.ndim = a.ndim; sa.commons = h.set.d_commons; sa.tbs = h.set.d_tbs; sa.multi = 1;
 }
 
 // the Philox streams of the runs; `late` is the error before the first run
 int cube_runs_set_ids(GfCubeRunsHost& h, const GfCubeRuns& a, const uint64_t* ids, const char* late)
 {
     if (h.initialised) return gf_fail_msg(GF_ERR_INVALID_ARG, "%s", late);
-    GF_HIP(hipSetDevice(h.device));
-    GF_HIP(hipMemcpyAsync(h.d_run_ids, ids, sizeof(uint64_t) * (size_t)a.nruns, hipMemcpyHostToDevice, h.stream));
-    GF_HIP(hipStreamSynchronize(h.stream));
+    GF_HIP(hipSetDevice(h.set.device));
+    GF_HIP(hipMemcpyAsync(h.d_run_ids, ids, sizeof(uint64_t) * (size_t)a.nruns, hipMemcpyHostToDevice, h.set.stream));
+    GF_HIP(hipStreamSynchronize(h.set.stream));
     return GF_OK;
 }
 
@@ -260,12 +224,12 @@ int cube_runs_set_ids(GfCubeRunsHost& h, const GfCubeRuns& a, const uint64_t* id
 int cube_runs_set_measurements(GfCubeRunsHost& h, const GfCubeRuns& a, const double* bf, const double* smearing, const char* who)
 {
     if (h.initialised) return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: before the first run", who);
-    if (h.table)
+    if (h.set.kind == GF_LLH_TABLE)
         return gf_fail_msg(GF_ERR_UNSUPPORTED, "%s: the runs' models carry a tabulated likelihood, which has no Gaussian measurement to replace", who);
-    if (h.binned)
+    if (h.set.kind == GF_LLH_BINNED)
         return gf_fail_msg(GF_ERR_UNSUPPORTED, "%s: the runs' models carry a binned measurement; a run's own measurement replaces the flux-averaged one only", who);
-    if (h.mode != MODE_SM_GAUSS && h.mode != MODE_BSM_GAUSS)
-        return gf_fail_msg(GF_ERR_UNSUPPORTED, "%s: the models have no Gaussian measurement (mode %d)", who, h.mode);
+    if (h.set.mode != MODE_SM_GAUSS && h.set.mode != MODE_BSM_GAUSS)
+        return gf_fail_msg(GF_ERR_UNSUPPORTED, "%s: the models have no Gaussian measurement (mode %d)", who, h.set.mode);
     const size_t R = a.nruns;
     std::vector<GfCommon> hc(R);
     for (size_t r = 0; r < R; ++r) {
@@ -273,7 +237,7 @@ int cube_runs_set_measurements(GfCubeRunsHost& h, const GfCubeRuns& a, const dou
         if (!(sm > 0.0) || !std::isfinite(sm) || !std::isfinite(bf[3 * r]) || !std::isfinite(bf[3 * r + 1]) || !std::isfinite(bf[3 * r + 2]))
             return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: run %zu needs a finite measurement and a smearing > 0", who, r);
         const GfCommon* c; const GfBsm* tb; const double* pt; int device, cus, nb;
-        const int rc = gf_model_constants(h.models[r], &c, &tb, &pt, &device, &cus, &nb);
+        const int rc = gf_model_constants(h.set.models[r], &c, &tb, &pt, &device, &cus, &nb);
         if (rc != GF_OK) return rc;
         hc[r] = *c;
         for (int k = 0; k < 3; ++k) hc[r].bf[k] = bf[3 * r + k];
@@ -281,9 +245,9 @@ int cube_runs_set_measurements(GfCubeRunsHost& h, const GfCubeRuns& a, const dou
         if (!std::isfinite(hc[r].gauss_mh) || !std::isfinite(hc[r].gauss_k))
             return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: the smearing of run %zu is outside the range of the Gaussian's constants", who, r);
     }
-    GF_HIP(hipSetDevice(h.device));
-    GF_HIP(hipMemcpyAsync(h.d_commons, hc.data(), sizeof(GfCommon) * R, hipMemcpyHostToDevice, h.stream));
-    GF_HIP(hipStreamSynchronize(h.stream));                              // hc goes out of scope
+    GF_HIP(hipSetDevice(h.set.device));
+    GF_HIP(hipMemcpyAsync(h.set.d_commons, hc.data(), sizeof(GfCommon) * R, hipMemcpyHostToDevice, h.set.stream));
+    GF_HIP(hipStreamSynchronize(h.set.stream));                              // hc goes out of scope
     return GF_OK;
 }
 
@@ -295,14 +259,14 @@ int cube_runs_set_binned_measurements(GfCubeRunsHost& h, const GfCubeRuns& a, in
                                       const char* who)
 {
     if (h.initialised) return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: before the first run", who);
-    if (h.table)
+    if (h.set.kind == GF_LLH_TABLE)
         return gf_fail_msg(GF_ERR_UNSUPPORTED, "%s: the runs' models carry a tabulated likelihood, which has no binned measurement to replace", who);
-    if (!h.binned)
+    if (h.set.kind != GF_LLH_BINNED)
         return gf_fail_msg(GF_ERR_UNSUPPORTED, "%s: the runs' models carry no binned measurement; a run's own binned measurement replaces a model's", who);
     const size_t R = a.nruns, nb = nbins > 0 ? nbins : 0;
     for (size_t r = 0; r < R; ++r) {
         const GfCommon* c; const GfBsm* tb; const double* pt; int device, cus, mnb;
-        const int rc = gf_model_constants(h.models[r], &c, &tb, &pt, &device, &cus, &mnb);
+        const int rc = gf_model_constants(h.set.models[r], &c, &tb, &pt, &device, &cus, &mnb);
         if (rc != GF_OK) return rc;
         if (nbins != mnb) return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: %d bins given, the model of run %zu has %d", who, nbins, r, mnb);
     }
@@ -321,12 +285,12 @@ int cube_runs_set_binned_measurements(GfCubeRunsHost& h, const GfCubeRuns& a, in
             if (!std::isfinite(t[3]) || !std::isfinite(t[4]))
                 return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: the width of bin %zu of run %zu is outside the range of the Gaussian's constants", who, k, r);
         }
-    GF_HIP(hipSetDevice(h.device));
+    GF_HIP(hipSetDevice(h.set.device));
     if (!h.d_btab_runs) GF_HIP(hipMalloc((void**)&h.d_btab_runs, sizeof(double) * tab.size()));
     for (size_t r = 0; r < R; ++r) hbt[r] = h.d_btab_runs + r * nb * GF_BINNED_STRIDE;
-    GF_HIP(hipMemcpyAsync(h.d_btab_runs, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, h.stream));
-    GF_HIP(hipMemcpyAsync((void*)h.d_btabs, hbt.data(), sizeof(void*) * R, hipMemcpyHostToDevice, h.stream));
-    GF_HIP(hipStreamSynchronize(h.stream));                              // the host vectors go out of scope
+    GF_HIP(hipMemcpyAsync(h.d_btab_runs, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, h.set.stream));
+    GF_HIP(hipMemcpyAsync((void*)h.set.d_btabs, hbt.data(), sizeof(void*) * R, hipMemcpyHostToDevice, h.set.stream));
+    GF_HIP(hipStreamSynchronize(h.set.stream));                              // the host vectors go out of scope
     return GF_OK;
 }
 
@@ -336,10 +300,10 @@ int cube_runs_draw(const GfCubeRunsHost& h, const GfCubeRuns& a, uint32_t it, in
                    int32_t* status)
 {
     const dim3 grid((unsigned)((n + GF_BLOCK - 1) / GF_BLOCK), a.nruns);
-    hipLaunchKernelGGL(k_cube_draw, grid, dim3(GF_BLOCK), 0, h.stream, a, it, n, u, theta);
+    hipLaunchKernelGGL(k_cube_draw, grid, dim3(GF_BLOCK), 0, h.set.stream, a, it, n, u, theta);
     GF_HIP(hipGetLastError());
     for (int r = 0; r < a.nruns; ++r) {
-        const int rc = gf_model_lnprob_on(h.models[r], h.stream, theta + (size_t)r * n * a.ndim, GF_LAYOUT_AOS, n,
+        const int rc = gf_model_lnprob_on(h.set.models[r], h.set.stream, theta + (size_t)r * n * a.ndim, GF_LAYOUT_AOS, n,
                                           lnl + (size_t)r * n, nullptr, status + (size_t)r * n);
         if (rc != GF_OK) return rc;
     }

@@ -1,4 +1,4 @@
-// Host pieces shared by the C ABI of the device samplers, of chain post-processing and of read-back (gf_sampler.hip, gf_postprocess.hip,
+// Host pieces shared by the C ABI of the device samplers, of chain post-processing and of read-back (gf_sampler_host.hip, gf_modelset.hip, gf_postprocess.hip,
 // gf_readback.hip, gf_nested.hip, gf_nested_post.hip, gf_reweight.hip, gf_simplex.hip, gf_region.hip, gf_marginal.hip, gf_elements.hip):
 // the library's internal functions (gf_internal.h), the error helpers that publish a message through gf_last_hip_error(), the holder
 // of a call's scratch buffers with the way an entry point reports a refused request of its own (GfScratch::take), and the allocation

@@ -40,6 +40,11 @@ int gf_model_propagate_on(gf_model* m, void* stream, const double* d_theta, int 
 int gf_model_bins_on(gf_model* m, void* stream, const double* d_theta, int layout, int64_t n, double* d_fr_bins, int bin_major,
                      const int32_t* d_status);
 
+// what a model's lnprob evaluates beside the prior: the flux-averaged likelihood of its mode, a measurement per energy bin
+// (gf_model_binned) or a tabulated flavour-plane likelihood (gf_model_table); a model carries one.  GF_LLH_MIXED: the models of a
+// refused set (gf_modelset.h) carry different ones.
+enum GfLikelihood { GF_LLH_MIXED = -1, GF_LLH_FLUX = 0, GF_LLH_BINNED = 1, GF_LLH_TABLE = 2 };
+
 // gf_pool.hip
 // streams of the device's pool (copy stream: for a large read-back that overlaps another stream's kernels); returned idle
 int gf_internal_borrow_stream(int device, void** stream);
@@ -66,8 +71,8 @@ void gf_internal_copy_rows(char* dst, size_t dpitch, const char* src, size_t wid
 // release the pinned slots of `device`'s ring unless a read-back holds it (gf_device_trim)
 void gf_internal_d2h_ring_trim(int device);
 
-// gf_sampler.hip
-struct GfChainView {              // the stored chain of a sampler, as post-processing (gf_postprocess.hip) sees it
+// gf_sampler_host.hip
+struct GfChainView {            // the stored chain of a sampler, as post-processing (gf_postprocess.hip) sees it
     int device; hipStream_t stream; int cus;
     int nchains, nwalkers, ndim;
     int64_t nstored, nstore_cap;
@@ -78,10 +83,11 @@ struct GfChainView {              // the stored chain of a sampler, as post-proc
     const uint64_t* d_stream_ids; // [nchains] the chains' random stream ids, NULL: chain ch has id ch
 };
 int gf_internal_sampler_chain_view(const gf_sampler* s, GfChainView* v);
-// 1 for a sampler of the energy-resolved likelihood (gf_sampler_create_binned), else 0
-int gf_internal_sampler_binned(const gf_sampler* s);
-// 1 for a sampler of the tabulated flavour-plane likelihood (gf_sampler_create_table), else 0
-int gf_internal_sampler_table(const gf_sampler* s);
+// the likelihood the sampler evaluates: GF_LLH_BINNED for gf_sampler_create_binned's, GF_LLH_TABLE for gf_sampler_create_table's, else
+// GF_LLH_FLUX
+int gf_internal_sampler_likelihood(const gf_sampler* s);
+
+// gf_sampler.hip
 // k_walker_mean on `stream`: chain [nchains][cap][nwalkers][ndim] -> mean [nchains][nstored][ndim], the ensemble mean of every step
 hipError_t gf_launch_walker_mean(const double* d_chain, int64_t cap, int64_t nstored, int nchains, int nwalkers, int ndim, double* d_mean,
                                  hipStream_t stream);

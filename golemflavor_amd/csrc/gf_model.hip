@@ -530,7 +530,7 @@ int gf_model_table(gf_model* m, const double** d_table)
     return ns;
 }
 
-// internal (not in the public header): gf_sampler.hip reaches the model's constants and stream through these
+// internal (not in the public header): gf_modelset.hip reaches the model's constants and stream through these
 int gf_model_internal(gf_model* m, const GfCommon** c, const GfBsm** d_bsm, const double** d_ptab, void** stream, int* device)
 {
     if (!m) return GF_ERR_INVALID_ARG;

@@ -405,10 +405,10 @@ int ns_grow_dead(gf_nested* s, int64_t need)
     GF_HIP(hipMalloc((void**)&w, sizeof(double) * per * cap));
     GF_HIP(hipMalloc((void**)&u, sizeof(double) * per * s->a.nscan * cap));
     if (s->dead_cap > 0) {
-        GF_HIP(hipMemcpyAsync(l, s->a.dead_l, sizeof(double) * per * s->dead_cap, hipMemcpyDeviceToDevice, s->rs.stream));
-        GF_HIP(hipMemcpyAsync(w, s->a.dead_w, sizeof(double) * per * s->dead_cap, hipMemcpyDeviceToDevice, s->rs.stream));
-        GF_HIP(hipMemcpyAsync(u, s->a.dead_u, sizeof(double) * per * s->a.nscan * s->dead_cap, hipMemcpyDeviceToDevice, s->rs.stream));
-        GF_HIP(hipStreamSynchronize(s->rs.stream));
+        GF_HIP(hipMemcpyAsync(l, s->a.dead_l, sizeof(double) * per * s->dead_cap, hipMemcpyDeviceToDevice, s->rs.set.stream));
+        GF_HIP(hipMemcpyAsync(w, s->a.dead_w, sizeof(double) * per * s->dead_cap, hipMemcpyDeviceToDevice, s->rs.set.stream));
+        GF_HIP(hipMemcpyAsync(u, s->a.dead_u, sizeof(double) * per * s->a.nscan * s->dead_cap, hipMemcpyDeviceToDevice, s->rs.set.stream));
+        GF_HIP(hipStreamSynchronize(s->rs.set.stream));
         (void)hipFree(s->a.dead_l); (void)hipFree(s->a.dead_w); (void)hipFree(s->a.dead_u);
     }
     s->a.dead_l = l; s->a.dead_w = w; s->a.dead_u = u;
@@ -423,7 +423,7 @@ int ns_init(gf_nested* s)
     const int rc = cube_runs_draw(s->rs, a, NS_INIT_ITER, a.nlive, a.live_u, a.theta, a.live_l, a.status);
     if (rc != GF_OK) return rc;
     const dim3 grid((unsigned)((a.nlive + GF_BLOCK - 1) / GF_BLOCK), a.nruns);
-    hipLaunchKernelGGL(k_ns_init_fix, grid, dim3(GF_BLOCK), 0, s->rs.stream, a);
+    hipLaunchKernelGGL(k_ns_init_fix, grid, dim3(GF_BLOCK), 0, s->rs.set.stream, a);
     GF_HIP(hipGetLastError());
     s->rs.initialised = 1;
     return GF_OK;
@@ -448,7 +448,7 @@ int gf_nested_create(gf_model* const* models, int nruns, int nscan, const int32_
     a.nlive = nlive; a.batch = batch; a.walks = walks; a.raise = on_nonunitary == 0;
     const size_t R = nruns, K = nlive, B = batch, D = nscan, W = R * B;
     hipError_t e = hipSuccess;
-    hipStream_t st = s->rs.stream;
+    hipStream_t st = s->rs.set.stream;
     auto al = [&](void** p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes); };
     al((void**)&a.runs, sizeof(NsRun) * R);
     al((void**)&a.lstar, sizeof(double) * R);
@@ -514,15 +514,15 @@ void gf_nested_destroy(gf_nested* s)
 int gf_nested_run(gf_nested* s, int64_t max_iter)
 {
     if (!s || max_iter < 1) return GF_ERR_INVALID_ARG;
-    GF_HIP(hipSetDevice(s->rs.device));
+    GF_HIP(hipSetDevice(s->rs.set.device));
     NsArgs& a = s->a;
     if (!s->rs.initialised) { const int rc = ns_init(s); if (rc != GF_OK) return rc; }
-    const int lpw = lanes_per_walker(cube_runs_eval_mode(s->rs), (int64_t)a.nruns * a.batch, a.nbins_max, s->rs.cus, {false, 32 * 1024, "GF_NESTED_LPW"});
+    const int lpw = lanes_per_walker(gf_modelset_eval_mode(&s->rs.set), (int64_t)a.nruns * a.batch, a.nbins_max, s->rs.set.cus, {false, 32 * 1024, "GF_NESTED_LPW"});
     constexpr int check = 4;
     std::vector<NsRun> hr(a.nruns);
     for (;;) {
-        GF_HIP(hipMemcpyAsync(hr.data(), a.runs, sizeof(NsRun) * a.nruns, hipMemcpyDeviceToHost, s->rs.stream));
-        GF_HIP(hipStreamSynchronize(s->rs.stream));
+        GF_HIP(hipMemcpyAsync(hr.data(), a.runs, sizeof(NsRun) * a.nruns, hipMemcpyDeviceToHost, s->rs.set.stream));
+        GF_HIP(hipStreamSynchronize(s->rs.set.stream));
         bool all = true;
         int64_t most = 0;
         for (const NsRun& x : hr) { all = all && x.done; if (!x.done && x.iter > most) most = x.iter; }
@@ -531,14 +531,14 @@ int gf_nested_run(gf_nested* s, int64_t max_iter)
         for (int i = 0; i < check; ++i) {
             const int rc = ns_grow_dead(s, s->launched + 1);
             if (rc != GF_OK) return rc;
-            hipLaunchKernelGGL(k_ns_select, dim3(a.nruns), dim3(NS_SEL_BLOCK), 0, s->rs.stream, a);
+            hipLaunchKernelGGL(k_ns_select, dim3(a.nruns), dim3(NS_SEL_BLOCK), 0, s->rs.set.stream, a);
             GF_HIP(hipGetLastError());
             for (int step = 0; step < a.walks; ++step) {
                 a.step = step;
-                GF_HIP(launch_walk_any(cube_runs_eval_mode(s->rs), lpw, a, s->rs.stream));
-                if (s->rs.mode == MODE_BSM_GAUSS) GF_HIP(gf_launch_nested_settle(s->sa, s->rs.cus, s->rs.stream));
+                GF_HIP(launch_walk_any(gf_modelset_eval_mode(&s->rs.set), lpw, a, s->rs.set.stream));
+                if (s->rs.set.mode == MODE_BSM_GAUSS) GF_HIP(gf_launch_nested_settle(s->sa, s->rs.set.cus, s->rs.set.stream));
             }
-            hipLaunchKernelGGL(k_ns_commit, dim3(a.nruns), dim3(GF_BLOCK), 0, s->rs.stream, a);
+            hipLaunchKernelGGL(k_ns_commit, dim3(a.nruns), dim3(GF_BLOCK), 0, s->rs.set.stream, a);
             GF_HIP(hipGetLastError());
             s->launched += 1;
         }
@@ -550,13 +550,13 @@ int gf_nested_result(gf_nested* s, double* lnz, double* lnz_err, double* info, d
                      uint32_t* nonunitary, int32_t* failed)
 {
     if (!s) return GF_ERR_INVALID_ARG;
-    GF_HIP(hipSetDevice(s->rs.device));
+    GF_HIP(hipSetDevice(s->rs.set.device));
     const int R = s->a.nruns;
     std::vector<NsRun> hr(R);
     std::vector<uint32_t> nu(R);
-    GF_HIP(hipMemcpyAsync(hr.data(), s->a.runs, sizeof(NsRun) * R, hipMemcpyDeviceToHost, s->rs.stream));
-    GF_HIP(hipMemcpyAsync(nu.data(), s->a.nonunit, sizeof(uint32_t) * R, hipMemcpyDeviceToHost, s->rs.stream));
-    GF_HIP(hipStreamSynchronize(s->rs.stream));
+    GF_HIP(hipMemcpyAsync(hr.data(), s->a.runs, sizeof(NsRun) * R, hipMemcpyDeviceToHost, s->rs.set.stream));
+    GF_HIP(hipMemcpyAsync(nu.data(), s->a.nonunit, sizeof(uint32_t) * R, hipMemcpyDeviceToHost, s->rs.set.stream));
+    GF_HIP(hipStreamSynchronize(s->rs.set.stream));
     for (int r = 0; r < R; ++r) {
         const NsRun& x = hr[r];
         if (lnz) lnz[r] = x.lnz;
@@ -576,11 +576,11 @@ int gf_nested_result(gf_nested* s, double* lnz, double* lnz_err, double* info, d
 int gf_internal_nested_state(gf_nested* s, double* scale, double* lnx)
 {
     if (!s) return GF_ERR_INVALID_ARG;
-    GF_HIP(hipSetDevice(s->rs.device));
+    GF_HIP(hipSetDevice(s->rs.set.device));
     const int R = s->a.nruns;
     std::vector<NsRun> hr(R);
-    GF_HIP(hipMemcpyAsync(hr.data(), s->a.runs, sizeof(NsRun) * R, hipMemcpyDeviceToHost, s->rs.stream));
-    GF_HIP(hipStreamSynchronize(s->rs.stream));
+    GF_HIP(hipMemcpyAsync(hr.data(), s->a.runs, sizeof(NsRun) * R, hipMemcpyDeviceToHost, s->rs.set.stream));
+    GF_HIP(hipStreamSynchronize(s->rs.set.stream));
     for (int r = 0; r < R; ++r) {
         if (scale) scale[r] = hr[r].scale;
         if (lnx) lnx[r] = hr[r].lnx;
@@ -593,19 +593,19 @@ int gf_internal_nested_view(gf_nested* s, GfNestedView* v, GfNestedRunState* sta
 {
     if (!s || !v) return GF_ERR_INVALID_ARG;
     const NsArgs& a = s->a;
-    v->device = s->rs.device; v->stream = s->rs.stream; v->cus = s->rs.cus;
+    v->device = s->rs.set.device; v->stream = s->rs.set.stream; v->cus = s->rs.set.cus;
     v->nruns = a.nruns; v->nlive = a.nlive; v->batch = a.batch; v->nscan = a.nscan; v->ndim = a.ndim;
     v->seed = a.seed;
     for (int d = 0; d < GF_MAX_DIM; ++d) v->slot[d] = a.slot[d];
     v->d_commons = a.commons; v->d_bases = a.bases; v->d_run_ids = a.run_ids;
     v->d_dead_l = a.dead_l; v->d_dead_w = a.dead_w; v->d_dead_u = a.dead_u;
     v->d_live_l = a.live_l; v->d_live_u = a.live_u;
-    v->models = s->rs.models;
+    v->models = s->rs.set.models.data();
     if (!state) return GF_OK;
-    GF_HIP(hipSetDevice(s->rs.device));
+    GF_HIP(hipSetDevice(s->rs.set.device));
     std::vector<NsRun> hr(a.nruns);
-    GF_HIP(hipMemcpyAsync(hr.data(), a.runs, sizeof(NsRun) * a.nruns, hipMemcpyDeviceToHost, s->rs.stream));
-    GF_HIP(hipStreamSynchronize(s->rs.stream));
+    GF_HIP(hipMemcpyAsync(hr.data(), a.runs, sizeof(NsRun) * a.nruns, hipMemcpyDeviceToHost, s->rs.set.stream));
+    GF_HIP(hipStreamSynchronize(s->rs.set.stream));
     for (int r = 0; r < a.nruns; ++r) {
         const NsRun& x = hr[r];
         state[r].iter = x.iter; state[r].lnx = x.lnx; state[r].lnz = x.lnz;
@@ -620,11 +620,11 @@ int gf_internal_nested_view(gf_nested* s, GfNestedView* v, GfNestedRunState* sta
 int gf_nested_get_dead(gf_nested* s, int run, int64_t cap, double* lnl, double* lnw, double* cube, int64_t* n)
 {
     if (!s || !n || run < 0 || run >= s->a.nruns) return GF_ERR_INVALID_ARG;
-    GF_HIP(hipSetDevice(s->rs.device));
+    GF_HIP(hipSetDevice(s->rs.set.device));
     const NsArgs& a = s->a;
     NsRun x;
-    GF_HIP(hipMemcpyAsync(&x, a.runs + run, sizeof(NsRun), hipMemcpyDeviceToHost, s->rs.stream));
-    GF_HIP(hipStreamSynchronize(s->rs.stream));
+    GF_HIP(hipMemcpyAsync(&x, a.runs + run, sizeof(NsRun), hipMemcpyDeviceToHost, s->rs.set.stream));
+    GF_HIP(hipStreamSynchronize(s->rs.set.stream));
     const int64_t nd = x.iter * a.batch, total = nd + a.nlive;
     *n = total;
     if (!lnl && !lnw && !cube) return GF_OK;
@@ -632,16 +632,16 @@ int gf_nested_get_dead(gf_nested* s, int run, int64_t cap, double* lnl, double* 
     const size_t B = a.batch, D = a.nscan, R = a.nruns;
     for (int64_t it = 0; it < x.iter; ++it) {
         const size_t off = ((size_t)it * R + run) * B;
-        if (lnl) GF_HIP(hipMemcpyAsync(lnl + it * B, a.dead_l + off, sizeof(double) * B, hipMemcpyDeviceToHost, s->rs.stream));
-        if (lnw) GF_HIP(hipMemcpyAsync(lnw + it * B, a.dead_w + off, sizeof(double) * B, hipMemcpyDeviceToHost, s->rs.stream));
-        if (cube) GF_HIP(hipMemcpyAsync(cube + it * B * D, a.dead_u + off * D, sizeof(double) * B * D, hipMemcpyDeviceToHost, s->rs.stream));
+        if (lnl) GF_HIP(hipMemcpyAsync(lnl + it * B, a.dead_l + off, sizeof(double) * B, hipMemcpyDeviceToHost, s->rs.set.stream));
+        if (lnw) GF_HIP(hipMemcpyAsync(lnw + it * B, a.dead_w + off, sizeof(double) * B, hipMemcpyDeviceToHost, s->rs.set.stream));
+        if (cube) GF_HIP(hipMemcpyAsync(cube + it * B * D, a.dead_u + off * D, sizeof(double) * B * D, hipMemcpyDeviceToHost, s->rs.set.stream));
     }
     double* ll = lnl ? lnl + nd : (double*)std::malloc(sizeof(double) * a.nlive);
     if (!ll) return GF_ERR_ALLOC;
-    GF_HIP(hipMemcpyAsync(ll, a.live_l + (size_t)run * a.nlive, sizeof(double) * a.nlive, hipMemcpyDeviceToHost, s->rs.stream));
+    GF_HIP(hipMemcpyAsync(ll, a.live_l + (size_t)run * a.nlive, sizeof(double) * a.nlive, hipMemcpyDeviceToHost, s->rs.set.stream));
     if (cube) GF_HIP(hipMemcpyAsync(cube + nd * D, a.live_u + (size_t)run * a.nlive * D, sizeof(double) * a.nlive * D,
-                                     hipMemcpyDeviceToHost, s->rs.stream));
-    const hipError_t e = hipStreamSynchronize(s->rs.stream);
+                                     hipMemcpyDeviceToHost, s->rs.set.stream));
+    const hipError_t e = hipStreamSynchronize(s->rs.set.stream);
     if (e == hipSuccess && lnw)
         for (int k = 0; k < a.nlive; ++k) lnw[nd + k] = x.lnx - std::log((double)a.nlive) + ll[k];
     if (!lnl) std::free(ll);

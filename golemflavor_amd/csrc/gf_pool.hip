@@ -289,7 +289,7 @@ int pool_lease_workspace(int device, hipStream_t st, int layout, int64_t n, GfUn
 
 extern "C" {
 
-// internal: a second stream from the device's pool (gf_sampler.hip: copies that overlap the sampler stream's kernels)
+// internal: a second stream from the device's pool (gf_sampler_host.hip: copies that overlap the sampler stream's kernels)
 int gf_internal_borrow_stream(int device, void** stream) { return borrow(device, stream, pool_stream, "pool_stream"); }
 // internal: a stream for a large read-back that overlaps another stream's kernels (pool_copy_stream: hardware queues of its own)
 int gf_internal_borrow_copy_stream(int device, void** stream) { return borrow(device, stream, pool_copy_stream, "pool_copy_stream"); }
@@ -319,7 +319,7 @@ void gf_internal_full_arbitration_grids(int device, void* stream, int on)
     w->h_seen[1] = on ? 1u : 0u;
 }
 
-// internal (gf_sampler.hip): the overflow report for launches the sampler put on `stream` and has just synchronised
+// internal (gf_sampler_host.hip): the overflow report for launches the sampler put on `stream` and has just synchronised
 int gf_internal_check_overflow(int device, void* stream)
 {
     if (!pool_has(device)) return GF_ERR_INVALID_ARG;

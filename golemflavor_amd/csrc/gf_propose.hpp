@@ -1,6 +1,7 @@
 // Device pieces shared by the ensemble sampler (gf_sampler.hip), the nested sampler (gf_nested.hip) and the maximiser
 // (gf_simplex.hip): the Philox4x32-10 block behind the random streams, the evaluation of one proposal with its unitarity verdict,
-// the parking of an undecided one, and the lanes-per-walker rule of their evaluation kernels.
+// the parking of an undecided one, and the lanes-per-walker rule of their evaluation kernels (host code: gf_sampler_host.hip takes
+// it from here too).
 #pragma once
 #include <cstdlib>
 

@@ -207,10 +207,11 @@ int rw_run(gf_sampler* s, const gf_reweight_spec* spec, const RwWant& want, cons
     int rc = rw_check(v, spec, who);
     if (rc != GF_OK) return rc;
     // measurement targets replace the chain's own Gaussian measurement; a chain sampled under a measurement per energy bin has none
-    if (!spec->models && gf_internal_sampler_binned(s))
+    const int sampled = gf_internal_sampler_likelihood(s);
+    if (!spec->models && sampled == GF_LLH_BINNED)
         return gf_fail_msg(GF_ERR_UNSUPPORTED, "%s: the sampler's chains were sampled under the energy-resolved likelihood, which has no single "
                            "Gaussian measurement to replace; give model targets", who);
-    if (!spec->models && gf_internal_sampler_table(s))
+    if (!spec->models && sampled == GF_LLH_TABLE)
         return gf_fail_msg(GF_ERR_UNSUPPORTED, "%s: the sampler's chains were sampled under a tabulated likelihood, which has no Gaussian measurement "
                            "to replace; give model targets", who);
     const int T = spec->ntargets, nd = v.ndim, nch = v.nchains;

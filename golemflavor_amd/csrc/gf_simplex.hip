@@ -459,10 +459,10 @@ int sx_init(gf_simplex* s)
         const int rc = cube_runs_draw(s->rs, a, SX_SEED_ITER, a.nseed, a.seed_u, a.theta, a.seed_l, a.seed_st);
         if (rc != GF_OK) return rc;
     }
-    hipLaunchKernelGGL(k_sx_pick, dim3(a.nruns), dim3(SX_PICK_BLOCK), 0, s->rs.stream, a);
+    hipLaunchKernelGGL(k_sx_pick, dim3(a.nruns), dim3(SX_PICK_BLOCK), 0, s->rs.set.stream, a);
     GF_HIP(hipGetLastError());
     if (s->d_counts) {
-        hipLaunchKernelGGL(k_sx_trim, dim3(a.nruns), dim3(SX_PICK_BLOCK), 0, s->rs.stream, a, s->d_counts);
+        hipLaunchKernelGGL(k_sx_trim, dim3(a.nruns), dim3(SX_PICK_BLOCK), 0, s->rs.set.stream, a, s->d_counts);
         GF_HIP(hipGetLastError());
     }
     s->rs.initialised = 1;
@@ -496,8 +496,8 @@ int gf_simplex_create(gf_model* const* models, int nruns, int nscan, const int32
     al((void**)&a.seed_l, sizeof(double) * R * M);
     al((void**)&a.seed_st, sizeof(int32_t) * R * M);
     al((void**)&a.theta, sizeof(double) * R * M * a.ndim);
-    if (e == hipSuccess) e = hipMemsetAsync(a.runs, 0, sizeof(SxRun) * R, s->rs.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(s->rs.stream);
+    if (e == hipSuccess) e = hipMemsetAsync(a.runs, 0, sizeof(SxRun) * R, s->rs.set.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->rs.set.stream);
     if (e != hipSuccess) { const int rc2 = gf_hip_fail(e, "gf_simplex_create"); gf_simplex_destroy(s); return rc2; }
     *out = s;
     return GF_OK;
@@ -516,12 +516,12 @@ int gf_simplex_set_starts(gf_simplex* s, int nuser, const double* cube)
     const size_t n = (size_t)s->a.nruns * nuser * s->a.nscan;
     for (size_t i = 0; i < n; ++i)
         if (!(cube[i] == cube[i])) return gf_fail_msg(GF_ERR_INVALID_ARG, "gf_simplex_set_starts: NaN in a start");
-    GF_HIP(hipSetDevice(s->rs.device));
+    GF_HIP(hipSetDevice(s->rs.set.device));
     if (s->d_ustart) { (void)hipFree(s->d_ustart); s->d_ustart = nullptr; }
     if (n > 0) {
         GF_HIP(hipMalloc((void**)&s->d_ustart, sizeof(double) * n));
-        GF_HIP(hipMemcpyAsync(s->d_ustart, cube, sizeof(double) * n, hipMemcpyHostToDevice, s->rs.stream));
-        GF_HIP(hipStreamSynchronize(s->rs.stream));
+        GF_HIP(hipMemcpyAsync(s->d_ustart, cube, sizeof(double) * n, hipMemcpyHostToDevice, s->rs.set.stream));
+        GF_HIP(hipStreamSynchronize(s->rs.set.stream));
     }
     s->a.ustart = s->d_ustart;
     s->a.nuser = nuser;
@@ -532,7 +532,7 @@ int gf_toys_set_measurements(gf_simplex* s, const double* bf, const double* smea
 {
     if (!s || !bf || !smearing) return GF_ERR_INVALID_ARG;
     // the set's own seeding goes through the models' bulk path (cube_runs_draw): it would score under the models' measurement
-    if (s->rs.table)
+    if (s->rs.set.kind == GF_LLH_TABLE)
         return gf_fail_msg(GF_ERR_UNSUPPORTED, "gf_toys_set_measurements: the runs' models carry a tabulated likelihood, which has no Gaussian measurement to replace");
     if (s->a.nseed > 0)
         return gf_fail_msg(GF_ERR_INVALID_ARG, "gf_toys_set_measurements: the set draws %d seed points per run, which its models would score; "
@@ -543,7 +543,7 @@ int gf_toys_set_measurements(gf_simplex* s, const double* bf, const double* smea
 int gf_toys_set_binned_measurements(gf_simplex* s, int nbins, const double* fr_bins, const double* sigma)
 {
     if (!s || !fr_bins || !sigma) return GF_ERR_INVALID_ARG;
-    if (s->rs.table)
+    if (s->rs.set.kind == GF_LLH_TABLE)
         return gf_fail_msg(GF_ERR_UNSUPPORTED, "gf_toys_set_binned_measurements: the runs' models carry a tabulated likelihood, which has no binned measurement to replace");
     // as gf_toys_set_measurements: the set's own seeding would score under the models' measurement
     if (s->a.nseed > 0)
@@ -561,10 +561,10 @@ int gf_toys_set_start_counts(gf_simplex* s, const int32_t* counts)
     for (int r = 0; r < s->a.nruns; ++r)
         if (counts[r] < 0 || counts[r] > s->a.nuser)
             return gf_fail_msg(GF_ERR_INVALID_ARG, "gf_toys_set_start_counts: run %d keeps %d of %d starts", r, counts[r], s->a.nuser);
-    GF_HIP(hipSetDevice(s->rs.device));
+    GF_HIP(hipSetDevice(s->rs.set.device));
     if (!s->d_counts) GF_HIP(hipMalloc((void**)&s->d_counts, sizeof(int32_t) * (size_t)s->a.nruns));
-    GF_HIP(hipMemcpyAsync(s->d_counts, counts, sizeof(int32_t) * (size_t)s->a.nruns, hipMemcpyHostToDevice, s->rs.stream));
-    GF_HIP(hipStreamSynchronize(s->rs.stream));
+    GF_HIP(hipMemcpyAsync(s->d_counts, counts, sizeof(int32_t) * (size_t)s->a.nruns, hipMemcpyHostToDevice, s->rs.set.stream));
+    GF_HIP(hipStreamSynchronize(s->rs.set.stream));
     return GF_OK;
 }
 
@@ -593,7 +593,7 @@ void gf_simplex_destroy(gf_simplex* s)
 int gf_simplex_run(gf_simplex* s, int64_t max_rounds)
 {
     if (!s || max_rounds < 1) return GF_ERR_INVALID_ARG;
-    GF_HIP(hipSetDevice(s->rs.device));
+    GF_HIP(hipSetDevice(s->rs.set.device));
     SxArgs& a = s->a;
     if (!s->rs.initialised) {
         // the per-start buffers are sized once the caller's starts are known
@@ -609,9 +609,9 @@ int gf_simplex_run(gf_simplex* s, int64_t max_rounds)
         al((void**)&a.pts, sizeof(double) * W * N);
         al((void**)&a.lnq, sizeof(double) * W);
         al((void**)&a.pst, sizeof(int32_t) * W);
-        if (e == hipSuccess) e = hipMemsetAsync(a.starts, 0, sizeof(SxStart) * R * S, s->rs.stream);
-        if (e == hipSuccess) e = hipMemsetAsync(a.pst, 0, sizeof(int32_t) * W, s->rs.stream);
-        if (e == hipSuccess) e = hipMemsetAsync(a.lnq, 0, sizeof(double) * W, s->rs.stream);
+        if (e == hipSuccess) e = hipMemsetAsync(a.starts, 0, sizeof(SxStart) * R * S, s->rs.set.stream);
+        if (e == hipSuccess) e = hipMemsetAsync(a.pst, 0, sizeof(int32_t) * W, s->rs.set.stream);
+        if (e == hipSuccess) e = hipMemsetAsync(a.lnq, 0, sizeof(double) * W, s->rs.set.stream);
         if (e == hipSuccess) e = cube_runs_alloc_queue(s->rs, a, W);
         if (e != hipSuccess) return gf_hip_fail(e, "gf_simplex_run: buffers");
         GfSettleArgs& sa = s->sa;
@@ -621,22 +621,22 @@ int gf_simplex_run(gf_simplex* s, int64_t max_rounds)
         if (rc != GF_OK) return rc;
     }
     if (a.S == 0) return GF_OK;
-    const int lpw = lanes_per_walker(cube_runs_eval_mode(s->rs), (int64_t)a.nruns * a.S * a.Q, a.nbins_max, s->rs.cus, {false, 32 * 1024, "GF_SIMPLEX_LPW"});
+    const int lpw = lanes_per_walker(gf_modelset_eval_mode(&s->rs.set), (int64_t)a.nruns * a.S * a.Q, a.nbins_max, s->rs.set.cus, {false, 32 * 1024, "GF_SIMPLEX_LPW"});
     constexpr int check = 4;
     std::vector<SxRun> hr(a.nruns);
     const dim3 sgrid((unsigned)((a.S + SX_STEP_BLOCK - 1) / SX_STEP_BLOCK), a.nruns);
     int64_t done_here = 0;
     for (;;) {
-        GF_HIP(hipMemcpyAsync(hr.data(), a.runs, sizeof(SxRun) * a.nruns, hipMemcpyDeviceToHost, s->rs.stream));
-        GF_HIP(hipStreamSynchronize(s->rs.stream));
+        GF_HIP(hipMemcpyAsync(hr.data(), a.runs, sizeof(SxRun) * a.nruns, hipMemcpyDeviceToHost, s->rs.set.stream));
+        GF_HIP(hipStreamSynchronize(s->rs.set.stream));
         bool all = true;
         for (const SxRun& x : hr) all = all && (x.active == 0 || x.failed);
         if (all) break;
         if (done_here >= max_rounds) return GF_OK;                      // stepping: the caller asked for this many rounds
         for (int i = 0; i < check && done_here < max_rounds; ++i, ++done_here) {
-            GF_HIP(launch_eval_any(cube_runs_eval_mode(s->rs), lpw, a, s->rs.stream));
-            if (s->rs.mode == MODE_BSM_GAUSS) GF_HIP(gf_launch_simplex_settle(s->sa, s->rs.cus, s->rs.stream));
-            hipLaunchKernelGGL(k_sx_step, sgrid, dim3(SX_STEP_BLOCK), 0, s->rs.stream, a);
+            GF_HIP(launch_eval_any(gf_modelset_eval_mode(&s->rs.set), lpw, a, s->rs.set.stream));
+            if (s->rs.set.mode == MODE_BSM_GAUSS) GF_HIP(gf_launch_simplex_settle(s->sa, s->rs.set.cus, s->rs.set.stream));
+            hipLaunchKernelGGL(k_sx_step, sgrid, dim3(SX_STEP_BLOCK), 0, s->rs.set.stream, a);
             GF_HIP(hipGetLastError());
             s->rounds += 1;
         }
@@ -648,19 +648,19 @@ int gf_simplex_result(gf_simplex* s, double* max_lnl, double* argmax_cube, int32
                       int64_t* nevals, uint32_t* nonunitary, uint32_t* parked, int32_t* failed)
 {
     if (!s) return GF_ERR_INVALID_ARG;
-    GF_HIP(hipSetDevice(s->rs.device));
+    GF_HIP(hipSetDevice(s->rs.set.device));
     const SxArgs& a = s->a;
     const int R = a.nruns, S = a.S, P = a.P, N = a.nscan;
     std::vector<SxRun> hr(R);
-    GF_HIP(hipMemcpyAsync(hr.data(), a.runs, sizeof(SxRun) * R, hipMemcpyDeviceToHost, s->rs.stream));
+    GF_HIP(hipMemcpyAsync(hr.data(), a.runs, sizeof(SxRun) * R, hipMemcpyDeviceToHost, s->rs.set.stream));
     std::vector<SxStart> hs((size_t)R * S);
     std::vector<double> f((size_t)R * S * P), x((size_t)R * S * P * N);
     if (s->rs.initialised && S > 0) {
-        GF_HIP(hipMemcpyAsync(hs.data(), a.starts, sizeof(SxStart) * hs.size(), hipMemcpyDeviceToHost, s->rs.stream));
-        GF_HIP(hipMemcpyAsync(f.data(), a.fsim, sizeof(double) * f.size(), hipMemcpyDeviceToHost, s->rs.stream));
-        GF_HIP(hipMemcpyAsync(x.data(), a.sim, sizeof(double) * x.size(), hipMemcpyDeviceToHost, s->rs.stream));
+        GF_HIP(hipMemcpyAsync(hs.data(), a.starts, sizeof(SxStart) * hs.size(), hipMemcpyDeviceToHost, s->rs.set.stream));
+        GF_HIP(hipMemcpyAsync(f.data(), a.fsim, sizeof(double) * f.size(), hipMemcpyDeviceToHost, s->rs.set.stream));
+        GF_HIP(hipMemcpyAsync(x.data(), a.sim, sizeof(double) * x.size(), hipMemcpyDeviceToHost, s->rs.set.stream));
     }
-    GF_HIP(hipStreamSynchronize(s->rs.stream));
+    GF_HIP(hipStreamSynchronize(s->rs.set.stream));
     for (int r = 0; r < R; ++r) {
         const int used = s->rs.initialised ? hr[r].nstarts : 0;
         double best = HUGE_VAL;
@@ -689,16 +689,16 @@ int gf_simplex_result(gf_simplex* s, double* max_lnl, double* argmax_cube, int32
 int gf_simplex_get_starts(gf_simplex* s, int run, double* fun, double* cube, int32_t* nit, int64_t* nfev)
 {
     if (!s || run < 0 || run >= s->a.nruns) return GF_ERR_INVALID_ARG;
-    GF_HIP(hipSetDevice(s->rs.device));
+    GF_HIP(hipSetDevice(s->rs.set.device));
     const SxArgs& a = s->a;
     const int S = a.S, P = a.P, N = a.nscan;
     if (!s->rs.initialised || S == 0) return GF_OK;
     std::vector<SxStart> hs(S);
     std::vector<double> f((size_t)S * P), x((size_t)S * P * N);
-    GF_HIP(hipMemcpyAsync(hs.data(), a.starts + (size_t)run * S, sizeof(SxStart) * S, hipMemcpyDeviceToHost, s->rs.stream));
-    GF_HIP(hipMemcpyAsync(f.data(), a.fsim + (size_t)run * S * P, sizeof(double) * f.size(), hipMemcpyDeviceToHost, s->rs.stream));
-    GF_HIP(hipMemcpyAsync(x.data(), a.sim + (size_t)run * S * P * N, sizeof(double) * x.size(), hipMemcpyDeviceToHost, s->rs.stream));
-    GF_HIP(hipStreamSynchronize(s->rs.stream));
+    GF_HIP(hipMemcpyAsync(hs.data(), a.starts + (size_t)run * S, sizeof(SxStart) * S, hipMemcpyDeviceToHost, s->rs.set.stream));
+    GF_HIP(hipMemcpyAsync(f.data(), a.fsim + (size_t)run * S * P, sizeof(double) * f.size(), hipMemcpyDeviceToHost, s->rs.set.stream));
+    GF_HIP(hipMemcpyAsync(x.data(), a.sim + (size_t)run * S * P * N, sizeof(double) * x.size(), hipMemcpyDeviceToHost, s->rs.set.stream));
+    GF_HIP(hipStreamSynchronize(s->rs.set.stream));
     for (int j = 0; j < S; ++j) {
         if (fun) fun[j] = hs[j].calls > 0 ? f[(size_t)j * P] : HUGE_VAL;
         if (cube) for (int d = 0; d < N; ++d) cube[(size_t)j * N + d] = x[(size_t)j * P * N + d];

@@ -109,8 +109,8 @@ int toys_upload_meas(ToySeedSet* t, const double* bf, int per_scale, const doubl
     if (rc != GF_OK) return rc;
     Meas* d = nullptr;
     if (scratch.take(&d, sizeof(Meas) * n, who) != GF_OK) return scratch.failed;
-    GF_HIP(hipMemcpyAsync(d, hm.data(), sizeof(Meas) * n, hipMemcpyHostToDevice, t->rs.stream));
-    GF_HIP(hipStreamSynchronize(t->rs.stream));                          // hm goes out of scope
+    GF_HIP(hipMemcpyAsync(d, hm.data(), sizeof(Meas) * n, hipMemcpyHostToDevice, t->rs.set.stream));
+    GF_HIP(hipStreamSynchronize(t->rs.set.stream));                          // hm goes out of scope
     a = ToySelArgs{};
     a.lp = t->d_lp; a.fr = t->d_fr; a.st = t->d_st; a.meas = d; a.meas_stride = per_scale ? ntoys : 0;
     a.M = t->nseed; a.T = ntoys; a.seed_u = t->d_u; a.N = t->a.nscan;
@@ -153,7 +153,7 @@ int gf_toys_select(gf_toys* h, const double* bf, int per_scale, const double* sm
     rc = toys_upload_meas(t, bf, per_scale, smearing, ntoys, scratch, a, "gf_toys_select");
     if (rc != GF_OK) return rc;
     a.K = K;
-    return toy_select_run(a, t->a.nruns, t->rs.stream, launch_select, index, score, count, cube, "gf_toys_select");
+    return toy_select_run(a, t->a.nruns, t->rs.set.stream, launch_select, index, score, count, cube, "gf_toys_select");
 }
 
 int gf_toys_scores(gf_toys* h, const double* bf, int per_scale, const double* smearing, int ntoys, double* scores)
@@ -169,10 +169,10 @@ int gf_toys_scores(gf_toys* h, const double* bf, int per_scale, const double* sm
     const size_t n = (size_t)t->a.nruns * ntoys * t->nseed;
     if (scratch.take(&a.all_scores, sizeof(double) * n, "gf_toys_scores") != GF_OK) return scratch.failed;
     const dim3 grid((unsigned)((a.M + GF_BLOCK - 1) / GF_BLOCK), (unsigned)ntoys, (unsigned)t->a.nruns);
-    hipLaunchKernelGGL(k_toy_score, grid, dim3(GF_BLOCK), 0, t->rs.stream, a);
+    hipLaunchKernelGGL(k_toy_score, grid, dim3(GF_BLOCK), 0, t->rs.set.stream, a);
     GF_HIP(hipGetLastError());
-    GF_HIP(hipMemcpyAsync(scores, a.all_scores, sizeof(double) * n, hipMemcpyDeviceToHost, t->rs.stream));
-    GF_HIP(hipStreamSynchronize(t->rs.stream));
+    GF_HIP(hipMemcpyAsync(scores, a.all_scores, sizeof(double) * n, hipMemcpyDeviceToHost, t->rs.set.stream));
+    GF_HIP(hipStreamSynchronize(t->rs.set.stream));
     return GF_OK;
 }
 

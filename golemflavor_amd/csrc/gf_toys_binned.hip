@@ -152,8 +152,8 @@ int toysb_upload(ToySeedSet* t, const double* meas, int per_scale, const double*
     if (rc != GF_OK) return rc;
     double* d = nullptr;
     if (scratch.take(&d, sizeof(double) * tab.size(), who) != GF_OK) return scratch.failed;
-    GF_HIP(hipMemcpyAsync(d, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, t->rs.stream));
-    GF_HIP(hipStreamSynchronize(t->rs.stream));                          // tab goes out of scope
+    GF_HIP(hipMemcpyAsync(d, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, t->rs.set.stream));
+    GF_HIP(hipStreamSynchronize(t->rs.set.stream));                          // tab goes out of scope
     a = ToybSelArgs{};
     a.lp = t->d_lp; a.frb = t->d_frb; a.st = t->d_st; a.tab = d; a.tab_stride = per_scale ? (int64_t)nb * NCONST * ntoys : 0;
     a.offset = t->offset; a.M = t->nseed; a.T = ntoys; a.nb = t->nbins; a.seed_u = t->d_u; a.N = t->a.nscan;
@@ -197,7 +197,7 @@ int gf_toys_select_binned(gf_toys_binned* h, const double* meas, int per_scale, 
     rc = toysb_upload(t, meas, per_scale, sigma, per_toy_sigma, ntoys, scratch, a, "gf_toys_select_binned");
     if (rc != GF_OK) return rc;
     a.K = K;
-    return toy_select_run(a, t->a.nruns, t->rs.stream, launch_select, index, score, count, cube, "gf_toys_select_binned");
+    return toy_select_run(a, t->a.nruns, t->rs.set.stream, launch_select, index, score, count, cube, "gf_toys_select_binned");
 }
 
 int gf_toys_scores_binned(gf_toys_binned* h, const double* meas, int per_scale, const double* sigma, int per_toy_sigma, int ntoys, double* scores)
@@ -215,10 +215,10 @@ int gf_toys_scores_binned(gf_toys_binned* h, const double* meas, int per_scale, 
     const size_t n = (size_t)t->a.nruns * ntoys * t->nseed;
     if (scratch.take(&a.all_scores, sizeof(double) * n, "gf_toys_scores_binned") != GF_OK) return scratch.failed;
     const dim3 grid((unsigned)((a.M + GF_BLOCK - 1) / GF_BLOCK), (unsigned)ntoys, (unsigned)t->a.nruns);
-    hipLaunchKernelGGL(k_toyb_score, grid, dim3(GF_BLOCK), 0, t->rs.stream, a);
+    hipLaunchKernelGGL(k_toyb_score, grid, dim3(GF_BLOCK), 0, t->rs.set.stream, a);
     GF_HIP(hipGetLastError());
-    GF_HIP(hipMemcpyAsync(scores, a.all_scores, sizeof(double) * n, hipMemcpyDeviceToHost, t->rs.stream));
-    GF_HIP(hipStreamSynchronize(t->rs.stream));
+    GF_HIP(hipMemcpyAsync(scores, a.all_scores, sizeof(double) * n, hipMemcpyDeviceToHost, t->rs.set.stream));
+    GF_HIP(hipStreamSynchronize(t->rs.set.stream));
     return GF_OK;
 }
 

@@ -63,14 +63,14 @@ int toy_seeds_create(void** out, gf_model* const* models, int nscales, int nscan
     if (!t) return GF_ERR_ALLOC;
     int rc = cube_runs_create(t->rs, t->a, models, nscales, nscan, cols, bases, seed, who);
     if (rc != GF_OK) { delete t; return rc; }
-    if (t->rs.table)
+    if (t->rs.set.kind == GF_LLH_TABLE)
         rc = gf_fail_msg(GF_ERR_UNSUPPORTED, "%s: the models carry a tabulated likelihood; a realisation of a table is not defined", who);
-    else if (binned && !t->rs.binned)
+    else if (binned && t->rs.set.kind != GF_LLH_BINNED)
         rc = gf_fail_msg(GF_ERR_UNSUPPORTED, "%s: the models carry no binned measurement; gf_toys_create seeds the flux-averaged Gaussian likelihood", who);
-    else if (!binned && t->rs.binned)
+    else if (!binned && t->rs.set.kind == GF_LLH_BINNED)
         rc = gf_fail_msg(GF_ERR_UNSUPPORTED, "%s: the models carry a binned measurement; realisations are of the flux-averaged Gaussian likelihood", who);
-    else if (!binned && t->rs.mode != MODE_SM_GAUSS && t->rs.mode != MODE_BSM_GAUSS)
-        rc = gf_fail_msg(GF_ERR_UNSUPPORTED, "%s: the models have no Gaussian measurement (mode %d)", who, t->rs.mode);
+    else if (!binned && t->rs.set.mode != MODE_SM_GAUSS && t->rs.set.mode != MODE_BSM_GAUSS)
+        rc = gf_fail_msg(GF_ERR_UNSUPPORTED, "%s: the models have no Gaussian measurement (mode %d)", who, t->rs.set.mode);
     t->nseed = nseed;
     t->seed_fn = seed_fn;
     for (int r = 0; r < nscales && rc == GF_OK; ++r) {
@@ -119,7 +119,7 @@ int toy_seeds_set_ids(ToySeedSet* t, const uint64_t* ids, const char* late)
 int toy_seeds_ready(const ToySeedSet& t, const char* who)
 {
     if (!t.seeded) return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: after %s", who, t.seed_fn);
-    GF_HIP(hipSetDevice(t.rs.device));
+    GF_HIP(hipSetDevice(t.rs.set.device));
     return GF_OK;
 }
 
@@ -127,29 +127,29 @@ int toy_seeds_seed(ToySeedSet* t, uint32_t* nonunitary, const char* who)
 {
     if (!t) return GF_ERR_INVALID_ARG;
     if (t->seeded) return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: the seeds have been drawn", who);
-    GF_HIP(hipSetDevice(t->rs.device));
+    GF_HIP(hipSetDevice(t->rs.set.device));
     const GfCubeRuns& a = t->a;
     const int n = t->nseed;
-    hipStream_t st = t->rs.stream;
+    hipStream_t st = t->rs.set.stream;
     const dim3 grid((unsigned)((n + GF_BLOCK - 1) / GF_BLOCK), a.nruns);
     hipLaunchKernelGGL(k_cube_draw, grid, dim3(GF_BLOCK), 0, st, a, SX_SEED_ITER, n, t->d_u, t->d_theta);
     GF_HIP(hipGetLastError());
     for (int r = 0; r < a.nruns; ++r) {
         const size_t at = (size_t)r * n;
-        int rc = gf_model_lnprob_on(t->rs.models[r], st, t->d_theta + at * a.ndim, GF_LAYOUT_AOS, n, t->d_lnl + at, t->d_fr + at * 3, t->d_st + at);
+        int rc = gf_model_lnprob_on(t->rs.set.models[r], st, t->d_theta + at * a.ndim, GF_LAYOUT_AOS, n, t->d_lnl + at, t->d_fr + at * 3, t->d_st + at);
         if (rc == GF_OK && t->d_frb)
-            rc = gf_model_bins_on(t->rs.models[r], st, t->d_theta + at * a.ndim, GF_LAYOUT_AOS, n, t->d_frb + at * 3 * t->nbins, 0, t->d_st + at);
+            rc = gf_model_bins_on(t->rs.set.models[r], st, t->d_theta + at * a.ndim, GF_LAYOUT_AOS, n, t->d_frb + at * 3 * t->nbins, 0, t->d_st + at);
         if (rc != GF_OK) return rc;
     }
     GF_HIP(hipMemsetAsync(t->d_nonunit, 0, sizeof(unsigned int) * a.nruns, st));
     // an energy-resolved set's models are BSM models (gf_model_bins_on has refused any other)
-    if (t->d_frb || t->rs.mode == MODE_BSM_GAUSS) hipLaunchKernelGGL(k_toy_prior<true>, grid, dim3(GF_BLOCK), 0, st, a, n, t->d_theta, t->d_st, t->d_lp, t->d_nonunit);
+    if (t->d_frb || t->rs.set.mode == MODE_BSM_GAUSS) hipLaunchKernelGGL(k_toy_prior<true>, grid, dim3(GF_BLOCK), 0, st, a, n, t->d_theta, t->d_st, t->d_lp, t->d_nonunit);
     else hipLaunchKernelGGL(k_toy_prior<false>, grid, dim3(GF_BLOCK), 0, st, a, n, t->d_theta, t->d_st, t->d_lp, t->d_nonunit);
     GF_HIP(hipGetLastError());
     std::vector<unsigned int> nu(a.nruns);
     GF_HIP(hipMemcpyAsync(nu.data(), t->d_nonunit, sizeof(unsigned int) * a.nruns, hipMemcpyDeviceToHost, st));
     GF_HIP(hipStreamSynchronize(st));
-    const int rc = gf_internal_check_overflow(t->rs.device, st);
+    const int rc = gf_internal_check_overflow(t->rs.set.device, st);
     if (rc != GF_OK) return rc;
     if (nonunitary) for (int r = 0; r < a.nruns; ++r) nonunitary[r] = nu[r];
     t->seeded = 1;
@@ -163,7 +163,7 @@ int toy_seeds_get(ToySeedSet* t, int scale, double* cube, double* lnprob, double
     const int rc = toy_seeds_ready(*t, who);
     if (rc != GF_OK) return rc;
     const size_t M = t->nseed, at = (size_t)scale * M, per = 3 * (size_t)t->nbins;
-    hipStream_t st = t->rs.stream;
+    hipStream_t st = t->rs.set.stream;
     if (cube) GF_HIP(hipMemcpyAsync(cube, t->d_u + at * t->a.nscan, sizeof(double) * M * t->a.nscan, hipMemcpyDeviceToHost, st));
     if (lnprob) GF_HIP(hipMemcpyAsync(lnprob, t->d_lnl + at, sizeof(double) * M, hipMemcpyDeviceToHost, st));
     if (lp) GF_HIP(hipMemcpyAsync(lp, t->d_lp + at, sizeof(double) * M, hipMemcpyDeviceToHost, st));

@@ -346,6 +346,17 @@ def test_refusals_leave_the_model_usable():
         with pytest.raises(_lib.GolemHipError) as e:
             mcmc_utils.DeviceEnsembleSampler(32, 7, m, seed=1)
         assert e.value.code == _lib.GF_ERR_UNSUPPORTED
+        # the models of a set share device, ndim and mode: the sampler names the model that differs, a run set the rule
+        with Model(compile_model(nps, "SM_GAUSS", bestfit_fr=fr_utils.angles_to_fr(asimov.values), smearing=0.02)) as sm:
+            differ = (C.c_void_p * 2)(other._h, sm._h)
+            h = C.c_void_p()
+            rc = L.gf_sampler_create_multi(differ, 2, 16, 5, 2.0, C.byref(h))
+            assert rc == _lib.GF_ERR_INVALID_ARG and not h.value
+            assert b"gf_sampler_create_multi: model 1 differs from model 0 in device, ndim or mode" in L.gf_last_hip_error()
+            for create, tail in ((L.gf_nested_create, (64, 8, 5, 1, 0)), (L.gf_simplex_create, (4, 64, 1, 0))):
+                rc = create(differ, 2, 6, cols.ctypes.data_as(_lib._ip), base.ctypes.data_as(_lib._dp), *tail, C.byref(h))
+                assert rc == _lib.GF_ERR_INVALID_ARG and not h.value
+                assert b"every model must share device, ndim and mode with model 0" in L.gf_last_hip_error()
         # both models are what they were
         assert same_bits(m.lnprob(th, want_status=False), binned)
         assert same_bits(other.lnprob(th, want_status=False), before)
