@@ -354,6 +354,15 @@ def pass_items(model_handle):
     return int(n.value)
 
 
+def likelihood_sets(model_handle):
+    """gf_model_likelihood_sets (gf_internal.h; not part of the public header, hence not in SIGNATURES): how many
+    gf_model_set_table_likelihood / gf_model_set_binned_measurement calls have succeeded on the model -- what tells a nested sampler or a
+    maximiser whose runs have begun that a likelihood was replaced, in place included.  0 for a NULL handle."""
+    fn = lib().gf_model_likelihood_sets
+    fn.restype, fn.argtypes = C.c_uint64, [_vp]
+    return int(fn(model_handle))
+
+
 def device_count():
     n = C.c_int(0)
     check(lib().gf_device_count(C.byref(n)), "gf_device_count")

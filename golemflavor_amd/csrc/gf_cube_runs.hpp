@@ -193,6 +193,30 @@ int cube_runs_create(GfCubeRunsHost& h, GfCubeRuns& a, gf_model* const* models, 
     return GF_OK;
 }
 
+// What a run set owes to models whose likelihood can be set after the set exists, for every entry point that
+// evaluates (`who`), before it launches or writes anything: the set's kind is fixed at creation -- a model that has since gained a
+// table or a measurement is refused; the call that initialises takes the models' tables of now (a binned table's address never
+// changes) and marks the models; a run that has begun is refused once a model's likelihood has been set again, in place included.
+int cube_runs_begin(GfCubeRunsHost& h, const char* who)
+{
+    int now = GF_LLH_FLUX;
+    const int differs = gf_modelset_kind_differs(&h.set, &now);
+    if (differs >= 0)
+        return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: model %d now carries %s; a set keeps the likelihood its models carried when it was created (%s)",
+                           who, differs, gf_likelihood_name(now), gf_likelihood_name(h.set.kind));
+    if (h.initialised) {
+        const int replaced = gf_modelset_replaced(&h.set);
+        if (replaced >= 0)
+            return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: the likelihood of model %d was replaced after the set's runs began; a run that has begun does not change likelihood",
+                               who, replaced);
+        return GF_OK;
+    }
+    const int rc = gf_modelset_refresh_tables(&h.set, who);
+    if (rc != GF_OK) return rc;
+    gf_modelset_mark(&h.set);
+    return GF_OK;
+}
+
 // BSM: the arbitration queue for `w` proposals a step, their pend rows and the settle kernel's counters, all empty
 hipError_t cube_runs_alloc_queue(GfCubeRunsHost& h, GfCubeRuns& a, size_t w)
 {

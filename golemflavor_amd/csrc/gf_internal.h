@@ -33,6 +33,9 @@ int gf_model_binned(gf_model* m, const double** d_btab);
 // the side of the model's tabulated likelihood (gf_model_set_table_likelihood), 0 without one; *d_table <- its device
 // table (NULL without one).  A replacement of another side moves the table.
 int gf_model_table(gf_model* m, const double** d_table);
+// how many gf_model_set_table_likelihood and gf_model_set_binned_measurement calls have succeeded on the model: a replacement written in
+// place leaves address and side as they were, the count moves (gf_modelset.h; 0 for NULL)
+uint64_t gf_model_likelihood_sets(const gf_model* m);
 // the model's kernels on a stream of the caller's
 int gf_model_lnprob_on(gf_model* m, void* stream, const double* d_theta, int layout, int64_t n, double* d_lnprob, double* d_fr, int32_t* d_status);
 int gf_model_propagate_on(gf_model* m, void* stream, const double* d_theta, int layout, int64_t n, double* d_fr, int32_t* d_status);

@@ -461,6 +461,7 @@ int gf_model_set_binned_measurement(gf_model* m, int nbins, const double* fr_bin
     }
     m->d_btab = d;
     m->binned = 1;
+    m->likelihood_sets += 1;
     return GF_OK;
 }
 
@@ -518,6 +519,7 @@ int gf_model_set_table_likelihood(gf_model* m, int nside, const double* values)
         m->table_cap = nodes;
     }
     m->table_nside = nside;
+    m->likelihood_sets += 1;
     return GF_OK;
 }
 
@@ -529,6 +531,8 @@ int gf_model_table(gf_model* m, const double** d_table)
     if (d_table) *d_table = ns > 0 ? m->d_table : nullptr;
     return ns;
 }
+
+uint64_t gf_model_likelihood_sets(const gf_model* m) { return m ? m->likelihood_sets : 0; }
 
 // internal (not in the public header): gf_modelset.hip reaches the model's constants and stream through these
 int gf_model_internal(gf_model* m, const GfCommon** c, const GfBsm** d_bsm, const double** d_ptab, void** stream, int* device)

@@ -32,6 +32,8 @@ struct GfModelSet {
     // or mode (-1: none), and the GfLikelihood of every model before it
     int differs = -1;
     std::vector<int> carries;
+    // gf_modelset_mark: every model's gf_model_likelihood_sets when the set's user began a run that must not change likelihood
+    std::vector<uint64_t> marked;
 };
 
 // Validates the models against models[0], takes what each carries and uploads the arrays on the set's stream, which is synchronised.
@@ -44,6 +46,18 @@ int gf_modelset_create(GfModelSet* set, gf_model* const* models, int nmodels, co
 // addresses never change, so a captured graph stays valid; an outgrown table is retired by its model, not freed.  Called with the
 // stream idle; `who` names the caller where a model has lost its table.
 int gf_modelset_refresh_tables(GfModelSet* set, const char* who);
+// The contract every user of a set keeps with models whose likelihood can be set after the set exists.  The set
+// reports, its users word the refusals.
+// A set's kind is fixed at creation: the first model that now carries another GfLikelihood than the set's (-1: none), and in *now what
+// it carries.  Host reads only.
+int gf_modelset_kind_differs(const GfModelSet* set, int* now);
+// a GfLikelihood as the refusals name it: "a tabulated likelihood", "a binned measurement", "the flux-averaged likelihood"
+inline const char* gf_likelihood_name(int kind) { return kind == GF_LLH_TABLE ? "a tabulated likelihood" : kind == GF_LLH_BINNED ? "a binned measurement" : "the flux-averaged likelihood"; }
+// A run that has begun does not change likelihood: _mark records every model's count of likelihoods set, _replaced is the first model
+// whose count has moved since (-1: none, or never marked) -- a table or measurement written in place, which leaves address and side as
+// they were, included.
+void gf_modelset_mark(GfModelSet* set);
+int gf_modelset_replaced(const GfModelSet* set);
 // the device arrays, after the stream has drained
 void gf_modelset_free(GfModelSet* set);
 // the MODE of the evaluation kernels' instance: the models' mode, MODE_BSM_BINNED or MODE_BSM_TABLE for such a set

@@ -71,6 +71,28 @@ int gf_modelset_refresh_tables(GfModelSet* set, const char* who)
     return GF_OK;
 }
 
+int gf_modelset_kind_differs(const GfModelSet* set, int* now)
+{
+    for (size_t r = 0; r < set->models.size(); ++r) {
+        const int has = gf_model_table(set->models[r], nullptr) > 0 ? GF_LLH_TABLE : gf_model_binned(set->models[r], nullptr) ? GF_LLH_BINNED : GF_LLH_FLUX;
+        if (has != set->kind) { if (now) *now = has; return (int)r; }
+    }
+    return -1;
+}
+
+void gf_modelset_mark(GfModelSet* set)
+{
+    set->marked.resize(set->models.size());
+    for (size_t r = 0; r < set->models.size(); ++r) set->marked[r] = gf_model_likelihood_sets(set->models[r]);
+}
+
+int gf_modelset_replaced(const GfModelSet* set)
+{
+    for (size_t r = 0; r < set->marked.size() && r < set->models.size(); ++r)
+        if (gf_model_likelihood_sets(set->models[r]) != set->marked[r]) return (int)r;
+    return -1;
+}
+
 void gf_modelset_free(GfModelSet* set)
 {
     if (set->stream) {

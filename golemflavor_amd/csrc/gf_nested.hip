@@ -516,6 +516,7 @@ int gf_nested_run(gf_nested* s, int64_t max_iter)
     if (!s || max_iter < 1) return GF_ERR_INVALID_ARG;
     GF_HIP(hipSetDevice(s->rs.set.device));
     NsArgs& a = s->a;
+    if (const int rc = cube_runs_begin(s->rs, "gf_nested_run")) return rc;
     if (!s->rs.initialised) { const int rc = ns_init(s); if (rc != GF_OK) return rc; }
     const int lpw = lanes_per_walker(gf_modelset_eval_mode(&s->rs.set), (int64_t)a.nruns * a.batch, a.nbins_max, s->rs.set.cus, {false, 32 * 1024, "GF_NESTED_LPW"});
     constexpr int check = 4;

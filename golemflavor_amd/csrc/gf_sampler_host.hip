@@ -97,6 +97,17 @@ int sampler_refusal(const GfModelSet& set, int want)
     return GF_OK;
 }
 
+// ... and stays the one the sampler was created for: a model that has since gained a table or a measurement is refused by every entry
+// point that evaluates (`who`), before it launches or writes anything.  The stored chain and state stay as they are.
+int sampler_kind_refusal(const gf_sampler* s, const char* who)
+{
+    int now = GF_LLH_FLUX;
+    const int differs = gf_modelset_kind_differs(&s->set, &now);
+    if (differs < 0) return GF_OK;
+    return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: model %d now carries %s; the sampler's kernels evaluate the likelihood it was created for (%s)", who, differs,
+                       gf_likelihood_name(now), gf_likelihood_name(s->set.kind));
+}
+
 // gf_sampler_create (multi false: every chain samples models[0]) and gf_sampler_create_multi (multi true: chain ch samples
 // models[ch]): the model set has one entry per model.  want: the likelihood the sampler evaluates -- GF_LLH_BINNED
 // (gf_sampler_create_binned), GF_LLH_TABLE (gf_sampler_create_table) or the flux-averaged one; every model must carry exactly that.
@@ -618,6 +629,7 @@ int gf_sampler_set_stream_ids(gf_sampler* s, const uint64_t* ids)
 int gf_sampler_set_state(gf_sampler* s, const double* pos)
 {
     if (!s || !pos) return GF_ERR_INVALID_ARG;
+    if (const int rc = sampler_kind_refusal(s, "gf_sampler_set_state")) return rc;
     GF_HIP(hipSetDevice(s->set.device));
     hipStream_t st = s->set.stream;
     const size_t nw = (size_t)s->nchains * s->nwalkers;
@@ -665,6 +677,7 @@ int gf_sampler_reset(gf_sampler* s)
 int gf_sampler_run(gf_sampler* s, int64_t nsteps, int thin, int store)
 {
     if (!s || nsteps < 0 || thin < 1) return GF_ERR_INVALID_ARG;
+    if (const int rc = sampler_kind_refusal(s, "gf_sampler_run")) return rc;
     GF_HIP(hipSetDevice(s->set.device));
     hipStream_t st = s->set.stream;
     const int64_t nstore = store ? (nsteps + thin - 1) / thin : 0;     // steps this run stores
@@ -726,6 +739,7 @@ int gf_sampler_sync(gf_sampler* s)
 int gf_sampler_run_to_host(gf_sampler* s, int64_t nsteps, int thin, double* chain, double* lnprob_chain, double* readback_tail_s)
 {
     if (!s || !chain || nsteps < 0 || thin < 1) return GF_ERR_INVALID_ARG;
+    if (const int refused = sampler_kind_refusal(s, "gf_sampler_run_to_host")) return refused;      // before the copy stream and the pipe
     GF_HIP(hipSetDevice(s->set.device));
     const int device = s->set.device;
     void* copy_stream = nullptr;

@@ -595,6 +595,7 @@ int gf_simplex_run(gf_simplex* s, int64_t max_rounds)
     if (!s || max_rounds < 1) return GF_ERR_INVALID_ARG;
     GF_HIP(hipSetDevice(s->rs.set.device));
     SxArgs& a = s->a;
+    if (const int rc = cube_runs_begin(s->rs, "gf_simplex_run")) return rc;
     if (!s->rs.initialised) {
         // the per-start buffers are sized once the caller's starts are known
         a.S = a.nstarts + a.nuser;

@@ -128,6 +128,7 @@ int toy_seeds_seed(ToySeedSet* t, uint32_t* nonunitary, const char* who)
     if (!t) return GF_ERR_INVALID_ARG;
     if (t->seeded) return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: the seeds have been drawn", who);
     GF_HIP(hipSetDevice(t->rs.set.device));
+    if (const int rc = cube_runs_begin(t->rs, who)) return rc;
     const GfCubeRuns& a = t->a;
     const int n = t->nseed;
     hipStream_t st = t->rs.set.stream;

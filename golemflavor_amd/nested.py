@@ -46,7 +46,9 @@ class _CubeRuns:
     theta), every other column at `bases` ([nruns][ndim] or [ndim]); the device object of the C ABI's gf_<_abi>_* calls.
     `run_ids`: the Philox stream of each run (default 0..nruns-1); a scan passes each point's index in its full list so that a
     point's result does not depend on what else shares the call.  `labels`: what an AssertionError names for a failed run
-    (default: the run index)."""
+    (default: the run index).  A table or binned measurement replaced on a model before the first run() is what the runs evaluate; one
+    replaced after the runs have begun, or given to a model that had none when the object was created, makes run() raise
+    GolemHipError (GF_ERR_INVALID_ARG) -- results so far stay readable."""
     _abi = None                 # "nested" or "simplex"
     _what = None                # a run's name in the AssertionError
 

@@ -719,8 +719,12 @@ int gf_model_is_binned(const gf_model* m);   /* 1 with a binned measurement, 0 w
  * 1 <= nside <= GF_TABLE_MAX_NSIDE, every value finite or -inf and one of them finite: else GF_ERR_INVALID_ARG.  A model of another mode,
  * or one with a binned measurement: GF_ERR_UNSUPPORTED (and gf_model_set_binned_measurement refuses a model with a table); either way
  * the model is unchanged.  A table can be replaced (no launch of the model may be in flight on a stream other than its own; a nested
- * sampler or maximiser created earlier keeps reading the table it was created with; an ensemble sampler of gf_sampler_create_table reads
- * the new one from its next run on) but not removed.  The ensemble sampler samples such a model through gf_sampler_create_table alone.
+ * sampler or maximiser created earlier reads the new one if it has not run yet, and once its runs have begun its next gf_nested_run /
+ * gf_simplex_run is GF_ERR_INVALID_ARG -- a run that has begun does not change likelihood, its results so far stay readable; an
+ * ensemble sampler of gf_sampler_create_table reads the new one from its next run on) but not removed.  A model that gains its first
+ * table, or its first binned measurement, after a sampler, nested sampler, maximiser or seed set was created over it is refused by
+ * that handle's next set_state / run / seed call (GF_ERR_INVALID_ARG naming the model; what the handle holds stays readable).
+ * The ensemble sampler samples such a model through gf_sampler_create_table alone.
  * Refused with GF_ERR_UNSUPPORTED: gf_sampler_create, gf_sampler_create_multi and gf_sampler_create_binned (their kernels evaluate another
  * likelihood), and what sets or reweights to a Gaussian measurement -- gf_toys_create*, gf_toys_set_measurements, gf_toys_set_binned_measurements,
  * gf_nested_toys_evidence.  Of the models of one nested sampler or maximiser all carry a table or none; the sides may differ. */

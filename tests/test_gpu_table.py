@@ -238,16 +238,21 @@ def full_window_models(tables):
     return models, cols, np.tile(np.array(ps.values, dtype=float), (len(tables), 1))
 
 
-def run_nested(models, cols, bases, run_ids, problems):
-    """(result, dead() of every run); every run's points are held to the bulk lnprob, what does not hold goes to `problems`"""
+def run_nested(models, cols, bases, run_ids, problems, before_run=None):
+    """(result, dead() of every run); every run's points are held to the bulk lnprob, what does not hold goes to `problems`.
+    before_run(): called between the sampler's creation and its run (tests/test_gpu_model_changes.py)."""
     with nested.NestedSampler(models, cols, bases, nlive=64, batch=8, walks=10, seed=13, tol=0.5, on_nonunitary="-inf", run_ids=run_ids) as s:
+        if before_run is not None:
+            before_run()
         res = s.run()
         return res, [check_dead_points(s, res, r, m, "table nested window", problems) for r, m in enumerate(models)]
 
 
-def run_simplex(models, cols, bases, run_ids, starts):
+def run_simplex(models, cols, bases, run_ids, starts, before_run=None):
     with P.SimplexMaximizer(models, cols, bases, nstarts=1, nseed=256, seed=5, starts=starts, maxiter=100, adaptive=True, restarts=1,
                             on_nonunitary="-inf", run_ids=run_ids) as s:
+        if before_run is not None:
+            before_run()
         res = s.run()
         return res, [s.starts(r) for r in range(len(models))], [s.cube_to_theta(r, s.starts(r)["cube"][:int(res["nstarts"][r])])
                                                                for r in range(len(models))]

@@ -330,15 +330,16 @@ def test_walkers_started_in_a_hole_leave_it_and_stay_out(oracle):
 # ---- 8. a table replaced between two runs ----------------------------------------------------------------------------------------------------
 def test_a_table_replaced_between_two_runs_is_the_one_the_next_run_samples(oracle):
     """A run of 36 steps (two graph replays) under a table of side 16; the model's table is replaced by another of side 16 (written in
-    place) and 34 more steps run, then by one of side 40 (the table moves) and 34 more.  Each later run equals the numpy move on the new
-    table from the run before's final state, the walkers holding the lnprob the device holds -- the old table's, not recomputed."""
+    place) and 34 more steps run, then by one of side 40 (the table moves) and 34 more, then by one of side 5 (smaller, written in place
+    into the buffer of the side-40 table) and 34 more.  Each later run equals the numpy move on the new table from the run before's final
+    state, the walkers holding the lnprob the device holds -- the old table's, not recomputed."""
     m, ps = table_model(7, 6, Texture.OET, 16, seed=50)
     with m:
         p0 = scale_rows(ps, 32, np.random.default_rng(28), 6)[None]
         smp, ref = run_against_reference(oracle, "before the replacement", [m], False, p0, 36, 29, None)
         try:
             done = 36
-            for N, sd in ((16, 51), (40, 52)):
+            for N, sd in ((16, 51), (40, 52), (5, 53)):
                 m.set_table_likelihood(surface(N, sd))
                 assert m.table_nside == N
                 smp.reset()
