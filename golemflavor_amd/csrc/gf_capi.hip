@@ -8,7 +8,7 @@
 #include <cstring>
 #include <mutex>
 
-#include "gf_devcache.h"                // large device allocations are cached, not handed back to the driver (hipMalloc / hipFree are macros from here on)
+#include "gf_devcache.h"                // large device allocations are cached, not handed back to the driver
 #include "gf_host.h"
 #include "gf_model.h"
 
@@ -30,13 +30,13 @@ int ensure_staging(gf_model* m, int64_t n, int64_t n_pin)
     if (n > m->cap) {
         int64_t cap = m->cap ? m->cap : 1024;
         while (cap < n) cap *= 2;
-        if (m->d_theta) (void)hipFree(m->d_theta);
-        if (m->d_out) (void)hipFree(m->d_out);
-        if (m->d_status) (void)hipFree(m->d_status);
+        if (m->d_theta) (void)gf_cached_free(m->d_theta);
+        if (m->d_out) (void)gf_cached_free(m->d_out);
+        if (m->d_status) (void)gf_cached_free(m->d_status);
         m->d_theta = nullptr; m->d_out = nullptr; m->d_status = nullptr; m->cap = 0;
-        GF_HIP(hipMalloc((void**)&m->d_theta, sizeof(double) * nd * cap));
-        GF_HIP(hipMalloc((void**)&m->d_out, sizeof(double) * 4 * cap));
-        GF_HIP(hipMalloc((void**)&m->d_status, sizeof(int32_t) * cap));
+        GF_HIP(gf_cached_malloc((void**)&m->d_theta, sizeof(double) * nd * cap));
+        GF_HIP(gf_cached_malloc((void**)&m->d_out, sizeof(double) * 4 * cap));
+        GF_HIP(gf_cached_malloc((void**)&m->d_status, sizeof(int32_t) * cap));
         m->cap = cap;
     }
     if (n_pin > m->hcap) {
@@ -302,9 +302,9 @@ int gf_lnprob_cube_batch(gf_model* m, const double* cube, int64_t n, int nscan, 
     double* h_cube = pin.theta;                              // the theta slot of the pinned mirror holds the (smaller) cube
     // device side: the cube rows get their own buffer, grown on demand (d_theta receives the expanded rows)
     if ((int64_t)m->cube_cap < n * nscan) {
-        if (m->d_cube) (void)hipFree(m->d_cube);
+        if (m->d_cube) (void)gf_cached_free(m->d_cube);
         m->d_cube = nullptr; m->cube_cap = 0;
-        GF_HIP(hipMalloc((void**)&m->d_cube, sizeof(double) * (size_t)n * nscan));
+        GF_HIP(gf_cached_malloc((void**)&m->d_cube, sizeof(double) * (size_t)n * nscan));
         m->cube_cap = (size_t)n * nscan;
     }
     std::memcpy(h_cube, cube, sizeof(double) * (size_t)n * nscan);
@@ -327,10 +327,10 @@ int gf_haar_draw(gf_model* m, uint64_t seed, int64_t first_draw, int64_t n, doub
     if (n == 0) return GF_OK;
     GF_STREAM(m);
     double *d_fr = nullptr, *d_ang = nullptr;
-    GF_HIP(hipMalloc((void**)&d_fr, sizeof(double) * 3 * n));
+    GF_HIP(gf_cached_malloc((void**)&d_fr, sizeof(double) * 3 * n));
     if (angles) {
-        hipError_t e = hipMalloc((void**)&d_ang, sizeof(double) * 4 * n);
-        if (e != hipSuccess) { (void)hipFree(d_fr); return gf_hip_fail(e, "hipMalloc(angles)"); }
+        hipError_t e = gf_cached_malloc((void**)&d_ang, sizeof(double) * 4 * n);
+        if (e != hipSuccess) { (void)gf_cached_free(d_fr); return gf_hip_fail(e, "hipMalloc(angles)"); }
     }
     int rc = gf_haar_draw_device(m, seed, first_draw, n, d_ang, d_fr);
     hipError_t e = hipSuccess;
@@ -338,8 +338,8 @@ int gf_haar_draw(gf_model* m, uint64_t seed, int64_t first_draw, int64_t n, doub
     if (rc == GF_OK && e == hipSuccess && angles)
         e = hipMemcpyAsync(angles, d_ang, sizeof(double) * 4 * n, hipMemcpyDeviceToHost, m->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
-    (void)hipFree(d_fr);
-    if (d_ang) (void)hipFree(d_ang);
+    (void)gf_cached_free(d_fr);
+    if (d_ang) (void)gf_cached_free(d_ang);
     if (rc != GF_OK) return rc;
     return e != hipSuccess ? gf_hip_fail(e, "gf_haar_draw") : GF_OK;
 }
@@ -349,7 +349,7 @@ int gf_device_alloc(gf_model* m, size_t bytes, void** dptr)
 {
     if (!m || !dptr) return GF_ERR_INVALID_ARG;
     GF_HIP(hipSetDevice(m->device));
-    GF_HIP(hipMalloc(dptr, bytes ? bytes : 16));
+    GF_HIP(gf_cached_malloc(dptr, bytes ? bytes : 16));
     return GF_OK;
 }
 
@@ -359,7 +359,7 @@ int gf_device_free(gf_model* m, void* dptr)
     if (!dptr) return GF_OK;
     GF_HIP(hipSetDevice(m->device));
     if (m->stream) GF_HIP(hipStreamSynchronize(m->stream));
-    GF_HIP(hipFree(dptr));
+    GF_HIP(gf_cached_free(dptr));
     return GF_OK;
 }
 
@@ -438,16 +438,16 @@ int gf_flavor_histogram(gf_model* m, const double* fr, int64_t n, int nbins, uin
     const size_t nbin3 = (size_t)nbins * nbins * nbins;
     double* d_fr = nullptr;
     uint64_t* d_c = nullptr;
-    GF_HIP(hipMalloc((void**)&d_c, sizeof(uint64_t) * nbin3));
+    GF_HIP(gf_cached_malloc((void**)&d_c, sizeof(uint64_t) * nbin3));
     hipError_t e = hipMemsetAsync(d_c, 0, sizeof(uint64_t) * nbin3, m->stream);
-    if (e == hipSuccess && n > 0) e = hipMalloc((void**)&d_fr, sizeof(double) * 3 * n);
+    if (e == hipSuccess && n > 0) e = gf_cached_malloc((void**)&d_fr, sizeof(double) * 3 * n);
     if (e == hipSuccess && n > 0) e = hipMemcpyAsync(d_fr, fr, sizeof(double) * 3 * n, hipMemcpyHostToDevice, m->stream);
     int rc = GF_OK;
     if (e == hipSuccess && n > 0) rc = gf_flavor_histogram_device(m, d_fr, n, nbins, d_c);
     if (e == hipSuccess && rc == GF_OK) e = hipMemcpyAsync(counts, d_c, sizeof(uint64_t) * nbin3, hipMemcpyDeviceToHost, m->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
-    if (d_fr) (void)hipFree(d_fr);
-    (void)hipFree(d_c);
+    if (d_fr) (void)gf_cached_free(d_fr);
+    (void)gf_cached_free(d_c);
     if (rc != GF_OK) return rc;
     return e != hipSuccess ? gf_hip_fail(e, "gf_flavor_histogram") : GF_OK;
 }

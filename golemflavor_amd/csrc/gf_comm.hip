@@ -12,7 +12,7 @@
 
 #include "../../include/golemflavor_hip.h"
 #include "gf_internal.h"
-#include "gf_devcache.h"                // large device allocations are cached, not handed back to the driver (hipMalloc / hipFree are macros from here on)
+#include "gf_devcache.h"                // large device allocations are cached, not handed back to the driver
 
 static_assert(GF_COMM_ID_BYTES == NCCL_UNIQUE_ID_BYTES, "RCCL unique id size changed");
 
@@ -116,7 +116,7 @@ int gf_comm_broadcast(gf_comm* c, void* host_buf, size_t bytes, int root)
     if (bytes == 0) return GF_OK;
     GF_CHIP(hipSetDevice(c->device));
     void* d = nullptr;
-    GF_CHIP(hipMalloc(&d, bytes));
+    GF_CHIP(gf_cached_malloc(&d, bytes));
     int rc = GF_OK;
     hipError_t e = hipSuccess;
     if (c->rank == root) e = hipMemcpyAsync(d, host_buf, bytes, hipMemcpyHostToDevice, c->stream);
@@ -130,7 +130,7 @@ int gf_comm_broadcast(gf_comm* c, void* host_buf, size_t bytes, int root)
     if (e == hipSuccess) e = e_copy;
     if (r != ncclSuccess) rc = comm_fail("ncclBroadcast", ncclGetErrorString(r));
     else if (e != hipSuccess) rc = comm_fail("gf_comm_broadcast", hipGetErrorString(e));
-    (void)hipFree(d);
+    (void)gf_cached_free(d);
     return rc;
 }
 
@@ -184,12 +184,12 @@ int gf_comm_barrier(gf_comm* c)
     if (!c) return GF_ERR_INVALID_ARG;
     GF_CHIP(hipSetDevice(c->device));
     int* d = nullptr;
-    GF_CHIP(hipMalloc((void**)&d, sizeof(int)));
+    GF_CHIP(gf_cached_malloc((void**)&d, sizeof(int)));
     hipError_t e = hipMemsetAsync(d, 0, sizeof(int), c->stream);
     ncclResult_t r = ncclSuccess;
     if (e == hipSuccess) r = ncclAllReduce(d, d, 1, ncclInt, ncclSum, c->comm, c->stream);
     if (e == hipSuccess && r == ncclSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
+    (void)gf_cached_free(d);
     if (r != ncclSuccess) return comm_fail("ncclAllReduce", ncclGetErrorString(r));
     if (e != hipSuccess) return comm_fail("gf_comm_barrier", hipGetErrorString(e));
     return GF_OK;
@@ -213,7 +213,7 @@ int gf_device_malloc(int device, size_t bytes, void** dptr)
     if (!dptr || bytes == 0) return GF_ERR_INVALID_ARG;
     *dptr = nullptr;
     GF_CHIP(hipSetDevice(device));
-    GF_CHIP(hipMalloc(dptr, bytes));
+    GF_CHIP(gf_cached_malloc(dptr, bytes));
     return GF_OK;
 }
 
@@ -221,7 +221,7 @@ int gf_device_release(int device, void* dptr)
 {
     if (!dptr) return GF_OK;
     GF_CHIP(hipSetDevice(device));
-    GF_CHIP(hipFree(dptr));
+    GF_CHIP(gf_cached_free(dptr));
     return GF_OK;
 }
 

@@ -10,7 +10,9 @@
 // cached free does the same, so no caller can tell the difference -- except that reused memory holds its previous content where
 // freshly mapped memory holds zeros (nothing in the library reads a large buffer before writing it).
 //
-// Include AFTER <hip/hip_runtime.h>: the two macros at the end route this translation unit's hipMalloc / hipFree calls here.
+// A call says which allocator it means: gf_cached_malloc / gf_cached_free here, hipMalloc / hipFree for the driver, GfMem (gf_host.h)
+// where a helper allocates for its caller.  What the cache gave must go back through gf_cached_free: a cached block freed with
+// hipFree stays in the cache's books under its old size.  DESIGN.md lists who takes memory from which.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -23,8 +25,3 @@ size_t gf_devcache_trim(int device);
 // diagnostics: bytes held idle / handed out through the cache on `device`
 void gf_devcache_stats(int device, size_t* idle_bytes, size_t* live_bytes, unsigned long long* reuses);
 }
-
-#ifndef GF_DEVCACHE_IMPL
-#define hipMalloc(p, n) gf_cached_malloc((void**)(p), (size_t)(n))
-#define hipFree(p) gf_cached_free((void*)(p))
-#endif

@@ -1,5 +1,4 @@
 // gf_devcache.hip -- see gf_devcache.h
-#define GF_DEVCACHE_IMPL
 #include "gf_devcache.h"
 #include "gf_internal.h"
 

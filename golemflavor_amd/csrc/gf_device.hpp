@@ -51,7 +51,7 @@ __device__ __forceinline__ double fast_rcp(double x)
 }
 
 // library sin/cos for huge or non-finite arguments, out of line (Payne-Hanek needs ~100 registers)
-static __device__ __attribute__((noinline)) void sincos_cold(double x, double* sn, double* cs) { sincos(x, sn, cs); }
+[[maybe_unused]] static __device__ __attribute__((noinline)) void sincos_cold(double x, double* sn, double* cs) { sincos(x, sn, cs); }
 
 // sin and cos of x, |x| < 2^20 * pi/2: three-step Cody-Waite reduction with FMA (33-bit pieces of pi/2,
 // the published fdlibm split), then the fdlibm minimax kernels on [-pi/4, pi/4].  Absolute error

@@ -17,7 +17,7 @@
 #include <stdint.h>
 
 #include "gf_devcache.h"                // the transposed chain and the per-walker functions are each about the size of one chain
-#include "gf_host.h"                    // (after gf_devcache.h: GfScratch allocates through the cache)
+#include "gf_host.h"
 #include "gf_diag.h"
 #include "gf_diag.hpp"
 
@@ -184,7 +184,7 @@ int gf_diag_run(hipStream_t st, const double* d_chain, int64_t chain_stride, int
     const int nlags = (int)(spec->maxlag < 0 ? nsteps - 1 : spec->maxlag) + 1;
     const int64_t K = (int64_t)nwalkers * ndim;
     const size_t per = (size_t)nchains * ndim;
-    GfScratch buf;
+    GfScratch buf(GF_MEM_CACHED);
     double *d_t = nullptr, *d_racf = nullptr, *d_mean = nullptr, *d_halves = nullptr, *d_rho = nullptr, *d_rho_mean = nullptr;
     double *d_tau = nullptr, *d_tau_mean = nullptr, *d_rhat = nullptr;
     int64_t *d_window = nullptr, *d_window_mean = nullptr;
@@ -274,7 +274,7 @@ int gf_chain_diagnostics(gf_model* m, const double* chain, int64_t nsteps, int n
     if (rc != GF_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     const size_t bytes = sizeof(double) * (size_t)nsteps * nwalkers * ndim;
-    GfScratch buf;
+    GfScratch buf(GF_MEM_CACHED);
     double* d_chain = nullptr;
     GF_HIP(buf.get(&d_chain, bytes));
     GF_HIP(hipMemcpyAsync(d_chain, chain, bytes, hipMemcpyHostToDevice, st));

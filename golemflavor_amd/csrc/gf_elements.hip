@@ -14,7 +14,7 @@
 #include <stdint.h>
 
 #include "gf_devcache.h"
-#include "gf_host.h"                    // (after gf_devcache.h: GfScratch allocates through the cache)
+#include "gf_host.h"
 #include "gf_elements.h"
 #include "gf_elements_exact.hpp"
 
@@ -120,7 +120,7 @@ hipError_t gf_element_run(hipStream_t st, const double* d_in, int64_t in_stride,
     if (blocks > cap) blocks = cap;
     const dim3 grid((unsigned)blocks, 1u, (unsigned)nchains), block((unsigned)(waves * EL_WAVE));
     const size_t lds = lds_wave * waves;
-    GfScratch buf;
+    GfScratch buf(GF_MEM_CACHED);
     unsigned long long* d_mask = nullptr;
     hipError_t e = buf.get(&d_mask, sizeof(unsigned long long) * (size_t)ntiles * nchains);
     if (e != hipSuccess) return e;
@@ -170,7 +170,7 @@ int gf_element_rows(gf_model* m, const double* rows, int64_t nrows, int width_in
     if (rc != GF_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     const size_t nin = sizeof(double) * (size_t)nrows * width_in, nout = sizeof(double) * (size_t)nrows * wout;
-    GfScratch buf;
+    GfScratch buf(GF_MEM_CACHED);
     double *d_in = nullptr, *d_out = nullptr;
     hipError_t e = buf.get(&d_in, nin);
     if (e == hipSuccess) e = buf.get(&d_out, nout);

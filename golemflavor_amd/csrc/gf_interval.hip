@@ -26,7 +26,7 @@
 #include <vector>
 
 #include "gf_devcache.h"
-#include "gf_host.h"                    // (after gf_devcache.h: GfScratch allocates through the cache)
+#include "gf_host.h"
 #include "gf_interval.h"
 #include "gf_interval.hpp"
 
@@ -324,7 +324,7 @@ int gf_interval_run(hipStream_t st, const double* d_rows, int64_t chain_stride, 
     int bchains = (int)std::min<size_t>((size_t)nchains, std::max<size_t>(1, iv_scratch_cap() / (2 * sizeof(uint64_t) * chain_keys)));
     bchains = std::max(1, std::min(bchains, 65535 / W));
     const size_t bsegs = (size_t)bchains * W;
-    GfScratch buf;
+    GfScratch buf(GF_MEM_CACHED);
     unsigned long long *d_a = nullptr, *d_b = nullptr, *d_nuniq = nullptr;
     unsigned int* d_hist = nullptr;
     int* d_flags = nullptr;
@@ -439,7 +439,7 @@ int gf_column_intervals(gf_model* m, const double* rows, int64_t nrows, int widt
     rc = gf_model_internal(m, &c, &tb, &ptab, &stream, &device);
     if (rc != GF_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-    GfScratch buf;
+    GfScratch buf(GF_MEM_CACHED);
     double* d_rows = nullptr;
     const size_t bytes = sizeof(double) * (size_t)nrows * width;
     hipError_t e = buf.get(&d_rows, bytes);

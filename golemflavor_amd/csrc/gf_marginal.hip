@@ -23,7 +23,7 @@
 #include <vector>
 
 #include "gf_devcache.h"
-#include "gf_host.h"                    // (after gf_devcache.h: GfScratch allocates through the cache)
+#include "gf_host.h"
 #include "gf_marginal.h"
 #include "gf_region.h"
 
@@ -408,7 +408,7 @@ int gf_marginal_run(hipStream_t st, const double* d_rows, int64_t chain_stride, 
     const int nb1 = sp->nbins1, nb2 = sp->nbins2, npairs = W * (W - 1) / 2, R = sp->nranks + 2 * sp->nq;
     const size_t n_c1 = (size_t)nchains * W * nb1, n_c2 = (size_t)nchains * npairs * nb2 * nb2;
     const int64_t nchunks = std::max<int64_t>(1, (nrows + MG_CHUNK - 1) / MG_CHUNK);
-    GfScratch buf;
+    GfScratch buf(GF_MEM_CACHED);
     double *d_e1 = nullptr, *d_e2 = nullptr, *d_part = nullptr, *d_sum = nullptr, *d_mean = nullptr, *d_part2 = nullptr, *d_sum2 = nullptr, *d_cov = nullptr;
     unsigned long long *d_c1 = nullptr, *d_c2 = nullptr, *d_nvalid = nullptr, *d_ncol = nullptr;
     hipError_t e = buf.get(&d_e1, sizeof(double) * W * (nb1 + 2));
@@ -596,7 +596,7 @@ int gf_marginals(gf_model* m, const double* rows, int64_t nrows, int width, cons
     rc = gf_model_internal(m, &c, &tb, &ptab, &stream, &device);
     if (rc != GF_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-    GfScratch buf;
+    GfScratch buf(GF_MEM_CACHED);
     double* d_rows = nullptr;
     const size_t bytes = sizeof(double) * (size_t)nrows * width;
     hipError_t e = buf.get(&d_rows, bytes);

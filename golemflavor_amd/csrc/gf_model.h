@@ -39,7 +39,7 @@ struct gf_model {
     int table_nside = 0;         // ... and while > 0 lnprob is lnprior + the table's value; c.mode stays BSM_GAUSS
     int64_t table_cap = 0;       // nodes d_table has room for: a replacement that fits is written in place
     std::vector<double*> tables_retired;   // tables a larger replacement outgrew, kept until the model goes: a run set created
-                                           // before the replacement still reads its own (gf_cube_runs.hpp)
+                                           // before the replacement still reads its own (gf_cube_runs.hip)
     uint64_t likelihood_sets = 0;   // successful gf_model_set_table_likelihood / gf_model_set_binned_measurement calls: what tells a run
                                     // that has begun that its likelihood was replaced, in place included (gf_model_likelihood_sets)
     std::mutex call_mu;          // serialises the entry points that use the model's staging buffers / the stream's unitarity workspace

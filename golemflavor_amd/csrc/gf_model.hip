@@ -10,7 +10,7 @@
 #include <mutex>
 #include <new>
 
-#include "gf_devcache.h"                // large device allocations are cached, not handed back to the driver (hipMalloc / hipFree are macros from here on)
+#include "gf_devcache.h"                // large device allocations are cached, not handed back to the driver
 #include "gf_host.h"
 #include "gf_model.h"
 #include "gf_spectrum.h"
@@ -403,18 +403,18 @@ void gf_model_destroy(gf_model* m)
     (void)hipSetDevice(m->device);
     if (m->stream) (void)hipStreamSynchronize(m->stream);
     pool_release(m->device, m->stream, m->d_block);
-    if (m->d_theta) (void)hipFree(m->d_theta);
-    if (m->d_out) (void)hipFree(m->d_out);
-    if (m->d_status) (void)hipFree(m->d_status);
+    if (m->d_theta) (void)gf_cached_free(m->d_theta);
+    if (m->d_out) (void)gf_cached_free(m->d_out);
+    if (m->d_status) (void)gf_cached_free(m->d_status);
     if (m->h_pin) (void)hipHostFree(m->h_pin);
     for (int k = 0; k < 2; ++k) {
         if (m->ev_up[k]) (void)hipEventDestroy(m->ev_up[k]);
         if (m->ev_down[k]) (void)hipEventDestroy(m->ev_down[k]);
     }
-    if (m->d_cube) (void)hipFree(m->d_cube);
-    if (m->d_btab) (void)hipFree(m->d_btab);
-    if (m->d_table) (void)hipFree(m->d_table);
-    for (double* t : m->tables_retired) (void)hipFree(t);
+    if (m->d_cube) (void)gf_cached_free(m->d_cube);
+    if (m->d_btab) (void)gf_cached_free(m->d_btab);
+    if (m->d_table) (void)gf_cached_free(m->d_table);
+    for (double* t : m->tables_retired) (void)gf_cached_free(t);
     delete m;
 }
 
@@ -449,14 +449,14 @@ int gf_model_set_binned_measurement(gf_model* m, int nbins, const double* fr_bin
     GF_HIP(hipSetDevice(m->device));
     if (m->stream) GF_HIP(hipStreamSynchronize(m->stream));              // a replaced table may still be read there
     double* d = m->d_btab;
-    if (!d) GF_HIP(hipMalloc((void**)&d, sizeof(double) * GF_BINNED_STRIDE * GF_MAX_BINS));
+    if (!d) GF_HIP(gf_cached_malloc((void**)&d, sizeof(double) * GF_BINNED_STRIDE * GF_MAX_BINS));
     hipStream_t up = nullptr;
     hipError_t e = pool_stream(m->device, &up);
     if (e == hipSuccess) e = hipMemcpyAsync(d, tab, sizeof(double) * GF_BINNED_STRIDE * (size_t)nbins, hipMemcpyHostToDevice, up);
     if (e == hipSuccess) e = hipStreamSynchronize(up);                   // `tab` goes out of scope
     if (up) pool_release(m->device, up, nullptr);
     if (e != hipSuccess) {
-        if (!m->d_btab) (void)hipFree(d);
+        if (!m->d_btab) (void)gf_cached_free(d);
         return gf_hip_fail(e, "gf_model_set_binned_measurement");
     }
     m->d_btab = d;
@@ -502,7 +502,7 @@ int gf_model_set_table_likelihood(gf_model* m, int nside, const double* values)
     const bool grow = nodes > m->table_cap;
     if (grow) {
         d = nullptr;
-        GF_HIP(hipMalloc((void**)&d, sizeof(double) * (size_t)nodes));
+        GF_HIP(gf_cached_malloc((void**)&d, sizeof(double) * (size_t)nodes));
     }
     hipStream_t up = nullptr;
     hipError_t e = pool_stream(m->device, &up);
@@ -510,7 +510,7 @@ int gf_model_set_table_likelihood(gf_model* m, int nside, const double* values)
     if (e == hipSuccess) e = hipStreamSynchronize(up);                   // `values` is the caller's
     if (up) pool_release(m->device, up, nullptr);
     if (e != hipSuccess) {
-        if (grow) (void)hipFree(d);
+        if (grow) (void)gf_cached_free(d);
         return gf_hip_fail(e, "gf_model_set_table_likelihood");
     }
     if (grow) {

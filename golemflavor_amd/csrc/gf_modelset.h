@@ -1,5 +1,5 @@
 // gf_modelset.h -- a set of models on one device that share ndim and mode, as the ensemble sampler (gf_sampler_host.hip: one model for
-// every chain, or one per chain) and the cube runs (gf_cube_runs.hpp: one per run) hand them to their kernels: per-model device
+// every chain, or one per chain) and the cube runs (gf_cube_runs.hip: one per run) hand them to their kernels: per-model device
 // arrays of the constants, the BSM, prior, binned and likelihood tables, and the one likelihood every model of the set carries.
 // Host code only (gf_modelset.hip).
 #pragma once

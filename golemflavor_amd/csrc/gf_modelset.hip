@@ -1,5 +1,5 @@
 // gf_modelset.hip -- see gf_modelset.h.  Host code only: no kernel.
-#include "gf_devcache.h"                // large device allocations are cached, not handed back to the driver (hipMalloc / hipFree are macros from here on)
+#include "gf_devcache.h"                // large device allocations are cached, not handed back to the driver
 #include "gf_host.h"
 #include "gf_modelset.h"
 
@@ -37,7 +37,7 @@ int gf_modelset_create(GfModelSet* set, gf_model* const* models, int nmodels, co
     // thread is capturing its sampler's graph fails and poisons that capture on this runtime
     hipError_t e = hipSetDevice(set->device);
     auto put = [&](void** d, const void* src, size_t bytes) {
-        if (e == hipSuccess) e = hipMalloc(d, bytes);
+        if (e == hipSuccess) e = gf_cached_malloc(d, bytes);
         if (e == hipSuccess) e = hipMemcpyAsync(*d, src, bytes, hipMemcpyHostToDevice, set->stream);
     };
     put((void**)&set->d_commons, hc.data(), sizeof(GfCommon) * nm);
@@ -100,7 +100,7 @@ void gf_modelset_free(GfModelSet* set)
         (void)hipStreamSynchronize(set->stream);
     }
     void* ptrs[] = {set->d_commons, (void*)set->d_tbs, (void*)set->d_ptabs, (void*)set->d_btabs, (void*)set->d_ttabs, set->d_tsides};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
+    for (void* p : ptrs) if (p) (void)gf_cached_free(p);
     set->d_commons = nullptr; set->d_tbs = nullptr; set->d_ptabs = nullptr; set->d_btabs = nullptr; set->d_ttabs = nullptr; set->d_tsides = nullptr;
     set->models.clear();
 }

@@ -13,7 +13,7 @@
 #include <vector>
 
 #include "gf_devcache.h"
-#include "gf_host.h"                    // (after gf_devcache.h: GfScratch allocates through the cache)
+#include "gf_host.h"
 #include "gf_rowsets.h"
 #include "gf_nested_post.hpp"
 #include "gf_weights.h"
@@ -53,7 +53,7 @@ __global__ __launch_bounds__(NP_BLOCK) void k_np_gather(const NpArgs a, const Gf
 
 // ---- host --------------------------------------------------------------------------------------------------------------------------
 struct NpWork {
-    GfScratch buf;
+    GfScratch buf{GF_MEM_CACHED};
     NpArgs a = {};
     GfNestedView v = {};
     std::vector<GfNestedRunState> state;
@@ -189,7 +189,7 @@ int np_reduce(gf_nested* s, int64_t nrows, int with_fr, bool elements, const gf_
     int rc = gf_rowsets_check(v.nruns, nrows, width, spec);
     if (rc != GF_OK) return rc;
     GF_HIP(hipSetDevice(v.device));
-    GfScratch buf; GfRowSets r = {nullptr, 0, v.nruns, nrows, 0, v.device, v.stream, v.cus}, e = r;
+    GfScratch buf(GF_MEM_CACHED); GfRowSets r = {nullptr, 0, v.nruns, nrows, 0, v.device, v.stream, v.cus}, e = r;
     rc = gf_rowsets_take(buf, r, elements ? v.ndim : width, who, &r);
     if (elements) rc = gf_rowsets_take(buf, r, width, who, &e);
     if (rc == GF_OK) rc = np_rows(s, nrows, with_fr, r.d_rows, nullptr, who);
@@ -260,7 +260,7 @@ int gf_nested_posterior_rows(gf_nested* s, int64_t nrows, int with_fr, double* r
     if (gf_internal_nested_view(s, &v, nullptr) != GF_OK || nrows < 1 || !rows) return GF_ERR_INVALID_ARG;
     GF_HIP(hipSetDevice(v.device));
     const size_t RN = (size_t)v.nruns * nrows, width = (with_fr ? 3 : 0) + (size_t)v.ndim;
-    GfScratch buf; double* d_rows = nullptr; int64_t* d_index = nullptr;
+    GfScratch buf(GF_MEM_CACHED); double* d_rows = nullptr; int64_t* d_index = nullptr;
     buf.take(&d_rows, sizeof(double) * RN * width, who);
     int rc = buf.take(&d_index, sizeof(int64_t) * RN, who);
     if (rc == GF_OK) rc = np_rows(s, nrows, with_fr, d_rows, d_index, who);

@@ -23,7 +23,7 @@
 #include <vector>
 
 #include "gf_devcache.h"
-#include "gf_host.h"                    // (after gf_devcache.h: GfScratch allocates through the cache)
+#include "gf_host.h"
 #include "gf_device.hpp"
 #include "gf_ns_toys.hpp"
 #include "gf_weights.h"
@@ -275,7 +275,7 @@ int gf_nested_toys_evidence(gf_nested* s, const double* bf, const double* smeari
     const int Tb = (int)std::min<size_t>(std::min<size_t>((size_t)T, (size_t)65535 * NT_TILE), std::max<size_t>(1, nt_scratch_cap() / per_toy));
     const size_t N = (size_t)total, RL = (size_t)R * (size_t)a.maxleaves;
 
-    GfScratch buf;
+    GfScratch buf(GF_MEM_CACHED);
     GfWeightRun* d_runs = nullptr;
     double *d_lnw = nullptr, *d_theta = nullptr, *d_fr = nullptr;
     int32_t* d_st = nullptr;

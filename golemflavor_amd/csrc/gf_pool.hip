@@ -9,7 +9,7 @@
 #include <unordered_map>
 #include <vector>
 
-#include "gf_devcache.h"                // large device allocations are cached, not handed back to the driver (hipMalloc / hipFree are macros from here on)
+#include "gf_devcache.h"                // large device allocations are cached, not handed back to the driver
 #include "gf_host.h"
 #include "gf_pool.h"
 
@@ -43,9 +43,9 @@ struct UniWork {
     }
     void release()
     {
-        if (d_uq) (void)hipFree(d_uq);
-        if (d_wq) (void)hipFree(d_wq);
-        if (d_t2sn) (void)hipFree(d_t2sn);
+        if (d_uq) (void)gf_cached_free(d_uq);
+        if (d_wq) (void)gf_cached_free(d_wq);
+        if (d_t2sn) (void)gf_cached_free(d_t2sn);
         d_uq = nullptr; d_wq = nullptr; d_t2sn = nullptr; uq_cap = wq_cap = 0;
     }
     // the pinned words the arbitration kernel and the host share, allocated on first use
@@ -157,9 +157,9 @@ int ensure_uq(UniWork* w, hipStream_t st, int layout, int64_t n, int64_t* items_
     GF_HIP(hipStreamSynchronize(st));          // earlier launches may still use the old buffers
     GfUniQueue hdr = {0, 0, 0, 0, {0}};
     if (cap != w->uq_cap) {
-        if (w->d_uq) (void)hipFree(w->d_uq);
+        if (w->d_uq) (void)gf_cached_free(w->d_uq);
         w->d_uq = nullptr; w->uq_cap = 0;
-        GF_HIP(hipMalloc((void**)&w->d_uq, sizeof(GfArbQueue) + sizeof(GfArbItem) * (size_t)cap));
+        GF_HIP(gf_cached_malloc((void**)&w->d_uq, sizeof(GfArbQueue) + sizeof(GfArbItem) * (size_t)cap));
         GfArbQueue ah;
         std::memset(&ah, 0, sizeof(ah));
         ah.cap = (unsigned int)cap;
@@ -168,11 +168,11 @@ int ensure_uq(UniWork* w, hipStream_t st, int layout, int64_t n, int64_t* items_
         w->uq_cap = cap;
     }
     if (need_w > w->wq_cap) {
-        if (w->d_wq) (void)hipFree(w->d_wq);
-        if (w->d_t2sn) (void)hipFree(w->d_t2sn);
+        if (w->d_wq) (void)gf_cached_free(w->d_wq);
+        if (w->d_t2sn) (void)gf_cached_free(w->d_t2sn);
         w->d_wq = nullptr; w->d_t2sn = nullptr; w->wq_cap = 0;
-        GF_HIP(hipMalloc((void**)&w->d_wq, sizeof(GfUniQueue) + sizeof(unsigned long long) * (size_t)need_w));
-        GF_HIP(hipMalloc((void**)&w->d_t2sn, sizeof(double) * 18 * (size_t)need_w));
+        GF_HIP(gf_cached_malloc((void**)&w->d_wq, sizeof(GfUniQueue) + sizeof(unsigned long long) * (size_t)need_w));
+        GF_HIP(gf_cached_malloc((void**)&w->d_t2sn, sizeof(double) * 18 * (size_t)need_w));
         hdr.cap = (unsigned int)need_w;
         GF_HIP(hipMemcpyAsync(w->d_wq, &hdr, offsetof(GfUniQueue, items), hipMemcpyHostToDevice, st));
         GF_HIP(hipStreamSynchronize(st));
@@ -225,7 +225,7 @@ hipError_t pool_stream(int device, hipStream_t* stream)
 
 hipError_t pool_block(int device, void** block)
 {
-    return pool_take(&DevicePool::blocks, device, block, [](void** b) { return hipMalloc(b, CONST_BLOCK_BYTES); });
+    return pool_take(&DevicePool::blocks, device, block, [](void** b) { return gf_cached_malloc(b, CONST_BLOCK_BYTES); });
 }
 
 void pool_release(int device, hipStream_t stream, void* block)
@@ -256,7 +256,7 @@ void pool_release(int device, hipStream_t stream, void* block)
     }
     if (drop && !trim) delete drop;
     if (stream) (void)hipStreamDestroy(stream);
-    if (block) (void)hipFree(block);
+    if (block) (void)gf_cached_free(block);
 }
 
 int check_queue_overflow(int device, hipStream_t st)
@@ -395,7 +395,7 @@ int gf_device_trim(int device, size_t* released_bytes)
         total += w->bytes();
         w->release();
     }
-    for (void* b : blocks) { (void)hipFree(b); total += CONST_BLOCK_BYTES; }
+    for (void* b : blocks) { (void)gf_cached_free(b); total += CONST_BLOCK_BYTES; }
     {
         std::lock_guard<std::mutex> lk(g_pool_mu);
         DevicePool& dp = g_pool[device];

@@ -7,7 +7,7 @@
 #include <stdint.h>
 
 #include "gf_devcache.h"                // the scratch buffers of a scan's post-processing are the multi-gigabyte allocations the cache exists for
-#include "gf_host.h"                    // (after gf_devcache.h: GfScratch allocates through the cache)
+#include "gf_host.h"
 #include "gf_rowsets.h"
 #include "gf_diag.h"
 
@@ -73,7 +73,7 @@ int chain_reduce(gf_sampler* s, gf_model* const* models, int with_fr, bool eleme
     if (rc != GF_OK) return rc;
     if (!elements && check_chain_models(v, models) != GF_OK) return GF_ERR_INVALID_ARG;
     GF_HIP(hipSetDevice(v.device));
-    GfScratch buf; GfRowSets r;
+    GfScratch buf(GF_MEM_CACHED); GfRowSets r;
     if (!elements) rc = chain_rows(s, v, models, with_fr, buf, who, &r);
     else if ((rc = gf_rowsets_take(buf, chain_as_rows(v), width, who, &r)) == GF_OK) rc = gf_rowsets_elements(chain_as_rows(v), plan, r, who);
     return rc != GF_OK ? rc : gf_rowsets_reduce(r, spec, out);
@@ -109,7 +109,7 @@ int gf_sampler_postprocess_with(gf_sampler* s, gf_model* const* models, double* 
     if (v.nstored == 0) return GF_OK;
     const int64_t per_chain = v.nstored * v.nwalkers;
     const size_t nbin3 = counts ? (size_t)nbins * nbins * nbins : 0;
-    GfScratch buf;
+    GfScratch buf(GF_MEM_CACHED);
     double* d_fr = nullptr; int32_t* d_st = nullptr; uint64_t* d_c = nullptr;
     const char* who = "gf_sampler_postprocess";
     buf.take(&d_fr, sizeof(double) * 3 * per_chain, who);             // sticky (gf_host.h): a run of takes is checked once
@@ -160,7 +160,7 @@ int gf_sampler_postprocess_rows_device(gf_sampler* s, gf_model* const* models, d
     hipStream_t st = v.stream;
     const int64_t per_chain = v.nstored * v.nwalkers;
     if (per_chain == 0) { GF_HIP(hipStreamSynchronize(st)); return GF_OK; }
-    GfScratch buf;
+    GfScratch buf(GF_MEM_CACHED);
     double* d_fr = nullptr; int32_t* d_st = nullptr;
     buf.take(&d_fr, sizeof(double) * 3 * per_chain * v.nchains, "gf_sampler_postprocess_rows_device");
     if (buf.take(&d_st, sizeof(int32_t) * per_chain * v.nchains, "gf_sampler_postprocess_rows_device") != GF_OK) return buf.failed;
@@ -191,7 +191,7 @@ int gf_sampler_postprocess_rows(gf_sampler* s, gf_model* const* models, double* 
     constexpr int MAX_GROUPS = 16;
     const int per_group = (v.nchains + MAX_GROUPS - 1) / MAX_GROUPS;
     const int ngroups = (v.nchains + per_group - 1) / per_group;
-    GfScratch buf;
+    GfScratch buf(GF_MEM_CACHED);
     double *d_fr = nullptr, *d_rows = nullptr; int32_t* d_st = nullptr;
     void* copy_stream = nullptr;
     hipEvent_t ev[MAX_GROUPS] = {};
@@ -247,7 +247,7 @@ int gf_sampler_regions(gf_sampler* s, gf_model* const* models, int nbins, int ra
     GF_HIP(hipSetDevice(v.device));
     hipStream_t st = v.stream;
     const int64_t per_chain = v.nstored * v.nwalkers;
-    GfScratch buf; GfRegionSets sets; double* d_fr = nullptr; int32_t* d_st = nullptr;
+    GfScratch buf(GF_MEM_CACHED); GfRegionSets sets; double* d_fr = nullptr; int32_t* d_st = nullptr;
     rc = sets.begin(buf, v.nchains, nbins, cus, st, who);
     if (rc == GF_OK && per_chain > 0) { buf.take(&d_fr, sizeof(double) * 3 * per_chain, who); rc = buf.take(&d_st, sizeof(int32_t) * per_chain, who); }
     hipError_t e = hipSuccess;
@@ -310,7 +310,7 @@ int gf_sampler_spectrum(gf_sampler* s, gf_model* const* models, const gf_spectru
     if (rc != GF_OK) return rc;
     GF_HIP(hipSetDevice(v.device));
     hipStream_t st = v.stream;
-    GfScratch buf;
+    GfScratch buf(GF_MEM_CACHED);
     double* d_slab = nullptr; int32_t* d_st = nullptr;
     buf.take(&d_slab, sizeof(double) * 3 * (size_t)per_chain * nbins_e, who);
     if (buf.take(&d_st, sizeof(int32_t) * (size_t)per_chain, who) != GF_OK) return buf.failed;

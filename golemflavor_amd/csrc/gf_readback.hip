@@ -446,7 +446,7 @@ int gf_internal_pinned_d2h_rate(int device, size_t bytes, double* gbps)
     void *h = nullptr, *d = nullptr;
     hipStream_t st = nullptr;
     hipError_t e = hipHostMalloc(&h, 2 * piece, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMalloc(&d, piece);
+    if (e == hipSuccess) e = gf_cached_malloc(&d, piece);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipMemcpyAsync(h, d, piece, hipMemcpyDeviceToHost, st);          // warm-up
     if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -457,7 +457,7 @@ int gf_internal_pinned_d2h_rate(int device, size_t bytes, double* gbps)
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (st) (void)hipStreamDestroy(st);
-    if (d) (void)hipFree(d);
+    if (d) (void)gf_cached_free(d);
     if (h) (void)hipHostFree(h);
     if (e != hipSuccess) return gf_hip_fail(e, "gf_internal_pinned_d2h_rate");
     *gbps = (double)done / dt / 1e9;

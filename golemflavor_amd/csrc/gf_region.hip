@@ -21,7 +21,7 @@
 #include <vector>
 
 #include "gf_devcache.h"
-#include "gf_host.h"                    // (after gf_devcache.h: GfScratch allocates through the cache)
+#include "gf_host.h"
 #include "gf_region.h"
 
 namespace {
@@ -356,7 +356,7 @@ int gf_region_run_shape(hipStream_t st, const uint64_t* d_counts, int nchains, i
 
     // one small block: sums [nchains][2] | nnz [nchains] | cursor [nchains] | thres [nres] | level_in | level_out | mass [nres] | saturated [nres]
     const size_t n_u64 = (size_t)4 * nchains, small_bytes = 8 * (n_u64 + (size_t)4 * nres) + 4 * (size_t)nres;
-    GfScratch buf;
+    GfScratch buf(GF_MEM_CACHED);
     unsigned char* d_small = nullptr;
     double *d_x = nullptr, *d_y = nullptr, *d_vals = nullptr;
     int32_t* d_idx = nullptr;
@@ -464,7 +464,7 @@ int gf_region_run_shape(hipStream_t st, const uint64_t* d_counts, int nchains, i
             }
         if (one_list && cap > 0 && (cells || density) && e == hipSuccess) {
             // cells / density are host arrays [nchains][cap]: gather on the device, then one copy each
-            GfScratch gathered;
+            GfScratch gathered(GF_MEM_CACHED);
             long long* d_take = nullptr;
             int32_t* d_cells = nullptr;
             double* d_dens = nullptr;
@@ -529,7 +529,7 @@ int gf_flavor_region(gf_model* m, const double* fr, int64_t n, int nbins, int ra
     if (rc != GF_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     const size_t nb3 = (size_t)nbins * nbins * nbins;
-    GfScratch buf;
+    GfScratch buf(GF_MEM_CACHED);
     double* d_fr = nullptr;
     uint64_t* d_c = nullptr;
     hipError_t e = buf.get(&d_c, sizeof(uint64_t) * nb3);

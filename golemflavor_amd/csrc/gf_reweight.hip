@@ -21,7 +21,7 @@
 #include <vector>
 
 #include "gf_devcache.h"
-#include "gf_host.h"                    // (after gf_devcache.h: GfScratch allocates through the cache)
+#include "gf_host.h"
 #include "gf_rowsets.h"
 #include "gf_device.hpp"
 #include "gf_reweight.hpp"
@@ -235,7 +235,7 @@ int rw_run(gf_sampler* s, const gf_reweight_spec* spec, const RwWant& want, cons
     const size_t K = moments ? GF_WEIGHT_PART_COV : GF_WEIGHT_PART, CT = (size_t)nch * T, ncnt = 1 + (size_t)RW_CNT * T;
     const int width = (want.with_fr ? 3 : 0) + nd;
 
-    GfScratch buf;
+    GfScratch buf(GF_MEM_CACHED);
     double *d_fr = nullptr, *d_lnw = nullptr, *d_stat = nullptr, *d_mean = nullptr, *d_cov = nullptr, *d_thN = nullptr, *d_frN = nullptr;
     int32_t *d_st = nullptr, *d_stN = nullptr;
     GfWeightRun* d_runs = nullptr;
@@ -402,7 +402,7 @@ int rw_row_sets(gf_sampler* s, const gf_reweight_spec* rw, int64_t N, int with_f
 template <class Spec, class Out>
 int rw_reduce(gf_sampler* s, const gf_reweight_spec* rw, int64_t nrows, int with_fr, const Spec* spec, const Out* out, const char* who)
 {
-    GfScratch buf; GfRowSets r;
+    GfScratch buf(GF_MEM_CACHED); GfRowSets r;
     const int rc = rw_row_sets(s, rw, nrows, with_fr, [&](int nsets, int64_t n, int width) { return gf_rowsets_check(nsets, n, width, spec); }, buf, who, &r);
     return rc != GF_OK ? rc : gf_rowsets_reduce(r, spec, out);
 }
@@ -443,7 +443,7 @@ int gf_sampler_reweight_rows(gf_sampler* s, const gf_reweight_spec* spec, int64_
     if (!rw_view(s, spec, nrows, &v) || !rows) return GF_ERR_INVALID_ARG;
     GF_HIP(hipSetDevice(v.device));
     const size_t RN = (size_t)v.nchains * spec->ntargets * nrows, width = (with_fr ? 3 : 0) + (size_t)v.ndim;
-    GfScratch buf; RwWant w; w.N = nrows; w.with_fr = with_fr;
+    GfScratch buf(GF_MEM_CACHED); RwWant w; w.N = nrows; w.with_fr = with_fr;
     buf.take(&w.d_rows, sizeof(double) * RN * width, who);
     int rc = buf.take(&w.d_index, sizeof(int64_t) * RN, who);
     if (rc == GF_OK) rc = rw_run(s, spec, w, who);
@@ -473,7 +473,7 @@ int gf_sampler_reweight_regions(gf_sampler* s, const gf_reweight_spec* rw, int64
                                 double* level_out, double* mass, int32_t* cells, double* density)
 {
     const char* who = "gf_sampler_reweight_regions";
-    GfScratch buf; GfRowSets r;
+    GfScratch buf(GF_MEM_CACHED); GfRowSets r;
     int rc = rw_row_sets(s, rw, nrows, 1, [&](int nsets, int64_t, int) { return gf_region_check_args(nsets, nbins, radius, weights, coverage, ncov, cap); },
                          buf, who, &r);
     if (rc != GF_OK) return rc;

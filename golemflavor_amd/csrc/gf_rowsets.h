@@ -2,15 +2,16 @@
 // (gf_nested_post.hip), a reweighted chain (gf_reweight.hip) -- for the reductions "of every set on the device".  A source checks its
 // own arguments and says where its rows are (GfRowSets); the reducers by the spec's type, the element push, the region counts, the
 // spectrum step and the propagate loop are written here once.  The pieces take scratch (gf_host.h: the order matters) and enqueue work
-// where they are called.  Include after gf_host.h.
+// where they are called.
 #pragma once
+#include "gf_host.h"
 #include "gf_elements.h"
 #include "gf_interval.h"
 #include "gf_marginal.h"
 #include "gf_region.h"
 #include "gf_spectrum.h"
 
-namespace {
+#pragma GCC visibility push(hidden)
 
 // nsets sets of n rows [n][width] of doubles on the device, set k at d_rows + k * stride (written only where they are scratch)
 struct GfRowSets { double* d_rows; int64_t stride; int nsets; int64_t n; int width; int device; hipStream_t stream; int cus; };
@@ -113,4 +114,4 @@ int gf_propagate_sets(int device, hipStream_t st, int nsets, int64_t n, double* 
     return rc;
 }
 
-}  // namespace
+#pragma GCC visibility pop

@@ -4,8 +4,8 @@
 #include <chrono>
 #include <new>
 
-#include "gf_devcache.h"                // large device allocations are cached, not handed back to the driver (hipMalloc / hipFree are macros from here on)
-#include "gf_host.h"                    // (after gf_devcache.h: gf_alloc_arb_queue allocates through the cache)
+#include "gf_devcache.h"                // large device allocations are cached, not handed back to the driver
+#include "gf_host.h"
 #include "gf_modelset.h"
 #include "gf_sampler_launch.h"
 #include "gf_propose.hpp"               // lanes_per_walker
@@ -130,13 +130,13 @@ int sampler_create(gf_model* const* models, bool multi, int nchains, int nwalker
     // issued while ANOTHER host thread is capturing its sampler's graph fails and poisons that capture on this runtime
     hipStream_t st0 = set.stream;
     hipError_t e = hipSetDevice(set.device);
-    if (e == hipSuccess) e = hipMalloc((void**)&s->d_pos, sizeof(double) * nw * s->ndim);
-    if (e == hipSuccess) e = hipMalloc((void**)&s->d_lnp, sizeof(double) * nw);
-    if (e == hipSuccess) e = hipMalloc((void**)&s->d_naccept, sizeof(uint32_t) * nw);
-    if (e == hipSuccess) e = hipMalloc((void**)&s->d_flags, sizeof(uint32_t) * 4);
+    if (e == hipSuccess) e = gf_cached_malloc((void**)&s->d_pos, sizeof(double) * nw * s->ndim);
+    if (e == hipSuccess) e = gf_cached_malloc((void**)&s->d_lnp, sizeof(double) * nw);
+    if (e == hipSuccess) e = gf_cached_malloc((void**)&s->d_naccept, sizeof(uint32_t) * nw);
+    if (e == hipSuccess) e = gf_cached_malloc((void**)&s->d_flags, sizeof(uint32_t) * 4);
     if (e == hipSuccess && set.mode == MODE_BSM_GAUSS)
-        e = gf_alloc_arb_queue((size_t)nchains * (nwalkers / 2), st0, &s->d_pq, &s->d_pend_rows, &s->d_pend_ctl);
-    if (e == hipSuccess) e = hipMalloc((void**)&s->d_state, sizeof(GfStepState));
+        e = gf_alloc_arb_queue(GF_MEM_CACHED, (size_t)nchains * (nwalkers / 2), st0, &s->d_pq, &s->d_pend_rows, &s->d_pend_ctl);
+    if (e == hipSuccess) e = gf_cached_malloc((void**)&s->d_state, sizeof(GfStepState));
     if (e == hipSuccess) e = hipMemsetAsync(s->d_state, 0, sizeof(GfStepState), st0);
     if (e == hipSuccess) e = hipMemsetAsync(s->d_naccept, 0, sizeof(uint32_t) * nw, st0);
     if (e == hipSuccess) e = hipMemsetAsync(s->d_flags, 0, sizeof(uint32_t) * 4, st0);
@@ -321,10 +321,10 @@ int grow_chain(gf_sampler* s, int64_t need)
     GF_HIP(hipStreamSynchronize(st));
     const auto t_grow = std::chrono::steady_clock::now();
     struct Grow { std::chrono::steady_clock::time_point t0; ~Grow() { g_last_run_prologue[0] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); } } grow_{t_grow};
-    GF_HIP(hipMalloc((void**)&nc, sizeof(double) * nw * s->ndim * cap));
+    GF_HIP(gf_cached_malloc((void**)&nc, sizeof(double) * nw * s->ndim * cap));
     {
-        hipError_t e_ = hipMalloc((void**)&nl, sizeof(double) * nw * cap);
-        if (e_ != hipSuccess) { (void)hipFree(nc); return gf_hip_fail(e_, "hipMalloc(lnprob chain)"); }
+        hipError_t e_ = gf_cached_malloc((void**)&nl, sizeof(double) * nw * cap);
+        if (e_ != hipSuccess) { (void)gf_cached_free(nc); return gf_hip_fail(e_, "hipMalloc(lnprob chain)"); }
     }
     if (s->nstored > 0) {
         // every chain's stored prefix in one strided copy: row = chain, pitch = old / new chain stride
@@ -335,10 +335,10 @@ int grow_chain(gf_sampler* s, int64_t need)
             e_ = hipMemcpy2DAsync(nl, lrow * cap, s->d_lnp_chain, lrow * s->nstore_cap, lrow * s->nstored, s->nchains,
                                   hipMemcpyDeviceToDevice, st);
         if (e_ == hipSuccess) e_ = hipStreamSynchronize(st);                  // the old buffers are freed next
-        if (e_ != hipSuccess) { (void)hipFree(nc); (void)hipFree(nl); return gf_hip_fail(e_, "chain repack"); }
+        if (e_ != hipSuccess) { (void)gf_cached_free(nc); (void)gf_cached_free(nl); return gf_hip_fail(e_, "chain repack"); }
     }
-    if (s->d_chain) (void)hipFree(s->d_chain);
-    if (s->d_lnp_chain) (void)hipFree(s->d_lnp_chain);
+    if (s->d_chain) (void)gf_cached_free(s->d_chain);
+    if (s->d_lnp_chain) (void)gf_cached_free(s->d_lnp_chain);
     s->d_chain = nc; s->d_lnp_chain = nl; s->nstore_cap = cap;
     // the captured graph froze the old buffers and their capacity stride in its kernel arguments
     if (s->graph) { (void)hipGraphExecDestroy(s->graph); s->graph = nullptr; }
@@ -393,13 +393,13 @@ int alloc_lazy_lists(gf_sampler* s)
     int64_t cap = ((int64_t)64 << 20) / ((int64_t)s->nchains * (int64_t)(sizeof(double) * GF_PEND_STRIDE + 8));
     if (cap > 1024) cap = 1024;
     if (cap < 2 * pass) cap = 2 * pass;
-    GF_HIP(hipMalloc((void**)&s->d_lazy_rows, sizeof(double) * GF_PEND_STRIDE * (size_t)cap * s->nchains));
+    GF_HIP(gf_cached_malloc((void**)&s->d_lazy_rows, sizeof(double) * GF_PEND_STRIDE * (size_t)cap * s->nchains));
     {
-        hipError_t e_ = hipMalloc((void**)&s->d_lazy_mask, sizeof(unsigned long long) * (size_t)cap * s->nchains);
-        if (e_ != hipSuccess) { (void)hipFree(s->d_lazy_rows); s->d_lazy_rows = nullptr; return gf_hip_fail(e_, "hipMalloc(lazy list)"); }
+        hipError_t e_ = gf_cached_malloc((void**)&s->d_lazy_mask, sizeof(unsigned long long) * (size_t)cap * s->nchains);
+        if (e_ != hipSuccess) { (void)gf_cached_free(s->d_lazy_rows); s->d_lazy_rows = nullptr; return gf_hip_fail(e_, "hipMalloc(lazy list)"); }
     }
     s->lazy_cap = (int)cap;
-    if (hipMalloc((void**)&s->d_chain_stats, sizeof(unsigned long long) * 8 * (size_t)s->nchains) == hipSuccess)
+    if (gf_cached_malloc((void**)&s->d_chain_stats, sizeof(unsigned long long) * 8 * (size_t)s->nchains) == hipSuccess)
         (void)hipMemsetAsync(s->d_chain_stats, 0, sizeof(unsigned long long) * 8 * (size_t)s->nchains, s->set.stream);
     else { s->d_chain_stats = nullptr; (void)hipGetLastError(); }
     return GF_OK;
@@ -605,7 +605,7 @@ void gf_sampler_destroy(gf_sampler* s)
     gf_modelset_free(&s->set);          // behind it the stream has drained
     void* ptrs[] = {s->d_pos, s->d_lnp, s->d_naccept, s->d_flags, s->d_pq, s->d_pend_rows, s->d_pend_ctl, s->d_lazy_rows, s->d_lazy_mask, s->d_chain_stats,
                     s->d_state, s->d_chain, s->d_lnp_chain, s->d_stream_ids};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
+    for (void* p : ptrs) if (p) (void)gf_cached_free(p);
     if (s->graph) (void)hipGraphExecDestroy(s->graph);
     for (int i = 0; i < gf_sampler::FLIGHT; ++i) if (s->flight_ev[i]) (void)hipEventDestroy(s->flight_ev[i]);
     delete s;
@@ -618,7 +618,7 @@ int gf_sampler_set_stream_ids(gf_sampler* s, const uint64_t* ids)
     GF_HIP(hipSetDevice(s->set.device));
     hipStream_t st = s->set.stream;
     GF_HIP(hipStreamSynchronize(st));
-    if (!s->d_stream_ids) GF_HIP(hipMalloc((void**)&s->d_stream_ids, sizeof(uint64_t) * (size_t)s->nchains));
+    if (!s->d_stream_ids) GF_HIP(gf_cached_malloc((void**)&s->d_stream_ids, sizeof(uint64_t) * (size_t)s->nchains));
     GF_HIP(hipMemcpyAsync(s->d_stream_ids, ids, sizeof(uint64_t) * (size_t)s->nchains, hipMemcpyHostToDevice, st));
     GF_HIP(hipStreamSynchronize(st));
     if (s->graph) { (void)hipGraphExecDestroy(s->graph); s->graph = nullptr; }     // its kernel arguments froze the old pointer
@@ -636,7 +636,7 @@ int gf_sampler_set_state(gf_sampler* s, const double* pos)
     GF_HIP(hipMemcpyAsync(s->d_pos, pos, sizeof(double) * nw * s->ndim, hipMemcpyHostToDevice, st));
     // BSM posteriors: with the unitarity status, so that a start position the reference would have raised on is treated as such
     int32_t* d_st = nullptr;
-    if (s->set.mode == MODE_BSM_GAUSS) GF_HIP(hipMalloc((void**)&d_st, sizeof(int32_t) * nw));
+    if (s->set.mode == MODE_BSM_GAUSS) GF_HIP(gf_cached_malloc((void**)&d_st, sizeof(int32_t) * nw));
     int rc = GF_OK;
     if (!s->multi) {
         rc = gf_model_lnprob_on(s->set.models[0], st, s->d_pos, GF_LAYOUT_AOS, (int64_t)nw, s->d_lnp, nullptr, d_st);
@@ -650,7 +650,7 @@ int gf_sampler_set_state(gf_sampler* s, const double* pos)
         e = gf_launch_fix_start(d_st, (int64_t)nw, s->d_lnp, s->d_flags, st);
     }
     const hipError_t e2 = hipStreamSynchronize(st);
-    if (d_st) (void)hipFree(d_st);
+    if (d_st) (void)gf_cached_free(d_st);
     if (rc != GF_OK) return rc;
     if (e == hipSuccess) e = e2;
     if (e != hipSuccess) return gf_hip_fail(e, "gf_sampler_set_state");
@@ -906,11 +906,11 @@ int gf_sampler_walker_mean(gf_sampler* s, double* mean)
     if (s->nstored == 0) { GF_HIP(hipStreamSynchronize(st)); return GF_OK; }
     const size_t bytes = sizeof(double) * (size_t)s->nchains * s->nstored * s->ndim;
     double* d_mean = nullptr;
-    GF_HIP(hipMalloc((void**)&d_mean, bytes));
+    GF_HIP(gf_cached_malloc((void**)&d_mean, bytes));
     hipError_t e = gf_launch_walker_mean(s->d_chain, s->nstore_cap, s->nstored, s->nchains, s->nwalkers, s->ndim, d_mean, st);
     if (e == hipSuccess) e = hipMemcpyAsync(mean, d_mean, bytes, hipMemcpyDeviceToHost, st);
     hipError_t e2 = hipStreamSynchronize(st);
-    (void)hipFree(d_mean);
+    (void)gf_cached_free(d_mean);
     if (e == hipSuccess) e = e2;
     if (e != hipSuccess) return gf_hip_fail(e, "gf_sampler_walker_mean");
     return GF_OK;

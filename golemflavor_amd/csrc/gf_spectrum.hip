@@ -186,7 +186,7 @@ int gf_propagate_bins(gf_model* m, const double* theta, int64_t n, double* fr_bi
     if (rc != GF_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     const size_t out_bytes = sizeof(double) * 3 * (size_t)nbins * (size_t)n;
-    GfScratch buf;
+    GfScratch buf(GF_MEM_CACHED);
     double *d_theta = nullptr, *d_out = nullptr; int32_t* d_st = nullptr;
     hipError_t e = buf.get(&d_theta, sizeof(double) * (size_t)c->ndim * n);
     if (e == hipSuccess) e = buf.get(&d_out, out_bytes);

@@ -148,7 +148,7 @@ int gf_toys_select(gf_toys* h, const double* bf, int per_scale, const double* sm
     if (K < 1 || K > MAX_STARTS) return gf_fail_msg(GF_ERR_INVALID_ARG, "gf_toys_select: %d starts asked for, 1 to %d can be selected", K, MAX_STARTS);
     int rc = toy_seeds_ready(*t, "gf_toys_select");
     if (rc != GF_OK) return rc;
-    GfScratch scratch;
+    GfScratch scratch(GF_MEM_DRIVER);
     ToySelArgs a;
     rc = toys_upload_meas(t, bf, per_scale, smearing, ntoys, scratch, a, "gf_toys_select");
     if (rc != GF_OK) return rc;
@@ -162,7 +162,7 @@ int gf_toys_scores(gf_toys* h, const double* bf, int per_scale, const double* sm
     if (!t || !bf || !smearing || !scores || ntoys < 1 || ntoys > 65535 || (per_scale != 0 && per_scale != 1)) return GF_ERR_INVALID_ARG;
     int rc = toy_seeds_ready(*t, "gf_toys_scores");
     if (rc != GF_OK) return rc;
-    GfScratch scratch;
+    GfScratch scratch(GF_MEM_DRIVER);
     ToySelArgs a;
     rc = toys_upload_meas(t, bf, per_scale, smearing, ntoys, scratch, a, "gf_toys_scores");
     if (rc != GF_OK) return rc;

@@ -192,7 +192,7 @@ int gf_toys_select_binned(gf_toys_binned* h, const double* meas, int per_scale, 
     if (K < 1 || K > MAX_STARTS) return gf_fail_msg(GF_ERR_INVALID_ARG, "gf_toys_select_binned: %d starts asked for, 1 to %d can be selected", K, MAX_STARTS);
     int rc = toy_seeds_ready(*t, "gf_toys_select_binned");
     if (rc != GF_OK) return rc;
-    GfScratch scratch;
+    GfScratch scratch(GF_MEM_DRIVER);
     ToybSelArgs a;
     rc = toysb_upload(t, meas, per_scale, sigma, per_toy_sigma, ntoys, scratch, a, "gf_toys_select_binned");
     if (rc != GF_OK) return rc;
@@ -208,7 +208,7 @@ int gf_toys_scores_binned(gf_toys_binned* h, const double* meas, int per_scale, 
         return GF_ERR_INVALID_ARG;
     int rc = toy_seeds_ready(*t, "gf_toys_scores_binned");
     if (rc != GF_OK) return rc;
-    GfScratch scratch;
+    GfScratch scratch(GF_MEM_DRIVER);
     ToybSelArgs a;
     rc = toysb_upload(t, meas, per_scale, sigma, per_toy_sigma, ntoys, scratch, a, "gf_toys_scores_binned");
     if (rc != GF_OK) return rc;

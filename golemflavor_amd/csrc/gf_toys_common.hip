@@ -2,7 +2,7 @@
 // gf_toys.hip and gf_toys_binned.hip.
 //
 // The seed set: a seed point's prior sum, its unitarity verdict and its compositions do not depend on the measurement.  Per scale:
-//   k_cube_draw     nseed cube points of Philox counter (the scale's run id, SX_SEED_ITER, point, pair of coordinates): the points
+//   k_cube_draw     (gf_cube_runs.hip) nseed cube points of Philox counter (the scale's run id, SX_SEED_ITER, point, pair of coordinates): the points
 //                   gf_simplex.hip's seeding draws for that run id
 //   the bulk path   gf_model_lnprob_on with compositions and status: the verdicts with the bulk path's own arbitration
 //   k_bsm_bins      an energy-resolved set only: gf_model_bins_on with that status, fr_bins [S][M][nb][3] (24 S M nb bytes), NaN for a
@@ -133,7 +133,7 @@ int toy_seeds_seed(ToySeedSet* t, uint32_t* nonunitary, const char* who)
     const int n = t->nseed;
     hipStream_t st = t->rs.set.stream;
     const dim3 grid((unsigned)((n + GF_BLOCK - 1) / GF_BLOCK), a.nruns);
-    hipLaunchKernelGGL(k_cube_draw, grid, dim3(GF_BLOCK), 0, st, a, SX_SEED_ITER, n, t->d_u, t->d_theta);
+    cube_runs_draw_points(t->rs, a, SX_SEED_ITER, n, t->d_u, t->d_theta);
     GF_HIP(hipGetLastError());
     for (int r = 0; r < a.nruns; ++r) {
         const size_t at = (size_t)r * n;
@@ -181,7 +181,7 @@ int toy_select_run(ToyTail& a, int S, hipStream_t st, ToySelectLaunch select, in
     const int KM = a.K <= 1 ? 1 : a.K <= 4 ? 4 : MAX_STARTS;
     a.nparts = (a.M + CHUNK - 1) / CHUNK;
     const size_t pairs = (size_t)S * a.T, ent = pairs * a.nparts * KM, sel = pairs * a.K;
-    GfScratch scratch;
+    GfScratch scratch(GF_MEM_DRIVER);
     scratch.take(&a.part_s, sizeof(double) * ent, who);
     scratch.take(&a.part_i, sizeof(int32_t) * ent, who);
     scratch.take(&a.out_index, sizeof(int32_t) * sel, who);
@@ -222,7 +222,7 @@ int toy_select_alone(int device, ToyTail& a, ToySelectLaunch select, const ToyUp
     if (rc != GF_OK) return rc;
     hipStream_t st = (hipStream_t)stv;
     {
-        GfScratch scratch;
+        GfScratch scratch(GF_MEM_DRIVER);
         std::vector<char*> d(nblocks, nullptr);
         for (int b = 0; b < nblocks; ++b) scratch.take(&d[b], blocks[b].bytes, who);
         rc = scratch.failed;

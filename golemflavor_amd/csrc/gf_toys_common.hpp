@@ -18,7 +18,7 @@ struct DevLogOfExp {
 };
 }  // namespace
 
-// The seeds of every scale (one run of a run set, gf_cube_runs.hpp, each).  Both public handles, gf_toys and gf_toys_binned, point to
+// The seeds of every scale (one run of a run set, gf_cube_runs.hpp / .hip, each).  Both public handles, gf_toys and gf_toys_binned, point to
 // one: the public types stay incomplete, and their files convert with toy_set.
 struct ToySeedSet {
     GfCubeRunsHost rs;

@@ -47,7 +47,7 @@ __device__ inline void load_matrix(const double* hi, const double* lo, cx87 u[3]
 
 // The per-walker part of fr.py:380-399 in the reference's arithmetic: the two Hamiltonian terms before their energy factors,
 // hsm = U diag(0, m21, m3x) U^+ (fr.py:383-386) and hnp = U~ diag(0, sc1, sc2) U~^+ (fr.py:380-393).
-__device__ __attribute__((noinline)) void walker_terms(const GfCommon& c, const GfBsm& tb, const double* __restrict__ theta, int layout,
+[[maybe_unused]] __device__ __attribute__((noinline)) void walker_terms(const GfCommon& c, const GfBsm& tb, const double* __restrict__ theta, int layout,
                                                         int64_t n, int64_t i, cx87 hsm[3][3], cx87 hnp[3][3])
 {
     const int ndim = c.ndim;
@@ -75,7 +75,7 @@ __device__ __attribute__((noinline)) void walker_terms(const GfCommon& c, const 
     sandwich(u, sc1, sc2, hnp);                                         // fr.py:391-394 (before the E^(d-3) factor)
 }
 
-__device__ __attribute__((noinline)) double walker_bin_residual(const cx87 hsm[3][3], const cx87 hnp[3][3], double pre, double epow)
+[[maybe_unused]] __device__ __attribute__((noinline)) double walker_bin_residual(const cx87 hsm[3][3], const cx87 hnp[3][3], double pre, double epow)
 {
     return bin_residual(hsm, hnp, pre, epow);
 }

@@ -1,5 +1,5 @@
 """GPU: live handles and a model whose likelihood is set again after they exist ("Models that change under a live
-handle"; csrc/gf_modelset.hip, cube_runs_begin in csrc/gf_cube_runs.hpp, sampler_kind_refusal in csrc/gf_sampler_host.hip).
+handle"; csrc/gf_modelset.hip, cube_runs_begin in csrc/gf_cube_runs.hip, sampler_kind_refusal in csrc/gf_sampler_host.hip).
 
 A. a set's kind -- tabulated, binned or neither -- is fixed at creation: a model that gains a likelihood afterwards is refused by every
    entry point that evaluates, and what the handle holds stays readable and unchanged;

@@ -302,3 +302,70 @@ def test_large_device_buffers_are_cached_not_freed():
     assert stats()[0] == (200 << 20) + (100 << 20) + (110 << 20)
     assert _lib.device_trim(0) >= (200 << 20) + (100 << 20) + (110 << 20)
     assert stats()[0] == 0
+
+
+def test_the_device_cache_balances_its_accounts_across_every_kind_of_handle(golden):
+    """gf_devcache.hip's books after one handle of every kind has worked and closed: what the cache handed out (`live_bytes`) is back at
+    the baseline after every close, and a trim then leaves nothing idle.  A cached block released with the driver's free instead of the
+    cache's stays in `live_bytes` (and under its old size in the cache's map of live blocks): that is the fault this guards against.
+    Which allocator the nested sampler, the maximiser and the seed sets use for their own buffers is not asserted -- only that each
+    pointer goes back where it came from.  The ensemble sampler's stored chain is sized past the cache's 64 MB threshold (16 chains x
+    100 walkers x 6 columns x 8 B = 76 800 B a step, 1100 steps = 84 MB), so the cache does take part."""
+    import ctypes as C
+    from golemflavor_amd import mcmc as mcmc_utils, nested, profile_llh as P, realisations as R
+    L = _lib.lib()
+    L.gf_devcache_stats.restype = None
+    L.gf_devcache_stats.argtypes = [C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_ulonglong)]
+
+    def stats():
+        idle, live, reuses = C.c_size_t(), C.c_size_t(), C.c_ulonglong()
+        L.gf_devcache_stats(0, C.byref(idle), C.byref(live), C.byref(reuses))
+        return idle.value, live.value
+
+    _lib.device_trim(0)
+    idle0, live0 = stats()
+    assert idle0 == 0
+
+    # the ensemble sampler, its post-processing and two reductions of the stored chain
+    asimov, ps = Cf.notebook_paramsets(golden["g6_asimov_angles"])
+    f = llh_utils.notebook_ln_prob(asimov, ps)
+    nch, nw, nd, nsteps = 16, 100, 6, 1100
+    box = np.array(ps.seeds, dtype=float)
+    p0 = np.random.default_rng(2).uniform(box[:, 0], box[:, 1], size=(nch, nw, nd))
+    s = mcmc_utils.DeviceEnsembleSampler(nw, nd, f, nchains=nch, seed=4)
+    s.run_mcmc(p0, nsteps)
+    assert s.nstored == nsteps and stats()[1] >= live0 + nch * nw * nd * 8 * nsteps      # the chain came from the cache
+    assert s.postprocess()["fr"].shape == (nch, nw, nsteps, 3)
+    assert len(s.marginals(bins_1d=16, bins_2d=8)) == nch
+    assert s.intervals()["low"].shape[0] == nch
+    s.close()
+    assert stats()[1] == live0, "ensemble sampler"
+    f.close()
+    assert stats()[1] == live0, "its model"
+
+    # two BSM scale models: a nested sampler, a profile maximiser and a seed set with a selection on them
+    args = argparse.Namespace(source_ratio=fr_utils.normalize_fr((0., 1., 0.)), dimension=6, texture=Texture.OET, binning=Cf.default_bin_edges(),
+                              smearing=0.05, injected_ratio=fr_utils.normalize_fr((1., 1., 1.)))
+    asimov, ps = Cf.sens_paramsets(6, (1., 1., 1.))
+    cols, models, bases, _ = nested._scan_models(args, asimov, ps, np.array([-45.0, -40.0]), 0.05, 0)
+    try:
+        with nested.NestedSampler(models, cols, bases, nlive=64, batch=8, walks=5, seed=1, tol=0.5, on_nonunitary="-inf") as ns:
+            try:
+                ns.run(max_iter=300)
+            except _lib.GolemHipError as exc:                       # a run that is not done after 300 iterations: it keeps its points
+                assert exc.code == _lib.GF_ERR_UNSUPPORTED
+            assert np.all(ns.result()["niter"] > 0) and ns.posterior()["npoints"].shape == (2,)
+        assert stats()[1] == live0, "nested sampler"
+        with P.SimplexMaximizer(models, cols, bases, nstarts=2, nseed=256, seed=5, maxiter=60, on_nonunitary="-inf") as sx:
+            assert np.all(sx.run()["nfev"] > 0)
+        assert stats()[1] == live0, "profile maximiser"
+        with R.ToySeeds(models, cols, bases, nseed=3000, seed=11) as seeds:
+            meas = R.draw_realisations(fr_utils.normalize_fr((1., 1., 1.)), 0.05, 5, seed=21)
+            assert seeds.select(meas, 0.05, 4)["count"].shape == (2, 5)
+        assert stats()[1] == live0, "seed set"
+    finally:
+        for m in models:
+            m.close()
+    assert stats()[1] == live0, "the scale models"
+    _lib.device_trim(0)
+    assert stats() == (0, live0)
