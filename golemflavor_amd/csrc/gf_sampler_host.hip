@@ -9,6 +9,8 @@
 #include "gf_modelset.h"
 #include "gf_sampler_launch.h"
 #include "gf_propose.hpp"               // lanes_per_walker
+#include "gf_temper.h"                  // the tempered sampler's kernels (gf_temper.hip)
+#include "gf_temper.hpp"                // MAX_TEMPS
 
 // ---- C ABI ---------------------------------------------------------------------------------------
 struct gf_sampler {
@@ -58,6 +60,22 @@ struct gf_sampler {
     int64_t flight_nstored[FLIGHT] = {};     // stored steps of every chain that are final once the slot's event has passed
     int64_t flight_enq = 0, flight_done = 0; // blocks of the current run: enqueued / consumed (waited for and, with a sink, copied)
     struct HostSink* sink = nullptr;
+    struct GfTempered* tp = nullptr;         // gf_sampler_create_tempered: the ladder and what a replica-exchange round works on, else null
+};
+// A tempered sampler: chain g * ntemps + t samples prior * L^betas[t] of group g's model.  Its model set has one entry per
+// chain (group g's model ntemps times), so everything that takes one model per chain -- the settle kernel, the chain view -- is the
+// multi-model sampler's.
+struct GfTempered {
+    int ngroups = 0, ntemps = 0, swap_every = 0;
+    std::vector<double> betas;          // [ntemps]
+    double* d_betas = nullptr;          // [nchains]: the chain's beta
+    double* d_lp = nullptr;             // [nchains][nwalkers]: lnprior and lnl of the current walkers, as the last split evaluation left them
+    double* d_lnl = nullptr;
+    int32_t* d_status = nullptr;
+    GfArbQueue* d_pq = nullptr;         // the split evaluation's parked rows (capacity: every walker), apart from the half-step's
+    double* d_pend_rows = nullptr;
+    unsigned int* d_pend_ctl = nullptr;
+    uint32_t* d_counts = nullptr;       // [nchains][2]: pairs (t, t + 1) proposed / accepted since creation
 };
 // gf_sampler_run_to_host's destination
 struct HostSink {
@@ -261,6 +279,7 @@ struct GridSteps {
     gf_sampler* s;
     StretchArgs a;
     GfSettleArgs sa;
+    const double* betas = nullptr;      // a tempered sampler: [nchains], and the half-step is k_stretch_tempered (gf_temper.hip)
     // `count` steps relative to the device-side base counters, then k_tick
     hipError_t enqueue(int count)
     {
@@ -268,7 +287,8 @@ struct GridSteps {
             a.step_offset = i;
             for (int half = 0; half < 2; ++half) {
                 a.half = half;
-                hipError_t e = gf_launch_stretch(*s->set.c, s->set.tb, s->set.ptab, a, s->set.stream);
+                hipError_t e = betas ? gf_launch_stretch_tempered(a, betas, s->ndim, s->set.stream)
+                                     : gf_launch_stretch(*s->set.c, s->set.tb, s->set.ptab, a, s->set.stream);
                 if (e != hipSuccess) return e;
                 if (s->set.mode == MODE_BSM_GAUSS) {
                     // the proposals whose unitarity the half-step could not settle: exact verdict, then their accept step
@@ -534,6 +554,69 @@ int run_grid(Run& r, GridSteps& g)
     return GF_OK;
 }
 
+// ---- a tempered sampler -----------------------------------------------------------------------------------------------
+// lnprior, lnl and status of the current walkers of every chain in one launch (k_lnprior_lnl and the exact verdict behind it); T (may
+// be null) <- the walkers' scalar at their chain's beta, NaN where the reference would have raised
+hipError_t tempered_split(gf_sampler* s, double* T)
+{
+    GfTempered* tp = s->tp;
+    GfSplitArgs a = {};
+    a.commons = s->set.d_commons; a.tbs = s->set.d_tbs; a.ptabs = s->set.d_ptabs;
+    a.theta = s->d_pos; a.lp = tp->d_lp; a.lnl = tp->d_lnl; a.status = tp->d_status;
+    a.pq = tp->d_pq; a.pend_rows = tp->d_pend_rows;
+    a.rows = s->nwalkers; a.ndim = s->ndim; a.nbins_max = s->set.nbins_max;
+    a.betas = tp->d_betas; a.T = T;
+    return gf_launch_lnprior_lnl(a, s->nchains, tp->d_pend_ctl, s->d_state, s->set.cus, s->set.stream);
+}
+
+// replica-exchange round `round`, eagerly on the sampler's stream: (lp, lnl) of every current walker again -- one step's evaluations --
+// then k_pt_swap
+hipError_t tempered_round(gf_sampler* s, uint64_t round)
+{
+    GfTempered* tp = s->tp;
+    hipError_t e = tempered_split(s, nullptr);
+    if (e != hipSuccess) return e;
+    GfSwapArgs w = {};
+    w.pos = s->d_pos; w.T = s->d_lnp; w.lp = tp->d_lp; w.lnl = tp->d_lnl; w.betas = tp->d_betas; w.stream_ids = s->d_stream_ids;
+    w.counts = tp->d_counts; w.seed = s->seed; w.round = round;
+    w.ngroups = tp->ngroups; w.ntemps = tp->ntemps; w.nwalkers = s->nwalkers; w.ndim = s->ndim;
+    return gf_launch_pt_swap(w, s->set.stream);
+}
+
+// The steps between two rounds as graph replays and eager blocks, a round's launches eagerly behind the step whose stored sample it
+// follows: the captured graph stays the serial chain of GRAPH_STEPS steps it is for every grid-shape sampler, and knows nothing of rounds.
+int run_tempered(Run& r, GridSteps& g)
+{
+    gf_sampler* s = r.s;
+    const GfTempered* tp = s->tp;
+    const bool no_graph = gf_internal_env("GF_SAMPLER_NO_GRAPH", 0) != nullptr;          // diagnostics, read per run
+    const bool graphs = !no_graph && r.nsteps >= 2 * GRAPH_STEPS;
+    if (graphs) capture_graph(s, g, r.store);
+    while (r.done < r.nsteps) {
+        const uint64_t i0 = s->iteration + (uint64_t)r.done;            // the next step, counted since creation
+        int64_t seg = r.nsteps - r.done;
+        bool round = false;
+        if (tp->swap_every > 0) {
+            const int64_t until = tp->swap_every - (int64_t)(i0 % (uint64_t)tp->swap_every);     // steps up to and including the round's
+            if (until <= seg) { seg = until; round = true; }
+        }
+        const int64_t end = r.done + seg;
+        while (graphs && s->graph && end - r.done >= GRAPH_STEPS) {
+            const int rc = run_block(r, GRAPH_STEPS, "hipGraphLaunch", [&] { return hipGraphLaunch(s->graph, s->set.stream); });
+            if (rc != GF_OK) return rc;
+        }
+        while (r.done < end) {
+            const int rc = grid_block(r, g, (int)(end - r.done < 64 ? end - r.done : 64));
+            if (rc != GF_OK) return rc;
+        }
+        if (round) {
+            const hipError_t e = tempered_round(s, (i0 + (uint64_t)seg) / (uint64_t)tp->swap_every - 1);
+            if (e != hipSuccess) return gf_hip_fail(e, "replica-exchange round");
+        }
+    }
+    return GF_OK;
+}
+
 // gf_sampler_create_binned / _table: one model for every chain, or (nmodels == nchains) one per chain
 int sampler_create_of(gf_model* const* models, int nmodels, int nchains, int nwalkers, uint64_t seed, double a, gf_sampler** out, int want)
 {
@@ -582,12 +665,124 @@ int gf_sampler_create_table(gf_model* const* models, int nmodels, int nchains, i
     return sampler_create_of(models, nmodels, nchains, nwalkers, seed, a, out, GF_LLH_TABLE);
 }
 
+// A tempered sampler (the header has the contract).  The model set holds group g's model once per rung, so the sampler is
+// a multi-model one whose chain g * ntemps + t also has a beta.
+int gf_sampler_create_tempered(gf_model* const* models, int nmodels, int ngroups, int ntemps, const double* betas, int nwalkers, uint64_t seed,
+                               double a, int swap_every, gf_sampler** out)
+{
+    const char* who = "gf_sampler_create_tempered";
+    if (!models || !betas || !out) return GF_ERR_INVALID_ARG;
+    *out = nullptr;
+    gf_internal_set_error("");
+    if (ngroups < 1 || ntemps < 1 || swap_every < 0 || (int64_t)ngroups * ntemps > 65535)
+        return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: %d groups of %d rungs, a round every %d steps: at least one of each, no negative period, at most 65535 chains", who, ngroups, ntemps, swap_every);
+    if (ntemps > gftp::MAX_TEMPS) return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: %d rungs; a ladder has at most %d", who, ntemps, gftp::MAX_TEMPS);
+    if (nmodels != 1 && nmodels != ngroups)
+        return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: %d models for %d groups; one for all groups, or one per group", who, nmodels, ngroups);
+    if (!(betas[0] == 1.0)) return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: betas[0] is %g; the first rung is the posterior itself, beta = 1", who, betas[0]);
+    for (int t = 1; t < ntemps; ++t)
+        if (!(betas[t] < betas[t - 1])) return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: betas[%d] = %g does not lie below betas[%d] = %g; a ladder is strictly decreasing", who, t, betas[t], t - 1, betas[t - 1]);
+    if (!(betas[ntemps - 1] >= 0.0)) return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: the last rung's beta is %g; it is >= 0", who, betas[ntemps - 1]);
+    for (int g = 0; g < nmodels; ++g) {
+        if (!models[g]) return GF_ERR_INVALID_ARG;
+        if (const int rc = gf_temper_model_refusal(models[g], who, g)) return rc;
+    }
+    const int nchains = ngroups * ntemps;
+    std::vector<gf_model*> per_chain((size_t)nchains);
+    std::vector<double> chain_beta((size_t)nchains);
+    for (int ch = 0; ch < nchains; ++ch) { per_chain[ch] = models[nmodels == 1 ? 0 : ch / ntemps]; chain_beta[ch] = betas[ch % ntemps]; }
+    gf_sampler* s = nullptr;
+    int rc = sampler_create(per_chain.data(), true, nchains, nwalkers, seed, a, &s);
+    if (rc != GF_OK) return rc;
+    GfTempered* tp = new (std::nothrow) GfTempered();
+    if (!tp) { gf_sampler_destroy(s); return GF_ERR_ALLOC; }
+    s->tp = tp;
+    s->shape = 2;                                                   // one launch shape: the per-half-step grid kernels
+    tp->ngroups = ngroups; tp->ntemps = ntemps; tp->swap_every = swap_every;
+    tp->betas.assign(betas, betas + ntemps);
+    const size_t nw = (size_t)nchains * nwalkers;
+    hipStream_t st = s->set.stream;
+    hipError_t e = gf_cached_malloc((void**)&tp->d_betas, sizeof(double) * (size_t)nchains);
+    if (e == hipSuccess) e = gf_cached_malloc((void**)&tp->d_lp, sizeof(double) * nw);
+    if (e == hipSuccess) e = gf_cached_malloc((void**)&tp->d_lnl, sizeof(double) * nw);
+    if (e == hipSuccess) e = gf_cached_malloc((void**)&tp->d_status, sizeof(int32_t) * nw);
+    if (e == hipSuccess) e = gf_cached_malloc((void**)&tp->d_counts, sizeof(uint32_t) * 2 * (size_t)nchains);
+    if (e == hipSuccess) e = gf_alloc_arb_queue(GF_MEM_CACHED, nw, st, &tp->d_pq, &tp->d_pend_rows, &tp->d_pend_ctl);
+    if (e == hipSuccess) e = hipMemcpyAsync(tp->d_betas, chain_beta.data(), sizeof(double) * (size_t)nchains, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(tp->d_counts, 0, sizeof(uint32_t) * 2 * (size_t)nchains, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);              // chain_beta goes out of scope
+    if (e != hipSuccess) { gf_sampler_destroy(s); return gf_hip_fail(e, who); }
+    *out = s;
+    return GF_OK;
+}
+
+int gf_sampler_betas(const gf_sampler* s, int* ngroups, int* ntemps, double* betas, int* swap_every)
+{
+    if (!s) return GF_ERR_INVALID_ARG;
+    if (!s->tp) return GF_ERR_UNSUPPORTED;
+    if (ngroups) *ngroups = s->tp->ngroups;
+    if (ntemps) *ntemps = s->tp->ntemps;
+    if (swap_every) *swap_every = s->tp->swap_every;
+    if (betas) for (int t = 0; t < s->tp->ntemps; ++t) betas[t] = s->tp->betas[t];
+    return GF_OK;
+}
+
+int gf_sampler_swap_counts(gf_sampler* s, uint32_t* proposed, uint32_t* accepted)
+{
+    if (!s) return GF_ERR_INVALID_ARG;
+    if (!s->tp) return GF_ERR_UNSUPPORTED;
+    GF_HIP(hipSetDevice(s->set.device));
+    std::vector<uint32_t> h(2 * (size_t)s->nchains);
+    GF_HIP(hipMemcpyAsync(h.data(), s->tp->d_counts, sizeof(uint32_t) * h.size(), hipMemcpyDeviceToHost, s->set.stream));
+    GF_HIP(hipStreamSynchronize(s->set.stream));
+    for (int ch = 0; ch < s->nchains; ++ch) {
+        if (proposed) proposed[ch] = h[2 * (size_t)ch];
+        if (accepted) accepted[ch] = h[2 * (size_t)ch + 1];
+    }
+    return GF_OK;
+}
+
+// series [nchains][nstored][5], lnl_chain (host) / d_lnl_chain (device) [nchains][nstored][nwalkers], either may be NULL
+int gf_sampler_tempered_series(gf_sampler* s, const double* d_up, const double* d_dn, double* series, double* lnl_chain, double* d_lnl_chain)
+{
+    if (!s || !d_up || !d_dn || !series) return GF_ERR_INVALID_ARG;
+    if (!s->tp) return gf_fail_msg(GF_ERR_UNSUPPORTED, "gf_sampler_tempered_series: the sampler is not a tempered one (gf_sampler_create_tempered)");
+    if (const int rc = sampler_kind_refusal(s, "gf_sampler_tempered_series")) return rc;
+    for (int ch = 0; ch < s->nchains; ++ch)
+        if (!(d_up[ch] >= 0.0) || !(d_dn[ch] >= 0.0) || !std::isfinite(d_up[ch]) || !std::isfinite(d_dn[ch]))
+            return gf_fail_msg(GF_ERR_INVALID_ARG, "gf_sampler_tempered_series: the exponents of chain %d are %g and %g; finite and >= 0", ch, d_up[ch], d_dn[ch]);
+    GF_HIP(hipSetDevice(s->set.device));
+    hipStream_t st = s->set.stream;
+    GF_HIP(hipStreamSynchronize(st));
+    if (s->nstored == 0) return GF_OK;
+    const size_t nch = (size_t)s->nchains, ns = (size_t)s->nstored;
+    GfScratch sc(GF_MEM_CACHED);
+    double *dd_up = nullptr, *dd_dn = nullptr, *d_out = nullptr, *d_lnl = d_lnl_chain;
+    (void)sc.take(&dd_up, sizeof(double) * nch, "gf_sampler_tempered_series");
+    (void)sc.take(&dd_dn, sizeof(double) * nch, "gf_sampler_tempered_series");
+    if (!d_lnl) (void)sc.take(&d_lnl, sizeof(double) * nch * ns * (size_t)s->nwalkers, "gf_sampler_tempered_series");
+    if (const int ra = sc.take(&d_out, sizeof(double) * nch * ns * gftp::SERIES, "gf_sampler_tempered_series")) return ra;
+    GF_HIP(hipMemcpyAsync(dd_up, d_up, sizeof(double) * nch, hipMemcpyHostToDevice, st));
+    GF_HIP(hipMemcpyAsync(dd_dn, d_dn, sizeof(double) * nch, hipMemcpyHostToDevice, st));
+    GfSeriesArgs a = {};
+    a.commons = s->set.d_commons; a.tbs = s->set.d_tbs; a.ptabs = s->set.d_ptabs;
+    a.chain = s->d_chain; a.lnp_chain = s->d_lnp_chain; a.cap = s->nstore_cap; a.nstored = s->nstored;
+    a.nwalkers = s->nwalkers; a.ndim = s->ndim; a.d_up = dd_up; a.d_dn = dd_dn; a.lnl = d_lnl; a.out = d_out;
+    hipError_t e = gf_launch_pt_series(a, s->nchains, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(series, d_out, sizeof(double) * nch * ns * gftp::SERIES, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && lnl_chain) e = hipMemcpyAsync(lnl_chain, d_lnl, sizeof(double) * nch * ns * (size_t)s->nwalkers, hipMemcpyDeviceToHost, st);
+    const hipError_t e2 = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) return gf_hip_fail(e, "gf_sampler_tempered_series");
+    return GF_OK;
+}
+
 // diagnostics (not part of the ABI): proposals since the last reset that the half-step kernel parked and k_stretch_settle completed;
-// counted by the energy-resolved and the tabulated instances alone, GF_ERR_UNSUPPORTED for every other sampler
+// counted by the energy-resolved, the tabulated and the tempered instances alone, GF_ERR_UNSUPPORTED for every other sampler
 int gf_internal_sampler_parked(gf_sampler* s, uint32_t* out)
 {
     if (!s || !out) return GF_ERR_INVALID_ARG;
-    if (s->set.kind == GF_LLH_FLUX) return GF_ERR_UNSUPPORTED;
+    if (s->set.kind == GF_LLH_FLUX && !s->tp) return GF_ERR_UNSUPPORTED;
     GF_HIP(hipSetDevice(s->set.device));
     GF_HIP(hipMemcpyAsync(out, s->d_flags + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, s->set.stream));
     GF_HIP(hipStreamSynchronize(s->set.stream));
@@ -608,6 +803,11 @@ void gf_sampler_destroy(gf_sampler* s)
     for (void* p : ptrs) if (p) (void)gf_cached_free(p);
     if (s->graph) (void)hipGraphExecDestroy(s->graph);
     for (int i = 0; i < gf_sampler::FLIGHT; ++i) if (s->flight_ev[i]) (void)hipEventDestroy(s->flight_ev[i]);
+    if (GfTempered* tp = s->tp) {
+        void* tptrs[] = {tp->d_betas, tp->d_lp, tp->d_lnl, tp->d_status, tp->d_pq, tp->d_pend_rows, tp->d_pend_ctl, tp->d_counts};
+        for (void* p : tptrs) if (p) (void)gf_cached_free(p);
+        delete tp;
+    }
     delete s;
 }
 
@@ -634,6 +834,15 @@ int gf_sampler_set_state(gf_sampler* s, const double* pos)
     hipStream_t st = s->set.stream;
     const size_t nw = (size_t)s->nchains * s->nwalkers;
     GF_HIP(hipMemcpyAsync(s->d_pos, pos, sizeof(double) * nw * s->ndim, hipMemcpyHostToDevice, st));
+    if (s->tp) {
+        // a tempered sampler: every chain's walkers in one split evaluation, T at the chain's beta, then k_fix_start as below
+        hipError_t e = tempered_split(s, s->d_lnp);
+        if (e == hipSuccess) e = gf_launch_fix_start(s->tp->d_status, (int64_t)nw, s->d_lnp, s->d_flags, st);
+        const hipError_t e2 = hipStreamSynchronize(st);
+        if (e == hipSuccess) e = e2;
+        if (e != hipSuccess) return gf_hip_fail(e, "gf_sampler_set_state");
+        return gf_internal_check_overflow(s->set.device, st);
+    }
     // BSM posteriors: with the unitarity status, so that a start position the reference would have raised on is treated as such
     int32_t* d_st = nullptr;
     if (s->set.mode == MODE_BSM_GAUSS) GF_HIP(gf_cached_malloc((void**)&d_st, sizeof(int32_t) * nw));
@@ -666,6 +875,7 @@ int gf_sampler_reset(gf_sampler* s)
     GF_HIP(hipMemsetAsync(s->d_naccept, 0, sizeof(uint32_t) * (size_t)s->nchains * s->nwalkers, st));
     GF_HIP(hipMemsetAsync(s->d_flags, 0, sizeof(uint32_t) * 4, st));
     if (s->d_chain_stats) GF_HIP(hipMemsetAsync(s->d_chain_stats, 0, sizeof(unsigned long long) * 8 * (size_t)s->nchains, st));
+    if (s->tp) GF_HIP(hipMemsetAsync(s->tp->d_counts, 0, sizeof(uint32_t) * 2 * (size_t)s->nchains, st));
     GF_HIP(hipStreamSynchronize(st));
     s->nstored = 0;
     s->steps_since_reset = 0;
@@ -707,7 +917,12 @@ int gf_sampler_run(gf_sampler* s, int64_t nsteps, int thin, int store)
     const char* env = gf_internal_env("GF_SAMPLER_PERSIST", 0);          // "0": always the per-half-step grid kernels
     const bool bsm = s->set.mode == MODE_BSM_GAUSS;
     int rc = GF_OK;
-    if (!bsm && lds > 0 && !(env && env[0] == '0')) {
+    if (s->tp) {
+        // a tempered sampler has the grid kernels alone, one model and one beta per chain, and its rounds between their blocks
+        g.betas = s->tp->d_betas;
+        s->last_lpw = g.a.lpw;
+        rc = run_tempered(r, g);
+    } else if (!bsm && lds > 0 && !(env && env[0] == '0')) {
         rc = run_persistent(r, threads, lds, workers);
     } else {
         bool grid = true;

@@ -1,0 +1,64 @@
+// gf_temper.h -- the seam between the tempered sampler's kernels (gf_temper.hip) and the sampler's host side
+// (gf_sampler_host.hip): the kernels' argument structs, which the host fills, and the launchers.  Not exported from the library.
+#pragma once
+#include "gf_consts.h"
+#include "gf_launch.h"
+#include "gf_sampler_launch.h"
+
+// k_lnprior_lnl: lnprior and lnl apart for `rows` rows of each of the grid's blockIdx.y models (row i of model r is row r * rows + i of
+// every array); the flux-averaged BSM likelihood only.  Rows whose unitarity verdict the in-kernel tiers cannot settle are parked
+// (pq / pend_rows, capacity: every row) and settled exactly, as the maximiser's candidates are, before k_pt_finish ends the call.
+struct GfSplitArgs {
+    const GfCommon* commons;        // [nmodels]
+    const GfBsm* const* tbs;        // [nmodels]
+    const double* const* ptabs;     // [nmodels]
+    const double* theta;            // [nmodels * rows][ndim]
+    double* lp;                     // [nmodels * rows]: lnprior, -inf outside the box
+    double* lnl;                    // [nmodels * rows]: lnL, -inf outside the box, NaN where the reference would have raised
+    int32_t* status;                // [nmodels * rows]: gf_status, as gf_lnprob_batch gives it
+    GfArbQueue* pq;
+    double* pend_rows;              // [nmodels * rows][GF_PEND_STRIDE]
+    int32_t rows, ndim, nbins_max;
+    // k_pt_finish, optional: T [nmodels * rows] <- lp + betas[r] lnl (gf_temper.hpp), NaN where the reference would have raised
+    const double* betas;            // [nmodels]
+    double* T;
+};
+
+// k_pt_swap: one replica-exchange round (gf_temper.hpp) over chains [ngroups][ntemps]
+struct GfSwapArgs {
+    double* pos;                    // [nchains][nwalkers][ndim]
+    double* T;                      // [nchains][nwalkers]: the walkers' scalar, recomputed for both walkers of an exchanged pair
+    const double* lp;               // [nchains][nwalkers]: of the current walkers (k_lnprior_lnl, just ahead in stream order)
+    const double* lnl;
+    const double* betas;            // [nchains]
+    const uint64_t* stream_ids;     // [nchains] or NULL
+    uint32_t* counts;               // [nchains][2]: pairs (t, t + 1) proposed / accepted, at the entry of chain (g, t)
+    uint64_t seed, round;
+    int32_t ngroups, ntemps, nwalkers, ndim;
+};
+
+// k_pt_series: lnl of every stored sample and its reduction over the walkers of a step (gf_temper.hpp)
+struct GfSeriesArgs {
+    const GfCommon* commons;        // [nchains]
+    const GfBsm* const* tbs;
+    const double* const* ptabs;
+    const double* chain;            // [nchains][cap][nwalkers][ndim]
+    const double* lnp_chain;        // [nchains][cap][nwalkers]: a sample stored at -inf (a start position that never moved) has lnl -inf
+    int64_t cap, nstored;
+    int32_t nwalkers, ndim;
+    const double* d_up;             // [nchains]
+    const double* d_dn;
+    double* lnl;                    // [nchains][nstored][nwalkers]
+    double* out;                    // [nchains][nstored][5]
+};
+
+#define GF_TEMPER_LOCAL __attribute__((visibility("hidden")))
+// one tempered half-step of every chain, one model per chain (a.commons set): chain ch samples prior * L^betas[ch]
+GF_TEMPER_LOCAL hipError_t gf_launch_stretch_tempered(const StretchArgs& a, const double* d_betas, int ndim, hipStream_t st);
+// k_lnprior_lnl, the exact verdict of the rows it parked (ctl: [nmodels * rows][2], zero between uses; state: any GfStepState on the
+// device) and k_pt_finish, in stream order
+GF_TEMPER_LOCAL hipError_t gf_launch_lnprior_lnl(const GfSplitArgs& a, int nmodels, unsigned int* ctl, const GfStepState* state, int cus, hipStream_t st);
+GF_TEMPER_LOCAL hipError_t gf_launch_pt_swap(const GfSwapArgs& a, hipStream_t st);
+GF_TEMPER_LOCAL hipError_t gf_launch_pt_series(const GfSeriesArgs& a, int nchains, hipStream_t st);
+// GF_OK, or GF_ERR_UNSUPPORTED with a message for a model (number `index` of `who`'s) that is not a flux-averaged BSM model
+GF_TEMPER_LOCAL int gf_temper_model_refusal(gf_model* m, const char* who, int index);

@@ -1,0 +1,454 @@
+// gf_temper.hip -- the kernels of the tempered ensemble sampler: chains that sample prior * L^beta, their replica
+// exchange, and the reduction of their lnl that the stepping-stone evidence starts from.  The flux-averaged BSM likelihood only.
+//
+//   k_lnprior_lnl       lnprior and lnl of a row apart, one model per row block: where the status is OK their rounded sum is lnprob bit
+//                       for bit.  The pieces are proposal_lnprob's (gf_propose.hpp); the exact verdict of a row the in-kernel tiers
+//                       cannot settle is taken by k_stretch_settle's maximiser variant, then k_pt_finish ends the call.
+//   k_stretch_tempered  the stretch half-step of gf_sampler.hip's grid shape (the move itself: gf_stretch.hpp) on the walker's scalar
+//                       T = lp + beta lnl (gf_temper.hpp), one model and one beta per chain.  Parking and k_stretch_settle behind it
+//                       are the untempered sampler's: the parked row's lnprob slot holds T.
+//   k_pt_swap           one replica-exchange round on (lp, lnl) of the current walkers.
+//   k_pt_series         lnl of every stored sample, reduced over the walkers of a step in gf_temper.hpp's order.
+//
+// and the bulk entry point gf_model_lnprior_lnl[_device].  The sampler's host side is gf_sampler_host.hip's (gf_temper.h).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "gf_host.h"
+#include "gf_temper.h"
+#include "gf_device.hpp"
+#include "gf_bsm_device.hpp"
+#include "gf_propose.hpp"
+#include "gf_stretch.hpp"
+#include "gf_temper.hpp"
+
+namespace {
+using namespace gfdev;
+
+// lnprior and lnl of the row in LDS `row`, and the walker's scalar at `beta`: proposal_lnprob's MODE_BSM_GAUSS body with the sum taken
+// apart.  st is what the bulk kernel gives the row (ST_NAN: lp + lnl is NaN); pending as proposal_lnprob's.
+template <int NDIM, int LPW>
+__device__ __forceinline__ double tempered_eval(const GfCommon& c, const GfBsm* tb, const double* ctab, const double* ttab, const double* row,
+                                                int ndim, double beta, int& st, int sub, double* fgrp, unsigned long long& pending, double& lp_out,
+                                                double& lnl_out)
+{
+    pending = 0ull;
+    double lp, fr[3];
+    const bool inbox = lnprior_tab<NDIM>(ctab, row, ndim, c.prior_const, lp);
+    asm volatile("" : "+v"(lp));       // keeps the prior sum ahead of the bin loop (see k_bsm, gf_bsm.hip)
+    double val = -gf_inf();
+    st = ST_OUT_OF_PRIOR;
+    lp_out = -gf_inf();
+    lnl_out = -gf_inf();
+    if (inbox) {
+        UniAcc acc = {0.0, 0.0, 0ull, 2.0};
+        flux_average<UNI_INLINE, LPW>(c, tb, ttab, row, fr, acc, sub, fgrp);
+        st = (acc.clear_max < tb->uni_hi) ? ST_OK : ST_NON_UNITARY;       // tiers 1 and 2 (gf_bsm_device.hpp)
+        pending = st == ST_OK ? uni_arbitration_mask(acc.amb, tb) : 0ull;
+        const double lnl = gauss_llh(c, fr);
+        val = gftp::temper(lp, lnl, beta);
+        if (lnl != lnl && st == ST_OK) st = ST_NAN;                        // lp is finite in the box: lp + lnl is NaN iff lnl is
+        lp_out = lp;
+        lnl_out = lnl;
+    }
+    return val;
+}
+
+template <int LPW>
+__global__ __launch_bounds__(GF_BLOCK) void k_lnprior_lnl(const GfSplitArgs a)
+{
+    const int r = blockIdx.y;
+    extern __shared__ __attribute__((aligned(16))) double fdyn[];
+    double* fgrp = LPW > 1 ? fdyn + (threadIdx.x / LPW) * GF_FGRP_DOUBLES(a.nbins_max, LPW) : nullptr;
+    __shared__ __attribute__((aligned(16))) double tiles[GF_WAVES_PER_BLOCK][GF_WAVE * GF_MAX_DIM];
+    __shared__ __attribute__((aligned(16))) double ctab[GF_MAX_DIM * 4 + 20];
+    const GfCommon& c = a.commons[r];
+    const GfBsm* tb = a.tbs[r];
+    double* ttab = ctab + GF_MAX_DIM * 4;
+    load_eval_tables(ctab, a.ptabs[r], tb, true);
+    __syncthreads();
+    const int t = blockIdx.x * GF_BLOCK + threadIdx.x;
+    const int k = t / LPW, sub = t % LPW;
+    if (k >= a.rows) return;
+    const int64_t i = (int64_t)r * a.rows + k;
+    const int lane = threadIdx.x & (GF_WAVE - 1);
+    double* row = tiles[threadIdx.x / GF_WAVE] + lane * GF_MAX_DIM;
+    const double* src = a.theta + i * a.ndim;
+    for (int d = 0; d < a.ndim; ++d) row[d] = src[d];
+    int st;
+    unsigned long long pending;
+    double lp, lnl;
+    (void)tempered_eval<0, LPW>(c, tb, ctab, ttab, row, a.ndim, 1.0, st, sub, fgrp, pending, lp, lnl);
+    if (LPW > 1 && sub != 0) return;                         // the group's results are identical: one writer
+    a.lp[i] = lp;
+    a.lnl[i] = lnl;
+    a.status[i] = st;
+    // undecided unitarity: park; k_stretch_settle<Team9, false, true> writes the verdict over the status
+    if (pending != 0ull) park_proposal(a.pq, a.pend_rows, i, row, a.ndim, lnl, pending);
+}
+
+// the end of a split evaluation: lnl is NaN where the reference would have raised (as lnprob is), and T, where asked for, is the walker's
+// scalar at its model's beta -- NaN there too, which k_fix_start turns into -inf and counts
+__global__ void k_pt_finish(const GfSplitArgs a, int64_t n)
+{
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const bool bad = a.status[i] == ST_NON_UNITARY;
+        if (bad) a.lnl[i] = gf_nan();
+        if (a.T) a.T[i] = bad ? gf_nan() : gftp::temper(a.lp[i], a.lnl[i], a.betas[i / a.rows]);
+    }
+}
+
+// stretch_body (gf_sampler.hip) for the tempered chains: blockIdx.y = chain, so that the chain's constants and its beta are
+// block-uniform and come from scalar loads.  flags[2] counts the parked proposals (one count per lane group).
+#ifndef GF_STRETCH_WAVES
+#define GF_STRETCH_WAVES 2
+#endif
+template <int NDIM, int LPW>
+__global__ __launch_bounds__(GF_BLOCK, GF_STRETCH_WAVES) void k_stretch_tempered(const StretchArgs s, const double* __restrict__ betas)
+{
+    const int chain = blockIdx.y;
+    const int t = blockIdx.x * GF_BLOCK + threadIdx.x;
+    const int k = t / LPW, sub = t % LPW;
+    const bool valid = k < s.nwalkers / 2;
+    const GfCommon& c = s.commons[chain];
+    const GfBsm* __restrict__ tb = s.tbs[chain];
+    const double beta = betas[chain];
+    extern __shared__ __attribute__((aligned(16))) double fdyn[];    // LPW > 1: per lane group [nbins_max][3] + [LPW]
+    double* fgrp = LPW > 1 ? fdyn + (threadIdx.x / LPW) * GF_FGRP_DOUBLES(s.nbins_max, LPW) : nullptr;
+    constexpr int ND = NDIM ? NDIM : GF_MAX_DIM;
+    __shared__ __attribute__((aligned(16))) double tiles[GF_WAVES_PER_BLOCK][GF_WAVE * ND];
+    __shared__ __attribute__((aligned(16))) double ctab[GF_MAX_DIM * 4 + 20];
+    double* ttab = ctab + GF_MAX_DIM * 4;
+    load_eval_tables(ctab, s.ptabs[chain], tb, true);
+    __syncthreads();
+
+    const int ndim = NDIM ? NDIM : c.ndim;
+    const int lane = threadIdx.x & (GF_WAVE - 1);
+    const int wave = threadIdx.x / GF_WAVE;
+    double* row = tiles[wave] + lane * ndim;
+    const uint64_t iteration = s.state->iteration_base + (uint64_t)s.step_offset;
+    const int64_t run_step = s.state->run_step_base + s.step_offset;
+    const int thin = s.state->thin;
+    const bool store_now = s.state->store != 0 && s.chain != nullptr && (run_step % thin) == 0;
+    const int64_t store_index = s.state->store_base + (run_step + thin - 1) / thin;   // stored steps before this one
+    const int nhalf = s.nwalkers / 2;
+    const uint64_t sid = s.stream_ids ? s.stream_ids[chain] : (uint64_t)chain;
+    const uint64_t g = sid * (uint64_t)nhalf + (uint64_t)k;  // walker slot of the chain's random stream: the Philox counter
+    if (!valid) return;
+    const int w = s.half * nhalf + k;                        // this walker, in the active half
+    const int cbase = (1 - s.half) * nhalf;                  // complementary half
+
+    double z, u3;
+    int j;
+    stretch_draw(s.seed, g, 2 * iteration + s.half, nhalf, s.a, z, j, u3);
+    const double* sk = s.pos + ((int64_t)chain * s.nwalkers + w) * ndim;
+    const double* cj = s.pos + ((int64_t)chain * s.nwalkers + cbase + j) * ndim;
+    stretch_row<NDIM>(row, cj, sk, z, ndim);
+    int st;
+    unsigned long long pending;
+    double lp, lnl;
+    const double lnq = tempered_eval<NDIM, LPW>(c, tb, ctab, ttab, row, ndim, beta, st, sub, fgrp, pending, lp, lnl);
+    const int64_t wi = (int64_t)chain * s.nwalkers + w;
+    const double lnk = s.lnp[wi];
+    const double lhs = stretch_lhs(z, u3, ndim);
+    if (pending != 0ull) {
+        // undecided unitarity, at every beta: park the proposal; k_stretch_settle completes this walker's half-step
+        if (sub == 0) {
+            park_proposal<true>(s.pq, s.pend_rows, (int64_t)chain * nhalf + k, row, ndim, lnq, pending, lhs);
+            atomicAdd(s.flags + 2, 1u);
+        }
+        return;
+    }
+    bool accept = lhs > lnk - lnq;                           // false for NaN and for lnq = -inf
+    if (st == ST_NON_UNITARY) {                              // the reference raises inside ln_prob here
+        accept = false;
+        if (sub == 0) atomicAdd(s.flags, 1u);
+    }
+    if (LPW > 1 && sub != 0) return;                         // the group's results are identical: one writer
+    if (accept) {
+        double* dst = s.pos + wi * ndim;
+#pragma unroll
+        for (int d = 0; d < ND; ++d) {
+            if (!NDIM && d >= ndim) break;
+            dst[d] = row[d];
+        }
+        s.lnp[wi] = lnq;
+        s.naccept[wi] += 1u;
+    }
+    if (store_now) {
+        double* dst = s.chain + (((int64_t)chain * s.nstore_cap + store_index) * s.nwalkers + w) * ndim;
+#pragma unroll
+        for (int d = 0; d < ND; ++d) {
+            if (!NDIM && d >= ndim) break;
+            dst[d] = accept ? row[d] : sk[d];
+        }
+        if (s.lnp_chain)
+            s.lnp_chain[((int64_t)chain * s.nstore_cap + store_index) * s.nwalkers + w] = accept ? lnq : lnk;
+    }
+}
+
+// one thread per (group, pair of the round, walker)
+__global__ __launch_bounds__(GF_BLOCK) void k_pt_swap(const GfSwapArgs a)
+{
+    const int par = (int)(a.round & 1ull);
+    const int npairs = (a.ntemps - par) / 2;                 // t = par, par + 2, ... with t + 1 < ntemps
+    const int64_t total = (int64_t)a.ngroups * npairs * a.nwalkers;
+    for (int64_t i = (int64_t)blockIdx.x * GF_BLOCK + threadIdx.x; i < total; i += (int64_t)gridDim.x * GF_BLOCK) {
+        const int w = (int)(i % a.nwalkers);
+        const int p = (int)((i / a.nwalkers) % npairs);
+        const int g = (int)(i / ((int64_t)a.nwalkers * npairs));
+        const int t = 2 * p + par;
+        const int ca = g * a.ntemps + t, cb = ca + 1;
+        const int64_t ia = (int64_t)ca * a.nwalkers + w, ib = (int64_t)cb * a.nwalkers + w;
+        if (!gftp::swap_live(a.T[ia]) || !gftp::swap_live(a.T[ib])) continue;
+        const uint64_t gsid = a.stream_ids ? a.stream_ids[g * a.ntemps] : (uint64_t)(g * a.ntemps);
+        const double u = gftp::swap_uniform(a.seed, gftp::swap_walker_word(gsid, a.nwalkers, w), gftp::swap_step_word(a.round, t));
+        const double ba = a.betas[ca], bb = a.betas[cb];
+        atomicAdd(a.counts + 2 * ca, 1u);
+        if (!(log(u) < gftp::swap_log_ratio(ba, bb, a.lnl[ia], a.lnl[ib]))) continue;
+        atomicAdd(a.counts + 2 * ca + 1, 1u);
+        double* pa = a.pos + ia * a.ndim;
+        double* pb = a.pos + ib * a.ndim;
+        for (int d = 0; d < a.ndim; ++d) { const double x = pa[d]; pa[d] = pb[d]; pb[d] = x; }
+        a.T[ia] = gftp::temper(a.lp[ib], a.lnl[ib], ba);
+        a.T[ib] = gftp::temper(a.lp[ia], a.lnl[ia], bb);
+    }
+}
+
+// the fold of 256 lane values in LDS, gfnp::fold_lanes' order; every thread returns the result
+__device__ __forceinline__ double fold256(double* s, double v)
+{
+    const int t = threadIdx.x;
+    __syncthreads();
+    s[t] = v;
+    __syncthreads();
+    for (int o = 32; o > 0; o >>= 1) {
+        if ((t & 63) < o) s[t] = gfnp::add(s[t], s[t + o]);
+        __syncthreads();
+    }
+    return gfnp::add(gfnp::add(gfnp::add(s[0], s[64]), s[128]), s[192]);
+}
+
+// one workgroup per (stored step, chain)
+__global__ __launch_bounds__(GF_BLOCK) void k_pt_series(const GfSeriesArgs a)
+{
+    static_assert(GF_BLOCK == gfnp::LANES, "the walker sum's lanes are the workgroup's");
+    __shared__ __attribute__((aligned(16))) double tiles[GF_WAVES_PER_BLOCK][GF_WAVE * GF_MAX_DIM];
+    __shared__ __attribute__((aligned(16))) double ctab[GF_MAX_DIM * 4 + 20];
+    __shared__ double red[GF_BLOCK];
+    __shared__ unsigned int cnt;
+    const int chain = blockIdx.y;
+    const int64_t step = blockIdx.x;
+    const GfCommon& c = a.commons[chain];
+    const GfBsm* tb = a.tbs[chain];
+    double* ttab = ctab + GF_MAX_DIM * 4;
+    load_eval_tables(ctab, a.ptabs[chain], tb, true);
+    if (threadIdx.x == 0) cnt = 0u;
+    __syncthreads();
+    const int lane = threadIdx.x & (GF_WAVE - 1);
+    double* row = tiles[threadIdx.x / GF_WAVE] + lane * GF_MAX_DIM;
+    const double* src = a.chain + (((int64_t)chain * a.cap + step) * a.nwalkers) * a.ndim;
+    const double* tsrc = a.lnp_chain + ((int64_t)chain * a.cap + step) * a.nwalkers;
+    double* lnl_out = a.lnl + ((int64_t)chain * a.nstored + step) * a.nwalkers;
+    double m = -gf_inf();
+    unsigned int mine = 0u;
+    for (int w = threadIdx.x; w < a.nwalkers; w += GF_BLOCK) {
+        double lnl = -gf_inf();
+        if (gftp::swap_live(tsrc[w])) {                      // else: a start position that never moved, outside the support
+            for (int d = 0; d < a.ndim; ++d) row[d] = src[(int64_t)w * a.ndim + d];
+            int st;
+            unsigned long long pending;
+            double lp;
+            (void)tempered_eval<0, 1>(c, tb, ctab, ttab, row, a.ndim, 1.0, st, 0, nullptr, pending, lp, lnl);
+        }
+        lnl_out[w] = lnl;
+        if (gftp::finite(lnl)) { ++mine; m = lnl > m ? lnl : m; }
+    }
+    if (mine) atomicAdd(&cnt, mine);
+    // the largest finite lnl: exact in any order
+    __syncthreads();
+    red[threadIdx.x] = m;
+    __syncthreads();
+    for (int o = GF_BLOCK / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] = red[threadIdx.x] > red[threadIdx.x + o] ? red[threadIdx.x] : red[threadIdx.x + o];
+        __syncthreads();
+    }
+    m = red[0];
+    const double dup = a.d_up[chain], ddn = a.d_dn[chain];
+    double sum = 0.0, up = 0.0, dn = 0.0;
+    for (int w = threadIdx.x; w < a.nwalkers; w += GF_BLOCK) {
+        const double lnl = lnl_out[w];                       // this thread's own store
+        sum = gfnp::add(sum, gftp::finite(lnl) ? lnl : 0.0);
+        up = gfnp::add(up, gftp::series_term(lnl, m, dup));
+        dn = gfnp::add(dn, gftp::series_term(lnl, m, ddn));
+    }
+    sum = fold256(red, sum);
+    up = fold256(red, up);
+    dn = fold256(red, dn);
+    if (threadIdx.x == 0) {
+        double* o = a.out + ((int64_t)chain * a.nstored + step) * gftp::SERIES;
+        o[0] = (double)cnt; o[1] = sum; o[2] = m; o[3] = up; o[4] = dn;
+    }
+}
+
+template <int NDIM>
+hipError_t launch_tempered_n(const StretchArgs& a, const double* d_betas, hipStream_t st)
+{
+    auto go = [&](auto l) {
+        constexpr int LPW = decltype(l)::value;
+        const size_t lds = LPW > 1 ? (size_t)(GF_BLOCK / LPW) * GF_FGRP_DOUBLES(a.nbins_max, LPW) * sizeof(double) : 0;
+        const dim3 grid((unsigned)(((int64_t)(a.nwalkers / 2) * LPW + GF_BLOCK - 1) / GF_BLOCK), a.nchains);
+        hipLaunchKernelGGL((k_stretch_tempered<NDIM, LPW>), grid, dim3(GF_BLOCK), lds, st, a, d_betas);
+        return hipGetLastError();
+    };
+    switch (a.lpw) {
+    case 2: return go(std::integral_constant<int, 2>());
+    case 4: return go(std::integral_constant<int, 4>());
+    case 16: return go(std::integral_constant<int, 16>());
+    default: return go(std::integral_constant<int, 1>());
+    }
+}
+
+// the lanes of a split evaluation: the nested sampler's and the maximiser's choices, forced by GF_TEMPER_LPW
+const GfLpwRule SPLIT_RULE = {false, 32 * 1024, "GF_TEMPER_LPW"};
+
+}  // namespace
+
+hipError_t gf_launch_stretch_tempered(const StretchArgs& a, const double* d_betas, int ndim, hipStream_t st)
+{
+    switch (ndim) {
+    case 7: return launch_tempered_n<7>(a, d_betas, st);
+    case 12: return launch_tempered_n<12>(a, d_betas, st);
+    default: return launch_tempered_n<0>(a, d_betas, st);
+    }
+}
+
+hipError_t gf_launch_lnprior_lnl(const GfSplitArgs& a, int nmodels, unsigned int* ctl, const GfStepState* state, int cus, hipStream_t st)
+{
+    const int64_t n = (int64_t)nmodels * a.rows;
+    if (n == 0) return hipSuccess;
+    const int lpw = lanes_per_walker(MODE_BSM_GAUSS, n, a.nbins_max, cus, SPLIT_RULE);
+    const size_t lds = lpw > 1 ? (size_t)(GF_BLOCK / lpw) * GF_FGRP_DOUBLES(a.nbins_max, lpw) * sizeof(double) : 0;
+    const dim3 grid((unsigned)(((int64_t)a.rows * lpw + GF_BLOCK - 1) / GF_BLOCK), nmodels);
+    switch (lpw) {
+    case 4: hipLaunchKernelGGL(k_lnprior_lnl<4>, grid, dim3(GF_BLOCK), lds, st, a); break;
+    case 16: hipLaunchKernelGGL(k_lnprior_lnl<16>, grid, dim3(GF_BLOCK), lds, st, a); break;
+    default: hipLaunchKernelGGL(k_lnprior_lnl<1>, grid, dim3(GF_BLOCK), lds, st, a); break;
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    // the parked rows' exact verdict: row t of model t / rows, as the maximiser's candidates (gf_simplex.hip)
+    GfSettleArgs sa = {};
+    sa.state = state; sa.pq = a.pq; sa.pend_rows = a.pend_rows; sa.ctl = ctl;
+    sa.nchains = nmodels; sa.nwalkers = 2 * a.rows; sa.ndim = a.ndim; sa.commons = a.commons; sa.tbs = a.tbs; sa.multi = 1;
+    sa.sx_lnq = a.lnl; sa.sx_status = a.status;
+    e = gf_launch_simplex_settle(sa, cus, st);
+    if (e != hipSuccess) return e;
+    const int64_t blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(k_pt_finish, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, st, a, n);
+    return hipGetLastError();
+}
+
+hipError_t gf_launch_pt_swap(const GfSwapArgs& a, hipStream_t st)
+{
+    const int64_t total = (int64_t)a.ngroups * (a.ntemps / 2) * a.nwalkers;
+    if (total == 0) return hipSuccess;
+    const int64_t blocks = (total + GF_BLOCK - 1) / GF_BLOCK;
+    hipLaunchKernelGGL(k_pt_swap, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(GF_BLOCK), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t gf_launch_pt_series(const GfSeriesArgs& a, int nchains, hipStream_t st)
+{
+    if (a.nstored == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_pt_series, dim3((unsigned)a.nstored, (unsigned)nchains), dim3(GF_BLOCK), 0, st, a);
+    return hipGetLastError();
+}
+
+// ---- the bulk entry point ----------------------------------------------------------------------------------------------------------
+// the flux-averaged BSM likelihood only: what gf_model_lnprior_lnl and gf_sampler_create_tempered say to any other model
+int gf_temper_model_refusal(gf_model* m, const char* who, int index)
+{
+    const GfCommon* c; const GfBsm* tb; const double* ptab; int device, cus, nbins;
+    if (!m || gf_model_constants(m, &c, &tb, &ptab, &device, &cus, &nbins) != GF_OK) return GF_ERR_INVALID_ARG;
+    if (c->mode != MODE_BSM_GAUSS)
+        return gf_fail_msg(GF_ERR_UNSUPPORTED, "%s: model %d has mode %d; lnprior and lnL are taken apart for the flux-averaged BSM likelihood only", who, index, c->mode);
+    if (gf_model_table(m, nullptr) > 0)
+        return gf_fail_msg(GF_ERR_UNSUPPORTED, "%s: model %d carries a tabulated likelihood; the flux-averaged BSM likelihood only", who, index);
+    if (gf_model_binned(m, nullptr))
+        return gf_fail_msg(GF_ERR_UNSUPPORTED, "%s: model %d carries a binned measurement; the flux-averaged BSM likelihood only", who, index);
+    return GF_OK;
+}
+
+extern "C" {
+
+// d_theta [n][ndim] (AoS) -> d_lp, d_lnl [n], d_status [n], all on the device; synchronous on return
+int gf_model_lnprior_lnl_device(gf_model* m, const double* d_theta, int64_t n, double* d_lp, double* d_lnl, int32_t* d_status)
+{
+    if (!m || n < 0 || (n > 0 && (!d_theta || !d_lp || !d_lnl || !d_status))) return GF_ERR_INVALID_ARG;
+    gf_internal_set_error("");
+    if (const int rc = gf_temper_model_refusal(m, "gf_model_lnprior_lnl", 0)) return rc;
+    const GfCommon* c; const GfBsm* tb; const double* ptab; void* stream; int device, cus, nbins;
+    int rc = gf_model_internal(m, &c, &tb, &ptab, &stream, &device);
+    if (rc == GF_OK) rc = gf_model_constants(m, &c, &tb, &ptab, &device, &cus, &nbins);
+    if (rc != GF_OK) return rc;
+    if (n == 0) return GF_OK;
+    hipStream_t st = (hipStream_t)stream;
+    constexpr int64_t PIECE = 1 << 18;                       // rows per launch: bounds the parked rows' buffers
+    const int64_t piece = n < PIECE ? n : PIECE;
+    // one model: the kernels' per-model arrays have one entry each
+    GfScratch sc(GF_MEM_CACHED);
+    GfCommon* d_common = nullptr; const GfBsm** d_tbs = nullptr; const double** d_ptabs = nullptr; GfStepState* d_state = nullptr;
+    (void)sc.take(&d_common, sizeof(GfCommon), "gf_model_lnprior_lnl");
+    (void)sc.take(&d_tbs, sizeof(void*), "gf_model_lnprior_lnl");
+    (void)sc.take(&d_ptabs, sizeof(void*), "gf_model_lnprior_lnl");
+    if (const int ra = sc.take(&d_state, sizeof(GfStepState), "gf_model_lnprior_lnl")) return ra;
+    GfArbQueue* pq = nullptr; double* pend = nullptr; unsigned int* ctl = nullptr;
+    hipError_t e = gf_alloc_arb_queue(GF_MEM_CACHED, (size_t)piece, st, &pq, &pend, &ctl);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_common, c, sizeof(GfCommon), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync((void*)d_tbs, &tb, sizeof(void*), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync((void*)d_ptabs, &ptab, sizeof(void*), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(d_state, 0, sizeof(GfStepState), st);
+    for (int64_t w0 = 0; w0 < n && e == hipSuccess; w0 += piece) {
+        GfSplitArgs a = {};
+        a.commons = d_common; a.tbs = d_tbs; a.ptabs = d_ptabs;
+        a.theta = d_theta + w0 * c->ndim; a.lp = d_lp + w0; a.lnl = d_lnl + w0; a.status = d_status + w0;
+        a.pq = pq; a.pend_rows = pend; a.rows = (int32_t)(n - w0 < piece ? n - w0 : piece); a.ndim = c->ndim; a.nbins_max = nbins;
+        e = gf_launch_lnprior_lnl(a, 1, ctl, d_state, cus, st);
+    }
+    const hipError_t e2 = hipStreamSynchronize(st);
+    for (void* p : {(void*)pq, (void*)pend, (void*)ctl}) if (p) (void)gf_cached_free(p);
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) return gf_hip_fail(e, "gf_model_lnprior_lnl");
+    return GF_OK;
+}
+
+// theta [n][ndim] -> lp, lnl [n], status [n] on the host
+int gf_model_lnprior_lnl(gf_model* m, const double* theta, int64_t n, double* lp, double* lnl, int32_t* status)
+{
+    if (!m || n < 0 || (n > 0 && (!theta || !lp || !lnl || !status))) return GF_ERR_INVALID_ARG;
+    gf_internal_set_error("");
+    if (const int rc = gf_temper_model_refusal(m, "gf_model_lnprior_lnl", 0)) return rc;
+    if (n == 0) return GF_OK;
+    const GfCommon* c; const GfBsm* tb; const double* ptab; void* stream; int device;
+    const int rc = gf_model_internal(m, &c, &tb, &ptab, &stream, &device);
+    if (rc != GF_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    GfScratch sc(GF_MEM_CACHED);
+    double *d_theta = nullptr, *d_lp = nullptr, *d_lnl = nullptr; int32_t* d_status = nullptr;
+    (void)sc.take(&d_theta, sizeof(double) * (size_t)n * c->ndim, "gf_model_lnprior_lnl");
+    (void)sc.take(&d_lp, sizeof(double) * (size_t)n, "gf_model_lnprior_lnl");
+    (void)sc.take(&d_lnl, sizeof(double) * (size_t)n, "gf_model_lnprior_lnl");
+    if (const int ra = sc.take(&d_status, sizeof(int32_t) * (size_t)n, "gf_model_lnprior_lnl")) return ra;
+    GF_HIP(hipMemcpyAsync(d_theta, theta, sizeof(double) * (size_t)n * c->ndim, hipMemcpyHostToDevice, st));
+    GF_HIP(hipStreamSynchronize(st));
+    const int re = gf_model_lnprior_lnl_device(m, d_theta, n, d_lp, d_lnl, d_status);
+    if (re != GF_OK) return re;
+    GF_HIP(hipMemcpyAsync(lp, d_lp, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
+    GF_HIP(hipMemcpyAsync(lnl, d_lnl, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
+    GF_HIP(hipMemcpyAsync(status, d_status, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
+    GF_HIP(hipStreamSynchronize(st));
+    return GF_OK;
+}
+
+}  // extern "C"

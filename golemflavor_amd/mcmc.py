@@ -209,16 +209,38 @@ class DeviceEnsembleSampler(rowsets.RowSetSource):
     (GF_ERR_UNSUPPORTED).  Everything that reads the chain works as for any sampler; `reweight` takes model targets only.  A table
     set on a model between two runs, of any side, is the one the next run samples; the walkers keep the lnprob they hold (the old
     table's) until they move -- pass the positions to `run_mcmc` again to have them evaluated under the new table.
+
+    betas=[1, ..., beta_min or 0] (`gf_sampler_create_tempered`): a tempered sampler of `ngroups` groups of len(betas)
+    chains; chain g * ntemps + t samples prior * L^betas[t] of group g's posterior (`lnpostfn`: one for all groups, or a list of one per
+    group -- the scales of a scan).  Flux-averaged BSM posteriors only.  `lnprobability` and the state's lnprob are the walker's scalar
+    T = lp + beta lnl (at beta = 1: `Model.lnprob`); `lnlikelihood()` has lnl itself.  swap_every=S > 0: a replica-exchange round
+    after every S-th step.  `.betas`, `.cold_chains`, `.swap_fraction`, `.lnl_series()`; `tempering.stepping_stone` turns the series into
+    ln(Z_1 / Z_0).  Everything that reads the chain works as for a sampler of nchains = ngroups * ntemps chains.  betas=None: none of this.
     """
 
     def __init__(self, nwalkers, dim, lnpostfn, a=2.0, nchains=1, seed=0, threads=1, stream_ids=None, energy_resolved=False,
-                 tabulated=False):
+                 tabulated=False, betas=None, swap_every=0, ngroups=None):
         import ctypes as C
         from . import _lib
         multi = isinstance(lnpostfn, (list, tuple))
         fns = list(lnpostfn) if multi else [lnpostfn]
         models = [getattr(f, "model", f) for f in fns]
-        if multi:
+        self.betas = None if betas is None else np.ascontiguousarray(betas, dtype=np.float64).reshape(-1)
+        if self.betas is not None:
+            # a tempered sampler: ngroups groups of len(betas) chains, one posterior for all groups or one per group
+            if energy_resolved or tabulated:
+                raise ValueError("betas: a tempered sampler evaluates the flux-averaged likelihood only")
+            if not models:
+                raise ValueError("empty list of posteriors")
+            self.ngroups = int(ngroups if ngroups is not None else (len(models) if multi else 1))
+            self.ntemps, self.swap_every = len(self.betas), int(swap_every)
+            self._group_models = models
+            nchains = self.ngroups * self.ntemps
+            if len(models) in (1, self.ngroups):
+                models = [models[0 if len(models) == 1 else ch // self.ntemps] for ch in range(nchains)]
+                fns = [fns[0 if len(fns) == 1 else ch // self.ntemps] for ch in range(nchains)]
+                multi = True
+        elif multi:
             if not models:
                 raise ValueError("empty list of posteriors")
             if nchains not in (1, len(models)):
@@ -253,7 +275,12 @@ class DeviceEnsembleSampler(rowsets.RowSetSource):
         self.k, self.dim, self.a, self.nchains = int(nwalkers), int(dim), float(a), int(nchains)
         self.models = models if multi else None               # one posterior per chain (kept alive here)
         h = C.c_void_p()
-        if self.energy_resolved:
+        if self.betas is not None:
+            gm = self._group_models
+            _lib.check(self._L.gf_sampler_create_tempered(rowsets.model_handles(gm, len(gm)), len(gm), self.ngroups, self.ntemps,
+                                                          self.betas.ctypes.data_as(_lib._dp), self.k, int(seed), self.a, self.swap_every,
+                                                          C.byref(h)), "gf_sampler_create_tempered")
+        elif self.energy_resolved:
             nmodels = self.nchains if multi else 1
             _lib.check(self._L.gf_sampler_create_binned(rowsets.model_handles(models, nmodels), nmodels, self.nchains, self.k, int(seed),
                                                         self.a, C.byref(h)), "gf_sampler_create_binned")
@@ -278,6 +305,59 @@ class DeviceEnsembleSampler(rowsets.RowSetSource):
                 raise ValueError("stream_ids must hold one id per chain (%d), got %s" % (self.nchains, ids.shape))
             _lib.check(self._L.gf_sampler_set_stream_ids(self._h, ids.ctypes.data_as(C.POINTER(C.c_uint64))),
                        "gf_sampler_set_stream_ids")
+
+    # -- a tempered sampler (betas given) ---------------------------------------
+    def _tempered(self):
+        if self.betas is None:
+            raise ValueError("not a tempered sampler: pass betas=...")
+
+    @property
+    def cold_chains(self):
+        """The indices of the chains that sample the posterior itself (beta == 1): chain g * ntemps of every group."""
+        self._tempered()
+        return np.arange(self.ngroups) * self.ntemps
+
+    def swap_counts(self):
+        """(proposed, accepted), each (ngroups, ntemps): the pairs of rungs (t, t + 1) since the last reset."""
+        self._tempered()
+        C = self._C
+        prop, acc = np.zeros((self.ngroups, self.ntemps), np.uint32), np.zeros((self.ngroups, self.ntemps), np.uint32)
+        self._lib.check(self._L.gf_sampler_swap_counts(self._h, prop.ctypes.data_as(C.POINTER(C.c_uint32)), acc.ctypes.data_as(C.POINTER(C.c_uint32))),
+                        "gf_sampler_swap_counts")
+        return prop, acc
+
+    @property
+    def swap_fraction(self):
+        """(ngroups, ntemps - 1): accepted / proposed exchanges of the rungs (t, t + 1) since the last reset, NaN where none was proposed."""
+        prop, acc = self.swap_counts()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return (acc / prop.astype(np.float64))[:, :-1]
+
+    def lnl_series(self, d_up=None, d_dn=None, want_lnl=False):
+        """The stored chains' lnl reduced over the walkers of a step on the device (gf_sampler_tempered_series): (nchains, nstored, 5) =
+        count of finite lnl, their sum, their max m, sum exp(d_up (lnl - m)), sum exp(d_dn (lnl - m)).  d_up, d_dn (nchains,), default:
+        the distance in beta to the rung above (colder; 0 for a group's first) and below (0 for its last) -- what
+        `tempering.stepping_stone` takes.  want_lnl: also the lnl of every stored sample, (nchains, nstored, nwalkers)."""
+        self._tempered()
+        b = np.tile(self.betas, self.ngroups).reshape(self.ngroups, self.ntemps)
+        if d_up is None:
+            d_up = np.concatenate([np.zeros((self.ngroups, 1)), b[:, :-1] - b[:, 1:]], axis=1)
+        if d_dn is None:
+            d_dn = np.concatenate([b[:, :-1] - b[:, 1:], np.zeros((self.ngroups, 1))], axis=1)
+        d_up = np.ascontiguousarray(np.broadcast_to(np.asarray(d_up, np.float64).reshape(-1), (self.nchains,)))
+        d_dn = np.ascontiguousarray(np.broadcast_to(np.asarray(d_dn, np.float64).reshape(-1), (self.nchains,)))
+        ns = self.nstored
+        out = np.empty((self.nchains, ns, 5))
+        lnl = np.empty((self.nchains, ns, self.k)) if want_lnl else None
+        self._lib.check(self._L.gf_sampler_tempered_series(self._h, d_up.ctypes.data_as(self._lib._dp), d_dn.ctypes.data_as(self._lib._dp),
+                                                           out.ctypes.data_as(self._lib._dp), lnl.ctypes.data_as(self._lib._dp) if want_lnl else None,
+                                                           None), "gf_sampler_tempered_series")
+        return (out, lnl) if want_lnl else out
+
+    def lnlikelihood(self):
+        """lnl of every stored sample, (nchains, nwalkers, nsteps) as `lnprobability` -- which for a tempered sampler is the walker's
+        scalar T = lp + beta lnl."""
+        return np.ascontiguousarray(self.lnl_series(want_lnl=True)[1].transpose(0, 2, 1))
 
     # -- what this source of row sets says about itself (rowsets.RowSetSource) ---------------
     _prefix, _sets = "gf_sampler_", "chains"

@@ -190,6 +190,17 @@ class Model:
             res += (st,)
         return res if len(res) > 1 else out
 
+    def lnprior_lnlike(self, theta):
+        """theta (n, ndim) -> (lp (n,), lnl (n,), status (n,) int32): lnprior and lnL apart (gf_model_lnprior_lnl).  The
+        status is `lnprob`'s, and where it is OK `lp + lnl` is `lnprob` bit for bit; outside the box both are -inf, where the reference
+        would have raised lnl is NaN.  A flux-averaged BSM model only: anything else is GolemHipError (GF_ERR_UNSUPPORTED)."""
+        th = _as_theta(theta, self.ndim)
+        n = th.shape[0]
+        lp, lnl, st = np.empty(n), np.empty(n), np.empty(n, dtype=np.int32)
+        check(self._L.gf_model_lnprior_lnl(self._h, th.ctypes.data_as(_lib._dp), n, lp.ctypes.data_as(_lib._dp), lnl.ctypes.data_as(_lib._dp),
+                                           st.ctypes.data_as(_lib._ip)), "gf_model_lnprior_lnl")
+        return lp, lnl, st
+
     def lnprob_cube(self, cube, cols, base, want_status=True):
         """MultiNest-style batch (mn.py:26-45): cube (n, nscan) in the unit cube -> lnprob (n,) [, status]; column
         cols[k] is mapped onto the model's own box on the device, the other columns take base[col]."""

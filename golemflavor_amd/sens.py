@@ -14,6 +14,9 @@ measurements thrown around the injected composition (with --energy
 writes fr_realisations{identifier}.npz beside fr_maxllh.
 --evidence-realisations T (the Bayesian method) reweights the evidence scan's own points to T such measurements and
 writes fr_evidence_realisations{identifier}.npz beside fr_stat; the Asimov arrays are what the command writes without the option.
+--evidence-method stepping-stone [--temperatures N --beta-min B --swap-every S --tempered-steps K] gives ln Z of every scale from
+tempered chains with replica exchange instead and writes fr_evidence_tempered{identifier}.npz beside fr_stat, which it
+neither writes nor replaces.
 """
 import argparse
 import json
@@ -112,7 +115,28 @@ def parse_args(argv=None):
     ap.add_argument("--likelihood-table", type=str, default=None, metavar="FILE.npy",
                     help="a tabulated flavour-plane likelihood in place of the Gaussian: the flat array of ln L at the (N + 1)(N + 2) / 2 "
                          "nodes of the flavour triangle's lattice (llh.TabulatedLikelihood.save); the output files carry _ltab")
+    ap.add_argument("--evidence-method", choices=["nested", "stepping-stone"], default="nested",
+                    help="bayesian: 'stepping-stone' gives ln Z of every scale from tempered chains with replica exchange instead "
+                         "(DESIGN.md 6n), an estimate independent of the nested sampler's, and writes fr_evidence_tempered<identifier>.npz "
+                         "beside fr_stat, which it neither writes nor replaces")
+    ap.add_argument("--temperatures", type=int, default=8, metavar="N", help="stepping-stone: geometric rungs from 1 down to --beta-min (the prior's rung 0 is added)")
+    ap.add_argument("--beta-min", type=float, default=1e-3, metavar="B", help="stepping-stone: the smallest positive beta")
+    ap.add_argument("--swap-every", type=int, default=8, metavar="S", help="stepping-stone: a replica-exchange round every S steps (0: never)")
+    ap.add_argument("--tempered-steps", type=int, default=1500, metavar="K", help="stepping-stone: stored steps per chain, after K // 3 of burn-in")
+    ap.add_argument("--tempered-walkers", type=int, default=256, help="stepping-stone: walkers per chain")
     args = ap.parse_args(argv)
+    if args.evidence_method == "stepping-stone":
+        if args.stat_method is not StatCateg.BAYESIAN:
+            ap.error("--evidence-method stepping-stone is an evidence: it needs the Bayesian method")
+        if args.energy_resolved or args.binned_measurement is not None or args.likelihood_table is not None:
+            ap.error("--evidence-method stepping-stone samples the flux-averaged likelihood only: it does not combine with "
+                     "--energy-resolved or --likelihood-table")
+        if args.realisations is not None or args.evidence_realisations is not None or args.posterior:
+            ap.error("--evidence-method stepping-stone does not combine with --realisations, --evidence-realisations or --posterior")
+        if args.temperatures < 1 or args.temperatures > 63 or not 0. < args.beta_min < 1. or args.swap_every < 0 or args.tempered_steps < 16:
+            ap.error("--temperatures takes 1 to 63, --beta-min a value in (0, 1), --swap-every S >= 0, --tempered-steps K >= 16")
+        if args.tempered_walkers < 24 or args.tempered_walkers % 2:
+            ap.error("--tempered-walkers takes an even number, at least twice the columns (24)")
     if args.likelihood_table is not None:
         if args.energy_resolved or args.binned_measurement is not None or args.binned_smearing is not None:
             ap.error("--likelihood-table replaces the flux-averaged likelihood: it does not combine with --energy-resolved")
@@ -260,6 +284,8 @@ def main(argv=None):
     args = parse_args(argv)
     scales = nested.sens_scales(args.dimension, args.segments)
     outfile, outfile_llh = output_paths(args, scales)
+    if getattr(args, "evidence_method", "nested") == "stepping-stone":
+        return _stepping_stone(args, scales)
     for f in (outfile, outfile_llh):
         if not args.overwrite and os.path.isfile(f + ".npy") and np.all(np.isfinite(np.load(f + ".npy"))):
             print("FILE EXISTS {0}".format(f + ".npy"))
@@ -306,6 +332,39 @@ def main(argv=None):
         "niter": res["niter"].tolist(), "nevals": int(res["nevals"].sum()), "nonunitary": res["nonunitary"].tolist(),
         "seconds": round(res["seconds"], 4), "evals_per_s": float(res["nevals"].sum() / max(res["seconds"], 1e-12)),
         "fr_stat": outfile + ".npy", "fr_maxllh": outfile_llh + ".npy"}))
+    return 0
+
+
+def evidence_tempered_path(args):
+    """fr_evidence_tempered<identifier>.npz beside fr_stat<identifier>.npy (with --eval-segment: its `_scale_` tail too)."""
+    stat = output_paths(args)[0]
+    return os.path.join(os.path.dirname(stat), os.path.basename(stat).replace("fr_stat", "fr_evidence_tempered", 1) + ".npz")
+
+
+def _stepping_stone(args, scales):
+    """--evidence-method stepping-stone: ln Z of every scale from tempered chains (`tempering.evidence_scan_tempered`), its file, the
+    JSON line.  fr_stat and fr_maxllh are neither read nor written: `nested.bayes_factor_limit` takes this file's ln_z as it takes theirs."""
+    from . import tempering
+    idx = np.arange(len(scales)) if args.eval_segment is None else np.array([args.eval_segment])
+    asimov, llh_ps = Cf.sens_paramsets(args.dimension, args.injected_ratio, data=args.data)
+    res = tempering.evidence_scan_tempered(args, asimov, llh_ps, scales[idx], ntemps=args.temperatures, beta_min=args.beta_min,
+                                           swap_every=args.swap_every, nwalkers=args.tempered_walkers, burnin=args.tempered_steps // 3,
+                                           nsteps=args.tempered_steps, seed=args.seed, on_nonunitary=args.on_nonunitary, device=args.device)
+    f = evidence_tempered_path(args)
+    os.makedirs(os.path.dirname(f) or ".", exist_ok=True)
+    with open(f, "wb") as fh:
+        np.savez(fh, scales=res["scales"], ln_z=res["ln_z"], ln_z_err=res["ln_z_err"], ln_ratio=res["ln_ratio"], ln_ratio_ti=res["ln_ratio_ti"],
+                 swap_fraction=res["swap_fraction"], nonunitary=np.int64(res["nonunitary"]), nonfinite_fraction=res["nonfinite_fraction"],
+                 betas=res["betas"])
+
+    def clean(a):
+        return [None if not np.isfinite(v) else float(v) for v in np.asarray(a, dtype=np.float64).ravel()]
+
+    print(json.dumps({"tool": "golemflavor_amd.sens", "evidence_method": "stepping-stone", "dimension": args.dimension, "texture": args.texture.name,
+                      "segments": args.segments, "scales": scales[idx].tolist(), "ln_z": clean(res["ln_z"]), "ln_z_err": clean(res["ln_z_err"]),
+                      "ln_z_thermodynamic_minus_ln_z0": clean(res["ln_ratio_ti"]), "betas": res["betas"].tolist(),
+                      "lowest_swap_fraction": clean([np.nanmin(res["swap_fraction"]) if np.isfinite(res["swap_fraction"]).any() else np.nan])[0],
+                      "nonunitary": int(res["nonunitary"]), "seconds": round(res["seconds"], 4), "fr_evidence_tempered": f}))
     return 0
 
 

@@ -276,6 +276,37 @@ int gf_sampler_create_binned(gf_model* const* models, int nmodels, int nchains, 
  * as for any sampler, except gf_sampler_reweight* with measurement targets: GF_ERR_UNSUPPORTED, such a chain has no Gaussian measurement
  * to replace; model targets work. */
 int gf_sampler_create_table(gf_model* const* models, int nmodels, int nchains, int nwalkers, uint64_t seed, double a, gf_sampler** out);
+/* ---- tempered chains, replica exchange, stepping-stone series; additive in ABI 5 ----
+ * lnprior and lnL of a flux-averaged BSM model apart: theta [n][ndim] -> lp, lnl, status [n].  status is gf_lnprob_batch's of the row,
+ * and where it is GF_ST_OK the rounded sum lp + lnl is gf_lnprob_batch's lnprob bit for bit.  Outside the box lp = lnl = -inf; where the
+ * reference would have raised lnl is NaN.  _device: device pointers, rows as [n][ndim].  Refused with GF_ERR_UNSUPPORTED and a message:
+ * any other mode, a model that carries a binned measurement or a tabulated likelihood. */
+int gf_model_lnprior_lnl(gf_model* m, const double* theta, int64_t n, double* lp, double* lnl, int32_t* status);
+int gf_model_lnprior_lnl_device(gf_model* m, const double* d_theta, int64_t n, double* d_lp, double* d_lnl, int32_t* d_status);
+/* A sampler of ngroups * ntemps chains: chain g * ntemps + t samples prior * L^betas[t] of group g's model (nmodels == 1: models[0] for
+ * every group; nmodels == ngroups: models[g]).  betas [ntemps]: strictly decreasing, betas[0] == 1, the last >= 0, ntemps <= 64.  The
+ * walker's scalar -- gf_sampler_get_state's lnprob, the stored lnprob chain -- is T = lp + beta * lnl, the product rounded, then the sum;
+ * beta == 0 is T = lp with no product, so a point with lnl = -inf is a sample of the prior chain.  At beta == 1 T is gf_lnprob_batch's
+ * lnprob bit for bit, and with betas = {1} the sampler is gf_sampler_create_multi's, chain for chain.  The unitarity verdict applies at
+ * every beta.  swap_every == 0: no exchange; else a replica-exchange round follows the stored sample of every step i, counted since
+ * creation, with (i + 1) % swap_every == 0: round r = (i + 1) / swap_every - 1 pairs walker w of rung t with walker w of rung t + 1 for
+ * the t with t % 2 == r % 2, skips (and does not count) a pair with a walker at -inf, and exchanges the two rows iff
+ * ln u < (beta_t - beta_t1) * (lnl_t1 - lnl_t); the draw is csrc/gf_temper.hpp's.  One launch shape (the per-half-step grid kernels).
+ * Everything that reads a stored chain works as for any sampler.  Refused: models other than flux-averaged BSM models
+ * (GF_ERR_UNSUPPORTED), a ladder or nmodels that break the rules above (GF_ERR_INVALID_ARG), each with a message. */
+int gf_sampler_create_tempered(gf_model* const* models, int nmodels, int ngroups, int ntemps, const double* betas, int nwalkers, uint64_t seed,
+                               double a, int swap_every, gf_sampler** out);
+/* lnl of every stored sample of a tempered sampler, reduced on the device over the walkers of a step: series [nchains][nstored][5] =
+ * {walkers with a finite lnl, their sum, their max m, S_up = sum_w exp(d_up (lnl_w - m)), S_dn likewise with d_dn}, d_up and d_dn
+ * [nchains] >= 0; a walker without a finite lnl contributes 0; the sums follow one fixed tree and the exp is the library's own
+ * (csrc/gf_temper.hpp, bit for bit its host build).  lnl_chain (host) and d_lnl_chain (device), [nchains][nstored][nwalkers]: the
+ * lnl themselves, either may be NULL.  GF_ERR_UNSUPPORTED for a sampler that is not tempered. */
+int gf_sampler_tempered_series(gf_sampler* s, const double* d_up, const double* d_dn, double* series, double* lnl_chain, double* d_lnl_chain);
+/* proposed, accepted [ngroups][ntemps]: the pairs (t, t + 1) of group g since the last gf_sampler_reset, at [g][t]; the last rung's
+ * entries stay 0.  Either may be NULL. */
+int gf_sampler_swap_counts(gf_sampler* s, uint32_t* proposed, uint32_t* accepted);
+/* the ladder of a tempered sampler: *ngroups, *ntemps, *swap_every and betas [ntemps] (any may be NULL); GF_ERR_UNSUPPORTED otherwise */
+int gf_sampler_betas(const gf_sampler* s, int* ngroups, int* ntemps, double* betas, int* swap_every);
 /* Random stream of each chain, ids [nchains] (default: the chain's index in this sampler).  A grid scan passes the
  * global grid index, so that a grid point's chain is the same whichever rank runs it and whatever else shares its
  * sampler (the reference's jobs are seeded per job, scripts/mc_texture.py:137-138).  Before the first run. */
