@@ -1,82 +1,16 @@
-// gf_sampler_host.hip -- the host side of the device-resident ensemble sampler: gf_sampler, its creation over a model set
-// (gf_modelset.h), the ring of blocks in flight, the three launch shapes of a run with the graph capture, and the C ABI.  The kernels,
-// their argument structs and their launchers are gf_sampler.hip's (gf_sampler_launch.h).  No kernel here.
+// gf_sampler_host.hip -- the host side of the device-resident ensemble sampler: the creation of a gf_sampler (gf_sampler_host.h) over
+// a model set (gf_modelset.h), the ring of blocks in flight, the launch shape of a run (run_shape) and the shapes themselves with the
+// graph capture and the one loop of the grid shape, and the C ABI.  The kernels, their argument structs and their launchers are
+// gf_sampler.hip's (gf_sampler_launch.h); a tempered sampler's own state and its run are gf_temper_host.hip's, reached through
+// gf_temper.h's four functions.  No kernel here.
 #include <chrono>
 #include <new>
 
 #include "gf_devcache.h"                // large device allocations are cached, not handed back to the driver
-#include "gf_host.h"
-#include "gf_modelset.h"
-#include "gf_sampler_launch.h"
+#include "gf_sampler_host.h"
 #include "gf_propose.hpp"               // lanes_per_walker
-#include "gf_temper.h"                  // the tempered sampler's kernels (gf_temper.hip)
-#include "gf_temper.hpp"                // MAX_TEMPS
+#include "gf_temper.h"                  // the tempered half-step's launcher, and the tempered sampler's host side (gf_temper_host.hip)
 
-// ---- C ABI ---------------------------------------------------------------------------------------
-struct gf_sampler {
-    // the chains' models: one that every chain samples, or (`multi`, gf_sampler_create_multi: even for one chain) one per chain.
-    // Model 0's stream carries the sampler's launches; the set's device arrays are what the kernels that take constants by pointer read
-    GfModelSet set;
-    bool multi = false;
-    int last_lpw = 0;                   // lanes per walker of the last run's grid kernels, 0 before the first (gf_internal_sampler_lpw)
-    int nchains = 0, nwalkers = 0, ndim = 0;
-    uint64_t seed = 0, iteration = 0;
-    double a = 2.0;
-    double* d_pos = nullptr;
-    double* d_lnp = nullptr;
-    uint32_t* d_naccept = nullptr;
-    uint32_t* d_flags = nullptr;
-    GfArbQueue* d_pq = nullptr;         // BSM posteriors: proposals parked for k_stretch_settle (capacity: one half-step's proposals)
-    double* d_pend_rows = nullptr;      // [nchains * nwalkers / 2][GF_PEND_STRIDE]
-    unsigned int* d_pend_ctl = nullptr; // [nchains * nwalkers / 2][2]: k_stretch_settle's per-walker counters, zero between uses
-    double* d_lazy_rows = nullptr;      // k_stretch_chain: [nchains][lazy_cap][GF_PEND_STRIDE], undecided proposals that are rejected either way
-    unsigned long long* d_lazy_mask = nullptr;   // [nchains][lazy_cap]
-    int lazy_cap = 0;
-    unsigned long long* d_chain_stats = nullptr;   // [nchains][8]: k_stretch_chain's per-chain census (ChainArgs::stats), zeroed by gf_sampler_reset
-    // launch shape of a BSM sampler on small ensembles: 0 = not decided yet, 1 = one workgroup per chain (k_stretch_chain), 2 = the
-    // per-half-step grid kernels + k_stretch_settle.  Decided at the start of every run of 128 steps or more, by timing a block of 16
-    // steps of each on the sampler's own chains (gf_sampler_run); GF_SAMPLER_CHAIN=0 / 1 forces one
-    int shape = 0;
-    double probe_us[2] = {0.0, 0.0};               // what the decision was taken on: us per block of 16 steps, [0] per chain, [1] grid
-    double* d_chain = nullptr;
-    double* d_lnp_chain = nullptr;
-    int64_t nstore_cap = 0, nstored = 0;
-    int64_t steps_since_reset = 0;
-    uint64_t* d_stream_ids = nullptr;   // per-chain random stream ids (gf_sampler_set_stream_ids), else null
-    GfStepState* d_state = nullptr;
-    GfStepState h_state = {};
-    // captured graph of GRAPH_STEPS steps (2 nodes per step + one tick), valid for the chain pointers it was built with
-    hipGraphExec_t graph = nullptr;
-    double* graph_chain = nullptr;
-    double* graph_lnp_chain = nullptr;
-    int64_t graph_cap = -1;
-    int graph_has_chain = -1;
-    // Blocks of steps in flight.  An event is recorded behind every block a run enqueues (a graph replay of 16 steps, or up to 64
-    // eager steps), in a ring of FLIGHT slots: block k is not enqueued before block k - FLIGHT has completed, so the host never runs
-    // more than FLIGHT blocks (~2 000 AQL packets) ahead of the GPU however long the run is.  gf_sampler_run_to_host hangs its
-    // read-back on the same events (`sink`): a completed block's stored steps are copied to the host before its slot is reused.
-    static constexpr int FLIGHT = 8;
-    hipEvent_t flight_ev[FLIGHT] = {};
-    int64_t flight_nstored[FLIGHT] = {};     // stored steps of every chain that are final once the slot's event has passed
-    int64_t flight_enq = 0, flight_done = 0; // blocks of the current run: enqueued / consumed (waited for and, with a sink, copied)
-    struct HostSink* sink = nullptr;
-    struct GfTempered* tp = nullptr;         // gf_sampler_create_tempered: the ladder and what a replica-exchange round works on, else null
-};
-// A tempered sampler: chain g * ntemps + t samples prior * L^betas[t] of group g's model.  Its model set has one entry per
-// chain (group g's model ntemps times), so everything that takes one model per chain -- the settle kernel, the chain view -- is the
-// multi-model sampler's.
-struct GfTempered {
-    int ngroups = 0, ntemps = 0, swap_every = 0;
-    std::vector<double> betas;          // [ntemps]
-    double* d_betas = nullptr;          // [nchains]: the chain's beta
-    double* d_lp = nullptr;             // [nchains][nwalkers]: lnprior and lnl of the current walkers, as the last split evaluation left them
-    double* d_lnl = nullptr;
-    int32_t* d_status = nullptr;
-    GfArbQueue* d_pq = nullptr;         // the split evaluation's parked rows (capacity: every walker), apart from the half-step's
-    double* d_pend_rows = nullptr;
-    unsigned int* d_pend_ctl = nullptr;
-    uint32_t* d_counts = nullptr;       // [nchains][2]: pairs (t, t + 1) proposed / accepted since creation
-};
 // gf_sampler_run_to_host's destination
 struct HostSink {
     double* chain; double* lnp; int64_t total;     // host arrays of `total` stored steps per chain
@@ -95,6 +29,27 @@ double g_last_run_to_host_times[8] = {};
 double g_last_run_prologue[4] = {};             // the last gf_sampler_run: [0] growing the chain buffers, [1] capturing + instantiating the graph (seconds)
 
 namespace {
+// a stopwatch from its construction on: the seconds it ran are added to *total when it stops -- at stop() or at the end of its scope --
+// and kept in *longest if they exceed it; without a total it only reads
+struct Stopwatch {
+    using clock = std::chrono::steady_clock;
+    double* total;
+    double* longest;
+    clock::time_point t0 = clock::now();
+    explicit Stopwatch(double* total_ = nullptr, double* longest_ = nullptr) : total(total_), longest(longest_) {}
+    static double since(clock::time_point t) { return std::chrono::duration<double>(clock::now() - t).count(); }
+    double seconds() const { return since(t0); }
+    void stop()
+    {
+        if (!total) return;
+        const double d = seconds();
+        *total += d;
+        if (longest && d > *longest) *longest = d;
+        total = nullptr;
+    }
+    ~Stopwatch() { stop(); }
+};
+
 // The stretch kernels evaluate ONE likelihood, the one the entry point asked for (`want`): never silently for a model whose lnprob is
 // another.  The refusals, model by model in the order the set examined them.
 int sampler_refusal(const GfModelSet& set, int want)
@@ -115,55 +70,8 @@ int sampler_refusal(const GfModelSet& set, int want)
     return GF_OK;
 }
 
-// ... and stays the one the sampler was created for: a model that has since gained a table or a measurement is refused by every entry
-// point that evaluates (`who`), before it launches or writes anything.  The stored chain and state stay as they are.
-int sampler_kind_refusal(const gf_sampler* s, const char* who)
-{
-    int now = GF_LLH_FLUX;
-    const int differs = gf_modelset_kind_differs(&s->set, &now);
-    if (differs < 0) return GF_OK;
-    return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: model %d now carries %s; the sampler's kernels evaluate the likelihood it was created for (%s)", who, differs,
-                       gf_likelihood_name(now), gf_likelihood_name(s->set.kind));
-}
-
-// gf_sampler_create (multi false: every chain samples models[0]) and gf_sampler_create_multi (multi true: chain ch samples
-// models[ch]): the model set has one entry per model.  want: the likelihood the sampler evaluates -- GF_LLH_BINNED
-// (gf_sampler_create_binned), GF_LLH_TABLE (gf_sampler_create_table) or the flux-averaged one; every model must carry exactly that.
-int sampler_create(gf_model* const* models, bool multi, int nchains, int nwalkers, uint64_t seed, double a, gf_sampler** out, int want = GF_LLH_FLUX)
-{
-    if (!out || nchains < 1 || nwalkers < 2 || (nwalkers & 1) || !(a > 1.0)) return GF_ERR_INVALID_ARG;
-    *out = nullptr;
-    const char* who = want == GF_LLH_TABLE ? "gf_sampler_create_table" : want == GF_LLH_BINNED ? "gf_sampler_create_binned" : multi ? "gf_sampler_create_multi" : "gf_sampler_create";
-    gf_sampler* s = new (std::nothrow) gf_sampler();
-    if (!s) return GF_ERR_ALLOC;
-    const GfModelSet& set = s->set;
-    int rc = gf_modelset_create(&s->set, models, multi ? nchains : 1, who);
-    if (set.ndim == 0 || nwalkers < 2 * set.ndim) rc = GF_ERR_INVALID_ARG;        // models[0] is unusable; emcee's own requirement
-    else if (const int refused = sampler_refusal(set, want)) rc = refused;
-    if (rc != GF_OK) { gf_sampler_destroy(s); return rc; }
-    s->multi = multi;
-    s->nchains = nchains; s->nwalkers = nwalkers; s->ndim = set.ndim; s->seed = seed; s->a = a;
-    const size_t nw = (size_t)nchains * nwalkers;
-    // every transfer of this file goes through the sampler's stream: a synchronous (null-stream) hipMemcpy / hipMemset
-    // issued while ANOTHER host thread is capturing its sampler's graph fails and poisons that capture on this runtime
-    hipStream_t st0 = set.stream;
-    hipError_t e = hipSetDevice(set.device);
-    if (e == hipSuccess) e = gf_cached_malloc((void**)&s->d_pos, sizeof(double) * nw * s->ndim);
-    if (e == hipSuccess) e = gf_cached_malloc((void**)&s->d_lnp, sizeof(double) * nw);
-    if (e == hipSuccess) e = gf_cached_malloc((void**)&s->d_naccept, sizeof(uint32_t) * nw);
-    if (e == hipSuccess) e = gf_cached_malloc((void**)&s->d_flags, sizeof(uint32_t) * 4);
-    if (e == hipSuccess && set.mode == MODE_BSM_GAUSS)
-        e = gf_alloc_arb_queue(GF_MEM_CACHED, (size_t)nchains * (nwalkers / 2), st0, &s->d_pq, &s->d_pend_rows, &s->d_pend_ctl);
-    if (e == hipSuccess) e = gf_cached_malloc((void**)&s->d_state, sizeof(GfStepState));
-    if (e == hipSuccess) e = hipMemsetAsync(s->d_state, 0, sizeof(GfStepState), st0);
-    if (e == hipSuccess) e = hipMemsetAsync(s->d_naccept, 0, sizeof(uint32_t) * nw, st0);
-    if (e == hipSuccess) e = hipMemsetAsync(s->d_flags, 0, sizeof(uint32_t) * 4, st0);
-    if (set.kind != GF_LLH_FLUX) s->shape = 2;                        // one launch shape: the per-half-step grid kernels
-    if (e == hipSuccess) e = hipStreamSynchronize(st0);
-    if (e != hipSuccess) { gf_sampler_destroy(s); return gf_hip_fail(e, who); }
-    *out = s;
-    return GF_OK;
-}
+// slot i of the run's HostSink::t, null without a sink: where a Stopwatch of the run adds to
+double* sink_t(gf_sampler* s, int i) { return s->sink ? &s->sink->t[i] : nullptr; }
 
 // the stored steps [sink->copied, upto) of every chain -> host: their chunks are ISSUED into the sink's pipe (pinned ring, copy stream); the
 // host threads empty them into the destination while the caller goes on
@@ -174,27 +82,19 @@ int sink_copy(gf_sampler* s, int64_t upto)
     if (upto > k->total) upto = k->total;
     const size_t row = sizeof(double) * (size_t)s->nwalkers * s->ndim, lrow = sizeof(double) * (size_t)s->nwalkers;
     const size_t prev = (size_t)k->copied, now = (size_t)(upto - k->copied);
-    int rc;
-    const auto t_in = std::chrono::steady_clock::now();
-    struct Clock { HostSink* k; std::chrono::steady_clock::time_point t0;
-                   ~Clock() { const double d = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); k->t[0] += d; if (d > k->t[1]) k->t[1] = d; k->t[4] += 1.0; } } clock_{k, t_in};
-    if (k->pipe) {
-        rc = gf_internal_d2h_pipe_rows(k->pipe, reinterpret_cast<char*>(k->chain) + row * prev, row * (size_t)k->total,
-                                       reinterpret_cast<const char*>(s->d_chain) + row * prev, row * (size_t)s->nstore_cap, row * now,
-                                       (size_t)s->nchains);
-        if (rc == GF_OK && k->lnp)
-            rc = gf_internal_d2h_pipe_rows(k->pipe, reinterpret_cast<char*>(k->lnp) + lrow * prev, lrow * (size_t)k->total,
-                                           reinterpret_cast<const char*>(s->d_lnp_chain) + lrow * prev, lrow * (size_t)s->nstore_cap, lrow * now,
-                                           (size_t)s->nchains);
-    } else {                                               // GF_RUN_TO_HOST_NO_PIPE (A/B): a pipeline of its own per block, as before the pipe
-        rc = gf_internal_d2h_2d(k->device, k->copy_stream, reinterpret_cast<char*>(k->chain) + row * prev, row * (size_t)k->total,
-                                reinterpret_cast<const char*>(s->d_chain) + row * prev, row * (size_t)s->nstore_cap, row * now,
-                                (size_t)s->nchains);
-        if (rc == GF_OK && k->lnp)
-            rc = gf_internal_d2h_2d(k->device, k->copy_stream, reinterpret_cast<char*>(k->lnp) + lrow * prev, lrow * (size_t)k->total,
-                                    reinterpret_cast<const char*>(s->d_lnp_chain) + lrow * prev, lrow * (size_t)s->nstore_cap, lrow * now,
-                                    (size_t)s->nchains);
-    }
+    Stopwatch clock(&k->t[0], &k->t[1]);
+    k->t[4] += 1.0;
+    // these steps of one of the two arrays, rows of `width` bytes per step: through the pipe, or (GF_RUN_TO_HOST_NO_PIPE, A/B) in a
+    // pipeline of its own per block, as before the pipe
+    auto steps = [&](double* host, const double* dev, size_t width) {
+        char* dst = reinterpret_cast<char*>(host) + width * prev;
+        const char* src = reinterpret_cast<const char*>(dev) + width * prev;
+        const size_t dpitch = width * (size_t)k->total, spitch = width * (size_t)s->nstore_cap;
+        return k->pipe ? gf_internal_d2h_pipe_rows(k->pipe, dst, dpitch, src, spitch, width * now, (size_t)s->nchains)
+                       : gf_internal_d2h_2d(k->device, k->copy_stream, dst, dpitch, src, spitch, width * now, (size_t)s->nchains);
+    };
+    int rc = steps(k->chain, s->d_chain, row);
+    if (rc == GF_OK && k->lnp) rc = steps(k->lnp, s->d_lnp_chain, lrow);
     k->rc = rc;
     k->copied = upto;
     return rc;
@@ -205,14 +105,11 @@ int sink_copy(gf_sampler* s, int64_t upto)
 hipError_t flight_consume(gf_sampler* s, bool wait)
 {
     const int slot = (int)(s->flight_done % gf_sampler::FLIGHT);
-    const auto t_w = std::chrono::steady_clock::now();
+    Stopwatch waited(wait ? sink_t(s, 2) : nullptr, sink_t(s, 3));
     hipError_t e = wait ? hipEventSynchronize(s->flight_ev[slot]) : hipEventQuery(s->flight_ev[slot]);
-    if (wait && s->sink) {
-        const double d = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_w).count();
-        s->sink->t[2] += d; if (d > s->sink->t[3]) s->sink->t[3] = d;
-    }
+    waited.stop();
     if (e != hipSuccess) return e;                                  // hipErrorNotReady: still running
-    if (s->sink) { s->sink->last_event = std::chrono::steady_clock::now(); (void)sink_copy(s, s->flight_nstored[slot]); }
+    if (s->sink) { s->sink->last_event = Stopwatch::clock::now(); (void)sink_copy(s, s->flight_nstored[slot]); }
     ++s->flight_done;
     return hipSuccess;
 }
@@ -237,7 +134,7 @@ hipError_t flight_admit(gf_sampler* s)
 hipError_t flight_mark(gf_sampler* s, hipStream_t st, int64_t nstored)
 {
     const int slot = (int)(s->flight_enq % gf_sampler::FLIGHT);
-    if (s->sink && s->sink->t[7] == 0.0) s->sink->t[7] = std::chrono::duration<double>(std::chrono::steady_clock::now() - s->sink->t_entry).count();
+    if (s->sink && s->sink->t[7] == 0.0) s->sink->t[7] = Stopwatch::since(s->sink->t_entry);
     hipEvent_t& e = s->flight_ev[slot];
     if (!e) { const hipError_t ec = hipEventCreateWithFlags(&e, hipEventDisableTiming); if (ec != hipSuccess) { e = nullptr; return ec; } }
     const hipError_t er = hipEventRecord(e, st);
@@ -247,16 +144,7 @@ hipError_t flight_mark(gf_sampler* s, hipStream_t st, int64_t nstored)
     return hipSuccess;
 }
 
-// ---- gf_sampler_run: a prologue, one of three launch shapes, an epilogue -------------------------------------------------------
-// One run: what it was asked for and the steps enqueued so far.  A shape enqueues the steps [done, nsteps); the per-chain shape
-// may leave the rest of the run to the grid shape after its probe.
-struct Run {
-    gf_sampler* s;
-    int64_t nsteps;
-    int thin, store;
-    int64_t done;
-};
-
+// ---- gf_sampler_run: a prologue, the launch shape run_shape names, an epilogue -------------------------------------------------
 // One block of `count` steps from r.done on, enqueued by launch(): admitted into the ring of blocks in flight, then marked with
 // the stored steps of every chain that are final once it has run.  `what` names a failed launch.
 template <class Launch>
@@ -273,62 +161,6 @@ int run_block(Run& r, int64_t count, const char* what, Launch launch)
     return GF_OK;
 }
 
-// The per-half-step grid kernels of a run: k_stretch (k_stretch_multi: one model per chain) over all chains, and for BSM
-// posteriors k_stretch_settle behind every half-step.
-struct GridSteps {
-    gf_sampler* s;
-    StretchArgs a;
-    GfSettleArgs sa;
-    const double* betas = nullptr;      // a tempered sampler: [nchains], and the half-step is k_stretch_tempered (gf_temper.hip)
-    // `count` steps relative to the device-side base counters, then k_tick
-    hipError_t enqueue(int count)
-    {
-        for (int i = 0; i < count; ++i) {
-            a.step_offset = i;
-            for (int half = 0; half < 2; ++half) {
-                a.half = half;
-                hipError_t e = betas ? gf_launch_stretch_tempered(a, betas, s->ndim, s->set.stream)
-                                     : gf_launch_stretch(*s->set.c, s->set.tb, s->set.ptab, a, s->set.stream);
-                if (e != hipSuccess) return e;
-                if (s->set.mode == MODE_BSM_GAUSS) {
-                    // the proposals whose unitarity the half-step could not settle: exact verdict, then their accept step
-                    sa.half = half; sa.step_offset = i;
-                    e = gf_launch_stretch_settle(sa, s->set.cus, s->set.stream);
-                    if (e != hipSuccess) return e;
-                }
-            }
-        }
-        return gf_launch_tick(s->d_state, count, s->set.stream);
-    }
-};
-
-GridSteps grid_steps(gf_sampler* s, int store, int lpw)
-{
-    GridSteps g;
-    g.s = s;
-    StretchArgs& a = g.a;
-    a = {};
-    a.state = s->d_state;
-    a.pos = s->d_pos; a.lnp = s->d_lnp; a.naccept = s->d_naccept; a.flags = s->d_flags;
-    a.pq = s->d_pq; a.pend_rows = s->d_pend_rows;
-    a.chain = store ? s->d_chain : nullptr;
-    a.lnp_chain = store ? s->d_lnp_chain : nullptr;
-    a.nstore_cap = s->nstore_cap; a.seed = s->seed; a.nchains = s->nchains; a.nwalkers = s->nwalkers; a.a = s->a;
-    a.commons = s->multi ? s->set.d_commons : nullptr; a.tbs = s->set.d_tbs; a.ptabs = s->set.d_ptabs;
-    a.nbins_max = s->set.nbins_max;
-    a.stream_ids = s->d_stream_ids;
-    a.btabs = s->set.d_btabs;
-    a.ttabs = s->set.d_ttabs; a.tsides = s->set.d_tsides;
-    a.lpw = lpw;
-    GfSettleArgs& sa = g.sa;
-    sa = {};
-    sa.state = s->d_state; sa.pq = s->d_pq; sa.pend_rows = s->d_pend_rows; sa.ctl = s->d_pend_ctl; sa.pos = s->d_pos; sa.lnp = s->d_lnp; sa.naccept = s->d_naccept;
-    sa.flags = s->d_flags; sa.chain = a.chain; sa.lnp_chain = a.lnp_chain; sa.nstore_cap = s->nstore_cap; sa.nchains = s->nchains;
-    sa.nwalkers = s->nwalkers; sa.half = 0; sa.step_offset = 0; sa.ndim = s->ndim; sa.commons = s->set.d_commons; sa.tbs = s->set.d_tbs; sa.tb = s->set.tb;
-    sa.multi = s->multi ? 1 : 0;
-    return g;
-}
-
 // room for `need` stored steps of every chain: chains are [chain][slot][walker][dim], so a new capacity changes the chain stride
 // and the stored prefix is repacked
 int grow_chain(gf_sampler* s, int64_t need)
@@ -339,8 +171,8 @@ int grow_chain(gf_sampler* s, int64_t need)
     while (cap < need) cap *= 2;
     double *nc = nullptr, *nl = nullptr;
     GF_HIP(hipStreamSynchronize(st));
-    const auto t_grow = std::chrono::steady_clock::now();
-    struct Grow { std::chrono::steady_clock::time_point t0; ~Grow() { g_last_run_prologue[0] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); } } grow_{t_grow};
+    g_last_run_prologue[0] = 0.0;
+    Stopwatch growing(&g_last_run_prologue[0]);
     GF_HIP(gf_cached_malloc((void**)&nc, sizeof(double) * nw * s->ndim * cap));
     {
         hipError_t e_ = gf_cached_malloc((void**)&nl, sizeof(double) * nw * cap);
@@ -359,17 +191,18 @@ int grow_chain(gf_sampler* s, int64_t need)
     }
     if (s->d_chain) (void)gf_cached_free(s->d_chain);
     if (s->d_lnp_chain) (void)gf_cached_free(s->d_lnp_chain);
-    s->d_chain = nc; s->d_lnp_chain = nl; s->nstore_cap = cap;
-    // the captured graph froze the old buffers and their capacity stride in its kernel arguments
-    if (s->graph) { (void)hipGraphExecDestroy(s->graph); s->graph = nullptr; }
+    s->d_chain = nc; s->d_lnp_chain = nl; s->nstore_cap = cap;         // (a captured graph froze the old ones: capture_graph sees it)
     return GF_OK;
 }
 
 // Small ensembles of a PRIOR_ONLY / SM_GAUSS posterior: one workgroup per ensemble (k_stretch_persist), the whole run in one
 // launch per CHUNK steps.
-int run_persistent(Run& r, int threads, size_t lds, int workers)
+int run_persistent(Run& r)
 {
     gf_sampler* s = r.s;
+    int threads = 0, workers = 0;
+    size_t lds = 0;
+    gf_persist_geometry(s->nwalkers, s->ndim, &threads, &lds, &workers, s->nchains, s->set.cus);
     PersistArgs pa = {};
     pa.commons = s->set.d_commons; pa.ptabs = s->set.d_ptabs; pa.nmodels = (int32_t)s->set.models.size();
     pa.nwalkers = s->nwalkers; pa.pos = s->d_pos; pa.lnp = s->d_lnp; pa.naccept = s->d_naccept;
@@ -434,18 +267,14 @@ int alloc_lazy_lists(gf_sampler* s)
 // Which is faster depends on where the chains live NOW (a burn-in that starts below the failing region and drifts into it parks
 // nothing at first), so every run of 128 steps or more times one block of each shape on its own chains at its start (the second
 // block of two, the first warms the kernel up; the blocks are the run's own steps, nothing is computed twice) and takes the faster
-// for the rest of the run; shorter runs take the last decision (none yet: per chain).  GF_SAMPLER_CHAIN=1 / 0 forces a shape.
-// *grid on return: the rest of the run is the grid shape's.
+// for the rest of the run; shorter runs take the last decision (none yet: per chain).  GF_SAMPLER_CHAIN=1 / 0 forces a shape
+// (run_shape).  The per-chain shape of a run, with the probe (`probe`) at its start: where that chose the grid kernels it returns
+// with r.done < r.nsteps, and the rest of the run is the grid shape's.
 constexpr int64_t CHAIN_STEPS = 16;                                      // steps per launch: the granule of the overlapped read-back
-int run_per_chain(Run& r, GridSteps& g, bool* grid)
+int run_per_chain(Run& r, GridSteps& g, bool probe)
 {
     gf_sampler* s = r.s;
     hipStream_t st = s->set.stream;
-    const char* env = gf_internal_env("GF_SAMPLER_CHAIN", 0);       // "0": grid kernels; "1": per chain (k_stretch_chain)
-    const bool forced = env && (env[0] == '0' || env[0] == '1');
-    const bool probe = !forced && r.nsteps >= 8 * CHAIN_STEPS;
-    *grid = forced ? env[0] == '0' : !probe && s->shape == 2;
-    if (*grid) return GF_OK;
     int rc = alloc_lazy_lists(s);
     if (rc != GF_OK) return rc;
     ChainArgs ca = {};
@@ -472,7 +301,7 @@ int run_per_chain(Run& r, GridSteps& g, bool* grid)
         for (int which = 0; which < 2; ++which)
             for (int rep = 0; rep < 2; ++rep) {
                 GF_HIP(hipStreamSynchronize(st));
-                const auto t0 = std::chrono::steady_clock::now();
+                const Stopwatch block;
                 if (which == 0) {
                     rc = chain_block(CHAIN_STEPS);
                     if (rc == GF_OK && gf_launch_tick(s->d_state, (int)CHAIN_STEPS, st) != hipSuccess) rc = GF_ERR_HIP;
@@ -481,12 +310,11 @@ int run_per_chain(Run& r, GridSteps& g, bool* grid)
                 }
                 if (rc != GF_OK) return rc;
                 GF_HIP(hipStreamSynchronize(st));
-                if (rep == 1) us[which] = 1e6 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+                if (rep == 1) us[which] = 1e6 * block.seconds();
             }
         s->probe_us[0] = us[0]; s->probe_us[1] = us[1];
         s->shape = us[0] <= us[1] ? 1 : 2;
-        *grid = s->shape == 2;
-        if (*grid) return GF_OK;
+        if (s->shape == 2) return GF_OK;
     }
     while (r.done < r.nsteps) {
         rc = chain_block(r.nsteps - r.done < CHAIN_STEPS ? r.nsteps - r.done : CHAIN_STEPS);
@@ -495,18 +323,18 @@ int run_per_chain(Run& r, GridSteps& g, bool* grid)
     return GF_OK;
 }
 
-// s->graph: GRAPH_STEPS steps of `g` captured (2 nodes per step + one tick), recaptured when the chain buffers, their capacity or
-// the store flag it froze in its kernel arguments have changed; null where capture fails (the run launches eagerly then)
+// s->graph: GRAPH_STEPS steps of `g` captured (2 nodes per step + one tick), recaptured when what it froze in its kernel arguments
+// (GfGraphFrozen) is no longer the run's -- the one place that decides so: grown chain buffers and a first set of stream ids show
+// here; null where capture fails (the run launches eagerly then)
 constexpr int GRAPH_STEPS = 16;
 void capture_graph(gf_sampler* s, GridSteps& g, int store)
 {
-    if (s->graph && s->graph_chain == g.a.chain && s->graph_lnp_chain == g.a.lnp_chain && s->graph_cap == g.a.nstore_cap &&
-        s->graph_has_chain == store)
-        return;
+    const GfGraphFrozen now = {g.a.chain, g.a.lnp_chain, g.a.nstore_cap, store, g.a.stream_ids};
+    if (s->graph && s->graph_of == now) return;
     if (s->graph) { (void)hipGraphExecDestroy(s->graph); s->graph = nullptr; }
     hipGraph_t gr = nullptr;
-    const auto t_cap = std::chrono::steady_clock::now();
-    struct Cap { std::chrono::steady_clock::time_point t0; ~Cap() { g_last_run_prologue[1] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); } } cap_{t_cap};
+    g_last_run_prologue[1] = 0.0;
+    Stopwatch capturing(&g_last_run_prologue[1]);
     hipError_t e = hipStreamBeginCapture(s->set.stream, hipStreamCaptureModeThreadLocal);
     if (e == hipSuccess) {
         e = g.enqueue(GRAPH_STEPS);
@@ -519,102 +347,32 @@ void capture_graph(gf_sampler* s, GridSteps& g, int store)
         (void)hipGetLastError();
         s->graph = nullptr;
     } else {
-        s->graph_chain = g.a.chain;
-        s->graph_lnp_chain = g.a.lnp_chain;
-        s->graph_cap = g.a.nstore_cap;
-        s->graph_has_chain = store;
+        s->graph_of = now;
     }
 }
 
-// Every other run, and what the per-chain shape leaves: graph replays of GRAPH_STEPS steps (the launch-bound inner loop), then
-// eager blocks of up to 64 steps.
-int run_grid(Run& r, GridSteps& g)
-{
-    gf_sampler* s = r.s;
-    const bool no_graph = gf_internal_env("GF_SAMPLER_NO_GRAPH", 0) != nullptr;          // diagnostics, read per run
-    if (!no_graph && r.nsteps >= 2 * GRAPH_STEPS) {
-        capture_graph(s, g, r.store);
-        while (s->graph && r.nsteps - r.done >= GRAPH_STEPS) {
-            const int rc = run_block(r, GRAPH_STEPS, "hipGraphLaunch", [&] {
-                const auto t_g = std::chrono::steady_clock::now();
-                const hipError_t e = hipGraphLaunch(s->graph, s->set.stream);
-                if (s->sink) {
-                    const double d = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_g).count();
-                    s->sink->t[5] += d; if (d > s->sink->t[6]) s->sink->t[6] = d;
-                }
-                return e;
-            });
-            if (rc != GF_OK) return rc;
-        }
-    }
-    while (r.done < r.nsteps) {
-        const int rc = grid_block(r, g, (int)(r.nsteps - r.done < 64 ? r.nsteps - r.done : 64));
-        if (rc != GF_OK) return rc;
-    }
-    return GF_OK;
-}
+// A sampler with ONE launch shape, the per-half-step grid kernels: the energy-resolved, the tabulated and the tempered ones.
+bool grid_only(const gf_sampler* s) { return s->set.kind != GF_LLH_FLUX || s->tp; }
 
-// ---- a tempered sampler -----------------------------------------------------------------------------------------------
-// lnprior, lnl and status of the current walkers of every chain in one launch (k_lnprior_lnl and the exact verdict behind it); T (may
-// be null) <- the walkers' scalar at their chain's beta, NaN where the reference would have raised
-hipError_t tempered_split(gf_sampler* s, double* T)
+// What a run of `nsteps` steps does -- the one place that decides it.  The overrides are read in this order, once per run, each only
+// where it could change the outcome's branch: GF_SAMPLER_PERSIST ("0": never the persistent kernel), then GF_SAMPLER_CHAIN ("0": grid
+// kernels; "1": per chain) for a flux-averaged BSM sampler of up to 1024 walkers.  Unforced, such a sampler probes at the start of a run
+// of 128 steps or more and takes its last probe's choice (none yet: per chain) in a shorter one.
+enum class Shape { PERSISTENT, PER_CHAIN, PER_CHAIN_PROBE, GRID, TEMPERED };
+Shape run_shape(const gf_sampler* s, int64_t nsteps)
 {
-    GfTempered* tp = s->tp;
-    GfSplitArgs a = {};
-    a.commons = s->set.d_commons; a.tbs = s->set.d_tbs; a.ptabs = s->set.d_ptabs;
-    a.theta = s->d_pos; a.lp = tp->d_lp; a.lnl = tp->d_lnl; a.status = tp->d_status;
-    a.pq = tp->d_pq; a.pend_rows = tp->d_pend_rows;
-    a.rows = s->nwalkers; a.ndim = s->ndim; a.nbins_max = s->set.nbins_max;
-    a.betas = tp->d_betas; a.T = T;
-    return gf_launch_lnprior_lnl(a, s->nchains, tp->d_pend_ctl, s->d_state, s->set.cus, s->set.stream);
-}
-
-// replica-exchange round `round`, eagerly on the sampler's stream: (lp, lnl) of every current walker again -- one step's evaluations --
-// then k_pt_swap
-hipError_t tempered_round(gf_sampler* s, uint64_t round)
-{
-    GfTempered* tp = s->tp;
-    hipError_t e = tempered_split(s, nullptr);
-    if (e != hipSuccess) return e;
-    GfSwapArgs w = {};
-    w.pos = s->d_pos; w.T = s->d_lnp; w.lp = tp->d_lp; w.lnl = tp->d_lnl; w.betas = tp->d_betas; w.stream_ids = s->d_stream_ids;
-    w.counts = tp->d_counts; w.seed = s->seed; w.round = round;
-    w.ngroups = tp->ngroups; w.ntemps = tp->ntemps; w.nwalkers = s->nwalkers; w.ndim = s->ndim;
-    return gf_launch_pt_swap(w, s->set.stream);
-}
-
-// The steps between two rounds as graph replays and eager blocks, a round's launches eagerly behind the step whose stored sample it
-// follows: the captured graph stays the serial chain of GRAPH_STEPS steps it is for every grid-shape sampler, and knows nothing of rounds.
-int run_tempered(Run& r, GridSteps& g)
-{
-    gf_sampler* s = r.s;
-    const GfTempered* tp = s->tp;
-    const bool no_graph = gf_internal_env("GF_SAMPLER_NO_GRAPH", 0) != nullptr;          // diagnostics, read per run
-    const bool graphs = !no_graph && r.nsteps >= 2 * GRAPH_STEPS;
-    if (graphs) capture_graph(s, g, r.store);
-    while (r.done < r.nsteps) {
-        const uint64_t i0 = s->iteration + (uint64_t)r.done;            // the next step, counted since creation
-        int64_t seg = r.nsteps - r.done;
-        bool round = false;
-        if (tp->swap_every > 0) {
-            const int64_t until = tp->swap_every - (int64_t)(i0 % (uint64_t)tp->swap_every);     // steps up to and including the round's
-            if (until <= seg) { seg = until; round = true; }
-        }
-        const int64_t end = r.done + seg;
-        while (graphs && s->graph && end - r.done >= GRAPH_STEPS) {
-            const int rc = run_block(r, GRAPH_STEPS, "hipGraphLaunch", [&] { return hipGraphLaunch(s->graph, s->set.stream); });
-            if (rc != GF_OK) return rc;
-        }
-        while (r.done < end) {
-            const int rc = grid_block(r, g, (int)(end - r.done < 64 ? end - r.done : 64));
-            if (rc != GF_OK) return rc;
-        }
-        if (round) {
-            const hipError_t e = tempered_round(s, (i0 + (uint64_t)seg) / (uint64_t)tp->swap_every - 1);
-            if (e != hipSuccess) return gf_hip_fail(e, "replica-exchange round");
-        }
-    }
-    return GF_OK;
+    int threads = 0;
+    size_t lds = 0;                                                 // 0: the ensemble does not fit one workgroup
+    gf_persist_geometry(s->nwalkers, s->ndim, &threads, &lds, nullptr, s->nchains, s->set.cus);
+    const char* env = gf_internal_env("GF_SAMPLER_PERSIST", 0);
+    const bool bsm = s->set.mode == MODE_BSM_GAUSS;
+    if (s->tp) return Shape::TEMPERED;
+    if (!bsm && lds > 0 && !(env && env[0] == '0')) return Shape::PERSISTENT;
+    if (!bsm || grid_only(s) || s->nwalkers / 2 > 512) return Shape::GRID;
+    env = gf_internal_env("GF_SAMPLER_CHAIN", 0);
+    if (env && (env[0] == '0' || env[0] == '1')) return env[0] == '0' ? Shape::GRID : Shape::PER_CHAIN;
+    if (nsteps >= 8 * CHAIN_STEPS) return Shape::PER_CHAIN_PROBE;
+    return s->shape == 2 ? Shape::GRID : Shape::PER_CHAIN;
 }
 
 // gf_sampler_create_binned / _table: one model for every chain, or (nmodels == nchains) one per chain
@@ -627,6 +385,126 @@ int sampler_create_of(gf_model* const* models, int nmodels, int nchains, int nwa
     return sampler_create(models, nmodels == nchains && nchains > 1, nchains, nwalkers, seed, a, out, want);
 }
 }  // namespace
+
+// ---- what the tempered sampler's host side shares (gf_sampler_host.h) ----------------------------------------------------------
+// The stretch kernels' likelihood stays the one the sampler was created for: a model that has since gained a table or a measurement is
+// refused by every entry point that evaluates (`who`), before it launches or writes anything.  The stored chain and state stay as they are.
+int sampler_kind_refusal(const gf_sampler* s, const char* who)
+{
+    int now = GF_LLH_FLUX;
+    const int differs = gf_modelset_kind_differs(&s->set, &now);
+    if (differs < 0) return GF_OK;
+    return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: model %d now carries %s; the sampler's kernels evaluate the likelihood it was created for (%s)", who, differs,
+                       gf_likelihood_name(now), gf_likelihood_name(s->set.kind));
+}
+
+int sampler_create(gf_model* const* models, bool multi, int nchains, int nwalkers, uint64_t seed, double a, gf_sampler** out, int want)
+{
+    if (!out || nchains < 1 || nwalkers < 2 || (nwalkers & 1) || !(a > 1.0)) return GF_ERR_INVALID_ARG;
+    *out = nullptr;
+    const char* who = want == GF_LLH_TABLE ? "gf_sampler_create_table" : want == GF_LLH_BINNED ? "gf_sampler_create_binned" : multi ? "gf_sampler_create_multi" : "gf_sampler_create";
+    gf_sampler* s = new (std::nothrow) gf_sampler();
+    if (!s) return GF_ERR_ALLOC;
+    const GfModelSet& set = s->set;
+    int rc = gf_modelset_create(&s->set, models, multi ? nchains : 1, who);
+    if (set.ndim == 0 || nwalkers < 2 * set.ndim) rc = GF_ERR_INVALID_ARG;        // models[0] is unusable; emcee's own requirement
+    else if (const int refused = sampler_refusal(set, want)) rc = refused;
+    if (rc != GF_OK) { gf_sampler_destroy(s); return rc; }
+    s->multi = multi;
+    s->nchains = nchains; s->nwalkers = nwalkers; s->ndim = set.ndim; s->seed = seed; s->a = a;
+    const size_t nw = (size_t)nchains * nwalkers;
+    // every transfer of this file goes through the sampler's stream: a synchronous (null-stream) hipMemcpy / hipMemset
+    // issued while ANOTHER host thread is capturing its sampler's graph fails and poisons that capture on this runtime
+    hipStream_t st0 = set.stream;
+    hipError_t e = hipSetDevice(set.device);
+    if (e == hipSuccess) e = gf_cached_malloc((void**)&s->d_pos, sizeof(double) * nw * s->ndim);
+    if (e == hipSuccess) e = gf_cached_malloc((void**)&s->d_lnp, sizeof(double) * nw);
+    if (e == hipSuccess) e = gf_cached_malloc((void**)&s->d_naccept, sizeof(uint32_t) * nw);
+    if (e == hipSuccess) e = gf_cached_malloc((void**)&s->d_flags, sizeof(uint32_t) * 4);
+    if (e == hipSuccess && set.mode == MODE_BSM_GAUSS)
+        e = gf_alloc_arb_queue(GF_MEM_CACHED, (size_t)nchains * (nwalkers / 2), st0, &s->d_pq, &s->d_pend_rows, &s->d_pend_ctl);
+    if (e == hipSuccess) e = gf_cached_malloc((void**)&s->d_state, sizeof(GfStepState));
+    if (e == hipSuccess) e = hipMemsetAsync(s->d_state, 0, sizeof(GfStepState), st0);
+    if (e == hipSuccess) e = hipMemsetAsync(s->d_naccept, 0, sizeof(uint32_t) * nw, st0);
+    if (e == hipSuccess) e = hipMemsetAsync(s->d_flags, 0, sizeof(uint32_t) * 4, st0);
+    if (e == hipSuccess) e = hipStreamSynchronize(st0);
+    if (e != hipSuccess) { gf_sampler_destroy(s); return gf_hip_fail(e, who); }
+    *out = s;
+    return GF_OK;
+}
+
+hipError_t GridSteps::enqueue(int count)
+{
+    for (int i = 0; i < count; ++i) {
+        a.step_offset = i;
+        for (int half = 0; half < 2; ++half) {
+            a.half = half;
+            hipError_t e = betas ? gf_launch_stretch_tempered(a, betas, s->ndim, s->set.stream)
+                                 : gf_launch_stretch(*s->set.c, s->set.tb, s->set.ptab, a, s->set.stream);
+            if (e != hipSuccess) return e;
+            if (s->set.mode == MODE_BSM_GAUSS) {
+                // the proposals whose unitarity the half-step could not settle: exact verdict, then their accept step
+                sa.half = half; sa.step_offset = i;
+                e = gf_launch_stretch_settle(sa, s->set.cus, s->set.stream);
+                if (e != hipSuccess) return e;
+            }
+        }
+    }
+    return gf_launch_tick(s->d_state, count, s->set.stream);
+}
+
+GridSteps grid_steps(gf_sampler* s, int store, int lpw)
+{
+    GridSteps g;
+    g.s = s;
+    StretchArgs& a = g.a;
+    a = {};
+    a.state = s->d_state;
+    a.pos = s->d_pos; a.lnp = s->d_lnp; a.naccept = s->d_naccept; a.flags = s->d_flags;
+    a.pq = s->d_pq; a.pend_rows = s->d_pend_rows;
+    a.chain = store ? s->d_chain : nullptr;
+    a.lnp_chain = store ? s->d_lnp_chain : nullptr;
+    a.nstore_cap = s->nstore_cap; a.seed = s->seed; a.nchains = s->nchains; a.nwalkers = s->nwalkers; a.a = s->a;
+    a.commons = s->multi ? s->set.d_commons : nullptr; a.tbs = s->set.d_tbs; a.ptabs = s->set.d_ptabs;
+    a.nbins_max = s->set.nbins_max;
+    a.stream_ids = s->d_stream_ids;
+    a.btabs = s->set.d_btabs;
+    a.ttabs = s->set.d_ttabs; a.tsides = s->set.d_tsides;
+    a.lpw = lpw;
+    GfSettleArgs& sa = g.sa;
+    sa = {};
+    sa.state = s->d_state; sa.pq = s->d_pq; sa.pend_rows = s->d_pend_rows; sa.ctl = s->d_pend_ctl; sa.pos = s->d_pos; sa.lnp = s->d_lnp; sa.naccept = s->d_naccept;
+    sa.flags = s->d_flags; sa.chain = a.chain; sa.lnp_chain = a.lnp_chain; sa.nstore_cap = s->nstore_cap; sa.nchains = s->nchains;
+    sa.nwalkers = s->nwalkers; sa.half = 0; sa.step_offset = 0; sa.ndim = s->ndim; sa.commons = s->set.d_commons; sa.tbs = s->set.d_tbs; sa.tb = s->set.tb;
+    sa.multi = s->multi ? 1 : 0;
+    return g;
+}
+
+void grid_begin(Run& r, GridSteps& g)
+{
+    const bool no_graph = gf_internal_env("GF_SAMPLER_NO_GRAPH", 0) != nullptr;          // diagnostics, read per run
+    r.graphs = !no_graph && r.nsteps >= 2 * GRAPH_STEPS;
+    if (r.graphs) capture_graph(r.s, g, r.store);
+}
+
+// The launch-bound inner loop of every grid-shape run: a plain one (end = r.nsteps), what the per-chain shape leaves after its probe,
+// and a tempered sampler's steps up to its next round.
+int run_grid(Run& r, GridSteps& g, int64_t end)
+{
+    gf_sampler* s = r.s;
+    while (r.graphs && s->graph && end - r.done >= GRAPH_STEPS) {
+        const int rc = run_block(r, GRAPH_STEPS, "hipGraphLaunch", [&] {
+            Stopwatch enqueue(sink_t(s, 5), sink_t(s, 6));
+            return hipGraphLaunch(s->graph, s->set.stream);
+        });
+        if (rc != GF_OK) return rc;
+    }
+    while (r.done < end) {
+        const int rc = grid_block(r, g, (int)(end - r.done < 64 ? end - r.done : 64));
+        if (rc != GF_OK) return rc;
+    }
+    return GF_OK;
+}
 
 extern "C" {
 
@@ -665,118 +543,6 @@ int gf_sampler_create_table(gf_model* const* models, int nmodels, int nchains, i
     return sampler_create_of(models, nmodels, nchains, nwalkers, seed, a, out, GF_LLH_TABLE);
 }
 
-// A tempered sampler (the header has the contract).  The model set holds group g's model once per rung, so the sampler is
-// a multi-model one whose chain g * ntemps + t also has a beta.
-int gf_sampler_create_tempered(gf_model* const* models, int nmodels, int ngroups, int ntemps, const double* betas, int nwalkers, uint64_t seed,
-                               double a, int swap_every, gf_sampler** out)
-{
-    const char* who = "gf_sampler_create_tempered";
-    if (!models || !betas || !out) return GF_ERR_INVALID_ARG;
-    *out = nullptr;
-    gf_internal_set_error("");
-    if (ngroups < 1 || ntemps < 1 || swap_every < 0 || (int64_t)ngroups * ntemps > 65535)
-        return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: %d groups of %d rungs, a round every %d steps: at least one of each, no negative period, at most 65535 chains", who, ngroups, ntemps, swap_every);
-    if (ntemps > gftp::MAX_TEMPS) return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: %d rungs; a ladder has at most %d", who, ntemps, gftp::MAX_TEMPS);
-    if (nmodels != 1 && nmodels != ngroups)
-        return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: %d models for %d groups; one for all groups, or one per group", who, nmodels, ngroups);
-    if (!(betas[0] == 1.0)) return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: betas[0] is %g; the first rung is the posterior itself, beta = 1", who, betas[0]);
-    for (int t = 1; t < ntemps; ++t)
-        if (!(betas[t] < betas[t - 1])) return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: betas[%d] = %g does not lie below betas[%d] = %g; a ladder is strictly decreasing", who, t, betas[t], t - 1, betas[t - 1]);
-    if (!(betas[ntemps - 1] >= 0.0)) return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: the last rung's beta is %g; it is >= 0", who, betas[ntemps - 1]);
-    for (int g = 0; g < nmodels; ++g) {
-        if (!models[g]) return GF_ERR_INVALID_ARG;
-        if (const int rc = gf_temper_model_refusal(models[g], who, g)) return rc;
-    }
-    const int nchains = ngroups * ntemps;
-    std::vector<gf_model*> per_chain((size_t)nchains);
-    std::vector<double> chain_beta((size_t)nchains);
-    for (int ch = 0; ch < nchains; ++ch) { per_chain[ch] = models[nmodels == 1 ? 0 : ch / ntemps]; chain_beta[ch] = betas[ch % ntemps]; }
-    gf_sampler* s = nullptr;
-    int rc = sampler_create(per_chain.data(), true, nchains, nwalkers, seed, a, &s);
-    if (rc != GF_OK) return rc;
-    GfTempered* tp = new (std::nothrow) GfTempered();
-    if (!tp) { gf_sampler_destroy(s); return GF_ERR_ALLOC; }
-    s->tp = tp;
-    s->shape = 2;                                                   // one launch shape: the per-half-step grid kernels
-    tp->ngroups = ngroups; tp->ntemps = ntemps; tp->swap_every = swap_every;
-    tp->betas.assign(betas, betas + ntemps);
-    const size_t nw = (size_t)nchains * nwalkers;
-    hipStream_t st = s->set.stream;
-    hipError_t e = gf_cached_malloc((void**)&tp->d_betas, sizeof(double) * (size_t)nchains);
-    if (e == hipSuccess) e = gf_cached_malloc((void**)&tp->d_lp, sizeof(double) * nw);
-    if (e == hipSuccess) e = gf_cached_malloc((void**)&tp->d_lnl, sizeof(double) * nw);
-    if (e == hipSuccess) e = gf_cached_malloc((void**)&tp->d_status, sizeof(int32_t) * nw);
-    if (e == hipSuccess) e = gf_cached_malloc((void**)&tp->d_counts, sizeof(uint32_t) * 2 * (size_t)nchains);
-    if (e == hipSuccess) e = gf_alloc_arb_queue(GF_MEM_CACHED, nw, st, &tp->d_pq, &tp->d_pend_rows, &tp->d_pend_ctl);
-    if (e == hipSuccess) e = hipMemcpyAsync(tp->d_betas, chain_beta.data(), sizeof(double) * (size_t)nchains, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemsetAsync(tp->d_counts, 0, sizeof(uint32_t) * 2 * (size_t)nchains, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);              // chain_beta goes out of scope
-    if (e != hipSuccess) { gf_sampler_destroy(s); return gf_hip_fail(e, who); }
-    *out = s;
-    return GF_OK;
-}
-
-int gf_sampler_betas(const gf_sampler* s, int* ngroups, int* ntemps, double* betas, int* swap_every)
-{
-    if (!s) return GF_ERR_INVALID_ARG;
-    if (!s->tp) return GF_ERR_UNSUPPORTED;
-    if (ngroups) *ngroups = s->tp->ngroups;
-    if (ntemps) *ntemps = s->tp->ntemps;
-    if (swap_every) *swap_every = s->tp->swap_every;
-    if (betas) for (int t = 0; t < s->tp->ntemps; ++t) betas[t] = s->tp->betas[t];
-    return GF_OK;
-}
-
-int gf_sampler_swap_counts(gf_sampler* s, uint32_t* proposed, uint32_t* accepted)
-{
-    if (!s) return GF_ERR_INVALID_ARG;
-    if (!s->tp) return GF_ERR_UNSUPPORTED;
-    GF_HIP(hipSetDevice(s->set.device));
-    std::vector<uint32_t> h(2 * (size_t)s->nchains);
-    GF_HIP(hipMemcpyAsync(h.data(), s->tp->d_counts, sizeof(uint32_t) * h.size(), hipMemcpyDeviceToHost, s->set.stream));
-    GF_HIP(hipStreamSynchronize(s->set.stream));
-    for (int ch = 0; ch < s->nchains; ++ch) {
-        if (proposed) proposed[ch] = h[2 * (size_t)ch];
-        if (accepted) accepted[ch] = h[2 * (size_t)ch + 1];
-    }
-    return GF_OK;
-}
-
-// series [nchains][nstored][5], lnl_chain (host) / d_lnl_chain (device) [nchains][nstored][nwalkers], either may be NULL
-int gf_sampler_tempered_series(gf_sampler* s, const double* d_up, const double* d_dn, double* series, double* lnl_chain, double* d_lnl_chain)
-{
-    if (!s || !d_up || !d_dn || !series) return GF_ERR_INVALID_ARG;
-    if (!s->tp) return gf_fail_msg(GF_ERR_UNSUPPORTED, "gf_sampler_tempered_series: the sampler is not a tempered one (gf_sampler_create_tempered)");
-    if (const int rc = sampler_kind_refusal(s, "gf_sampler_tempered_series")) return rc;
-    for (int ch = 0; ch < s->nchains; ++ch)
-        if (!(d_up[ch] >= 0.0) || !(d_dn[ch] >= 0.0) || !std::isfinite(d_up[ch]) || !std::isfinite(d_dn[ch]))
-            return gf_fail_msg(GF_ERR_INVALID_ARG, "gf_sampler_tempered_series: the exponents of chain %d are %g and %g; finite and >= 0", ch, d_up[ch], d_dn[ch]);
-    GF_HIP(hipSetDevice(s->set.device));
-    hipStream_t st = s->set.stream;
-    GF_HIP(hipStreamSynchronize(st));
-    if (s->nstored == 0) return GF_OK;
-    const size_t nch = (size_t)s->nchains, ns = (size_t)s->nstored;
-    GfScratch sc(GF_MEM_CACHED);
-    double *dd_up = nullptr, *dd_dn = nullptr, *d_out = nullptr, *d_lnl = d_lnl_chain;
-    (void)sc.take(&dd_up, sizeof(double) * nch, "gf_sampler_tempered_series");
-    (void)sc.take(&dd_dn, sizeof(double) * nch, "gf_sampler_tempered_series");
-    if (!d_lnl) (void)sc.take(&d_lnl, sizeof(double) * nch * ns * (size_t)s->nwalkers, "gf_sampler_tempered_series");
-    if (const int ra = sc.take(&d_out, sizeof(double) * nch * ns * gftp::SERIES, "gf_sampler_tempered_series")) return ra;
-    GF_HIP(hipMemcpyAsync(dd_up, d_up, sizeof(double) * nch, hipMemcpyHostToDevice, st));
-    GF_HIP(hipMemcpyAsync(dd_dn, d_dn, sizeof(double) * nch, hipMemcpyHostToDevice, st));
-    GfSeriesArgs a = {};
-    a.commons = s->set.d_commons; a.tbs = s->set.d_tbs; a.ptabs = s->set.d_ptabs;
-    a.chain = s->d_chain; a.lnp_chain = s->d_lnp_chain; a.cap = s->nstore_cap; a.nstored = s->nstored;
-    a.nwalkers = s->nwalkers; a.ndim = s->ndim; a.d_up = dd_up; a.d_dn = dd_dn; a.lnl = d_lnl; a.out = d_out;
-    hipError_t e = gf_launch_pt_series(a, s->nchains, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(series, d_out, sizeof(double) * nch * ns * gftp::SERIES, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && lnl_chain) e = hipMemcpyAsync(lnl_chain, d_lnl, sizeof(double) * nch * ns * (size_t)s->nwalkers, hipMemcpyDeviceToHost, st);
-    const hipError_t e2 = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) return gf_hip_fail(e, "gf_sampler_tempered_series");
-    return GF_OK;
-}
-
 // diagnostics (not part of the ABI): proposals since the last reset that the half-step kernel parked and k_stretch_settle completed;
 // counted by the energy-resolved, the tabulated and the tempered instances alone, GF_ERR_UNSUPPORTED for every other sampler
 int gf_internal_sampler_parked(gf_sampler* s, uint32_t* out)
@@ -803,11 +569,7 @@ void gf_sampler_destroy(gf_sampler* s)
     for (void* p : ptrs) if (p) (void)gf_cached_free(p);
     if (s->graph) (void)hipGraphExecDestroy(s->graph);
     for (int i = 0; i < gf_sampler::FLIGHT; ++i) if (s->flight_ev[i]) (void)hipEventDestroy(s->flight_ev[i]);
-    if (GfTempered* tp = s->tp) {
-        void* tptrs[] = {tp->d_betas, tp->d_lp, tp->d_lnl, tp->d_status, tp->d_pq, tp->d_pend_rows, tp->d_pend_ctl, tp->d_counts};
-        for (void* p : tptrs) if (p) (void)gf_cached_free(p);
-        delete tp;
-    }
+    gf_temper_free(s->tp);
     delete s;
 }
 
@@ -820,8 +582,7 @@ int gf_sampler_set_stream_ids(gf_sampler* s, const uint64_t* ids)
     GF_HIP(hipStreamSynchronize(st));
     if (!s->d_stream_ids) GF_HIP(gf_cached_malloc((void**)&s->d_stream_ids, sizeof(uint64_t) * (size_t)s->nchains));
     GF_HIP(hipMemcpyAsync(s->d_stream_ids, ids, sizeof(uint64_t) * (size_t)s->nchains, hipMemcpyHostToDevice, st));
-    GF_HIP(hipStreamSynchronize(st));
-    if (s->graph) { (void)hipGraphExecDestroy(s->graph); s->graph = nullptr; }     // its kernel arguments froze the old pointer
+    GF_HIP(hipStreamSynchronize(st));               // (a graph captured without ids froze a null pointer: capture_graph sees it)
     return GF_OK;
 }
 
@@ -834,15 +595,7 @@ int gf_sampler_set_state(gf_sampler* s, const double* pos)
     hipStream_t st = s->set.stream;
     const size_t nw = (size_t)s->nchains * s->nwalkers;
     GF_HIP(hipMemcpyAsync(s->d_pos, pos, sizeof(double) * nw * s->ndim, hipMemcpyHostToDevice, st));
-    if (s->tp) {
-        // a tempered sampler: every chain's walkers in one split evaluation, T at the chain's beta, then k_fix_start as below
-        hipError_t e = tempered_split(s, s->d_lnp);
-        if (e == hipSuccess) e = gf_launch_fix_start(s->tp->d_status, (int64_t)nw, s->d_lnp, s->d_flags, st);
-        const hipError_t e2 = hipStreamSynchronize(st);
-        if (e == hipSuccess) e = e2;
-        if (e != hipSuccess) return gf_hip_fail(e, "gf_sampler_set_state");
-        return gf_internal_check_overflow(s->set.device, st);
-    }
+    if (s->tp) return gf_temper_start(s);           // a tempered sampler: the walkers' scalar at their chain's beta
     // BSM posteriors: with the unitarity status, so that a start position the reference would have raised on is treated as such
     int32_t* d_st = nullptr;
     if (s->set.mode == MODE_BSM_GAUSS) GF_HIP(gf_cached_malloc((void**)&d_st, sizeof(int32_t) * nw));
@@ -875,7 +628,7 @@ int gf_sampler_reset(gf_sampler* s)
     GF_HIP(hipMemsetAsync(s->d_naccept, 0, sizeof(uint32_t) * (size_t)s->nchains * s->nwalkers, st));
     GF_HIP(hipMemsetAsync(s->d_flags, 0, sizeof(uint32_t) * 4, st));
     if (s->d_chain_stats) GF_HIP(hipMemsetAsync(s->d_chain_stats, 0, sizeof(unsigned long long) * 8 * (size_t)s->nchains, st));
-    if (s->tp) GF_HIP(hipMemsetAsync(s->tp->d_counts, 0, sizeof(uint32_t) * 2 * (size_t)s->nchains, st));
+    if (s->tp) GF_HIP(gf_temper_clear_counts(s));
     GF_HIP(hipStreamSynchronize(st));
     s->nstored = 0;
     s->steps_since_reset = 0;
@@ -904,31 +657,33 @@ int gf_sampler_run(gf_sampler* s, int64_t nsteps, int thin, int store)
     GF_HIP(hipMemcpyAsync(s->d_state, &hs, sizeof(hs), hipMemcpyHostToDevice, st));
     if (const int rc = gf_modelset_refresh_tables(&s->set, "gf_sampler_run")) return rc;       // a table sampler: the models' tables of now
 
-    // the launch shape; the overrides are read in this order, once per run
+    // the launch shape; the overrides are read in this order, once per run: GF_SAMPLER_LPW, run_shape's, GF_SAMPLER_NO_GRAPH (grid_begin)
     Run r = {s, nsteps, thin, store ? 1 : 0, 0};
-    // (a sampler of the energy-resolved likelihood has one shape, the grid kernels at one lane per walker: no override is read for it;
-    // a sampler of the tabulated likelihood has the grid kernels too, at the lanes per walker the flux-averaged rule gives)
-    const int kind = s->set.kind;
-    GridSteps g = grid_steps(s, r.store, kind == GF_LLH_BINNED ? 1 : lanes_per_walker(s->set.mode, (int64_t)s->nchains * (s->nwalkers / 2), s->set.nbins_max, s->set.cus,
-                                                                        {true, 48 * 1024, "GF_SAMPLER_LPW"}));
-    int threads = 0, workers = 0;
-    size_t lds = 0;
-    gf_persist_geometry(s->nwalkers, s->ndim, &threads, &lds, &workers, s->nchains, s->set.cus);
-    const char* env = gf_internal_env("GF_SAMPLER_PERSIST", 0);          // "0": always the per-half-step grid kernels
-    const bool bsm = s->set.mode == MODE_BSM_GAUSS;
+    // (a sampler of the energy-resolved likelihood has the grid kernels at one lane per walker: no override is read for that;
+    // a sampler of the tabulated likelihood has them at the lanes per walker the flux-averaged rule gives)
+    GridSteps g = grid_steps(s, r.store, s->set.kind == GF_LLH_BINNED ? 1 : lanes_per_walker(s->set.mode, (int64_t)s->nchains * (s->nwalkers / 2), s->set.nbins_max, s->set.cus,
+                                                                               {true, 48 * 1024, "GF_SAMPLER_LPW"}));
+    const Shape shape = run_shape(s, nsteps);
     int rc = GF_OK;
-    if (s->tp) {
-        // a tempered sampler has the grid kernels alone, one model and one beta per chain, and its rounds between their blocks
-        g.betas = s->tp->d_betas;
+    switch (shape) {
+    case Shape::TEMPERED:               // the grid kernels alone, one model and one beta per chain, and its rounds between their blocks
         s->last_lpw = g.a.lpw;
-        rc = run_tempered(r, g);
-    } else if (!bsm && lds > 0 && !(env && env[0] == '0')) {
-        rc = run_persistent(r, threads, lds, workers);
-    } else {
-        bool grid = true;
-        if (bsm && kind == GF_LLH_FLUX && s->nwalkers / 2 <= 512) rc = run_per_chain(r, g, &grid);
-        s->last_lpw = grid ? g.a.lpw : 0;
-        if (rc == GF_OK && grid) rc = run_grid(r, g);
+        rc = gf_temper_run(r, g);
+        break;
+    case Shape::PERSISTENT:
+        rc = run_persistent(r);
+        break;
+    case Shape::PER_CHAIN:
+    case Shape::PER_CHAIN_PROBE:
+        s->last_lpw = 0;
+        rc = run_per_chain(r, g, shape == Shape::PER_CHAIN_PROBE);
+        if (rc != GF_OK || r.done == r.nsteps) break;
+        [[fallthrough]];                // the probe chose the grid kernels for the rest of the run
+    case Shape::GRID:
+        s->last_lpw = g.a.lpw;
+        grid_begin(r, g);
+        rc = run_grid(r, g, r.nsteps);
+        break;
     }
     if (rc != GF_OK) return rc;
 
@@ -966,7 +721,7 @@ int gf_sampler_run_to_host(gf_sampler* s, int64_t nsteps, int thin, double* chai
     HostSink sink;
     sink.chain = chain; sink.lnp = lnprob_chain; sink.total = s->nstored + (nsteps + thin - 1) / thin;
     sink.copy_stream = copy_stream; sink.device = device;
-    sink.last_event = sink.t_entry = std::chrono::steady_clock::now();
+    sink.last_event = sink.t_entry = Stopwatch::clock::now();
     if (gf_internal_env("GF_RUN_TO_HOST_NO_PIPE", 0) == nullptr) {       // diagnostics / A-B: else every block is a read-back of its own
         rc = gf_internal_d2h_pipe_open(device, copy_stream, &sink.pipe);
         if (rc != GF_OK) { gf_internal_return_copy_stream(device, copy_stream); return rc; }
@@ -978,7 +733,7 @@ int gf_sampler_run_to_host(gf_sampler* s, int64_t nsteps, int thin, double* chai
     while (rc == GF_OK && e == hipSuccess && s->flight_done < s->flight_enq) e = flight_consume(s, true);   // the blocks still in flight
     s->sink = nullptr;
     const hipError_t e2 = hipStreamSynchronize(s->set.stream);
-    auto t_done = marks && s->flight_enq > 0 ? sink.last_event : std::chrono::steady_clock::now();        // when the run itself was complete on the GPU
+    auto t_done = marks && s->flight_enq > 0 ? sink.last_event : Stopwatch::clock::now();        // when the run itself was complete on the GPU
     if (rc == GF_OK && e == hipSuccess && e2 == hipSuccess && sink.rc == GF_OK) {
         s->sink = &sink;                                            // whatever no block's event covered (one-launch runs; no marks)
         (void)sink_copy(s, s->nstored);
@@ -988,7 +743,7 @@ int gf_sampler_run_to_host(gf_sampler* s, int64_t nsteps, int thin, double* chai
     (void)hipStreamSynchronize((hipStream_t)copy_stream);
     gf_internal_return_copy_stream(device, copy_stream);
     if (rc == GF_OK && sink.rc == GF_OK) sink.rc = rc_pipe;
-    if (readback_tail_s) *readback_tail_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_done).count();
+    if (readback_tail_s) *readback_tail_s = Stopwatch::since(t_done);
     for (int i = 0; i < 8; ++i) g_last_run_to_host_times[i] = sink.t[i];
     if (rc != GF_OK) return rc;
     if (sink.rc != GF_OK) return sink.rc;
@@ -1028,7 +783,7 @@ int gf_internal_run_prologue_times(double out[4])
 int gf_internal_sampler_shape(const gf_sampler* s, double out[3])
 {
     if (!s || !out) return GF_ERR_INVALID_ARG;
-    out[0] = (double)s->shape; out[1] = s->probe_us[0]; out[2] = s->probe_us[1];
+    out[0] = grid_only(s) ? 2.0 : (double)s->shape; out[1] = s->probe_us[0]; out[2] = s->probe_us[1];
     return GF_OK;
 }
 

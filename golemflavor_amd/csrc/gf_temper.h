@@ -1,5 +1,6 @@
-// gf_temper.h -- the seam between the tempered sampler's kernels (gf_temper.hip) and the sampler's host side
-// (gf_sampler_host.hip): the kernels' argument structs, which the host fills, and the launchers.  Not exported from the library.
+// gf_temper.h -- the two seams of the tempered sampler.  Between its kernels (gf_temper.hip) and its host side
+// (gf_temper_host.hip): the kernels' argument structs, which the host fills, and the launchers.  Between its host side and the ensemble
+// sampler's (gf_sampler_host.hip), which holds a GfTempered only as a pointer: the four functions at the end.  Not exported from the library.
 #pragma once
 #include "gf_consts.h"
 #include "gf_launch.h"
@@ -60,5 +61,18 @@ GF_TEMPER_LOCAL hipError_t gf_launch_stretch_tempered(const StretchArgs& a, cons
 GF_TEMPER_LOCAL hipError_t gf_launch_lnprior_lnl(const GfSplitArgs& a, int nmodels, unsigned int* ctl, const GfStepState* state, int cus, hipStream_t st);
 GF_TEMPER_LOCAL hipError_t gf_launch_pt_swap(const GfSwapArgs& a, hipStream_t st);
 GF_TEMPER_LOCAL hipError_t gf_launch_pt_series(const GfSeriesArgs& a, int nchains, hipStream_t st);
-// GF_OK, or GF_ERR_UNSUPPORTED with a message for a model (number `index` of `who`'s) that is not a flux-averaged BSM model
-GF_TEMPER_LOCAL int gf_temper_model_refusal(gf_model* m, const char* who, int index);
+
+// What gf_sampler_host.hip asks of a tempered sampler (s->tp set; gf_temper_host.hip):
+struct gf_sampler;
+struct GfTempered;
+struct Run;
+struct GridSteps;
+// gf_sampler_set_state behind the upload of the positions: the state's scalar T of every walker at its chain's beta, -inf (and counted)
+// where the reference would have raised; synchronous on return
+GF_TEMPER_LOCAL int gf_temper_start(gf_sampler* s);
+// gf_sampler_reset: the swap counters <- 0, on the sampler's stream
+GF_TEMPER_LOCAL hipError_t gf_temper_clear_counts(gf_sampler* s);
+// the run `r` of the grid kernels `g`, with a replica-exchange round behind every swap_every-th step since creation
+GF_TEMPER_LOCAL int gf_temper_run(Run& r, GridSteps& g);
+// gf_sampler_destroy: tp (may be null) and its device buffers
+GF_TEMPER_LOCAL void gf_temper_free(GfTempered* tp);

@@ -10,7 +10,8 @@
 //   k_pt_swap           one replica-exchange round on (lp, lnl) of the current walkers.
 //   k_pt_series         lnl of every stored sample, reduced over the walkers of a step in gf_temper.hpp's order.
 //
-// and the bulk entry point gf_model_lnprior_lnl[_device].  The sampler's host side is gf_sampler_host.hip's (gf_temper.h).
+// Kernels and launchers only (gf_temper.h): the tempered sampler's host side and the bulk entry point gf_model_lnprior_lnl[_device] are
+// gf_temper_host.hip's.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -364,91 +365,3 @@ hipError_t gf_launch_pt_series(const GfSeriesArgs& a, int nchains, hipStream_t s
     hipLaunchKernelGGL(k_pt_series, dim3((unsigned)a.nstored, (unsigned)nchains), dim3(GF_BLOCK), 0, st, a);
     return hipGetLastError();
 }
-
-// ---- the bulk entry point ----------------------------------------------------------------------------------------------------------
-// the flux-averaged BSM likelihood only: what gf_model_lnprior_lnl and gf_sampler_create_tempered say to any other model
-int gf_temper_model_refusal(gf_model* m, const char* who, int index)
-{
-    const GfCommon* c; const GfBsm* tb; const double* ptab; int device, cus, nbins;
-    if (!m || gf_model_constants(m, &c, &tb, &ptab, &device, &cus, &nbins) != GF_OK) return GF_ERR_INVALID_ARG;
-    if (c->mode != MODE_BSM_GAUSS)
-        return gf_fail_msg(GF_ERR_UNSUPPORTED, "%s: model %d has mode %d; lnprior and lnL are taken apart for the flux-averaged BSM likelihood only", who, index, c->mode);
-    if (gf_model_table(m, nullptr) > 0)
-        return gf_fail_msg(GF_ERR_UNSUPPORTED, "%s: model %d carries a tabulated likelihood; the flux-averaged BSM likelihood only", who, index);
-    if (gf_model_binned(m, nullptr))
-        return gf_fail_msg(GF_ERR_UNSUPPORTED, "%s: model %d carries a binned measurement; the flux-averaged BSM likelihood only", who, index);
-    return GF_OK;
-}
-
-extern "C" {
-
-// d_theta [n][ndim] (AoS) -> d_lp, d_lnl [n], d_status [n], all on the device; synchronous on return
-int gf_model_lnprior_lnl_device(gf_model* m, const double* d_theta, int64_t n, double* d_lp, double* d_lnl, int32_t* d_status)
-{
-    if (!m || n < 0 || (n > 0 && (!d_theta || !d_lp || !d_lnl || !d_status))) return GF_ERR_INVALID_ARG;
-    gf_internal_set_error("");
-    if (const int rc = gf_temper_model_refusal(m, "gf_model_lnprior_lnl", 0)) return rc;
-    const GfCommon* c; const GfBsm* tb; const double* ptab; void* stream; int device, cus, nbins;
-    int rc = gf_model_internal(m, &c, &tb, &ptab, &stream, &device);
-    if (rc == GF_OK) rc = gf_model_constants(m, &c, &tb, &ptab, &device, &cus, &nbins);
-    if (rc != GF_OK) return rc;
-    if (n == 0) return GF_OK;
-    hipStream_t st = (hipStream_t)stream;
-    constexpr int64_t PIECE = 1 << 18;                       // rows per launch: bounds the parked rows' buffers
-    const int64_t piece = n < PIECE ? n : PIECE;
-    // one model: the kernels' per-model arrays have one entry each
-    GfScratch sc(GF_MEM_CACHED);
-    GfCommon* d_common = nullptr; const GfBsm** d_tbs = nullptr; const double** d_ptabs = nullptr; GfStepState* d_state = nullptr;
-    (void)sc.take(&d_common, sizeof(GfCommon), "gf_model_lnprior_lnl");
-    (void)sc.take(&d_tbs, sizeof(void*), "gf_model_lnprior_lnl");
-    (void)sc.take(&d_ptabs, sizeof(void*), "gf_model_lnprior_lnl");
-    if (const int ra = sc.take(&d_state, sizeof(GfStepState), "gf_model_lnprior_lnl")) return ra;
-    GfArbQueue* pq = nullptr; double* pend = nullptr; unsigned int* ctl = nullptr;
-    hipError_t e = gf_alloc_arb_queue(GF_MEM_CACHED, (size_t)piece, st, &pq, &pend, &ctl);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_common, c, sizeof(GfCommon), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync((void*)d_tbs, &tb, sizeof(void*), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync((void*)d_ptabs, &ptab, sizeof(void*), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemsetAsync(d_state, 0, sizeof(GfStepState), st);
-    for (int64_t w0 = 0; w0 < n && e == hipSuccess; w0 += piece) {
-        GfSplitArgs a = {};
-        a.commons = d_common; a.tbs = d_tbs; a.ptabs = d_ptabs;
-        a.theta = d_theta + w0 * c->ndim; a.lp = d_lp + w0; a.lnl = d_lnl + w0; a.status = d_status + w0;
-        a.pq = pq; a.pend_rows = pend; a.rows = (int32_t)(n - w0 < piece ? n - w0 : piece); a.ndim = c->ndim; a.nbins_max = nbins;
-        e = gf_launch_lnprior_lnl(a, 1, ctl, d_state, cus, st);
-    }
-    const hipError_t e2 = hipStreamSynchronize(st);
-    for (void* p : {(void*)pq, (void*)pend, (void*)ctl}) if (p) (void)gf_cached_free(p);
-    if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) return gf_hip_fail(e, "gf_model_lnprior_lnl");
-    return GF_OK;
-}
-
-// theta [n][ndim] -> lp, lnl [n], status [n] on the host
-int gf_model_lnprior_lnl(gf_model* m, const double* theta, int64_t n, double* lp, double* lnl, int32_t* status)
-{
-    if (!m || n < 0 || (n > 0 && (!theta || !lp || !lnl || !status))) return GF_ERR_INVALID_ARG;
-    gf_internal_set_error("");
-    if (const int rc = gf_temper_model_refusal(m, "gf_model_lnprior_lnl", 0)) return rc;
-    if (n == 0) return GF_OK;
-    const GfCommon* c; const GfBsm* tb; const double* ptab; void* stream; int device;
-    const int rc = gf_model_internal(m, &c, &tb, &ptab, &stream, &device);
-    if (rc != GF_OK) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    GfScratch sc(GF_MEM_CACHED);
-    double *d_theta = nullptr, *d_lp = nullptr, *d_lnl = nullptr; int32_t* d_status = nullptr;
-    (void)sc.take(&d_theta, sizeof(double) * (size_t)n * c->ndim, "gf_model_lnprior_lnl");
-    (void)sc.take(&d_lp, sizeof(double) * (size_t)n, "gf_model_lnprior_lnl");
-    (void)sc.take(&d_lnl, sizeof(double) * (size_t)n, "gf_model_lnprior_lnl");
-    if (const int ra = sc.take(&d_status, sizeof(int32_t) * (size_t)n, "gf_model_lnprior_lnl")) return ra;
-    GF_HIP(hipMemcpyAsync(d_theta, theta, sizeof(double) * (size_t)n * c->ndim, hipMemcpyHostToDevice, st));
-    GF_HIP(hipStreamSynchronize(st));
-    const int re = gf_model_lnprior_lnl_device(m, d_theta, n, d_lp, d_lnl, d_status);
-    if (re != GF_OK) return re;
-    GF_HIP(hipMemcpyAsync(lp, d_lp, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
-    GF_HIP(hipMemcpyAsync(lnl, d_lnl, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
-    GF_HIP(hipMemcpyAsync(status, d_status, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
-    GF_HIP(hipStreamSynchronize(st));
-    return GF_OK;
-}
-
-}  // extern "C"

@@ -369,6 +369,48 @@ def test_graph_replays_and_eager_steps_give_the_same_chain(posts):
     assert np.array_equal(ca[0], cb[0]) and np.array_equal(ca[1], cb[1]) and ca[0].sum() > 0
 
 
+def rounds_run(posts, run):
+    """the shape of the test above -- 6 chains, a round every 20 steps: 16 replayed and 4 eager steps before each, an 8-step tail of 48 --
+    on a fresh sampler: what `run(smp, p0)` returns, what it left on the device, and the swap counts"""
+    p0 = prior_draws(posts["ps"], 6 * NW, np.random.default_rng(63)).reshape(6, NW, 12)
+    smp = tempered([posts["s01"], posts["out01"]], [1.0, 0.3, 0.0], seed=47, swap_every=20, ngroups=2)
+    try:
+        out = run(smp, p0)
+        return out, device_run(smp), smp.swap_counts()
+    finally:
+        smp.close()
+
+
+def whole_run(posts):
+    return shared("rounds: 48 steps at thin 2", lambda: rounds_run(posts, lambda smp, p0: smp.run_mcmc(p0, 48, thin=2))[1:])
+
+
+def test_read_back_during_a_tempered_run(posts):
+    """run_mcmc_to_host over two rounds: what crossed to the host block by block is the stored chain of the same run, bit for bit, and
+    the run is the one run_mcmc makes"""
+    ref, counts = whole_run(posts)
+    (c, lnp), got, cb = rounds_run(posts, lambda smp, p0: smp.run_mcmc_to_host(p0, 48, thin=2, lnprob=True))
+    assert c.shape == (6, 24, NW, 12) and lnp.shape == (6, 24, NW)
+    assert same_bits(c, ref["chain"]) and same_bits(lnp, ref["lnp_chain"])
+    assert_same_run(got, ref, "run_mcmc_to_host against run_mcmc")
+    assert np.array_equal(cb[0], counts[0]) and np.array_equal(cb[1], counts[1]) and counts[0].sum() > 0
+
+
+def test_a_run_continued_across_a_round(posts):
+    """30 steps, then 18: rounds are counted from creation, so the second run has its round behind its 10th step, and the two are the
+    single run of 48.  Both are below the 32 steps from which a run replays a graph: eager blocks cut at other steps than the single
+    run's replays and blocks, the same chain."""
+    ref, counts = whole_run(posts)
+
+    def two_runs(smp, p0):
+        smp.run_mcmc(p0, 30, thin=2)
+        smp.run_mcmc(None, 18, thin=2)
+
+    _, got, cb = rounds_run(posts, two_runs)
+    assert_same_run(got, ref, "30 + 18 steps against 48")
+    assert np.array_equal(cb[0], counts[0]) and np.array_equal(cb[1], counts[1]) and counts[0].sum() > 0
+
+
 # ---- 5. the series kernel ----------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("nw, nsteps", [(24, 1), (24, 7), (100, 1), (100, 7)])
 def test_series_against_the_host_build(posts, nw, nsteps):
