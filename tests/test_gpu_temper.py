@@ -88,8 +88,8 @@ def posts():
         f[k].close()
 
 
-def tempered(fns, betas, nw=NW, seed=5, swap_every=0, ngroups=None, stream_ids=None):
-    return mcmc_utils.DeviceEnsembleSampler(nw, 12, fns, seed=seed, betas=betas, swap_every=swap_every, ngroups=ngroups, stream_ids=stream_ids)
+def tempered(fns, betas, nw=NW, seed=5, swap_every=0, ngroups=None, stream_ids=None, ndim=12):
+    return mcmc_utils.DeviceEnsembleSampler(nw, ndim, fns, seed=seed, betas=betas, swap_every=swap_every, ngroups=ngroups, stream_ids=stream_ids)
 
 
 # ---- 1. lnprior and lnl apart ---------------------------------------------------------------------------------------------------------------
@@ -250,8 +250,10 @@ def test_tempered_half_step_through_the_failing_region(oracle, posts, lpw):
 
 
 # ---- 4. replica exchange against a numpy restatement of the round ---------------------------------------------------------------------------
-def numpy_tempered(oracle, models, betas, p0, nsteps, seed, swap_every, stream_ids=None):
-    """The tempered run in numpy: reference_stretch between the rounds, TH.swap_round for a round.  models: one per group."""
+def numpy_tempered(oracle, models, betas, p0, nsteps, seed, swap_every, stream_ids=None, rounds=None):
+    """The tempered run in numpy: reference_stretch between the rounds, TH.swap_round for a round.  models: one per group.  rounds: a
+    list that receives one dict per round -- its number, and copies of what the round started from (pos, T, lp, lnl, status) and of the
+    positions it left."""
     K = len(betas)
     nch = p0.shape[0]
     oms = [(models[ch // K], betas[ch % K]) for ch in range(nch)]
@@ -270,7 +272,12 @@ def numpy_tempered(oracle, models, betas, p0, nsteps, seed, swap_every, stream_i
         if swap_every and it % swap_every == 0:
             ev = [m.lnprior_lnlike(np.ascontiguousarray(pos[ch])) for ch, (m, _) in enumerate(oms)]
             lp, lnl = np.stack([e[0] for e in ev]), np.stack([e[1] for e in ev])
+            if rounds is not None:
+                rounds.append({"round": it // swap_every - 1, "pos": pos.copy(), "T": lnp.copy(), "lp": lp, "lnl": lnl,
+                               "status": np.stack([e[2] for e in ev])})
             TH.swap_round(oracle, seed, it // swap_every - 1, betas, pos, lnp, lp, lnl, counts, stream_ids)
+            if rounds is not None:
+                rounds[-1]["pos_after"] = pos.copy()
     return {"chain": np.concatenate(chain, axis=1), "lnp_chain": np.concatenate(lnp_chain, axis=1), "pos": pos, "lnp": lnp, "nacc": nacc,
             "counts": counts}
 
@@ -412,6 +419,26 @@ def test_a_run_continued_across_a_round(posts):
 
 
 # ---- 5. the series kernel ----------------------------------------------------------------------------------------------------------------------
+def series_against_host(smp, models, betas):
+    """(series, lnl) of the stored chain, held to the host build of gf_temper.hpp fed lnprior_lnlike of the stored chain; models: one
+    per group"""
+    K = len(betas)
+    ser, lnl = smp.lnl_series(want_lnl=True)
+    chain = device_run(smp)["chain"]
+    nch, nsteps, nw, ndim = chain.shape
+    assert ser.shape == (nch, nsteps, 5) and lnl.shape == (nch, nsteps, nw)
+    b = np.array(betas)
+    d_up = np.concatenate([[0.0], b[:-1] - b[1:]])                     # the distance in beta to the rung above, and below
+    d_dn = np.concatenate([b[:-1] - b[1:], [0.0]])
+    for ch in range(nch):
+        want_lnl = models[ch // K].lnprior_lnlike(chain[ch].reshape(-1, ndim))[1].reshape(nsteps, nw)
+        fin = np.isfinite(want_lnl)
+        assert np.array_equal(fin, np.isfinite(lnl[ch])) and same_bits(lnl[ch][fin], want_lnl[fin])
+        want = TH.host_series(want_lnl, d_up[ch % K], d_dn[ch % K])
+        assert same_bits(ser[ch], want), (ch, ser[ch], want)
+    return ser, lnl
+
+
 @pytest.mark.parametrize("nw, nsteps", [(24, 1), (24, 7), (100, 1), (100, 7)])
 def test_series_against_the_host_build(posts, nw, nsteps):
     """all five outputs against the host build of gf_temper.hpp fed lnprior_lnlike of the stored chain; rung 1 starts outside the
@@ -423,18 +450,8 @@ def test_series_against_the_host_build(posts, nw, nsteps):
     smp = tempered(f, betas, nw=nw, seed=53, swap_every=2)
     try:
         smp.run_mcmc(p0, nsteps)
-        ser, lnl = smp.lnl_series(want_lnl=True)
-        chain = device_run(smp)["chain"]
+        ser, lnl = series_against_host(smp, [f.model], betas)
         assert ser.shape == (4, nsteps, 5) and lnl.shape == (4, nsteps, nw)
-        b = np.array(betas)
-        d_up = np.concatenate([[0.0], b[:-1] - b[1:]])                     # the distance in beta to the rung above, and below
-        d_dn = np.concatenate([b[:-1] - b[1:], [0.0]])
-        for ch in range(4):
-            want_lnl = f.model.lnprior_lnlike(chain[ch].reshape(-1, 12))[1].reshape(nsteps, nw)
-            fin = np.isfinite(want_lnl)
-            assert np.array_equal(fin, np.isfinite(lnl[ch])) and same_bits(lnl[ch][fin], want_lnl[fin])
-            want = TH.host_series(want_lnl, d_up[ch], d_dn[ch])
-            assert same_bits(ser[ch], want), (ch, ser[ch], want)
         assert np.all(ser[1, :, 0] == 0) and np.all(ser[1, :, 1] == 0) and np.all(ser[1, :, 2] == -np.inf) and np.all(ser[1, :, 3:] == 0)
         assert np.all(ser[0, :, 0] > 0) and np.any(ser[3, :, 0] < nw)          # the prior chain holds samples on the plateau
         assert same_bits(smp.lnlikelihood(), lnl.transpose(0, 2, 1))
