@@ -63,7 +63,7 @@ def reference_counts(x, ranges, nb1, nb2):
     W = x.shape[1]
     c1 = np.stack([np.histogram(x[:, c], bins=nb1, range=tuple(ranges[c]))[0] for c in range(W)])
     c2 = [np.histogram2d(x[:, i], x[:, j], bins=nb2, range=[tuple(ranges[i]), tuple(ranges[j])])[0] for i in range(W) for j in range(i + 1, W)]
-    return c1.astype(np.uint64), np.array(c2, dtype=np.uint64).reshape(-1, nb2, nb2)
+    return c1.astype(np.uint64), np.array(c2, dtype=np.uint64).reshape(len(c2), nb2, nb2)        # (0, nb2, nb2) for one column
 
 
 def reference_region(counts, coverage, sigma):
@@ -86,9 +86,9 @@ def synthetic(n=250000, seed=5):
     return np.ascontiguousarray(x), [(0., 1.), (0., 1.), TWO_PI, LOGLAM, (0., 4.), (-2.5, 3.)]
 
 
-def planted(ranges, nb_list, seed=9):
+def planted(ranges, nb_list, seed=9, nrows=None, nan_col=1):
     """rows with values on every edge of every binning, at lo and hi, one ulp on either side of each, outside the range, and NaN
-    in one column only; the other entries uniform over a slightly wider range"""
+    in one column only; the other entries uniform over a slightly wider range.  nrows: that many rows instead of the default."""
     rng = np.random.default_rng(seed)
     W = len(ranges)
     special = []
@@ -98,11 +98,12 @@ def planted(ranges, nb_list, seed=9):
             e = np.linspace(lo, hi, nb + 1)
             vals += list(e) + list(np.nextafter(e, -np.inf)) + list(np.nextafter(e, np.inf))
         special.append(np.array(vals))
-    n = max(len(s) for s in special) * 3 + 4000
+    n = max(len(s) for s in special) * 3 + 4000 if nrows is None else int(nrows)
+    assert n >= max(len(s) for s in special) + 37
     x = np.stack([rng.uniform(lo - 0.05 * (hi - lo), hi + 0.05 * (hi - lo), n) for lo, hi in ranges], axis=1)
     for c, s in enumerate(special):
         x[rng.permutation(n)[:len(s)], c] = s
-    x[rng.permutation(n)[:37], 1] = np.nan                      # NaN in one column only
+    x[rng.permutation(n)[:37], nan_col] = np.nan                # NaN in one column only
     return np.ascontiguousarray(x)
 
 
@@ -124,6 +125,10 @@ def check_counts_and_order_statistics(res, x, ranges, nb1, nb2, q, ranks, what):
                 assert res.order_ranks[c, slot] == -1 and np.isnan(res.order_stats[c, slot]), (what, c, k)
         for t, qq in enumerate(q):
             lo, hi = res.order_ranks[c, len(ranks) + 2 * t], res.order_ranks[c, len(ranks) + 2 * t + 1]
+            if n == 0:                                            # a column of NaN alone: no rank, NaN as np.percentile of nothing
+                assert lo == hi == -1 and np.all(np.isnan(res.order_stats[c, len(ranks) + 2 * t:len(ranks) + 2 * t + 2])), (what, c, qq)
+                assert np.isnan(res.percentiles[c, t]), (what, c, qq)
+                continue
             assert res.order_stats[c, len(ranks) + 2 * t] == s[lo] and res.order_stats[c, len(ranks) + 2 * t + 1] == s[hi], (what, c, qq)
             assert res.percentiles[c, t] == np.percentile(s, qq), (what, c, qq, res.percentiles[c, t], np.percentile(s, qq))
 
