@@ -288,6 +288,8 @@ SIGNATURES = {
     "gf_model_lnprior_lnl": (C.c_int, [_vp, _dp, C.c_int64, _dp, _dp, _ip]),
     "gf_model_lnprior_lnl_device": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp]),
     "gf_sampler_create_tempered": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_uint64, C.c_double, C.c_int, C.POINTER(_vp)]),
+    "gf_sampler_create_tempered_binned": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_uint64, C.c_double, C.c_int, C.POINTER(_vp)]),
+    "gf_sampler_create_tempered_table": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_uint64, C.c_double, C.c_int, C.POINTER(_vp)]),
     "gf_sampler_tempered_series": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _vp]),
     "gf_sampler_swap_counts": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "gf_sampler_betas": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), _dp, C.POINTER(C.c_int)]),

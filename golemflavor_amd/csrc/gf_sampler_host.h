@@ -95,6 +95,9 @@ GridSteps grid_steps(gf_sampler* s, int store, int lpw);
 // models[ch]): the model set has one entry per model.  want: the likelihood the sampler evaluates -- GF_LLH_BINNED
 // (gf_sampler_create_binned), GF_LLH_TABLE (gf_sampler_create_table) or the flux-averaged one; every model must carry exactly that.
 int sampler_create(gf_model* const* models, bool multi, int nchains, int nwalkers, uint64_t seed, double a, gf_sampler** out, int want = GF_LLH_FLUX);
+// GF_OK, or the refusal -- code and message -- of a model that carries the GfLikelihood `has` where the sampler evaluates `want`; index:
+// the model's, as the caller numbers its models (a tempered sampler: the group's, not the chain's)
+int sampler_likelihood_refusal(int want, int has, int index);
 // GF_OK, or the refusal of the entry point `who` for a sampler whose models' likelihood is no longer the one it was created for
 int sampler_kind_refusal(const gf_sampler* s, const char* who);
 // Once per run, before its first grid block and with `g` complete: whether the run replays a graph (GF_SAMPLER_NO_GRAPH unset, at least

@@ -54,17 +54,8 @@ struct Stopwatch {
 // another.  The refusals, model by model in the order the set examined them.
 int sampler_refusal(const GfModelSet& set, int want)
 {
-    for (int ch = 0; ch < (int)set.carries.size(); ++ch) {
-        const int has = set.carries[ch];
-        if (has == want) continue;
-        if (want == GF_LLH_TABLE)
-            return gf_fail_msg(GF_ERR_INVALID_ARG, "gf_sampler_create_table: model %d carries no tabulated likelihood; all of a sampler's models must", ch);
-        if (has == GF_LLH_TABLE)
-            return gf_fail_msg(GF_ERR_UNSUPPORTED, "gf_sampler_create: model %d carries a tabulated likelihood; sample the flux-averaged model and reweight the chain to this one", ch);
-        if (want == GF_LLH_BINNED)
-            return gf_fail_msg(GF_ERR_INVALID_ARG, "gf_sampler_create_binned: model %d carries no binned measurement; all of a sampler's models must", ch);
-        return gf_fail_msg(GF_ERR_UNSUPPORTED, "gf_sampler_create: model %d carries a binned measurement; sample the flux-averaged model and reweight the chain to this one", ch);
-    }
+    for (int ch = 0; ch < (int)set.carries.size(); ++ch)
+        if (const int rc = sampler_likelihood_refusal(want, set.carries[ch], ch)) return rc;
     if (set.differs >= 0)
         return gf_fail_msg(GF_ERR_INVALID_ARG, "gf_sampler_create_multi: model %d differs from model 0 in device, ndim or mode", set.differs);
     return GF_OK;
@@ -396,6 +387,18 @@ int sampler_kind_refusal(const gf_sampler* s, const char* who)
     if (differs < 0) return GF_OK;
     return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: model %d now carries %s; the sampler's kernels evaluate the likelihood it was created for (%s)", who, differs,
                        gf_likelihood_name(now), gf_likelihood_name(s->set.kind));
+}
+
+int sampler_likelihood_refusal(int want, int has, int index)
+{
+    if (has == want) return GF_OK;
+    if (want == GF_LLH_TABLE)
+        return gf_fail_msg(GF_ERR_INVALID_ARG, "gf_sampler_create_table: model %d carries no tabulated likelihood; all of a sampler's models must", index);
+    if (has == GF_LLH_TABLE)
+        return gf_fail_msg(GF_ERR_UNSUPPORTED, "gf_sampler_create: model %d carries a tabulated likelihood; sample the flux-averaged model and reweight the chain to this one", index);
+    if (want == GF_LLH_BINNED)
+        return gf_fail_msg(GF_ERR_INVALID_ARG, "gf_sampler_create_binned: model %d carries no binned measurement; all of a sampler's models must", index);
+    return gf_fail_msg(GF_ERR_UNSUPPORTED, "gf_sampler_create: model %d carries a binned measurement; sample the flux-averaged model and reweight the chain to this one", index);
 }
 
 int sampler_create(gf_model* const* models, bool multi, int nchains, int nwalkers, uint64_t seed, double a, gf_sampler** out, int want)

@@ -7,7 +7,7 @@
 #include "gf_sampler_launch.h"
 
 // k_lnprior_lnl: lnprior and lnl apart for `rows` rows of each of the grid's blockIdx.y models (row i of model r is row r * rows + i of
-// every array); the flux-averaged BSM likelihood only.  Rows whose unitarity verdict the in-kernel tiers cannot settle are parked
+// every array), under the likelihood the models carry.  Rows whose unitarity verdict the in-kernel tiers cannot settle are parked
 // (pq / pend_rows, capacity: every row) and settled exactly, as the maximiser's candidates are, before k_pt_finish ends the call.
 struct GfSplitArgs {
     const GfCommon* commons;        // [nmodels]
@@ -23,6 +23,11 @@ struct GfSplitArgs {
     // k_pt_finish, optional: T [nmodels * rows] <- lp + betas[r] lnl (gf_temper.hpp), NaN where the reference would have raised
     const double* betas;            // [nmodels]
     double* T;
+    // the likelihood the models carry, as StretchArgs has it: [nmodels] the binned measurements (the energy-resolved instance), or the
+    // tables in global memory and their sides (the tabulated instance); all NULL: the flux-averaged instance
+    const double* const* btabs;
+    const double* const* ttabs;
+    const int32_t* tsides;
 };
 
 // k_pt_swap: one replica-exchange round (gf_temper.hpp) over chains [ngroups][ntemps]
@@ -51,10 +56,14 @@ struct GfSeriesArgs {
     const double* d_dn;
     double* lnl;                    // [nchains][nstored][nwalkers]
     double* out;                    // [nchains][nstored][5]
+    const double* const* btabs;     // [nchains], as GfSplitArgs'
+    const double* const* ttabs;
+    const int32_t* tsides;
 };
 
 #define GF_TEMPER_LOCAL __attribute__((visibility("hidden")))
-// one tempered half-step of every chain, one model per chain (a.commons set): chain ch samples prior * L^betas[ch]
+// one tempered half-step of every chain, one model per chain (a.commons set): chain ch samples prior * L^betas[ch]; the instance is the
+// tabulated likelihood's where a.ttabs is set, the energy-resolved one's where a.btabs is, else the flux-averaged one's
 GF_TEMPER_LOCAL hipError_t gf_launch_stretch_tempered(const StretchArgs& a, const double* d_betas, int ndim, hipStream_t st);
 // k_lnprior_lnl, the exact verdict of the rows it parked (ctl: [nmodels * rows][2], zero between uses; state: any GfStepState on the
 // device) and k_pt_finish, in stream order

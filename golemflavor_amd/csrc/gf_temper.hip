@@ -1,5 +1,6 @@
 // gf_temper.hip -- the kernels of the tempered ensemble sampler: chains that sample prior * L^beta, their replica
-// exchange, and the reduction of their lnl that the stepping-stone evidence starts from.  The flux-averaged BSM likelihood only.
+// exchange, and the reduction of their lnl that the stepping-stone evidence starts from.  One instance per likelihood of a BSM model: the
+// flux-averaged Gaussian, the energy-resolved Gaussian and the tabulated flavour-plane likelihood.
 //
 //   k_lnprior_lnl       lnprior and lnl of a row apart, one model per row block: where the status is OK their rounded sum is lnprob bit
 //                       for bit.  The pieces are proposal_lnprob's (gf_propose.hpp); the exact verdict of a row the in-kernel tiers
@@ -26,13 +27,19 @@
 namespace {
 using namespace gfdev;
 
-// lnprior and lnl of the row in LDS `row`, and the walker's scalar at `beta`: proposal_lnprob's MODE_BSM_GAUSS body with the sum taken
-// apart.  st is what the bulk kernel gives the row (ST_NAN: lp + lnl is NaN); pending as proposal_lnprob's.
-template <int NDIM, int LPW>
+// lnprior and lnl of the row in LDS `row`, and the walker's scalar at `beta`: proposal_lnprob's (gf_propose.hpp) BSM bodies with the sum
+// taken apart -- its pieces, its verdict lines, its `pending`; the likelihood stays where each body has it (behind the verdict lines,
+// but for the binned one, whose bin loop carries the verdict's tiers).  st is what the bulk kernel gives the row (ST_NAN: lp + lnl is
+// NaN).  MODE_BSM_BINNED (one lane per walker only): `ltab` is the model's binned measurement, staged in LDS by the caller.
+// MODE_BSM_TABLE: `ltab` is the model's table in global memory and `tside` its side; a hole (lnl = -inf) is a legal point of the box:
+// T = -inf at every beta > 0 and T = lp at beta = 0.
+template <int NDIM, int MODE, int LPW>
 __device__ __forceinline__ double tempered_eval(const GfCommon& c, const GfBsm* tb, const double* ctab, const double* ttab, const double* row,
                                                 int ndim, double beta, int& st, int sub, double* fgrp, unsigned long long& pending, double& lp_out,
-                                                double& lnl_out)
+                                                double& lnl_out, const double* ltab = nullptr, int tside = 0)
 {
+    static_assert(MODE == MODE_BSM_GAUSS || MODE == MODE_BSM_BINNED || MODE == MODE_BSM_TABLE, "a tempered chain samples a BSM likelihood");
+    static_assert(MODE != MODE_BSM_BINNED || LPW == 1, "the binned likelihood runs one lane per point");
     pending = 0ull;
     double lp, fr[3];
     const bool inbox = lnprior_tab<NDIM>(ctab, row, ndim, c.prior_const, lp);
@@ -43,10 +50,13 @@ __device__ __forceinline__ double tempered_eval(const GfCommon& c, const GfBsm* 
     lnl_out = -gf_inf();
     if (inbox) {
         UniAcc acc = {0.0, 0.0, 0ull, 2.0};
-        flux_average<UNI_INLINE, LPW>(c, tb, ttab, row, fr, acc, sub, fgrp);
+        double lnl = 0.0;
+        if constexpr (MODE == MODE_BSM_BINNED) lnl = binned_llh<UNI_INLINE>(c, tb, ttab, ltab, row, acc) + c.offset;
+        else flux_average<UNI_INLINE, LPW>(c, tb, ttab, row, fr, acc, sub, fgrp);
         st = (acc.clear_max < tb->uni_hi) ? ST_OK : ST_NON_UNITARY;       // tiers 1 and 2 (gf_bsm_device.hpp)
         pending = st == ST_OK ? uni_arbitration_mask(acc.amb, tb) : 0ull;
-        const double lnl = gauss_llh(c, fr);
+        if constexpr (MODE == MODE_BSM_GAUSS) lnl = gauss_llh(c, fr);
+        if constexpr (MODE == MODE_BSM_TABLE) lnl = gftab::lookup(ltab, tside, fr[0], fr[1]);
         val = gftp::temper(lp, lnl, beta);
         if (lnl != lnl && st == ST_OK) st = ST_NAN;                        // lp is finite in the box: lp + lnl is NaN iff lnl is
         lp_out = lp;
@@ -55,7 +65,30 @@ __device__ __forceinline__ double tempered_eval(const GfCommon& c, const GfBsm* 
     return val;
 }
 
-template <int LPW>
+// the likelihood table of chain / model r as tempered_eval takes it: the binned measurement staged in LDS (the caller syncs), the table's
+// address in global memory and its side, or nothing.  The LDS array exists in the binned instances alone: declared in the kernels, even
+// at one double, it moves the flux-averaged instances' register figures.
+// (The arrays are handed over one by one: the kernels' argument structs taken by reference move the flux-averaged instances' figures too.)
+struct LlhTable {
+    const double* tab;
+    int side;
+};
+template <int MODE>
+__device__ __forceinline__ LlhTable stage_llh_table(const double* const* btabs, const double* const* ttabs, const int32_t* tsides, int r,
+                                                    const GfBsm* tb)
+{
+    if constexpr (MODE == MODE_BSM_BINNED) {
+        __shared__ __attribute__((aligned(16))) double btab[GF_BINNED_DOUBLES];
+        load_binned_table(btab, btabs[r], tb->nbins);
+        return {btab, 0};
+    } else if constexpr (MODE == MODE_BSM_TABLE) {
+        return {ttabs[r], tsides[r]};
+    } else {
+        return {nullptr, 0};
+    }
+}
+
+template <int MODE, int LPW>
 __global__ __launch_bounds__(GF_BLOCK) void k_lnprior_lnl(const GfSplitArgs a)
 {
     const int r = blockIdx.y;
@@ -67,6 +100,7 @@ __global__ __launch_bounds__(GF_BLOCK) void k_lnprior_lnl(const GfSplitArgs a)
     const GfBsm* tb = a.tbs[r];
     double* ttab = ctab + GF_MAX_DIM * 4;
     load_eval_tables(ctab, a.ptabs[r], tb, true);
+    const LlhTable lt = stage_llh_table<MODE>(a.btabs, a.ttabs, a.tsides, r, tb);
     __syncthreads();
     const int t = blockIdx.x * GF_BLOCK + threadIdx.x;
     const int k = t / LPW, sub = t % LPW;
@@ -79,7 +113,7 @@ __global__ __launch_bounds__(GF_BLOCK) void k_lnprior_lnl(const GfSplitArgs a)
     int st;
     unsigned long long pending;
     double lp, lnl;
-    (void)tempered_eval<0, LPW>(c, tb, ctab, ttab, row, a.ndim, 1.0, st, sub, fgrp, pending, lp, lnl);
+    (void)tempered_eval<0, MODE, LPW>(c, tb, ctab, ttab, row, a.ndim, 1.0, st, sub, fgrp, pending, lp, lnl, lt.tab, lt.side);
     if (LPW > 1 && sub != 0) return;                         // the group's results are identical: one writer
     a.lp[i] = lp;
     a.lnl[i] = lnl;
@@ -104,7 +138,7 @@ __global__ void k_pt_finish(const GfSplitArgs a, int64_t n)
 #ifndef GF_STRETCH_WAVES
 #define GF_STRETCH_WAVES 2
 #endif
-template <int NDIM, int LPW>
+template <int NDIM, int MODE, int LPW>
 __global__ __launch_bounds__(GF_BLOCK, GF_STRETCH_WAVES) void k_stretch_tempered(const StretchArgs s, const double* __restrict__ betas)
 {
     const int chain = blockIdx.y;
@@ -121,6 +155,7 @@ __global__ __launch_bounds__(GF_BLOCK, GF_STRETCH_WAVES) void k_stretch_tempered
     __shared__ __attribute__((aligned(16))) double ctab[GF_MAX_DIM * 4 + 20];
     double* ttab = ctab + GF_MAX_DIM * 4;
     load_eval_tables(ctab, s.ptabs[chain], tb, true);
+    const LlhTable lt = stage_llh_table<MODE>(s.btabs, s.ttabs, s.tsides, chain, tb);
     __syncthreads();
 
     const int ndim = NDIM ? NDIM : c.ndim;
@@ -148,7 +183,7 @@ __global__ __launch_bounds__(GF_BLOCK, GF_STRETCH_WAVES) void k_stretch_tempered
     int st;
     unsigned long long pending;
     double lp, lnl;
-    const double lnq = tempered_eval<NDIM, LPW>(c, tb, ctab, ttab, row, ndim, beta, st, sub, fgrp, pending, lp, lnl);
+    const double lnq = tempered_eval<NDIM, MODE, LPW>(c, tb, ctab, ttab, row, ndim, beta, st, sub, fgrp, pending, lp, lnl, lt.tab, lt.side);
     const int64_t wi = (int64_t)chain * s.nwalkers + w;
     const double lnk = s.lnp[wi];
     const double lhs = stretch_lhs(z, u3, ndim);
@@ -230,7 +265,9 @@ __device__ __forceinline__ double fold256(double* s, double v)
     return gfnp::add(gfnp::add(gfnp::add(s[0], s[64]), s[128]), s[192]);
 }
 
-// one workgroup per (stored step, chain)
+// one workgroup per (stored step, chain).  Static LDS: 32 KiB of tiles, ctab, the fold's 2 KiB and, in the binned instance, the chain's
+// measurement (GF_BINNED_DOUBLES doubles = 2.5 KiB): 37.5 KiB of a workgroup's 64.
+template <int MODE>
 __global__ __launch_bounds__(GF_BLOCK) void k_pt_series(const GfSeriesArgs a)
 {
     static_assert(GF_BLOCK == gfnp::LANES, "the walker sum's lanes are the workgroup's");
@@ -244,6 +281,7 @@ __global__ __launch_bounds__(GF_BLOCK) void k_pt_series(const GfSeriesArgs a)
     const GfBsm* tb = a.tbs[chain];
     double* ttab = ctab + GF_MAX_DIM * 4;
     load_eval_tables(ctab, a.ptabs[chain], tb, true);
+    const LlhTable lt = stage_llh_table<MODE>(a.btabs, a.ttabs, a.tsides, chain, tb);
     if (threadIdx.x == 0) cnt = 0u;
     __syncthreads();
     const int lane = threadIdx.x & (GF_WAVE - 1);
@@ -260,7 +298,7 @@ __global__ __launch_bounds__(GF_BLOCK) void k_pt_series(const GfSeriesArgs a)
             int st;
             unsigned long long pending;
             double lp;
-            (void)tempered_eval<0, 1>(c, tb, ctab, ttab, row, a.ndim, 1.0, st, 0, nullptr, pending, lp, lnl);
+            (void)tempered_eval<0, MODE, 1>(c, tb, ctab, ttab, row, a.ndim, 1.0, st, 0, nullptr, pending, lp, lnl, lt.tab, lt.side);
         }
         lnl_out[w] = lnl;
         if (gftp::finite(lnl)) { ++mine; m = lnl > m ? lnl : m; }
@@ -292,26 +330,55 @@ __global__ __launch_bounds__(GF_BLOCK) void k_pt_series(const GfSeriesArgs a)
     }
 }
 
-template <int NDIM>
-hipError_t launch_tempered_n(const StretchArgs& a, const double* d_betas, hipStream_t st)
+template <int NDIM, int MODE>
+hipError_t launch_tempered_nm(const StretchArgs& a, const double* d_betas, hipStream_t st)
 {
     auto go = [&](auto l) {
         constexpr int LPW = decltype(l)::value;
         const size_t lds = LPW > 1 ? (size_t)(GF_BLOCK / LPW) * GF_FGRP_DOUBLES(a.nbins_max, LPW) * sizeof(double) : 0;
         const dim3 grid((unsigned)(((int64_t)(a.nwalkers / 2) * LPW + GF_BLOCK - 1) / GF_BLOCK), a.nchains);
-        hipLaunchKernelGGL((k_stretch_tempered<NDIM, LPW>), grid, dim3(GF_BLOCK), lds, st, a, d_betas);
+        hipLaunchKernelGGL((k_stretch_tempered<NDIM, MODE, LPW>), grid, dim3(GF_BLOCK), lds, st, a, d_betas);
         return hipGetLastError();
     };
-    switch (a.lpw) {
-    case 2: return go(std::integral_constant<int, 2>());
-    case 4: return go(std::integral_constant<int, 4>());
-    case 16: return go(std::integral_constant<int, 16>());
-    default: return go(std::integral_constant<int, 1>());
+    if constexpr (MODE != MODE_BSM_BINNED) {
+        switch (a.lpw) {
+        case 2: return go(std::integral_constant<int, 2>());
+        case 4: return go(std::integral_constant<int, 4>());
+        case 16: return go(std::integral_constant<int, 16>());
+        default: break;
+        }
     }
+    return go(std::integral_constant<int, 1>());
+}
+
+// the instance of the likelihood the arguments carry a table for, as gf_launch_stretch: the tabulated one's where ttabs is set, the
+// energy-resolved one's where btabs is, else the flux-averaged one's
+template <int NDIM>
+hipError_t launch_tempered_n(const StretchArgs& a, const double* d_betas, hipStream_t st)
+{
+    if (a.ttabs) return launch_tempered_nm<NDIM, MODE_BSM_TABLE>(a, d_betas, st);
+    if (a.btabs) return launch_tempered_nm<NDIM, MODE_BSM_BINNED>(a, d_betas, st);
+    return launch_tempered_nm<NDIM, MODE_BSM_GAUSS>(a, d_betas, st);
 }
 
 // the lanes of a split evaluation: the nested sampler's and the maximiser's choices, forced by GF_TEMPER_LPW
 const GfLpwRule SPLIT_RULE = {false, 32 * 1024, "GF_TEMPER_LPW"};
+
+template <int MODE>
+hipError_t launch_split_m(const GfSplitArgs& a, int nmodels, int lpw, hipStream_t st)
+{
+    const size_t lds = lpw > 1 ? (size_t)(GF_BLOCK / lpw) * GF_FGRP_DOUBLES(a.nbins_max, lpw) * sizeof(double) : 0;
+    const dim3 grid((unsigned)(((int64_t)a.rows * lpw + GF_BLOCK - 1) / GF_BLOCK), nmodels);
+    if constexpr (MODE != MODE_BSM_BINNED) {
+        switch (lpw) {
+        case 4: hipLaunchKernelGGL((k_lnprior_lnl<MODE, 4>), grid, dim3(GF_BLOCK), lds, st, a); return hipGetLastError();
+        case 16: hipLaunchKernelGGL((k_lnprior_lnl<MODE, 16>), grid, dim3(GF_BLOCK), lds, st, a); return hipGetLastError();
+        default: break;
+        }
+    }
+    hipLaunchKernelGGL((k_lnprior_lnl<MODE, 1>), grid, dim3(GF_BLOCK), lds, st, a);
+    return hipGetLastError();
+}
 
 }  // namespace
 
@@ -328,15 +395,11 @@ hipError_t gf_launch_lnprior_lnl(const GfSplitArgs& a, int nmodels, unsigned int
 {
     const int64_t n = (int64_t)nmodels * a.rows;
     if (n == 0) return hipSuccess;
-    const int lpw = lanes_per_walker(MODE_BSM_GAUSS, n, a.nbins_max, cus, SPLIT_RULE);
-    const size_t lds = lpw > 1 ? (size_t)(GF_BLOCK / lpw) * GF_FGRP_DOUBLES(a.nbins_max, lpw) * sizeof(double) : 0;
-    const dim3 grid((unsigned)(((int64_t)a.rows * lpw + GF_BLOCK - 1) / GF_BLOCK), nmodels);
-    switch (lpw) {
-    case 4: hipLaunchKernelGGL(k_lnprior_lnl<4>, grid, dim3(GF_BLOCK), lds, st, a); break;
-    case 16: hipLaunchKernelGGL(k_lnprior_lnl<16>, grid, dim3(GF_BLOCK), lds, st, a); break;
-    default: hipLaunchKernelGGL(k_lnprior_lnl<1>, grid, dim3(GF_BLOCK), lds, st, a); break;
-    }
-    hipError_t e = hipGetLastError();
+    // the energy-resolved likelihood: one lane per row; the tabulated one: the flux-averaged rule, whose bins it splits
+    const int lpw = a.btabs ? 1 : lanes_per_walker(MODE_BSM_GAUSS, n, a.nbins_max, cus, SPLIT_RULE);
+    hipError_t e = a.ttabs ? launch_split_m<MODE_BSM_TABLE>(a, nmodels, lpw, st)
+                 : a.btabs ? launch_split_m<MODE_BSM_BINNED>(a, nmodels, lpw, st)
+                           : launch_split_m<MODE_BSM_GAUSS>(a, nmodels, lpw, st);
     if (e != hipSuccess) return e;
     // the parked rows' exact verdict: row t of model t / rows, as the maximiser's candidates (gf_simplex.hip)
     GfSettleArgs sa = {};
@@ -362,6 +425,9 @@ hipError_t gf_launch_pt_swap(const GfSwapArgs& a, hipStream_t st)
 hipError_t gf_launch_pt_series(const GfSeriesArgs& a, int nchains, hipStream_t st)
 {
     if (a.nstored == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_pt_series, dim3((unsigned)a.nstored, (unsigned)nchains), dim3(GF_BLOCK), 0, st, a);
+    const dim3 grid((unsigned)a.nstored, (unsigned)nchains);
+    if (a.ttabs) hipLaunchKernelGGL(k_pt_series<MODE_BSM_TABLE>, grid, dim3(GF_BLOCK), 0, st, a);
+    else if (a.btabs) hipLaunchKernelGGL(k_pt_series<MODE_BSM_BINNED>, grid, dim3(GF_BLOCK), 0, st, a);
+    else hipLaunchKernelGGL(k_pt_series<MODE_BSM_GAUSS>, grid, dim3(GF_BLOCK), 0, st, a);
     return hipGetLastError();
 }

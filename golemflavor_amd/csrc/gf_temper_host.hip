@@ -25,13 +25,21 @@ struct GfTempered {
 };
 
 namespace {
-// the flux-averaged BSM likelihood only: what gf_model_lnprior_lnl and gf_sampler_create_tempered say to any other model
-int model_refusal(gf_model* m, const char* who, int index)
+// a BSM model: what every entry point here says to any other mode
+int mode_refusal(gf_model* m, const char* who, int index)
 {
     const GfCommon* c; const GfBsm* tb; const double* ptab; int device, cus, nbins;
     if (!m || gf_model_constants(m, &c, &tb, &ptab, &device, &cus, &nbins) != GF_OK) return GF_ERR_INVALID_ARG;
     if (c->mode != GF_MODE_BSM_GAUSS)
         return gf_fail_msg(GF_ERR_UNSUPPORTED, "%s: model %d has mode %d; lnprior and lnL are taken apart for the flux-averaged BSM likelihood only", who, index, c->mode);
+    return GF_OK;
+}
+
+// the flux-averaged BSM likelihood only: what gf_sampler_create_tempered says to any other model (the energy-resolved and the tabulated
+// likelihood have entry points of their own, as the untempered sampler's)
+int model_refusal(gf_model* m, const char* who, int index)
+{
+    if (const int rc = mode_refusal(m, who, index)) return rc;
     if (gf_model_table(m, nullptr) > 0)
         return gf_fail_msg(GF_ERR_UNSUPPORTED, "%s: model %d carries a tabulated likelihood; the flux-averaged BSM likelihood only", who, index);
     if (gf_model_binned(m, nullptr))
@@ -50,6 +58,7 @@ hipError_t tempered_split(gf_sampler* s, double* T)
     a.pq = tp->d_pq; a.pend_rows = tp->d_pend_rows;
     a.rows = s->nwalkers; a.ndim = s->ndim; a.nbins_max = s->set.nbins_max;
     a.betas = tp->d_betas; a.T = T;
+    a.btabs = s->set.d_btabs; a.ttabs = s->set.d_ttabs; a.tsides = s->set.d_tsides;       // the instance of the sampler's kind
     return gf_launch_lnprior_lnl(a, s->nchains, tp->d_pend_ctl, s->d_state, s->set.cus, s->set.stream);
 }
 
@@ -72,6 +81,9 @@ int gf_temper_start(gf_sampler* s)
 {
     // every chain's walkers in one split evaluation, T at the chain's beta, then k_fix_start as for every BSM sampler
     hipStream_t st = s->set.stream;
+    // a table sampler: the models' tables of now, as at the start of a run (the upload of the positions is all the stream holds)
+    GF_HIP(hipStreamSynchronize(st));
+    if (const int rc = gf_modelset_refresh_tables(&s->set, "gf_sampler_set_state")) return rc;
     hipError_t e = tempered_split(s, s->d_lnp);
     if (e == hipSuccess) e = gf_launch_fix_start(s->tp->d_status, (int64_t)s->nchains * s->nwalkers, s->d_lnp, s->d_flags, st);
     const hipError_t e2 = hipStreamSynchronize(st);
@@ -120,14 +132,13 @@ void gf_temper_free(GfTempered* tp)
     delete tp;
 }
 
-extern "C" {
-
+namespace {
 // A tempered sampler (the header has the contract).  The model set holds group g's model once per rung, so the sampler is
-// a multi-model one whose chain g * ntemps + t also has a beta.
-int gf_sampler_create_tempered(gf_model* const* models, int nmodels, int ngroups, int ntemps, const double* betas, int nwalkers, uint64_t seed,
-                               double a, int swap_every, gf_sampler** out)
+// a multi-model one whose chain g * ntemps + t also has a beta.  want: the likelihood every model carries, as sampler_create's -- the
+// flux-averaged entry point words its own refusal of the other two, the entry points of those leave it to sampler_create.
+int create_tempered(const char* who, int want, gf_model* const* models, int nmodels, int ngroups, int ntemps, const double* betas, int nwalkers,
+                    uint64_t seed, double a, int swap_every, gf_sampler** out)
 {
-    const char* who = "gf_sampler_create_tempered";
     if (!models || !betas || !out) return GF_ERR_INVALID_ARG;
     *out = nullptr;
     gf_internal_set_error("");
@@ -142,14 +153,19 @@ int gf_sampler_create_tempered(gf_model* const* models, int nmodels, int ngroups
     if (!(betas[ntemps - 1] >= 0.0)) return gf_fail_msg(GF_ERR_INVALID_ARG, "%s: the last rung's beta is %g; it is >= 0", who, betas[ntemps - 1]);
     for (int g = 0; g < nmodels; ++g) {
         if (!models[g]) return GF_ERR_INVALID_ARG;
-        if (const int rc = model_refusal(models[g], who, g)) return rc;
+        if (const int rc = want == GF_LLH_FLUX ? model_refusal(models[g], who, g) : mode_refusal(models[g], who, g)) return rc;
+        // gf_sampler_create_binned's / _table's refusal, naming the group's model (the model set numbers the chains')
+        if (want != GF_LLH_FLUX) {
+            const int has = gf_model_table(models[g], nullptr) > 0 ? GF_LLH_TABLE : gf_model_binned(models[g], nullptr) ? GF_LLH_BINNED : GF_LLH_FLUX;
+            if (const int rc = sampler_likelihood_refusal(want, has, g)) return rc;
+        }
     }
     const int nchains = ngroups * ntemps;
     std::vector<gf_model*> per_chain((size_t)nchains);
     std::vector<double> chain_beta((size_t)nchains);
     for (int ch = 0; ch < nchains; ++ch) { per_chain[ch] = models[nmodels == 1 ? 0 : ch / ntemps]; chain_beta[ch] = betas[ch % ntemps]; }
     gf_sampler* s = nullptr;
-    int rc = sampler_create(per_chain.data(), true, nchains, nwalkers, seed, a, &s);
+    int rc = sampler_create(per_chain.data(), true, nchains, nwalkers, seed, a, &s, want);
     if (rc != GF_OK) return rc;
     GfTempered* tp = new (std::nothrow) GfTempered();
     if (!tp) { gf_sampler_destroy(s); return GF_ERR_ALLOC; }
@@ -170,6 +186,30 @@ int gf_sampler_create_tempered(gf_model* const* models, int nmodels, int ngroups
     if (e != hipSuccess) { gf_sampler_destroy(s); return gf_hip_fail(e, who); }
     *out = s;
     return GF_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int gf_sampler_create_tempered(gf_model* const* models, int nmodels, int ngroups, int ntemps, const double* betas, int nwalkers, uint64_t seed,
+                               double a, int swap_every, gf_sampler** out)
+{
+    return create_tempered("gf_sampler_create_tempered", GF_LLH_FLUX, models, nmodels, ngroups, ntemps, betas, nwalkers, seed, a, swap_every, out);
+}
+
+// the tempered sampler of the energy-resolved likelihood: every model carries a binned measurement, as gf_sampler_create_binned's
+int gf_sampler_create_tempered_binned(gf_model* const* models, int nmodels, int ngroups, int ntemps, const double* betas, int nwalkers,
+                                      uint64_t seed, double a, int swap_every, gf_sampler** out)
+{
+    return create_tempered("gf_sampler_create_tempered_binned", GF_LLH_BINNED, models, nmodels, ngroups, ntemps, betas, nwalkers, seed, a, swap_every, out);
+}
+
+// the tempered sampler of the tabulated flavour-plane likelihood: every model carries a table, as gf_sampler_create_table's;
+// the set's tables are taken again at the start of every run, every gf_sampler_set_state and every gf_sampler_tempered_series
+int gf_sampler_create_tempered_table(gf_model* const* models, int nmodels, int ngroups, int ntemps, const double* betas, int nwalkers,
+                                     uint64_t seed, double a, int swap_every, gf_sampler** out)
+{
+    return create_tempered("gf_sampler_create_tempered_table", GF_LLH_TABLE, models, nmodels, ngroups, ntemps, betas, nwalkers, seed, a, swap_every, out);
 }
 
 int gf_sampler_betas(const gf_sampler* s, int* ngroups, int* ntemps, double* betas, int* swap_every)
@@ -211,6 +251,7 @@ int gf_sampler_tempered_series(gf_sampler* s, const double* d_up, const double* 
     hipStream_t st = s->set.stream;
     GF_HIP(hipStreamSynchronize(st));
     if (s->nstored == 0) return GF_OK;
+    if (const int rc = gf_modelset_refresh_tables(&s->set, "gf_sampler_tempered_series")) return rc;      // a table sampler: the models' tables of now
     const size_t nch = (size_t)s->nchains, ns = (size_t)s->nstored;
     GfScratch sc(GF_MEM_CACHED);
     double *dd_up = nullptr, *dd_dn = nullptr, *d_out = nullptr, *d_lnl = d_lnl_chain;
@@ -224,6 +265,7 @@ int gf_sampler_tempered_series(gf_sampler* s, const double* d_up, const double* 
     a.commons = s->set.d_commons; a.tbs = s->set.d_tbs; a.ptabs = s->set.d_ptabs;
     a.chain = s->d_chain; a.lnp_chain = s->d_lnp_chain; a.cap = s->nstore_cap; a.nstored = s->nstored;
     a.nwalkers = s->nwalkers; a.ndim = s->ndim; a.d_up = dd_up; a.d_dn = dd_dn; a.lnl = d_lnl; a.out = d_out;
+    a.btabs = s->set.d_btabs; a.ttabs = s->set.d_ttabs; a.tsides = s->set.d_tsides;
     hipError_t e = gf_launch_pt_series(a, s->nchains, st);
     if (e == hipSuccess) e = hipMemcpyAsync(series, d_out, sizeof(double) * nch * ns * gftp::SERIES, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && lnl_chain) e = hipMemcpyAsync(lnl_chain, d_lnl, sizeof(double) * nch * ns * (size_t)s->nwalkers, hipMemcpyDeviceToHost, st);
@@ -238,7 +280,7 @@ int gf_model_lnprior_lnl_device(gf_model* m, const double* d_theta, int64_t n, d
 {
     if (!m || n < 0 || (n > 0 && (!d_theta || !d_lp || !d_lnl || !d_status))) return GF_ERR_INVALID_ARG;
     gf_internal_set_error("");
-    if (const int rc = model_refusal(m, "gf_model_lnprior_lnl", 0)) return rc;
+    if (const int rc = mode_refusal(m, "gf_model_lnprior_lnl", 0)) return rc;
     const GfCommon* c; const GfBsm* tb; const double* ptab; void* stream; int device, cus, nbins;
     int rc = gf_model_internal(m, &c, &tb, &ptab, &stream, &device);
     if (rc == GF_OK) rc = gf_model_constants(m, &c, &tb, &ptab, &device, &cus, &nbins);
@@ -247,9 +289,17 @@ int gf_model_lnprior_lnl_device(gf_model* m, const double* d_theta, int64_t n, d
     hipStream_t st = (hipStream_t)stream;
     constexpr int64_t PIECE = 1 << 18;                       // rows per launch: bounds the parked rows' buffers
     const int64_t piece = n < PIECE ? n : PIECE;
+    // the likelihood the model carries now, as gf_lnprob_batch evaluates it: a table, a binned measurement, or neither
+    const double* ltab = nullptr; const double* bmeas = nullptr;
+    const int32_t tside = gf_model_table(m, &ltab);
+    const bool binned = tside <= 0 && gf_model_binned(m, &bmeas);
+    if (binned) ltab = bmeas;
     // one model: the kernels' per-model arrays have one entry each
     GfScratch sc(GF_MEM_CACHED);
     GfCommon* d_common = nullptr; const GfBsm** d_tbs = nullptr; const double** d_ptabs = nullptr; GfStepState* d_state = nullptr;
+    const double** d_ltab = nullptr; int32_t* d_tside = nullptr;
+    (void)sc.take(&d_ltab, sizeof(void*), "gf_model_lnprior_lnl");
+    (void)sc.take(&d_tside, sizeof(int32_t), "gf_model_lnprior_lnl");
     (void)sc.take(&d_common, sizeof(GfCommon), "gf_model_lnprior_lnl");
     (void)sc.take(&d_tbs, sizeof(void*), "gf_model_lnprior_lnl");
     (void)sc.take(&d_ptabs, sizeof(void*), "gf_model_lnprior_lnl");
@@ -259,12 +309,16 @@ int gf_model_lnprior_lnl_device(gf_model* m, const double* d_theta, int64_t n, d
     if (e == hipSuccess) e = hipMemcpyAsync(d_common, c, sizeof(GfCommon), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync((void*)d_tbs, &tb, sizeof(void*), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync((void*)d_ptabs, &ptab, sizeof(void*), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync((void*)d_ltab, &ltab, sizeof(void*), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_tside, &tside, sizeof(int32_t), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemsetAsync(d_state, 0, sizeof(GfStepState), st);
     for (int64_t w0 = 0; w0 < n && e == hipSuccess; w0 += piece) {
         GfSplitArgs a = {};
         a.commons = d_common; a.tbs = d_tbs; a.ptabs = d_ptabs;
         a.theta = d_theta + w0 * c->ndim; a.lp = d_lp + w0; a.lnl = d_lnl + w0; a.status = d_status + w0;
         a.pq = pq; a.pend_rows = pend; a.rows = (int32_t)(n - w0 < piece ? n - w0 : piece); a.ndim = c->ndim; a.nbins_max = nbins;
+        if (tside > 0) { a.ttabs = d_ltab; a.tsides = d_tside; }
+        else if (binned) a.btabs = d_ltab;
         e = gf_launch_lnprior_lnl(a, 1, ctl, d_state, cus, st);
     }
     const hipError_t e2 = hipStreamSynchronize(st);
@@ -279,7 +333,7 @@ int gf_model_lnprior_lnl(gf_model* m, const double* theta, int64_t n, double* lp
 {
     if (!m || n < 0 || (n > 0 && (!theta || !lp || !lnl || !status))) return GF_ERR_INVALID_ARG;
     gf_internal_set_error("");
-    if (const int rc = model_refusal(m, "gf_model_lnprior_lnl", 0)) return rc;
+    if (const int rc = mode_refusal(m, "gf_model_lnprior_lnl", 0)) return rc;
     if (n == 0) return GF_OK;
     const GfCommon* c; const GfBsm* tb; const double* ptab; void* stream; int device;
     const int rc = gf_model_internal(m, &c, &tb, &ptab, &stream, &device);

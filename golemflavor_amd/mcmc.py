@@ -212,7 +212,9 @@ class DeviceEnsembleSampler(rowsets.RowSetSource):
 
     betas=[1, ..., beta_min or 0] (`gf_sampler_create_tempered`): a tempered sampler of `ngroups` groups of len(betas)
     chains; chain g * ntemps + t samples prior * L^betas[t] of group g's posterior (`lnpostfn`: one for all groups, or a list of one per
-    group -- the scales of a scan).  Flux-averaged BSM posteriors only.  `lnprobability` and the state's lnprob are the walker's scalar
+    group -- the scales of a scan).  BSM posteriors; with energy_resolved=True / tabulated=True the chains sample that likelihood
+    (`gf_sampler_create_tempered_binned` / `_table`) under the keyword's own conditions, else the flux-averaged one; a hole of a
+    table (lnl = -inf) is a legal sample of a beta = 0 chain.  `lnprobability` and the state's lnprob are the walker's scalar
     T = lp + beta lnl (at beta = 1: `Model.lnprob`); `lnlikelihood()` has lnl itself.  swap_every=S > 0: a replica-exchange round
     after every S-th step.  `.betas`, `.cold_chains`, `.swap_fraction`, `.lnl_series()`; `tempering.stepping_stone` turns the series into
     ln(Z_1 / Z_0).  Everything that reads the chain works as for a sampler of nchains = ngroups * ntemps chains.  betas=None: none of this.
@@ -228,8 +230,6 @@ class DeviceEnsembleSampler(rowsets.RowSetSource):
         self.betas = None if betas is None else np.ascontiguousarray(betas, dtype=np.float64).reshape(-1)
         if self.betas is not None:
             # a tempered sampler: ngroups groups of len(betas) chains, one posterior for all groups or one per group
-            if energy_resolved or tabulated:
-                raise ValueError("betas: a tempered sampler evaluates the flux-averaged likelihood only")
             if not models:
                 raise ValueError("empty list of posteriors")
             self.ngroups = int(ngroups if ngroups is not None else (len(models) if multi else 1))
@@ -254,16 +254,25 @@ class DeviceEnsembleSampler(rowsets.RowSetSource):
         self.energy_resolved, self.tabulated = bool(energy_resolved), bool(tabulated)
         if self.energy_resolved and self.tabulated:
             raise ValueError("tabulated=True and energy_resolved=True: a posterior carries a table or a binned measurement, not both")
+        # a tempered sampler names the posteriors as they were given (one per group), and what the one it refuses carries instead
+        given = self._group_models if self.betas is not None else models
+
+        def carries(k, model):
+            if self.betas is None:
+                return ""
+            return ": posterior %d carries %s" % (k, "a tabulated likelihood" if getattr(model, "table_nside", 0) else
+                                                  "a binned measurement" if getattr(model, "binned", None) is not None else
+                                                  "the flux-averaged likelihood only")
         if self.energy_resolved:
-            for k, model in enumerate(models):
+            for k, model in enumerate(given):
                 if getattr(model, "binned", None) is None:
                     raise ValueError("energy_resolved=True, but posterior %d carries no binned measurement "
-                                     "(Model.set_binned_measurement)" % k)
+                                     "(Model.set_binned_measurement)" % k + carries(k, model))
         if self.tabulated:
-            for k, model in enumerate(models):
+            for k, model in enumerate(given):
                 if not getattr(model, "table_nside", 0):
                     raise ValueError("tabulated=True, but posterior %d carries no tabulated likelihood "
-                                     "(Model.set_table_likelihood)" % k)
+                                     "(Model.set_table_likelihood)" % k + carries(k, model))
         model, lnpostfn = models[0], fns[0]
         if nwalkers % 2:
             raise AssertionError("The number of walkers must be even.")
@@ -277,9 +286,10 @@ class DeviceEnsembleSampler(rowsets.RowSetSource):
         h = C.c_void_p()
         if self.betas is not None:
             gm = self._group_models
-            _lib.check(self._L.gf_sampler_create_tempered(rowsets.model_handles(gm, len(gm)), len(gm), self.ngroups, self.ntemps,
-                                                          self.betas.ctypes.data_as(_lib._dp), self.k, int(seed), self.a, self.swap_every,
-                                                          C.byref(h)), "gf_sampler_create_tempered")
+            create = "gf_sampler_create_tempered" + ("_binned" if self.energy_resolved else "_table" if self.tabulated else "")
+            _lib.check(getattr(self._L, create)(rowsets.model_handles(gm, len(gm)), len(gm), self.ngroups, self.ntemps,
+                                                self.betas.ctypes.data_as(_lib._dp), self.k, int(seed), self.a, self.swap_every,
+                                                C.byref(h)), create)
         elif self.energy_resolved:
             nmodels = self.nchains if multi else 1
             _lib.check(self._L.gf_sampler_create_binned(rowsets.model_handles(models, nmodels), nmodels, self.nchains, self.k, int(seed),

@@ -193,7 +193,9 @@ class Model:
     def lnprior_lnlike(self, theta):
         """theta (n, ndim) -> (lp (n,), lnl (n,), status (n,) int32): lnprior and lnL apart (gf_model_lnprior_lnl).  The
         status is `lnprob`'s, and where it is OK `lp + lnl` is `lnprob` bit for bit; outside the box both are -inf, where the reference
-        would have raised lnl is NaN.  A flux-averaged BSM model only: anything else is GolemHipError (GF_ERR_UNSUPPORTED)."""
+        would have raised lnl is NaN.  lnl is the likelihood the model carries, as `lnprob`'s: the flux-averaged Gaussian, the binned
+        measurement's or the table's (-inf in a hole of the table, with status OK).  BSM models only: any other mode is GolemHipError
+        (GF_ERR_UNSUPPORTED)."""
         th = _as_theta(theta, self.ndim)
         n = th.shape[0]
         lp, lnl, st = np.empty(n), np.empty(n), np.empty(n, dtype=np.int32)

@@ -170,13 +170,19 @@ def _opt(args, name, default):
 
 
 def evidence_scan_tempered(args, asimov_paramset, llh_paramset, scales, ntemps=8, beta_min=1e-3, swap_every=8, nwalkers=256, burnin=500,
-                           nsteps=1500, discard=0, nbatch=16, seed=None, on_nonunitary="raise", smearing=None, device=0):
+                           nsteps=1500, discard=0, nbatch=16, seed=None, on_nonunitary="raise", smearing=None, device=0, binned=None,
+                           table=None):
     """ln Z of every scale by stepping-stone, the integral `nested.evidence_scan` does: per scale the model over every column but the
     scale, the scale fixed (`scale_fixed`) -- the scale's own prior is uniform and adds nothing --, the scales as the groups of ONE
     tempered sampler on `geometric_ladder(ntemps, beta_min)`.  Returns dict(scales, ln_z, ln_z_err, ln_ratio, ln_ratio_ti, swap_fraction
     (nscales, ntemps), nonunitary, nonfinite_fraction, betas, seconds, start_ess).  Every chain starts from `ladder_start`'s positions
     (start_ess (nscales, ntemps): the effective number of prior draws behind each).  With on_nonunitary="-inf" the ratio is over the region where the
-    reference does not raise: `nonunitary` counts the proposals it would have died on, and nothing corrects for them."""
+    reference does not raise: `nonunitary` counts the proposals it would have died on, and nothing corrects for them.  binned
+    (`llh.BinnedMeasurement`): the evidence of the energy-resolved likelihood -- the measurement is attached to every
+    scale's model, as `nested.evidence_scan` does, and the sampler is the tempered binned one.  table (`llh.TabulatedLikelihood`):
+    likewise the tabulated flavour-plane likelihood; not together with `binned`."""
+    if binned is not None and table is not None:
+        raise ValueError("binned and table are two likelihoods: give one")
     from . import fr as fr_utils
     from .descriptor import compile_model
     from .llh import LnProb
@@ -196,7 +202,12 @@ def evidence_scan_tempered(args, asimov_paramset, llh_paramset, scales, ntemps=8
             fns.append(LnProb(compile_model(ps, "BSM_GAUSS", bestfit_fr=bf, smearing=smearing, source_ratio=args.source_ratio,
                                             texture=args.texture, dimension=args.dimension, binning=args.binning, scale_fixed=float(sc)),
                               device=device, on_nonunitary=on_nonunitary))
-        s = DeviceEnsembleSampler(int(nwalkers), len(ps), fns, seed=seed, betas=betas, swap_every=int(swap_every), ngroups=len(scales))
+            if binned is not None:
+                fns[-1].model.set_binned_measurement(binned)
+            if table is not None:
+                fns[-1].model.set_table_likelihood(table)
+        s = DeviceEnsembleSampler(int(nwalkers), len(ps), fns, seed=seed, betas=betas, swap_every=int(swap_every), ngroups=len(scales),
+                                  energy_resolved=binned is not None, tabulated=table is not None)
         try:
             rng = np.random.default_rng(seed)
             starts = [ladder_start(f.model, ps, betas, int(nwalkers), rng) for f in fns]

@@ -277,10 +277,12 @@ int gf_sampler_create_binned(gf_model* const* models, int nmodels, int nchains, 
  * to replace; model targets work. */
 int gf_sampler_create_table(gf_model* const* models, int nmodels, int nchains, int nwalkers, uint64_t seed, double a, gf_sampler** out);
 /* ---- tempered chains, replica exchange, stepping-stone series; additive in ABI 5 ----
- * lnprior and lnL of a flux-averaged BSM model apart: theta [n][ndim] -> lp, lnl, status [n].  status is gf_lnprob_batch's of the row,
- * and where it is GF_ST_OK the rounded sum lp + lnl is gf_lnprob_batch's lnprob bit for bit.  Outside the box lp = lnl = -inf; where the
- * reference would have raised lnl is NaN.  _device: device pointers, rows as [n][ndim].  Refused with GF_ERR_UNSUPPORTED and a message:
- * any other mode, a model that carries a binned measurement or a tabulated likelihood. */
+ * lnprior and lnL of a BSM model apart: theta [n][ndim] -> lp, lnl, status [n].  lnl is the likelihood the model carries, as
+ * gf_lnprob_batch evaluates it: the flux-averaged Gaussian, the energy-resolved one of a binned measurement or the
+ * tabulated one (-inf at a hole of the table, with status GF_ST_OK).  status is gf_lnprob_batch's of the row, and where it
+ * is GF_ST_OK the rounded sum lp + lnl is gf_lnprob_batch's lnprob bit for bit.  Outside the box lp = lnl = -inf; where the reference
+ * would have raised lnl is NaN.  _device: device pointers, rows as [n][ndim].  Refused with GF_ERR_UNSUPPORTED and a message: any other
+ * mode. */
 int gf_model_lnprior_lnl(gf_model* m, const double* theta, int64_t n, double* lp, double* lnl, int32_t* status);
 int gf_model_lnprior_lnl_device(gf_model* m, const double* d_theta, int64_t n, double* d_lp, double* d_lnl, int32_t* d_status);
 /* A sampler of ngroups * ntemps chains: chain g * ntemps + t samples prior * L^betas[t] of group g's model (nmodels == 1: models[0] for
@@ -296,6 +298,19 @@ int gf_model_lnprior_lnl_device(gf_model* m, const double* d_theta, int64_t n, d
  * (GF_ERR_UNSUPPORTED), a ladder or nmodels that break the rules above (GF_ERR_INVALID_ARG), each with a message. */
 int gf_sampler_create_tempered(gf_model* const* models, int nmodels, int ngroups, int ntemps, const double* betas, int nwalkers, uint64_t seed,
                                double a, int swap_every, gf_sampler** out);
+/* gf_sampler_create_tempered for the energy-resolved likelihood (_binned: every model carries a binned measurement) and for the tabulated
+ * flavour-plane likelihood (_table: every model carries a table; the sides may differ from group to group): the same parameters, the same
+ * ladder rules, and L is that likelihood in the half-step, the rounds, gf_sampler_set_state and gf_sampler_tempered_series.  A model
+ * that carries another likelihood is refused with gf_sampler_create_binned's / gf_sampler_create_table's code and wording; the call above
+ * goes on refusing both kinds (GF_ERR_UNSUPPORTED).  A hole of a table (lnl = -inf) lies in the box: T = -inf at every beta > 0, T = lp at
+ * beta == 0, where it is a sample of the prior chain.  _binned runs one lane per walker, _table the lanes of gf_sampler_create_table's rule.
+ * _table takes each model's table again at the start of every gf_sampler_run, gf_sampler_set_state and gf_sampler_tempered_series, as
+ * gf_sampler_create_table does per run; a model whose kind of likelihood changes under the live sampler is refused by all three
+ * (GF_ERR_INVALID_ARG), the chain left as it is.  Additive in ABI 5. */
+int gf_sampler_create_tempered_binned(gf_model* const* models, int nmodels, int ngroups, int ntemps, const double* betas, int nwalkers, uint64_t seed,
+                                      double a, int swap_every, gf_sampler** out);
+int gf_sampler_create_tempered_table(gf_model* const* models, int nmodels, int ngroups, int ntemps, const double* betas, int nwalkers, uint64_t seed,
+                                     double a, int swap_every, gf_sampler** out);
 /* lnl of every stored sample of a tempered sampler, reduced on the device over the walkers of a step: series [nchains][nstored][5] =
  * {walkers with a finite lnl, their sum, their max m, S_up = sum_w exp(d_up (lnl_w - m)), S_dn likewise with d_dn}, d_up and d_dn
  * [nchains] >= 0; a walker without a finite lnl contributes 0; the sums follow one fixed tree and the exp is the library's own

@@ -6,8 +6,13 @@
    around synchronous stored runs of --steps steps after a warm-up run; the --reps runs and their median.  Nothing is gated.
 2. ln Z of --scales scales by `tempering.evidence_scan_tempered` beside `nested.evidence_scan`, both error bars (--compare).
 
+--likelihood binned | table: both under the energy-resolved likelihood (a measurement per energy bin at the equal-information widths of
+--smearing, around the injected composition) or the tabulated one (the Gaussian of --smearing tabulated at side 64) instead of the
+flux-averaged Gaussian; every line names the likelihood.
+
     python tools/bench_tempering.py [--groups 5] [--temperatures 8] [--beta-min 1e-3] [--nwalkers 256] [--steps 200] [--reps 5]
                                     [--smearing 0.1] [--untempered-only] [--compare] [--scales 5] [--out FILE.jsonl]
+                                    [--likelihood flux|binned|table]
 
 One JSON line per measurement; with --out they are appended to the file as well."""
 import argparse
@@ -41,6 +46,19 @@ def sens_args(a):
                               smearing=a.smearing, seed=25)
 
 
+def likelihood(a):
+    """(the sampler's keywords, evidence_scan's keywords) of --likelihood"""
+    asimov, _ = Cf.sens_paramsets(6, (1., 1., 1.))
+    bf = fr_utils.angles_to_fr(asimov.from_tag(ParamTag.BESTFIT, values=True))
+    if a.likelihood == "binned":
+        edges = Cf.default_bin_edges()
+        return dict(energy_resolved=True), dict(binned=llh.BinnedMeasurement(np.tile(np.asarray(bf, dtype=float), (len(edges) - 1, 1)), a.smearing,
+                                                                             binning=edges))
+    if a.likelihood == "table":
+        return dict(tabulated=True), dict(table=llh.TabulatedLikelihood.from_gaussian(bf, a.smearing, 64))
+    return {}, {}
+
+
 def scale_posteriors(a, scales):
     """one 11-column posterior per scale (the scale fixed), as evidence_scan_tempered builds them"""
     asimov, llh_ps = Cf.sens_paramsets(6, (1., 1., 1.))
@@ -49,6 +67,12 @@ def scale_posteriors(a, scales):
     args = sens_args(a)
     fns = [llh.LnProb(compile_model(ps, "BSM_GAUSS", bestfit_fr=bf, smearing=a.smearing, source_ratio=args.source_ratio, texture=args.texture,
                                     dimension=6, binning=args.binning, scale_fixed=float(sc)), on_nonunitary="-inf") for sc in scales]
+    scan_kw = likelihood(a)[1]
+    for f in fns:
+        if "binned" in scan_kw:
+            f.model.set_binned_measurement(scan_kw["binned"])
+        if "table" in scan_kw:
+            f.model.set_table_likelihood(scan_kw["table"])
     return fns, ps
 
 
@@ -78,7 +102,9 @@ def main(argv=None):
     ap.add_argument("--compare", action="store_true")
     ap.add_argument("--scales", type=int, default=5)
     ap.add_argument("--out", type=str, default=None)
+    ap.add_argument("--likelihood", choices=["flux", "binned", "table"], default="flux")
     a = ap.parse_args(argv)
+    smp_kw, scan_kw = likelihood(a)
     b = Cf.SCALE_BOUNDARIES[6]
     scales = np.linspace(b[0], b[1], a.groups)
     fns, ps = scale_posteriors(a, scales)
@@ -91,9 +117,9 @@ def main(argv=None):
             rng = np.random.default_rng(1)
             p0 = tempering.prior_draws(ps, nchains * a.nwalkers, rng).reshape(nchains, a.nwalkers, ndim)
             for swap_every in (0, 8):
-                smp = mcmc_utils.DeviceEnsembleSampler(a.nwalkers, ndim, fns, seed=25, betas=betas, swap_every=swap_every, ngroups=a.groups)
+                smp = mcmc_utils.DeviceEnsembleSampler(a.nwalkers, ndim, fns, seed=25, betas=betas, swap_every=swap_every, ngroups=a.groups, **smp_kw)
                 us = timed(smp, p0, a)
-                emit({"what": "tempered", "chains": nchains, "groups": a.groups, "rungs": len(betas), "nwalkers": a.nwalkers, "swap_every": swap_every,
+                emit({"what": "tempered", "likelihood": a.likelihood, "chains": nchains, "groups": a.groups, "rungs": len(betas), "nwalkers": a.nwalkers, "swap_every": swap_every,
                       "steps": a.steps, "us_per_step": [round(u, 2) for u in us], "median_us_per_step": round(float(np.median(us)), 2),
                       "lanes_per_walker": smp.launch_shape()["lanes_per_walker"],
                       "swap_fraction_min": None if not swap_every else round(float(np.nanmin(smp.swap_fraction)), 3)}, a.out)
@@ -105,9 +131,9 @@ def main(argv=None):
         old = os.environ.get("GF_SAMPLER_CHAIN")
         os.environ["GF_SAMPLER_CHAIN"] = "0"
         try:
-            smp = mcmc_utils.DeviceEnsembleSampler(a.nwalkers, ndim, [fns[ch % a.groups] for ch in range(nchains)], seed=25)
+            smp = mcmc_utils.DeviceEnsembleSampler(a.nwalkers, ndim, [fns[ch % a.groups] for ch in range(nchains)], seed=25, **smp_kw)
             us = timed(smp, p0, a)
-            emit({"what": "untempered multi-model sampler, grid shape", "chains": nchains, "nwalkers": a.nwalkers, "steps": a.steps,
+            emit({"what": "untempered multi-model sampler, grid shape", "likelihood": a.likelihood, "chains": nchains, "nwalkers": a.nwalkers, "steps": a.steps,
                   "us_per_step": [round(u, 2) for u in us], "median_us_per_step": round(float(np.median(us)), 2),
                   "lanes_per_walker": smp.launch_shape()["lanes_per_walker"]}, a.out)
             smp.close()
@@ -124,9 +150,9 @@ def main(argv=None):
         args = sens_args(a)
         sc = np.linspace(b[0], b[1], a.scales)
         ss = tempering.evidence_scan_tempered(args, asimov, llh_ps, sc, ntemps=a.temperatures, beta_min=a.beta_min, nwalkers=a.nwalkers,
-                                              on_nonunitary="-inf", smearing=a.smearing, seed=25)
-        ns = nested.evidence_scan(args, asimov, llh_ps, sc, on_nonunitary="-inf", smearing=a.smearing, seed=25)
-        emit({"what": "ln Z per scale, stepping-stone beside the nested sampler", "smearing": a.smearing, "scales": sc.tolist(),
+                                              on_nonunitary="-inf", smearing=a.smearing, seed=25, **scan_kw)
+        ns = nested.evidence_scan(args, asimov, llh_ps, sc, on_nonunitary="-inf", smearing=a.smearing, seed=25, **scan_kw)
+        emit({"what": "ln Z per scale, stepping-stone beside the nested sampler", "likelihood": a.likelihood, "smearing": a.smearing, "scales": sc.tolist(),
               "ln_z_stepping_stone": ss["ln_z"].tolist(), "ln_z_err_stepping_stone": ss["ln_z_err"].tolist(),
               "lnz_nested": ns["lnz"].tolist(), "lnz_err_nested": ns["lnz_err"].tolist(),
               "difference": (ss["ln_z"] - ns["lnz"]).tolist(),
